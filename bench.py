@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the ST-GCN stem forward, tcn0(gcn0(x)), on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            # N=1
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]     # N=1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # N>1, launched by the driver
 
@@ -21,10 +21,12 @@ same process and reported beside it (`other_scaling`), so both scaling kinds are
   --weak                 force the weak-scaling workload at N > 1 (256 clips on every rank);
   --global-clips G       force the strong-scaling workload with G clips (also at N = 1: 8192 = configs[4]'s base point).
 
-Rank 0 prints ONE JSON line.  Besides the contract's fields:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps, writes --dump-outputs and prints
+the line; the other blocks below run only with --full.  Besides the contract's fields:
   roofline      the dominant kernel, HIP-event timed on the launching stream over the timed region;
                 `traffic` (HBM bytes per launch from the committed rocprofv3 PMC summary) is quoted only when
                 the kernels' sources are byte-identical to the ones that profile was taken on (`traffic_source`);
+--full adds:
   steady_state  a second, longer timed block in the same process (the driver's 20 steps run while the
                 clocks still ramp after idle; this block shows where the figure settles);
   alt           a short block with the exact-fp32 arithmetic (STGCN_MATH_F32) and its own roofline;
@@ -33,6 +35,11 @@ Rank 0 prints ONE JSON line.  Besides the contract's fields:
                 reference itself runs), rank 0 at N=1 only; `cpu_oracle` = the einsum oracle timed the same way.
 Order inside the process: headline block, steady-state block, fp32 block, training block, CPU legs (the GPU is never left
 idle behind a CPU leg before a GPU measurement).
+
+--dump-outputs DIR writes the stem output of the headline block's last timed step as DIR/stem_out.npy (float32; at N>1
+stem_out_rank<r>.npy, this rank's shard): every value in logical (N,C,T,V) order when the output holds at most
+DUMP_VALUES / N of them, otherwise the values at that many flat positions drawn with a fixed seed (sorted).  Inputs and
+weights are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import hashlib
@@ -53,6 +60,7 @@ import torch         # noqa: E402
 
 HBM_PEAK = 8.0e12                       # B/s, MI355X spec (MI355X_MICROARCH.md); measured copy ~6.29e12
 MFMA_PEAK = {"f32": 157.3e12, "f32_valu": 157.3e12, "bf16": 2.5e15, "bf16x3": 2.5e15, "f16mx": 2.5e15}   # dense FLOP/s (16-bit rate)
+DUMP_VALUES = 1 << 23                   # float32 values written by --dump-outputs over all ranks: 32 MB
 DTYPE_NAME = {"f32": "f32", "f32_valu": "f32", "bf16": "bf16",
               "bf16x3": "bf16x3 (fp32 operands split hi+lo bf16, 3 MFMAs, fp32 accumulate)",
               "f16mx": "f16mx (fp32 operands as fp16 + two e4m3 residual products on the scaled MFMA, fp32 accumulate)"}
@@ -125,6 +133,26 @@ def cpu_legs(gcn_state, tcn_state, A, T, V, clips, reps):
     return base, orc
 
 
+def dump_outputs(outs, directory, name, budget):
+    """Write the sub-batch outputs `outs` (laid end to end, logical (N,C,T,V) order) to directory/name.npy: all of them
+    when they hold at most `budget` values, else the values at `budget` seeded flat positions."""
+    sizes = [o.numel() for o in outs]
+    total = sum(sizes)
+    if total <= budget:
+        vals = torch.cat([o.reshape(-1).cpu() for o in outs])
+    else:
+        idx = torch.randint(total, (budget,), generator=torch.Generator().manual_seed(2024)).sort().values
+        parts, lo = [], 0
+        for o, n in zip(outs, sizes):
+            sel = idx[(idx >= lo) & (idx < lo + n)] - lo
+            if sel.numel():
+                parts.append(o.reshape(-1)[sel.to(o.device)].cpu())
+            lo += n
+        vals = torch.cat(parts)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), vals.numpy().astype(np.float32))
+
+
 def csrc_digest():
     """Content hash of every kernel source + the ABI header: identifies the binary a profile belongs to (the GPU box
     has no .git).  tools/summarize_profiles.py stores the same digest next to the counters it condenses."""
@@ -189,11 +217,16 @@ def main():
                     help="timed steps of the secondary training block: forward + backward of the stem in .train() (0 = skip)")
     ap.add_argument("--deeper-steps", type=int, default=20,
                     help="timed steps of the tertiary block: training step of the two deeper TCN_GCN_unit shapes (0 = skip; 1 GPU only)")
-    ap.add_argument("--no-extras", action="store_true", help="headline block only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline block, also run the secondary blocks (steady state, other scaling kind, fp32, "
+                         "training, deeper layers) and the CPU baselines; off: headline block only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the stem output of the last timed step to DIR/*.npy (float32; seeded sample when large)")
+    ap.add_argument("--no-extras", action="store_true", help="headline block only, also with --full (profiling runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-clips", type=int, default=64)
     args = ap.parse_args()
-    if args.no_extras:
+    if args.no_extras or not args.full:
         args.steady_steps = args.alt_steps = args.train_steps = args.other_steps = args.deeper_steps = 0
         args.no_cpu_baseline = True
 
@@ -254,15 +287,19 @@ def main():
     stats, pending = None, None
     current = wl
 
+    keep_all = args.dump_outputs is not None                     # hold every sub-batch's output of a step, not only the last
+
     def step():
         nonlocal stats, pending
-        out = None
+        out, outs = None, []
         with torch.no_grad():
             for xs in current["shard"]:
                 out = tcn(gcn(xs))
+                if keep_all:
+                    outs.append(out)
         if world > 1:   # tiny, latency-bound; RCCL over xGMI on its own stream, beside the next step's kernels
             stats, pending = sd.all_reduce_stats_async(sd.step_stats(out, current["n_local"]))
-        return out
+        return outs if keep_all else [out]
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -270,7 +307,8 @@ def main():
         torch.cuda.synchronize(dev)
 
     def timed_block(steps, warm):
-        """`warm` untimed steps, then exactly `steps` steps between two fences; (seconds max over ranks, kernel ms)."""
+        """`warm` untimed steps, then exactly `steps` steps between two fences; (seconds max over ranks, kernel ms,
+        launches timed, the last step's outputs)."""
         out = None
         for _ in range(warm):
             out = step()
@@ -285,12 +323,15 @@ def main():
         F.kernel_timer = None
         return sd.max_over_ranks(dt, dev), timer.mean_ms("stem_tail"), timer.count("stem_tail"), out
 
-    elapsed, kern_ms, n_launch, out = timed_block(args.steps, args.warmup)
-    assert torch.isfinite(out).all()
+    elapsed, kern_ms, n_launch, outs = timed_block(args.steps, args.warmup)
+    assert all(torch.isfinite(o).all() for o in outs)
     if pending is not None:
         pending.wait()
     if stats is not None:
         assert int(round(stats[0].item())) == n_global, "all-reduced clip count disagrees with the sharding"
+    if args.dump_outputs is not None:
+        dump_outputs(outs, args.dump_outputs, "stem_out" if world == 1 else f"stem_out_rank{rank}", DUMP_VALUES // world)
+    del outs
 
     bytes_clip = 4 * T * V * (3 + 128)                       # fused stem: x in + activation out
     flops_clip = 2 * 128 * 128 * 9 * T * V + 2 * T * V * (3 * 3 * V + 128 * 13)   # temporal conv + graph conv
@@ -371,7 +412,7 @@ def main():
         ow = make_workload(not strong, 8192)
         current = ow
         eo, ko, no_, outo = timed_block(args.other_steps, 3)
-        assert torch.isfinite(outo).all()
+        assert all(torch.isfinite(o).all() for o in outo)
         if pending is not None:
             pending.wait()
         if stats is not None:
@@ -392,7 +433,7 @@ def main():
     if args.alt_steps > 0 and args.math != "f32":
         stgcn_amd.set_math_mode(tcn, "f32")
         e3, k3, n3, out3 = timed_block(args.alt_steps, 5)
-        assert torch.isfinite(out3).all()
+        assert all(torch.isfinite(o).all() for o in out3)
         stgcn_amd.set_math_mode(tcn, args.math)
         if rank == 0:
             v3 = n_global * args.alt_steps / e3

@@ -8,7 +8,7 @@ STGCN_LIB=$B timeout -k 10 300 python -m pytest tests -m gpu -q -x -k "stem_vs_g
 for r in 1 2 3; do
   for which in A B; do
     if [ $which = B ]; then export STGCN_LIB=$B; else unset STGCN_LIB; fi
-    timeout -k 10 200 python bench.py --steps 20 --warmup 5 --steady-steps 400 --alt-steps 0 --train-steps 0 --other-steps 0 --no-cpu-baseline "$@" > $O/ab_${V}_$which$r.log 2>&1 || { tail -5 $O/ab_${V}_$which$r.log; exit 1; }
+    timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --steady-steps 400 --alt-steps 0 --train-steps 0 --other-steps 0 --no-cpu-baseline "$@" > $O/ab_${V}_$which$r.log 2>&1 || { tail -5 $O/ab_${V}_$which$r.log; exit 1; }
     python - <<PY
 import json
 d=json.loads([l for l in open("$O/ab_${V}_$which$r.log") if l.startswith("{")][-1])

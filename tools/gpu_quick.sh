@@ -12,7 +12,7 @@ rc=$?; tail -4 $O/${TAG}_pytest.log
 if [ $rc -ne 0 ]; then grep -n "Error\|error\|assert" $O/${TAG}_pytest.log | head -20; exit $rc; fi
 timeout -k 10 200 python tools/time_k1.py > $O/${TAG}_k1.log 2>&1 || { tail -5 $O/${TAG}_k1.log; exit 1; }
 cat $O/${TAG}_k1.log
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --alt-steps 0 --no-cpu-baseline > $O/${TAG}_bench.log 2>&1 || { tail -5 $O/${TAG}_bench.log; exit 1; }
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --alt-steps 0 --no-cpu-baseline > $O/${TAG}_bench.log 2>&1 || { tail -5 $O/${TAG}_bench.log; exit 1; }
 python - <<PY
 import json
 d=json.loads([l for l in open("$O/${TAG}_bench.log") if l.startswith("{")][-1])

@@ -16,8 +16,8 @@ step() {   # step <seconds> <log> <cmd...>
 }
 step 900 $O/${TAG}_pytest.log python -m pytest tests -m gpu -q -x --durations=15
 tail -5 $O/${TAG}_pytest.log
-step 300 $O/${TAG}_bench_default.log python bench.py --steps 20 --warmup 5 && tail -1 $O/${TAG}_bench_default.log | cut -c1-1500
-step 300 $O/${TAG}_bench_strong1.log python bench.py --global-clips 8192 --steps 5 --warmup 2 --steady-steps 20 --alt-steps 0 --no-cpu-baseline && tail -1 $O/${TAG}_bench_strong1.log | cut -c1-600
-STGCN_DIST_BACKEND=gloo step 300 $O/${TAG}_bench_strong2_gloo.log python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --global-clips 8192 --steps 5 --warmup 2 --steady-steps 20 --alt-steps 0 && tail -1 $O/${TAG}_bench_strong2_gloo.log | cut -c1-600
-step 300 $O/${TAG}_bench_nofuse.log python bench.py --no-fuse --steps 50 --warmup 10 --steady-steps 0 --alt-steps 0 --no-cpu-baseline && tail -1 $O/${TAG}_bench_nofuse.log | cut -c1-400
+step 300 $O/${TAG}_bench_default.log python bench.py --full --steps 20 --warmup 5 && tail -1 $O/${TAG}_bench_default.log | cut -c1-1500
+step 300 $O/${TAG}_bench_strong1.log python bench.py --full --global-clips 8192 --steps 5 --warmup 2 --steady-steps 20 --alt-steps 0 --no-cpu-baseline && tail -1 $O/${TAG}_bench_strong1.log | cut -c1-600
+STGCN_DIST_BACKEND=gloo step 300 $O/${TAG}_bench_strong2_gloo.log python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --global-clips 8192 --steps 5 --warmup 2 --steady-steps 20 --alt-steps 0 && tail -1 $O/${TAG}_bench_strong2_gloo.log | cut -c1-600
+step 300 $O/${TAG}_bench_nofuse.log python bench.py --full --no-fuse --steps 50 --warmup 10 --steady-steps 0 --alt-steps 0 --no-cpu-baseline && tail -1 $O/${TAG}_bench_nofuse.log | cut -c1-400
 exit 0
