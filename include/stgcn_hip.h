@@ -152,14 +152,14 @@ int stgcn_stem_prepare(const float *Wd, const float *bd, const float *Wdown, con
                        const float *down_shift, const float *Wt, const float *t_scale, void *prep,
                        int Cin, int C, int K, int subsets, unsigned flags, void *stream);
 /* Workspace of the fused stem (caller-provided, stgcn_stem_ws_bytes bytes): the attention matrices
- * P (N,S,V,V) at offset 0 (valid on return) followed by per-pixel graph-conv features for the kernels
- * that consume them, or (STGCN_IN_NTVC on the other kernels) a channel-major copy of x. */
+ * P (N,S,V,V) at offset 0 (valid on return), then whatever the chosen kernel reads besides them. */
 size_t stgcn_stem_ws_bytes(int N, int Cin, int C, int T, int V, int K, int subsets, unsigned flags);
-/* Name of the kernel stgcn_stem_tail_prepared launches for the shape ("stem_bf16_v6_kernel", "stem_bf16_v4_kernel",
- * "stem_mfma_bf16_kernel", "stem_mfma_f32_kernel"; "" when no fused kernel covers it) — for profilers and benchmarks
- * that match kernel names in rocprofv3 output. */
+/* Name of the kernel stgcn_stem_tail_prepared launches for the shape ("stem_f16mx_kernel", "stem_bf16_v6_kernel",
+ * "stem_bf16_v4_kernel", "stem_mfma_bf16_kernel", "stem_mfma_f32_kernel"; "" when no fused kernel covers it) — for
+ * profilers and benchmarks that match kernel names in rocprofv3 output. */
 const char *stgcn_stem_kernel_name(int Cin, int C, int T, int V, int K, int subsets, unsigned flags);
-/* 1 when the large-tile persistent kernel (which reads the feature part of the workspace) serves the shape */
+/* 1 when one of the large-tile kernels serves the shape (stem_bf16_v4/_v6/_f16mx_kernel): the workspace then holds,
+ * behind P, graph-conv features or attention fragments that stgcn_stem_attention writes for the kernel */
 int stgcn_stem_features_used(int Cin, int C, int T, int V, int K, int subsets, unsigned flags);
 /* The two halves of stgcn_stem_forward_prepared, separately launchable (e.g. to time them):
  * stgcn_stem_attention fills the workspace; stgcn_stem_tail_prepared launches only the fused

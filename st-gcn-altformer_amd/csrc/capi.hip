@@ -175,7 +175,7 @@ int stgcn_tcn_supported(int Cin, int Cout, int T, int V, int K, int stride, unsi
 
 int stgcn_stem_supported(int Cin, int C, int T, int V, int K, int subsets, unsigned flags) {
     if (Cin <= 0 || C <= 0 || T <= 0 || V <= 0 || K <= 0 || subsets <= 0) return 0;
-    return stem_fused_supported(Cin, C, T, V, K, subsets, flags) ? 1 : 0;
+    return plan_stem(1, Cin, C, T, V, K, subsets, flags).kernel != StemKernel::none ? 1 : 0;
 }
 
 int stgcn_tcn_pack(const float *W, const float *scale, void *Wp, int Cin, int Cout, int K, unsigned flags,
@@ -208,7 +208,7 @@ int stgcn_tcn_forward(const float *x, const float *W, const float *scale, const 
 
 size_t stgcn_stem_prep_bytes(int Cin, int C, int K, int subsets, unsigned flags) {
     if (Cin <= 0 || C <= 0 || K <= 0 || subsets <= 0) return 0;
-    return stem_prep_bytes(Cin, C, K, subsets, flags);
+    return plan_stem_prep(C, K, flags).bytes;
 }
 
 int stgcn_stem_prepare(const float *Wd, const float *bd, const float *Wdown, const float *bdown,
@@ -225,25 +225,18 @@ int stgcn_stem_prepare(const float *Wd, const float *bd, const float *Wdown, con
 
 size_t stgcn_stem_ws_bytes(int N, int Cin, int C, int T, int V, int K, int subsets, unsigned flags) {
     if (N <= 0 || Cin <= 0 || C <= 0 || T <= 0 || V <= 0 || K <= 0 || subsets <= 0) return 0;
-    return stem_ws_bytes(N, Cin, C, T, V, K, subsets, flags);
+    return plan_stem(N, Cin, C, T, V, K, subsets, flags).ws_bytes;
 }
 
 const char *stgcn_stem_kernel_name(int Cin, int C, int T, int V, int K, int subsets, unsigned flags) {
     if (Cin <= 0 || C <= 0 || T <= 0 || V <= 0 || K <= 0 || subsets <= 0) return "";
-    if (!stem_fused_supported(Cin, C, T, V, K, subsets, flags)) return "";
-    if (stem_v4_supported(Cin, C, T, V, K, subsets, flags)) {
-        if (stem_v4_features_in_kernel(C, T, V, K, flags) &&
-            (stem_v6_supported(C, T, V, K, flags) || stem_v6w_supported(C, T, V, K, flags)))
-            return stem_f16mx_supported(C, T, V, K, flags) ? "stem_f16mx_kernel" : "stem_bf16_v6_kernel";
-        return "stem_bf16_v4_kernel";
-    }
-    const unsigned math = flags & STGCN_MATH_MASK;
-    return (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) ? "stem_mfma_bf16_kernel" : "stem_mfma_f32_kernel";
+    return stem_kernel_name(plan_stem(1, Cin, C, T, V, K, subsets, flags).kernel);
 }
 
 int stgcn_stem_features_used(int Cin, int C, int T, int V, int K, int subsets, unsigned flags) {
     if (Cin <= 0 || C <= 0 || T <= 0 || V <= 0 || K <= 0 || subsets <= 0) return 0;
-    return stem_v4_supported(Cin, C, T, V, K, subsets, flags) ? 1 : 0;
+    const StemPart part = plan_stem(1, Cin, C, T, V, K, subsets, flags).part;
+    return part == StemPart::features || part == StemPart::frags ? 1 : 0;
 }
 
 int stgcn_stem_attention(const float *x, const float *A_eff, const float *Wa, const float *ba, const float *Wb,
@@ -254,15 +247,14 @@ int stgcn_stem_attention(const float *x, const float *A_eff, const float *Wa, co
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(C); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(inter_c);
     REQUIRE_POS(subsets); REQUIRE_POS(K);
     if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "stem: N=%d > 65535 clips per call", N);
-    const size_t need = stem_ws_bytes(N, Cin, C, T, V, K, subsets, flags);
-    if (ws_bytes < need) return fail(STGCN_ERR_WORKSPACE, "stem: workspace %zu B < %zu B", ws_bytes, need);
-    float *fpart = stem_ws_features(ws, N, Cin, C, T, V, K, subsets, flags);   // feature rows, or attention fragments
-    const bool frags = fpart != nullptr && stem_v4_features_in_kernel(C, T, V, K, flags);
-    return launch_attention(x, A_eff, Wa, ba, Wb, bb, (float *)ws, frags ? nullptr : fpart, N, Cin, T, V, inter_c, subsets,
-                            (hipStream_t)stream, (flags & STGCN_IN_NTVC) != 0,
-                            stem_ws_xcopy(ws, N, Cin, C, T, V, K, subsets, flags), frags ? fpart : nullptr,
-                            frags ? stem_wide_split(V) : 0,    // wide frames: fragments for the two joint halves
-                            frags ? stem_ws_bounds(ws, N, Cin, C, T, V, K, subsets, flags) : nullptr);
+    const StemPlan pl = plan_stem(N, Cin, C, T, V, K, subsets, flags);
+    if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "stem: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);
+    char *w = (char *)ws;
+    float *part = (float *)(w + pl.part_off);
+    return launch_attention(x, A_eff, Wa, ba, Wb, bb, (float *)ws, pl.part == StemPart::features ? part : nullptr, N, Cin, T, V,
+                            inter_c, subsets, (hipStream_t)stream, (flags & STGCN_IN_NTVC) != 0,
+                            pl.part == StemPart::xcopy ? part : nullptr, pl.part == StemPart::frags ? part : nullptr, pl.split,
+                            pl.bounds_off ? (float *)(w + pl.bounds_off) : nullptr);
 }
 
 int stgcn_stem_tail_prepared(const float *x, const void *ws, size_t ws_bytes, const void *prep, const float *t_shift,
@@ -271,11 +263,9 @@ int stgcn_stem_tail_prepared(const float *x, const void *ws, size_t ws_bytes, co
     REQUIRE_PTR(x); REQUIRE_PTR(ws); REQUIRE_PTR(prep); REQUIRE_PTR(t_shift); REQUIRE_PTR(out);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(C); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(subsets);
     REQUIRE_POS(K);
-    const size_t need = stem_ws_bytes(N, Cin, C, T, V, K, subsets, flags);
-    if (ws_bytes < need) return fail(STGCN_ERR_WORKSPACE, "stem: workspace %zu B < %zu B", ws_bytes, need);
-    if (const float *xc = stem_ws_xcopy(const_cast<void *>(ws), N, Cin, C, T, V, K, subsets, flags)) x = xc;  // (N,T,V,Cin) input
-    return launch_stem(x, (const float *)ws, stem_ws_features(const_cast<void *>(ws), N, Cin, C, T, V, K, subsets, flags),
-                       prep, t_shift, out, N, Cin, C, T, V, subsets, K, flags, (hipStream_t)stream);
+    const StemPlan pl = plan_stem(N, Cin, C, T, V, K, subsets, flags);
+    if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "stem: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);
+    return launch_stem(pl, x, ws, prep, t_shift, out, N, Cin, C, T, V, subsets, K, flags, (hipStream_t)stream);
 }
 
 int stgcn_stem_forward_prepared(const float *x, const float *A_eff, const float *Wa, const float *ba,

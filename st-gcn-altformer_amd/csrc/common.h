@@ -126,31 +126,29 @@ int launch_tcn(const float *x, const void *Wp, const float *shift, void *y, int 
                int Cout, int T, int V, int K, int stride, unsigned flags, hipStream_t st);
 
 // bf16 matrix-core variants (tcn_bf16.hip)
-bool bf16_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags, bool fused);
+bool bf16_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
 bool bf16_packs(int Cin, int Cout, unsigned math);
 int launch_tcn_pack_bf16(const float *W, const float *scale, void *Wp, int Cin, int Cout, int K, hipStream_t st);
-int launch_tcn_bf16(const float *x, const float *P, const float *W12, const void *Wp, const float *shift, void *y,
-                    int N, int Cin, int Cout, int T, int V, int K, int stride, unsigned flags, bool fused,
-                    hipStream_t st);
+int launch_tcn_bf16(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V, int K,
+                    int stride, unsigned flags, hipStream_t st);
+// the 128-pixel fused stem on the bf16 matrix cores: reads x (channel-major) and P, computes the features per tile
+bool stem_bf16_small_supported(int C, int T, int V, int K, unsigned flags);
+int launch_stem_bf16_small(const float *x, const float *P, const float *W12, const void *Wp, const float *shift, void *out, int N,
+                           int C, int T, int V, int K, unsigned flags, hipStream_t st);
 
 bool tcn_mfma_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
-bool stem_fused_supported(int Cin, int C, int T, int V, int K, int S, unsigned flags);
 
-// large-tile persistent bf16 stem (stem_bf16_v4.hip); consumes the feature tensor the attention kernel emits
+// large-tile persistent bf16 stem, eight waves (stem_bf16_v4.hip); *frags: the 256-pixel tile (features from fragments)
 bool attention_emits_features(int Cin, int V, int S);
-bool stem_v4_supported(int Cin, int C, int T, int V, int K, int S, unsigned flags);
-// true: the kernel computes the graph-conv features itself from x and the attention fragments (`feat` then points at the
-// (N,12,64) x 16 B fragments the attention kernel wrote); false: `feat` is the (N,T*V) x 64 B feature tensor
-bool stem_v4_features_in_kernel(int C, int T, int V, int K, unsigned flags);
+bool stem_v4_supported(int Cin, int C, int T, int V, int K, int S, unsigned flags, bool *frags = nullptr);
 int launch_stem_v4(const float *x, bool x_ntvc, const float *feat, const void *prep_w12, const void *Wp, const float *shift,
                    void *out, int N, int C, int T, int V, int K, unsigned flags, hipStream_t st);  // honours STGCN_OUT_NTVC
 
 // the same tile with ONE WAVE PER SIMD on v_mfma_f32_16x16x32_bf16 (stem_bf16_v6.hip: 256 threads, a wave owns all 128
-// channels of 64 pixels); reads the temporal weights in its own pair order, which stgcn_stem_prepare appends to the prep
-// blob behind the 32x32x16 packing
+// channels of 64 pixels), on pair-order temporal weights
 bool stem_v6_supported(int C, int T, int V, int K, unsigned flags);
 // ... and for wide frames (32 < V <= 64, V even: the two-hand graph) the same kernel over the two joint halves [0, V0) and
-// [V0, V), each handled like a narrow clip (stem_bf16_v6w.hip); the attention kernel then emits 48 fragments per clip
+// [V0, V), each handled like a narrow clip (stem_bf16_v6w.hip)
 static inline int stem_wide_split(int V) {     // V0 (a multiple of 4: 16-byte aligned half rows), or 0 when V does not split
     if (V <= 32 || V > 64 || (V & 1)) return 0;
     const int v0 = (V / 2 + 3) / 4 * 4;
@@ -298,17 +296,34 @@ int launch_agcn_bwd_generic(const float *x, const float *P, const float *A_eff, 
                             float *dbd, float *dWdown, float *dbdown, float *dPA, float *dx, int dx_initialised, int N,
                             int Cin, int Cout, int T, int V, int inter_c, int S, hipStream_t st);
 
-// fused stem
-size_t stem_prep_bytes(int Cin, int C, int K, int S, unsigned flags);
+// fused stem: the f32 kernel and the graph-conv fold (tcn_conv.hip) ...
+size_t stem_w12_bytes(int C);
+int launch_stem_fold(const float *Wd, const float *bd, const float *Wdown, const float *bdown, const float *bn_scale,
+                     const float *bn_shift, const float *down_scale, const float *down_shift, float *W12, int Cin, int C, int S,
+                     hipStream_t st);
+bool stem_f32_supported(int C, int T, int V, int K);   // Cin = 3, 3 subsets
+int launch_stem_f32(const float *x, const float *P, const float *W12, const void *Wp, const float *shift, void *out, int N, int C,
+                    int T, int V, int K, unsigned flags, hipStream_t st);   // (the same signature as launch_stem_bf16_small)
+
+// ... and the plan every stem entry point reads (stem.hip; the layouts are described there)
+enum class StemKernel { none, f32, bf16_small, kf4_features, kf4_frags, kf6, kf6w, kf7 };
+enum class StemPart { none, features, frags, xcopy };   // the workspace part behind P
+struct StemPrep { size_t bytes = 0, single = 0, pairs = 0, f16mx = 0; };   // prep blob: bytes, offsets of its parts (0: absent)
+struct StemPlan {
+    StemKernel kernel = StemKernel::none;
+    StemPrep prep;
+    StemPart part = StemPart::none;
+    size_t ws_bytes = 0, part_off = 0, bounds_off = 0;  // P at 0; bounds_off: KF7's per-clip bounds (0: not written)
+    int split = 0;                                      // frags of wide frames: V0 of the joint halves, else 0
+};
+StemPrep plan_stem_prep(int C, int K, unsigned flags);
+StemPlan plan_stem(int N, int Cin, int C, int T, int V, int K, int S, unsigned flags);
+const char *stem_kernel_name(StemKernel k);
 int launch_stem_prepare(const float *Wd, const float *bd, const float *Wdown, const float *bdown,
                         const float *bn_scale, const float *bn_shift, const float *down_scale,
                         const float *down_shift, const float *Wt, const float *t_scale, void *prep,
                         int Cin, int C, int K, int S, unsigned flags, hipStream_t st);
-size_t stem_ws_bytes(int N, int Cin, int C, int T, int V, int K, int S, unsigned flags);
-float *stem_ws_features(void *ws, int N, int Cin, int C, int T, int V, int K, int S, unsigned flags);  // NULL if unused
-float *stem_ws_bounds(void *ws, int N, int Cin, int C, int T, int V, int K, int S, unsigned flags);    // NULL unless KF7 serves the shape
-float *stem_ws_xcopy(void *ws, int N, int Cin, int C, int T, int V, int K, int S, unsigned flags);     // NULL if unused
-int launch_stem(const float *x, const float *P, const float *feat, const void *prep, const float *t_shift,
-                void *out, int N, int Cin, int C, int T, int V, int S, int K, unsigned flags, hipStream_t st);
+int launch_stem(const StemPlan &p, const float *x, const void *ws, const void *prep, const float *t_shift, void *out, int N,
+                int Cin, int C, int T, int V, int S, int K, unsigned flags, hipStream_t st);
 
 }  // namespace stgcn

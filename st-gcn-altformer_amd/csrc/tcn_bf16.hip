@@ -485,12 +485,12 @@ __global__ __launch_bounds__(NT) void stem_mfma_bf16_kernel(
     }
 }
 
-struct StemPlan {
+struct Bf16StemTile {
     int pb = 0, rows = 0;
     size_t lds = 0;
 };
 
-inline bool plan_stem_bf16(int C, int V, int K, int T, int terms, StemPlan &pl) {
+inline bool plan_stem_bf16(int C, int V, int K, int T, int terms, Bf16StemTile &pl) {
     if (C % CCB != 0 || C % 128 != 0) return false;
     int dt = ceil_div(NPB - 1, V);
     if (dt > T - 1) dt = T - 1;
@@ -512,7 +512,7 @@ inline bool plan_stem_bf16(int C, int V, int K, int T, int terms, StemPlan &pl) 
 
 template <int PB, int TERMS, int KT>
 int launch_stem_variant(const float *x, const float *P, const float *W12, const uint4 *Wp, const float *shift, void *y,
-                        int N, int C, int T, int V, int K, const StemPlan &pl, bool bf16out, int opt, hipStream_t st) {
+                        int N, int C, int T, int V, int K, const Bf16StemTile &pl, bool bf16out, int opt, hipStream_t st) {
     const dim3 grid(ceil_div(T * V, NPB), C / 128, N);
     if (bf16out) {
         auto kern = stem_mfma_bf16_kernel<PB, TERMS, true, KT>;
@@ -529,7 +529,7 @@ int launch_stem_variant(const float *x, const float *P, const float *W12, const 
 
 template <int TERMS>
 int dispatch_stem(const float *x, const float *P, const float *W12, const uint4 *Wp, const float *shift, void *y, int N,
-                  int C, int T, int V, int K, const StemPlan &pl, bool bf16out, int opt, hipStream_t st) {
+                  int C, int T, int V, int K, const Bf16StemTile &pl, bool bf16out, int opt, hipStream_t st) {
 #define GO(PB, KT) return launch_stem_variant<PB, TERMS, KT>(x, P, W12, Wp, shift, y, N, C, T, V, K, pl, bf16out, opt, st)
     if (K == 9) {
         if (pl.pb <= 3) GO(3, 9);
@@ -603,19 +603,21 @@ int dispatch_tcn(const float *x, const uint4 *Wp, const float *shift, void *y, i
 
 }  // namespace
 
-bool bf16_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags, bool fused) {
+bool bf16_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
     const unsigned math = flags & STGCN_MATH_MASK;
     if (math != STGCN_MATH_BF16X3 && math != STGCN_MATH_BF16) return false;
     const int Tout = (T + 2 * ((K - 1) / 2) - K) / stride + 1;
     if (Tout < 1) return false;
-    const int terms = math == STGCN_MATH_BF16X3 ? 3 : 1;
-    if (fused) {
-        StemPlan sp;
-        return Cin == Cout && stride == 1 && plan_stem_bf16(Cin, V, K, T, terms, sp);
-    }
     if (tcn_v6_supported(Cin, Cout, T, V, K, stride, flags) || tcn_v4_supported(Cin, Cout, T, V, K, stride, flags)) return true;
     Bf16Plan pl;
-    return plan_bf16(Cin, Cout, V, K, stride, Tout, terms, pl);
+    return plan_bf16(Cin, Cout, V, K, stride, Tout, math == STGCN_MATH_BF16X3 ? 3 : 1, pl);
+}
+
+bool stem_bf16_small_supported(int C, int T, int V, int K, unsigned flags) {
+    const unsigned math = flags & STGCN_MATH_MASK;
+    Bf16StemTile sp;   // (T + 2 * ((K - 1) / 2) - K + 1: the output frames)
+    return (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) && T + 2 * ((K - 1) / 2) - K + 1 >= 1 &&
+           plan_stem_bf16(C, V, K, T, math == STGCN_MATH_BF16X3 ? 3 : 1, sp);
 }
 
 bool bf16_packs(int Cin, int Cout, unsigned math) {
@@ -631,21 +633,23 @@ int launch_tcn_pack_bf16(const float *W, const float *scale, void *Wp, int Cin, 
     return STGCN_OK;
 }
 
-int launch_tcn_bf16(const float *x, const float *P, const float *W12, const void *Wp, const float *shift, void *y,
-                    int N, int Cin, int Cout, int T, int V, int K, int stride, unsigned flags, bool fused,
-                    hipStream_t st) {
+int launch_stem_bf16_small(const float *x, const float *P, const float *W12, const void *Wp, const float *shift, void *out, int N,
+                           int C, int T, int V, int K, unsigned flags, hipStream_t st) {
+    const bool three = (flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3;
+    Bf16StemTile sp;
+    if (!plan_stem_bf16(C, V, K, T, three ? 3 : 1, sp))
+        return fail(STGCN_ERR_UNSUPPORTED, "fused bf16 stem kernel does not cover C=%d V=%d K=%d T=%d", C, V, K, T);
+    return (three ? dispatch_stem<3> : dispatch_stem<1>)(x, P, W12, (const uint4 *)Wp, shift, out, N, C, T, V, K, sp,
+                                                         (flags & STGCN_OUT_BF16) != 0,
+                                                         (flags & STGCN_OUT_NTVC) ? OPT_OUT_NTVC : 0, st);
+}
+
+int launch_tcn_bf16(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V, int K,
+                    int stride, unsigned flags, hipStream_t st) {
     const unsigned math = flags & STGCN_MATH_MASK;
     const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
     const int terms = math == STGCN_MATH_BF16X3 ? 3 : 1;
     const int Tout = (T + 2 * ((K - 1) / 2) - K) / stride + 1;
-    if (fused) {
-        StemPlan sp;
-        if (Cin != Cout || stride != 1 || !plan_stem_bf16(Cin, V, K, T, terms, sp))
-            return fail(STGCN_ERR_UNSUPPORTED, "fused bf16 stem kernel does not cover C=%d V=%d K=%d T=%d", Cin, V, K, T);
-        const int opt = (flags & STGCN_OUT_NTVC) ? OPT_OUT_NTVC : 0;
-        if (terms == 3) return dispatch_stem<3>(x, P, W12, (const uint4 *)Wp, shift, y, N, Cin, T, V, K, sp, bf16out, opt, st);
-        return dispatch_stem<1>(x, P, W12, (const uint4 *)Wp, shift, y, N, Cin, T, V, K, sp, bf16out, opt, st);
-    }
     // K = 9, stride 1: large-tile persistent kernels — one wave per SIMD on 16x16x32 where that form covers the shape
     // (diagnostic builds: mask 8192 keeps the eight-wave kernel for A/B runs in one process)
     if (tcn_v6_supported(Cin, Cout, T, V, K, stride, flags) && !(ablate_mask() & 8192))

@@ -571,7 +571,7 @@ int launch_tcn(const float *x, const void *Wp, const float *shift, void *y, int 
     if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "tcn: N=%d > 65535 clips per call", N);
     if (math > STGCN_MATH_F32_VALU) return fail(STGCN_ERR_ARG, "tcn: unknown math mode %u", math);
     if (bf16_packs(Cin, Cout, math))
-        return launch_tcn_bf16(x, nullptr, nullptr, Wp, shift, y, N, Cin, Cout, T, V, K, stride, flags, false, st);
+        return launch_tcn_bf16(x, Wp, shift, y, N, Cin, Cout, T, V, K, stride, flags, st);
 
     if (packs_as_mfma(Cin, Cout, math)) {
         if (!mfma_f32_shape_ok(Cin, Cout, V, K, stride, Tout))
@@ -610,143 +610,42 @@ int launch_tcn(const float *x, const void *Wp, const float *shift, void *y, int 
 bool tcn_mfma_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
     const unsigned math = flags & STGCN_MATH_MASK;
     if (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16)
-        return bf16_supported(Cin, Cout, T, V, K, stride, flags, false);
+        return bf16_supported(Cin, Cout, T, V, K, stride, flags);
     const int Tout = (T + 2 * ((K - 1) / 2) - K) / stride + 1;
     return Tout >= 1 && packs_as_mfma(Cin, Cout, math) && mfma_f32_shape_ok(Cin, Cout, V, K, stride, Tout);
 }
 
-// ---- fused stem -------------------------------------------------------------------------
-// prep blob: [ W12 : C*W12P floats, 256-B aligned ][ packed temporal weights ]
-static size_t stem_w12_bytes(int C) { return align_up((size_t)C * W12P * sizeof(float), 256); }
+// ---- fused stem, f32 (the other kernels and the plan that picks one: stem.hip) ------------------
+size_t stem_w12_bytes(int C) { return align_up((size_t)C * W12P * sizeof(float), 256); }
 
-// bf16 modes, K = 9: a second copy of the temporal weights in KF6's pair order follows the first
-static bool stem_prep_has_pairs(int C, int K, unsigned flags) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    return (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) && K == 9 && C % 128 == 0;
+int launch_stem_fold(const float *Wd, const float *bd, const float *Wdown, const float *bdown, const float *bn_scale,
+                     const float *bn_shift, const float *down_scale, const float *down_shift, float *W12, int Cin, int C, int S,
+                     hipStream_t st) {
+    hipLaunchKernelGGL(stem_fold_kernel, dim3(ceil_div(C * W12P, 256)), dim3(256), 0, st, Wd, bd, Wdown, bdown,
+                       bn_scale, bn_shift, down_scale, down_shift, W12, Cin, C, S);
+    STGCN_LAUNCH_CHECK("stem_fold_kernel");
+    return STGCN_OK;
 }
 
-// STGCN_STEM_F16MX: a third packing (KF7, stem_f16mx.hip) behind the pair-order copy
-static bool stem_prep_has_f16mx(int C, int K, unsigned flags) {
-    return (flags & STGCN_STEM_F16MX) && (flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3 && stem_prep_has_pairs(C, K, flags);
-}
-static size_t stem_f16mx_offset(int C, int K, unsigned flags) { return stem_w12_bytes(C) + 2 * tcn_packed_single_bytes(C, C, K, flags); }
-
-size_t stem_prep_bytes(int Cin, int C, int K, int S, unsigned flags) {
-    (void)Cin; (void)S;
-    return stem_w12_bytes(C) + tcn_packed_single_bytes(C, C, K, flags) * (stem_prep_has_pairs(C, K, flags) ? 2 : 1) +
-           (stem_prep_has_f16mx(C, K, flags) ? align_up(stem_f16mx_prep_bytes(C, K), 256) : 0);
-}
-
-static bool stem_shape_ok(int Cin, int C, int V, int K, int S, int T) {
-    if (Cin != 3 || S != 3) return false;
+bool stem_f32_supported(int C, int T, int V, int K) {
+    constexpr int Cin = 3, S = 3;
     if (!mfma_f32_shape_ok(C, C, V, K, 1, T)) return false;
     const int ROW = row_stride(V, K, 1, T);
     if ((size_t)S * V * V + (size_t)Cin * (ROW - 1) > (size_t)CC * ROW) return false;  // Ps+Xs alias buf1
     return ((size_t)C * W12P + (size_t)2 * CC * ROW) * 4 <= (size_t)kLdsBytes;
 }
 
-bool stem_fused_supported(int Cin, int C, int T, int V, int K, int S, unsigned flags) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    if (Cin != 3 || S != 3 || T < 1) return false;
-    if (stem_v4_supported(Cin, C, T, V, K, S, flags)) return true;
-    if (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) return bf16_supported(C, C, T, V, K, 1, flags, true);
-    return math == STGCN_MATH_F32 && stem_shape_ok(Cin, C, V, K, S, T);
-}
-
-int launch_stem_prepare(const float *Wd, const float *bd, const float *Wdown, const float *bdown,
-                        const float *bn_scale, const float *bn_shift, const float *down_scale,
-                        const float *down_shift, const float *Wt, const float *t_scale, void *prep, int Cin,
-                        int C, int K, int S, unsigned flags, hipStream_t st) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    if (math != STGCN_MATH_F32 && math != STGCN_MATH_BF16X3 && math != STGCN_MATH_BF16)
-        return fail(STGCN_ERR_UNSUPPORTED, "stem: no fused kernel for math mode %u", math);
-    if (Cin != 3 || S != 3 || C % 128 != 0)
-        return fail(STGCN_ERR_UNSUPPORTED, "stem: fused kernel covers Cin=3, 3 subsets, C%%128==0 (got Cin=%d S=%d C=%d)",
-                    Cin, S, C);
-    hipLaunchKernelGGL(stem_fold_kernel, dim3(ceil_div(C * W12P, 256)), dim3(256), 0, st, Wd, bd, Wdown, bdown,
-                       bn_scale, bn_shift, down_scale, down_shift, (float *)prep, Cin, C, S);
-    STGCN_LAUNCH_CHECK("stem_fold_kernel");
-    int rc = launch_tcn_pack(Wt, t_scale, (char *)prep + stem_w12_bytes(C), C, C, K, flags, st);
-    if (rc != STGCN_OK || !stem_prep_has_pairs(C, K, flags)) return rc;
-    rc = launch_tcn_pack_bf16_pairs(Wt, t_scale, (char *)prep + stem_w12_bytes(C) + tcn_packed_single_bytes(C, C, K, flags), C, C, st);
-    if (rc != STGCN_OK || !stem_prep_has_f16mx(C, K, flags)) return rc;
-    return launch_stem_f16mx_prepare((const float *)prep, Wt, t_scale, (char *)prep + stem_f16mx_offset(C, K, flags), C, st);
-}
-
-// workspace of the fused stem: [ P : N*S*V*V floats, 256-B aligned ] then ONE of
-//   [ features : N*T*V x 64 B (16 features as bf16 hi + lo) ]   when the large-tile kernel serves the shape and reads
-//                                                                features (wide frames), or
-//   [ fragments: N x 12 KiB (attention matrices as bf16 hi/lo MFMA B fragments; 48 KiB for wide frames) ]  when it computes
-//                                                                them itself, or
-//   [ x copy   : N*Cin*T*V floats, channel-major ]              with STGCN_IN_NTVC on the kernels that read x themselves
-static size_t stem_ws_p_bytes(int N, int V, int S) { return align_up((size_t)N * S * V * V * sizeof(float), 256); }
-
-static size_t stem_ws_feat_bytes(int N, int Cin, int C, int T, int V, int K, int S, unsigned flags) {
-    if (!stem_v4_supported(Cin, C, T, V, K, S, flags)) return 0;
-    return stem_v4_features_in_kernel(C, T, V, K, flags) ? (size_t)N * (V > 32 ? 48 : 12) * 1024   // (wide frames: both joint halves)
-                                                         : (size_t)N * T * V * 16 * sizeof(float);
-}
-
-size_t stem_ws_bytes(int N, int Cin, int C, int T, int V, int K, int S, unsigned flags) {
-    size_t b = stem_ws_p_bytes(N, V, S);
-    if (stem_v4_supported(Cin, C, T, V, K, S, flags)) {
-        b += stem_ws_feat_bytes(N, Cin, C, T, V, K, S, flags);
-        if (stem_f16mx_supported(C, T, V, K, flags)) b += align_up((size_t)N * 4 * sizeof(float), 256);   // per-clip bounds (KF7)
-    } else if (flags & STGCN_IN_NTVC) b += (size_t)N * Cin * T * V * sizeof(float);
-    return b;
-}
-
-// (N,4) floats behind the fragments when KF7 serves the shape, else NULL
-float *stem_ws_bounds(void *ws, int N, int Cin, int C, int T, int V, int K, int S, unsigned flags) {
-    if (!stem_v4_supported(Cin, C, T, V, K, S, flags) || !stem_f16mx_supported(C, T, V, K, flags)) return nullptr;
-    return reinterpret_cast<float *>(static_cast<char *>(ws) + stem_ws_p_bytes(N, V, S) + stem_ws_feat_bytes(N, Cin, C, T, V, K, S, flags));
-}
-
-float *stem_ws_features(void *ws, int N, int Cin, int C, int T, int V, int K, int S, unsigned flags) {
-    if (!stem_v4_supported(Cin, C, T, V, K, S, flags)) return nullptr;
-    return reinterpret_cast<float *>(static_cast<char *>(ws) + stem_ws_p_bytes(N, V, S));
-}
-
-float *stem_ws_xcopy(void *ws, int N, int Cin, int C, int T, int V, int K, int S, unsigned flags) {
-    if (!(flags & STGCN_IN_NTVC) || stem_v4_supported(Cin, C, T, V, K, S, flags)) return nullptr;
-    return reinterpret_cast<float *>(static_cast<char *>(ws) + stem_ws_p_bytes(N, V, S));
-}
-
-int launch_stem(const float *x, const float *P, const float *feat, const void *prep, const float *t_shift,
-                void *out, int N, int Cin, int C, int T, int V, int S, int K, unsigned flags, hipStream_t st) {
-    const unsigned math = flags & STGCN_MATH_MASK;
+int launch_stem_f32(const float *x, const float *P, const float *W12, const void *Wp, const float *t_shift, void *out, int N, int C,
+                    int T, int V, int K, unsigned flags, hipStream_t st) {
     const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
-    if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "stem: N=%d > 65535 clips per call", N);
-    if (feat != nullptr && stem_v4_supported(Cin, C, T, V, K, S, flags)) {
-        if (stem_f16mx_supported(C, T, V, K, flags) && stem_v4_features_in_kernel(C, T, V, K, flags) && !(ablate_mask() & 512))
-            return launch_stem_f16mx(x, (flags & STGCN_IN_NTVC) != 0, feat,
-                                     (const char *)feat + stem_ws_feat_bytes(N, Cin, C, T, V, K, S, flags), prep,
-                                     (const char *)prep + stem_f16mx_offset(C, K, flags), t_shift, out, N, C, T, V, K, flags, st);
-        return launch_stem_v4(x, (flags & STGCN_IN_NTVC) != 0, feat, prep, (const char *)prep + stem_w12_bytes(C), t_shift,
-                              out, N, C, T, V, K, flags, st);
-    }
-    if (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) {
-        if (Cin != 3 || S != 3)
-            return fail(STGCN_ERR_UNSUPPORTED, "stem: fused kernel covers Cin=3, 3 subsets (got %d, %d)", Cin, S);
-        return launch_tcn_bf16(x, P, (const float *)prep, (const char *)prep + stem_w12_bytes(C), t_shift, out, N, C,
-                               C, T, V, K, 1, flags, true, st);
-    }
-    if (math != STGCN_MATH_F32)
-        return fail(STGCN_ERR_UNSUPPORTED, "stem: no fused kernel for math mode %u", math);
-    if (!stem_shape_ok(Cin, C, V, K, S, T))
-        return fail(STGCN_ERR_UNSUPPORTED,
-                    "stem: fused kernel does not cover Cin=%d S=%d C=%d V=%d K=%d T=%d; call the two-stage path",
-                    Cin, S, C, V, K, T);
     const int ROW = row_stride(V, K, 1, T);
     const int jpr = ceil_div(ROW - 1, 256);
     const size_t lds = ((size_t)C * W12P + (size_t)2 * CC * ROW) * 4;
-    const float *W12 = (const float *)prep;
-    const float4 *Wp = (const float4 *)((const char *)prep + stem_w12_bytes(C));
     const dim3 grid(ceil_div(T * V, NP), C / 128, N);
 #define LAUNCH_STEM(J, B)                                                                               \
     do {                                                                                                \
         STGCN_HIP_CHECK(allow_lds(stem_mfma_f32_kernel<J, B>, lds));                                    \
-        hipLaunchKernelGGL((stem_mfma_f32_kernel<J, B>), grid, dim3(256), lds, st, x, P, W12, Wp, t_shift, \
+        hipLaunchKernelGGL((stem_mfma_f32_kernel<J, B>), grid, dim3(256), lds, st, x, P, W12, (const float4 *)Wp, t_shift, \
                            out, C, T, V, K, ROW, ablate_mask() | ((flags & STGCN_OUT_NTVC) ? OPT_OUT_NTVC : 0)); \
     } while (0)
     if (jpr == 1) { if (bf16out) LAUNCH_STEM(1, true); else LAUNCH_STEM(1, false); }
