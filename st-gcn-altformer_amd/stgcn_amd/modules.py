@@ -8,12 +8,17 @@ there is no torch-op implementation of the math in this package.
 Eval-mode parameters are folded/packed once and cached; the cache is keyed on the version
 counter AND the storage address of every parameter and buffer, so an optimizer step,
 ``load_state_dict``, a manual in-place edit or a ``param.data = other`` swap invalidates it.
+
+Under ``nn.DataParallel`` the replicas (new objects on every forward, without ``parameters()``) find
+their weights by attribute, record the module they were made from, and stage into that module's
+per-device cache, keyed on its tensors.
 """
 from __future__ import annotations
 
 import math
 import warnings
 import os
+import threading
 from typing import Optional
 
 import torch
@@ -38,15 +43,77 @@ def _identity(x):
     return x
 
 
+def _master(mod: nn.Module) -> nn.Module:
+    """The module an nn.DataParallel replica was made from (``_replicate_for_data_parallel``); the module itself otherwise."""
+    return mod.__dict__.get("_dp_master", mod)
+
+
+def _state_tensors(mod: nn.Module):
+    """Every weight and buffer of a unit_agcn / Unit2D.  The weights are found by attribute (``mod._weights()``), not by
+    ``parameters()``: an nn.DataParallel replica holds them as plain attributes and has no parameters
+    (torch/nn/parallel/replicate.py).  Buffers stay registered on a replica."""
+    return [t for t in mod._weights() if t is not None] + list(mod.buffers())
+
+
 def _versions(mod: nn.Module):
     """Cache key over every parameter and buffer: (version counter, storage address).  The counter sees in-place edits
     (an optimizer step, load_state_dict, ``p.data.mul_()``); the address sees ``param.data = new_tensor`` — an EMA or
     weight swap done that way leaves ``_version`` where it was (round-2 review) but moves ``data_ptr()``."""
-    return tuple((t._version, t.data_ptr()) for t in list(mod.parameters()) + list(mod.buffers()))
+    return tuple((t._version, t.data_ptr()) for t in _state_tensors(mod))
 
 
 def _wants_grad(mod: nn.Module, x: torch.Tensor) -> bool:
-    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in mod.parameters()))
+    return torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in mod._weights()))
+
+
+class _DeviceSlot(dict):
+    """One device's staged state of a module, with the lock that guards it."""
+
+    def __init__(self):
+        super().__init__()
+        self.lock = threading.RLock()
+
+
+class _DeviceStaging:
+    """What outlives one forward of a unit_agcn / Unit2D, per device: the staged (stacked, folded, packed) weights and the
+    device copy of the constant ``A``.  It belongs to the master module; nn.DataParallel replicas — new objects on every
+    forward, run in parallel_apply's threads — use their master's, so a replica's second forward finds its device's
+    entries.  A copy or an unpickled module starts with an empty store (staged device tensors belong to the original)."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self._slots = {}
+        self._zeros = {}
+
+    def slot(self, device) -> _DeviceSlot:
+        with self._lock:
+            s = self._slots.get(device)
+            if s is None:
+                s = self._slots[device] = _DeviceSlot()
+            return s
+
+    def zeros(self, device, dtype) -> torch.Tensor:
+        """64 zeros (the staging's alignment padding), one tensor per device and dtype."""
+        with self._lock:
+            z = self._zeros.get((device, dtype))
+            if z is None:
+                z = self._zeros[(device, dtype)] = torch.zeros(64, device=device, dtype=dtype)
+            return z
+
+    def __reduce__(self):
+        return (_DeviceStaging, ())
+
+
+def _slot(mod: nn.Module, device) -> _DeviceSlot:
+    return _store(mod).slot(device)
+
+
+def _store(mod: nn.Module) -> _DeviceStaging:
+    m = _master(mod)
+    store = m.__dict__.get("_staging")
+    if store is None:                    # (a module pickled before the store existed)
+        store = m.__dict__.setdefault("_staging", _DeviceStaging())
+    return store
 
 
 def _check_input(mod: nn.Module, x: torch.Tensor, backward_ok: bool = False, bn_training: Optional[bool] = None):
@@ -254,6 +321,9 @@ class unit_agcn(nn.Module):
     This is reproduced on purpose (results must match the reference for the same checkpoint);
     assign ``module.A = graph_tensor`` afterwards to use the true graph as the fixed term.
     ``use_local_bn`` / ``mask_learning`` are accepted and ignored, as in the reference.
+
+    ``last_attention`` holds P of this module's latest forward.  Under nn.DataParallel each replica sets its own and the
+    master's is not updated: attention maps are not gathered across replicas.
     """
 
     def __init__(self, in_channels, out_channels, A, coff_embedding=4, num_subset=3, use_local_bn=False,
@@ -294,19 +364,36 @@ class unit_agcn(nn.Module):
         for i in range(self.num_subset):
             _conv_branch_init(self.conv_d[i], self.num_subset)
 
-        self._cache = None
+        self._staging = _DeviceStaging()
         self._fused_tcn: Optional["Unit2D"] = None
         self.last_attention: Optional[torch.Tensor] = None   # P (N,S,V,V) of the latest forward
+
+    def _replicate_for_data_parallel(self):
+        replica = super()._replicate_for_data_parallel()
+        object.__setattr__(replica, "_dp_master", _master(self))     # (not a sub-module: no Module.__setattr__)
+        return replica
 
     # -- parameter staging ---------------------------------------------------------------
     def _has_down(self) -> bool:
         return isinstance(self.down, nn.Sequential)
 
+    def _cache_key(self, device):
+        """The device, and version + storage of every tensor of the master module (a replica's tensors are copies of them
+        made for one forward) and of the constant A."""
+        return (device, _versions(_master(self)), self.A._version, id(self.A), self.A.data_ptr())
+
     def _staged(self, device):
-        """Stacked / folded device tensors for the C ABI, cached until any parameter changes."""
-        key = (device, _versions(self), self.A._version, id(self.A), self.A.data_ptr())
-        if self._cache is not None and self._cache["key"] == key:
-            return self._cache
+        """Stacked / folded device tensors for the C ABI, cached per device until any parameter changes.  Staged from this
+        module's own tensors; the cache is the master's (a replica's tensors are bitwise copies of the master's)."""
+        key = self._cache_key(device)
+        slot = _slot(self, device)
+        with slot.lock:
+            st = slot.get("st")
+            if st is None or st["key"] != key:
+                st = slot["st"] = self._stage(device, key, slot)
+            return st
+
+    def _stage(self, device, key, slot):
         with torch.no_grad():
             S = self.num_subset
             st = {"key": key}
@@ -315,10 +402,7 @@ class unit_agcn(nn.Module):
             groups = [(self.conv_a, "Wa", "ba"), (self.conv_b, "Wb", "bb"), (self.conv_d, "Wd", "bd")]
             pieces, views, off = [], [], 0
             w0 = self.conv_a[0].weight
-            zkey = (w0.device, w0.dtype)
-            if getattr(self, "_zpad_key", None) != zkey:     # every group starts 256-byte aligned, like an allocation
-                object.__setattr__(self, "_zpad", torch.zeros(64, device=w0.device, dtype=w0.dtype))
-                object.__setattr__(self, "_zpad_key", zkey)
+            zpad = _store(self).zeros(w0.device, w0.dtype)     # every group starts 256-byte aligned, like an allocation
             for convs, wn, bn_ in groups:
                 c0 = convs[0]
                 for name, shape, ts in ((wn, (len(convs), c0.out_channels, c0.in_channels), [c.weight for c in convs]),
@@ -328,7 +412,7 @@ class unit_agcn(nn.Module):
                     views.append((name, shape, off, n))
                     pad = -n % 64
                     if pad:
-                        pieces.append(self._zpad[:pad])
+                        pieces.append(zpad[:pad])
                     off += n + pad
             flat = torch.cat(pieces).to(device=device, dtype=torch.float32)
             for name, shape, o, n in views:
@@ -336,11 +420,11 @@ class unit_agcn(nn.Module):
             # A = self.A.cuda(dev) + self.PA  (model/unit_agcn.py:75-76).  The constant A is uploaded once per device and
             # version — not per call, and not per restage either: in training every step restages (PA moved), and a
             # host-to-device copy there would synchronise the host each step and forbid capturing the step in a HIP graph
-            akey = (device, self.A._version, id(self.A), self.A.data_ptr())
-            if getattr(self, "_A_dev_key", None) != akey:
-                object.__setattr__(self, "_A_dev", self.A.to(device=device, dtype=torch.float32).contiguous())
-                object.__setattr__(self, "_A_dev_key", akey)
-            st["A_eff"] = (self._A_dev + self.PA.to(device)).contiguous()
+            akey = (self.A._version, id(self.A), self.A.data_ptr())
+            if slot.get("A_key") != akey:
+                slot["A_dev"] = self.A.to(device=device, dtype=torch.float32).contiguous()
+                slot["A_key"] = akey
+            st["A_eff"] = (slot["A_dev"] + self.PA.to(device)).contiguous()
             # folded running-statistics BatchNorms: what the inference kernels take — made on first use (_folded), not per
             # training step
             st["bn_scale"] = st["bn_shift"] = st["down_scale"] = st["down_shift"] = None
@@ -352,13 +436,12 @@ class unit_agcn(nn.Module):
             else:
                 st["Wdown"] = st["bdown"] = None
             assert S == st["Wd"].shape[0]
-        self._cache = st
         return st
 
     def _folded(self, st):
         """scale / shift of the running-statistics BatchNorms (eval forward), cached in the staged set."""
-        if st["bn_scale"] is None:
-            with torch.no_grad():
+        with _slot(self, st["key"][0]).lock, torch.no_grad():
+            if st["bn_scale"] is None:
                 bn = self.bn
                 st["bn_scale"], st["bn_shift"] = F.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, None, bn.eps)
                 if self._has_down():
@@ -379,13 +462,13 @@ class unit_agcn(nn.Module):
 
     def _fusable(self, x) -> bool:
         t = self._fused_tcn
-        if t is None or getattr(self, "_is_replica", False) or t.bn.training or not self._has_down():
+        if t is None or t.bn.training or not self._has_down():
             return False
         if t.dim != 2 or t.stride != 1 or t.conv.in_channels != self.out_channels \
                 or t.conv.out_channels != self.out_channels:
             return False
-        if t.conv.weight.device != x.device:
-            return False
+        if t.conv.weight.device != x.device and _master(self) is self:
+            return False                     # (a replica's partner is its master's Unit2D: staged for the replica's device)
         _, C, T, V = x.shape
         return F.stem_supported(C, self.out_channels, T, V, t.kernel_size, self.num_subset, t.math_mode)
 
@@ -400,24 +483,27 @@ class unit_agcn(nn.Module):
             raise RuntimeError(f"unit_agcn: input has {x.shape[3]} joints, adjacency has {self.PA.shape[-1]}")
         st = self._staged(x.device)
         wants = _wants_grad(self, x)
-        if wants and not bn_training and self._fused_tcn is not None and not getattr(self, "_warned_fusion_bypass", False):
-            object.__setattr__(self, "_warned_fusion_bypass", True)
+        master = _master(self)
+        if wants and not bn_training and self._fused_tcn is not None and not getattr(master, "_warned_fusion_bypass", False):
+            object.__setattr__(master, "_warned_fusion_bypass", True)
             warnings.warn("unit_agcn: eval-mode call with gradients enabled — taking the differentiable two-kernel path, not "
                           "the fused inference kernel; wrap inference in torch.no_grad() (as train_sttran.py:207-210 does)",
                           stacklevel=2)
         if not bn_training and not wants and self._fusable(x):
             if not F._is_channels_last(x):     # the permuted (N,T,V,C) batch of ST_GCN_AltFormer.py:62-68 is read in place
                 x = x.contiguous()
-            t = self._fused_tcn
+            t = self._fused_tcn                # (on a replica: its master's Unit2D, staged for this device)
             ts = t._staged(x.device)
             pkey = (st["key"], ts["key"], t.math_mode)
-            if st.get("stem_key") != pkey:
-                self._folded(st)
-                st["stem_prep"] = F.stem_prepare(st["Wd"], st["bd"], st["Wdown"], st["bdown"], st["bn_scale"],
-                                                 st["bn_shift"], st["down_scale"], st["down_shift"], ts["W"],
-                                                 ts["scale"], t.math_mode)
-                st["stem_key"] = pkey
-            out, P = F.stem_forward(x, st["A_eff"], st["Wa"], st["ba"], st["Wb"], st["bb"], st["stem_prep"],
+            with _slot(self, x.device).lock:   # (replicas on one device share the entry)
+                if st.get("stem_key") != pkey:
+                    self._folded(st)
+                    st["stem_prep"] = F.stem_prepare(st["Wd"], st["bd"], st["Wdown"], st["bdown"], st["bn_scale"],
+                                                     st["bn_shift"], st["down_scale"], st["down_shift"], ts["W"],
+                                                     ts["scale"], t.math_mode)
+                    st["stem_key"] = pkey
+                prep = st["stem_prep"]
+            out, P = F.stem_forward(x, st["A_eff"], st["Wa"], st["ba"], st["Wb"], st["bb"], prep,
                                     ts["shift"], self.out_channels, t.kernel_size, t.math_mode, t.out_bf16,
                                     channels_last_out=t.channels_last_out)
             self.last_attention = P
@@ -433,15 +519,22 @@ class unit_agcn(nn.Module):
         return y
 
 
-    def _train_params(self):
-        """Parameters in the order _AgcnTrainFn.backward returns their gradients."""
-        ps = [self.PA]
+    def _weights(self):
+        """The parameters by attribute (an nn.DataParallel replica has no ``parameters()``), in the order
+        _AgcnTrainFn.backward returns their gradients; a generator, so that _wants_grad stops at the first."""
+        yield self.PA
         for convs in (self.conv_a, self.conv_b, self.conv_d):
             for c in convs:
-                ps += [c.weight, c.bias]
+                yield c.weight
+                yield c.bias
         if self._has_down():
-            ps += [self.down[0].weight, self.down[0].bias, self.down[1].weight, self.down[1].bias]
-        return ps + [self.bn.weight, self.bn.bias]
+            yield from (self.down[0].weight, self.down[0].bias, self.down[1].weight, self.down[1].bias)
+        yield self.bn.weight
+        yield self.bn.bias
+
+    def _train_params(self):
+        """Parameters in the order _AgcnTrainFn.backward returns their gradients."""
+        return list(self._weights())
 
     def _forward_train(self, x, st, frozen=False):
         """Batch-statistics BatchNorm forward (model/unit_agcn.py:91-92 with self.training); updates running buffers.
@@ -513,29 +606,53 @@ class Unit2D(nn.Module):
         self.math_mode = _default_math()
         self.out_bf16 = False
         self.channels_last_out = False       # set_output_layout(): (N,C,T,V) result laid out (N,T,V,C)
-        self._cache = None
+        self._staging = _DeviceStaging()
+
+    def _replicate_for_data_parallel(self):
+        replica = super()._replicate_for_data_parallel()
+        object.__setattr__(replica, "_dp_master", _master(self))     # (not a sub-module: no Module.__setattr__)
+        return replica
+
+    def _weights(self):
+        """The parameters by attribute (an nn.DataParallel replica has no ``parameters()``); a generator, as unit_agcn's."""
+        c, bn = self.conv, self.bn
+        yield c.weight
+        yield c.bias
+        yield bn.weight
+        yield bn.bias
+
+    def _cache_key(self, device):
+        return (device, _versions(_master(self)), self.math_mode)
 
     def _staged(self, device):
-        key = (device, _versions(self), self.math_mode)
-        if self._cache is not None and self._cache["key"] == key:
-            return self._cache
-        with torch.no_grad():
-            c, bn = self.conv, self.bn
-            W = c.weight.reshape(c.out_channels, c.in_channels, self.kernel_size).to(
-                device=device, dtype=torch.float32).contiguous()
-            scale, shift = F.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, c.bias, bn.eps)
-            st = {"key": key, "W": W, "scale": scale, "shift": shift, "packed": {}}
-        self._cache = st
-        return st
+        """Weights and folded BatchNorm on ``device``, cached per device on the master module.  ``device`` may differ from
+        the weights' own: a replica's fused stem stages its master's Unit2D for the replica's device."""
+        key = self._cache_key(device)
+        slot = _slot(self, device)
+        with slot.lock:
+            st = slot.get("st")
+            if st is not None and st["key"] == key:
+                return st
+            with torch.no_grad():
+                c, bn = self.conv, self.bn
+                on = lambda t: None if t is None else t.to(device)
+                W = c.weight.reshape(c.out_channels, c.in_channels, self.kernel_size).to(
+                    device=device, dtype=torch.float32).contiguous()
+                scale, shift = F.bn_fold(on(bn.weight), on(bn.bias), on(bn.running_mean), on(bn.running_var), on(c.bias),
+                                         bn.eps)
+                st = slot["st"] = {"key": key, "W": W, "scale": scale, "shift": shift, "packed": {}}
+            return st
 
     def _packed(self, st, math_mode):
-        if math_mode not in st["packed"]:
-            st["packed"][math_mode] = F.tcn_pack(st["W"], st["scale"], math_mode)
-        return st["packed"][math_mode]
+        with _slot(self, st["key"][0]).lock:
+            if math_mode not in st["packed"]:
+                st["packed"][math_mode] = F.tcn_pack(st["W"], st["scale"], math_mode)
+            return st["packed"][math_mode]
 
     def forward(self, x):
         if isinstance(x, FusedStemOutput):
-            if getattr(x, "_stgcn_consumer", None) is not self:
+            consumer = getattr(x, "_stgcn_consumer", None)
+            if consumer is not self and consumer is not _master(self):   # (a replica takes its master's)
                 raise RuntimeError("Unit2D: received the fused stem result of ANOTHER Unit2D (enable_stem_fusion pairs one "
                                    "unit_agcn with one Unit2D); call disable_stem_fusion on that unit_agcn")
             return x.unwrap()             # tcn0(gcn0(x)), computed by the fused stem kernel in unit_agcn.forward
@@ -598,7 +715,8 @@ def enable_stem_fusion(gcn: unit_agcn, tcn: Unit2D) -> None:
     which every operation raises — and ``tcn.forward`` unwraps it.  Anything else that touches gcn0's
     return value (a forward hook, a residual branch as in TCN_GCN_unit, a cast) therefore fails loudly
     instead of reading tcn0's activation as gcn0's.  Falls back to the two-stage path whenever the fused
-    kernel does not cover the shape, under nn.DataParallel replicas, or with batch-statistics BatchNorm.
+    kernel does not cover the shape, or with batch-statistics BatchNorm.  nn.DataParallel replicas of ``gcn``
+    take the fused path on their own devices, with ``tcn``'s weights staged for each device.
     """
     object.__setattr__(gcn, "_fused_tcn", tcn)
 
