@@ -144,8 +144,8 @@ bool stem_v4_supported(int Cin, int C, int T, int V, int K, int S, unsigned flag
 int launch_stem_v4(const float *x, bool x_ntvc, const float *feat, const void *prep_w12, const void *Wp, const float *shift,
                    void *out, int N, int C, int T, int V, int K, unsigned flags, hipStream_t st);  // honours STGCN_OUT_NTVC
 
-// the same tile with ONE WAVE PER SIMD on v_mfma_f32_16x16x32_bf16 (stem_bf16_v6.hip: 256 threads, a wave owns all 128
-// channels of 64 pixels), on pair-order temporal weights
+// the same tile with ONE WAVE PER SIMD on v_mfma_f32_16x16x32_bf16 (kernel in kf6.h, narrow form instantiated by
+// stem_bf16_v6.hip: 256 threads, a wave owns all 128 channels of 64 pixels), on pair-order temporal weights
 bool stem_v6_supported(int C, int T, int V, int K, unsigned flags);
 // ... and for wide frames (32 < V <= 64, V even: the two-hand graph) the same kernel over the two joint halves [0, V0) and
 // [V0, V), each handled like a narrow clip (stem_bf16_v6w.hip)

@@ -1,6 +1,6 @@
 // KF7 — the fused stem with the temporal conv as  fp16 x fp16  +  two block-scaled e4m3 residual products
 // (STGCN_STEM_F16MX on top of STGCN_MATH_BF16X3): same tile, LDS images, feature phase, producer MFMAs, weight ring and
-// epilogue as KF6 (stem_bf16_v6.hip: read that file first), with the three bf16 terms of a product replaced by
+// epilogue as KF6 (kf6.h: read that first), with the three bf16 terms of a product replaced by
 //
 //     W y  =  Wh yh            v_mfma_f32_16x16x32_f16      K = 32 per instruction (a pair of k-steps), 16 cycles
 //           + Wl y8 + W8 r8    v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 x e4m3), K = 128 per instruction, 32 cycles
@@ -27,33 +27,12 @@
 // Scales: K1 leaves max|x| and max|x| * (largest column abs-sum of each attention matrix) per clip, stgcn_stem_prepare the
 // largest row abs-sums of the folded graph-conv matrix per feature group: their product bounds every |y| the producer can
 // emit, so the pre-scaled values stay below e4m3's 448 by construction (no saturation path), whatever the input's units.
-#include <type_traits>
-
-#include "bf16_common.h"
-
+#include "kf6.h"
 
 namespace stgcn {
 
 namespace {
 
-// max(x, 0) as ONE v_max_f32 (fmaxf canonicalises its operand first: a second v_max per element in the producer's slots)
-__device__ __forceinline__ float relu1(float x) {
-    float r;
-    asm("v_max_f32_e32 %0, 0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-
-using namespace bf16k;
-
-constexpr int NP6 = 256;   // output pixels per tile
-constexpr int NT6 = 256;   // threads per workgroup: one wave per SIMD
-constexpr int KT6 = 9;     // temporal taps
-constexpr int FRAG6 = 1024;
-constexpr int PAIR6 = 16 * FRAG6;   // weights of one pair: 8 blocks of 16 channels x (hi, lo)
-constexpr int RING6 = 3 * PAIR6;
-constexpr int EPI6 = 4096; // epilogue staging per wave: 16 channels x 64 pixels fp32
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using i32x8 = __attribute__((ext_vector_type(8))) int;
 
@@ -65,36 +44,6 @@ constexpr int hi_index_reg(int s) { return s < 4 ? s : 4 + 2 * ((s - 4) / 3) + (
 constexpr bool mx_slot_t8(int s) { return s >= 4 && (s >= 88 || (s - 4) % 3 != 2); }
 constexpr int mx_index_t8(int s) { return s >= 88 ? 56 + (s - 88) : 2 * ((s - 4) / 3) + (s - 4) % 3; }
 constexpr int hi_index_t8(int s) { return s < 4 ? s : 4 + (s - 4) / 3; }
-typedef __attribute__((address_space(3))) void *lptr6_t;
-
-__device__ __forceinline__ void dma16v6(const void *g, unsigned lds_addr) {
-    // M0 = LDS destination (wave-uniform).  M0 is declared clobbered instead of saved and restored around every transfer:
-    // nothing else in these kernels lives in M0, and the three extra scalar instructions per transfer are not free when a
-    // single wave owns the SIMD (they sit in the MFMA stream).
-    const unsigned lds = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds) : "memory", "m0");
-}
-__device__ __forceinline__ void dma_wait6() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void dma_wait6_keep4() { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-
-struct FragB6 { uint4 hi[4], lo[4]; };     // activations of one pair: 4 pixel blocks of 16
-
-// compile-time loop: f(std::integral_constant<int, I>{}) for I = I0 .. N-1
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for6(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for6<I + 1, N>(f);
-    }
-}
-
-
-struct TileInfo6 {
-    int n, Vh, j0, half;
-    TileGeomB g;
-};
-
-// WIDE: V0 = joints of the first half, tpc1 = tiles of a clip's second half (tiles_per_clip counts both halves)
 template <bool BF16OUT>
 __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
     const uint4 *__restrict__ pfrag, const float *__restrict__ x, int xsc, int xsp, const float *__restrict__ W12,
@@ -102,15 +51,8 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
     int tiles_per_clip, int ntiles, int abl, unsigned long long *dbg, const float *__restrict__ meta,
     const float *__restrict__ bounds) {
     constexpr int TERMS = 3;                 // (LDS budget of the three-image form: fp16 image + two fp8 images = 64 B per row)
-    constexpr bool WIDE = false;
-    const int V0 = 0, tpc1 = 0;
-#ifdef STGCN_ABLATION  // in-kernel cycle stamps (diagnostic builds only; dbg == NULL otherwise)
-#define V6_STAMP(var) unsigned long long var = 0; if (dbg) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); }
-#define V6_ACC(slot, a, b) if (dbg) { tsum[slot] += (b) - (a); }
+#ifdef STGCN_ABLATION
     unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#else
-#define V6_STAMP(var)
-#define V6_ACC(slot, a, b)
 #endif
     extern __shared__ __attribute__((aligned(16))) char smem6[];
     const int tid = threadIdx.x;
@@ -120,16 +62,14 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
     const int nch = C / CCB;                 // channel chunks (C = 128 -> 8)
     const int npairs = nch * KT6 / 2;        // K = 32 steps per tile (nch even: host side)
     const int img_bytes = ROWS * PXB;
-    const int buf_bytes = img_bytes * (TERMS == 3 ? 2 : 1);
+    const int buf_bytes = img_bytes * 2;
     // LDS carve: W12 (bf16 hi/lo) | weight ring (3 pairs) | images buf0, buf1 (= epilogue staging, 4 x 4 KiB) | Fs | Pf
     uint4 *W12q = reinterpret_cast<uint4 *>(smem6);
     char *ring = smem6 + C * W12P * 4;
     char *buf0 = ring + RING6;
     char *buf1 = buf0 + buf_bytes;
     uint4 *Fs = reinterpret_cast<uint4 *>(buf0 + max(2 * buf_bytes, 4 * EPI6));
-    // WIDE, three-term arithmetic: the half's 24 fragments (24 KiB) sit in the second image buffer, which is idle from the
-    // end of a tile's main loop to the next tile's first period (the budget has no 24 KiB of its own)
-    const uint4 *Pf = (WIDE && TERMS == 3) ? reinterpret_cast<const uint4 *>(buf1) : Fs + 4 * ROWS;
+    const uint4 *Pf = Fs + 4 * ROWS;
     const unsigned lds0 = (unsigned)(size_t)(lptr6_t)smem6;
     const unsigned ring_lds = lds0 + (unsigned)(ring - smem6);
     const unsigned pf_lds = lds0 + (unsigned)(reinterpret_cast<const char *>(Pf) - smem6);
@@ -144,91 +84,40 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         const int bw = d >> 1, img = d & 1;
         dma16v6(wsrc + ((size_t)(bw * npairs + qsrc) * 2 + img) * 64, ring_lds + slot * PAIR6 + ((2 * wave + bw) * 2 + img) * FRAG6);
     };
-    // tile -> clip, joint half and geometry.  WIDE: a clip's tiles alternate between the halves (half-0 tile i, half-1 tile i,
-    // ...; the first half may own one more), so that the two column halves of a frame range are written close in time
-    auto tile_info = [&](int tile) {
-        TileInfo6 ti;
-        ti.n = tile / tiles_per_clip;
-        const int r = tile - ti.n * tiles_per_clip;
-        int idx;
-        if (r < 2 * tpc1) { ti.half = r & 1; idx = r >> 1; }
-        else { ti.half = 0; idx = r - tpc1; }
-        ti.Vh = ti.half ? V - V0 : V0;
-        ti.j0 = ti.half ? V0 : 0;
-        ti.g = tile_geom_b(idx, ti.Vh, KT6, 1, T, NP6);
-        return ti;
-    };
-    auto dma_pfrag = [&](int tile) {         // 12 KiB: the clip's attention fragments -> Pf  (WIDE: the half's 24 KiB)
-        if constexpr (WIDE) {
-            const TileInfo6 ti = tile_info(tile);
-            const uint4 *src = pfrag + ((size_t)ti.n * 48 + ti.half * 24) * 64 + lane;
+    auto dma_pfrag = [&](int tile) {         // 12 KiB: the clip's attention fragments -> Pf
+        const int n = tile / tiles_per_clip;
+        const uint4 *src = pfrag + (size_t)n * 12 * 64 + lane;
 #pragma unroll
-            for (int i = 0; i < 6; ++i) dma16v6(src + (wave + 4 * i) * 64, pf_lds + (wave + 4 * i) * FRAG6);
-        } else {
-            const int n = tile / tiles_per_clip;
-            const uint4 *src = pfrag + (size_t)n * 12 * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) dma16v6(src + (wave + 4 * i) * 64, pf_lds + (wave + 4 * i) * FRAG6);
-        }
+        for (int i = 0; i < 3; ++i) dma16v6(src + (wave + 4 * i) * 64, pf_lds + (wave + 4 * i) * FRAG6);
     };
 
     // ---- features of a tile from x and the clip's attention fragments (see stem_bf16_v4.hip, FK form) -------------
-    struct XRegs { float xa[WIDE ? 16 : 8]; float xp[3]; };
+    struct XRegs { float xa[8]; float xp[3]; };
     auto load_x = [&](XRegs &xr, int tile, int u) {
         int ln = tid & 63;                   // opaque per call: keeps lane-only address terms from being hoisted and spilled
         asm volatile("" : "+v"(ln));
         const int mb = u >> 1, hh = u & 1;
-        TileInfo6 ti;
-        if constexpr (WIDE) ti = tile_info(tile);
-        else {
-            ti.n = tile / tiles_per_clip;
-            ti.g = tile_geom_b(tile - ti.n * tiles_per_clip, V, KT6, 1, T, NP6);
-        }
-        const int n = ti.n;
-        const TileGeomB g = ti.g;
+        const int n = tile / tiles_per_clip;
+        const TileGeomB g = tile_geom_b(tile - n * tiles_per_clip, V, KT6, 1, T, NP6);
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float *>(x + (size_t)n * 3 * TV), 0, (unsigned)(3 * TV * 4), 0x00020000);
         const int tf = g.t_first - (KT6 - 1) / 2 + 4 * mb;
-        if constexpr (WIDE) {
-            // (every offset is computed unconditionally and made opaque before the select: with the product inside the
-            //  conditional hipcc turns each of the 19 selects into a branch around its load)
+        {
             const int k = ln & 3, t = tf + ((ln & 15) >> 2), v0 = 8 * (ln >> 4);
-            const bool okr = (k < 3) & (t >= 0) & (t < T);
-            unsigned base = (unsigned)((k * xsc + (t * V + v0) * xsp) * 4);
-            asm volatile("" : "+v"(base));
+            const bool okr = k < 3 && t >= 0 && t < T;
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {     // joints 0-31 and 32-63: the two k-steps of the aggregation
-                const int dv = (j & 7) + 32 * (j >> 3);
-                const unsigned off = (okr & (v0 + dv < V)) ? base + (unsigned)(dv * xsp * 4) : 0x7ffffff0u;   // (&: no short-circuit branch)
+            for (int j = 0; j < 8; ++j) {
+                const unsigned off = (okr && v0 + j < V) ? (unsigned)((k * xsc + (t * V + v0 + j) * xsp) * 4) : 0x7ffffff0u;
                 xr.xa[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
             }
-            const int t2 = tf + (ln >> 4), w = 16 * hh + (ln & 15);        // w: column within the half
-            const bool ok = (t2 >= 0) & (t2 < T) & (w < ti.Vh);
-            unsigned base2 = (unsigned)(((t2 * V + ti.j0 + w) * xsp) * 4);
-            asm volatile("" : "+v"(base2));
+        }
+        {
+            const int t = tf + (ln >> 4), w = 16 * hh + (ln & 15);
+            const bool ok = t >= 0 && t < T && w < V;
 #pragma unroll
-            for (int k2 = 0; k2 < 3; ++k2) {
-                const unsigned off = ok ? base2 + (unsigned)(k2 * xsc * 4) : 0x7ffffff0u;
-                xr.xp[k2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
-            }
-        } else {
-            {
-                const int k = ln & 3, t = tf + ((ln & 15) >> 2), v0 = 8 * (ln >> 4);
-                const bool okr = k < 3 && t >= 0 && t < T;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const unsigned off = (okr && v0 + j < V) ? (unsigned)((k * xsc + (t * V + v0 + j) * xsp) * 4) : 0x7ffffff0u;
-                    xr.xa[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
-                }
-            }
-            {
-                const int t = tf + (ln >> 4), w = 16 * hh + (ln & 15);
-                const bool ok = t >= 0 && t < T && w < V;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const unsigned off = ok ? (unsigned)((k * xsc + (t * V + w) * xsp) * 4) : 0x7ffffff0u;
-                    xr.xp[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
-                }
+            for (int k = 0; k < 3; ++k) {
+                const unsigned off = ok ? (unsigned)((k * xsc + (t * V + w) * xsp) * 4) : 0x7ffffff0u;
+                xr.xp[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
             }
         }
     };
@@ -238,29 +127,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         asm volatile("" : "+v"(ln));
         const int mb = u >> 1, hh = u & 1;
         f32x4 d[3];
-        if constexpr (WIDE) {
-            float xk[2][8];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) xk[j >> 3][j & 7] = xr.xa[j];
-#pragma unroll
-            for (int s = 0; s < 3; ++s) d[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                uint4 xh, xl;
-                split8(xk[ks], xh, xl);
-                const bf16x8 ah = __builtin_bit_cast(bf16x8, xh), al = __builtin_bit_cast(bf16x8, xl);
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    const int f = ((s * 2 + hh) * 2 + ks) * 2;
-                    const bf16x8 bh = __builtin_bit_cast(bf16x8, Pf[(f + 0) * 64 + ln]);
-                    const bf16x8 bl = __builtin_bit_cast(bf16x8, Pf[(f + 1) * 64 + ln]);
-                    d[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bl, d[s], 0, 0, 0);
-                    d[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, d[s], 0, 0, 0);
-                    d[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, d[s], 0, 0, 0);
-                    d[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, d[s], 0, 0, 0);
-                }
-            }
-        } else {
+        {
             uint4 xh, xl;
             split8(xr.xa, xh, xl);
             const bf16x8 ah = __builtin_bit_cast(bf16x8, xh), al = __builtin_bit_cast(bf16x8, xl);
@@ -275,7 +142,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
                 d[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, d[s], 0, 0, 0);
             }
         }
-        const int Vh = ti.Vh;                                 // joints of this tile's pixel space (= V unless WIDE)
+        const int Vh = ti.Vh;                                 // joints of this tile's pixel space
         const int w = 16 * hh + (ln & 15);
         const int p = (4 * mb + (ln >> 4)) * Vh + w;         // pixel row of the tile
         const int gi = g.origin + p;
@@ -294,16 +161,13 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
             Fs[(size_t)3 * ROWS + p] = lb;
         }
     };
-    // units wave, wave+4, wave+8 arrive prefetched; any further ones (narrow frames only) are loaded here
+    // units wave, wave+4, wave+8 arrive prefetched; any further ones are loaded here
     auto feature_phase = [&](int tile, const XRegs &x0, const XRegs &x1, const XRegs &x2) {
         TileInfo6 ti;
-        if constexpr (WIDE) ti = tile_info(tile);
-        else {
-            ti.n = tile / tiles_per_clip;
-            ti.Vh = V;
-            ti.j0 = ti.half = 0;
-            ti.g = tile_geom_b(tile - ti.n * tiles_per_clip, V, KT6, 1, T, NP6);
-        }
+        ti.n = tile / tiles_per_clip;
+        ti.Vh = V;
+        ti.j0 = ti.half = 0;
+        ti.g = tile_geom_b(tile - ti.n * tiles_per_clip, V, KT6, 1, T, NP6);
         const TileGeomB &g = ti.g;
         const int need = min(ROWS, ((g.span + 15) >> 4) << 4);       // rows the producer will read
         const int nun = (((need + ti.Vh - 1) / ti.Vh + 3) >> 2) * 2; // M-blocks x 2 joint halves
@@ -335,17 +199,6 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         pr.d = f32x4{0.f, 0.f, 0.f, 0.f};
         pr.d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, pr.wh), f, pr.d, 0, 0, 0);
         pr.d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, pr.wl), f, pr.d, 0, 0, 0);
-    };
-    // The same inside the slot-structured loop, with a VGPR destination: the result feeds VALU work, and through the
-    // builtin hipcc computed it in AGPRs and copied it out (4 v_accvgpr_read + an s_nop 6 per block).  As inline asm the
-    // hazard recogniser does not see the matrix-core write: the consumer sits four slots (>= 4 main MFMAs, 64+ cycles)
-    // further down, far beyond the 7 wait states a 4-pass MFMA result needs; the second MFMA accumulates onto the first
-    // with identical vDst / SrcC (back-to-back forwarding).
-    auto prod_mfma_slots = [&](Prod &pr) {
-        using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-        const u32x4 wh = __builtin_bit_cast(u32x4, pr.wh), wl = __builtin_bit_cast(u32x4, pr.wl), fb = __builtin_bit_cast(u32x4, pr.fb);
-        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(pr.d) : "v"(wh), "v"(fb));
-        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(pr.d) : "v"(wl), "v"(fb));
     };
     // split of one produced value: h = fp16 (round to nearest), residual v - h exact in fp32 and <= 2^-11 |v|; both v and the residual also as e4m3 after the tile's power-of-two pre-scales (sH, sL: no value can
     // exceed 256 of e4m3's 448 by the bound K1 and stgcn_stem_prepare supply)
@@ -386,24 +239,22 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         }
 #pragma unroll
         for (int d = 0; d < 4; ++d) { dma_frag(0, 0, d); dma_frag(1, 1, d); }
-        dma_wait6();
+        vm_wait_keep<0>();
         __syncthreads();                      // W12q, Pf(tile), weight pairs 0 and 1 landed
         if (tile < ntiles) feature_phase(tile, x0, x1, x2);
         __syncthreads();
     }
 
-    // ring bookkeeping without divisions: slot of the current pair, and (slot, source index) of the pair two ahead
-    int gq = 0, slot0 = 0, slot2 = 2, q2 = 2 % npairs;
+    // ring bookkeeping without divisions: slot of the current pair gq (the comments' running pair index), and (slot,
+    // source index) of pair gq + 2
+    int slot0 = 0, slot2 = 2, q2 = 2 % npairs;
     const int sel = lane >> 5, chh = (lane >> 4) & 1;   // B fragment lane groups: step of the pair, channel half
     for (; tile < ntiles; tile += gridDim.x) {
         TileInfo6 ti;
-        if constexpr (WIDE) ti = tile_info(tile);
-        else {
-            ti.n = tile / tiles_per_clip;
-            ti.Vh = V;
-            ti.j0 = ti.half = 0;
-            ti.g = tile_geom_b(tile - ti.n * tiles_per_clip, V, KT6, 1, T, NP6);
-        }
+        ti.n = tile / tiles_per_clip;
+        ti.Vh = V;
+        ti.j0 = ti.half = 0;
+        ti.g = tile_geom_b(tile - ti.n * tiles_per_clip, V, KT6, 1, T, NP6);
         const int n = ti.n;
         const TileGeomB g = ti.g;
         const int Vh = ti.Vh;
@@ -436,7 +287,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
             prod_mfma(pr);
             prod_finish(buf0, pr, sY);
         }
-        // LDS offsets of this lane's activation rows per tap, for the wave's FIRST 16-pixel block (see stem_bf16_v6.hip)
+        // LDS offsets of this lane's activation rows per tap, for the wave's FIRST 16-pixel block (see KF6 in kf6.h)
         unsigned boff[KT6];
         // ... and of its e4m3 rows: lane group g = lane >> 4 of a scaled MFMA carries taps 2g and 2g + 1 (16 channels = 16
         // bytes each); the tap-8 product of a period carries tap 8 of both chunks in lane group 0
@@ -464,7 +315,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         auto cat8 = [](const uint4 &a, const uint4 &b) {
             return i32x8{(int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y, (int)b.z, (int)b.w};
         };
-        // fp16 activation fragments of the pair with local steps l0 = 2*pi, l1 = l0 + 1 (as stem_bf16_v6.hip)
+        // fp16 activation fragments of the pair with local steps l0 = 2*pi, l1 = l0 + 1 (as KF6 in kf6.h)
         auto load_b = [&](FragB6 &b, auto l0_c, auto nb_c) {
             constexpr int l0 = decltype(l0_c)::value, l1 = l0 + 1, nb = decltype(nb_c)::value;
             const char *b0 = (l0 >= KT6 ? buf1 : buf0), *b1 = (l1 >= KT6 ? buf1 : buf0);
@@ -486,7 +337,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         i32x8 b8A[4], b8B[4];                 // two sets of e4m3 activation fragments (4 pixel blocks each), see the table below
         uint4 ah0n = rd(ring + slot0 * PAIR6 + lane * 16);
         i32x8 a8n = cat8(rd(ring + slot0 * PAIR6 + lane * 16 + 1 * FRAG6), rd(ring + slot0 * PAIR6 + lane * 16 + 3 * FRAG6));
-        static_for6<0, 4>([&](auto nb_c) {      // pair 0 of the tile (chunk 0 is complete)
+        static_for<0, 4>([&](auto nb_c) {      // pair 0 of the tile (chunk 0 is complete)
             constexpr int nb = decltype(nb_c)::value;
             load_b(b_cur, IC0{}, nb_c);
             b8A[nb] = load_b8(buf0, 0, nb);
@@ -495,7 +346,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         const int nper = nch / 2;
         for (int per = 0; per < nper; ++per) {
             if (per + 1 == nper && next_tile < ntiles) dma_pfrag(next_tile);   // Pf is idle after the tile's feature phase
-            static_for6<0, 9>([&](auto pi_c) {
+            static_for<0, 9>([&](auto pi_c) {
                 constexpr int pi = decltype(pi_c)::value;
                 constexpr int l0 = 2 * pi;
                 constexpr bool T8 = pi == 4;            // the pair that also carries the period's tap-8 residual products
@@ -532,7 +383,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
                 f16x2 ph01 = {}, ph23 = {};
                 float pv0 = 0.f, pv1 = 0.f, pv2 = 0.f, pv3 = 0.f;
                 int poff = 0, p8off = 0, py8 = 0, pl8 = 0;
-                // legacy filler v (0 .. 95): what stem_bf16_v6.hip places between its MFMAs, minus the lo-image work
+                // legacy filler v (0 .. 95): what KF6 (kf6.h) places between its MFMAs, minus the lo-image work
                 auto filler = [&](auto v_c) {
                     constexpr int v = decltype(v_c)::value;
                     if constexpr (v % 12 == 2 && v / 12 < 7) ah[(v / 12 + 1) & 1] = rd(aslot + ((v / 12 + 1) * 2) * FRAG6);
@@ -606,7 +457,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
                         if constexpr (u >= 52 && u < 60 && u % 2 == 0) b8A[(u - 52) / 2] = load_b8(buf1, 0, (u - 52) / 2);
                     }
                 };
-                static_for6<0, NS>([&](auto s_c) {
+                static_for<0, NS>([&](auto s_c) {
                     constexpr int s = decltype(s_c)::value;
                     constexpr bool mx = T8 ? mx_slot_t8(s) : mx_slot_reg(s);
                     if constexpr (!mx) {
@@ -629,34 +480,29 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
                                                                                        t8 ? scYh : scYl, 0, t8 ? scYl : scYh);
                         asm volatile("" : "+a"(acc[mb][nb]));
                     }
-                    static_for6<s * FPS, (s + 1) * FPS>(filler);
-                    static_for6<s * FPS, (s + 1) * FPS>(mxfill);
+                    static_for<s * FPS, (s + 1) * FPS>(filler);
+                    static_for<s * FPS, (s + 1) * FPS>(mxfill);
                     __builtin_amdgcn_sched_barrier(0);
                 });
                 b_cur = b_nxt;
                 V6_STAMP(t_s1)
                 V6_ACC((pi == 4 ? 6 : (pi == 0 ? 7 : (pi == 3 ? 5 : 4))), t_p0, t_s1)
-                dma_wait6();                  // pair gq+2's weights (issued early in this pair) have landed
+                vm_wait_keep<0>();                  // pair gq+2's weights (issued early in this pair) have landed
                 __syncthreads();              // ... and are visible; produced image rows are visible; slot gq%3 is free
                 V6_STAMP(t_s2)
                 V6_ACC(2, t_s1, t_s2)
-                ++gq;
                 slot0 = slot1;
                 slot2 = slot2 == 2 ? 0 : slot2 + 1;
                 q2 = q2 + 1 == npairs ? 0 : q2 + 1;
             });
         }
-        dma_wait6();                          // (the next tile's attention fragments)
+        vm_wait_keep<0>();                          // (the next tile's attention fragments)
         V6_STAMP(t_2)
         V6_ACC(1, t_1, t_2)
 
         // ---- epilogue: each 16-channel x 64-pixel block through this wave's 4 KiB staging slice, 16 B per lane ----------
         // D[row = channel 4*(lane>>4) + r][col = pixel lane&15] per 16x16 block.  Store addresses = scalar base + one
         // per-lane term; the last tile of a clip keeps per-lane bounds checks.
-        // WIDE: the second image buffer is idle from here on (every wave is past the last pair's barrier): the next tile's
-        // attention fragments go there now, land during the stores and are waited for in front of the feature phase
-        if constexpr (WIDE)
-            if (next_tile < ntiles) dma_pfrag(next_tile);
         XRegs xn0, xn1, xn2;                  // next tile's x: in flight while this tile's results are stored
         load_x(xn0, min(next_tile, ntiles - 1), wave);
         load_x(xn1, min(next_tile, ntiles - 1), wave + 4);
@@ -665,76 +511,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         float *stg = reinterpret_cast<float *>(buf0 + wave * EPI6);
         const int qw = g.q0 + wave * 64;
         const bool full = g.q0 + NP6 - 1 <= g.q_last;            // (scalar) every pixel of the tile lies inside the clip
-        if constexpr (WIDE) {
-            // half-space pixel q = t*Vh + v'  ->  pixel t*V + j0 + v' of the clip
-            auto clip_pixel = [&](int q) { const int t = q / Vh; return t * V + ti.j0 + (q - t * Vh); };
-            if (abl & OPT_OUT_NTVC) {
-                // (N,T,V,C): as the narrow form, with the four pixels a lane stores mapped one by one
-                unsigned pt[4];
-                bool pok[4];
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const int q = qw + it * 16 + (lane >> 2);
-                    pok[it] = q <= g.q_last;
-                    pt[it] = (unsigned)(clip_pixel(min(q, g.q_last)) * C + 4 * (lane & 3));
-                }
-#pragma unroll
-                for (int mb = 0; mb < 8; ++mb) {
-                    const int ob = cg * 128 + mb * 16;
-                    const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 4 * (lane >> 4));
-#pragma unroll
-                    for (int nb = 0; nb < 4; ++nb) {
-                        const int px = nb * 16 + (lane & 15);
-                        const float4 v = make_float4(fmaxf(fmaf(acc[mb][nb][0], osc, sh4.x), 0.f), fmaxf(fmaf(acc[mb][nb][1], osc, sh4.y), 0.f),
-                                                     fmaxf(fmaf(acc[mb][nb][2], osc, sh4.z), 0.f), fmaxf(fmaf(acc[mb][nb][3], osc, sh4.w), 0.f));
-                        *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
-                    }
-                    const size_t tbase = (size_t)n * TV * C + ob;            // scalar
-#pragma unroll
-                    for (int it = 0; it < 4; ++it) {
-                        const int idx = it * 64 + lane, px = idx >> 2, sl = idx & 3;
-                        const float4 v = *reinterpret_cast<const float4 *>(stg + px * 16 + ((sl ^ (px & 3)) << 2));
-                        if (pok[it]) {
-                            if constexpr (BF16OUT)
-                                *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + tbase + pt[it]) =
-                                    make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-                            else
-                                *reinterpret_cast<float4 *>(reinterpret_cast<float *>(y) + tbase + pt[it]) = v;
-                        }
-                    }
-                }
-            } else {
-                // (N,C,T,V): a lane owns ONE pair of pixels of the wave's 64 (2*(lane&31), +1: V, V0 and Vh are even, so a
-                // pair never straddles a frame or the halves and sits 8-byte aligned in the clip) and walks the 16 channel
-                // rows of a block two at a time: eight 8-byte stores per block
-                const int qp = qw + 2 * (lane & 31);
-                const bool pok = qp <= g.q_last;
-                const unsigned lterm = (unsigned)((lane >> 5) * TV + clip_pixel(min(qp, g.q_last)));
-#pragma unroll
-                for (int mb = 0; mb < 8; ++mb) {
-                    const int ob = cg * 128 + mb * 16;
-                    const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 4 * (lane >> 4));
-                    const float shv[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
-#pragma unroll
-                    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(fmaf(acc[mb][nb][r], osc, shv[r]), 0.f);
-                    const size_t tbase = ((size_t)n * C + ob) * TV;           // scalar
-#pragma unroll
-                    for (int it = 0; it < 8; ++it) {
-                        const float2 v = *reinterpret_cast<const float2 *>(stg + (it * 2 + (lane >> 5)) * 64 + 2 * (lane & 31));
-                        const size_t sbase = tbase + (size_t)(it * 2) * TV;    // scalar
-                        if (pok) {
-                            if constexpr (BF16OUT)
-                                *reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(y) + sbase + lterm) = pack_bf16x2(v.x, v.y);
-                            else
-                                *reinterpret_cast<float2 *>(reinterpret_cast<float *>(y) + sbase + lterm) = v;
-                        }
-                    }
-                }
-            }
-        } else if (abl & OPT_OUT_NTVC) {
+        if (abl & OPT_OUT_NTVC) {
             // (N,T,V,C): staged pixel-major [64 px][16 ch]: a lane's four channels of a pixel are one 16-byte slot
             // (slot XOR-swizzled by the pixel: conflict-free b128 accesses); a store then writes 16 pixels x 64 B
             const unsigned lterm = (unsigned)((lane >> 2) * C + 4 * (lane & 3));
@@ -802,11 +579,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
         }
         V6_STAMP(t_3)
         V6_ACC(3, t_2, t_3)
-        if (next_tile < ntiles) {             // its fragments landed at the last stage barrier, its x during the stores;
-            if constexpr (WIDE) {             // (WIDE: fragments issued at the head of this epilogue — landed, then visible)
-                dma_wait6();
-                __syncthreads();
-            }
+        if (next_tile < ntiles) {             // its fragments landed at the last stage barrier, its x during the stores
             feature_phase(next_tile, xn0, xn1, xn2);   // Fs lies behind the staging area: no barrier needed in front
             V6_STAMP(t_4)
             __syncthreads();                  // Fs complete, every wave's staging reads done (chunk 0 overwrites buf0)
@@ -817,27 +590,6 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
     if (dbg && lane == 0 && blockIdx.x < 8 && blockIdx.y == 0)
         for (int i = 0; i < 8; ++i) dbg[(blockIdx.x * 8 + wave) * 8 + i] = tsum[i];
 #endif
-}
-
-struct V7Plan {
-    int rows = 0, tiles_per_clip = 0;
-    size_t lds = 0;
-};
-
-inline bool plan_v7(int C, int T, int V, int K, V7Plan &pl) {
-    if (K != KT6 || C % 128 != 0 || V > 32) return false;
-    int dt = ceil_div(NP6 - 1, V);
-    if (dt > T - 1) dt = T - 1;
-    const int span = (dt + K) * V;
-    if (ceil_div(ceil_div(span, 16), 4) > 8) return false;   // producer: 3 + 3 + 2 blocks per wave and chunk
-    const int rows = (span + 15) / 16 * 16;
-    const size_t buf = (size_t)rows * PXB * 2;               // fp16 image + two e4m3 images = 64 B per row
-    const size_t img = 2 * buf > (size_t)4 * EPI6 ? 2 * buf : (size_t)4 * EPI6;
-    pl.lds = (size_t)C * W12P * 4 + RING6 + img + (size_t)rows * 64 + 12 * FRAG6;
-    if (pl.lds > (size_t)kLdsBytes) return false;
-    pl.rows = rows;
-    pl.tiles_per_clip = ceil_div(T * V, NP6);
-    return true;
 }
 
 // ---- weight packing ---------------------------------------------------------------------------------------------------
@@ -927,21 +679,14 @@ __global__ void f16mx_pack_kernel(const float *__restrict__ W, const float *__re
 }
 
 int launch_v7(const uint4 *pf, const float *x, int xsc, int xsp, const float *W12, const uint4 *Wq, const float *shift, void *y,
-              int N, int C, int T, int V, const V7Plan &pl, bool bf16out, int opt, int num_cu, const float *meta,
+              int N, int C, int T, int V, const V6Plan &pl, bool bf16out, int opt, int num_cu, const float *meta,
               const float *bounds, hipStream_t st) {
     const int ntiles = N * pl.tiles_per_clip;
     const dim3 grid(ntiles < num_cu ? ntiles : num_cu, C / 128, 1);
-    if (bf16out) {
-        auto kern = stem_f16mx_kernel<true>;
-        STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
-        hipLaunchKernelGGL(kern, grid, dim3(NT6), pl.lds, st, pf, x, xsc, xsp, W12, Wq, shift, y, C, T, V, pl.rows,
-                           pl.tiles_per_clip, ntiles, opt, debug_buffer(), meta, bounds);
-    } else {
-        auto kern = stem_f16mx_kernel<false>;
-        STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
-        hipLaunchKernelGGL(kern, grid, dim3(NT6), pl.lds, st, pf, x, xsc, xsp, W12, Wq, shift, y, C, T, V, pl.rows,
-                           pl.tiles_per_clip, ntiles, opt, debug_buffer(), meta, bounds);
-    }
+    auto kern = bf16out ? stem_f16mx_kernel<true> : stem_f16mx_kernel<false>;
+    STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
+    hipLaunchKernelGGL(kern, grid, dim3(NT6), pl.lds, st, pf, x, xsc, xsp, W12, Wq, shift, y, C, T, V, pl.rows,
+                       pl.tiles_per_clip, ntiles, opt, debug_buffer(), meta, bounds);
     STGCN_LAUNCH_CHECK("stem_f16mx_kernel");
     return STGCN_OK;
 }
@@ -950,8 +695,8 @@ int launch_v7(const uint4 *pf, const float *x, int xsc, int xsp, const float *W1
 
 bool stem_f16mx_supported(int C, int T, int V, int K, unsigned flags) {
     if ((flags & STGCN_MATH_MASK) != STGCN_MATH_BF16X3 || !(flags & STGCN_STEM_F16MX)) return false;
-    V7Plan pl;
-    return T >= 1 && plan_v7(C, T, V, K, pl);
+    V6Plan pl;
+    return T >= 1 && plan_v6_narrow(C, T, V, K, 3, pl);
 }
 
 // bytes of KF7's weights behind the other packings of the prep blob: 256-byte header (meta) + the pair-order blob
@@ -973,8 +718,8 @@ int launch_stem_f16mx(const float *x, bool x_ntvc, const void *pfrag, const void
                       const float *shift, void *out, int N, int C, int T, int V, int K, unsigned flags, hipStream_t st) {
     const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
     const int opt = (flags & STGCN_OUT_NTVC) ? OPT_OUT_NTVC : 0;
-    V7Plan pl;
-    if (!plan_v7(C, T, V, K, pl))
+    V6Plan pl;
+    if (!plan_v6_narrow(C, T, V, K, 3, pl))
         return fail(STGCN_ERR_UNSUPPORTED, "stem f16mx kernel does not cover C=%d T=%d V=%d K=%d", C, T, V, K);
     if ((size_t)3 * T * V * 4 >= ((size_t)1 << 31))
         return fail(STGCN_ERR_UNSUPPORTED, "stem f16mx: clip of T=%d V=%d exceeds a buffer resource", T, V);

@@ -1,4 +1,4 @@
-// K3v6 — the stand-alone temporal conv block (Unit2D: K = 9, stride 1) in KF6's form (stem_bf16_v6.hip): ONE WAVE PER SIMD
+// K3v6 — the stand-alone temporal conv block (Unit2D: K = 9, stride 1) in KF6's form (kf6.h): ONE WAVE PER SIMD
 // (256 threads; a wave owns all 128 output channels of 64 pixels) on v_mfma_f32_16x16x32_bf16, slot-structured loop, weights
 // through a ring of 3 pair slots filled by LDS-DMA two pairs ahead, accumulators pinned to the AGPR file.  Serves Unit2D.eval,
 // the training forward (raw mode) and the input gradient (this kernel on flipped weights).
@@ -13,45 +13,13 @@
 // with its first chunk in place, there is no chunk-0 phase, and the epilogue has its own 16 KiB of staging.
 // The input loads share vmcnt with the weight DMAs.  They are issued BEHIND the pair's four DMAs, and the pair ends with
 // s_waitcnt vmcnt(n) for its n input loads: the DMAs (older) have landed, the loads stay in flight across the barrier.
-#include <type_traits>
-
-#include "bf16_common.h"
+#include "kf6.h"
 
 namespace stgcn {
 
 namespace {
 
-using namespace bf16k;
-
-constexpr int NP6 = 256;   // output pixels per tile
-constexpr int NT6 = 256;   // threads per workgroup: one wave per SIMD
-constexpr int KT6 = 9;     // temporal taps
-constexpr int FRAG6 = 1024;
-constexpr int PAIR6 = 16 * FRAG6;   // weights of one pair: 8 blocks of 16 channels x (hi, lo)
-constexpr int RING6 = 3 * PAIR6;
-constexpr int EPI6 = 4096; // epilogue staging per wave: 16 channels x 64 pixels fp32
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) void *lptr6_t;
-
-__device__ __forceinline__ void dma16t6(const void *g, unsigned lds_addr) {
-    const unsigned lds = __builtin_amdgcn_readfirstlane(lds_addr);   // (M0 clobbered, not saved: see stem_bf16_v6.hip)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds) : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void vm_wait_keep() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-struct FragB6 { uint4 hi[4], lo[4]; };     // activations of one pair: 4 pixel blocks of 16
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for6(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for6<I + 1, N>(f);
-    }
-}
-
-// weight packing in pair order (stem_bf16_v6.hip), with the output channels padded to a multiple of 128 (64 -> 128: rows
+// weight packing in pair order (KF6's, stem_bf16_v6.hip), with the output channels padded to a multiple of 128 (64 -> 128: rows
 // beyond Cout are zero and never stored)
 __global__ void tcn_pack_pairs_padded_kernel(const float *__restrict__ W, const float *__restrict__ scale,
                                              unsigned short *__restrict__ Wq, int Cin, int Cout, int CoutP) {
@@ -115,7 +83,7 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
     const uint4 *wsrc = Wp + ((size_t)(cg * 8 + 2 * wave) * npairs * 2) * 64 + lane;
     auto dma_frag = [&](int qsrc, int slot, int d) {
         const int bw = d >> 1, img = d & 1;
-        dma16t6(wsrc + ((size_t)(bw * npairs + qsrc) * 2 + img) * 64, ring_lds + slot * PAIR6 + ((2 * wave + bw) * 2 + img) * FRAG6);
+        dma16v6(wsrc + ((size_t)(bw * npairs + qsrc) * 2 + img) * 64, ring_lds + slot * PAIR6 + ((2 * wave + bw) * 2 + img) * FRAG6);
     };
 
     // ---- input staging: this lane's four (pixel row, channel half) units of a chunk image -----------------------------
@@ -193,14 +161,15 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
     vm_wait_keep<32>();                       // the eight weight fragments have landed (the 32 input loads stay in flight)
     __syncthreads();
 
-    // ring bookkeeping without divisions: slot of the current pair, and (slot, source index) of the pair two ahead
-    int gq = 0, slot0 = 0, slot2 = 2, q2 = 2 % npairs;
+    // ring bookkeeping without divisions: slot of the current pair gq (the comments' running pair index), and (slot,
+    // source index) of pair gq + 2
+    int slot0 = 0, slot2 = 2, q2 = 2 % npairs;
     const int sel = lane >> 5, chh = (lane >> 4) & 1;   // B fragment lane groups: step of the pair, channel half
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int n = tile / tiles_per_clip;
         const TileGeomB g = tile_geom_b(tile - n * tiles_per_clip, V, KT6, 1, T, NP6);
         // LDS offsets of this lane's activation rows per tap, for the wave's first 16-pixel block (block nb sits nb*16*PXB
-        // bytes further: ds_read immediates; see stem_bf16_v6.hip)
+        // bytes further: ds_read immediates; see KF6 in kf6.h)
         unsigned boff[KT6];
         {
             const int q = g.q0 + wave * 64 + (lane & 15);
@@ -226,13 +195,13 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
         using IC0 = std::integral_constant<int, 0>;
         FragB6 b_cur = {}, b_nxt = {};
         uint4 ah0n = rd(ring + slot0 * PAIR6 + lane * 16), al0n = rd(ring + slot0 * PAIR6 + lane * 16 + FRAG6);
-        static_for6<0, 4>([&](auto nb_c) {      // pair 0 of the tile (its chunk 0 was stored during the previous tile)
+        static_for<0, 4>([&](auto nb_c) {      // pair 0 of the tile (its chunk 0 was stored during the previous tile)
             load_b(b_cur, IC0{}, nb_c, std::false_type{});
             if constexpr (TERMS == 3) load_b(b_cur, IC0{}, nb_c, std::true_type{});
         });
         const int nper = nch / 2;
         for (int per = 0; per < nper; ++per) {
-            static_for6<0, 9>([&](auto pi_c) {
+            static_for<0, 9>([&](auto pi_c) {
                 constexpr int pi = decltype(pi_c)::value;
                 constexpr int l0 = 2 * pi;
                 // staging windows: pairs 0-2 store the held element into buf1, pairs 5-7 the next one into buf0; units
@@ -286,7 +255,7 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
                     if constexpr (v == 88) ah0n = rd(anext);
                     if constexpr (TERMS == 3 && v == 89) al0n = rd(anext + FRAG6);
                 };
-                static_for6<0, NM>([&](auto i_c) {
+                static_for<0, NM>([&](auto i_c) {
                     constexpr int i = decltype(i_c)::value;
                     constexpr int mb = i / (4 * TERMS), nb = (i / TERMS) % 4, term = i % TERMS;
                     const bf16x8 a_h = __builtin_bit_cast(bf16x8, ah[mb & 1]), b_h = __builtin_bit_cast(bf16x8, b_cur.hi[nb]);
@@ -299,14 +268,13 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
                         acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_h, b_h, acc[mb][nb], 0, 0, 0);
                     }
                     if constexpr (term == TERMS - 1) asm volatile("" : "+a"(acc[mb][nb]));   // accumulators live in AGPRs
-                    static_for6<i * (96 / NM), (i + 1) * (96 / NM)>(filler);
+                    static_for<i * (96 / NM), (i + 1) * (96 / NM)>(filler);
                     __builtin_amdgcn_sched_barrier(0);
                 });
                 b_cur = b_nxt;
                 // pair gq+2's weights have landed; this pair's input loads (issued behind them) stay in flight
                 vm_wait_keep<nun * 8>();
                 __syncthreads();              // ... weights and stored image rows are visible; slot gq%3 is free
-                ++gq;
                 slot0 = slot1;
                 slot2 = slot2 == 2 ? 0 : slot2 + 1;
                 q2 = q2 + 1 == npairs ? 0 : q2 + 1;
@@ -393,7 +361,7 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
                                 make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
                         else
                             {   // non-temporal (round 3: whole lines streamed past the L2 that serves the weight ring: -0.7 % on the
-                                // training step, -1 % on the two-stage eval path in same-box A/Bs; see stem_bf16_v6.hip)
+                                // training step, -1 % on the two-stage eval path in same-box A/Bs; see st_out4 in kf6.h)
                                 using f32x4v = __attribute__((ext_vector_type(4))) float;
                                 __builtin_nontemporal_store(f32x4v{v.x, v.y, v.z, v.w},
                                                             reinterpret_cast<f32x4v *>(reinterpret_cast<float *>(y) + sbase + lterm));

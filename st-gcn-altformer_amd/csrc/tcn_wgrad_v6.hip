@@ -15,9 +15,7 @@
 //     instructions that sit in the slots BEHIND the MFMAs of unit g — there is no staging phase; one barrier per unit;
 //   * fragment reads of the next tap group are issued before the current group's MFMAs.
 // Partial sums per workgroup, summed in a fixed order by sum_partials_kernel as before.
-#include <type_traits>
-
-#include "bf16_common.h"
+#include "kf6.h"
 
 namespace stgcn {
 
@@ -35,14 +33,6 @@ constexpr int WQ_LEAD = 4;       // lead-in units per clip: (WQ_WIN - WQ_TFM) / 
 constexpr int WQ_PITCH_A = 112;  // bytes per dz row of a unit: 2 frames x 48 B, 16 B x odd
 constexpr int WQ_PITCH_B = 784;  // bytes per input row: 16 slots x 48 B, 16 B x odd
 constexpr int WQ_FRB = 48;       // bytes per frame slot
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_forq(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_forq<I + 1, N>(f);
-    }
-}
 
 // NOB: 32-channel dz blocks per wave.  NOB = 1: wave w = block w, 32 input channels per workgroup.  NOB = 2: wave w = blocks
 // 2 (w & 1), +1 and input-channel block w >> 1 of a 64-channel group — every input fragment read then feeds two blocks: with
@@ -321,7 +311,7 @@ __global__ __launch_bounds__(WQ_THREADS) void tcn_wgrad_v6_kernel(const float *_
                 als[0][b] = ahs[0][b];
                 if constexpr (TERMS == 3) als[0][b] = *reinterpret_cast<const uint4 *>(acur + AIMG + a_lane + b * 32 * WQ_PITCH_A);
             }
-            static_forq<0, 9>([&](auto s_c) {                   // 9 MFMA groups: (k-step, tap group)
+            static_for<0, 9>([&](auto s_c) {                   // 9 MFMA groups: (k-step, tap group)
                 constexpr int s = decltype(s_c)::value, ks = s / 3, grp = s % 3, set = s & 1;
 #ifdef STGCN_ABLATION
                 unsigned long long t_g0 = 0;
@@ -384,11 +374,11 @@ __global__ __launch_bounds__(WQ_THREADS) void tcn_wgrad_v6_kernel(const float *_
                 };
                 // slot m: MFMA m — order (term, tap, block): consecutive MFMAs go to different accumulators (the three terms of
                 // one block are a dependent chain) — then fillers [m NF / NM, (m+1) NF / NM)
-                static_forq<0, NM>([&](auto m_c) {
+                static_for<0, NM>([&](auto m_c) {
                     constexpr int m = decltype(m_c)::value;
                     constexpr int term = TERMS == 3 ? m / (3 * NOB) : 2, kk = (m / NOB) % 3, b = m % NOB;
                     mfma1(std::integral_constant<int, kk>{}, std::integral_constant<int, b>{}, std::integral_constant<int, term>{});
-                    static_forq<m * NF / NM, (m + 1) * NF / NM>([&](auto f_c) { filler(f_c); });
+                    static_for<m * NF / NM, (m + 1) * NF / NM>([&](auto f_c) { filler(f_c); });
                     __builtin_amdgcn_sched_barrier(0);
                 });
 #ifdef STGCN_ABLATION
