@@ -12,6 +12,7 @@
  *   stgcn_stem_*                                <- model/AltFormer/ST_GCN_AltFormer.py:70-72
  *                                                  (tcn0(gcn0(x)) fused, intermediate kept on chip)
  *   stgcn_bn_fold                               <- eval-mode nn.BatchNorm2d at unit_agcn.py:54,60, net.py:40
+ *   stgcn_st_attention_*                        <- model/ST_TR/gcn_attention.py:96-156 (gcn_unit_attention.forward)
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer owned by the caller (e.g. the PyTorch caching
@@ -35,7 +36,7 @@
 extern "C" {
 #endif
 
-#define STGCN_ABI_VERSION 8
+#define STGCN_ABI_VERSION 9
 
 typedef enum {
     STGCN_OK = 0,
@@ -286,6 +287,46 @@ int stgcn_patch_embed(const float *z, const float *W, const float *b, const floa
 int stgcn_step_stats(const void *out, int out_is_bf16, float *stats, int N, int C, long clip_stride,
                      long chan_stride, float n_local, const float *logits, const long long *labels, long long *pred,
                      int n_logits, int classes, void *stream);
+
+/* ---- ST-TR spatial self-attention unit (gcn_unit_attention, ABI 9) ---------------------------------------------------
+ * model/ST_TR/gcn_attention.py:96-156 with spatial_transformer.py:82-156, in the configuration the reference's scripts
+ * build (only_attention, data_normalization, skip_conn, bn_flag, drop_connect; no relative / adjacency / more_channels):
+ *   xn = data_bn(x)   (BatchNorm1d over the Cin*V channels (c,v) of the (N, Cin*V, T) view: channel c*V + v)
+ *   qkv = Wqkv . xn + bqkv per frame, Wqkv (2dk+Cout, Cin); q, k, v and the heads are contiguous channel blocks
+ *   w = softmax over keys of (q_h * dkh^-0.5)^T k_h  (V x V per frame and head); training with drop-connect:
+ *       w = w*m[key] / (sum_key w*m[key] + 1e-8), mask m (N*T, heads, V) floats of 0 / 1 (NULL: no drop-connect)
+ *   o = heads of w . v_h^T concatenated (Cout channels);  z = Wout . o + bout (+ x when Cin == Cout), Wout (Cout, Cout)
+ *   y = relu(BatchNorm2d(z))
+ * x, y: (N,Cin,T,V) / (N,Cout,T,V).  dk = Cout/4 in the reference's configuration; covered: (dk/heads, Cout/heads) in
+ * {(4,16), (8,32), (16,64)} — Cout in {128, 256, 512} with 8 heads — any Cin, V <= 64 (else STGCN_ERR_UNSUPPORTED). */
+int stgcn_st_attention_supported(int Cin, int Cout, int dk, int V, int heads);
+/* workspace bytes of pass 0 = stgcn_st_attention_forward, 1 = _forward_train, 2 = _backward (0 for invalid sizes) */
+size_t stgcn_st_attention_ws_bytes(int N, int Cin, int Cout, int dk, int T, int V, int heads, int pass);
+/* Eval forward: both BatchNorms folded on their running statistics (stgcn_bn_fold; data_bn over Cin*V channels). */
+int stgcn_st_attention_forward(const float *x, const float *dbn_scale, const float *dbn_shift, const float *Wqkv,
+                               const float *bqkv, const float *Wout, const float *bout, const float *bn_scale,
+                               const float *bn_shift, void *ws, size_t ws_bytes, float *y, int N, int Cin, int Cout,
+                               int dk, int T, int V, int heads, void *stream);
+/* Training forward: batch statistics for both BatchNorms (running buffers updated like torch, with one momentum / eps for
+ * both), or with STGCN_BN_FROZEN the running statistics (nothing updated).  Saved for the backward: save_qkv
+ * (N,2dk+Cout,T,V), save_o (N,Cout,T,V), save_z (N,Cout,T,V), save_rowstats (N*T*heads*V float4: row max, sum of
+ * exponentials, drop-connect sum, 0), save_stats (2*Cin*V + 2*Cout floats: mean, invstd of data_bn, then of bn). */
+int stgcn_st_attention_forward_train(const float *x, const float *dbn_weight, const float *dbn_bias, float *dbn_running_mean,
+                                     float *dbn_running_var, const float *Wqkv, const float *bqkv, const float *Wout,
+                                     const float *bout, const float *bn_weight, const float *bn_bias,
+                                     float *bn_running_mean, float *bn_running_var, const float *mask, float momentum,
+                                     float eps, void *ws, size_t ws_bytes, float *y, float *save_qkv, float *save_o,
+                                     float *save_z, float *save_rowstats, float *save_stats, int N, int Cin, int Cout,
+                                     int dk, int T, int V, int heads, unsigned flags, void *stream);
+/* Backward from dy (N,Cout,T,V) with what the training forward saved (same flags and mask): the gradients of data_bn's
+ * weight / bias (Cin*V), Wqkv / bqkv, Wout / bout, bn's weight / bias, and dx (N,Cin,T,V; NULL when x needs none). */
+int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const float *dbn_bias, const float *Wqkv,
+                                const float *Wout, const float *bn_weight, const float *bn_bias, const float *mask,
+                                const float *save_qkv, const float *save_o, const float *save_z, const float *save_rowstats,
+                                const float *save_stats, const float *dy, float *dx, float *ddbn_weight, float *ddbn_bias,
+                                float *dWqkv, float *dbqkv, float *dWout, float *dbout, float *dbn_weight_grad,
+                                float *dbn_bias_grad, void *ws, size_t ws_bytes, int N, int Cin, int Cout, int dk, int T,
+                                int V, int heads, unsigned flags, void *stream);
 
 #ifdef __cplusplus
 }

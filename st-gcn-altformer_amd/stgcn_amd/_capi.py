@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STGCN_LIB") or os.path.join(_HERE, "libstgcn_hip.so")   # STGCN_LIB: diagnostic builds
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # stgcn_math / flags (include/stgcn_hip.h)
 MATH_F32 = 0
@@ -65,6 +65,12 @@ PROTOTYPES = {
     "stgcn_tcn_forward_train": (c_int, [_P] * 7 + [c_float, c_float, _P, c_size_t] + [_P] * 4 + [c_int] * 7 + [c_uint, _P]),
     "stgcn_tcn_backward_ws_bytes": (c_size_t, [c_int] * 7 + [c_uint]),
     "stgcn_tcn_backward_train": (c_int, [_P] * 13 + [_P, c_size_t] + [c_int] * 7 + [c_uint, _P]),
+    "stgcn_st_attention_supported": (c_int, [c_int] * 5),
+    "stgcn_st_attention_ws_bytes": (c_size_t, [c_int] * 8),
+    "stgcn_st_attention_forward": (c_int, [_P] * 10 + [c_size_t, _P] + [c_int] * 7 + [_P]),
+    "stgcn_st_attention_forward_train": (c_int, [_P] * 14 + [c_float, c_float, _P, c_size_t] + [_P] * 6 + [c_int] * 7
+                                         + [c_uint, _P]),
+    "stgcn_st_attention_backward": (c_int, [_P] * 24 + [c_size_t] + [c_int] * 7 + [c_uint, _P]),
 }
 
 _lib = None

@@ -437,3 +437,81 @@ class KernelTimer:
 
 
 kernel_timer: Optional[KernelTimer] = None
+
+
+# ---- ST-TR spatial self-attention unit (gcn_unit_attention) --------------------------------------------------------------
+def st_attention_supported(Cin, Cout, dk, V, heads) -> bool:
+    return bool(_capi.lib().stgcn_st_attention_supported(Cin, Cout, dk, V, heads))
+
+
+def _st_ws(dev, N, Cin, Cout, dk, T, V, heads, pass_):
+    nbytes = _capi.lib().stgcn_st_attention_ws_bytes(N, Cin, Cout, dk, T, V, heads, pass_)
+    return torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64), nbytes
+
+
+def st_attention_forward(x, dbn_scale, dbn_shift, Wqkv, bqkv, Wout, bout, bn_scale, bn_shift, dk, heads) -> torch.Tensor:
+    """Eval forward of gcn_unit_attention with both BatchNorms folded (data_bn over Cin*V channels).  Wqkv (2dk+Cout, Cin),
+    Wout (Cout, Cout).  Returns y (N,Cout,T,V)."""
+    dev = x.device
+    N, Cin, T, V = x.shape
+    Cout = Wout.shape[0]
+    ws, nbytes = _st_ws(dev, N, Cin, Cout, dk, T, V, heads, 0)
+    y = torch.empty(N, Cout, T, V, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_st_attention_forward", _dev_ptr(x, "x", dev), _dev_ptr(dbn_scale, "dbn_scale", dev),
+                   _dev_ptr(dbn_shift, "dbn_shift", dev), _dev_ptr(Wqkv, "Wqkv", dev), _dev_ptr(bqkv, "bqkv", dev),
+                   _dev_ptr(Wout, "Wout", dev), _dev_ptr(bout, "bout", dev), _dev_ptr(bn_scale, "bn_scale", dev),
+                   _dev_ptr(bn_shift, "bn_shift", dev), c_void_p(ws.data_ptr()), c_size_t(nbytes), _dev_ptr(y, "y"),
+                   c_int(N), c_int(Cin), c_int(Cout), c_int(dk), c_int(T), c_int(V), c_int(heads), _stream(dev))
+    return y
+
+
+def st_attention_forward_train(x, data_bn, Wqkv, bqkv, Wout, bout, bn, mask, dk, heads, momentum=0.1, eps=BN_EPS,
+                               frozen=False):
+    """Training forward (batch statistics, or running ones with ``frozen``).  ``data_bn`` / ``bn``: (weight, bias,
+    running_mean, running_var); ``mask`` (N*T*heads*V) of 0 / 1, or None.  Returns (y, saved) with saved = dict of the
+    tensors stgcn_st_attention_backward reads."""
+    dev = x.device
+    N, Cin, T, V = x.shape
+    Cout = Wout.shape[0]
+    Cq = Wqkv.shape[0]
+    ws, nbytes = _st_ws(dev, N, Cin, Cout, dk, T, V, heads, 1)
+    f32 = dict(device=dev, dtype=torch.float32)
+    y = torch.empty(N, Cout, T, V, **f32)
+    sv = {"qkv": torch.empty(N, Cq, T, V, **f32), "o": torch.empty(N, Cout, T, V, **f32),
+          "z": torch.empty(N, Cout, T, V, **f32), "rowstats": torch.empty(N * T * heads * V, 4, **f32),
+          "stats": torch.empty(2 * Cin * V + 2 * Cout, **f32)}
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_st_attention_forward_train", _dev_ptr(x, "x", dev),
+                   *[_dev_ptr(t, "data_bn", dev) for t in data_bn], _dev_ptr(Wqkv, "Wqkv", dev), _dev_ptr(bqkv, "bqkv", dev),
+                   _dev_ptr(Wout, "Wout", dev), _dev_ptr(bout, "bout", dev), *[_dev_ptr(t, "bn", dev) for t in bn],
+                   _dev_ptr(mask, "mask", dev), c_float(momentum), c_float(eps), c_void_p(ws.data_ptr()), c_size_t(nbytes),
+                   _dev_ptr(y, "y"), *[_dev_ptr(sv[k], k) for k in ("qkv", "o", "z", "rowstats", "stats")], c_int(N),
+                   c_int(Cin), c_int(Cout), c_int(dk), c_int(T), c_int(V), c_int(heads),
+                   c_uint(_capi.BN_FROZEN if frozen else 0), _stream(dev))
+    return y, sv
+
+
+def st_attention_backward(x, dbn_weight, dbn_bias, Wqkv, Wout, bn_weight, bn_bias, mask, saved, dy, dk, heads,
+                          need_dx=True, frozen=False):
+    """Backward of st_attention_forward_train.  Returns a dict: dx (or None), ddbn_weight, ddbn_bias (Cin*V), dWqkv, dbqkv,
+    dWout, dbout, dbn_weight, dbn_bias."""
+    dev = x.device
+    N, Cin, T, V = x.shape
+    Cout = Wout.shape[0]
+    ws, nbytes = _st_ws(dev, N, Cin, Cout, dk, T, V, heads, 2)
+    g = {"dx": torch.empty_like(x) if need_dx else None,
+         "ddbn_weight": torch.empty_like(dbn_weight), "ddbn_bias": torch.empty_like(dbn_bias),
+         "dWqkv": torch.empty_like(Wqkv), "dbqkv": torch.empty(Wqkv.shape[0], device=dev, dtype=torch.float32),
+         "dWout": torch.empty_like(Wout), "dbout": torch.empty(Cout, device=dev, dtype=torch.float32),
+         "dbn_weight": torch.empty_like(bn_weight), "dbn_bias": torch.empty_like(bn_bias)}
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_st_attention_backward", _dev_ptr(x, "x", dev), _dev_ptr(dbn_weight, "dbn_weight", dev),
+                   _dev_ptr(dbn_bias, "dbn_bias", dev), _dev_ptr(Wqkv, "Wqkv", dev), _dev_ptr(Wout, "Wout", dev),
+                   _dev_ptr(bn_weight, "bn_weight", dev), _dev_ptr(bn_bias, "bn_bias", dev), _dev_ptr(mask, "mask", dev),
+                   *[_dev_ptr(saved[k], k, dev) for k in ("qkv", "o", "z", "rowstats", "stats")], _dev_ptr(dy, "dy", dev),
+                   *[_dev_ptr(g[k], k) for k in ("dx", "ddbn_weight", "ddbn_bias", "dWqkv", "dbqkv", "dWout", "dbout",
+                                                  "dbn_weight", "dbn_bias")],
+                   c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(N), c_int(Cin), c_int(Cout), c_int(dk), c_int(T),
+                   c_int(V), c_int(heads), c_uint(_capi.BN_FROZEN if frozen else 0), _stream(dev))
+    return g
