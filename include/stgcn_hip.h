@@ -13,6 +13,7 @@
  *                                                  (tcn0(gcn0(x)) fused, intermediate kept on chip)
  *   stgcn_bn_fold                               <- eval-mode nn.BatchNorm2d at unit_agcn.py:54,60, net.py:40
  *   stgcn_st_attention_*                        <- model/ST_TR/gcn_attention.py:96-156 (gcn_unit_attention.forward)
+ *   stgcn_vit_*                                 <- model/AltFormer/model_ST.py:18-88 (Mlp, Attention, Block; eval forward)
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer owned by the caller (e.g. the PyTorch caching
@@ -36,7 +37,7 @@
 extern "C" {
 #endif
 
-#define STGCN_ABI_VERSION 9
+#define STGCN_ABI_VERSION 10
 
 typedef enum {
     STGCN_OK = 0,
@@ -327,6 +328,40 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
                                 float *dWqkv, float *dbqkv, float *dWout, float *dbout, float *dbn_weight_grad,
                                 float *dbn_bias_grad, void *ws, size_t ws_bytes, int N, int Cin, int Cout, int dk, int T,
                                 int V, int heads, unsigned flags, void *stream);
+
+/* ---- AltFormer heads: transformer block (Block of model/AltFormer/model_ST.py:18-88 = model_TS.py, ABI 10) -----------
+ * Eval forward only (no dropout, no stochastic depth), tokens in rows, x (B, L, D) dense fp32:
+ *   x1 = x  + proj(MHA(LN1(x)))          qkv = LN1(x) Wqkv^T (+ bqkv), packed (B, L, 3, heads, hd) as nn.Linear writes it;
+ *   y  = x1 + fc2(GELU(fc1(LN2(x1))))    softmax over keys of scale * q k^T; GELU in its exact erf form.
+ * Weights are nn.Linear.weight as stored: (out_features, in_features), in_features contiguous.
+ * `flags`: low 4 bits STGCN_MATH_F32 (v_mfma_f32_32x32x2_f32) or STGCN_MATH_BF16X3 (hi + lo split of both operands, three
+ * bf16 MFMAs, fp32 accumulate) for the linears; the attention itself always runs on the fp32 matrix cores. */
+#define STGCN_VIT_GELU 0x1000u    /* stgcn_vit_linear: exact GELU after the bias                                     */
+#define STGCN_VIT_QKV_F32 0x2000u /* stgcn_vit_block_forward: the qkv linear in f32 whatever the low bits say (an error
+                                   * in q or k is multiplied by the size of the scores before the exponential)        */
+/* y (M, Nout) = act(LN?(x) W^T + bias) (+ residual).  x (M, K), W (Nout, K).  bias, residual may be NULL; LayerNorm over
+ * the rows of x when ln_weight / ln_bias (K) are given (both or neither), biased variance, eps inside the root.
+ * Covered: any M, any Nout, K % 32 == 0, with LayerNorm K <= 4096; f32 or bf16x3 (else STGCN_ERR_UNSUPPORTED).
+ * y may alias residual, not x.  One launch: the row statistics are taken inside the workgroup that owns the rows. */
+int stgcn_vit_linear_supported(int M, int K, int Nout, unsigned flags);
+int stgcn_vit_linear(const float *x, const float *W, const float *bias, const float *ln_weight, const float *ln_bias,
+                     float ln_eps, const float *residual, float *y, int M, int K, int Nout, unsigned flags,
+                     void *stream);
+/* out (B, L, heads*head_dim) = concatenated heads of softmax(scale * q k^T) v, qkv (B, L, 3, heads, head_dim).
+ * Covered: head_dim in {32, 64}, 1 <= L <= 256, any B and heads (else STGCN_ERR_UNSUPPORTED).  One launch. */
+int stgcn_vit_attention_supported(int L, int heads, int head_dim);
+int stgcn_vit_attention(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream);
+/* One block.  Covered: head_dim = D / heads in {32, 64}, L <= 256, D and hidden multiples of 64, D <= 4096, any B (else
+ * STGCN_ERR_UNSUPPORTED).  bqkv may be NULL (qkv_bias=False); bproj, b1, b2 may be NULL too.  eps: both LayerNorms.
+ * ws: stgcn_vit_block_ws_bytes(B, L, D, hidden) bytes (bounded: the input is walked in slabs of whole sequences).
+ * y must not alias x.  Five launches per slab, no atomics: results are bit-identical from run to run. */
+int stgcn_vit_block_supported(int L, int D, int heads, int hidden);
+size_t stgcn_vit_block_ws_bytes(int B, int L, int D, int hidden);
+int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
+                            const float *bqkv, const float *Wproj, const float *bproj, const float *norm2_weight,
+                            const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,
+                            float eps, float scale, void *ws, size_t ws_bytes, float *y, int B, int L, int D, int heads,
+                            int hidden, unsigned flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,140 @@
+// C entry points of the AltFormer heads' transformer block (include/stgcn_hip.h, "ViT block", ABI 10): the linear and the
+// attention on their own, and the eval forward of one Block = five launches on one stream from a caller workspace:
+//   qkv = LN1(x) Wqkv^T + b -> attention -> x1 = a Wproj^T + b + x -> h = GELU(LN2(x1) W1^T + b1) -> y = h W2^T + b2 + x1
+// (both LayerNorms inside the linear that consumes them).
+// Long inputs are walked in slabs of whole sequences (kSlabRows tokens): the four intermediates of a slab (about 7 KB per
+// token at D = 256) then stay within reach of the caches between the launches that write and read them, and the
+// workspace does not grow with the batch.
+#include "vit.h"
+
+namespace stgcn {
+namespace vit {
+namespace {
+
+constexpr int kSlabRows = 32768;
+constexpr int kMaxLnDim = 4096;   // longest row a LayerNorm is fused over
+
+bool math_ok(unsigned flags) {
+    const unsigned m = flags & STGCN_MATH_MASK;
+    return m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3;
+}
+
+bool linear_ok(int K, int Nout, bool ln) { return K % 32 == 0 && Nout >= 1 && (!ln || K <= kMaxLnDim); }
+
+bool block_ok(int L, int D, int heads, int hidden) {
+    if (L < 1 || D < 1 || heads < 1 || hidden < 1 || D % heads != 0) return false;
+    const int hd = D / heads;
+    return (hd == 32 || hd == 64) && L <= kMaxL && D % 64 == 0 && hidden % 64 == 0 && D <= kMaxLnDim;
+}
+
+int slab_seqs(int B, int L) {
+    const int s = kSlabRows / L;
+    return s < 1 ? 1 : (s > B ? B : s);
+}
+
+struct BlockWs {
+    size_t qkv, att, x1, hid, total;
+    BlockWs(int B, int L, int D, int hidden) {
+        const size_t rows = (size_t)slab_seqs(B, L) * L;
+        size_t o = 0;
+        auto take = [&](size_t floats) {
+            const size_t at = o;
+            o += align_up(floats * sizeof(float), 256);
+            return at;
+        };
+        qkv = take(rows * 3 * D);
+        att = take(rows * D);
+        x1 = take(rows * D);
+        hid = take(rows * hidden);
+        total = o;
+    }
+};
+
+}  // namespace
+}  // namespace vit
+}  // namespace stgcn
+
+using namespace stgcn;
+using namespace stgcn::vit;
+
+extern "C" {
+
+int stgcn_vit_linear_supported(int M, int K, int Nout, unsigned flags) {
+    return M >= 1 && K >= 1 && math_ok(flags) && linear_ok(K, Nout, false) ? 1 : 0;
+}
+
+int stgcn_vit_linear(const float *x, const float *W, const float *bias, const float *ln_weight, const float *ln_bias,
+                     float ln_eps, const float *residual, float *y, int M, int K, int Nout, unsigned flags,
+                     void *stream) {
+    if (!x || !W || !y || M < 1 || K < 1 || Nout < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: null pointer or empty shape");
+    if ((ln_weight == nullptr) != (ln_bias == nullptr)) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: ln_weight and ln_bias go together");
+    if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: y must not alias x");
+    const bool ln = ln_weight != nullptr;
+    if (!math_ok(flags) || !linear_ok(K, Nout, ln))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_linear: K = %d, Nout = %d, math %u (covered: K %% 32 == 0, f32 / bf16x3)", K,
+                    Nout, flags & STGCN_MATH_MASK);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return launch_linear(x, W, bias, residual, ln_weight, ln_bias, ln_eps, y, M, K, Nout, (flags & STGCN_VIT_GELU) != 0,
+                         flags & STGCN_MATH_MASK, st);
+}
+
+int stgcn_vit_attention_supported(int L, int heads, int head_dim) {
+    return L >= 1 && L <= kMaxL && heads >= 1 && (head_dim == 32 || head_dim == 64) ? 1 : 0;
+}
+
+int stgcn_vit_attention(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream) {
+    if (!qkv || !out || B < 1 || L < 1 || heads < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_attention: null pointer or empty shape");
+    if (!stgcn_vit_attention_supported(L, heads, head_dim))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)", L,
+                    head_dim, kMaxL);
+    return launch_attention_packed(qkv, out, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
+}
+
+int stgcn_vit_block_supported(int L, int D, int heads, int hidden) { return block_ok(L, D, heads, hidden) ? 1 : 0; }
+
+size_t stgcn_vit_block_ws_bytes(int B, int L, int D, int hidden) {
+    if (B < 1 || L < 1 || D < 1 || hidden < 1) return 0;
+    return BlockWs(B, L, D, hidden).total;
+}
+
+int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
+                            const float *bqkv, const float *Wproj, const float *bproj, const float *norm2_weight,
+                            const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,
+                            float eps, float scale, void *ws, size_t ws_bytes, float *y, int B, int L, int D, int heads,
+                            int hidden, unsigned flags, void *stream) {
+    if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !y || !ws)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: null pointer");
+    if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: B = %d", B);
+    if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: y must not alias x");
+    if (!block_ok(L, D, heads, hidden) || !math_ok(flags))
+        return fail(STGCN_ERR_UNSUPPORTED,
+                    "stgcn_vit_block_forward: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
+                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxL);
+    const BlockWs w(B, L, D, hidden);
+    if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward: workspace %zu < %zu bytes", ws_bytes, w.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *base = static_cast<char *>(ws);
+    float *qkv = reinterpret_cast<float *>(base + w.qkv);
+    float *att = reinterpret_cast<float *>(base + w.att), *x1 = reinterpret_cast<float *>(base + w.x1);
+    float *hid = reinterpret_cast<float *>(base + w.hid);
+    const unsigned math = flags & STGCN_MATH_MASK;
+    const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : math;
+    const int per = slab_seqs(B, L);
+    for (int b0 = 0; b0 < B; b0 += per) {
+        const int nb = B - b0 < per ? B - b0 : per;
+        const int M = nb * L;
+        const float *xs = x + (size_t)b0 * L * D;
+        float *ys = y + (size_t)b0 * L * D;
+        int rc;
+        if ((rc = launch_linear(xs, Wqkv, bqkv, nullptr, norm1_weight, norm1_bias, eps, qkv, M, D, 3 * D, false, math_qkv, st)))
+            return rc;
+        if ((rc = launch_attention_packed(qkv, att, nb, L, heads, D / heads, scale, st))) return rc;
+        if ((rc = launch_linear(att, Wproj, bproj, xs, nullptr, nullptr, 0.f, x1, M, D, D, false, math, st))) return rc;
+        if ((rc = launch_linear(x1, W1, b1, nullptr, norm2_weight, norm2_bias, eps, hid, M, D, hidden, true, math, st)))
+            return rc;
+        if ((rc = launch_linear(hid, W2, b2, x1, nullptr, nullptr, 0.f, ys, M, hidden, D, false, math, st))) return rc;
+    }
+    return STGCN_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,241 @@
+// Token-major linear layer of the AltFormer heads' transformer blocks (model/AltFormer/model_ST.py:18-88):
+//     Y (M, Nout) = act(LN?(X) W^T + b) (+ R),   X (M, K) and W (Nout, K) both K-contiguous (nn.Linear.weight as stored).
+// These are plain large GEMMs (M = 126,720 tokens at batch 32, K = 256 or 512), so the tiling is the usual one and not
+// gemm_f32.hip's small strided-batched one: a workgroup of 4 waves owns a 128 x 128 tile of Y, each wave a 64 x 64 quarter
+// (2 x 2 MFMA blocks of 32 x 32, 64 accumulator registers), K in chunks of 32 through LDS with the next chunk's global
+// loads in flight while the current one multiplies.  Tiles are numbered with the Nout tiles fastest, so the workgroups
+// that share a 128-row slab of X run together and the slab is read from HBM once.
+//
+// Two arithmetics (STGCN_MATH_*):
+//   f32    : v_mfma_f32_32x32x2_f32 on the fp32 tiles (exact products, fp32 accumulate);
+//   bf16x3 : both tiles are split into bf16 hi + lo while they are staged (the weights too: the split of a 128 x 32 weight
+//            chunk is 16 values per thread and hides under the 24 MFMAs of the chunk, so there is no packed weight format
+//            and nothing to cache on the host), then lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16.
+// The k index inside a chunk is permuted the same way for both operands (a dot product does not care): lanes 0-31 of an
+// MFMA take the first half of the chunk / k-step and lanes 32-63 the second, so every fragment is a run of consecutive
+// LDS bytes read with 16-byte loads.  Row strides (36 floats, 40 bf16) make those loads bank-conflict free.
+//
+// LayerNorm: every workgroup first takes the (mean, rstd) of its 128 rows (see the kernel) and applies them to the A tile
+// between the global load and the LDS store, so the normalised tensor never exists in memory.
+// No atomics anywhere: one thread owns each output element and sums in a fixed order.
+#include "bf16_common.h"
+#include "vit.h"
+
+namespace stgcn {
+namespace vit {
+
+using bf16k::bf16_hi_to_f32;
+using bf16k::bf16_lo_to_f32;
+using bf16k::f32x16;
+using bf16k::Frag2;
+using bf16k::pack_bf16x2;
+
+namespace {
+
+constexpr int BM = 128, BN = 128, KC = 32;
+constexpr int LDF = KC + 4;  // fp32 tile row stride, floats
+constexpr int LDH = KC + 8;  // bf16 tile row stride, elements (80 bytes)
+
+__device__ __forceinline__ void split4(const float4 v, uint2 &hi, uint2 &lo) {
+    hi.x = pack_bf16x2(v.x, v.y);
+    hi.y = pack_bf16x2(v.z, v.w);
+    lo.x = pack_bf16x2(v.x - bf16_lo_to_f32(hi.x), v.y - bf16_hi_to_f32(hi.x));
+    lo.y = pack_bf16x2(v.z - bf16_lo_to_f32(hi.y), v.w - bf16_hi_to_f32(hi.y));
+}
+
+template <int MATH>
+struct Tiles;
+template <>
+struct Tiles<STGCN_MATH_F32> {
+    float a[BM * LDF];
+    float b[BN * LDF];
+};
+template <>
+struct Tiles<STGCN_MATH_BF16X3> {
+    unsigned short ah[BM * LDH], al[BM * LDH];
+    unsigned short bh[BN * LDH], bl[BN * LDH];
+};
+
+template <int MATH>
+__global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict__ X, const float *__restrict__ W,
+                                                        const float *__restrict__ bias, const float *R,
+                                                        const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                        float eps, float *Y, int M, int K, int Nout, int tiles_n,
+                                                        int gelu) {
+    __shared__ __attribute__((aligned(16))) Tiles<MATH> lds;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int n0 = ((int)blockIdx.x % tiles_n) * BN, m0 = ((int)blockIdx.x / tiles_n) * BM;
+    const int lr = tid >> 3, lc = (tid & 7) * 4;   // staging: rows lr + 32 i, floats lc .. lc + 3 of the chunk
+    const int l31 = lane & 31, half = lane >> 5;
+
+    // LayerNorm statistics of the tile's 128 rows, workgroup-local: the 8 threads that stage a row read it once (K is the
+    // whole row; it is about to be read again for the A tiles, so this pass mostly primes the cache), sum x - c and
+    // (x - c)^2 with c = the row's first element (no cancellation for rows with a large offset), and combine with three
+    // exchanges in a fixed order.  Every workgroup of a row slab repeats this; it replaces a pre-pass and its buffer.
+    const bool ln = gamma != nullptr;
+    float mean[4], rstd[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = m0 + lr + 32 * i;
+        float s = 0.f, q = 0.f, c = 0.f;
+        if (ln && row < M) {
+            const float4 *p = reinterpret_cast<const float4 *>(X + (size_t)row * K);
+            c = X[(size_t)row * K];
+            for (int j = tid & 7; j < (K >> 2); j += 8) {
+                const float4 v = p[j];
+                const float a = v.x - c, b = v.y - c, d = v.z - c, e = v.w - c;
+                s += (a + b) + (d + e);
+                q += (a * a + b * b) + (d * d + e * e);
+            }
+        }
+#pragma unroll
+        for (int o = 1; o <= 4; o <<= 1) {
+            s += __shfl_xor(s, o, 64);
+            q += __shfl_xor(q, o, 64);
+        }
+        const float ms = s / (float)K;
+        mean[i] = c + ms;
+        rstd[i] = 1.0f / sqrtf(fmaxf(q / (float)K - ms * ms, 0.f) + eps);
+    }
+
+    float4 xa[4], wb[4];
+    auto gload = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = m0 + lr + 32 * i, n = n0 + lr + 32 * i;
+            xa[i] = row < M ? *reinterpret_cast<const float4 *>(X + (size_t)row * K + k0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
+            wb[i] = n < Nout ? *reinterpret_cast<const float4 *>(W + (size_t)n * K + k0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto sstore = [&](int k0) {
+        float4 g = make_float4(1.f, 1.f, 1.f, 1.f), b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ln) {
+            g = *reinterpret_cast<const float4 *>(gamma + k0 + lc);
+            b = *reinterpret_cast<const float4 *>(beta + k0 + lc);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float4 v = xa[i];
+            if (ln) {
+                v.x = (v.x - mean[i]) * rstd[i] * g.x + b.x;
+                v.y = (v.y - mean[i]) * rstd[i] * g.y + b.y;
+                v.z = (v.z - mean[i]) * rstd[i] * g.z + b.z;
+                v.w = (v.w - mean[i]) * rstd[i] * g.w + b.w;
+            }
+            const int r = lr + 32 * i;
+            if constexpr (MATH == STGCN_MATH_F32) {
+                *reinterpret_cast<float4 *>(&lds.a[r * LDF + lc]) = v;
+                *reinterpret_cast<float4 *>(&lds.b[r * LDF + lc]) = wb[i];
+            } else {
+                uint2 hi, lo;
+                split4(v, hi, lo);
+                *reinterpret_cast<uint2 *>(&lds.ah[r * LDH + lc]) = hi;
+                *reinterpret_cast<uint2 *>(&lds.al[r * LDH + lc]) = lo;
+                split4(wb[i], hi, lo);
+                *reinterpret_cast<uint2 *>(&lds.bh[r * LDH + lc]) = hi;
+                *reinterpret_cast<uint2 *>(&lds.bl[r * LDH + lc]) = lo;
+            }
+        }
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
+
+    const int chunks = K / KC;
+    gload(0);
+    sstore(0);
+    __syncthreads();
+    for (int c = 0; c < chunks; ++c) {
+        const bool more = c + 1 < chunks;
+        if (more) gload((c + 1) * KC);
+        if constexpr (MATH == STGCN_MATH_F32) {
+            float a[2][16], b[2][16];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const float4 *ap = reinterpret_cast<const float4 *>(&lds.a[(wm * 64 + m * 32 + l31) * LDF + half * 16]);
+                const float4 *bp = reinterpret_cast<const float4 *>(&lds.b[(wn * 64 + m * 32 + l31) * LDF + half * 16]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float4 va = ap[j], vb = bp[j];
+                    a[m][4 * j] = va.x, a[m][4 * j + 1] = va.y, a[m][4 * j + 2] = va.z, a[m][4 * j + 3] = va.w;
+                    b[m][4 * j] = vb.x, b[m][4 * j + 1] = vb.y, b[m][4 * j + 2] = vb.z, b[m][4 * j + 3] = vb.w;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][s], b[n][s], acc[m][n], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < KC / 16; ++ks) {
+                Frag2<3> fa, fb;
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const int ao = (wm * 64 + m * 32 + l31) * LDH + ks * 16 + half * 8;
+                    const int bo = (wn * 64 + m * 32 + l31) * LDH + ks * 16 + half * 8;
+                    fa.hi[m] = *reinterpret_cast<const uint4 *>(&lds.ah[ao]);
+                    fa.lo[m] = *reinterpret_cast<const uint4 *>(&lds.al[ao]);
+                    fb.hi[m] = *reinterpret_cast<const uint4 *>(&lds.bh[bo]);
+                    fb.lo[m] = *reinterpret_cast<const uint4 *>(&lds.bl[bo]);
+                }
+                bf16k::mfma_kstep_bf16<3>(acc, fa, fb);
+            }
+        }
+        __syncthreads();
+        if (more) {
+            sstore((c + 1) * KC);
+            __syncthreads();
+        }
+    }
+
+    // epilogue: lane holds column n = l31 of each 32 x 32 block, rows 8 (i / 4) + 4 half + i % 4
+    constexpr float kRsqrt2 = 0.70710678118654752440f;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int col = n0 + wn * 64 + n * 32 + l31;
+        if (col >= Nout) continue;
+        const float bv = bias != nullptr ? bias[col] : 0.f;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = m0 + wm * 64 + m * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                if (row >= M) continue;
+                float v = acc[m][n][i] + bv;
+                if (gelu) v = 0.5f * v * (1.0f + erff(v * kRsqrt2));
+                const size_t idx = (size_t)row * Nout + col;
+                if (R != nullptr) v += R[idx];
+                Y[idx] = v;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+int launch_linear(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
+                  float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, hipStream_t st) {
+    const int tiles_n = ceil_div(Nout, BN);
+    const long long tiles = (long long)tiles_n * ceil_div(M, BM);
+    if (tiles > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit linear: %lld tiles", tiles);
+    const dim3 grid((unsigned)tiles), block(256);
+    if (math == STGCN_MATH_F32)
+        vit_linear_kernel<STGCN_MATH_F32><<<grid, block, 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, tiles_n, gelu);
+    else
+        vit_linear_kernel<STGCN_MATH_BF16X3><<<grid, block, 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, tiles_n,
+                                                                     gelu);
+    STGCN_LAUNCH_CHECK("vit_linear_kernel");
+    return STGCN_OK;
+}
+
+}  // namespace vit
+}  // namespace stgcn

@@ -1,7 +1,8 @@
 """ctypes binding of libstgcn_hip.so (C ABI declared in include/stgcn_hip.h).
 
 The library is the product: if it is missing or fails to load, every op raises — there is
-no CPU or PyTorch fallback anywhere in this package.
+no CPU or PyTorch fallback behind any entry point.  (Only the AltFormer head modules of
+altformer.py carry a torch-op path of their own, for autograd, CPU tensors and uncovered shapes.)
 """
 from __future__ import annotations
 
@@ -12,7 +13,7 @@ from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STGCN_LIB") or os.path.join(_HERE, "libstgcn_hip.so")   # STGCN_LIB: diagnostic builds
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # stgcn_math / flags (include/stgcn_hip.h)
 MATH_F32 = 0
@@ -28,6 +29,8 @@ EMBED_TS = 0x100  # stgcn_patch_embed: rows ordered (clip, joint, frame)
 BN_FROZEN = 0x200  # training entry points: BatchNorm on its running statistics (eval mode under autograd)
 STEM_F16MX = 0x400  # stem entry points, with MATH_BF16X3: fp16 x fp16 + two scaled-e4m3 residual products where KF7 covers the shape
 CONV_ALONG_V = 0x800  # stgcn_tcn_forward[_packed], MATH_F32_VALU: convolve along the joint axis (Unit2D(dim=3))
+VIT_GELU = 0x1000  # stgcn_vit_linear: exact GELU after the bias
+VIT_QKV_F32 = 0x2000  # stgcn_vit_block_forward: the qkv linear in f32 whatever the math bits say
 MATH_F16MX = MATH_BF16X3 | STEM_F16MX   # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
 
 STATUS = {0: "STGCN_OK", -1: "STGCN_ERR_ARG", -2: "STGCN_ERR_UNSUPPORTED",
@@ -71,6 +74,13 @@ PROTOTYPES = {
     "stgcn_st_attention_forward_train": (c_int, [_P] * 14 + [c_float, c_float, _P, c_size_t] + [_P] * 6 + [c_int] * 7
                                          + [c_uint, _P]),
     "stgcn_st_attention_backward": (c_int, [_P] * 24 + [c_size_t] + [c_int] * 7 + [c_uint, _P]),
+    "stgcn_vit_linear_supported": (c_int, [c_int] * 3 + [c_uint]),
+    "stgcn_vit_linear": (c_int, [_P] * 5 + [c_float] + [_P] * 2 + [c_int] * 3 + [c_uint, _P]),
+    "stgcn_vit_attention_supported": (c_int, [c_int] * 3),
+    "stgcn_vit_attention": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
+    "stgcn_vit_block_supported": (c_int, [c_int] * 4),
+    "stgcn_vit_block_ws_bytes": (c_size_t, [c_int] * 4),
+    "stgcn_vit_block_forward": (c_int, [_P] * 13 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
 }
 
 _lib = None

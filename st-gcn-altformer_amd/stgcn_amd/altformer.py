@@ -1,0 +1,335 @@
+"""The AltFormer transformer heads (``ST``: spatial blocks then temporal blocks, ``TS``: the other way round) and the whole
+``ST_GCN_AltFormer`` model, with the blocks' inference forward on libstgcn_hip.so.
+
+``Mlp``, ``Attention``, ``Block``, ``ST``, ``TS`` mirror model/AltFormer/model_ST.py and model_TS.py of the reference: the same
+constructor arguments, attribute names, ``state_dict`` keys, shapes and order, and the same RNG draws in the same order
+(``torch.manual_seed(s)`` followed by construction gives the reference's initial parameters; checkpoints load strictly).
+``timm`` and ``einops`` are not needed: stochastic depth is the local ``DropPath``, the rearranges are permutes.
+
+Two paths, one result:
+
+* HIP (``stgcn_vit_block_forward``): CUDA float32 input of a covered shape while autograd records nothing that concerns the
+  block (``torch.no_grad()``, or no input and no parameter requires a gradient), no dropout / stochastic depth is active, and
+  the call has at least ``HIP_MIN_TOKENS`` tokens (smaller calls are latency-bound; ``set_hip_min_tokens(model, 0)`` lifts it).
+  The head's first patch embedding then runs through ``functional.patch_embed`` on the stem output (contiguous or
+  channels-last, consumed in place); pooling, the second embedding and ``mlp_head`` are torch ops.
+* torch ops: everything else - training, ``.eval()`` with gradients, CPU tensors, shapes the kernels do not cover.  This is the
+  reference's arithmetic op for op, so its training scripts keep working unchanged.  (A HIP backward for the block is not
+  part of this module yet.)
+
+Arithmetic of the block's linears (``set_head_math`` / env ``STGCN_VIT_MATH``): ``'f32'`` (fp32 matrix cores, exact products),
+``'bf16x3'`` (three bf16 products per fp32 product, fp32 accumulate) or ``'mixed'`` (bf16x3 with the qkv linear in f32: an
+error in q or k is multiplied by the size of the scores before the exponential).  The attention itself is always fp32.
+
+Nothing is packed or cached: the kernels read ``nn.Linear.weight`` as stored, so an ``nn.DataParallel`` replica (whose
+parameters are plain attributes, fresh clones on every call) needs no staging on its master.
+"""
+from __future__ import annotations
+
+import os
+from functools import partial
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import functional as F
+from ._capi import MATH_BF16X3, MATH_F32, VIT_QKV_F32
+from .modules import Unit2D, enable_stem_fusion, import_class, unit_agcn
+
+HEAD_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32}
+DEFAULT_HEAD_MATH = "mixed"
+
+
+def _default_head_math() -> int:
+    return HEAD_MATH[os.environ.get("STGCN_VIT_MATH", DEFAULT_HEAD_MATH).lower()]
+
+
+HIP_MIN_TOKENS = 4096   # below this many tokens (B * L) per call a block's five launches are latency-bound and the library's
+#                         small GEMMs are as fast or faster (measured at batch 32: the TS head's spatial stage, 1472 and 704
+#                         tokens, 0.32 against 0.27 ms per block): the block then takes its torch path
+
+
+def set_hip_min_tokens(module: nn.Module, tokens: int) -> None:
+    """The token count (B * L) from which every ``Block`` below uses the HIP path where it applies (0: always)."""
+    for sub in module.modules():
+        if isinstance(sub, Block):
+            sub.hip_min_tokens = int(tokens)
+
+
+def set_head_math(module: nn.Module, mode) -> None:
+    """Arithmetic of the linears of every ``Block`` below: 'f32' | 'bf16x3' | 'mixed', or None for the default."""
+    m = None if mode is None else HEAD_MATH[mode] if isinstance(mode, str) else int(mode)
+    for sub in module.modules():
+        if isinstance(sub, Block):
+            sub.math_mode = m
+
+
+class DropPath(nn.Module):
+    """Stochastic depth per sample: in training each sample's branch is kept with probability ``1 - drop_prob`` and the kept
+    ones are scaled by ``1 / keep`` (one bernoulli draw of batch-size elements per call); identity in eval or at rate 0."""
+
+    def __init__(self, drop_prob: float = 0.0, scale_by_keep: bool = True):
+        super().__init__()
+        self.drop_prob = drop_prob
+        self.scale_by_keep = scale_by_keep
+
+    def forward(self, x):
+        if self.drop_prob == 0.0 or not self.training:
+            return x
+        keep = 1.0 - self.drop_prob
+        mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+        if keep > 0.0 and self.scale_by_keep:
+            mask.div_(keep)
+        return x * mask
+
+    def extra_repr(self):
+        return f"drop_prob={round(self.drop_prob, 3):0.3f}"
+
+
+class Mlp(nn.Module):
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
+        super().__init__()
+        self.fc1 = nn.Linear(in_features, hidden_features or in_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features or in_features, out_features or in_features)
+        self.drop = nn.Dropout(drop)
+
+    def forward(self, x):
+        return self.drop(self.fc2(self.drop(self.act(self.fc1(x)))))
+
+
+class Attention(nn.Module):
+    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        self.num_heads = num_heads
+        self.scale = qk_scale or (dim // num_heads) ** -0.5
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+
+    def forward(self, x):
+        B, L, D = x.shape
+        q, k, v = self.qkv(x).reshape(B, L, 3, self.num_heads, D // self.num_heads).permute(2, 0, 3, 1, 4).unbind(0)
+        w = self.attn_drop(((q @ k.transpose(-2, -1)) * self.scale).softmax(dim=-1))
+        return self.proj_drop(self.proj((w @ v).transpose(1, 2).reshape(B, L, D)))
+
+
+def _drop_active(mod: nn.Module) -> bool:
+    """Any dropout or stochastic depth below ``mod`` that would draw random numbers in this call."""
+    for sub in mod.modules():
+        if sub.training and ((isinstance(sub, nn.Dropout) and sub.p > 0) or (isinstance(sub, DropPath) and sub.drop_prob > 0)):
+            return True
+    return False
+
+
+class Block(nn.Module):
+    """``x + attn(norm1(x))`` then ``x + mlp(norm2(x))`` (each branch through ``drop_path``); x is (B, L, dim)."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop,
+                              proj_drop=drop)
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.math_mode = None                  # None: _default_head_math() at call time
+        self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
+        self.hip_min_tokens = HIP_MIN_TOKENS   # set_hip_min_tokens
+
+    def _weights(self):
+        """The parameters by attribute (an nn.DataParallel replica has no ``parameters()``)."""
+        for lin in (self.norm1, self.attn.qkv, self.attn.proj, self.norm2, self.mlp.fc1, self.mlp.fc2):
+            yield lin.weight
+            yield lin.bias
+
+    def hip_applies(self, x: torch.Tensor) -> bool:
+        """Whether this call runs on the HIP kernels (see the module docstring)."""
+        if self.force_torch or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
+            return False
+        if not (type(self.norm1) is nn.LayerNorm and type(self.norm2) is nn.LayerNorm and isinstance(self.mlp.act, nn.GELU)
+                and getattr(self.mlp.act, "approximate", "none") == "none" and self.norm1.elementwise_affine
+                and self.norm2.elementwise_affine and self.norm1.eps == self.norm2.eps
+                and self.norm1.bias is not None and self.norm2.bias is not None):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in self._weights())):
+            return False
+        if _drop_active(self):
+            return False
+        B, L, D = x.shape
+        if B < 1 or D != self.norm1.normalized_shape[0] or self.mlp.fc2.out_features != D:
+            return False
+        return F.vit_block_supported(L, D, self.attn.num_heads, self.mlp.fc1.out_features)
+
+    def uses_hip(self, x: torch.Tensor) -> bool:
+        """``hip_applies`` and the call is large enough for the HIP path to be the faster one (``hip_min_tokens``)."""
+        return x.dim() == 3 and x.shape[0] * x.shape[1] >= self.hip_min_tokens and self.hip_applies(x)
+
+    def forward(self, x):
+        if self.uses_hip(x):
+            a, m = self.attn, self.mlp
+            math = _default_head_math() if self.math_mode is None else self.math_mode
+            with torch.no_grad():
+                return F.vit_block_forward(x.contiguous(), (self.norm1.weight, self.norm1.bias), (a.qkv.weight, a.qkv.bias),
+                                           (a.proj.weight, a.proj.bias), (self.norm2.weight, self.norm2.bias),
+                                           (m.fc1.weight, m.fc1.bias), (m.fc2.weight, m.fc2.bias), a.num_heads, self.norm1.eps,
+                                           a.scale, math)
+        x = x + self.drop_path(self.attn(self.norm1(x)))
+        return x + self.drop_path(self.mlp(self.norm2(x)))
+
+
+def _embed_on_hip(x, lin) -> bool:
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and not (torch.is_grad_enabled() and (x.requires_grad or lin.weight.requires_grad or lin.bias.requires_grad)))
+
+
+class _Head(nn.Module):
+    """What ST and TS share: the construction after the two embeddings (so that the RNG draws keep the reference's order) and
+    the two stages of the forward."""
+
+    def _build_common(self, class_num, num_frame, embed_dim, spatial_dim, temporal_dim, depth, num_heads, mlp_ratio, qkv_bias,
+                      qk_scale, drop_rate, attn_drop_rate, drop_path_rate, norm_layer):
+        self.pos_drop = nn.Dropout(p=drop_rate)
+        dpr = [r.item() for r in torch.linspace(0, drop_path_rate, depth)]
+
+        def stack(dim):
+            return nn.ModuleList([Block(dim=dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
+                                        drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[i], norm_layer=norm_layer)
+                                  for i in range(depth)])
+        self.Spatial_blocks = stack(spatial_dim)
+        self.blocks = stack(temporal_dim)
+        self.Spatial_norm = norm_layer(spatial_dim)       # in the state_dict, not in the forward (as in the reference)
+        self.Temporal_norm = norm_layer(temporal_dim)
+        self.pool = 'cls'
+        self.to_latent = nn.Identity()
+        self.weighted_mean = nn.Conv1d(in_channels=num_frame, out_channels=1, kernel_size=1)
+        self.mlp_head = nn.Sequential(nn.LayerNorm(embed_dim), nn.Linear(embed_dim, class_num))
+        self.fcn = nn.Conv1d(512, class_num, kernel_size=1)
+
+    def _first_stage(self, x, lin, pos, blocks, order):
+        """Stem output (N, C, T, V) -> rows (N*T, V, E) ('ST') or (N*V, T, E) ('TS') through the first embedding and blocks."""
+        if _embed_on_hip(x, lin):
+            with torch.no_grad():
+                x = F.patch_embed(x, lin.weight, lin.bias, pos, order=order)
+        else:
+            N, C, T, V = x.shape
+            rows = x.permute(0, 2, 3, 1).reshape(N * T, V, C) if order == "ST" else x.permute(0, 3, 2, 1).reshape(N * V, T, C)
+            x = lin(rows)
+            x += pos
+        x = self.pos_drop(x)
+        for blk in blocks:
+            x = blk(x)
+        return x
+
+    def _second_stage(self, x, lin, pos, blocks):
+        x = lin(x)
+        x += pos
+        x = self.pos_drop(x)
+        for blk in blocks:
+            x = blk(x)
+        return x
+
+
+class ST(_Head):
+    """Spatial blocks over the joints of every frame (dim ``embed_dim_ratio``), mean over joints, temporal blocks over the
+    frames (dim 2 * ``embed_dim_ratio``), max over frames, ``mlp_head``.  Input: the stem output (N, in_chans, T, V)."""
+
+    def __init__(self, class_num, num_frame=180, num_joints=22, in_chans=128, embed_dim_ratio=256, depth=4, num_heads=8,
+                 mlp_ratio=2., qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.2,
+                 norm_layer=None):
+        super().__init__()
+        self.class_num = class_num
+        norm_layer = norm_layer or partial(nn.LayerNorm, eps=1e-6)
+        embed_dim = embed_dim_ratio * 2
+        self.Spatial_patch_to_embedding = nn.Linear(in_chans, embed_dim_ratio)
+        self.Spatial_pos_embed = nn.Parameter(torch.zeros(1, num_joints, embed_dim_ratio))
+        self.Spatial_cls_token = nn.Parameter(torch.randn(1, 1, embed_dim_ratio))
+        self.Temporal_patch_to_embedding = nn.Linear(embed_dim_ratio, embed_dim)
+        self.Temporal_pos_embed = nn.Parameter(torch.zeros(1, num_frame, embed_dim))
+        self.cls_token = nn.Parameter(torch.randn(1, 1, embed_dim))
+        self._build_common(class_num, num_frame, embed_dim, embed_dim_ratio, embed_dim, depth, num_heads, mlp_ratio, qkv_bias,
+                           qk_scale, drop_rate, attn_drop_rate, drop_path_rate, norm_layer)
+
+    def Spatial_forward_features(self, x):
+        N, _, T, _ = x.shape
+        x = self._first_stage(x, self.Spatial_patch_to_embedding, self.Spatial_pos_embed, self.Spatial_blocks, "ST")
+        return x.mean(dim=1).reshape(N, T, -1)
+
+    def forward_features(self, x):
+        x = self._second_stage(x, self.Temporal_patch_to_embedding, self.Temporal_pos_embed, self.blocks)
+        feature = x.max(dim=1).values
+        return self.mlp_head(feature), feature.unsqueeze(-1)
+
+    def forward(self, x):
+        return self.forward_features(self.Spatial_forward_features(x))[0]
+
+
+class TS(_Head):
+    """Temporal blocks over the frames of every joint (dim ``embed_dim_ratio``), max over frames, spatial blocks over the joints
+    (dim 2 * ``embed_dim_ratio``), mean over joints, ``mlp_head``.  Input: the stem output (N, in_chans, T, V)."""
+
+    def __init__(self, class_num, num_frame=180, num_joints=22, in_chans=128, embed_dim_ratio=256, depth=4, num_heads=8,
+                 mlp_ratio=2., qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.2,
+                 norm_layer=None):
+        super().__init__()
+        self.class_num = class_num
+        norm_layer = norm_layer or partial(nn.LayerNorm, eps=1e-6)
+        embed_dim = embed_dim_ratio * 2
+        self.temporal_patch_to_embedding = nn.Linear(in_chans, embed_dim_ratio)
+        self.Temporal_pos_embed = nn.Parameter(torch.zeros(1, num_frame, embed_dim_ratio))
+        self.cls_token = nn.Parameter(torch.randn(1, 1, embed_dim_ratio))
+        self.Spatial_patch_to_embedding = nn.Linear(embed_dim_ratio, embed_dim)
+        self.Spatial_pos_embed = nn.Parameter(torch.zeros(1, num_joints, embed_dim))
+        self.Spatial_cls_token = nn.Parameter(torch.randn(1, 1, embed_dim))
+        self._build_common(class_num, num_frame, embed_dim, embed_dim, embed_dim_ratio, depth, num_heads, mlp_ratio, qkv_bias,
+                           qk_scale, drop_rate, attn_drop_rate, drop_path_rate, norm_layer)
+
+    def Temporal_forward_features(self, x):
+        N, _, _, V = x.shape
+        x = self._first_stage(x, self.temporal_patch_to_embedding, self.Temporal_pos_embed, self.blocks, "TS")
+        return x.max(dim=1).values.reshape(N, V, -1)
+
+    def Spatial_forward_features(self, x):
+        x = self._second_stage(x, self.Spatial_patch_to_embedding, self.Spatial_pos_embed, self.Spatial_blocks)
+        return self.mlp_head(x.mean(dim=1))
+
+    def forward(self, x):
+        return self.Spatial_forward_features(self.Temporal_forward_features(x))
+
+
+class ST_GCN_AltFormer(nn.Module):
+    """The whole model of model/AltFormer/ST_GCN_AltFormer.py: ``gcn0`` -> ``tcn0`` (the fused HIP stem) -> ``modelA`` (ST) and /
+    or ``modelB`` (TS), chosen by ``style`` ('ST', 'TS', anything else: the sum of both).  Input (N, T, V, channel) as the data
+    loader delivers it; the stem reads the permuted view in place."""
+
+    def __init__(self, channel, num_class, backbone_in_c=128, num_frame=180, num_joints=22, style=None, graph=None,
+                 graph_args=dict(), mask_learning=False, use_local_bn=False):
+        super().__init__()
+        if graph is None:
+            raise ValueError()
+        self.graph = import_class(graph)(**graph_args)
+        self.A = torch.from_numpy(self.graph.A.astype(np.float32))
+        self.num_frame = num_frame
+        self.num_joints = num_joints
+        self.num_class = num_class
+        self.backbone_in_c = backbone_in_c
+        self.style = style
+        self.gcn0 = unit_agcn(channel, backbone_in_c, self.A, mask_learning=mask_learning, use_local_bn=use_local_bn)
+        self.tcn0 = Unit2D(backbone_in_c, backbone_in_c, kernel_size=9)
+        head = dict(num_frame=num_frame, num_joints=num_joints, in_chans=128, embed_dim_ratio=256, depth=6, num_heads=8,
+                    mlp_ratio=2., qkv_bias=True, qk_scale=None, drop_path_rate=0.1)
+        self.modelA = ST(num_class, **head)
+        self.modelB = TS(num_class, **head)
+        enable_stem_fusion(self.gcn0, self.tcn0)
+
+    def forward(self, x):
+        x = self.tcn0(self.gcn0(x.permute(0, 3, 1, 2)))
+        if self.style == 'ST':
+            return self.modelA(x)
+        if self.style == 'TS':
+            return self.modelB(x)
+        x_st = self.modelA(x)
+        return self.modelB(x) + x_st

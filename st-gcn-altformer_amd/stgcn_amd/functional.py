@@ -515,3 +515,83 @@ def st_attention_backward(x, dbn_weight, dbn_bias, Wqkv, Wout, bn_weight, bn_bia
                    c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(N), c_int(Cin), c_int(Cout), c_int(dk), c_int(T),
                    c_int(V), c_int(heads), c_uint(_capi.BN_FROZEN if frozen else 0), _stream(dev))
     return g
+
+
+# ---- AltFormer heads: transformer block (stgcn_vit_*) ---------------------------------------------------------------------
+def _vit_flags(math: int) -> int:
+    return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32)
+
+
+def _bytes(dev, nbytes):
+    return torch.empty((max(nbytes, 8) + 7) // 8, device=dev, dtype=torch.float64)
+
+
+def vit_linear_supported(M, K, Nout, math=MATH_F32) -> bool:
+    return bool(_capi.lib().stgcn_vit_linear_supported(M, K, Nout, math & _capi.MATH_MASK))
+
+
+def vit_linear(x, weight, bias=None, ln=None, residual=None, gelu=False, math=MATH_F32) -> torch.Tensor:
+    """``act(LN?(x) W^T + b) (+ residual)`` on the last axis of x (..., K); weight (Nout, K) as nn.Linear stores it.
+    ``ln`` = (weight, bias, eps) of a LayerNorm over K applied to x's rows first, or None; ``gelu``: exact GELU."""
+    dev = x.device
+    K = x.shape[-1]
+    M = x.numel() // K
+    Nout = weight.shape[0]
+    if weight.shape[1] != K:
+        raise ValueError(f"weight is {tuple(weight.shape)}, x has {K} features")
+    if residual is not None and residual.numel() != M * Nout:
+        raise ValueError(f"residual has {residual.numel()} elements, expected {M * Nout}")
+    y = torch.empty(x.shape[:-1] + (Nout,), device=dev, dtype=torch.float32)
+    lnw, lnb, eps = ln if ln is not None else (None, None, 0.0)
+    fl = (math & _capi.MATH_MASK) | (_capi.VIT_GELU if gelu else 0)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_linear", _dev_ptr(x, "x", dev), _dev_ptr(weight, "weight", dev), _dev_ptr(bias, "bias", dev),
+                   _dev_ptr(lnw, "ln weight", dev), _dev_ptr(lnb, "ln bias", dev), c_float(eps),
+                   _dev_ptr(residual, "residual", dev), _dev_ptr(y, "y"), c_int(M), c_int(K), c_int(Nout), c_uint(fl), _stream(dev))
+    return y
+
+
+def vit_attention_supported(L, heads, head_dim) -> bool:
+    return bool(_capi.lib().stgcn_vit_attention_supported(L, heads, head_dim))
+
+
+def vit_attention(qkv, heads, scale=None) -> torch.Tensor:
+    """Multi-head attention over the packed qkv (B, L, 3*D) = (B, L, 3, heads, D/heads) as the qkv nn.Linear writes it;
+    returns (B, L, D), heads concatenated.  ``scale`` defaults to head_dim ** -0.5."""
+    dev = qkv.device
+    B, L, D3 = qkv.shape
+    D = D3 // 3
+    hd = D // heads
+    if D * 3 != D3 or hd * heads != D:
+        raise ValueError(f"qkv is {tuple(qkv.shape)}: the last axis must be 3 * heads * head_dim (heads = {heads})")
+    out = torch.empty(B, L, D, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_attention", _dev_ptr(qkv, "qkv", dev), _dev_ptr(out, "out"), c_int(B), c_int(L), c_int(heads),
+                   c_int(hd), c_float(hd ** -0.5 if scale is None else scale), _stream(dev))
+    return out
+
+
+def vit_block_supported(L, D, heads, hidden) -> bool:
+    return bool(_capi.lib().stgcn_vit_block_supported(L, D, heads, hidden))
+
+
+def vit_block_forward(x, norm1, qkv, proj, norm2, fc1, fc2, heads, eps, scale, math=MATH_F32) -> torch.Tensor:
+    """Eval forward of one transformer Block on x (B, L, D).  ``norm1`` / ``norm2`` = (weight, bias) of the LayerNorms (one
+    ``eps``), ``qkv`` / ``proj`` / ``fc1`` / ``fc2`` = (weight, bias or None) of the nn.Linears as stored.  ``math``: MATH_F32
+    or MATH_BF16X3, optionally | VIT_QKV_F32."""
+    dev = x.device
+    B, L, D = x.shape
+    hidden = fc1[0].shape[0]
+    nbytes = _capi.lib().stgcn_vit_block_ws_bytes(B, L, D, hidden)
+    ws = _bytes(dev, nbytes)
+    y = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_block_forward", _dev_ptr(x, "x", dev), _dev_ptr(norm1[0], "norm1.weight", dev),
+                   _dev_ptr(norm1[1], "norm1.bias", dev), _dev_ptr(qkv[0], "qkv.weight", dev), _dev_ptr(qkv[1], "qkv.bias", dev),
+                   _dev_ptr(proj[0], "proj.weight", dev), _dev_ptr(proj[1], "proj.bias", dev),
+                   _dev_ptr(norm2[0], "norm2.weight", dev), _dev_ptr(norm2[1], "norm2.bias", dev),
+                   _dev_ptr(fc1[0], "fc1.weight", dev), _dev_ptr(fc1[1], "fc1.bias", dev), _dev_ptr(fc2[0], "fc2.weight", dev),
+                   _dev_ptr(fc2[1], "fc2.bias", dev), c_float(eps), c_float(scale), c_void_p(ws.data_ptr()), c_size_t(nbytes),
+                   _dev_ptr(y, "y"), c_int(B), c_int(L), c_int(D), c_int(heads), c_int(hidden), c_uint(_vit_flags(math)),
+                   _stream(dev))
+    return y

@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""Time the AltFormer heads: the HIP path of every stage's transformer block and of the whole ST / TS models against the
+torch-op path of the same module, in one process, alternating, with device events.
+
+    python tools/time_altformer.py [--batch 32] [--repeats 7] [--warmup 2] [--out profiles/altformer_times.json]
+
+Prints ONE JSON line.  Per stage (a Block at the stage's shape, batch ``--batch``): ms of the HIP path (default arithmetic,
+and 'f32' / 'bf16x3' for comparison) and of the torch path (min, median, max over the repeats; ``spread`` = (max - min) / min of
+the torch path and of the HIP path, the noise the comparison has to be read against), the block's FLOPs counted from the
+shapes, and per launch (the four linears in the arithmetic the default uses for them, the attention) ms, achieved TFLOP/s and
+the share of the relevant peak: 155 TFLOP/s for the fp32 matrix cores (measured), 2500 / 3 for bf16x3.  Whole models: the
+reference's SHREC configuration (14 classes, 180 frames, 22 joints) from skeleton clips to logits, stem + head, clips/s.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "st-gcn-altformer_amd"))
+
+PEAK_F32 = 155.0            # TFLOP/s, v_mfma_f32_32x32x2_f32, measured
+PEAK_BF16X3 = 2500.0 / 3    # three bf16 products per fp32 product
+
+# stage: (sequences per clip, L, D) - the heads of the reference's three scripts (SHREC, DHG: V = 22; LMDHG: V = 46)
+STAGES = {
+    "ST spatial SHREC (180 x 22)": (180, 22, 256),
+    "ST spatial DHG (150 x 22)": (150, 22, 256),
+    "ST temporal 180": (1, 180, 512),
+    "ST temporal 150": (1, 150, 512),
+    "TS temporal LMDHG (46 x 180)": (46, 180, 256),
+    "TS temporal (22 x 180)": (22, 180, 256),
+    "TS spatial 46": (1, 46, 512),
+    "TS spatial 22": (1, 22, 512),
+}
+
+
+def events(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def alternate(fns, repeats, warmup):
+    """{name: [ms, ...]}: the candidates run in turn, ``warmup`` untimed rounds first."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    out = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            out[k].append(events(fn))
+    return out
+
+
+def summary(ts):
+    return {"min": round(min(ts), 4), "median": round(statistics.median(ts), 4), "max": round(max(ts), 4),
+            "spread": round((max(ts) - min(ts)) / min(ts), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert args.repeats >= 5
+    import stgcn_amd
+    from stgcn_amd import functional as F
+    from stgcn_amd.altformer import DEFAULT_HEAD_MATH, HEAD_MATH, Block, set_head_math
+    from functools import partial
+    dev = torch.device("cuda:0")
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    res = {"batch": args.batch, "repeats": args.repeats, "default_math": DEFAULT_HEAD_MATH, "device": torch.cuda.get_device_name(0),
+           "stages": {}, "models": {}}
+    flags = HEAD_MATH[DEFAULT_HEAD_MATH]
+    math_rest = flags & F._capi.MATH_MASK
+    math_qkv = F.MATH_F32 if flags & F._capi.VIT_QKV_F32 else math_rest
+    with torch.no_grad():
+        for name, (per_clip, L, D) in STAGES.items():
+            B = args.batch * per_clip
+            M, hidden, heads = B * L, 2 * D, 8
+            torch.manual_seed(0)
+            blk = Block(D, heads, mlp_ratio=2., qkv_bias=True, norm_layer=norm).to(dev).eval()
+            x = torch.randn(B, L, D, device=dev)
+            chooses = "hip" if blk.uses_hip(x) else "torch"      # what the module does at this size on its own
+            blk.hip_min_tokens = 0                               # the stage rows time the kernels whatever the policy says
+
+            def run(mode):
+                blk.force_torch = mode == "torch"
+                if mode != "torch":
+                    set_head_math(blk, mode)
+                return blk(x)
+            ts = alternate({m: partial(run, m) for m in ("torch", DEFAULT_HEAD_MATH, "f32", "bf16x3")}, args.repeats, args.warmup)
+            blk.force_torch = False
+            a, m = blk.attn, blk.mlp
+            ln1, ln2 = (blk.norm1.weight, blk.norm1.bias, 1e-6), (blk.norm2.weight, blk.norm2.bias, 1e-6)
+            qkv = F.vit_linear(x, a.qkv.weight, a.qkv.bias, ln=ln1, math=math_qkv)
+            att = F.vit_attention(qkv, heads, a.scale)
+            h = F.vit_linear(x, m.fc1.weight, m.fc1.bias, ln=ln2, gelu=True, math=math_rest)
+            parts = alternate({
+                "qkv": lambda: F.vit_linear(x, a.qkv.weight, a.qkv.bias, ln=ln1, math=math_qkv),
+                "attention": lambda: F.vit_attention(qkv, heads, a.scale),
+                "proj": lambda: F.vit_linear(att, a.proj.weight, a.proj.bias, residual=x, math=math_rest),
+                "fc1": lambda: F.vit_linear(x, m.fc1.weight, m.fc1.bias, ln=ln2, gelu=True, math=math_rest),
+                "fc2": lambda: F.vit_linear(h, m.fc2.weight, m.fc2.bias, residual=x, math=math_rest),
+            }, args.repeats, args.warmup)
+            flops = {"qkv": 2 * M * D * 3 * D, "attention": 4 * B * heads * L * L * (D // heads), "proj": 2 * M * D * D,
+                     "fc1": 2 * M * D * hidden, "fc2": 2 * M * hidden * D}
+            launches = {}
+            for k, t in parts.items():
+                f32 = k == "attention" or (k == "qkv" and math_qkv == F.MATH_F32) or (k != "qkv" and math_rest == F.MATH_F32)
+                tf = flops[k] / (min(t) * 1e-3) / 1e12
+                launches[k] = {"ms": summary(t), "gflop": round(flops[k] / 1e9, 3), "tflops": round(tf, 1),
+                               "arithmetic": "f32" if f32 else "bf16x3",
+                               "share_of_peak": round(tf / (PEAK_F32 if f32 else PEAK_BF16X3), 3)}
+            hip, tor = ts[DEFAULT_HEAD_MATH], ts["torch"]
+            res["stages"][name] = {
+                "B": B, "L": L, "D": D, "tokens": M, "module_chooses": chooses, "gflop": round(sum(flops.values()) / 1e9, 2),
+                "hip_ms": summary(hip), "torch_ms": summary(tor), "hip_f32_ms": summary(ts["f32"]),
+                "hip_bf16x3_ms": summary(ts["bf16x3"]), "speedup_median": round(statistics.median(tor) / statistics.median(hip), 3),
+                "hip_not_slower": statistics.median(hip) <= statistics.median(tor) * (1 + summary(hip)["spread"]),
+                "tflops_block": round(sum(flops.values()) / (min(hip) * 1e-3) / 1e12, 1), "launches": launches}
+        for style in ("ST", "TS"):
+            torch.manual_seed(1)
+            model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=22, style=style,
+                                               graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).eval()
+            clips = torch.randn(args.batch, 180, 22, 3, device=dev)
+            blocks = [b for b in model.modules() if isinstance(b, Block)]
+
+            def run_model(torch_path):
+                for b in blocks:
+                    b.force_torch = torch_path
+                return model(clips)
+            ts = alternate({"torch": partial(run_model, True), "hip": partial(run_model, False)}, args.repeats, args.warmup)
+            stem = alternate({"stem": lambda: model.tcn0(model.gcn0(clips.permute(0, 3, 1, 2)))}, args.repeats, args.warmup)["stem"]
+            res["models"][style] = {"hip_ms": summary(ts["hip"]), "torch_ms": summary(ts["torch"]), "stem_ms": summary(stem),
+                                    "speedup_median": round(statistics.median(ts["torch"]) / statistics.median(ts["hip"]), 3),
+                                    "clips_per_s_hip": round(args.batch / (statistics.median(ts["hip"]) * 1e-3), 1),
+                                    "clips_per_s_torch": round(args.batch / (statistics.median(ts["torch"]) * 1e-3), 1)}
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
