@@ -705,35 +705,33 @@ inline AgcnBwdPlan plan_agcn_bwd(int N, int Cin, int Cout, int T, int V, int S_)
     return pl;
 }
 
-// workspace of the fused path (bytes, each block 256-aligned):
-//   [G: Cout*NG doubles][rr: 96 floats][dM sum: S*C1*C1 floats][wda: Cout*12 floats] | part_g [grid][Cout][NG] | hbuf [N][SC][T*V]
-//   | part_pa [grid][S][V][V] | part_m [grid][S][C1][C1]
+// workspace of the fused path
 struct AgcnBwdWs {
-    size_t g = 0, rr = 0, dm = 0, wda = 0, part_g = 0, hbuf = 0, part_pa = 0, part_m = 0, total = 0;
+    double *G;                               // [Cout][NG]
+    float *rr, *dm_sum, *wda;                // 96 floats; dM sum [S][C1][C1]; [Cout][12]
+    float *part_g, *hbuf, *part_pa, *part_m; // [grid][Cout][NG]; [N][SC][T*V]; [grid][S][V][V]; [grid][S][C1][C1]
+    size_t total;
 };
-inline AgcnBwdWs ws_layout(const AgcnBwdPlan &pl, int N, int Cout, int T, int V) {
+inline AgcnBwdWs ws_layout(void *base, const AgcnBwdPlan &pl, int N, int Cout, int T, int V) {
+    Carve c(base);
     AgcnBwdWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-    w.g = take((size_t)Cout * NG * sizeof(double));
-    w.rr = take(96 * sizeof(float));
-    w.dm = take((size_t)S * C1 * C1 * sizeof(float));
-    w.wda = take((size_t)Cout * 12 * sizeof(float));
-    w.part_g = take((size_t)pl.grid * Cout * NG * sizeof(float));
-    w.hbuf = take((size_t)N * SC * T * V * sizeof(float));
-    w.part_pa = take((size_t)pl.grid * S * V * V * sizeof(float));
-    w.part_m = take((size_t)pl.grid * S * C1 * C1 * sizeof(float));
-    w.total = off;
+    w.G = c.take<double>((size_t)Cout * NG);
+    w.rr = c.take<float>(96);
+    w.dm_sum = c.take<float>((size_t)S * C1 * C1);
+    w.wda = c.take<float>((size_t)Cout * 12);
+    w.part_g = c.take<float>((size_t)pl.grid * Cout * NG);
+    w.hbuf = c.take<float>((size_t)N * SC * T * V);
+    w.part_pa = c.take<float>((size_t)pl.grid * S * V * V);
+    w.part_m = c.take<float>((size_t)pl.grid * S * C1 * C1);
+    w.total = c.off;
     return w;
 }
 
 }  // namespace
 
-bool agcn_bwd_supported(int N, int Cin, int Cout, int T, int V, int S_) { return plan_agcn_bwd(N, Cin, Cout, T, V, S_).ok; }
-
 size_t agcn_bwd_ws_bytes(int N, int Cin, int Cout, int T, int V, int S_) {
     const AgcnBwdPlan pl = plan_agcn_bwd(N, Cin, Cout, T, V, S_);
-    return pl.ok ? ws_layout(pl, N, Cout, T, V).total : 0;
+    return pl.ok ? ws_layout(nullptr, pl, N, Cout, T, V).total : 0;
 }
 
 // y: the forward's output (the ReLU mask); stats: the forward's save_stats (4*Cout floats: batch mean / invstd of both
@@ -749,12 +747,9 @@ int launch_agcn_bwd(const float *x, const float *P, const float *A_eff, const fl
         return fail(STGCN_ERR_UNSUPPORTED,
                     "agcn backward (moment form) covers Cin=3, 3 subsets, Cout in {64,128,256} with a down branch (got Cin=%d S=%d Cout=%d V=%d)",
                     Cin, S_, Cout, V);
-    const AgcnBwdWs w = ws_layout(pl, N, Cout, T, V);
-    char *base = (char *)ws;
-    double *G = (double *)(base + w.g);
-    float *rr = (float *)(base + w.rr), *dm_sum = (float *)(base + w.dm), *part_g = (float *)(base + w.part_g);
-    float *wda = (float *)(base + w.wda);
-    float *hbuf = (float *)(base + w.hbuf), *part_pa = (float *)(base + w.part_pa), *part_m = (float *)(base + w.part_m);
+    const AgcnBwdWs w = ws_layout(ws, pl, N, Cout, T, V);
+    double *G = w.G;
+    float *rr = w.rr, *dm_sum = w.dm_sum, *wda = w.wda, *part_g = w.part_g, *hbuf = w.hbuf, *part_pa = w.part_pa, *part_m = w.part_m;
     const double *mom = (const double *)(stats + 4 * Cout);
     hipLaunchKernelGGL(agcn_bwd_prep_kernel, dim3(ceil_div(Cout * 12, 256)), dim3(256), 0, st, Wd, bn_w, stats + Cout, wda, Cout);
     STGCN_LAUNCH_CHECK("agcn_bwd_prep_kernel");

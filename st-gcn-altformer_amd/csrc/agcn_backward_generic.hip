@@ -53,13 +53,33 @@ int k_split(int batch, int tiles, int K, size_t m, size_t part_cap) {
     return ks < 1 ? 1 : (int)ks;
 }
 
+// scratch of the chain, all fp32
+struct ChainWs {
+    float *U, *DU;               // u_s = x P_s and its gradient, (N, S, Cin, T*V)
+    float *EA, *EB, *DA, *DB;    // the embeddings and their gradients, (N, S, inter_c, T*V)
+    float *DP, *DS;              // gradients of P and of the soft-max argument, (N, S, V, V)
+    float *part, *bpart;         // K-split / per-clip slices of the weight gradients; per-clip row sums (bias gradients)
+    size_t part_cap, floats;
+};
+ChainWs carve_chain(float *base, int N, int Cin, int Cout, int T, int V, int inter_c, int S) {
+    Carve c(base);
+    ChainWs w;
+    const size_t P = (size_t)T * V;
+    const size_t big = (size_t)N * S * Cin * P, emb = (size_t)N * S * inter_c * P, vv = (size_t)N * S * V * V;
+    w.U = c.packed<float>(big); w.DU = c.packed<float>(big);
+    w.EA = c.packed<float>(emb); w.EB = c.packed<float>(emb); w.DA = c.packed<float>(emb); w.DB = c.packed<float>(emb);
+    w.DP = c.packed<float>(vv); w.DS = c.packed<float>(vv);
+    w.part_cap = part_floats(N, Cin, Cout, inter_c, V, S);
+    w.part = c.packed<float>(w.part_cap);
+    w.bpart = c.packed<float>((size_t)N * (Cout > S * inter_c ? Cout : S * inter_c) + 64);
+    w.floats = c.off / sizeof(float);
+    return w;
+}
+
 }  // namespace
 
 size_t agcn_bwd_generic_ws_floats(int N, int Cin, int Cout, int T, int V, int inter_c, int S) {
-    const size_t P = (size_t)T * V;
-    const size_t big = (size_t)N * S * Cin * P, emb = (size_t)N * S * inter_c * P, vv = (size_t)N * S * V * V;
-    const size_t rows = (size_t)N * (Cout > S * inter_c ? Cout : S * inter_c);
-    return 2 * big + 4 * emb + 2 * vv + part_floats(N, Cin, Cout, inter_c, V, S) + rows + 64;
+    return carve_chain(nullptr, N, Cin, Cout, T, V, inter_c, S).floats;
 }
 
 int launch_agcn_bwd_generic(const float *x, const float *Pm, const float *A_eff, const float *dzm, const float *dzd,
@@ -71,10 +91,10 @@ int launch_agcn_bwd_generic(const float *x, const float *Pm, const float *A_eff,
     const int R = Cin * T, RI = inter_c * T;           // rows of the per-frame joint products
     const int SI = S * inter_c;                         // the embeddings of all subsets, stacked
     const long long xs = (long long)Cin * P, zs = (long long)Cout * P, es = (long long)inter_c * P;   // per-clip / per-subset strides
-    const size_t big = (size_t)N * S * Cin * P, emb = (size_t)N * S * inter_c * P, vv = (size_t)N * S * VV;
-    const size_t part_cap = part_floats(N, Cin, Cout, inter_c, V, S);
-    float *U = ws, *DU = U + big, *EA = DU + big, *EB = EA + emb, *DA = EB + emb, *DB = DA + emb, *DP = DB + emb, *DS = DP + vv,
-          *part = DS + vv, *bpart = part + part_cap;
+    const ChainWs w = carve_chain(ws, N, Cin, Cout, T, V, inter_c, S);
+    float *U = w.U, *DU = w.DU, *EA = w.EA, *EB = w.EB, *DA = w.DA, *DB = w.DB, *DP = w.DP, *DS = w.DS, *part = w.part,
+          *bpart = w.bpart;
+    const size_t part_cap = w.part_cap;
     int rc;
 #define OK(expr) do { rc = (expr); if (rc != STGCN_OK) return rc; } while (0)
     // sum over clips (and K parts) of dY[b] (rows x P) X[b]^T (cols x P) -> out; batch entries = N*inner, entry b = (n, i):

@@ -1,4 +1,5 @@
-// Training-mode forward of unit_agcn WITHOUT materialising its two pre-BatchNorm branches (stem shape class:
+// Training mode of unit_agcn: the plans and launch sequences of its forward and backward entry points (bottom of the file),
+// and the forward WITHOUT materialising its two pre-BatchNorm branches (stem shape class:
 // C_in = 3, 3 subsets, down branch).
 //
 // Both branches are linear in a handful of per-pixel features,
@@ -11,6 +12,8 @@
 // them into every channel's (scale, shift), saved mean / invstd and running-buffer update, and the eval-mode expansion
 // kernel then writes the module output directly.  Against the materialising path this drops two full-size tensors
 // (2 x 4*C*T*V bytes per clip written, read twice) and three elementwise passes.
+#include <algorithm>
+
 #include "common.h"
 
 namespace stgcn {
@@ -190,14 +193,12 @@ inline int moments_grid(int N) { return N < 256 ? N : 256; }
 
 }  // namespace
 
-bool agcn_moments_supported(int Cin, int V, int S) {
+static bool agcn_moments_supported(int Cin, int V, int S) {
     return Cin == 3 && S == 3 && ((size_t)S * V * V + (size_t)Cin * (MOM_NT / V > 0 ? MOM_NT / V : 1) * V) * 4 <= (size_t)kLdsBytes && V <= MOM_NT;
 }
 
-size_t agcn_moments_ws_bytes(int N) { return (size_t)moments_grid(N) * NMOM * sizeof(double); }
-
-// part: agcn_moments_ws_bytes(N) bytes of scratch.  Writes s_m, t_m, s_d, t_d (Cout each) and updates the running buffers.
-int launch_agcn_moments(const float *x, const float *P, double *part, const float *Wd, const float *bd, const float *Wdown,
+// part: moments_grid(N) * NMOM doubles of scratch.  Writes s_m, t_m, s_d, t_d (Cout each) and updates the running buffers.
+static int launch_agcn_moments(const float *x, const float *P, double *part, const float *Wd, const float *bd, const float *Wdown,
                         const float *bdown, const float *bn_w, const float *bn_b, float *bn_rm, float *bn_rv,
                         const float *dbn_w, const float *dbn_b, float *dbn_rm, float *dbn_rv, float momentum, float eps,
                         float *s_m, float *t_m, float *s_d, float *t_d, float *save_stats, int N, int Cin, int Cout, int T,
@@ -217,6 +218,199 @@ int launch_agcn_moments(const float *x, const float *P, double *part, const floa
                        save_stats, Cout);
     STGCN_LAUNCH_CHECK("agcn_moments_finalize_kernel");
     return STGCN_OK;
+}
+
+// ---- training forward: plan, workspace, launch sequence ------------------------------------------------------------
+namespace {
+
+struct AgcnTrainWs {
+    TrainSmall v;
+    double *part;        // moments path: the per-workgroup partial moments
+    float *zm, *zd;      // materialising path: the two pre-BatchNorm branches
+    size_t bytes;
+};
+AgcnTrainWs carve_agcn_train(void *base, bool moments, int N, int Cout, int T, int V) {
+    Carve c(base);
+    AgcnTrainWs w{};
+    w.v = carve_train_small(c, Cout);
+    if (moments) {
+        w.part = c.packed<double>((size_t)moments_grid(N) * NMOM);
+    } else {
+        w.zm = c.packed<float>((size_t)N * Cout * T * V);
+        w.zd = c.packed<float>((size_t)N * Cout * T * V);
+    }
+    w.bytes = c.off;
+    return w;
+}
+
+}  // namespace
+
+AgcnTrainPlan plan_agcn_train(int N, int Cin, int Cout, int T, int V, int S, bool materialise, bool has_down, bool frozen) {
+    AgcnTrainPlan p;
+    p.frozen = frozen;
+    p.has_down = has_down;
+    p.moments = !materialise && agcn_moments_supported(Cin, V, S);
+    // Outside the stem class the residual rows are left out of the main branch's contraction altogether (no Wdown: "identity"
+    // with the residual term off, mode bit 1) and conv_down runs as one plain product — the expansion kernel run a second time
+    // with the main scales at zero did the whole work of both branches again (2 x 208 us at 64 -> 128 channels, 64 clips).
+    p.down_as_gemm = has_down && Cin != 3;
+    p.ws_bytes = carve_agcn_train(nullptr, p.moments, N, Cout, T, V).bytes;
+    return p;
+}
+
+// P: the attention matrices of this call (launch_attention).  save_zm / save_zd (optional) receive the branches in place of
+// the workspace's; save_stats (4*Cout + 128, optional): batch mean, invstd of the main BatchNorm, then of the down BatchNorm,
+// then the feature-moment block.
+int launch_agcn_forward_train(const AgcnTrainPlan &p, const float *x, const float *P, const float *Wd, const float *bd,
+                              const float *Wdown, const float *bdown, const float *bn_weight, const float *bn_bias,
+                              float *bn_running_mean, float *bn_running_var, const float *dbn_weight, const float *dbn_bias,
+                              float *dbn_running_mean, float *dbn_running_var, float momentum, float eps, void *ws, float *y,
+                              float *save_zm, float *save_zd, float *save_stats, int N, int Cin, int Cout, int T, int V, int S,
+                              hipStream_t st) {
+    const AgcnTrainWs w = carve_agcn_train(ws, p.moments, N, Cout, T, V);
+    float *ones = w.v.ones, *zeros = w.v.zeros, *s1 = w.v.s1, *t1 = w.v.t1, *s2 = w.v.s2, *t2 = w.v.t2;
+    int rc;
+    if (p.moments) {   // batch statistics from the moments of the 12 per-pixel features; the branches are never written
+        if ((rc = launch_agcn_moments(x, P, w.part, Wd, bd, Wdown, bdown, bn_weight, bn_bias, bn_running_mean, bn_running_var,
+                                      dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, momentum, eps, s1, t1, s2, t2,
+                                      save_stats, N, Cin, Cout, T, V, S, st)))
+            return rc;
+        return launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, s1, t1, s2, t2, y, N, Cin, Cout, T, V, S, 0, st);
+    }
+    float *zm = save_zm ? save_zm : w.zm, *zd = save_zd ? save_zd : w.zd;
+    const size_t plane = (size_t)T * V, total = (size_t)N * Cout * plane;
+    // (scale, shift) of one BatchNorm over z, from its running statistics (frozen) or from the batch's; sv: its mean and invstd
+    auto finalize = [&](const float *z, double *sums, const float *weight, const float *bias, float *rm, float *rv, float *s,
+                        float *t, float *sv) {
+        float *sv_inv = sv ? sv + Cout : nullptr;
+        if (p.frozen) return launch_bn_frozen_finalize(weight, bias, rm, rv, eps, s, t, Cout, st, sv, sv_inv);
+        if (int r = launch_bn_batch_stats(z, sums, N, Cout, plane, st)) return r;
+        return launch_bn_train_finalize(sums, (double)N * plane, weight, bias, rm, rv, momentum, eps, s, t, Cout, st, sv, sv_inv);
+    };
+    if (save_stats)   // no feature moments on this path: clear their block incl. the validity mark the moment-form backward checks
+        STGCN_HIP_CHECK(hipMemsetAsync(save_stats + 4 * Cout, 0, 128 * sizeof(float), st));
+    if ((rc = launch_fill_ones_zeros(ones, zeros, Cout, st))) return rc;
+    // main branch, pre-BN: sum_s conv_d_s(x P_s)   (unit scale on the main path, zero on the residual path, no ReLU)
+    rc = p.down_as_gemm ? launch_agcn_expand(x, P, Wd, bd, nullptr, nullptr, ones, zeros, nullptr, nullptr, zm, N, Cin, Cout, T, V,
+                                             S, 1 | 2, st)
+                        : launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, ones, zeros, p.has_down ? zeros : nullptr,
+                                             p.has_down ? zeros : nullptr, zm, N, Cin, Cout, T, V, S, 1 | 2, st);
+    if (rc != STGCN_OK) return rc;
+    if ((rc = finalize(zm, w.v.sums1, bn_weight, bn_bias, bn_running_mean, bn_running_var, s1, t1, save_stats))) return rc;
+    if (!p.has_down) return launch_bn_apply(zm, s1, t1, x, nullptr, nullptr, y, total, Cout, plane, st);  // identity residual: + x
+    if (p.down_as_gemm) {     // residual branch, pre-BN: zd[n] = Wdown x[n] + bdown
+        const long long Pl = (long long)plane;
+        GemmArgs g{Wdown, x, zd, bdown, Cout, (int)plane, Cin, Cin, 1, 0, Pl, 1, (long long)Cin * Pl, Pl, 1, (long long)Cout * Pl, 1.f, 0};
+        rc = launch_gemm_f32(g, N, st);
+    } else {
+        rc = launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, zeros, zeros, ones, zeros, zd, N, Cin, Cout, T, V, S, 1, st);
+    }
+    if (rc != STGCN_OK) return rc;
+    if ((rc = finalize(zd, w.v.sums2, dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, s2, t2,
+                       save_stats ? save_stats + 2 * Cout : nullptr)))
+        return rc;
+    return launch_bn_apply(zm, s1, t1, zd, s2, t2, y, total, Cout, plane, st);
+}
+
+// ---- training backward: plan, workspace, launch sequence -------------------------------------------------------------
+namespace {
+
+struct AgcnBackwardWs {   // of the generic GEMM chain (the moment form lays out its own: agcn_backward.hip)
+    double *sums;
+    float *coefm, *coefd, *sm, *tm, *sd, *td, *ones, *zeros;
+    float *dzm, *dzd, *chain;   // both pre-BatchNorm gradients, launch_agcn_bwd_generic's scratch
+    float *zm, *zd;             // recompute: the rebuilt branches
+    size_t bytes;
+};
+AgcnBackwardWs carve_agcn_backward(void *base, const AgcnBackwardPlan &p, int N, int Cin, int Cout, int T, int V, int S) {
+    Carve c(base);
+    AgcnBackwardWs w{};
+    const size_t C = Cout, total = (size_t)N * Cout * T * V;
+    w.sums = c.packed<double>(3 * C);
+    w.coefm = c.packed<float>(3 * C); w.coefd = c.packed<float>(3 * C);
+    w.sm = c.packed<float>(C); w.tm = c.packed<float>(C); w.sd = c.packed<float>(C); w.td = c.packed<float>(C);
+    w.ones = c.packed<float>(C); w.zeros = c.packed<float>(C);
+    c.pad();
+    w.dzm = c.packed<float>(total); w.dzd = c.packed<float>(total);
+    w.chain = c.packed<float>(agcn_bwd_generic_ws_floats(N, Cin, Cout, T, V, p.inter_c_max, S));
+    c.pad();
+    if (p.recompute) { w.zm = c.packed<float>(total); w.zd = c.packed<float>(total); }
+    w.bytes = c.off;
+    return w;
+}
+
+}  // namespace
+
+// The moment-form backward (agcn_backward.hip) serves the stem's shape class after a moments-path forward when no input
+// gradient is wanted; everything else (any Cin / Cout / subsets, identity residual, dx, saved branches) takes the generic
+// GEMM chain.  The moment form is the closed form of the BATCH-statistics BatchNorm: frozen statistics take the chain too.
+AgcnBackwardPlan plan_agcn_backward(int N, int Cin, int Cout, int T, int V, int S, bool recompute, bool generic, bool has_down,
+                                    bool frozen) {
+    AgcnBackwardPlan p;
+    p.frozen = frozen;
+    p.has_down = has_down;
+    if (V > 64) return p;
+    const size_t fused_bytes = agcn_bwd_ws_bytes(N, Cin, Cout, T, V, S);      // 0: the moment form does not cover the shape
+    p.fused = !generic && fused_bytes != 0;
+    p.ws_bytes = fused_bytes;                                                 // the moment form needs neither branch
+    if (p.fused) return p;
+    p.recompute = recompute;
+    p.inter_c_max = Cout / 4 > 0 ? Cout / 4 : 1;   // upper bound used for sizing: unit_agcn's coff_embedding = 4
+    // (a workspace sized for the chain also serves the moment form, should the entry point take that after all)
+    p.ws_bytes = std::max(carve_agcn_backward(nullptr, p, N, Cin, Cout, T, V, S).bytes, fused_bytes);
+    return p;
+}
+
+int launch_agcn_backward_train(const AgcnBackwardPlan &p, const float *x, const float *A_eff, const float *Wa, const float *ba,
+                               const float *Wb, const float *bb, const float *Wd, const float *bd, const float *Wdown,
+                               const float *bdown, const float *P, const float *zm, const float *zd, const float *bn_weight,
+                               const float *bn_bias, const float *dbn_weight, const float *dbn_bias, const float *save_stats,
+                               const float *y, const float *dy, float *dWa, float *dba, float *dWb, float *dbb, float *dWd,
+                               float *dbd, float *dWdown, float *dbdown, float *dgamma, float *dbeta, float *ddgamma,
+                               float *ddbeta, float *dPA, float *dx, void *ws, int N, int Cin, int Cout, int T, int V,
+                               int inter_c, int S, hipStream_t st) {
+    if (p.fused)
+        return launch_agcn_bwd(x, P, A_eff, y, dy, Wa, ba, Wb, bb, Wd, bd, Wdown, bdown, bn_weight, dbn_weight, save_stats, ws,
+                               dWa, dba, dWb, dbb, dWd, dbd, dWdown, dbdown, dgamma, dbeta, ddgamma, ddbeta, dPA, N, Cin, Cout,
+                               T, V, inter_c, S, st);
+    const AgcnBackwardWs w = carve_agcn_backward(ws, p, N, Cin, Cout, T, V, S);
+    const bool has_down = p.has_down;
+    const size_t plane = (size_t)T * V;
+    const double count = (double)N * plane;
+    int rc;
+    if (p.recompute) {   // the forward kept no branches (moments path): rebuild them with the raw-mode expansion kernel
+        if ((rc = launch_fill_ones_zeros(w.ones, w.zeros, Cout, st))) return rc;
+        if ((rc = launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, w.ones, w.zeros, has_down ? w.zeros : nullptr,
+                                     has_down ? w.zeros : nullptr, w.zm, N, Cin, Cout, T, V, S, 1 | 2, st)))
+            return rc;
+        zm = w.zm;
+        if (has_down) {
+            if ((rc = launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, w.zeros, w.zeros, w.ones, w.zeros, w.zd, N, Cin, Cout, T, V, S,
+                                         1, st)))
+                return rc;
+            zd = w.zd;
+        }
+    }
+    const float *mean_m = save_stats, *inv_m = save_stats + Cout, *mean_d = save_stats + 2 * Cout, *inv_d = save_stats + 3 * Cout;
+    if ((rc = launch_bn_scale_shift(bn_weight, bn_bias, mean_m, inv_m, w.sm, w.tm, Cout, st))) return rc;
+    if (has_down && (rc = launch_bn_scale_shift(dbn_weight, dbn_bias, mean_d, inv_d, w.sd, w.td, Cout, st))) return rc;
+    // side b of the ReLU's argument: the second BatchNorm, or (scale == NULL) the identity residual x itself
+    const float *zb = has_down ? zd : x, *sb = has_down ? w.sd : nullptr, *tb = has_down ? w.td : nullptr;
+    const float *mb = has_down ? mean_d : nullptr, *ib = has_down ? inv_d : nullptr;
+    if ((rc = launch_bn_relu_bwd_stats(zm, w.sm, w.tm, mean_m, inv_m, zb, sb, tb, mb, ib, dy, w.sums, N, Cout, plane, st))) return rc;
+    if ((rc = launch_bn_bwd_finalize(w.sums, 1, count, bn_weight, inv_m, dgamma, dbeta, w.coefm, Cout, st, p.frozen))) return rc;
+    if (has_down && (rc = launch_bn_bwd_finalize(w.sums, 2, count, dbn_weight, inv_d, ddgamma, ddbeta, w.coefd, Cout, st, p.frozen)))
+        return rc;
+    // materialise both pre-BatchNorm gradients, then the GEMM chain
+    // (identity residual, unit_agcn.py:57-58,92: dL/dx of the "+ x" term is the masked cotangent itself — written by the same
+    //  pass as dx's first term; it was a kernel of its own re-reading zm, x and dy)
+    const bool dx_from_g = dx != nullptr && !has_down;
+    if ((rc = launch_bn_relu_bwd_apply(zm, w.sm, w.tm, mean_m, inv_m, zb, sb, tb, mb, ib, dy, w.coefm, has_down ? w.coefd : nullptr,
+                                       w.dzm, has_down ? w.dzd : nullptr, nullptr, N, Cout, plane, st, dx_from_g ? dx : nullptr)))
+        return rc;
+    return launch_agcn_bwd_generic(x, P, A_eff, w.dzm, has_down ? w.dzd : nullptr, Wa, ba, Wb, bb, Wd, Wdown, w.chain, dWa, dba,
+                                   dWb, dbb, dWd, dbd, dWdown, dbdown, dPA, dx, dx_from_g ? 1 : 0, N, Cin, Cout, T, V, inter_c, S,
+                                   st);
 }
 
 }  // namespace stgcn

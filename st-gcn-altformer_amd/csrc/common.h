@@ -37,6 +37,16 @@ int fail(stgcn_status st, const char *fmt, ...);
                                hipGetErrorString(_e));                                     \
     } while (0)
 
+// argument checks of the extern "C" entry points
+#define REQUIRE_PTR(p)                                                                     \
+    do {                                                                                   \
+        if ((p) == nullptr) return stgcn::fail(STGCN_ERR_ARG, "%s: %s is NULL", __func__, #p); \
+    } while (0)
+#define REQUIRE_POS(v)                                                                     \
+    do {                                                                                   \
+        if ((v) <= 0) return stgcn::fail(STGCN_ERR_ARG, "%s: %s = %d must be positive", __func__, #v, (int)(v)); \
+    } while (0)
+
 // phases switched off by a diagnostic build (see tcn_conv.hip); always 0 in the shipped library
 // kernel option bits that travel in the high half of the kernels' `abl` argument (the low half is the ablation mask)
 constexpr int OPT_OUT_NTVC = 1 << 16;  // store the output as (N,T,V,C) instead of (N,C,T,V)
@@ -62,6 +72,26 @@ static inline unsigned long long *debug_buffer() {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+
+// Workspace carving.  A layout is written once, as a function that takes pieces from a Carve in order: run on a NULL base it
+// sizes the workspace (`off` is the total, every piece NULL), run on the caller's pointer it places the pieces.
+struct Carve {
+    char *p;
+    size_t off = 0;
+    explicit Carve(void *base) : p((char *)base) {}
+    template <typename T>
+    T *take(size_t n, size_t align = 256) {        // n elements; the piece occupies a multiple of `align` bytes
+        T *r = p ? reinterpret_cast<T *>(p + off) : nullptr;
+        off += align_up(n * sizeof(T), align);
+        return r;
+    }
+    template <typename T>
+    T *packed(size_t n) { return take<T>(n, sizeof(T)); }   // no padding behind the piece (blocks of small vectors)
+    void pad(size_t align = 256) { off = align_up(off, align); }
+};
+
+// output frames of the temporal conv: pad (K-1)/2 on both sides (an even K drops a frame at stride 1)
+static inline int tcn_out_frames(int T, int K, int stride) { return (T + 2 * ((K - 1) / 2) - K) / stride + 1; }
 
 // Opt a kernel in to more than 64 KiB of dynamic LDS.
 template <typename K>
@@ -180,6 +210,7 @@ int launch_tcn_v4(const float *x, const void *Wp, const float *shift, void *y, i
                   int stride, unsigned flags, hipStream_t st);
 
 // training-mode BatchNorm helpers (train_bn.hip)
+int launch_fill_ones_zeros(float *ones, float *zeros, int C, hipStream_t st);
 int launch_bn_batch_stats(const float *z, double *sums, int N, int C, size_t plane, hipStream_t st);
 int launch_bn_train_finalize(const double *sums, double count, const float *weight, const float *bias,
                              float *running_mean, float *running_var, float momentum, float eps, float *scale,
@@ -209,7 +240,6 @@ int launch_doubles_to_floats(const double *src, float *dst, int n, hipStream_t s
 int launch_weight_flip(const float *W, float *Wf, int Cout, int Cin, int K, hipStream_t st);
 int launch_tcn_dgrad_valu(const float *dz, const float *W, float *dx, int N, int Cin, int Cout, int T, int V, int K,
                           int stride, int Tout, hipStream_t st);
-bool tcn_wgrad_mfma_supported(int N, int Cin, int Cout, int T, int V, int K, int stride);
 size_t tcn_wgrad_ws_bytes(int N, int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
 // one wave per SIMD, input tile as a ring (tcn_wgrad_v6.hip): 17 <= V <= 24
 bool tcn_wgrad_v6_supported(int N, int Cin, int Cout, int T, int V, int K, int stride);
@@ -219,18 +249,87 @@ int launch_tcn_wgrad_v6(const float *dz, const float *x, float *part, int N, int
 int launch_tcn_wgrad(const float *dz, const float *x, float *dW, float *part, int N, int Cin, int Cout, int T, int V, int K,
                      int stride, int Tout, unsigned flags, hipStream_t st);
 
-// training-mode graph conv without materialised branches (agcn_train.hip)
-bool agcn_moments_supported(int Cin, int V, int S);
-size_t agcn_moments_ws_bytes(int N);
-int launch_agcn_moments(const float *x, const float *P, double *part, const float *Wd, const float *bd, const float *Wdown,
-                        const float *bdown, const float *bn_w, const float *bn_b, float *bn_rm, float *bn_rv,
-                        const float *dbn_w, const float *dbn_b, float *dbn_rm, float *dbn_rv, float momentum, float eps,
-                        float *s_m, float *t_m, float *s_d, float *t_d, float *save_stats, int N, int Cin, int Cout, int T,
-                        int V, int S, hipStream_t st);
+// The per-channel vectors of a training forward, one block at the head of its workspace: unit / zero vectors for the
+// raw-mode kernels, (scale, shift) and the fp64 sums of two BatchNorms.  The temporal conv has one BatchNorm and leaves
+// s2, t2 and sums2 unused.
+struct TrainSmall {
+    float *ones, *zeros, *s1, *t1, *s2, *t2;
+    double *sums1, *sums2;      // 2*C each: sum, sum of squares
+};
+static inline TrainSmall carve_train_small(Carve &c, int C) {
+    TrainSmall w;
+    w.ones = c.packed<float>(C); w.zeros = c.packed<float>(C);
+    w.s1 = c.packed<float>(C); w.t1 = c.packed<float>(C); w.s2 = c.packed<float>(C); w.t2 = c.packed<float>(C);
+    w.sums1 = c.packed<double>(2 * (size_t)C); w.sums2 = c.packed<double>(2 * (size_t)C);
+    c.pad();
+    return w;
+}
+
+// training-mode temporal conv block (tcn_train.hip): the plan both the size query and the entry point read — the path
+// choice and, through the carve over it, every region of the workspace.  `flags` may carry STGCN_BN_FROZEN (no size depends
+// on it).  ws_bytes == 0: T, K and stride leave no output frame.
+struct TcnTrainPlan {
+    bool frozen = false, stats_in_conv = false;   // stats_in_conv: the one-wave kernel sums the batch statistics in its epilogue
+    unsigned flags = 0, cflags = 0;               // without STGCN_BN_FROZEN; the raw convolution's
+    int Tout = 0;
+    size_t ws_bytes = 0;
+};
+TcnTrainPlan plan_tcn_train(int N, int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
+int launch_tcn_forward_train(const TcnTrainPlan &p, const float *x, const float *W, const float *conv_bias,
+                             const float *bn_weight, const float *bn_bias, float *bn_running_mean, float *bn_running_var,
+                             float momentum, float eps, void *ws, float *y, float *save_z, float *save_mean,
+                             float *save_invstd, int N, int Cin, int Cout, int T, int V, int K, int stride, hipStream_t st);
+struct TcnBackwardPlan {
+    bool frozen = false;
+    bool upsampled = false;         // stride 2, odd K: run as the stride-1 block's backward on dz upsampled with zero frames
+    bool dgrad_by_forward = false;  // dx = the forward kernels on the flipped weights
+    unsigned flags = 0, dgrad_flags = 0;
+    int Tout = 0, stride = 0, Tz = 0;   // stride and frames of the gradient tensor the two conv gradients read (after upsampling)
+    size_t wgrad_bytes = 0;             // partials of the matrix-core wgrad (0: it does not serve the shape)
+    size_t ws_bytes = 0;
+};
+TcnBackwardPlan plan_tcn_backward(int N, int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
+int launch_tcn_backward_train(const TcnBackwardPlan &p, const float *x, const float *W, const float *z, const float *bn_weight,
+                              const float *bn_bias, const float *save_mean, const float *save_invstd, const float *dy, float *dx,
+                              float *dW, float *dbias, float *dgamma, float *dbeta, void *ws, int N, int Cin, int Cout, int T,
+                              int V, int K, hipStream_t st);
+
+// training-mode graph conv (agcn_train.hip): the plans of its two entry points, read by the size queries and the entry points alike
+struct AgcnTrainPlan {
+    bool frozen = false, has_down = false;
+    bool moments = false;        // batch statistics from the feature moments: the two pre-BatchNorm branches are never written
+    bool down_as_gemm = false;   // materialising path: conv_down as one plain product (outside the stem class)
+    size_t ws_bytes = 0;
+};
+// materialise: the branches are to be saved, the statistics are frozen or there is no down branch (the size query's hint)
+AgcnTrainPlan plan_agcn_train(int N, int Cin, int Cout, int T, int V, int S, bool materialise, bool has_down, bool frozen);
+int launch_agcn_forward_train(const AgcnTrainPlan &p, const float *x, const float *P, const float *Wd, const float *bd,
+                              const float *Wdown, const float *bdown, const float *bn_weight, const float *bn_bias,
+                              float *bn_running_mean, float *bn_running_var, const float *dbn_weight, const float *dbn_bias,
+                              float *dbn_running_mean, float *dbn_running_var, float momentum, float eps, void *ws, float *y,
+                              float *save_zm, float *save_zd, float *save_stats, int N, int Cin, int Cout, int T, int V, int S,
+                              hipStream_t st);
+struct AgcnBackwardPlan {
+    bool frozen = false, has_down = false;
+    bool fused = false;          // the moment form (agcn_backward.hip); else the generic GEMM chain
+    bool recompute = false;      // generic: the forward kept no branches, they are rebuilt in the workspace
+    int inter_c_max = 0;         // generic: the embedding width the workspace is sized for
+    size_t ws_bytes = 0;         // 0: V > 64
+};
+// generic: the caller wants the GEMM chain (input gradient, identity residual, saved branches, frozen statistics)
+AgcnBackwardPlan plan_agcn_backward(int N, int Cin, int Cout, int T, int V, int S, bool recompute, bool generic, bool has_down,
+                                    bool frozen);
+int launch_agcn_backward_train(const AgcnBackwardPlan &p, const float *x, const float *A_eff, const float *Wa, const float *ba,
+                               const float *Wb, const float *bb, const float *Wd, const float *bd, const float *Wdown,
+                               const float *bdown, const float *P, const float *zm, const float *zd, const float *bn_weight,
+                               const float *bn_bias, const float *dbn_weight, const float *dbn_bias, const float *save_stats,
+                               const float *y, const float *dy, float *dWa, float *dba, float *dWb, float *dbb, float *dWd,
+                               float *dbd, float *dWdown, float *dbdown, float *dgamma, float *dbeta, float *ddgamma,
+                               float *ddbeta, float *dPA, float *dx, void *ws, int N, int Cin, int Cout, int T, int V,
+                               int inter_c, int S, hipStream_t st);
 
 // backward of the training-mode graph conv (agcn_backward.hip)
-bool agcn_bwd_supported(int N, int Cin, int Cout, int T, int V, int S);
-size_t agcn_bwd_ws_bytes(int N, int Cin, int Cout, int T, int V, int S);
+size_t agcn_bwd_ws_bytes(int N, int Cin, int Cout, int T, int V, int S);   // 0: the moment form does not cover the shape
 int launch_agcn_bwd(const float *x, const float *P, const float *A_eff, const float *y, const float *dy, const float *Wa,
                     const float *ba, const float *Wb, const float *bb, const float *Wd, const float *bd, const float *Wdown,
                     const float *bdown, const float *bn_w, const float *dbn_w, const float *stats, void *ws, float *dWa,

@@ -464,19 +464,6 @@ int bias_grad(const float *G, float *part, float *db, int M, long long TV, int N
     return launch_sum_parts(part, db, N, (size_t)M, st);
 }
 
-// workspace carving (256-byte aligned pieces)
-struct Carve {
-    char *p;
-    size_t off = 0;
-    explicit Carve(void *base) : p((char *)base) {}
-    template <typename T>
-    T *take(size_t n) {
-        T *r = p ? reinterpret_cast<T *>(p + off) : nullptr;
-        off += align_up(n * sizeof(T), 256);
-        return r;
-    }
-};
-
 struct Dims {
     int N, Cin, Cout, dk, T, V, H, dkh, dvh, Cq, CV;
     size_t TV;
@@ -487,7 +474,7 @@ struct Dims {
     size_t act(int C) const { return (size_t)N * C * TV; }
 };
 
-// eval / training forward workspace
+// eval / training forward workspace (carved in 256-byte aligned pieces)
 struct FwdWs {
     float *xn, *qkv, *o, *dscale, *dshift, *bscale, *bshift;
     double *parts, *sums;
@@ -539,9 +526,6 @@ BwdWs carve_bwd(void *base, const Dims &d, size_t *bytes) {
 
 using namespace stgcn;
 
-#define STA_REQUIRE(p) \
-    do { if ((p) == nullptr) return fail(STGCN_ERR_ARG, "%s: %s is NULL", __func__, #p); } while (0)
-
 extern "C" {
 
 int stgcn_st_attention_supported(int Cin, int Cout, int dk, int V, int heads) {
@@ -562,8 +546,8 @@ int stgcn_st_attention_forward(const float *x, const float *dbn_scale, const flo
                                const float *bqkv, const float *Wout, const float *bout, const float *bn_scale,
                                const float *bn_shift, void *ws, size_t ws_bytes, float *y, int N, int Cin, int Cout,
                                int dk, int T, int V, int heads, void *stream) {
-    STA_REQUIRE(x); STA_REQUIRE(dbn_scale); STA_REQUIRE(dbn_shift); STA_REQUIRE(Wqkv); STA_REQUIRE(bqkv);
-    STA_REQUIRE(Wout); STA_REQUIRE(bout); STA_REQUIRE(bn_scale); STA_REQUIRE(bn_shift); STA_REQUIRE(ws); STA_REQUIRE(y);
+    REQUIRE_PTR(x); REQUIRE_PTR(dbn_scale); REQUIRE_PTR(dbn_shift); REQUIRE_PTR(Wqkv); REQUIRE_PTR(bqkv);
+    REQUIRE_PTR(Wout); REQUIRE_PTR(bout); REQUIRE_PTR(bn_scale); REQUIRE_PTR(bn_shift); REQUIRE_PTR(ws); REQUIRE_PTR(y);
     if (int rc = check_shape("st_attention_forward", N, Cin, Cout, dk, T, V, heads)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Dims d(N, Cin, Cout, dk, T, V, heads);
@@ -587,11 +571,11 @@ int stgcn_st_attention_forward_train(const float *x, const float *dbn_weight, co
                                      float eps, void *ws, size_t ws_bytes, float *y, float *save_qkv, float *save_o,
                                      float *save_z, float *save_rowstats, float *save_stats, int N, int Cin, int Cout,
                                      int dk, int T, int V, int heads, unsigned flags, void *stream) {
-    STA_REQUIRE(x); STA_REQUIRE(dbn_weight); STA_REQUIRE(dbn_bias); STA_REQUIRE(dbn_running_mean);
-    STA_REQUIRE(dbn_running_var); STA_REQUIRE(Wqkv); STA_REQUIRE(bqkv); STA_REQUIRE(Wout); STA_REQUIRE(bout);
-    STA_REQUIRE(bn_weight); STA_REQUIRE(bn_bias); STA_REQUIRE(bn_running_mean); STA_REQUIRE(bn_running_var);
-    STA_REQUIRE(ws); STA_REQUIRE(y); STA_REQUIRE(save_qkv); STA_REQUIRE(save_o); STA_REQUIRE(save_z);
-    STA_REQUIRE(save_rowstats); STA_REQUIRE(save_stats);
+    REQUIRE_PTR(x); REQUIRE_PTR(dbn_weight); REQUIRE_PTR(dbn_bias); REQUIRE_PTR(dbn_running_mean);
+    REQUIRE_PTR(dbn_running_var); REQUIRE_PTR(Wqkv); REQUIRE_PTR(bqkv); REQUIRE_PTR(Wout); REQUIRE_PTR(bout);
+    REQUIRE_PTR(bn_weight); REQUIRE_PTR(bn_bias); REQUIRE_PTR(bn_running_mean); REQUIRE_PTR(bn_running_var);
+    REQUIRE_PTR(ws); REQUIRE_PTR(y); REQUIRE_PTR(save_qkv); REQUIRE_PTR(save_o); REQUIRE_PTR(save_z);
+    REQUIRE_PTR(save_rowstats); REQUIRE_PTR(save_stats);
     if (int rc = check_shape("st_attention_forward_train", N, Cin, Cout, dk, T, V, heads)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Dims d(N, Cin, Cout, dk, T, V, heads);
@@ -639,11 +623,11 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
                                 float *dWqkv, float *dbqkv, float *dWout, float *dbout, float *dbn_weight_grad,
                                 float *dbn_bias_grad, void *ws, size_t ws_bytes, int N, int Cin, int Cout, int dk, int T,
                                 int V, int heads, unsigned flags, void *stream) {
-    STA_REQUIRE(x); STA_REQUIRE(dbn_weight); STA_REQUIRE(dbn_bias); STA_REQUIRE(Wqkv); STA_REQUIRE(Wout);
-    STA_REQUIRE(bn_weight); STA_REQUIRE(bn_bias); STA_REQUIRE(save_qkv); STA_REQUIRE(save_o); STA_REQUIRE(save_z);
-    STA_REQUIRE(save_rowstats); STA_REQUIRE(save_stats); STA_REQUIRE(dy); STA_REQUIRE(ddbn_weight); STA_REQUIRE(ddbn_bias);
-    STA_REQUIRE(dWqkv); STA_REQUIRE(dbqkv); STA_REQUIRE(dWout); STA_REQUIRE(dbout); STA_REQUIRE(dbn_weight_grad);
-    STA_REQUIRE(dbn_bias_grad); STA_REQUIRE(ws);
+    REQUIRE_PTR(x); REQUIRE_PTR(dbn_weight); REQUIRE_PTR(dbn_bias); REQUIRE_PTR(Wqkv); REQUIRE_PTR(Wout);
+    REQUIRE_PTR(bn_weight); REQUIRE_PTR(bn_bias); REQUIRE_PTR(save_qkv); REQUIRE_PTR(save_o); REQUIRE_PTR(save_z);
+    REQUIRE_PTR(save_rowstats); REQUIRE_PTR(save_stats); REQUIRE_PTR(dy); REQUIRE_PTR(ddbn_weight); REQUIRE_PTR(ddbn_bias);
+    REQUIRE_PTR(dWqkv); REQUIRE_PTR(dbqkv); REQUIRE_PTR(dWout); REQUIRE_PTR(dbout); REQUIRE_PTR(dbn_weight_grad);
+    REQUIRE_PTR(dbn_bias_grad); REQUIRE_PTR(ws);
     if (int rc = check_shape("st_attention_backward", N, Cin, Cout, dk, T, V, heads)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Dims d(N, Cin, Cout, dk, T, V, heads);

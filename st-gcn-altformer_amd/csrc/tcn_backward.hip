@@ -612,10 +612,6 @@ int launch_tcn_dgrad_valu(const float *dz, const float *W, float *dx, int N, int
     return STGCN_OK;
 }
 
-bool tcn_wgrad_mfma_supported(int N, int Cin, int Cout, int T, int V, int K, int stride) {
-    return plan_wgrad(N, Cin, Cout, T, V, K, stride).ok;
-}
-
 size_t tcn_wgrad_ws_bytes(int N, int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
     const unsigned math = flags & STGCN_MATH_MASK;
     if (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) {

@@ -606,7 +606,7 @@ int dispatch_tcn(const float *x, const uint4 *Wp, const float *shift, void *y, i
 bool bf16_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
     const unsigned math = flags & STGCN_MATH_MASK;
     if (math != STGCN_MATH_BF16X3 && math != STGCN_MATH_BF16) return false;
-    const int Tout = (T + 2 * ((K - 1) / 2) - K) / stride + 1;
+    const int Tout = tcn_out_frames(T, K, stride);
     if (Tout < 1) return false;
     if (tcn_v6_supported(Cin, Cout, T, V, K, stride, flags) || tcn_v4_supported(Cin, Cout, T, V, K, stride, flags)) return true;
     Bf16Plan pl;
@@ -649,7 +649,7 @@ int launch_tcn_bf16(const float *x, const void *Wp, const float *shift, void *y,
     const unsigned math = flags & STGCN_MATH_MASK;
     const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
     const int terms = math == STGCN_MATH_BF16X3 ? 3 : 1;
-    const int Tout = (T + 2 * ((K - 1) / 2) - K) / stride + 1;
+    const int Tout = tcn_out_frames(T, K, stride);
     // K = 9, stride 1: large-tile persistent kernels — one wave per SIMD on 16x16x32 where that form covers the shape
     // (diagnostic builds: mask 8192 keeps the eight-wave kernel for A/B runs in one process)
     if (tcn_v6_supported(Cin, Cout, T, V, K, stride, flags) && !(ablate_mask() & 8192))

@@ -611,7 +611,7 @@ bool tcn_mfma_supported(int Cin, int Cout, int T, int V, int K, int stride, unsi
     const unsigned math = flags & STGCN_MATH_MASK;
     if (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16)
         return bf16_supported(Cin, Cout, T, V, K, stride, flags);
-    const int Tout = (T + 2 * ((K - 1) / 2) - K) / stride + 1;
+    const int Tout = tcn_out_frames(T, K, stride);
     return Tout >= 1 && packs_as_mfma(Cin, Cout, math) && mfma_f32_shape_ok(Cin, Cout, V, K, stride, Tout);
 }
 

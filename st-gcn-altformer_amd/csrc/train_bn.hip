@@ -7,6 +7,12 @@
 // statistics do not depend on the reduction order beyond fp64 rounding.
 #include "common.h"
 
+// (file scope: kernel traces keep the name earlier profiles of the training step recorded for it)
+__global__ static void fill_ones_zeros_kernel(float *ones, float *zeros, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < C) { ones[c] = 1.f; zeros[c] = 0.f; }
+}
+
 namespace stgcn {
 
 namespace {
@@ -130,6 +136,13 @@ __global__ void bn_scale_shift_kernel(const float *__restrict__ weight, const fl
 }
 
 }  // namespace
+
+// the unit scale and zero shift the raw-mode kernels take
+int launch_fill_ones_zeros(float *ones, float *zeros, int C, hipStream_t st) {
+    hipLaunchKernelGGL(fill_ones_zeros_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, ones, zeros, C);
+    STGCN_LAUNCH_CHECK("fill_ones_zeros_kernel");
+    return STGCN_OK;
+}
 
 int launch_bn_scale_shift(const float *weight, const float *bias, const float *mean, const float *invstd, float *scale,
                           float *shift, int C, hipStream_t st) {

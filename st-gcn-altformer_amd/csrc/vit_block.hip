@@ -33,20 +33,16 @@ int slab_seqs(int B, int L) {
 }
 
 struct BlockWs {
-    size_t qkv, att, x1, hid, total;
-    BlockWs(int B, int L, int D, int hidden) {
+    float *qkv, *att, *x1, *hid;
+    size_t total;
+    BlockWs(void *base, int B, int L, int D, int hidden) {
         const size_t rows = (size_t)slab_seqs(B, L) * L;
-        size_t o = 0;
-        auto take = [&](size_t floats) {
-            const size_t at = o;
-            o += align_up(floats * sizeof(float), 256);
-            return at;
-        };
-        qkv = take(rows * 3 * D);
-        att = take(rows * D);
-        x1 = take(rows * D);
-        hid = take(rows * hidden);
-        total = o;
+        Carve c(base);
+        qkv = c.take<float>(rows * 3 * D);
+        att = c.take<float>(rows * D);
+        x1 = c.take<float>(rows * D);
+        hid = c.take<float>(rows * hidden);
+        total = c.off;
     }
 };
 
@@ -94,7 +90,7 @@ int stgcn_vit_block_supported(int L, int D, int heads, int hidden) { return bloc
 
 size_t stgcn_vit_block_ws_bytes(int B, int L, int D, int hidden) {
     if (B < 1 || L < 1 || D < 1 || hidden < 1) return 0;
-    return BlockWs(B, L, D, hidden).total;
+    return BlockWs(nullptr, B, L, D, hidden).total;
 }
 
 int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
@@ -110,13 +106,10 @@ int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const flo
         return fail(STGCN_ERR_UNSUPPORTED,
                     "stgcn_vit_block_forward: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
                     "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxL);
-    const BlockWs w(B, L, D, hidden);
+    const BlockWs w(ws, B, L, D, hidden);
     if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward: workspace %zu < %zu bytes", ws_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *base = static_cast<char *>(ws);
-    float *qkv = reinterpret_cast<float *>(base + w.qkv);
-    float *att = reinterpret_cast<float *>(base + w.att), *x1 = reinterpret_cast<float *>(base + w.x1);
-    float *hid = reinterpret_cast<float *>(base + w.hid);
+    float *qkv = w.qkv, *att = w.att, *x1 = w.x1, *hid = w.hid;
     const unsigned math = flags & STGCN_MATH_MASK;
     const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : math;
     const int per = slab_seqs(B, L);
