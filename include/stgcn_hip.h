@@ -363,6 +363,53 @@ int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const flo
                             float eps, float scale, void *ws, size_t ws_bytes, float *y, int B, int L, int D, int heads,
                             int hidden, unsigned flags, void *stream);
 
+/* ---- ViT block: training (additive to ABI 10: new symbols and flag bits only) ------------------------------------------
+ * The training forward is the eval forward's five launches with the tensors the backward reads written to the caller's
+ * `saved` buffer: qkv (M,3D), the attention output (M,D), x1 (M,D), the fc1 output before and after the GELU (M,hidden
+ * each); M = B*L.  scale1 / scale2 (B floats each, or NULL = 1) are stochastic depth's per-sequence factors (0 or
+ * 1 / keep): x1 = x + scale1[b] * branch, y = x1 + scale2[b] * branch.  The backward takes the same two vectors.
+ * No atomics anywhere: reductions over the tokens are partial slabs added in a fixed order, two runs are bit-identical.
+ * Arithmetic: `flags` as in the forward select f32 / bf16x3 for the dgrads (which run the forward's linear kernel on
+ * transposed weights) and STGCN_VIT_QKV_F32 keeps the qkv dgrad in f32; weight gradients, LayerNorm and attention
+ * backward always run in fp32 (v_mfma_f32_32x32x2_f32 where they are products). */
+#define STGCN_VIT_DGELU 0x4000u      /* stgcn_vit_linear_backward: dx is multiplied by GELU'(h_pre) (exact erf form)    */
+#define STGCN_VIT_ACCUMULATE 0x8000u /* stgcn_vit_linear_backward: dx += instead of dx =                                 */
+/* Backward of y = a W^T + b:  dx (M,K) = dy W [* GELU'(h_pre (M,K))] [+ dx],  dW (Nout,K) = dy^T a,  db (Nout) = column sums
+ * of dy.  dx, dW, db may each be NULL (db only with dW); `a` is the linear's input as the forward saw it.
+ * Covered: K % 32 == 0, Nout % 4 == 0, any M.  ws: stgcn_vit_linear_backward_ws_bytes (0 for uncovered shapes). */
+int stgcn_vit_linear_backward_supported(int M, int K, int Nout, unsigned flags);
+size_t stgcn_vit_linear_backward_ws_bytes(int M, int K, int Nout);
+int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, const float *h_pre, float *dx, float *dW,
+                              float *db, void *ws, size_t ws_bytes, int M, int K, int Nout, unsigned flags, void *stream);
+/* dqkv (B,L,3,heads,head_dim) from the packed qkv, the forward's output `out` and its gradient dout (both (B,L,heads*head_dim));
+ * S and P are recomputed on chip.  Same coverage as the forward.  One launch, no workspace. */
+int stgcn_vit_attention_backward_supported(int L, int heads, int head_dim);
+int stgcn_vit_attention_backward(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int heads,
+                                 int head_dim, float scale, void *stream);
+/* LayerNorm backward over the rows of x (M,D), dn = gradient of the LayerNorm's output: dx = rstd (g - mean(g) - xhat
+ * mean(g xhat)) (+ dres), g = dn * weight;  dweight = sum dn xhat,  dbias = sum dn.  D % 4 == 0.  dx may alias dn or dres. */
+size_t stgcn_vit_layernorm_backward_ws_bytes(int M, int D);
+int stgcn_vit_layernorm_backward(const float *x, const float *dn, const float *weight, float eps, const float *dres, float *dx,
+                                 float *dweight, float *dbias, void *ws, size_t ws_bytes, int M, int D, void *stream);
+/* One block, training.  Coverage = stgcn_vit_block_supported.  The size queries return 0 for shapes outside it. */
+int stgcn_vit_block_train_supported(int L, int D, int heads, int hidden);
+size_t stgcn_vit_block_saved_bytes(int B, int L, int D, int hidden);
+size_t stgcn_vit_block_backward_ws_bytes(int B, int L, int D, int hidden);
+int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
+                                  const float *bqkv, const float *Wproj, const float *bproj, const float *norm2_weight,
+                                  const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,
+                                  const float *scale1, const float *scale2, float eps, float scale, void *saved,
+                                  size_t saved_bytes, float *y, int B, int L, int D, int heads, int hidden, unsigned flags,
+                                  void *stream);
+/* dy (B,L,D) -> dx and the twelve parameter gradients (dbqkv may be NULL: qkv_bias=False), each written, not added to. */
+int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
+                             const float *Wproj, const float *norm2_weight, const float *norm2_bias, const float *W1,
+                             const float *W2, const float *scale1, const float *scale2, const void *saved, size_t saved_bytes,
+                             const float *dy, float *dx, float *dnorm1_weight, float *dnorm1_bias, float *dWqkv, float *dbqkv,
+                             float *dWproj, float *dbproj, float *dnorm2_weight, float *dnorm2_bias, float *dW1, float *db1,
+                             float *dW2, float *db2, float eps, float scale, void *ws, size_t ws_bytes, int B, int L, int D,
+                             int heads, int hidden, unsigned flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
-// Launchers of the AltFormer heads' transformer-block kernels (vit_linear.hip, vit_attention.hip), shared with the
-// block entry point in vit_block.hip.  All enqueue on `st` and return a stgcn_status.
+// Launchers of the AltFormer heads' transformer-block kernels (vit_linear.hip, vit_attention.hip, vit_backward.hip) and the
+// coverage rules, shared by the entry points in vit_block.hip (inference) and vit_block_train.hip (training).
+// All launchers enqueue on `st` and return a stgcn_status.
 #pragma once
 
 #include "common.h"
@@ -9,15 +10,82 @@ namespace vit {
 
 constexpr int kMaxL = 256;      // longest sequence the attention kernel keeps on chip
 
+// ---- what the entry points cover (vit_block.hip, vit_block_train.hip) ----
+// Long inputs are walked in slabs of whole sequences of about this many tokens (forward and backward alike).
+constexpr int kSlabRows = 32768;
+constexpr int kMaxLnDim = 4096;   // longest row a LayerNorm is fused over
+
+inline bool math_ok(unsigned flags) {
+    const unsigned m = flags & STGCN_MATH_MASK;
+    return m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3;
+}
+
+inline bool linear_ok(int K, int Nout, bool ln) { return K % 32 == 0 && Nout >= 1 && (!ln || K <= kMaxLnDim); }
+
+inline bool block_ok(int L, int D, int heads, int hidden) {
+    if (L < 1 || D < 1 || heads < 1 || hidden < 1 || D % heads != 0) return false;
+    const int hd = D / heads;
+    return (hd == 32 || hd == 64) && L <= kMaxL && D % 64 == 0 && hidden % 64 == 0 && D <= kMaxLnDim;
+}
+
+inline int slab_seqs(int B, int L) {
+    const int s = kSlabRows / L;
+    return s < 1 ? 1 : (s > B ? B : s);
+}
+
 // Y (M, Nout) = act(LN?(X) W^T + bias) (+ R).  X (M, K), W (Nout, K), K % 32 == 0.  gamma / beta / eps: LayerNorm of X's
 // rows applied while the A tile is staged (gamma == nullptr: none).  math: STGCN_MATH_F32 or STGCN_MATH_BF16X3.
 // Y may alias R (each element is read and written by one thread); it must not alias X.
 int launch_linear(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
                   float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, hipStream_t st);
 
+// What the training forward and the backward add to the linear (all optional, zero-initialised = the plain linear above):
+//   pre      : the value before the activation, acc + bias, is also stored here (M, Nout)           [forward_train: h_pre]
+//   dgelu    : the result is multiplied by GELU'(dgelu[row][col]), exact erf form                   [dgrad of fc2]
+//   rowscale : then by rowscale[row / L] (stochastic depth: one factor per sequence), before R is added
+//   kx       : X's rows are kx long (kx <= K, kx % 4 == 0) and read as zero from kx to K            [dgrad with Nout % 32 != 0]
+struct LinearExtra {
+    float *pre = nullptr;
+    const float *dgelu = nullptr;
+    const float *rowscale = nullptr;
+    int L = 1;
+    int kx = 0;
+};
+int launch_linear_ex(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
+                     float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, const LinearExtra &ex,
+                     hipStream_t st);
+
 // out (B, L, H*hd) = softmax(scale * q k^T) v per (sequence, head) of the packed qkv (B, L, 3, H, hd); hd in {32, 64},
 // L <= kMaxL.
 int launch_attention_packed(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
+
+// ---- backward (vit_backward.hip) ----------------------------------------------------------------------------------------
+// Wt (cols, rows_pad) = W (rows, cols)^T, the columns from `rows` to rows_pad zero-filled: the dgrad dX = dY W is the
+// forward linear on the transposed weight, so it shares launch_linear's kernel, arithmetic modes and epilogues.
+int launch_transpose_pad(const float *W, float *Wt, int rows, int cols, int rows_pad, hipStream_t st);
+
+// Weight / bias gradient of Y = A W^T + b over the rows [0, M):  dW (Nout, K) = (s dY)^T A,  db (Nout) = column sums of s dY,
+// s = rowscale[row / L] or 1.  The reduction over M is cut into wgrad_splits(M, K, Nout) row ranges; each writes one slab of
+// `part` ((Nout * K) floats per split, then Nout floats per split for the bias) and launch_sum_parts adds them in split order.
+// fp32 matrix cores (v_mfma_f32_32x32x2_f32), no atomics.  `accumulate`: add onto dW / db (sum in `tmp` first).
+int wgrad_splits(int M, int K, int Nout);
+size_t wgrad_part_floats(int M, int K, int Nout);   // floats of `part`, and of `tmp` = Nout * K + Nout
+int launch_wgrad(const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part, float *tmp,
+                 int M, int K, int Nout, bool accumulate, hipStream_t st);
+
+// LayerNorm backward over the rows of x (M, D):  dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ dres),  g = dn * gamma; also
+// writes a = LN(x) (the input of the linear behind the LayerNorm, for its wgrad; may be NULL) and the rows' (mean, rstd) to
+// `stats` (M, 2), which launch_ln_param_grad reads for dgamma = sum dn xhat, dbeta = sum dn (two-stage, fixed order).
+// dx may alias dres or dn (one wave owns a row and reads all of it before it writes).
+int launch_ln_backward(const float *x, const float *dn, const float *gamma, const float *beta, float eps, const float *dres,
+                       float *dx, float *a, float *stats, int M, int D, hipStream_t st);
+int ln_param_splits(int M);
+int launch_ln_param_grad(const float *x, const float *dn, const float *stats, float *dgamma, float *dbeta, float *part,
+                         float *tmp, int M, int D, bool accumulate, hipStream_t st);   // part: splits * 2 D, tmp: D floats
+
+// dqkv (B, L, 3, H, hd) from the packed qkv, the forward's output `out` and its gradient `dout` (both (B, L, H*hd)).
+int launch_attention_backward(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int H, int hd,
+                              float scale, hipStream_t st);
 
 }  // namespace vit
 }  // namespace stgcn

@@ -11,27 +11,6 @@ namespace stgcn {
 namespace vit {
 namespace {
 
-constexpr int kSlabRows = 32768;
-constexpr int kMaxLnDim = 4096;   // longest row a LayerNorm is fused over
-
-bool math_ok(unsigned flags) {
-    const unsigned m = flags & STGCN_MATH_MASK;
-    return m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3;
-}
-
-bool linear_ok(int K, int Nout, bool ln) { return K % 32 == 0 && Nout >= 1 && (!ln || K <= kMaxLnDim); }
-
-bool block_ok(int L, int D, int heads, int hidden) {
-    if (L < 1 || D < 1 || heads < 1 || hidden < 1 || D % heads != 0) return false;
-    const int hd = D / heads;
-    return (hd == 32 || hd == 64) && L <= kMaxL && D % 64 == 0 && hidden % 64 == 0 && D <= kMaxLnDim;
-}
-
-int slab_seqs(int B, int L) {
-    const int s = kSlabRows / L;
-    return s < 1 ? 1 : (s > B ? B : s);
-}
-
 struct BlockWs {
     float *qkv, *att, *x1, *hid;
     size_t total;

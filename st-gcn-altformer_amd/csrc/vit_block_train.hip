@@ -1,0 +1,304 @@
+// C entry points for training the AltFormer heads' transformer block (include/stgcn_hip.h, "ViT block: training"):
+// the three backward pieces on their own (linear, attention, LayerNorm), the training forward of one Block, which is the
+// eval forward's five launches writing what the backward reads into the caller's `saved` buffer, and the backward.
+//
+// Backward of one slab of whole sequences (M tokens), in this order, every temporary in the caller's workspace:
+//   dhid = (s2 dy) W2 * GELU'(h_pre)            dW2, db2   = (s2 dy)^T hid
+//   dn   = dhid W1                              LN2 backward: dx1 = dy + ...,  a = LN2(x1),  dnorm2
+//                                               dW1, db1   = dhid^T a
+//   datt = (s1 dx1) Wproj                       dWproj, dbproj = (s1 dx1)^T att
+//   dqkv = attention backward(qkv, att, datt)
+//   dn   = dqkv Wqkv                            LN1 backward: dx = dx1 + ...,  a = LN1(x),   dnorm1
+//                                               dWqkv, dbqkv = dqkv^T a
+// The dgrads are the forward linear kernel on weights transposed once per call (f32 or bf16x3 like the forward); the
+// weight gradients run on the fp32 matrix cores.  Parameter gradients of the second and later slabs are added onto the
+// first slab's in slab order, so the result does not depend on anything but the shapes.
+#include "vit.h"
+
+namespace stgcn {
+namespace vit {
+namespace {
+
+size_t max2(size_t a, size_t b) { return a > b ? a : b; }
+
+// what the training forward keeps for the backward, whole batch: 9 D floats per token at hidden = 2 D
+struct BlockSaved {
+    float *qkv, *att, *x1, *hpre, *hid;
+    size_t total;
+    BlockSaved(void *base, int B, int L, int D, int hidden) {
+        const size_t rows = (size_t)B * L;
+        Carve c(base);
+        qkv = c.take<float>(rows * 3 * D);
+        att = c.take<float>(rows * D);
+        x1 = c.take<float>(rows * D);
+        hpre = c.take<float>(rows * hidden);
+        hid = c.take<float>(rows * hidden);
+        total = c.off;
+    }
+};
+
+// the backward's temporaries: one slab of gradients, the four transposed weights, the partial sums of one reduction
+struct BackwardWs {
+    float *dhid, *dn, *dx1, *datt, *dqkv, *a, *stats, *wt_qkv, *wt_proj, *wt_fc1, *wt_fc2, *part, *tmp;
+    size_t total;
+    BackwardWs(void *base, int B, int L, int D, int hidden) {
+        const int M = slab_seqs(B, L) * L;
+        const size_t rows = (size_t)M;
+        Carve c(base);
+        dhid = c.take<float>(rows * hidden);
+        dn = c.take<float>(rows * D);
+        dx1 = c.take<float>(rows * D);
+        datt = c.take<float>(rows * D);
+        dqkv = c.take<float>(rows * 3 * D);
+        a = c.take<float>(rows * D);
+        stats = c.take<float>(rows * 2);
+        wt_qkv = c.take<float>((size_t)3 * D * D);
+        wt_proj = c.take<float>((size_t)D * D);
+        wt_fc1 = c.take<float>((size_t)D * hidden);
+        wt_fc2 = c.take<float>((size_t)D * hidden);
+        size_t p = wgrad_part_floats(M, D, 3 * D);
+        p = max2(p, wgrad_part_floats(M, D, D));
+        p = max2(p, wgrad_part_floats(M, D, hidden));
+        p = max2(p, wgrad_part_floats(M, hidden, D));
+        p = max2(p, (size_t)ln_param_splits(M) * 2 * D);
+        part = c.take<float>(p);
+        tmp = c.take<float>(max2((size_t)3 * D * D, (size_t)D * hidden) + max2((size_t)3 * D, (size_t)hidden));
+        total = c.off;
+    }
+};
+
+struct LinearBwdWs {
+    float *wt, *part, *tmp;
+    int nout_pad;
+    size_t total;
+    LinearBwdWs(void *base, int M, int K, int Nout) {
+        nout_pad = ceil_div(Nout, 32) * 32;
+        Carve c(base);
+        wt = c.take<float>((size_t)K * nout_pad);
+        part = c.take<float>(wgrad_part_floats(M, K, Nout));
+        tmp = c.take<float>((size_t)Nout * K + Nout);
+        total = c.off;
+    }
+};
+
+struct LnBwdWs {
+    float *stats, *part, *tmp;
+    size_t total;
+    LnBwdWs(void *base, int M, int D) {
+        Carve c(base);
+        stats = c.take<float>((size_t)M * 2);
+        part = c.take<float>((size_t)ln_param_splits(M) * 2 * D);
+        tmp = c.take<float>((size_t)D);
+        total = c.off;
+    }
+};
+
+bool linear_bwd_ok(int M, int K, int Nout, unsigned flags) {
+    return M >= 1 && K >= 1 && Nout >= 1 && K % 32 == 0 && Nout % 4 == 0 && math_ok(flags);
+}
+
+}  // namespace
+}  // namespace vit
+}  // namespace stgcn
+
+using namespace stgcn;
+using namespace stgcn::vit;
+
+extern "C" {
+
+int stgcn_vit_linear_backward_supported(int M, int K, int Nout, unsigned flags) { return linear_bwd_ok(M, K, Nout, flags) ? 1 : 0; }
+
+size_t stgcn_vit_linear_backward_ws_bytes(int M, int K, int Nout) {
+    if (!linear_bwd_ok(M, K, Nout, 0)) return 0;
+    return LinearBwdWs(nullptr, M, K, Nout).total;
+}
+
+int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, const float *h_pre, float *dx, float *dW,
+                              float *db, void *ws, size_t ws_bytes, int M, int K, int Nout, unsigned flags, void *stream) {
+    if (!dy || !ws || M < 1 || K < 1 || Nout < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: null pointer or empty shape");
+    if ((dx != nullptr && !W) || (dW != nullptr && !a) || (db != nullptr && !dW))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: dx needs W, dW needs a, db goes with dW");
+    if (((flags & STGCN_VIT_DGELU) != 0) != (h_pre != nullptr))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: h_pre and STGCN_VIT_DGELU go together");
+    if (dx == dy) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: dx must not alias dy");
+    if (!linear_bwd_ok(M, K, Nout, flags))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_linear_backward: K = %d, Nout = %d, math %u (covered: K %% 32 == 0, Nout %% 4 == 0, "
+                    "f32 / bf16x3)", K, Nout, flags & STGCN_MATH_MASK);
+    const LinearBwdWs w(ws, M, K, Nout);
+    if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_linear_backward: workspace %zu < %zu bytes", ws_bytes, w.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    if (dx != nullptr) {
+        if ((rc = launch_transpose_pad(W, w.wt, Nout, K, w.nout_pad, st))) return rc;
+        LinearExtra ex;
+        ex.dgelu = h_pre;
+        ex.kx = Nout;
+        const float *R = (flags & STGCN_VIT_ACCUMULATE) ? dx : nullptr;
+        if ((rc = launch_linear_ex(dy, w.wt, nullptr, R, nullptr, nullptr, 0.f, dx, M, w.nout_pad, K, false, flags & STGCN_MATH_MASK,
+                                   ex, st)))
+            return rc;
+    }
+    if (dW != nullptr && (rc = launch_wgrad(dy, a, nullptr, 1, dW, db, w.part, w.tmp, M, K, Nout, false, st))) return rc;
+    return STGCN_OK;
+}
+
+int stgcn_vit_attention_backward_supported(int L, int heads, int head_dim) {
+    return L >= 1 && L <= kMaxL && heads >= 1 && (head_dim == 32 || head_dim == 64) ? 1 : 0;
+}
+
+int stgcn_vit_attention_backward(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int heads,
+                                 int head_dim, float scale, void *stream) {
+    if (!qkv || !out || !dout || !dqkv || B < 1 || L < 1 || heads < 1)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_attention_backward: null pointer or empty shape");
+    if (!stgcn_vit_attention_backward_supported(L, heads, head_dim))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention_backward: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)",
+                    L, head_dim, kMaxL);
+    return launch_attention_backward(qkv, out, dout, dqkv, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
+}
+
+size_t stgcn_vit_layernorm_backward_ws_bytes(int M, int D) {
+    if (M < 1 || D < 1 || D % 4 != 0) return 0;
+    return LnBwdWs(nullptr, M, D).total;
+}
+
+int stgcn_vit_layernorm_backward(const float *x, const float *dn, const float *weight, float eps, const float *dres, float *dx,
+                                 float *dweight, float *dbias, void *ws, size_t ws_bytes, int M, int D, void *stream) {
+    if (!x || !dn || !weight || !dx || !dweight || !dbias || !ws || M < 1 || D < 1)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_layernorm_backward: null pointer or empty shape");
+    if (D % 4 != 0) return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_layernorm_backward: D = %d (covered: D %% 4 == 0)", D);
+    const LnBwdWs w(ws, M, D);
+    if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_layernorm_backward: workspace %zu < %zu bytes", ws_bytes, w.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    if ((rc = launch_ln_backward(x, dn, weight, nullptr, eps, dres, dx, nullptr, w.stats, M, D, st))) return rc;
+    return launch_ln_param_grad(x, dn, w.stats, dweight, dbias, w.part, w.tmp, M, D, false, st);
+}
+
+int stgcn_vit_block_train_supported(int L, int D, int heads, int hidden) { return block_ok(L, D, heads, hidden) ? 1 : 0; }
+
+size_t stgcn_vit_block_saved_bytes(int B, int L, int D, int hidden) {
+    if (B < 1 || L < 1 || D < 1 || hidden < 1 || D % 64 != 0 || hidden % 64 != 0 || L > kMaxL) return 0;
+    return BlockSaved(nullptr, B, L, D, hidden).total;
+}
+
+size_t stgcn_vit_block_backward_ws_bytes(int B, int L, int D, int hidden) {
+    if (B < 1 || L < 1 || D < 1 || hidden < 1 || D % 64 != 0 || hidden % 64 != 0 || L > kMaxL) return 0;
+    return BackwardWs(nullptr, B, L, D, hidden).total;
+}
+
+int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
+                                  const float *bqkv, const float *Wproj, const float *bproj, const float *norm2_weight,
+                                  const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,
+                                  const float *scale1, const float *scale2, float eps, float scale, void *saved,
+                                  size_t saved_bytes, float *y, int B, int L, int D, int heads, int hidden, unsigned flags,
+                                  void *stream) {
+    if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !y || !saved)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: null pointer");
+    if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: B = %d", B);
+    if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: y must not alias x");
+    if (!block_ok(L, D, heads, hidden) || !math_ok(flags))
+        return fail(STGCN_ERR_UNSUPPORTED,
+                    "stgcn_vit_block_forward_train: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
+                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxL);
+    const BlockSaved sv(saved, B, L, D, hidden);
+    if (saved_bytes < sv.total)
+        return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward_train: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned math = flags & STGCN_MATH_MASK;
+    const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : math;
+    const int per = slab_seqs(B, L);
+    for (int b0 = 0; b0 < B; b0 += per) {
+        const int nb = B - b0 < per ? B - b0 : per;
+        const int M = nb * L;
+        const size_t r0 = (size_t)b0 * L;
+        const float *xs = x + r0 * D;
+        float *qkv = sv.qkv + r0 * 3 * D, *att = sv.att + r0 * D, *x1 = sv.x1 + r0 * D;
+        LinearExtra e1, eh, e2;
+        e1.rowscale = scale1 != nullptr ? scale1 + b0 : nullptr;
+        e2.rowscale = scale2 != nullptr ? scale2 + b0 : nullptr;
+        e1.L = e2.L = L;
+        eh.pre = sv.hpre + r0 * hidden;
+        int rc;
+        if ((rc = launch_linear(xs, Wqkv, bqkv, nullptr, norm1_weight, norm1_bias, eps, qkv, M, D, 3 * D, false, math_qkv, st)))
+            return rc;
+        if ((rc = launch_attention_packed(qkv, att, nb, L, heads, D / heads, scale, st))) return rc;
+        if ((rc = launch_linear_ex(att, Wproj, bproj, xs, nullptr, nullptr, 0.f, x1, M, D, D, false, math, e1, st))) return rc;
+        if ((rc = launch_linear_ex(x1, W1, b1, nullptr, norm2_weight, norm2_bias, eps, sv.hid + r0 * hidden, M, D, hidden, true, math,
+                                   eh, st)))
+            return rc;
+        if ((rc = launch_linear_ex(sv.hid + r0 * hidden, W2, b2, x1, nullptr, nullptr, 0.f, y + r0 * D, M, hidden, D, false, math, e2,
+                                   st)))
+            return rc;
+    }
+    return STGCN_OK;
+}
+
+int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
+                             const float *Wproj, const float *norm2_weight, const float *norm2_bias, const float *W1,
+                             const float *W2, const float *scale1, const float *scale2, const void *saved, size_t saved_bytes,
+                             const float *dy, float *dx, float *dnorm1_weight, float *dnorm1_bias, float *dWqkv, float *dbqkv,
+                             float *dWproj, float *dbproj, float *dnorm2_weight, float *dnorm2_bias, float *dW1, float *db1,
+                             float *dW2, float *db2, float eps, float scale, void *ws, size_t ws_bytes, int B, int L, int D,
+                             int heads, int hidden, unsigned flags, void *stream) {
+    if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !saved || !dy || !dx ||
+        !dnorm1_weight || !dnorm1_bias || !dWqkv || !dWproj || !dbproj || !dnorm2_weight || !dnorm2_bias || !dW1 || !db1 || !dW2 ||
+        !db2 || !ws)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: null pointer");
+    if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: B = %d", B);
+    if (dx == dy || dx == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: dx must not alias dy or x");
+    if (!block_ok(L, D, heads, hidden) || !math_ok(flags))
+        return fail(STGCN_ERR_UNSUPPORTED,
+                    "stgcn_vit_block_backward: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
+                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxL);
+    const BlockSaved sv(const_cast<void *>(saved), B, L, D, hidden);
+    if (saved_bytes < sv.total)
+        return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
+    const BackwardWs w(ws, B, L, D, hidden);
+    if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: workspace %zu < %zu bytes", ws_bytes, w.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned math = flags & STGCN_MATH_MASK;
+    const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : math;
+    int rc;
+    if ((rc = launch_transpose_pad(Wqkv, w.wt_qkv, 3 * D, D, 3 * D, st))) return rc;
+    if ((rc = launch_transpose_pad(Wproj, w.wt_proj, D, D, D, st))) return rc;
+    if ((rc = launch_transpose_pad(W1, w.wt_fc1, hidden, D, hidden, st))) return rc;
+    if ((rc = launch_transpose_pad(W2, w.wt_fc2, D, hidden, D, st))) return rc;
+    const int per = slab_seqs(B, L);
+    for (int b0 = 0; b0 < B; b0 += per) {
+        const int nb = B - b0 < per ? B - b0 : per;
+        const int M = nb * L;
+        const size_t r0 = (size_t)b0 * L;
+        const bool acc = b0 > 0;
+        const float *xs = x + r0 * D, *dys = dy + r0 * D;
+        const float *qkv = sv.qkv + r0 * 3 * D, *att = sv.att + r0 * D, *x1 = sv.x1 + r0 * D;
+        const float *hpre = sv.hpre + r0 * hidden, *hid = sv.hid + r0 * hidden;
+        const float *s1 = scale1 != nullptr ? scale1 + b0 : nullptr, *s2 = scale2 != nullptr ? scale2 + b0 : nullptr;
+        LinearExtra e2, e1;
+        e2.dgelu = hpre;
+        e2.rowscale = s2;
+        e1.rowscale = s1;
+        e1.L = e2.L = L;
+        // MLP branch
+        if ((rc = launch_linear_ex(dys, w.wt_fc2, nullptr, nullptr, nullptr, nullptr, 0.f, w.dhid, M, D, hidden, false, math, e2, st)))
+            return rc;
+        if ((rc = launch_wgrad(dys, hid, s2, L, dW2, db2, w.part, w.tmp, M, hidden, D, acc, st))) return rc;
+        if ((rc = launch_linear(w.dhid, w.wt_fc1, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, hidden, D, false, math, st)))
+            return rc;
+        if ((rc = launch_ln_backward(x1, w.dn, norm2_weight, norm2_bias, eps, dys, w.dx1, w.a, w.stats, M, D, st))) return rc;
+        if ((rc = launch_ln_param_grad(x1, w.dn, w.stats, dnorm2_weight, dnorm2_bias, w.part, w.tmp, M, D, acc, st))) return rc;
+        if ((rc = launch_wgrad(w.dhid, w.a, nullptr, L, dW1, db1, w.part, w.tmp, M, D, hidden, acc, st))) return rc;
+        // attention branch
+        if ((rc = launch_linear_ex(w.dx1, w.wt_proj, nullptr, nullptr, nullptr, nullptr, 0.f, w.datt, M, D, D, false, math, e1, st)))
+            return rc;
+        if ((rc = launch_wgrad(w.dx1, att, s1, L, dWproj, dbproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
+        if ((rc = launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st))) return rc;
+        if ((rc = launch_linear(w.dqkv, w.wt_qkv, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, 3 * D, D, false, math_qkv, st)))
+            return rc;
+        if ((rc = launch_ln_backward(xs, w.dn, norm1_weight, norm1_bias, eps, w.dx1, dx + r0 * D, w.a, w.stats, M, D, st))) return rc;
+        if ((rc = launch_ln_param_grad(xs, w.dn, w.stats, dnorm1_weight, dnorm1_bias, w.part, w.tmp, M, D, acc, st))) return rc;
+        if ((rc = launch_wgrad(w.dqkv, w.a, nullptr, L, dWqkv, dbqkv, w.part, w.tmp, M, D, 3 * D, acc, st))) return rc;
+    }
+    return STGCN_OK;
+}
+
+}  // extern "C"

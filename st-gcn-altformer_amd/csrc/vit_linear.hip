@@ -18,6 +18,8 @@
 // LayerNorm: every workgroup first takes the (mean, rstd) of its 128 rows (see the kernel) and applies them to the A tile
 // between the global load and the LDS store, so the normalised tensor never exists in memory.
 // No atomics anywhere: one thread owns each output element and sums in a fixed order.
+// Training (vit_block_train.hip) runs this kernel too: the forward with LinearExtra's pre-activation store and row factor,
+// the dgrads as this linear on a transposed weight with the GELU' and row-factor steps of the epilogue (vit.h).
 #include "bf16_common.h"
 #include "vit.h"
 
@@ -61,7 +63,7 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
                                                         const float *__restrict__ bias, const float *R,
                                                         const float *__restrict__ gamma, const float *__restrict__ beta,
                                                         float eps, float *Y, int M, int K, int Nout, int tiles_n,
-                                                        int gelu) {
+                                                        int gelu, const LinearExtra ex) {
     __shared__ __attribute__((aligned(16))) Tiles<MATH> lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -99,12 +101,14 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
         rstd[i] = 1.0f / sqrtf(fmaxf(q / (float)K - ms * ms, 0.f) + eps);
     }
 
+    const int kx = ex.kx > 0 ? ex.kx : K;   // X's row length: K, or (backward) a length that is no multiple of KC, zero-padded
     float4 xa[4], wb[4];
     auto gload = [&](int k0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = m0 + lr + 32 * i, n = n0 + lr + 32 * i;
-            xa[i] = row < M ? *reinterpret_cast<const float4 *>(X + (size_t)row * K + k0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
+            xa[i] = row < M && k0 + lc < kx ? *reinterpret_cast<const float4 *>(X + (size_t)row * kx + k0 + lc)
+                                            : make_float4(0.f, 0.f, 0.f, 0.f);
             wb[i] = n < Nout ? *reinterpret_cast<const float4 *>(W + (size_t)n * K + k0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
@@ -211,8 +215,14 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
                 const int row = m0 + wm * 64 + m * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
                 if (row >= M) continue;
                 float v = acc[m][n][i] + bv;
-                if (gelu) v = 0.5f * v * (1.0f + erff(v * kRsqrt2));
                 const size_t idx = (size_t)row * Nout + col;
+                if (ex.pre != nullptr) ex.pre[idx] = v;
+                if (gelu) v = 0.5f * v * (1.0f + erff(v * kRsqrt2));
+                if (ex.dgelu != nullptr) {   // d GELU / dh = Phi(h) + h phi(h)
+                    const float h = ex.dgelu[idx];
+                    v *= 0.5f * (1.0f + erff(h * kRsqrt2)) + h * 0.39894228040143267794f * __expf(-0.5f * h * h);
+                }
+                if (ex.rowscale != nullptr) v *= ex.rowscale[row / ex.L];
                 if (R != nullptr) v += R[idx];
                 Y[idx] = v;
             }
@@ -224,15 +234,21 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
 
 int launch_linear(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
                   float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, hipStream_t st) {
+    return launch_linear_ex(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, math, LinearExtra{}, st);
+}
+
+int launch_linear_ex(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
+                     float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, const LinearExtra &ex,
+                     hipStream_t st) {
     const int tiles_n = ceil_div(Nout, BN);
     const long long tiles = (long long)tiles_n * ceil_div(M, BM);
     if (tiles > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit linear: %lld tiles", tiles);
     const dim3 grid((unsigned)tiles), block(256);
     if (math == STGCN_MATH_F32)
-        vit_linear_kernel<STGCN_MATH_F32><<<grid, block, 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, tiles_n, gelu);
+        vit_linear_kernel<STGCN_MATH_F32><<<grid, block, 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, tiles_n, gelu, ex);
     else
         vit_linear_kernel<STGCN_MATH_BF16X3><<<grid, block, 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, tiles_n,
-                                                                     gelu);
+                                                                     gelu, ex);
     STGCN_LAUNCH_CHECK("vit_linear_kernel");
     return STGCN_OK;
 }

@@ -31,6 +31,8 @@ STEM_F16MX = 0x400  # stem entry points, with MATH_BF16X3: fp16 x fp16 + two sca
 CONV_ALONG_V = 0x800  # stgcn_tcn_forward[_packed], MATH_F32_VALU: convolve along the joint axis (Unit2D(dim=3))
 VIT_GELU = 0x1000  # stgcn_vit_linear: exact GELU after the bias
 VIT_QKV_F32 = 0x2000  # stgcn_vit_block_forward: the qkv linear in f32 whatever the math bits say
+VIT_DGELU = 0x4000  # stgcn_vit_linear_backward: dx times GELU'(h_pre)
+VIT_ACCUMULATE = 0x8000  # stgcn_vit_linear_backward: dx += instead of dx =
 MATH_F16MX = MATH_BF16X3 | STEM_F16MX   # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
 
 STATUS = {0: "STGCN_OK", -1: "STGCN_ERR_ARG", -2: "STGCN_ERR_UNSUPPORTED",
@@ -81,6 +83,19 @@ PROTOTYPES = {
     "stgcn_vit_block_supported": (c_int, [c_int] * 4),
     "stgcn_vit_block_ws_bytes": (c_size_t, [c_int] * 4),
     "stgcn_vit_block_forward": (c_int, [_P] * 13 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
+    "stgcn_vit_linear_backward_supported": (c_int, [c_int] * 3 + [c_uint]),
+    "stgcn_vit_linear_backward_ws_bytes": (c_size_t, [c_int] * 3),
+    "stgcn_vit_linear_backward": (c_int, [_P] * 8 + [c_size_t] + [c_int] * 3 + [c_uint, _P]),
+    "stgcn_vit_attention_backward_supported": (c_int, [c_int] * 3),
+    "stgcn_vit_attention_backward": (c_int, [_P] * 4 + [c_int] * 4 + [c_float, _P]),
+    "stgcn_vit_layernorm_backward_ws_bytes": (c_size_t, [c_int] * 2),
+    "stgcn_vit_layernorm_backward": (c_int, [_P] * 3 + [c_float] + [_P] * 5 + [c_size_t, c_int, c_int, _P]),
+    "stgcn_vit_block_train_supported": (c_int, [c_int] * 4),
+    "stgcn_vit_block_saved_bytes": (c_size_t, [c_int] * 4),
+    "stgcn_vit_block_backward_ws_bytes": (c_size_t, [c_int] * 4),
+    "stgcn_vit_block_forward_train": (c_int, [_P] * 15 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
+    "stgcn_vit_block_backward": (c_int, [_P] * 12 + [c_size_t] + [_P] * 14 + [c_float, c_float, _P, c_size_t] + [c_int] * 5
+                                 + [c_uint, _P]),
 }
 
 _lib = None

@@ -13,9 +13,15 @@ Two paths, one result:
   the call has at least ``HIP_MIN_TOKENS`` tokens (smaller calls are latency-bound; ``set_hip_min_tokens(model, 0)`` lifts it).
   The head's first patch embedding then runs through ``functional.patch_embed`` on the stem output (contiguous or
   channels-last, consumed in place); pooling, the second embedding and ``mlp_head`` are torch ops.
-* torch ops: everything else - training, ``.eval()`` with gradients, CPU tensors, shapes the kernels do not cover.  This is the
-  reference's arithmetic op for op, so its training scripts keep working unchanged.  (A HIP backward for the block is not
-  part of this module yet.)
+* HIP, training (``stgcn_vit_block_forward_train`` / ``stgcn_vit_block_backward`` behind one ``autograd.Function``): the same
+  input conditions while autograd IS recording something that concerns the block (``.train()``, or ``.eval()`` with gradients),
+  no ``nn.Dropout`` active, at least ``HIP_TRAIN_MIN_TOKENS`` tokens (``set_hip_train_min_tokens``; ``set_hip_min_tokens`` sets
+  both thresholds), env ``STGCN_VIT_TRAIN`` not ``0``.  Stochastic depth is covered: ``Block.draw_drop_path`` draws the two masks
+  with the torch path's calls in its order (same seed, same masks) and the kernels apply them per sequence.  The parameters
+  are taken by attribute, so an ``nn.DataParallel`` replica's gradients reach its master.  ``Block.trains_on_hip(x)`` tells.
+  Default arithmetic ``'f32'`` (``DEFAULT_TRAIN_MATH``, env ``STGCN_VIT_TRAIN_MATH``; ``set_head_math`` overrides both paths).
+* torch ops: everything else - CPU tensors, shapes the kernels do not cover, active dropout, calls under the thresholds,
+  ``force_torch``.  This is the reference's arithmetic op for op, so its training scripts keep working unchanged.
 
 Arithmetic of the block's linears (``set_head_math`` / env ``STGCN_VIT_MATH``): ``'f32'`` (fp32 matrix cores, exact products),
 ``'bf16x3'`` (three bf16 products per fp32 product, fp32 accumulate) or ``'mixed'`` (bf16x3 with the qkv linear in f32: an
@@ -32,6 +38,7 @@ from functools import partial
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import functional as F
 from ._capi import MATH_BF16X3, MATH_F32, VIT_QKV_F32
@@ -45,16 +52,39 @@ def _default_head_math() -> int:
     return HEAD_MATH[os.environ.get("STGCN_VIT_MATH", DEFAULT_HEAD_MATH).lower()]
 
 
+DEFAULT_TRAIN_MATH = "f32"   # the fastest arithmetic whose gradients hold both criteria of the fp32 contract on every tensor,
+#                              in the six block cases and through the twelve blocks of a whole model:
+#                              'mixed' is 9-12 % faster and holds both on a single block, but only the max-norm criterion on some
+#                              tensors of the whole model (1.1e-5 of max|.|); 'bf16x3' holds the max-norm criterion only
+
+
+def _default_train_math() -> int:
+    return HEAD_MATH[os.environ.get("STGCN_VIT_TRAIN_MATH", DEFAULT_TRAIN_MATH).lower()]
+
+
+HIP_TRAIN_MIN_TOKENS = 13200   # forward + backward of a block (tools/time_altformer_train.py at batch 2, 4, 8, 32): every measured
+#                                stage from 13,200 tokens up is faster on HIP by more than the spread (1.29-1.78 x); below, some
+#                                thirty launches per block are latency-bound and the picture is mixed (5,760 tokens at D = 512:
+#                                0.83 x; 6,600 at D = 256: 1.26 x), so such calls stay on torch ops
 HIP_MIN_TOKENS = 4096   # below this many tokens (B * L) per call a block's five launches are latency-bound and the library's
 #                         small GEMMs are as fast or faster (measured at batch 32: the TS head's spatial stage, 1472 and 704
 #                         tokens, 0.32 against 0.27 ms per block): the block then takes its torch path
 
 
 def set_hip_min_tokens(module: nn.Module, tokens: int) -> None:
-    """The token count (B * L) from which every ``Block`` below uses the HIP path where it applies (0: always)."""
+    """The token count (B * L) from which every ``Block`` below uses the HIP path where it applies (0: always).  One knob for
+    "always HIP": it sets the training threshold (``set_hip_train_min_tokens``) to the same value."""
     for sub in module.modules():
         if isinstance(sub, Block):
             sub.hip_min_tokens = int(tokens)
+            sub.hip_train_min_tokens = int(tokens)
+
+
+def set_hip_train_min_tokens(module: nn.Module, tokens: int) -> None:
+    """The token count (B * L) from which every ``Block`` below trains on the HIP kernels where they apply (0: always)."""
+    for sub in module.modules():
+        if isinstance(sub, Block):
+            sub.hip_train_min_tokens = int(tokens)
 
 
 def set_head_math(module: nn.Module, mode) -> None:
@@ -74,14 +104,21 @@ class DropPath(nn.Module):
         self.drop_prob = drop_prob
         self.scale_by_keep = scale_by_keep
 
-    def forward(self, x):
+    def draw(self, x):
+        """This call's per-sample factors (0 or 1 / keep), shape (B, 1, ..., 1), or None where the module is the identity.
+        The only place that consumes random numbers: the torch path multiplies by it, the HIP training path hands it to the
+        kernels, so both use the same masks after the same seed."""
         if self.drop_prob == 0.0 or not self.training:
-            return x
+            return None
         keep = 1.0 - self.drop_prob
         mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
         if keep > 0.0 and self.scale_by_keep:
             mask.div_(keep)
-        return x * mask
+        return mask
+
+    def forward(self, x):
+        mask = self.draw(x)
+        return x if mask is None else x * mask
 
     def extra_repr(self):
         return f"drop_prob={round(self.drop_prob, 3):0.3f}"
@@ -124,6 +161,29 @@ def _drop_active(mod: nn.Module) -> bool:
     return False
 
 
+class _BlockTrain(torch.autograd.Function):
+    """One Block on the HIP training kernels: ``stgcn_vit_block_forward_train`` / ``stgcn_vit_block_backward``.  The twelve
+    parameters arrive as arguments (taken by attribute from the module), so the gradients of an ``nn.DataParallel`` replica's
+    clones flow back to its master through autograd like any other op's."""
+
+    @staticmethod
+    def forward(ctx, x, s1, s2, heads, eps, scale, math, *params):
+        x = x.contiguous()
+        y, saved = F.vit_block_forward_train(x, params, heads, eps, scale, math, s1, s2)
+        ctx.save_for_backward(x, s1, s2, *params)
+        ctx.saved_buf, ctx.cfg = saved, (heads, eps, scale, math)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, s1, s2, *params = ctx.saved_tensors
+        heads, eps, scale, math = ctx.cfg
+        g = F.vit_block_backward(x, params, ctx.saved_buf, dy.contiguous(), heads, eps, scale, math, s1, s2)
+        ctx.saved_buf = None
+        return (g["x"], None, None, None, None, None, None) + tuple(g[n] for n in F.VIT_BLOCK_PARAMS)
+
+
 class Block(nn.Module):
     """``x + attn(norm1(x))`` then ``x + mlp(norm2(x))`` (each branch through ``drop_path``); x is (B, L, dim)."""
 
@@ -139,6 +199,7 @@ class Block(nn.Module):
         self.math_mode = None                  # None: _default_head_math() at call time
         self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
         self.hip_min_tokens = HIP_MIN_TOKENS   # set_hip_min_tokens
+        self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
 
     def _weights(self):
         """The parameters by attribute (an nn.DataParallel replica has no ``parameters()``)."""
@@ -146,8 +207,8 @@ class Block(nn.Module):
             yield lin.weight
             yield lin.bias
 
-    def hip_applies(self, x: torch.Tensor) -> bool:
-        """Whether this call runs on the HIP kernels (see the module docstring)."""
+    def _kernels_cover(self, x: torch.Tensor) -> bool:
+        """CUDA float32 (B, L, D) input and a module the kernels implement (LayerNorms with affine, exact GELU, covered sizes)."""
         if self.force_torch or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
             return False
         if not (type(self.norm1) is nn.LayerNorm and type(self.norm2) is nn.LayerNorm and isinstance(self.mlp.act, nn.GELU)
@@ -155,14 +216,40 @@ class Block(nn.Module):
                 and self.norm2.elementwise_affine and self.norm1.eps == self.norm2.eps
                 and self.norm1.bias is not None and self.norm2.bias is not None):
             return False
-        if torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in self._weights())):
-            return False
-        if _drop_active(self):
-            return False
         B, L, D = x.shape
         if B < 1 or D != self.norm1.normalized_shape[0] or self.mlp.fc2.out_features != D:
             return False
         return F.vit_block_supported(L, D, self.attn.num_heads, self.mlp.fc1.out_features)
+
+    def _records_grad(self, x: torch.Tensor) -> bool:
+        return torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in self._weights()))
+
+    def hip_applies(self, x: torch.Tensor) -> bool:
+        """Whether this call can run on the inference kernels (see the module docstring)."""
+        if x.dim() != 3 or self._records_grad(x) or _drop_active(self):
+            return False
+        return self._kernels_cover(x)
+
+    def trains_on_hip(self, x: torch.Tensor) -> bool:
+        """Whether this call runs on the HIP training kernels (forward that saves for the backward, backward on
+        ``loss.backward()``): autograd is recording something that concerns the block, no ``nn.Dropout`` is active
+        (stochastic depth may be), the shape is covered and the call has at least ``hip_train_min_tokens`` tokens."""
+        if x.dim() != 3 or os.environ.get("STGCN_VIT_TRAIN", "1") == "0" or not self._records_grad(x):
+            return False
+        if x.shape[0] * x.shape[1] < self.hip_train_min_tokens:
+            return False
+        if any(sub.training and sub.p > 0 for sub in self.modules() if isinstance(sub, nn.Dropout)):
+            return False
+        if not isinstance(self.drop_path, (DropPath, nn.Identity)):
+            return False
+        return self._kernels_cover(x)
+
+    def draw_drop_path(self, x: torch.Tensor):
+        """The stochastic-depth factors of this call, attention branch first, then the MLP branch - the order, shapes and
+        generator calls of the torch path - as two (B, 1, 1) tensors, or None where nothing is drawn."""
+        if not isinstance(self.drop_path, DropPath):
+            return None, None
+        return self.drop_path.draw(x), self.drop_path.draw(x)
 
     def uses_hip(self, x: torch.Tensor) -> bool:
         """``hip_applies`` and the call is large enough for the HIP path to be the faster one (``hip_min_tokens``)."""
@@ -177,8 +264,19 @@ class Block(nn.Module):
                                            (a.proj.weight, a.proj.bias), (self.norm2.weight, self.norm2.bias),
                                            (m.fc1.weight, m.fc1.bias), (m.fc2.weight, m.fc2.bias), a.num_heads, self.norm1.eps,
                                            a.scale, math)
+        if self.trains_on_hip(x):
+            s1, s2 = self.draw_drop_path(x)
+            math = _default_train_math() if self.math_mode is None else self.math_mode
+            return _BlockTrain.apply(x, None if s1 is None else s1.reshape(-1), None if s2 is None else s2.reshape(-1),
+                                     self.attn.num_heads, self.norm1.eps, self.attn.scale, math, *self._weights())
         x = x + self.drop_path(self.attn(self.norm1(x)))
         return x + self.drop_path(self.mlp(self.norm2(x)))
+
+
+def max_over_tokens(x):
+    """``x.max(dim=1).values``, the heads' pooling over the frames.  Its gradient goes to the token that holds the maximum, so
+    a tie at the last bit sends it elsewhere; the one place where a comparison of two arithmetic paths can pin the picks."""
+    return x.max(dim=1).values
 
 
 def _embed_on_hip(x, lin) -> bool:
@@ -260,7 +358,7 @@ class ST(_Head):
 
     def forward_features(self, x):
         x = self._second_stage(x, self.Temporal_patch_to_embedding, self.Temporal_pos_embed, self.blocks)
-        feature = x.max(dim=1).values
+        feature = max_over_tokens(x)
         return self.mlp_head(feature), feature.unsqueeze(-1)
 
     def forward(self, x):
@@ -290,7 +388,7 @@ class TS(_Head):
     def Temporal_forward_features(self, x):
         N, _, _, V = x.shape
         x = self._first_stage(x, self.temporal_patch_to_embedding, self.Temporal_pos_embed, self.blocks, "TS")
-        return x.max(dim=1).values.reshape(N, V, -1)
+        return max_over_tokens(x).reshape(N, V, -1)
 
     def Spatial_forward_features(self, x):
         x = self._second_stage(x, self.Spatial_patch_to_embedding, self.Spatial_pos_embed, self.Spatial_blocks)

@@ -595,3 +595,118 @@ def vit_block_forward(x, norm1, qkv, proj, norm2, fc1, fc2, heads, eps, scale, m
                    _dev_ptr(y, "y"), c_int(B), c_int(L), c_int(D), c_int(heads), c_int(hidden), c_uint(_vit_flags(math)),
                    _stream(dev))
     return y
+
+
+# ---- AltFormer heads: training (stgcn_vit_*_backward, stgcn_vit_block_forward_train) ------------------------------------------
+def vit_linear_backward_supported(M, K, Nout, math=MATH_F32) -> bool:
+    return bool(_capi.lib().stgcn_vit_linear_backward_supported(M, K, Nout, math & _capi.MATH_MASK))
+
+
+def vit_linear_backward(dy, a, weight, h_pre=None, dx_accumulate=None, need_dx=True, need_dw=True, need_db=True,
+                        math=MATH_F32):
+    """Backward of ``y = a W^T + b`` on the last axis: returns ``(dx, dW, db)`` (None where not asked for).
+    ``dx = dy W``, multiplied by ``GELU'(h_pre)`` when ``h_pre`` (shape of ``a``) is given - the dgrad of the linear behind
+    a GELU whose input was ``h_pre`` - and added onto ``dx_accumulate`` (in place, returned) when that is given."""
+    dev = dy.device
+    Nout, K = weight.shape
+    M = dy.numel() // Nout
+    dx = None
+    if need_dx:
+        dx = dx_accumulate if dx_accumulate is not None else torch.empty(dy.shape[:-1] + (K,), device=dev, dtype=torch.float32)
+    dW = torch.empty_like(weight) if need_dw else None
+    db = torch.empty(Nout, device=dev, dtype=torch.float32) if need_dw and need_db else None
+    nbytes = _capi.lib().stgcn_vit_linear_backward_ws_bytes(M, K, Nout)
+    ws = _bytes(dev, nbytes)
+    fl = (math & _capi.MATH_MASK) | (_capi.VIT_DGELU if h_pre is not None and need_dx else 0) \
+        | (_capi.VIT_ACCUMULATE if dx_accumulate is not None else 0)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_linear_backward", _dev_ptr(dy, "dy", dev), _dev_ptr(a if need_dw else None, "a", dev),
+                   _dev_ptr(weight, "weight", dev), _dev_ptr(h_pre if need_dx else None, "h_pre", dev), _dev_ptr(dx, "dx", dev),
+                   _dev_ptr(dW, "dW"), _dev_ptr(db, "db"), c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(M), c_int(K),
+                   c_int(Nout), c_uint(fl), _stream(dev))
+    return dx, dW, db
+
+
+def vit_attention_backward(qkv, out, dout, heads, scale=None) -> torch.Tensor:
+    """Gradient of the packed qkv (B, L, 3*D) from the forward's output ``out`` and its gradient ``dout`` (B, L, D)."""
+    dev = qkv.device
+    B, L, D3 = qkv.shape
+    hd = D3 // 3 // heads
+    if hd * heads * 3 != D3 or out.shape != (B, L, D3 // 3) or dout.shape != out.shape:
+        raise ValueError(f"qkv {tuple(qkv.shape)}, out {tuple(out.shape)}, dout {tuple(dout.shape)} with {heads} heads")
+    dqkv = torch.empty_like(qkv)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_attention_backward", _dev_ptr(qkv, "qkv", dev), _dev_ptr(out, "out", dev), _dev_ptr(dout, "dout", dev),
+                   _dev_ptr(dqkv, "dqkv"), c_int(B), c_int(L), c_int(heads), c_int(hd),
+                   c_float(hd ** -0.5 if scale is None else scale), _stream(dev))
+    return dqkv
+
+
+def vit_layernorm_backward(x, dn, weight, eps, dres=None):
+    """LayerNorm backward over the last axis: ``(dx (+ dres), dweight, dbias)`` from ``dn``, the gradient of its output."""
+    dev = x.device
+    D = x.shape[-1]
+    M = x.numel() // D
+    dx = torch.empty_like(x)
+    dw = torch.empty(D, device=dev, dtype=torch.float32)
+    db = torch.empty(D, device=dev, dtype=torch.float32)
+    nbytes = _capi.lib().stgcn_vit_layernorm_backward_ws_bytes(M, D)
+    ws = _bytes(dev, nbytes)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_layernorm_backward", _dev_ptr(x, "x", dev), _dev_ptr(dn, "dn", dev), _dev_ptr(weight, "weight", dev),
+                   c_float(eps), _dev_ptr(dres, "dres", dev), _dev_ptr(dx, "dx"), _dev_ptr(dw, "dweight"), _dev_ptr(db, "dbias"),
+                   c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(M), c_int(D), _stream(dev))
+    return dx, dw, db
+
+
+def vit_block_train_supported(L, D, heads, hidden) -> bool:
+    return bool(_capi.lib().stgcn_vit_block_train_supported(L, D, heads, hidden))
+
+
+VIT_BLOCK_PARAMS = ("norm1.weight", "norm1.bias", "qkv.weight", "qkv.bias", "proj.weight", "proj.bias", "norm2.weight",
+                    "norm2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
+
+
+def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=None, scale2=None):
+    """Training forward of one Block on x (B, L, D): returns ``(y, saved)``.  ``params``: the twelve tensors in the order of
+    ``VIT_BLOCK_PARAMS`` (qkv.bias may be None).  ``scale1`` / ``scale2`` (B,): stochastic depth's per-sequence factors of the
+    attention and the MLP branch (None = 1).  ``saved`` is an opaque buffer for ``vit_block_backward``."""
+    dev = x.device
+    B, L, D = x.shape
+    hidden = params[8].shape[0]
+    nbytes = _capi.lib().stgcn_vit_block_saved_bytes(B, L, D, hidden)
+    saved = _bytes(dev, nbytes)
+    y = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_block_forward_train", _dev_ptr(x, "x", dev),
+                   *[_dev_ptr(p, n, dev) for n, p in zip(VIT_BLOCK_PARAMS, params)],
+                   _dev_ptr(scale1, "scale1", dev), _dev_ptr(scale2, "scale2", dev), c_float(eps), c_float(scale),
+                   c_void_p(saved.data_ptr()), c_size_t(nbytes), _dev_ptr(y, "y"), c_int(B), c_int(L), c_int(D), c_int(heads),
+                   c_int(hidden), c_uint(_vit_flags(math)), _stream(dev))
+    return y, saved
+
+
+def vit_block_backward(x, params, saved, dy, heads, eps, scale, math=MATH_F32, scale1=None, scale2=None) -> dict:
+    """Backward of ``vit_block_forward_train`` (same arguments): ``{"x": dx, "norm1.weight": ..., ...}`` with a gradient for
+    ``x`` and for every entry of ``VIT_BLOCK_PARAMS`` (``qkv.bias``: None when the block has none)."""
+    dev = x.device
+    B, L, D = x.shape
+    hidden = params[8].shape[0]
+    sbytes = _capi.lib().stgcn_vit_block_saved_bytes(B, L, D, hidden)
+    nbytes = _capi.lib().stgcn_vit_block_backward_ws_bytes(B, L, D, hidden)
+    if saved.numel() * saved.element_size() < sbytes:
+        raise ValueError("saved does not come from vit_block_forward_train of these shapes")
+    ws = _bytes(dev, nbytes)
+    grads = {"x": torch.empty_like(x)}
+    for n, p in zip(VIT_BLOCK_PARAMS, params):
+        grads[n] = None if p is None else torch.empty_like(p)
+    w = dict(zip(VIT_BLOCK_PARAMS, params))
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_block_backward", _dev_ptr(x, "x", dev),
+                   *[_dev_ptr(w[n], n, dev) for n in ("norm1.weight", "norm1.bias", "qkv.weight", "proj.weight", "norm2.weight",
+                                                      "norm2.bias", "fc1.weight", "fc2.weight")],
+                   _dev_ptr(scale1, "scale1", dev), _dev_ptr(scale2, "scale2", dev), c_void_p(saved.data_ptr()), c_size_t(sbytes),
+                   _dev_ptr(dy, "dy", dev), _dev_ptr(grads["x"], "dx"), *[_dev_ptr(grads[n], "d" + n) for n in VIT_BLOCK_PARAMS],
+                   c_float(eps), c_float(scale), c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(B), c_int(L), c_int(D),
+                   c_int(heads), c_int(hidden), c_uint(_vit_flags(math)), _stream(dev))
+    return grads

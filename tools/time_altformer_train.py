@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Time training of the AltFormer heads: forward + backward of one transformer block at every stage of both heads, and one
+training step (forward, CrossEntropyLoss, backward, no optimizer) of the whole ST / TS models in ``.train()`` with stochastic
+depth on - the HIP training path against the torch-op path of the same module, in one process, alternating, device events.
+
+    python tools/time_altformer_train.py [--batch 32] [--repeats 7] [--warmup 2] [--out profiles/altformer_train_times.json]
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/time_altformer_train.py --stages-only --repeats 5
+
+Prints ONE JSON line.  Per stage: ms of forward + backward (min, median, max, ``spread`` = (max - min) / min) of the torch
+path and of the HIP path in each arithmetic ('f32', 'mixed', 'bf16x3'), the speed-up of the default arithmetic, and
+``hip_faster`` = the HIP median is below the torch median by more than the larger of the two spreads (the rule
+``HIP_TRAIN_MIN_TOKENS`` follows).  Whole models: ms per step and clips/s for both paths.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+from functools import partial
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "st-gcn-altformer_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from time_altformer import STAGES, alternate, summary   # noqa: E402  (same stages, same way of timing)
+
+MODES = ("f32", "mixed", "bf16x3")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--stages-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert args.repeats >= 5
+    import stgcn_amd
+    from stgcn_amd.altformer import DEFAULT_TRAIN_MATH, HIP_TRAIN_MIN_TOKENS, Block, set_head_math, set_hip_min_tokens
+    dev = torch.device("cuda:0")
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    res = {"batch": args.batch, "repeats": args.repeats, "default_train_math": DEFAULT_TRAIN_MATH,
+           "hip_train_min_tokens": HIP_TRAIN_MIN_TOKENS, "device": torch.cuda.get_device_name(0), "stages": {}, "models": {}}
+    for name, (per_clip, L, D) in STAGES.items():
+        B = args.batch * per_clip
+        torch.manual_seed(0)
+        blk = Block(D, 8, mlp_ratio=2., qkv_bias=True, drop_path=0.1, norm_layer=norm).to(dev).train()
+        x = torch.randn(B, L, D, device=dev, requires_grad=True)
+        dy = torch.randn(B, L, D, device=dev)
+        chooses = "hip" if blk.trains_on_hip(x) else "torch"
+        blk.hip_train_min_tokens = 0
+
+        def run(mode):
+            blk.force_torch = mode == "torch"
+            if mode != "torch":
+                set_head_math(blk, mode)
+                assert blk.trains_on_hip(x)
+            x.grad = None
+            for p in blk.parameters():
+                p.grad = None
+            blk(x).backward(dy)
+        ts = alternate({m: partial(run, m) for m in ("torch",) + MODES}, args.repeats, args.warmup)
+        tor, hip = ts["torch"], ts[DEFAULT_TRAIN_MATH]
+        margin = max(summary(tor)["spread"], summary(hip)["spread"])
+        res["stages"][name] = {
+            "B": B, "L": L, "D": D, "tokens": B * L, "module_chooses": chooses, "torch_ms": summary(tor),
+            **{f"hip_{m}_ms": summary(ts[m]) for m in MODES},
+            "speedup_median": round(statistics.median(tor) / statistics.median(hip), 3),
+            "hip_faster": statistics.median(hip) * (1 + margin) < statistics.median(tor)}
+        del blk, x, dy
+        torch.cuda.empty_cache()
+    for style in () if args.stages_only else ("ST", "TS"):
+        torch.manual_seed(1)
+        model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=22, style=style,
+                                           graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).train()
+        clips = torch.randn(args.batch, 180, 22, 3, device=dev)
+        labels = torch.arange(args.batch, device=dev) % 14
+        ce = torch.nn.CrossEntropyLoss()
+        blocks = [b for b in model.modules() if isinstance(b, Block)]
+
+        def step(path):
+            for b in blocks:
+                b.force_torch = path == "torch"
+            if path == "hip_all":
+                set_hip_min_tokens(model, 0)
+            elif path == "hip":
+                for b in blocks:
+                    b.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS
+            model.zero_grad(set_to_none=True)
+            ce(model(clips), labels).backward()
+        ts = alternate({p: partial(step, p) for p in ("torch", "hip", "hip_all")}, args.repeats, args.warmup)
+        med = {k: statistics.median(v) for k, v in ts.items()}
+        res["models"][style] = {
+            "torch_ms": summary(ts["torch"]), "hip_ms": summary(ts["hip"]), "hip_every_block_ms": summary(ts["hip_all"]),
+            "speedup_median": round(med["torch"] / med["hip"], 3),
+            "clips_per_s_hip": round(args.batch / (med["hip"] * 1e-3), 1),
+            "clips_per_s_torch": round(args.batch / (med["torch"] * 1e-3), 1)}
+        del model
+        torch.cuda.empty_cache()
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
