@@ -118,9 +118,11 @@ __device__ __forceinline__ float relu1(float x) {
 
 // Result stores of the NARROW kernel's epilogue: NON-TEMPORAL (round 3).  The 0.5 GB of output per launch pass through the same
 // 4 MiB L2s that serve the weight ring (2.4 GB per launch, re-read by every tile); streamed as `nt` whole 128-byte lines displace
-// less of it: 0.9-1.7 % off the kernel in same-box A/Bs of two libraries (tools/ab_libs.sh; write-through `sc1` stores
-// instead: 11 % slower).  The WIDE form keeps plain stores: its 8-byte pair stores fill a line from two workgroups a tile
-// apart, and pushed out early as `nt` halves they measured 3 % slower.  -DV6_PLAIN_STORES builds the plain form for that A/B.
+// less of it.  Round 3 measured 0.9-1.7 % off the kernel in same-box A/Bs of two libraries (tools/ab_libs.sh; write-through
+// `sc1` stores instead: 11 % slower) — on an epilogue in which every 16-channel block still waited for the previous block's
+// stores; DESIGN section 3 ("The narrow kernel's tile tail") records where that A/B stands on the straight-line epilogue.
+// The WIDE form keeps plain stores: its 8-byte pair stores fill a line from two workgroups a tile apart, and pushed out early
+// as `nt` halves they measured 3 % slower.  -DV6_PLAIN_STORES builds the plain form for that A/B.
 template <bool NT>
 __device__ __forceinline__ void st_out4(float *p, const float4 &v) {
 #ifndef V6_PLAIN_STORES
@@ -397,6 +399,19 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
         split8(w8, hi, lo);
         W12q[(size_t)kh * C + c] = hi;
         W12q[(size_t)(2 + kh) * C + c] = lo;
+    }
+    // Folded-BN shift of this workgroup's 128 output channels (narrow form), read ONCE: lane l keeps channels l and 64 + l in
+    // two registers, and the epilogue fetches a lane's four channel rows of a 16-channel block from them through the LDS
+    // crossbar (ds_bpermute: counts in lgkmcnt, touches no memory).  A per-block global load of the shift shares vmcnt with
+    // the result stores: it made every block wait for the previous block's stores to complete (eight store round trips in
+    // series per tile).  Eight float4 per lane instead would not fit every instantiation (the wide bf16 form holds 252
+    // AGPRs, K3v6 with statistics 256), and 512 B of LDS would take the kernel from C = 256 shapes that fill the budget.
+    // Three-term narrow form only: its main loop comes out instruction for instruction as without them.  The one-term form
+    // and the WIDE form keep their per-block load (see their epilogues and DESIGN section 3).
+    float sh_lo = 0.f, sh_hi = 0.f;
+    if constexpr (!WIDE && TERMS == 3) {
+        sh_lo = shift[cg * 128 + lane];
+        sh_hi = shift[cg * 128 + 64 + lane];
     }
     int tile = blockIdx.x;
     {
@@ -680,69 +695,165 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
                     }
                 }
             }
-        } else if (abl & OPT_OUT_NTVC) {
-            // (N,T,V,C): staged pixel-major [64 px][16 ch]: a lane's four channels of a pixel are one 16-byte slot
-            // (slot XOR-swizzled by the pixel: conflict-free b128 accesses); a store then writes 16 pixels x 64 B
-            const unsigned lterm = (unsigned)((lane >> 2) * C + 4 * (lane & 3));
+        } else {
+            if constexpr (TERMS == 1) {
+                // One term: the epilogue as it was (per-block shift load, a branch per store).  With the two-form epilogue below
+                // hipcc's allocation moved in this instantiation's MAIN LOOP (1,045 -> 1,073 instructions per period, 24 more AGPR
+                // copies; with the shift re-read per tile just the same), which its contract does not allow.
+                if (abl & OPT_OUT_NTVC) {
+                    // (N,T,V,C): staged pixel-major [64 px][16 ch]: a lane's four channels of a pixel are one 16-byte slot
+                    // (slot XOR-swizzled by the pixel: conflict-free b128 accesses); a store then writes 16 pixels x 64 B
+                    const unsigned lterm = (unsigned)((lane >> 2) * C + 4 * (lane & 3));
 #pragma unroll
-            for (int mb = 0; mb < 8; ++mb) {
-                const int ob = cg * 128 + mb * 16;
-                const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 4 * (lane >> 4));
+                    for (int mb = 0; mb < 8; ++mb) {
+                        const int ob = cg * 128 + mb * 16;
+                        const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 4 * (lane >> 4));
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) {
-                    const int px = nb * 16 + (lane & 15);
-                    const float4 v = make_float4(fmaxf(acc[mb][nb][0] + sh4.x, 0.f), fmaxf(acc[mb][nb][1] + sh4.y, 0.f),
-                                                 fmaxf(acc[mb][nb][2] + sh4.z, 0.f), fmaxf(acc[mb][nb][3] + sh4.w, 0.f));
-                    *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
-                }
-                const size_t tbase = ((size_t)n * TV + qw) * C + ob;      // scalar
+                        for (int nb = 0; nb < 4; ++nb) {
+                            const int px = nb * 16 + (lane & 15);
+                            const float4 v = make_float4(fmaxf(acc[mb][nb][0] + sh4.x, 0.f), fmaxf(acc[mb][nb][1] + sh4.y, 0.f),
+                                                         fmaxf(acc[mb][nb][2] + sh4.z, 0.f), fmaxf(acc[mb][nb][3] + sh4.w, 0.f));
+                            *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
+                        }
+                        const size_t tbase = ((size_t)n * TV + qw) * C + ob;      // scalar
 #pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const int idx = it * 64 + lane, px = idx >> 2, sl = idx & 3;
-                    const float4 v = *reinterpret_cast<const float4 *>(stg + px * 16 + ((sl ^ (px & 3)) << 2));
-                    if (full || qw + px <= g.q_last) {
-                        if constexpr (BF16OUT) {
-                            unsigned short *yb = reinterpret_cast<unsigned short *>(y) + tbase + (size_t)(it * 16) * C;
-                            *reinterpret_cast<uint2 *>(yb + lterm) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-                        } else {
-                            float *yb = reinterpret_cast<float *>(y) + tbase + (size_t)(it * 16) * C;
-                            st_out4<true>(yb + lterm, v);
+                        for (int it = 0; it < 4; ++it) {
+                            const int idx = it * 64 + lane, px = idx >> 2, sl = idx & 3;
+                            const float4 v = *reinterpret_cast<const float4 *>(stg + px * 16 + ((sl ^ (px & 3)) << 2));
+                            if (full || qw + px <= g.q_last) {
+                                if constexpr (BF16OUT) {
+                                    unsigned short *yb = reinterpret_cast<unsigned short *>(y) + tbase + (size_t)(it * 16) * C;
+                                    *reinterpret_cast<uint2 *>(yb + lterm) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+                                } else {
+                                    float *yb = reinterpret_cast<float *>(y) + tbase + (size_t)(it * 16) * C;
+                                    st_out4<true>(yb + lterm, v);
+                                }
+                            }
+                        }
+                    }
+                } else {
+                    // element offset of (row = idx>>4, 4-pixel group c4 = 4*(idx&15)) for idx = it*64 + lane
+                    const unsigned lterm = (unsigned)((lane >> 4) * TV + 4 * (lane & 15));
+                    const int c4l = 4 * (lane & 15);
+#pragma unroll
+                    for (int mb = 0; mb < 8; ++mb) {
+                        const int ob = cg * 128 + mb * 16;
+                        const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 4 * (lane >> 4));
+                        const float shv[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
+#pragma unroll
+                        for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(acc[mb][nb][r] + shv[r], 0.f);
+                        const size_t tbase = ((size_t)n * C + ob) * TV + qw;      // scalar
+                        const bool al16 = ((tbase & 3) == 0) && (TV % 4 == 0);    // 16-byte (8-byte for bf16) aligned rows
+#pragma unroll
+                        for (int it = 0; it < 4; ++it) {
+                            const float4 v = *reinterpret_cast<const float4 *>(stg + (it * 4 + (lane >> 4)) * 64 + c4l);
+                            const size_t sbase = tbase + (size_t)(it * 4) * TV;    // scalar
+                            if (full && al16) {
+                                if constexpr (BF16OUT)
+                                    *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + sbase + lterm) =
+                                        make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+                                else
+                                    st_out4<true>(reinterpret_cast<float *>(y) + sbase + lterm, v);
+                            } else {                                     // last tile of a clip / unaligned rows: element by element
+                                const float e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                                for (int e = 0; e < 4; ++e)
+                                    if (qw + c4l + e <= g.q_last) store_out<BF16OUT>(y, sbase + lterm + e, e4[e]);
+                            }
                         }
                     }
                 }
-            }
-        } else {
-            // element offset of (row = idx>>4, 4-pixel group c4 = 4*(idx&15)) for idx = it*64 + lane
-            const unsigned lterm = (unsigned)((lane >> 4) * TV + 4 * (lane & 15));
-            const int c4l = 4 * (lane & 15);
-#pragma unroll
-            for (int mb = 0; mb < 8; ++mb) {
-                const int ob = cg * 128 + mb * 16;
-                const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 4 * (lane >> 4));
-                const float shv[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb)
+            } else {
+                // The narrow forms below exist twice, chosen by ONE uniform branch per tile: FAST (every pixel inside the clip, rows
+                // aligned) is straight-line code whose stores issue back to back — nothing between a tile's first and last store
+                // waits on vmcnt, so the next tile's x loads (issued above) and the stores all stay in flight; the other keeps the
+                // per-lane / per-element bounds checks for a clip's last tile and unaligned rows.
+                const int bpa = 16 * (lane >> 4);                        // ds_bpermute byte address of source lane 4 * (lane >> 4)
+                // shift of channel rows 4*(lane>>4) + r, r = 0 .. 3, of 16-channel block mb
+                auto block_shift = [&](int mb, float (&shv)[4]) {
+                    const int src = __builtin_bit_cast(int, mb < 4 ? sh_lo : sh_hi);
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(acc[mb][nb][r] + shv[r], 0.f);
-                const size_t tbase = ((size_t)n * C + ob) * TV + qw;      // scalar
-                const bool al16 = ((tbase & 3) == 0) && (TV % 4 == 0);    // 16-byte (8-byte for bf16) aligned rows
+                        shv[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bpa + 4 * ((mb & 3) * 16 + r), src));
+                };
+                if (abl & OPT_OUT_NTVC) {
+                    // (N,T,V,C): staged pixel-major [64 px][16 ch]: a lane's four channels of a pixel are one 16-byte slot
+                    // (slot XOR-swizzled by the pixel: conflict-free b128 accesses); a store then writes 16 pixels x 64 B
+                    const unsigned lterm = (unsigned)((lane >> 2) * C + 4 * (lane & 3));
+                    auto blocks = [&](auto fast_c) {
+                        constexpr bool FAST = decltype(fast_c)::value;
 #pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const float4 v = *reinterpret_cast<const float4 *>(stg + (it * 4 + (lane >> 4)) * 64 + c4l);
-                    const size_t sbase = tbase + (size_t)(it * 4) * TV;    // scalar
-                    if (full && al16) {
-                        if constexpr (BF16OUT)
-                            *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + sbase + lterm) =
-                                make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-                        else
-                            st_out4<true>(reinterpret_cast<float *>(y) + sbase + lterm, v);
-                    } else {                                     // last tile of a clip / unaligned rows: element by element
-                        const float e4[4] = {v.x, v.y, v.z, v.w};
+                        for (int mb = 0; mb < 8; ++mb) {
+                            const int ob = cg * 128 + mb * 16;
+                            float shv[4];
+                            block_shift(mb, shv);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (qw + c4l + e <= g.q_last) store_out<BF16OUT>(y, sbase + lterm + e, e4[e]);
-                    }
+                            for (int nb = 0; nb < 4; ++nb) {
+                                const int px = nb * 16 + (lane & 15);
+                                const float4 v = make_float4(fmaxf(acc[mb][nb][0] + shv[0], 0.f), fmaxf(acc[mb][nb][1] + shv[1], 0.f),
+                                                             fmaxf(acc[mb][nb][2] + shv[2], 0.f), fmaxf(acc[mb][nb][3] + shv[3], 0.f));
+                                *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
+                            }
+                            const size_t tbase = ((size_t)n * TV + qw) * C + ob;      // scalar
+#pragma unroll
+                            for (int it = 0; it < 4; ++it) {
+                                const int idx = it * 64 + lane, px = idx >> 2, sl = idx & 3;
+                                const float4 v = *reinterpret_cast<const float4 *>(stg + px * 16 + ((sl ^ (px & 3)) << 2));
+                                if (FAST || qw + px <= g.q_last) {
+                                    if constexpr (BF16OUT) {
+                                        unsigned short *yb = reinterpret_cast<unsigned short *>(y) + tbase + (size_t)(it * 16) * C;
+                                        *reinterpret_cast<uint2 *>(yb + lterm) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+                                    } else {
+                                        float *yb = reinterpret_cast<float *>(y) + tbase + (size_t)(it * 16) * C;
+                                        st_out4<true>(yb + lterm, v);
+                                    }
+                                }
+                            }
+                        }
+                    };
+                    if (full) blocks(std::true_type{}); else blocks(std::false_type{});
+                } else {
+                    // element offset of (row = idx>>4, 4-pixel group c4 = 4*(idx&15)) for idx = it*64 + lane
+                    const unsigned lterm = (unsigned)((lane >> 4) * TV + 4 * (lane & 15));
+                    const int c4l = 4 * (lane & 15);
+                    const size_t tb0 = ((size_t)n * C + cg * 128) * TV + qw;      // scalar: the wave's pixels in channel row 0 of the group
+                    // 16-byte (8-byte for bf16) aligned rows: the same for all eight blocks (a block is 16 rows of TV further)
+                    const bool al16 = ((tb0 & 3) == 0) && (TV % 4 == 0);
+                    auto blocks = [&](auto fast_c) {
+                        constexpr bool FAST = decltype(fast_c)::value;
+#pragma unroll
+                        for (int mb = 0; mb < 8; ++mb) {
+                            float shv[4];
+                            block_shift(mb, shv);
+#pragma unroll
+                            for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+                                for (int r = 0; r < 4; ++r)
+                                    stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(acc[mb][nb][r] + shv[r], 0.f);
+                            const size_t tbase = tb0 + (size_t)(mb * 16) * TV;        // scalar
+#pragma unroll
+                            for (int it = 0; it < 4; ++it) {
+                                const float4 v = *reinterpret_cast<const float4 *>(stg + (it * 4 + (lane >> 4)) * 64 + c4l);
+                                const size_t sbase = tbase + (size_t)(it * 4) * TV;    // scalar
+                                if constexpr (FAST) {
+                                    if constexpr (BF16OUT)
+                                        *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + sbase + lterm) =
+                                            make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+                                    else
+                                        st_out4<true>(reinterpret_cast<float *>(y) + sbase + lterm, v);
+                                } else {                                     // last tile of a clip / unaligned rows: element by element
+                                    const float e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                                    for (int e = 0; e < 4; ++e)
+                                        if (qw + c4l + e <= g.q_last) store_out<BF16OUT>(y, sbase + lterm + e, e4[e]);
+                                }
+                            }
+                        }
+                    };
+                    if (full && al16) blocks(std::true_type{}); else blocks(std::false_type{});
                 }
             }
         }
