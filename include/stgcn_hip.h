@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define STGCN_ABI_VERSION 10
+#define STGCN_ABI_VERSION 11
 
 typedef enum {
     STGCN_OK = 0,
@@ -131,6 +131,10 @@ int stgcn_agcn_forward(const float *x, const float *A_eff, const float *Wa, cons
 size_t stgcn_tcn_packed_bytes(int Cin, int Cout, int K, unsigned flags);
 /* 1 when the matrix-core kernel of `flags` covers the shape, 0 when only STGCN_MATH_F32_VALU does */
 int stgcn_tcn_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
+/* Name of the kernel stgcn_tcn_forward[_packed] launches for the shape ("tcn_bf16_v6_kernel", "tcn_bf16_v4_kernel",
+ * "tcn_mfma_bf16_kernel", "tcn_mfma_f32_kernel", "tcn_valu_kernel", "tcn_valu_joint_axis_kernel"; "" when the call is
+ * refused) — for profilers and benchmarks that match kernel names in rocprofv3 output.  (ABI 11) */
+const char *stgcn_tcn_kernel_name(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
 int stgcn_tcn_pack(const float *W, const float *scale, void *Wp, int Cin, int Cout, int K,
                    unsigned flags, void *stream);
 int stgcn_tcn_forward_packed(const float *x, const void *Wp, const float *shift, void *y, int N,

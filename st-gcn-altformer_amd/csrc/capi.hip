@@ -156,12 +156,17 @@ int stgcn_agcn_forward(const float *x, const float *A_eff, const float *Wa, cons
 
 size_t stgcn_tcn_packed_bytes(int Cin, int Cout, int K, unsigned flags) {
     if (Cin <= 0 || Cout <= 0 || K <= 0) return 0;
-    return tcn_packed_bytes(Cin, Cout, K, flags);
+    return plan_tcn_pack(Cin, Cout, K, flags).bytes;
 }
 
 int stgcn_tcn_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
     if (Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || K <= 0 || stride <= 0) return 0;
-    return tcn_mfma_supported(Cin, Cout, T, V, K, stride, flags) ? 1 : 0;
+    return tcn_on_matrix_cores(plan_tcn(Cin, Cout, T, V, K, stride, flags).kernel) ? 1 : 0;
+}
+
+const char *stgcn_tcn_kernel_name(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
+    if (Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || K <= 0 || stride <= 0) return "";
+    return tcn_kernel_name(plan_tcn(Cin, Cout, T, V, K, stride, flags).kernel);
 }
 
 int stgcn_stem_supported(int Cin, int C, int T, int V, int K, int subsets, unsigned flags) {
@@ -173,7 +178,7 @@ int stgcn_tcn_pack(const float *W, const float *scale, void *Wp, int Cin, int Co
                    void *stream) {
     REQUIRE_PTR(W); REQUIRE_PTR(scale); REQUIRE_PTR(Wp);
     REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(K);
-    return launch_tcn_pack(W, scale, Wp, Cin, Cout, K, flags, (hipStream_t)stream);
+    return launch_tcn_pack(plan_tcn_pack(Cin, Cout, K, flags), W, scale, Wp, Cin, Cout, K, (hipStream_t)stream);
 }
 
 int stgcn_tcn_forward_packed(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin,
@@ -181,7 +186,8 @@ int stgcn_tcn_forward_packed(const float *x, const void *Wp, const float *shift,
     REQUIRE_PTR(x); REQUIRE_PTR(Wp); REQUIRE_PTR(shift); REQUIRE_PTR(y);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(K);
     REQUIRE_POS(stride);
-    return launch_tcn(x, Wp, shift, y, N, Cin, Cout, T, V, K, stride, flags, (hipStream_t)stream);
+    return launch_tcn(plan_tcn(Cin, Cout, T, V, K, stride, flags), x, Wp, shift, y, N, Cin, Cout, T, V, K, stride, flags,
+                      (hipStream_t)stream);
 }
 
 int stgcn_tcn_forward(const float *x, const float *W, const float *scale, const float *shift, void *y, int N,
@@ -189,7 +195,7 @@ int stgcn_tcn_forward(const float *x, const float *W, const float *scale, const 
                       unsigned flags, void *stream) {
     REQUIRE_PTR(ws);
     REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(K);
-    const size_t need = tcn_packed_bytes(Cin, Cout, K, flags);
+    const size_t need = plan_tcn_pack(Cin, Cout, K, flags).bytes;
     if (ws_bytes < need)
         return fail(STGCN_ERR_WORKSPACE, "tcn_forward: workspace %zu B < %zu B", ws_bytes, need);
     int rc = stgcn_tcn_pack(W, scale, ws, Cin, Cout, K, flags, stream);
@@ -363,7 +369,7 @@ int stgcn_tcn_forward_train(const float *x, const float *W, const float *conv_bi
     const TcnTrainPlan pl = plan_tcn_train(N, Cin, Cout, T, V, K, stride, flags);
     if (pl.ws_bytes == 0) return fail(STGCN_ERR_ARG, "tcn_forward_train: T=%d K=%d stride=%d gives no output frame", T, K, stride);
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "tcn_forward_train: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);
-    if (pl.flags & STGCN_OUT_BF16) return fail(STGCN_ERR_UNSUPPORTED, "tcn_forward_train: fp32 output only");
+    if (flags & STGCN_OUT_BF16) return fail(STGCN_ERR_UNSUPPORTED, "tcn_forward_train: fp32 output only");
     return launch_tcn_forward_train(pl, x, W, conv_bias, bn_weight, bn_bias, bn_running_mean, bn_running_var, momentum, eps, ws, y,
                                     save_z, save_mean, save_invstd, N, Cin, Cout, T, V, K, stride, (hipStream_t)stream);
 }

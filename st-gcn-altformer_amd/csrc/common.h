@@ -147,26 +147,57 @@ int launch_agcn_expand(const float *x, const float *P, const float *Wd, const fl
                        const float *bn_shift, const float *down_scale, const float *down_shift,
                        float *y, int N, int Cin, int Cout, int T, int V, int S, int mode, hipStream_t st);
 
-// temporal conv
-size_t tcn_packed_bytes(int Cin, int Cout, int K, unsigned flags);          // everything launch_tcn_pack writes
-size_t tcn_packed_single_bytes(int Cin, int Cout, int K, unsigned flags);   // the first layout alone (a pair-order copy may follow)
-int launch_tcn_pack(const float *W, const float *scale, void *Wp, int Cin, int Cout, int K,
-                    unsigned flags, hipStream_t st);
-int launch_tcn(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin,
-               int Cout, int T, int V, int K, int stride, unsigned flags, hipStream_t st);
-
-// bf16 matrix-core variants (tcn_bf16.hip)
-bool bf16_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
-bool bf16_packs(int Cin, int Cout, unsigned math);
+// temporal conv (Unit2D): the plan every entry point reads (tcn.hip; the packed blob's layout is described there)
+enum class TcnKernel { none, valu, valu_joint_axis, mfma_f32, bf16_small, v4, v6 };
+enum class TcnLayout { none, valu, f32_frags, bf16 };
+struct TcnPack {   // depends on (Cin, Cout, K, math) only.  bytes: all of it; single: the first layout alone; pairs: offset of the
+    TcnLayout layout = TcnLayout::none;                                                     // pair-order copy (0: it has none)
+    size_t bytes = 0, single = 0, pairs = 0;
+};
+struct TcnTile { int rows = 0, n = 0; size_t lds = 0; };   // the chosen kernel's tile: written by its *_covers, read by its launch
+struct TcnPlan {
+    TcnKernel kernel = TcnKernel::none;
+    TcnPack pack;
+    TcnTile tile;
+    int Tout = 0;                    // output frames (joint axis: T)
+    bool stats_in_conv_ok = false;   // launch_tcn may be given `stats`
+};
+TcnPack plan_tcn_pack(int Cin, int Cout, int K, unsigned flags);
+TcnPlan plan_tcn(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
+static inline bool tcn_on_matrix_cores(TcnKernel k) { return k >= TcnKernel::mfma_f32; }
+const char *tcn_kernel_name(TcnKernel k);
+int launch_tcn_pack(const TcnPack &p, const float *W, const float *scale, void *Wp, int Cin, int Cout, int K, hipStream_t st);
+// stats (optional, 2*Cout doubles ZEROED by the caller): per-channel sum and sum of squares of the stored output
+int launch_tcn(const TcnPlan &p, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T,
+               int V, int K, int stride, unsigned flags, hipStream_t st, double *stats = nullptr);
+// its kernels, one coverage predicate and one launcher each (the predicates are called by plan_tcn[_pack] only): VALU and f32
+// matrix cores (tcn_conv.hip) ...
+int launch_tcn_pack_f32(bool frags, const float *W, const float *scale, void *Wp, int Cin, int Cout, int K, hipStream_t st);
+int launch_tcn_valu(bool joint_axis, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T,
+                    int V, int K, int stride, int Lout, unsigned flags, hipStream_t st);
+bool tcn_mfma_f32_covers(int Cin, int Cout, int V, int K, int stride, int Tout, TcnTile &t);
+int launch_tcn_mfma_f32(const TcnTile &t, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout,
+                        int T, int V, int K, int stride, int Tout, unsigned flags, hipStream_t st);
+// ... the 128-pixel tile on the bf16 matrix cores (tcn_bf16.hip) ...
 int launch_tcn_pack_bf16(const float *W, const float *scale, void *Wp, int Cin, int Cout, int K, hipStream_t st);
-int launch_tcn_bf16(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V, int K,
-                    int stride, unsigned flags, hipStream_t st);
+bool tcn_bf16_small_covers(int Cin, int Cout, int V, int K, int stride, int Tout, int terms, TcnTile &t);
+int launch_tcn_bf16_small(const TcnTile &t, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout,
+                          int T, int V, int K, int stride, int Tout, unsigned flags, hipStream_t st);
+// ... the large-tile persistent form (stem_bf16_v4.hip): K = 9, stride 1 ...
+bool tcn_v4_covers(int Cin, int Cout, int T, int V, int K, int stride, int terms, TcnTile &t);
+int launch_tcn_v4(const TcnTile &t, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T,
+                  int V, unsigned flags, hipStream_t st);
+// ... and the same in KF6's form (tcn_bf16_v6.hip): one wave per SIMD, on the pair-order copy of the weights
+bool tcn_v6_takes_weights(int Cin, int Cout, int K);   // the blob carries the pair-order copy
+bool tcn_v6_covers(int Cin, int Cout, int T, int V, int K, int stride, int terms, TcnTile &t, bool &stats_ok);
+int launch_tcn_pack_pairs_padded(const float *W, const float *scale, void *Wq, int Cin, int Cout, hipStream_t st);
+int launch_tcn_v6(const TcnTile &t, const float *x, const void *Wq, const float *shift, void *y, int N, int Cin, int Cout, int T,
+                  int V, unsigned flags, hipStream_t st, double *stats = nullptr);
+
 // the 128-pixel fused stem on the bf16 matrix cores: reads x (channel-major) and P, computes the features per tile
 bool stem_bf16_small_supported(int C, int T, int V, int K, unsigned flags);
 int launch_stem_bf16_small(const float *x, const float *P, const float *W12, const void *Wp, const float *shift, void *out, int N,
                            int C, int T, int V, int K, unsigned flags, hipStream_t st);
-
-bool tcn_mfma_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
 
 // large-tile persistent bf16 stem, eight waves (stem_bf16_v4.hip); *frags: the 256-pixel tile (features from fragments)
 bool attention_emits_features(int Cin, int V, int S);
@@ -196,18 +227,6 @@ int launch_stem_v6w(const float *x, bool x_ntvc, const void *pfrag, const void *
 int launch_tcn_pack_bf16_pairs(const float *W, const float *scale, void *Wq, int Cin, int Cout, hipStream_t st);
 int launch_stem_v6(const float *x, bool x_ntvc, const void *pfrag, const void *prep_w12, const void *Wq, const float *shift,
                    void *out, int N, int C, int T, int V, int K, unsigned flags, hipStream_t st);
-
-// stand-alone temporal conv in the large-tile persistent form (stem_bf16_v4.hip): K = 9, stride 1, Cout % 128 == 0
-bool tcn_v4_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
-// ... and in KF6's form (tcn_bf16_v6.hip): one wave per SIMD, pair-order weights (appended to the packed blob by launch_tcn_pack)
-bool tcn_v6_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);
-bool tcn_v6_stats_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags);   // launch_tcn_v6(..., stats)
-bool tcn_v6_packs(int Cin, int Cout, int K, unsigned math);
-int launch_tcn_pack_pairs_padded(const float *W, const float *scale, void *Wq, int Cin, int Cout, hipStream_t st);
-int launch_tcn_v6(const float *x, const void *Wq, const float *shift, void *y, int N, int Cin, int Cout, int T, int V, int K,
-                  int stride, unsigned flags, hipStream_t st, double *stats = nullptr);   // stats: see tcn_bf16_v6.hip
-int launch_tcn_v4(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V, int K,
-                  int stride, unsigned flags, hipStream_t st);
 
 // training-mode BatchNorm helpers (train_bn.hip)
 int launch_fill_ones_zeros(float *ones, float *zeros, int C, hipStream_t st);
@@ -270,7 +289,8 @@ static inline TrainSmall carve_train_small(Carve &c, int C) {
 // on it).  ws_bytes == 0: T, K and stride leave no output frame.
 struct TcnTrainPlan {
     bool frozen = false, stats_in_conv = false;   // stats_in_conv: the one-wave kernel sums the batch statistics in its epilogue
-    unsigned flags = 0, cflags = 0;               // without STGCN_BN_FROZEN; the raw convolution's
+    unsigned cflags = 0;                          // the raw convolution's flags ...
+    TcnPlan conv;                                 // ... and its plan
     int Tout = 0;
     size_t ws_bytes = 0;
 };
@@ -282,8 +302,9 @@ int launch_tcn_forward_train(const TcnTrainPlan &p, const float *x, const float 
 struct TcnBackwardPlan {
     bool frozen = false;
     bool upsampled = false;         // stride 2, odd K: run as the stride-1 block's backward on dz upsampled with zero frames
-    bool dgrad_by_forward = false;  // dx = the forward kernels on the flipped weights
+    bool dgrad_by_forward = false;  // dx = the forward kernels on the flipped weights:
     unsigned flags = 0, dgrad_flags = 0;
+    TcnPlan dgrad;                  // the plan of that convolution (Cout input, Cin output channels), run with dgrad_flags
     int Tout = 0, stride = 0, Tz = 0;   // stride and frames of the gradient tensor the two conv gradients read (after upsampling)
     size_t wgrad_bytes = 0;             // partials of the matrix-core wgrad (0: it does not serve the shape)
     size_t ws_bytes = 0;

@@ -4,23 +4,24 @@
 
 namespace stgcn {
 
-// prep blob: [ W12 : C x 16 floats ][ temporal weights, single packing (launch_tcn_pack) ]
-//            [ the same weights in KF6's pair order ]   bf16 modes, K = 9, C % 128 == 0
+// prep blob: [ W12 : C x 16 floats ][ temporal weights, single packing (the temporal conv's, tcn.hip) ]
+//            [ the same weights in KF6's pair order ]   where the temporal conv's blob has its pair-order copy and C % 128 == 0
 //            [ KF7's header + weights ]                 STGCN_STEM_F16MX with bf16x3, behind the pair-order copy
-// every part 256-B aligned.  It depends on (C, K, flags) only: one blob serves every batch shape.
+// every part 256-B aligned.  It depends on (C, K, flags) only: one blob serves every batch shape.  The two weight parts have
+// the sizes and offsets of the temporal conv's packed blob (plan_tcn_pack); the pair-order part is written by KF6's own pack
+// kernel (stem_bf16_v6.hip), whose lo image differs from K3v6's in a last bit here and there.
 StemPrep plan_stem_prep(int C, int K, unsigned flags) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    const size_t single = tcn_packed_single_bytes(C, C, K, flags);
+    const TcnPack t = plan_tcn_pack(C, C, K, flags);
+    // (the fused kernels take C % 128 == 0 only and launch_stem_prepare refuses the rest; the size query answers for C = 64
+    //  without the pair-order part, as it always has)
+    const bool pairs = t.pairs && C % 128 == 0;
     StemPrep p;
     p.single = stem_w12_bytes(C);
-    p.bytes = p.single + single;
-    if ((math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) && K == 9 && C % 128 == 0) {
-        p.pairs = p.bytes;
-        p.bytes += single;
-        if ((flags & STGCN_STEM_F16MX) && math == STGCN_MATH_BF16X3) {
-            p.f16mx = p.bytes;
-            p.bytes += align_up(stem_f16mx_prep_bytes(C, K), 256);
-        }
+    p.pairs = pairs ? p.single + t.pairs : 0;
+    p.bytes = p.single + (pairs ? t.bytes : t.single);
+    if (p.pairs && (flags & STGCN_STEM_F16MX) && (flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3) {
+        p.f16mx = p.bytes;
+        p.bytes += align_up(stem_f16mx_prep_bytes(C, K), 256);
     }
     return p;
 }
@@ -93,7 +94,9 @@ int launch_stem_prepare(const float *Wd, const float *bd, const float *Wdown, co
     const StemPrep p = plan_stem_prep(C, K, flags);
     char *const blob = (char *)prep;
     int rc = launch_stem_fold(Wd, bd, Wdown, bdown, bn_scale, bn_shift, down_scale, down_shift, (float *)blob, Cin, C, S, st);
-    if (rc == STGCN_OK) rc = launch_tcn_pack(Wt, t_scale, blob + p.single, C, C, K, flags, st);
+    TcnPack single = plan_tcn_pack(C, C, K, flags);
+    single.bytes = single.single, single.pairs = 0;   // the single packing alone: the pair-order part is KF6's own
+    if (rc == STGCN_OK) rc = launch_tcn_pack(single, Wt, t_scale, blob + p.single, C, C, K, st);
     if (rc == STGCN_OK && p.pairs) rc = launch_tcn_pack_bf16_pairs(Wt, t_scale, blob + p.pairs, C, C, st);
     if (rc == STGCN_OK && p.f16mx) rc = launch_stem_f16mx_prepare((const float *)blob, Wt, t_scale, blob + p.f16mx, C, st);
     return rc;

@@ -836,12 +836,10 @@ int launch_v4(const float4 *feat, const float *x, int xsc, int xsp, const float 
     return STGCN_OK;
 }
 
-struct T4Plan {
-    int rows = 0, tiles_per_clip = 0;
-    size_t lds = 0;
-};
+}  // namespace
 
-inline bool plan_t4(int Cin, int Cout, int T, int V, int K, int stride, int terms, T4Plan &pl) {
+// t.n: tiles per clip
+bool tcn_v4_covers(int Cin, int Cout, int T, int V, int K, int stride, int terms, TcnTile &t) {
     if (K != KT4 || stride != 1 || (Cout % 128 != 0 && Cout != 64) || Cin % CCB != 0 || T < 1) return false;
     int dt = ceil_div(NP4 - 1, V);
     if (dt > T - 1) dt = T - 1;
@@ -850,44 +848,29 @@ inline bool plan_t4(int Cin, int Cout, int T, int V, int K, int stride, int term
     if (rows > NT4) return false;                 // two (pixel, 8-channel) units per thread
     const size_t buf = (size_t)rows * PXB * (terms == 3 ? 2 : 1);
     const size_t img = 2 * buf > (size_t)8 * EPI_BYTES ? 2 * buf : (size_t)8 * EPI_BYTES;
-    pl.lds = 2 * STAGE_BYTES + img;
-    if (pl.lds > (size_t)kLdsBytes) return false;
-    pl.rows = rows;
-    pl.tiles_per_clip = ceil_div(T * V, NP4);
+    const size_t lds = 2 * STAGE_BYTES + img;
+    if (lds > (size_t)kLdsBytes) return false;
+    t = TcnTile{rows, ceil_div(T * V, NP4), lds};
     return true;
 }
 
-}  // namespace
-
-bool tcn_v4_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    if (math != STGCN_MATH_BF16X3 && math != STGCN_MATH_BF16) return false;
-    T4Plan pl;
-    return plan_t4(Cin, Cout, T, V, K, stride, math == STGCN_MATH_BF16X3 ? 3 : 1, pl);
-}
-
-int launch_tcn_v4(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V, int K,
-                  int stride, unsigned flags, hipStream_t st) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    const int terms = math == STGCN_MATH_BF16X3 ? 3 : 1;
+int launch_tcn_v4(const TcnTile &pl, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T,
+                  int V, unsigned flags, hipStream_t st) {
+    const int terms = (flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3 ? 3 : 1;
     const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
     const float act_lo = (flags & STGCN_RAW) ? -__builtin_huge_valf() : 0.f;
     const int opt = (flags & STGCN_OUT_NTVC) ? OPT_OUT_NTVC : 0;
-    T4Plan pl;
-    if (!plan_t4(Cin, Cout, T, V, K, stride, terms, pl))
-        return fail(STGCN_ERR_UNSUPPORTED, "tcn v4 kernel does not cover Cin=%d Cout=%d T=%d V=%d K=%d stride=%d", Cin, Cout, T,
-                    V, K, stride);
     int dev = 0, num_cu = 256;
     STGCN_HIP_CHECK(hipGetDevice(&dev));
     STGCN_HIP_CHECK(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    const int ntiles = N * pl.tiles_per_clip;
+    const int ntiles = N * pl.n;
     const dim3 grid(ntiles < num_cu ? ntiles : num_cu, ceil_div(Cout, 128), 1);
 #define LAUNCH_T4(TERMS, B)                                                                                       \
     do {                                                                                                          \
         auto kern = tcn_bf16_v4_kernel<TERMS, B>;                                                                 \
         STGCN_HIP_CHECK(allow_lds(kern, pl.lds));                                                                 \
         hipLaunchKernelGGL(kern, grid, dim3(NT4), pl.lds, st, x, (const uint4 *)Wp, shift, y, Cin, Cout, T, V, pl.rows, \
-                           pl.tiles_per_clip, ntiles, act_lo, opt);                                               \
+                           pl.n, ntiles, act_lo, opt);                                                            \
     } while (0)
     if (terms == 3) { if (bf16out) LAUNCH_T4(3, true); else LAUNCH_T4(3, false); }
     else { if (bf16out) LAUNCH_T4(1, true); else LAUNCH_T4(1, false); }

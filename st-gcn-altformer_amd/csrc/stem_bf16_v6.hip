@@ -8,6 +8,9 @@ namespace {
 
 // weight packing for KF6: Wq (bf16) index ((((ob*npairs + q)*2 + img)*64 + lane)*8 + j
 //   o = ob*16 + (lane&15); step f = 2q + (lane>>5); chunk f/9, tap f%9; c = chunk*16 + 8*((lane>>4)&1) + j
+// (the order of tcn_pack_pairs_padded_kernel, tcn_bf16_v6.hip, but NOT its bytes: here the compiler contracts the lo image's
+//  residual scale*W - hi into one fma, there the product is rounded first, and one lo value in a few hundred differs in its last
+//  bit.  The fused stem keeps this packing so that KF6 / KF6w read the bytes they always have.)
 __global__ void tcn_pack_bf16_pairs_kernel(const float *__restrict__ W, const float *__restrict__ scale,
                                            unsigned short *__restrict__ Wq, int Cin, int Cout) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;  // one thread per (weight, img)

@@ -514,15 +514,9 @@ template <int PB, int TERMS, int KT>
 int launch_stem_variant(const float *x, const float *P, const float *W12, const uint4 *Wp, const float *shift, void *y,
                         int N, int C, int T, int V, int K, const Bf16StemTile &pl, bool bf16out, int opt, hipStream_t st) {
     const dim3 grid(ceil_div(T * V, NPB), C / 128, N);
-    if (bf16out) {
-        auto kern = stem_mfma_bf16_kernel<PB, TERMS, true, KT>;
-        STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
-        hipLaunchKernelGGL(kern, grid, dim3(NT), pl.lds, st, x, P, W12, Wp, shift, y, C, T, V, K, pl.rows, ablate_mask() | opt);
-    } else {
-        auto kern = stem_mfma_bf16_kernel<PB, TERMS, false, KT>;
-        STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
-        hipLaunchKernelGGL(kern, grid, dim3(NT), pl.lds, st, x, P, W12, Wp, shift, y, C, T, V, K, pl.rows, ablate_mask() | opt);
-    }
+    auto kern = bf16out ? stem_mfma_bf16_kernel<PB, TERMS, true, KT> : stem_mfma_bf16_kernel<PB, TERMS, false, KT>;
+    STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
+    hipLaunchKernelGGL(kern, grid, dim3(NT), pl.lds, st, x, P, W12, Wp, shift, y, C, T, V, K, pl.rows, ablate_mask() | opt);
     STGCN_LAUNCH_CHECK("stem_mfma_bf16_kernel");
     return STGCN_OK;
 }
@@ -547,12 +541,38 @@ inline int rows_needed(int V, int K, int stride, int Tout) {
     return (dt * stride + K) * V + 1;
 }
 
-struct Bf16Plan {
-    int jpr = 0, rows = 0;
-    size_t lds = 0;
-};
+template <int JPR, int TERMS, int KT>
+int launch_variant(const float *x, const uint4 *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V,
+                   int K, int stride, int Tout, const TcnTile &pl, bool bf16out, float act_lo, hipStream_t st) {
+    const dim3 grid(ceil_div(Tout * V, NPB), ceil_div(Cout, 128), N);
+    auto kern = bf16out ? tcn_mfma_bf16_kernel<JPR, TERMS, true, KT> : tcn_mfma_bf16_kernel<JPR, TERMS, false, KT>;
+    STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
+    hipLaunchKernelGGL(kern, grid, dim3(NT), pl.lds, st, x, Wp, shift, y, Cin, Cout, T, V, K, stride, Tout, pl.rows, ablate_mask(),
+                       act_lo);
+    STGCN_LAUNCH_CHECK("tcn_mfma_bf16_kernel");
+    return STGCN_OK;
+}
 
-inline bool plan_bf16(int Cin, int Cout, int V, int K, int stride, int Tout, int terms, Bf16Plan &pl) {
+template <int TERMS>
+int dispatch_tcn(const float *x, const uint4 *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V,
+                 int K, int stride, int Tout, const TcnTile &pl, bool bf16out, float act_lo, hipStream_t st) {
+#define GO(JPR, KT) \
+    return launch_variant<JPR, TERMS, KT>(x, Wp, shift, y, N, Cin, Cout, T, V, K, stride, Tout, pl, bf16out, act_lo, st)
+    if (K == 9) {
+        if (pl.n == 1) GO(1, 9);
+        if (pl.n == 2) GO(2, 9);
+        GO(3, 9);
+    }
+    if (pl.n == 1) GO(1, 0);
+    if (pl.n == 2) GO(2, 0);
+    GO(3, 0);
+#undef GO
+}
+
+}  // namespace
+
+// the 128-pixel tile of tcn_mfma_bf16_kernel; t.n: tile columns per thread
+bool tcn_bf16_small_covers(int Cin, int Cout, int V, int K, int stride, int Tout, int terms, TcnTile &t) {
     if (Cin % CCB != 0 || (Cout % 128 != 0 && Cout != 64)) return false;
     const int rows = rows_needed(V, K, stride, Tout);
     const int jpr = ceil_div(rows - 1, NT);
@@ -560,57 +580,8 @@ inline bool plan_bf16(int Cin, int Cout, int V, int K, int stride, int Tout, int
     const size_t buf = (size_t)rows * PXB * (terms == 3 ? 2 : 1);
     const size_t lds = 2 * buf;
     if (lds > (size_t)kLdsBytes) return false;
-    pl.jpr = jpr;
-    pl.rows = rows;
-    pl.lds = lds;
+    t = TcnTile{rows, jpr, lds};
     return true;
-}
-
-template <int JPR, int TERMS, int KT>
-int launch_variant(const float *x, const uint4 *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V,
-                   int K, int stride, int Tout, const Bf16Plan &pl, bool bf16out, float act_lo, hipStream_t st) {
-    const dim3 grid(ceil_div(Tout * V, NPB), ceil_div(Cout, 128), N);
-    if (bf16out) {
-        auto kern = tcn_mfma_bf16_kernel<JPR, TERMS, true, KT>;
-        STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
-        hipLaunchKernelGGL(kern, grid, dim3(NT), pl.lds, st, x, Wp, shift, y, Cin, Cout, T, V, K, stride, Tout, pl.rows,
-                           ablate_mask(), act_lo);
-    } else {
-        auto kern = tcn_mfma_bf16_kernel<JPR, TERMS, false, KT>;
-        STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
-        hipLaunchKernelGGL(kern, grid, dim3(NT), pl.lds, st, x, Wp, shift, y, Cin, Cout, T, V, K, stride, Tout, pl.rows,
-                           ablate_mask(), act_lo);
-    }
-    STGCN_LAUNCH_CHECK("tcn_mfma_bf16_kernel");
-    return STGCN_OK;
-}
-
-template <int TERMS>
-int dispatch_tcn(const float *x, const uint4 *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V,
-                 int K, int stride, int Tout, const Bf16Plan &pl, bool bf16out, float act_lo, hipStream_t st) {
-#define GO(JPR, KT) \
-    return launch_variant<JPR, TERMS, KT>(x, Wp, shift, y, N, Cin, Cout, T, V, K, stride, Tout, pl, bf16out, act_lo, st)
-    if (K == 9) {
-        if (pl.jpr == 1) GO(1, 9);
-        if (pl.jpr == 2) GO(2, 9);
-        GO(3, 9);
-    }
-    if (pl.jpr == 1) GO(1, 0);
-    if (pl.jpr == 2) GO(2, 0);
-    GO(3, 0);
-#undef GO
-}
-
-}  // namespace
-
-bool bf16_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    if (math != STGCN_MATH_BF16X3 && math != STGCN_MATH_BF16) return false;
-    const int Tout = tcn_out_frames(T, K, stride);
-    if (Tout < 1) return false;
-    if (tcn_v6_supported(Cin, Cout, T, V, K, stride, flags) || tcn_v4_supported(Cin, Cout, T, V, K, stride, flags)) return true;
-    Bf16Plan pl;
-    return plan_bf16(Cin, Cout, V, K, stride, Tout, math == STGCN_MATH_BF16X3 ? 3 : 1, pl);
 }
 
 bool stem_bf16_small_supported(int C, int T, int V, int K, unsigned flags) {
@@ -618,10 +589,6 @@ bool stem_bf16_small_supported(int C, int T, int V, int K, unsigned flags) {
     Bf16StemTile sp;   // (T + 2 * ((K - 1) / 2) - K + 1: the output frames)
     return (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) && T + 2 * ((K - 1) / 2) - K + 1 >= 1 &&
            plan_stem_bf16(C, V, K, T, math == STGCN_MATH_BF16X3 ? 3 : 1, sp);
-}
-
-bool bf16_packs(int Cin, int Cout, unsigned math) {
-    return (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) && Cin % CCB == 0 && (Cout % 128 == 0 || Cout == 64);
 }
 
 int launch_tcn_pack_bf16(const float *W, const float *scale, void *Wp, int Cin, int Cout, int K, hipStream_t st) {
@@ -644,28 +611,12 @@ int launch_stem_bf16_small(const float *x, const float *P, const float *W12, con
                                                          (flags & STGCN_OUT_NTVC) ? OPT_OUT_NTVC : 0, st);
 }
 
-int launch_tcn_bf16(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T, int V, int K,
-                    int stride, unsigned flags, hipStream_t st) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
-    const int terms = math == STGCN_MATH_BF16X3 ? 3 : 1;
-    const int Tout = tcn_out_frames(T, K, stride);
-    // K = 9, stride 1: large-tile persistent kernels — one wave per SIMD on 16x16x32 where that form covers the shape
-    // (diagnostic builds: mask 8192 keeps the eight-wave kernel for A/B runs in one process)
-    if (tcn_v6_supported(Cin, Cout, T, V, K, stride, flags) && !(ablate_mask() & 8192))
-        return launch_tcn_v6(x, (const char *)Wp + tcn_packed_single_bytes(Cin, Cout, K, flags), shift, y, N, Cin, Cout, T, V, K,
-                             stride, flags, st);
-    if (tcn_v4_supported(Cin, Cout, T, V, K, stride, flags))
-        return launch_tcn_v4(x, Wp, shift, y, N, Cin, Cout, T, V, K, stride, flags, st);
-    Bf16Plan pl;
-    if (Tout < 1 || !plan_bf16(Cin, Cout, V, K, stride, Tout, terms, pl))
-        return fail(STGCN_ERR_UNSUPPORTED,
-                    "bf16 MFMA kernel does not cover Cin=%d Cout=%d V=%d K=%d stride=%d T=%d (needs Cin%%16==0, "
-                    "Cout%%128==0, tile rows that fit LDS)", Cin, Cout, V, K, stride, T);
-    const uint4 *wp = (const uint4 *)Wp;
+int launch_tcn_bf16_small(const TcnTile &t, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout,
+                          int T, int V, int K, int stride, int Tout, unsigned flags, hipStream_t st) {
+    const bool bf16out = (flags & STGCN_OUT_BF16) != 0, three = (flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3;
     const float act_lo = (flags & STGCN_RAW) ? -__builtin_huge_valf() : 0.f;  // raw = pre-activation (training-mode BN)
-    if (terms == 3) return dispatch_tcn<3>(x, wp, shift, y, N, Cin, Cout, T, V, K, stride, Tout, pl, bf16out, act_lo, st);
-    return dispatch_tcn<1>(x, wp, shift, y, N, Cin, Cout, T, V, K, stride, Tout, pl, bf16out, act_lo, st);
+    return (three ? dispatch_tcn<3> : dispatch_tcn<1>)(x, (const uint4 *)Wp, shift, y, N, Cin, Cout, T, V, K, stride, Tout, t,
+                                                       bf16out, act_lo, st);
 }
 
 }  // namespace stgcn

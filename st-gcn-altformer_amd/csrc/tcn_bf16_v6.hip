@@ -395,50 +395,28 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
     }
 }
 
-struct T6Plan {
-    int rows = 0, tiles_per_clip = 0;
-    size_t lds = 0;
-};
+}  // namespace
 
-inline bool plan_t6(int Cin, int Cout, int T, int V, int K, int stride, int terms, T6Plan &pl) {
-    if (K != KT6 || stride != 1 || T < 1 || V > 32) return false;
-    if ((Cout % 128 != 0 && Cout != 64) || Cin % 32 != 0) return false;   // (an even number of 16-channel chunks)
+// the part of the coverage that the weights' shape alone decides: where it holds, the packed blob carries the pair-order copy
+bool tcn_v6_takes_weights(int Cin, int Cout, int K) {
+    return K == KT6 && Cin % 32 == 0 && (Cout % 128 == 0 || Cout == 64);   // (an even number of 16-channel chunks)
+}
+
+// t.n: tiles per clip.  stats_ok: the STATS form fits too (2 KiB of LDS on top: its per-workgroup fp64 sums)
+bool tcn_v6_covers(int Cin, int Cout, int T, int V, int K, int stride, int terms, TcnTile &t, bool &stats_ok) {
+    if (!tcn_v6_takes_weights(Cin, Cout, K) || stride != 1 || T < 1 || V > 32) return false;
     int dt = ceil_div(NP6 - 1, V);
     if (dt > T - 1) dt = T - 1;
     const int span = (dt + K) * V;
     const int rows = (span + 15) / 16 * 16;
     if (2 * rows > 4 * NT6) return false;                        // four (pixel, 8-channel) units per lane
     const size_t buf = (size_t)rows * PXB * (terms == 3 ? 2 : 1);
-    pl.lds = RING6 + 2 * buf + (size_t)4 * EPI6;
-    if (pl.lds > (size_t)kLdsBytes) return false;
+    const size_t lds = RING6 + 2 * buf + (size_t)4 * EPI6;
+    if (lds > (size_t)kLdsBytes) return false;
     if ((size_t)(Cin > Cout ? Cin : Cout) * T * V * 4 >= ((size_t)1 << 31)) return false;   // per-clip buffer resources
-    pl.rows = rows;
-    pl.tiles_per_clip = ceil_div(T * V, NP6);
+    t = TcnTile{rows, ceil_div(T * V, NP6), lds};
+    stats_ok = lds + 2 * 128 * sizeof(double) <= (size_t)kLdsBytes;
     return true;
-}
-
-}  // namespace
-
-bool tcn_v6_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    if (math != STGCN_MATH_BF16X3 && math != STGCN_MATH_BF16) return false;
-    T6Plan pl;
-    return plan_t6(Cin, Cout, T, V, K, stride, math == STGCN_MATH_BF16X3 ? 3 : 1, pl);
-}
-
-// the STATS form needs 2 KiB of LDS on top (its per-workgroup fp64 sums)
-bool tcn_v6_stats_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    if ((math != STGCN_MATH_BF16X3 && math != STGCN_MATH_BF16) || (flags & (STGCN_OUT_BF16 | STGCN_OUT_NTVC))) return false;
-    T6Plan pl;
-    return plan_t6(Cin, Cout, T, V, K, stride, math == STGCN_MATH_BF16X3 ? 3 : 1, pl) &&
-           pl.lds + 2 * 128 * sizeof(double) <= (size_t)kLdsBytes;
-}
-
-// true when launch_tcn_pack appends the pair-order copy of the weights for (Cin, Cout, K, math) — shape-independent part
-// of tcn_v6_supported
-bool tcn_v6_packs(int Cin, int Cout, int K, unsigned math) {
-    return (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) && K == KT6 && Cin % 32 == 0 && (Cout % 128 == 0 || Cout == 64);
 }
 
 int launch_tcn_pack_pairs_padded(const float *W, const float *scale, void *Wq, int Cin, int Cout, hipStream_t st) {
@@ -450,34 +428,27 @@ int launch_tcn_pack_pairs_padded(const float *W, const float *scale, void *Wq, i
     return STGCN_OK;
 }
 
-// stats (optional, 2*Cout doubles ZEROED by the caller): per-channel sum and sum of squares of the stored output
-// (fp32, (N,C,T,V) layout only) — the training forward's batch statistics
-int launch_tcn_v6(const float *x, const void *Wq, const float *shift, void *y, int N, int Cin, int Cout, int T, int V, int K,
-                  int stride, unsigned flags, hipStream_t st, double *stats) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    const int terms = math == STGCN_MATH_BF16X3 ? 3 : 1;
+// Wq: the pair-order copy.  stats (optional, 2*Cout doubles ZEROED by the caller; needs stats_ok and the fp32 (N,C,T,V) output):
+// per-channel sum and sum of squares of the stored output — the training forward's batch statistics
+int launch_tcn_v6(const TcnTile &pl, const float *x, const void *Wq, const float *shift, void *y, int N, int Cin, int Cout, int T,
+                  int V, unsigned flags, hipStream_t st, double *stats) {
+    const int terms = (flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3 ? 3 : 1;
     const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
     const float act_lo = (flags & STGCN_RAW) ? -__builtin_huge_valf() : 0.f;
     const int opt = (flags & STGCN_OUT_NTVC) ? OPT_OUT_NTVC : 0;
-    T6Plan pl;
-    if (!plan_t6(Cin, Cout, T, V, K, stride, terms, pl))
-        return fail(STGCN_ERR_UNSUPPORTED, "tcn v6 kernel does not cover Cin=%d Cout=%d T=%d V=%d K=%d stride=%d", Cin, Cout, T,
-                    V, K, stride);
     int dev = 0, num_cu = 256;
     STGCN_HIP_CHECK(hipGetDevice(&dev));
     STGCN_HIP_CHECK(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    const int ntiles = N * pl.tiles_per_clip;
+    const int ntiles = N * pl.n;
     const dim3 grid(ntiles < num_cu ? ntiles : num_cu, ceil_div(Cout, 128), 1);
     if (stats != nullptr) {
-        if (bf16out || opt) return fail(STGCN_ERR_UNSUPPORTED, "tcn v6 kernel: channel statistics go with the fp32 (N,C,T,V) output");
         const size_t lds = pl.lds + 2 * 128 * sizeof(double);
-        if (lds > (size_t)kLdsBytes) return fail(STGCN_ERR_UNSUPPORTED, "tcn v6 kernel: no LDS left for the channel statistics");
 #define LAUNCH_T6S(TERMS)                                                                                         \
     do {                                                                                                          \
         auto kern = tcn_bf16_v6_kernel<TERMS, false, true>;                                                       \
         STGCN_HIP_CHECK(allow_lds(kern, lds));                                                                    \
         hipLaunchKernelGGL(kern, grid, dim3(NT6), lds, st, x, (const uint4 *)Wq, shift, y, Cin, Cout, T, V, pl.rows, \
-                           pl.tiles_per_clip, ntiles, act_lo, opt, stats);                                        \
+                           pl.n, ntiles, act_lo, opt, stats);                                                     \
     } while (0)
         if (terms == 3) LAUNCH_T6S(3); else LAUNCH_T6S(1);
 #undef LAUNCH_T6S
@@ -489,7 +460,7 @@ int launch_tcn_v6(const float *x, const void *Wq, const float *shift, void *y, i
         auto kern = tcn_bf16_v6_kernel<TERMS, B>;                                                                 \
         STGCN_HIP_CHECK(allow_lds(kern, pl.lds));                                                                 \
         hipLaunchKernelGGL(kern, grid, dim3(NT6), pl.lds, st, x, (const uint4 *)Wq, shift, y, Cin, Cout, T, V, pl.rows, \
-                           pl.tiles_per_clip, ntiles, act_lo, opt, nullptr);                                      \
+                           pl.n, ntiles, act_lo, opt, nullptr);                                                   \
     } while (0)
     if (terms == 3) { if (bf16out) LAUNCH_T6(3, true); else LAUNCH_T6(3, false); }
     else { if (bf16out) LAUNCH_T6(1, true); else LAUNCH_T6(1, false); }

@@ -505,114 +505,54 @@ inline bool mfma_f32_shape_ok(int Cin, int Cout, int V, int K, int stride, int T
 }  // namespace
 
 // =========================================================================================
-size_t tcn_packed_single_bytes(int Cin, int Cout, int K, unsigned flags) {
-    // f32 and VALU layouts are one float per weight, the bf16 layout two bf16 images; the latter pads 64 output channels to 128
-    const int CoutP = bf16_packs(Cin, Cout, flags & STGCN_MATH_MASK) ? (Cout + 127) / 128 * 128 : Cout;
-    return align_up((size_t)Cin * CoutP * K * sizeof(float), 256);
-}
-
-// bf16 modes, K = 9: a second copy in pair order (K3v6, tcn_bf16_v6.hip) follows the first
-size_t tcn_packed_bytes(int Cin, int Cout, int K, unsigned flags) {
-    const size_t one = tcn_packed_single_bytes(Cin, Cout, K, flags);
-    return tcn_v6_packs(Cin, Cout, K, flags & STGCN_MATH_MASK) ? 2 * one : one;
-}
-
-// true when launch_tcn_pack lays the weights out in MFMA fragment order for this shape
-static bool packs_as_mfma(int Cin, int Cout, unsigned math) {
-    return math == STGCN_MATH_F32 && Cin % CC == 0 && Cout % 128 == 0;
-}
-
-int launch_tcn_pack(const float *W, const float *scale, void *Wp, int Cin, int Cout, int K, unsigned flags,
-                    hipStream_t st) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    const size_t total = (size_t)Cin * Cout * K;
-    const int blocks = (int)((total + 255) / 256);
-    if (bf16_packs(Cin, Cout, math)) {
-        const int rc = launch_tcn_pack_bf16(W, scale, Wp, Cin, Cout, K, st);
-        if (rc != STGCN_OK || !tcn_v6_packs(Cin, Cout, K, math)) return rc;
-        return launch_tcn_pack_pairs_padded(W, scale, (char *)Wp + tcn_packed_single_bytes(Cin, Cout, K, flags), Cin, Cout, st);
-    }
-    if (packs_as_mfma(Cin, Cout, math)) {
-        hipLaunchKernelGGL(tcn_pack_f32_kernel, dim3(blocks), dim3(256), 0, st, W, scale, (float *)Wp, Cin,
-                           Cout, K);
-    } else if (math <= STGCN_MATH_F32_VALU) {  // shapes the matrix-core kernels do not cover: VALU layout
-        hipLaunchKernelGGL(tcn_pack_valu_kernel, dim3(blocks), dim3(256), 0, st, W, scale, (float *)Wp, Cin,
-                           Cout, K);
-    } else {
-        return fail(STGCN_ERR_UNSUPPORTED, "tcn_pack: math mode %u not built", math);
-    }
+// one float per weight: MFMA fragment order (TcnLayout::f32_frags) or the VALU kernels' order
+int launch_tcn_pack_f32(bool frags, const float *W, const float *scale, void *Wp, int Cin, int Cout, int K, hipStream_t st) {
+    const int blocks = (int)(((size_t)Cin * Cout * K + 255) / 256);
+    hipLaunchKernelGGL(frags ? tcn_pack_f32_kernel : tcn_pack_valu_kernel, dim3(blocks), dim3(256), 0, st, W, scale, (float *)Wp,
+                       Cin, Cout, K);
     STGCN_LAUNCH_CHECK("tcn_pack");
     return STGCN_OK;
 }
 
-int launch_tcn(const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout,
-               int T, int V, int K, int stride, unsigned flags, hipStream_t st) {
-    const unsigned math = flags & STGCN_MATH_MASK;
+// Lout: output joints (joint_axis: Unit2D(dim=3)) or frames
+int launch_tcn_valu(bool joint_axis, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout, int T,
+                    int V, int K, int stride, int Lout, unsigned flags, hipStream_t st) {
     const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
     const float lo = (flags & STGCN_RAW) ? -__builtin_huge_valf() : 0.f;  // raw = pre-activation (training-mode BN)
-    const int pad = (K - 1) / 2;
-    if (flags & STGCN_CONV_ALONG_V) {      // Unit2D(dim=3): the joint axis
-        if (math != STGCN_MATH_F32_VALU) return fail(STGCN_ERR_UNSUPPORTED, "tcn: STGCN_CONV_ALONG_V goes with STGCN_MATH_F32_VALU");
-        const int Vout = (V + 2 * pad - K) / stride + 1;
-        if (Vout < 1) return fail(STGCN_ERR_ARG, "tcn: V=%d K=%d stride=%d gives no output joint", V, K, stride);
-        if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "tcn: N=%d > 65535 clips per call", N);
-        const dim3 gridv(ceil_div(T * Vout, 256), ceil_div(Cout, OBV), N);
-        if (bf16out)
-            hipLaunchKernelGGL((tcn_valu_joint_axis_kernel<true>), gridv, dim3(256), 0, st, x, (const float *)Wp, shift, y, Cin, Cout,
-                               T, V, K, stride, Vout, lo);
-        else
-            hipLaunchKernelGGL((tcn_valu_joint_axis_kernel<false>), gridv, dim3(256), 0, st, x, (const float *)Wp, shift, y, Cin, Cout,
-                               T, V, K, stride, Vout, lo);
-        STGCN_LAUNCH_CHECK("tcn_valu_joint_axis_kernel");
-        return STGCN_OK;
-    }
-    const int Tout = (T + 2 * pad - K) / stride + 1;
-    if (Tout < 1) return fail(STGCN_ERR_ARG, "tcn: T=%d K=%d stride=%d gives no output frame", T, K, stride);
-    if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "tcn: N=%d > 65535 clips per call", N);
-    if (math > STGCN_MATH_F32_VALU) return fail(STGCN_ERR_ARG, "tcn: unknown math mode %u", math);
-    if (bf16_packs(Cin, Cout, math))
-        return launch_tcn_bf16(x, Wp, shift, y, N, Cin, Cout, T, V, K, stride, flags, st);
+    const dim3 grid(ceil_div(joint_axis ? T * Lout : Lout * V, 256), ceil_div(Cout, OBV), N);
+    auto kern = joint_axis ? (bf16out ? tcn_valu_joint_axis_kernel<true> : tcn_valu_joint_axis_kernel<false>)
+                           : (bf16out ? tcn_valu_kernel<true> : tcn_valu_kernel<false>);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, x, (const float *)Wp, shift, y, Cin, Cout, T, V, K, stride, Lout, lo);
+    STGCN_LAUNCH_CHECK(joint_axis ? "tcn_valu_joint_axis_kernel" : "tcn_valu_kernel");
+    return STGCN_OK;
+}
 
-    if (packs_as_mfma(Cin, Cout, math)) {
-        if (!mfma_f32_shape_ok(Cin, Cout, V, K, stride, Tout))
-            return fail(STGCN_ERR_UNSUPPORTED,
-                        "tcn: f32 MFMA kernel needs a tile row <= 768 floats (V=%d K=%d stride=%d); "
-                        "use STGCN_MATH_F32_VALU",
-                        V, K, stride);
-        const int ROW = row_stride(V, K, stride, Tout);
-        const int jpr = ceil_div(ROW - 1, 256);
-        const size_t lds = (size_t)2 * CC * ROW * 4;
-        const dim3 grid(ceil_div(Tout * V, NP), Cout / 128, N);
+bool tcn_mfma_f32_covers(int Cin, int Cout, int V, int K, int stride, int Tout, TcnTile &t) {
+    if (!mfma_f32_shape_ok(Cin, Cout, V, K, stride, Tout)) return false;
+    const int ROW = row_stride(V, K, stride, Tout);
+    t = TcnTile{ROW, ceil_div(ROW - 1, 256), (size_t)2 * CC * ROW * 4};   // (t.n: tile columns per thread)
+    return true;
+}
+
+int launch_tcn_mfma_f32(const TcnTile &t, const float *x, const void *Wp, const float *shift, void *y, int N, int Cin, int Cout,
+                        int T, int V, int K, int stride, int Tout, unsigned flags, hipStream_t st) {
+    const bool bf16out = (flags & STGCN_OUT_BF16) != 0;
+    const float lo = (flags & STGCN_RAW) ? -__builtin_huge_valf() : 0.f;
+    const int ROW = t.rows, jpr = t.n;
+    const size_t lds = t.lds;
+    const dim3 grid(ceil_div(Tout * V, NP), Cout / 128, N);
 #define LAUNCH_TCN(J, B)                                                                            \
     do {                                                                                            \
         STGCN_HIP_CHECK(allow_lds(tcn_mfma_f32_kernel<J, B>, lds));                                 \
         hipLaunchKernelGGL((tcn_mfma_f32_kernel<J, B>), grid, dim3(256), lds, st, x, (const float4 *)Wp, \
                            shift, y, Cin, Cout, T, V, K, stride, Tout, ROW, lo);                    \
     } while (0)
-        if (jpr == 1) { if (bf16out) LAUNCH_TCN(1, true); else LAUNCH_TCN(1, false); }
-        else if (jpr == 2) { if (bf16out) LAUNCH_TCN(2, true); else LAUNCH_TCN(2, false); }
-        else { if (bf16out) LAUNCH_TCN(3, true); else LAUNCH_TCN(3, false); }
+    if (jpr == 1) { if (bf16out) LAUNCH_TCN(1, true); else LAUNCH_TCN(1, false); }
+    else if (jpr == 2) { if (bf16out) LAUNCH_TCN(2, true); else LAUNCH_TCN(2, false); }
+    else { if (bf16out) LAUNCH_TCN(3, true); else LAUNCH_TCN(3, false); }
 #undef LAUNCH_TCN
-        STGCN_LAUNCH_CHECK("tcn_mfma_f32_kernel");
-        return STGCN_OK;
-    }
-    const dim3 grid(ceil_div(Tout * V, 256), ceil_div(Cout, OBV), N);
-    if (bf16out)
-        hipLaunchKernelGGL((tcn_valu_kernel<true>), grid, dim3(256), 0, st, x, (const float *)Wp, shift, y, Cin,
-                           Cout, T, V, K, stride, Tout, lo);
-    else
-        hipLaunchKernelGGL((tcn_valu_kernel<false>), grid, dim3(256), 0, st, x, (const float *)Wp, shift, y,
-                           Cin, Cout, T, V, K, stride, Tout, lo);
-    STGCN_LAUNCH_CHECK("tcn_valu_kernel");
+    STGCN_LAUNCH_CHECK("tcn_mfma_f32_kernel");
     return STGCN_OK;
-}
-
-bool tcn_mfma_supported(int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
-    const unsigned math = flags & STGCN_MATH_MASK;
-    if (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16)
-        return bf16_supported(Cin, Cout, T, V, K, stride, flags);
-    const int Tout = tcn_out_frames(T, K, stride);
-    return Tout >= 1 && packs_as_mfma(Cin, Cout, math) && mfma_f32_shape_ok(Cin, Cout, V, K, stride, Tout);
 }
 
 // ---- fused stem, f32 (the other kernels and the plan that picks one: stem.hip) ------------------

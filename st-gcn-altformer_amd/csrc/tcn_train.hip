@@ -17,7 +17,7 @@ TcnTrainWs carve_tcn_train(void *base, const TcnTrainPlan &p, int N, int Cin, in
     Carve c(base);
     TcnTrainWs w{};
     w.v = carve_train_small(c, Cout);
-    w.packed = c.packed<char>(tcn_packed_bytes(Cin, Cout, K, p.flags));
+    w.packed = c.packed<char>(p.conv.pack.bytes);
     w.z = c.packed<float>((size_t)N * Cout * p.Tout * V);
     w.bytes = c.off;
     return w;
@@ -28,12 +28,12 @@ TcnTrainWs carve_tcn_train(void *base, const TcnTrainPlan &p, int N, int Cin, in
 TcnTrainPlan plan_tcn_train(int N, int Cin, int Cout, int T, int V, int K, int stride, unsigned flags) {
     TcnTrainPlan p;
     p.frozen = (flags & STGCN_BN_FROZEN) != 0;
-    p.flags = flags & ~STGCN_BN_FROZEN;
-    p.cflags = (p.flags & STGCN_MATH_MASK) | STGCN_RAW;
-    p.Tout = tcn_out_frames(T, K, stride);
+    p.cflags = (flags & STGCN_MATH_MASK) | STGCN_RAW;
+    p.conv = plan_tcn(Cin, Cout, T, V, K, stride, p.cflags);
+    p.Tout = p.conv.Tout;
     if (p.Tout < 1) return p;
 #ifndef STGCN_NO_CONV_STATS    /* A/B builds: the separate statistics pass */
-    p.stats_in_conv = !p.frozen && tcn_v6_stats_supported(Cin, Cout, T, V, K, stride, p.cflags) && !(ablate_mask() & 8192);
+    p.stats_in_conv = !p.frozen && p.conv.stats_in_conv_ok;
 #endif
     p.ws_bytes = carve_tcn_train(nullptr, p, N, Cin, Cout, V, K).bytes;
     return p;
@@ -49,16 +49,12 @@ int launch_tcn_forward_train(const TcnTrainPlan &p, const float *x, const float 
     const size_t plane = (size_t)p.Tout * V, total = (size_t)N * Cout * plane;
     int rc;
     if ((rc = launch_fill_ones_zeros(w.v.ones, w.v.zeros, Cout, st))) return rc;
-    if ((rc = launch_tcn_pack(W, w.v.ones, w.packed, Cin, Cout, K, p.flags, st))) return rc;   // unit scale: the raw convolution
+    if ((rc = launch_tcn_pack(p.conv.pack, W, w.v.ones, w.packed, Cin, Cout, K, st))) return rc;   // unit scale: the raw convolution
     const float *bias = conv_bias ? conv_bias : w.v.zeros;
-    if (p.stats_in_conv) {   // the one-wave kernel sums the batch statistics in its epilogue (no separate pass over z)
-        STGCN_HIP_CHECK(hipMemsetAsync(sums, 0, sizeof(double) * 2 * Cout, st));
-        rc = launch_tcn_v6(x, w.packed + tcn_packed_single_bytes(Cin, Cout, K, p.cflags), bias, z, N, Cin, Cout, T, V, K, stride,
-                           p.cflags, st, sums);
-    } else {
-        rc = launch_tcn(x, w.packed, bias, z, N, Cin, Cout, T, V, K, stride, p.cflags, st);
-    }
-    if (rc != STGCN_OK) return rc;
+    // stats_in_conv: the one-wave kernel sums the batch statistics in its epilogue (no separate pass over z)
+    if (p.stats_in_conv) STGCN_HIP_CHECK(hipMemsetAsync(sums, 0, sizeof(double) * 2 * Cout, st));
+    if ((rc = launch_tcn(p.conv, x, w.packed, bias, z, N, Cin, Cout, T, V, K, stride, p.cflags, st, p.stats_in_conv ? sums : nullptr)))
+        return rc;
     if (p.frozen) {
         rc = launch_bn_frozen_finalize(bn_weight, bn_bias, bn_running_mean, bn_running_var, eps, w.v.s1, w.v.t1, Cout, st,
                                        save_mean, save_invstd);
@@ -95,7 +91,7 @@ TcnBackwardWs carve_tcn_backward(void *base, const TcnBackwardPlan &p, int N, in
     if (p.upsampled) w.dzu = c.take<float>((size_t)N * Cout * T * V);
     if (p.dgrad_by_forward) {
         w.Wf = c.take<float>((size_t)Cout * Cin * K);
-        w.packed = c.take<char>(tcn_packed_bytes(Cout, Cin, K, p.dgrad_flags));
+        w.packed = c.take<char>(p.dgrad.pack.bytes);
     }
     if (p.wgrad_bytes) w.part = c.packed<float>(p.wgrad_bytes / sizeof(float));
     w.bytes = c.off;
@@ -119,10 +115,13 @@ TcnBackwardPlan plan_tcn_backward(int N, int Cin, int Cout, int T, int V, int K,
     // conv pads K-1-pad frames, which equals the forward's pad = (K-1)/2 when K is odd.  With an even K the forward drops a
     // frame (Tout = T-1) and that shortcut would write T-2 misaligned frames: even K runs the general VALU dgrad instead.
     p.dgrad_by_forward = p.stride == 1 && (K & 1) == 1;
-    if (p.dgrad_by_forward) {   // dgrad = forward conv with Cout input and Cin output channels
-        p.dgrad_flags = p.flags & STGCN_MATH_MASK;
-        if (p.dgrad_flags != STGCN_MATH_F32_VALU && !tcn_mfma_supported(Cout, Cin, p.Tz, V, K, 1, p.dgrad_flags))
-            p.dgrad_flags = STGCN_MATH_F32_VALU;
+    if (p.dgrad_by_forward) {   // dgrad = forward conv with Cout input and Cin output channels, on the VALU where no
+        p.dgrad_flags = (p.flags & STGCN_MATH_MASK) | STGCN_RAW;                        // matrix-core kernel takes it
+        p.dgrad = plan_tcn(Cout, Cin, p.Tz, V, K, 1, p.dgrad_flags);
+        if (!tcn_on_matrix_cores(p.dgrad.kernel)) {
+            p.dgrad_flags = STGCN_MATH_F32_VALU | STGCN_RAW;
+            p.dgrad = plan_tcn(Cout, Cin, p.Tz, V, K, 1, p.dgrad_flags);
+        }
     }
     p.wgrad_bytes = tcn_wgrad_ws_bytes(N, Cin, Cout, T, V, K, p.stride, p.flags);
     p.ws_bytes = carve_tcn_backward(nullptr, p, N, Cin, Cout, T, V, K).bytes;
@@ -154,8 +153,8 @@ int launch_tcn_backward_train(const TcnBackwardPlan &p, const float *x, const fl
     if (dx != nullptr && p.dgrad_by_forward) {   // dx = conv_t(dz, flipped W): the forward kernels, raw output
         if ((rc = launch_fill_ones_zeros(w.ones, w.zeros, Cin, st))) return rc;
         if ((rc = launch_weight_flip(W, w.Wf, Cout, Cin, K, st))) return rc;
-        if ((rc = launch_tcn_pack(w.Wf, w.ones, w.packed, Cout, Cin, K, p.dgrad_flags, st))) return rc;
-        if ((rc = launch_tcn(dz, w.packed, w.zeros, dx, N, Cout, Cin, p.Tz, V, K, 1, p.dgrad_flags | STGCN_RAW, st))) return rc;
+        if ((rc = launch_tcn_pack(p.dgrad.pack, w.Wf, w.ones, w.packed, Cout, Cin, K, st))) return rc;
+        if ((rc = launch_tcn(p.dgrad, dz, w.packed, w.zeros, dx, N, Cout, Cin, p.Tz, V, K, 1, p.dgrad_flags, st))) return rc;
     } else if (dx != nullptr) {
         if ((rc = launch_tcn_dgrad_valu(dz, W, dx, N, Cin, Cout, T, V, K, p.stride, p.Tz, st))) return rc;
     }

@@ -13,7 +13,7 @@ from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STGCN_LIB") or os.path.join(_HERE, "libstgcn_hip.so")   # STGCN_LIB: diagnostic builds
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # stgcn_math / flags (include/stgcn_hip.h)
 MATH_F32 = 0
@@ -48,6 +48,7 @@ PROTOTYPES = {
     "stgcn_agcn_forward": (c_int, [_P] * 16 + [c_int] * 7 + [_P]),
     "stgcn_tcn_packed_bytes": (c_size_t, [c_int, c_int, c_int, c_uint]),
     "stgcn_tcn_supported": (c_int, [c_int] * 6 + [c_uint]),
+    "stgcn_tcn_kernel_name": (c_char_p, [c_int] * 6 + [c_uint]),
     "stgcn_tcn_pack": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_uint, _P]),
     "stgcn_tcn_forward_packed": (c_int, [_P] * 4 + [c_int] * 7 + [c_uint, _P]),
     "stgcn_tcn_forward": (c_int, [_P] * 5 + [c_int] * 7 + [_P, c_size_t, c_uint, _P]),

@@ -143,9 +143,9 @@ def test_vit_abi_declared_and_exported():
     for n in ABI_NAMES:
         assert re.search(rf"\b{n}\s*\(", hdr), n
         assert n in _capi.PROTOTYPES and hasattr(handle, n), n
-    assert re.search(r"#define\s+STGCN_ABI_VERSION\s+10\b", hdr)
+    assert re.search(r"#define\s+STGCN_ABI_VERSION\s+11\b", hdr)
     lib = _capi.lib()
-    assert _capi.ABI_VERSION == 10 and lib.stgcn_version() == 10
+    assert _capi.ABI_VERSION == 11 and lib.stgcn_version() == 11
     for L, D, hidden in ((22, 256, 512), (150, 512, 1024), (180, 512, 1024), (180, 256, 512), (46, 512, 1024), (256, 256, 512)):
         assert lib.stgcn_vit_block_supported(L, D, 8, hidden) == 1
         assert lib.stgcn_vit_block_ws_bytes(32, L, D, hidden) >= min(32, max(1, 32768 // L)) * L * (5 * D + hidden) * 4

@@ -33,9 +33,9 @@ def test_training_abi_declared_and_exported():
     for n in TRAIN_ABI:
         assert re.search(rf"\b{n}\s*\(", hdr), n
         assert n in _capi.PROTOTYPES and hasattr(handle, n), n
-    assert re.search(r"#define\s+STGCN_ABI_VERSION\s+10\b", hdr)
+    assert re.search(r"#define\s+STGCN_ABI_VERSION\s+11\b", hdr)
     lib = _capi.lib()
-    assert _capi.ABI_VERSION == 10 and lib.stgcn_version() == 10
+    assert _capi.ABI_VERSION == 11 and lib.stgcn_version() == 11
     assert (_capi.VIT_DGELU, _capi.VIT_ACCUMULATE) == (0x4000, 0x8000)
     for name, value in (("STGCN_VIT_DGELU", "0x4000u"), ("STGCN_VIT_ACCUMULATE", "0x8000u"), ("STGCN_VIT_GELU", "0x1000u"),
                         ("STGCN_VIT_QKV_F32", "0x2000u")):
