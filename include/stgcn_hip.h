@@ -343,6 +343,22 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
 #define STGCN_VIT_GELU 0x1000u    /* stgcn_vit_linear: exact GELU after the bias                                     */
 #define STGCN_VIT_QKV_F32 0x2000u /* stgcn_vit_block_forward: the qkv linear in f32 whatever the low bits say (an error
                                    * in q or k is multiplied by the size of the scores before the exponential)        */
+/* Tile form of the linears (additive to ABI 10: new flag bits and one query).  The linear kernel exists in three forms that
+ * differ only in the tile of y a workgroup owns: 128 x 128, 64 x 64, and 32 rows x 64 columns.  Every form computes an
+ * element of y with the same instructions in the same order, so results are bit-identical across forms; the smaller ones
+ * spread a small call (one clip) over more workgroups.  stgcn_vit_linear and stgcn_vit_block_forward (all four linears)
+ * honour the field; the training entry points (stgcn_vit_block_forward_train, stgcn_vit_block_backward,
+ * stgcn_vit_linear_backward) always run 128 x 128 and answer STGCN_ERR_ARG to a non-zero field. */
+#define STGCN_VIT_TILE_MASK 0x30000u
+#define STGCN_VIT_TILE_AUTO 0x10000u /* the plan picks: the largest form that gives at least 256 tiles, else the smallest  */
+#define STGCN_VIT_TILE_64 0x20000u   /* force 64 x 64                                                                  */
+#define STGCN_VIT_TILE_32 0x30000u   /* force the 32-row form (32 x 64)                                                */
+/* field 0: 128 x 128 */
+/* The form `flags` gives a linear of this shape, as (BM << 16) | BN; 0 if stgcn_vit_linear does not cover it.  Pure host
+ * function of its arguments (no device query).  stgcn_vit_block_forward walks inputs of more than 32768 tokens in slabs of
+ * whole sequences and plans each slab's linears with M = the slab's tokens, so for such a call ask with a slab's M (and a
+ * short last slab may get a smaller form than the others; the result does not depend on it). */
+int stgcn_vit_linear_tile(int M, int K, int Nout, unsigned flags);
 /* y (M, Nout) = act(LN?(x) W^T + bias) (+ residual).  x (M, K), W (Nout, K).  bias, residual may be NULL; LayerNorm over
  * the rows of x when ln_weight / ln_bias (K) are given (both or neither), biased variance, eps inside the root.
  * Covered: any M, any Nout, K % 32 == 0, with LayerNorm K <= 4096; f32 or bf16x3 (else STGCN_ERR_UNSUPPORTED).

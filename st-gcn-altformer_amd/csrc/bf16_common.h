@@ -130,5 +130,26 @@ __device__ __forceinline__ void mfma_half_bf16(f32x16 (&acc)[2][NJ], const Frag2
     }
 }
 
+// One k-step on a WM x WN accumulator tile: mfma_kstep_bf16 above with the block counts as parameters, and the same product
+// order per block (hi * lo, lo * hi, then hi * hi), which is what makes tiles of different sizes agree bit for bit.
+template <int TERMS, int WM, int WN>
+__device__ __forceinline__ void mfma_kstep_bf16(f32x16 (&acc)[WM][WN], const FragB<TERMS, WM> &a, const FragB<TERMS, WN> &b) {
+#pragma unroll
+    for (int m = 0; m < WM; ++m) {
+        const bf16x8 ah = __builtin_bit_cast(bf16x8, a.hi[m]);
+#pragma unroll
+        for (int n = 0; n < WN; ++n) {
+            const bf16x8 bh = __builtin_bit_cast(bf16x8, b.hi[n]);
+            if constexpr (TERMS == 3) {
+                const bf16x8 al = __builtin_bit_cast(bf16x8, a.lo[m]);
+                const bf16x8 bl = __builtin_bit_cast(bf16x8, b.lo[n]);
+                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m][n], 0, 0, 0);
+                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m][n], 0, 0, 0);
+            }
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m][n], 0, 0, 0);
+        }
+    }
+}
+
 }  // namespace bf16k
 }  // namespace stgcn

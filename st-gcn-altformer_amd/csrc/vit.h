@@ -22,6 +22,37 @@ inline bool math_ok(unsigned flags) {
 
 inline bool linear_ok(int K, int Nout, bool ln) { return K % 32 == 0 && Nout >= 1 && (!ln || K <= kMaxLnDim); }
 
+// ---- the linear's tile form, chosen here and nowhere else (launch_linear_ex and stgcn_vit_linear_tile read it) ----
+// vit_linear.hip has three forms of one kernel: 128 x 128 (4 waves, 2 x 2 blocks of 32 x 32 each), 64 x 64 (4 waves, one
+// block each) and 32 x 64 (2 waves, one block each).  All compute an element of Y with the same instructions in the same
+// order, so the choice moves time, never a bit of the result.
+struct LinearTile {
+    int bm, bn;
+};
+constexpr LinearTile kLinearTiles[3] = {{128, 128}, {64, 64}, {32, 64}};   // largest first
+// STGCN_VIT_TILE_AUTO takes the largest form that cuts the linear into at least this many tiles, the smallest if none does.
+// A compile-time constant (the plan never asks the device): 256 is the CU count of the MI355X, one workgroup per CU.
+// NOT MEASURED yet: tools/time_altformer.py --tiles sweep is the run that settles it (DESIGN section 14 "small calls").
+constexpr int kLinearTileCut = 256;
+
+inline long long linear_tiles(int M, int Nout, LinearTile t) {
+    return (long long)ceil_div(M, t.bm) * ceil_div(Nout, t.bn);
+}
+
+// `flags`: only the STGCN_VIT_TILE_MASK field is read (0: 128 x 128, today's behaviour and what training always runs).
+inline LinearTile linear_tile(int M, int K, int Nout, unsigned flags) {
+    (void)K;   // every form walks all of K in one workgroup
+    switch (flags & STGCN_VIT_TILE_MASK) {
+        case STGCN_VIT_TILE_64: return kLinearTiles[1];
+        case STGCN_VIT_TILE_32: return kLinearTiles[2];
+        case STGCN_VIT_TILE_AUTO:
+            for (const LinearTile t : kLinearTiles)
+                if (linear_tiles(M, Nout, t) >= kLinearTileCut) return t;
+            return kLinearTiles[2];
+        default: return kLinearTiles[0];
+    }
+}
+
 inline bool block_ok(int L, int D, int heads, int hidden) {
     if (L < 1 || D < 1 || heads < 1 || hidden < 1 || D % heads != 0) return false;
     const int hd = D / heads;
@@ -34,7 +65,8 @@ inline int slab_seqs(int B, int L) {
 }
 
 // Y (M, Nout) = act(LN?(X) W^T + bias) (+ R).  X (M, K), W (Nout, K), K % 32 == 0.  gamma / beta / eps: LayerNorm of X's
-// rows applied while the A tile is staged (gamma == nullptr: none).  math: STGCN_MATH_F32 or STGCN_MATH_BF16X3.
+// rows applied while the A tile is staged (gamma == nullptr: none).  math: STGCN_MATH_F32 or STGCN_MATH_BF16X3, optionally
+// with a STGCN_VIT_TILE_* field for linear_tile (every other bit must be clear).
 // Y may alias R (each element is read and written by one thread); it must not alias X.
 int launch_linear(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
                   float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, hipStream_t st);

@@ -1,7 +1,7 @@
 // C entry points of the AltFormer heads' transformer block (include/stgcn_hip.h, "ViT block", ABI 10): the linear and the
 // attention on their own, and the eval forward of one Block = five launches on one stream from a caller workspace:
 //   qkv = LN1(x) Wqkv^T + b -> attention -> x1 = a Wproj^T + b + x -> h = GELU(LN2(x1) W1^T + b1) -> y = h W2^T + b2 + x1
-// (both LayerNorms inside the linear that consumes them).
+// (both LayerNorms inside the linear that consumes them).  A STGCN_VIT_TILE_* field in `flags` goes to the four linears.
 // Long inputs are walked in slabs of whole sequences (kSlabRows tokens): the four intermediates of a slab (about 7 KB per
 // token at D = 256) then stay within reach of the caches between the launches that write and read them, and the
 // workspace does not grow with the batch.
@@ -38,6 +38,12 @@ int stgcn_vit_linear_supported(int M, int K, int Nout, unsigned flags) {
     return M >= 1 && K >= 1 && math_ok(flags) && linear_ok(K, Nout, false) ? 1 : 0;
 }
 
+int stgcn_vit_linear_tile(int M, int K, int Nout, unsigned flags) {
+    if (!stgcn_vit_linear_supported(M, K, Nout, flags)) return 0;
+    const LinearTile t = linear_tile(M, K, Nout, flags);
+    return (t.bm << 16) | t.bn;
+}
+
 int stgcn_vit_linear(const float *x, const float *W, const float *bias, const float *ln_weight, const float *ln_bias,
                      float ln_eps, const float *residual, float *y, int M, int K, int Nout, unsigned flags,
                      void *stream) {
@@ -50,7 +56,7 @@ int stgcn_vit_linear(const float *x, const float *W, const float *bias, const fl
                     Nout, flags & STGCN_MATH_MASK);
     hipStream_t st = static_cast<hipStream_t>(stream);
     return launch_linear(x, W, bias, residual, ln_weight, ln_bias, ln_eps, y, M, K, Nout, (flags & STGCN_VIT_GELU) != 0,
-                         flags & STGCN_MATH_MASK, st);
+                         flags & (STGCN_MATH_MASK | STGCN_VIT_TILE_MASK), st);
 }
 
 int stgcn_vit_attention_supported(int L, int heads, int head_dim) {
@@ -89,8 +95,9 @@ int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const flo
     if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward: workspace %zu < %zu bytes", ws_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *qkv = w.qkv, *att = w.att, *x1 = w.x1, *hid = w.hid;
-    const unsigned math = flags & STGCN_MATH_MASK;
-    const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : math;
+    const unsigned tile = flags & STGCN_VIT_TILE_MASK;   // the plan (vit.h) reads it per linear
+    const unsigned math = (flags & STGCN_MATH_MASK) | tile;
+    const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 | tile : math;
     const int per = slab_seqs(B, L);
     for (int b0 = 0; b0 < B; b0 += per) {
         const int nb = B - b0 < per ? B - b0 : per;

@@ -20,6 +20,13 @@
 // No atomics anywhere: one thread owns each output element and sums in a fixed order.
 // Training (vit_block_train.hip) runs this kernel too: the forward with LinearExtra's pre-activation store and row factor,
 // the dgrads as this linear on a transposed weight with the GELU' and row-factor steps of the epilogue (vit.h).
+//
+// Tile forms (Form below; vit.h's linear_tile chooses): the kernel is one template over the waves of a workgroup and the
+// 32 x 32 blocks of a wave.  128 x 128 is the form described above; 64 x 64 (4 waves, one block each) and 32 x 64 (2 waves,
+// one block each) exist for calls too small to fill the part with 128 x 128 tiles (one clip: 62 of them in a proj linear).
+// A form only changes which workgroup and wave owns a 32 x 32 block of Y: the block's accumulator sees the same k pairs in
+// the same MFMA instructions in the same order, and a row's LayerNorm statistics are the same 8-thread sums and three
+// exchanges, so every form's result is bit-identical to the 128 x 128 form's.
 #include "bf16_common.h"
 #include "vit.h"
 
@@ -29,12 +36,12 @@ namespace vit {
 using bf16k::bf16_hi_to_f32;
 using bf16k::bf16_lo_to_f32;
 using bf16k::f32x16;
-using bf16k::Frag2;
+using bf16k::FragB;
 using bf16k::pack_bf16x2;
 
 namespace {
 
-constexpr int BM = 128, BN = 128, KC = 32;
+constexpr int KC = 32;
 constexpr int LDF = KC + 4;  // fp32 tile row stride, floats
 constexpr int LDH = KC + 8;  // bf16 tile row stride, elements (80 bytes)
 
@@ -45,41 +52,57 @@ __device__ __forceinline__ void split4(const float4 v, uint2 &hi, uint2 &lo) {
     lo.y = pack_bf16x2(v.z - bf16_lo_to_f32(hi.y), v.w - bf16_hi_to_f32(hi.y));
 }
 
-template <int MATH>
+// A workgroup of WAVES waves, two of them side by side along Nout, each owning WM x WN blocks of 32 x 32.
+template <int WAVES_, int WM_, int WN_>
+struct Form {
+    static constexpr int WAVES = WAVES_, WM = WM_, WN = WN_;
+    static constexpr int THREADS = 64 * WAVES;
+    static constexpr int BM = (WAVES / 2) * WM * 32, BN = 2 * WN * 32;
+    static constexpr int RS = THREADS / 8;            // rows staged per pass: 8 threads, one float4 each, per 32-float row
+    static constexpr int PA = BM / RS, PB = BN / RS;  // passes over the A and the B tile
+    static constexpr int PMAX = PA > PB ? PA : PB;
+    static_assert(WAVES % 2 == 0 && BM % RS == 0 && BN % RS == 0 && WM == WN, "tile form");
+};
+using Form128 = Form<4, 2, 2>;   // 128 x 128
+using Form64 = Form<4, 1, 1>;    //  64 x  64
+using Form32 = Form<2, 1, 1>;    //  32 x  64
+
+template <int MATH, int BM, int BN>
 struct Tiles;
-template <>
-struct Tiles<STGCN_MATH_F32> {
+template <int BM, int BN>
+struct Tiles<STGCN_MATH_F32, BM, BN> {
     float a[BM * LDF];
     float b[BN * LDF];
 };
-template <>
-struct Tiles<STGCN_MATH_BF16X3> {
+template <int BM, int BN>
+struct Tiles<STGCN_MATH_BF16X3, BM, BN> {
     unsigned short ah[BM * LDH], al[BM * LDH];
     unsigned short bh[BN * LDH], bl[BN * LDH];
 };
 
-template <int MATH>
-__global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict__ X, const float *__restrict__ W,
+template <int MATH, class F>
+__global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const float *__restrict__ X, const float *__restrict__ W,
                                                         const float *__restrict__ bias, const float *R,
                                                         const float *__restrict__ gamma, const float *__restrict__ beta,
                                                         float eps, float *Y, int M, int K, int Nout, int tiles_n,
                                                         int gelu, const LinearExtra ex) {
-    __shared__ __attribute__((aligned(16))) Tiles<MATH> lds;
+    constexpr int BM = F::BM, BN = F::BN, RS = F::RS, PA = F::PA, PB = F::PB, WM = F::WM, WN = F::WN;
+    __shared__ __attribute__((aligned(16))) Tiles<MATH, BM, BN> lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int n0 = ((int)blockIdx.x % tiles_n) * BN, m0 = ((int)blockIdx.x / tiles_n) * BM;
-    const int lr = tid >> 3, lc = (tid & 7) * 4;   // staging: rows lr + 32 i, floats lc .. lc + 3 of the chunk
+    const int lr = tid >> 3, lc = (tid & 7) * 4;   // staging: rows lr + RS i, floats lc .. lc + 3 of the chunk
     const int l31 = lane & 31, half = lane >> 5;
 
-    // LayerNorm statistics of the tile's 128 rows, workgroup-local: the 8 threads that stage a row read it once (K is the
+    // LayerNorm statistics of the tile's BM rows, workgroup-local: the 8 threads that stage a row read it once (K is the
     // whole row; it is about to be read again for the A tiles, so this pass mostly primes the cache), sum x - c and
     // (x - c)^2 with c = the row's first element (no cancellation for rows with a large offset), and combine with three
     // exchanges in a fixed order.  Every workgroup of a row slab repeats this; it replaces a pre-pass and its buffer.
     const bool ln = gamma != nullptr;
-    float mean[4], rstd[4];
+    float mean[PA], rstd[PA];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = m0 + lr + 32 * i;
+    for (int i = 0; i < PA; ++i) {
+        const int row = m0 + lr + RS * i;
         float s = 0.f, q = 0.f, c = 0.f;
         if (ln && row < M) {
             const float4 *p = reinterpret_cast<const float4 *>(X + (size_t)row * K);
@@ -102,14 +125,16 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
     }
 
     const int kx = ex.kx > 0 ? ex.kx : K;   // X's row length: K, or (backward) a length that is no multiple of KC, zero-padded
-    float4 xa[4], wb[4];
+    float4 xa[PA], wb[PB];
     auto gload = [&](int k0) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = m0 + lr + 32 * i, n = n0 + lr + 32 * i;
-            xa[i] = row < M && k0 + lc < kx ? *reinterpret_cast<const float4 *>(X + (size_t)row * kx + k0 + lc)
-                                            : make_float4(0.f, 0.f, 0.f, 0.f);
-            wb[i] = n < Nout ? *reinterpret_cast<const float4 *>(W + (size_t)n * K + k0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int i = 0; i < F::PMAX; ++i) {
+            const int row = m0 + lr + RS * i, n = n0 + lr + RS * i;
+            if (i < PA)
+                xa[i] = row < M && k0 + lc < kx ? *reinterpret_cast<const float4 *>(X + (size_t)row * kx + k0 + lc)
+                                                : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (i < PB)
+                wb[i] = n < Nout ? *reinterpret_cast<const float4 *>(W + (size_t)n * K + k0 + lc) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
     auto sstore = [&](int k0) {
@@ -119,35 +144,42 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
             b = *reinterpret_cast<const float4 *>(beta + k0 + lc);
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float4 v = xa[i];
-            if (ln) {
-                v.x = (v.x - mean[i]) * rstd[i] * g.x + b.x;
-                v.y = (v.y - mean[i]) * rstd[i] * g.y + b.y;
-                v.z = (v.z - mean[i]) * rstd[i] * g.z + b.z;
-                v.w = (v.w - mean[i]) * rstd[i] * g.w + b.w;
+        for (int i = 0; i < F::PMAX; ++i) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (i < PA) {
+                v = xa[i];
+                if (ln) {
+                    v.x = (v.x - mean[i]) * rstd[i] * g.x + b.x;
+                    v.y = (v.y - mean[i]) * rstd[i] * g.y + b.y;
+                    v.z = (v.z - mean[i]) * rstd[i] * g.z + b.z;
+                    v.w = (v.w - mean[i]) * rstd[i] * g.w + b.w;
+                }
             }
-            const int r = lr + 32 * i;
+            const int r = lr + RS * i;
             if constexpr (MATH == STGCN_MATH_F32) {
-                *reinterpret_cast<float4 *>(&lds.a[r * LDF + lc]) = v;
-                *reinterpret_cast<float4 *>(&lds.b[r * LDF + lc]) = wb[i];
+                if (i < PA) *reinterpret_cast<float4 *>(&lds.a[r * LDF + lc]) = v;
+                if (i < PB) *reinterpret_cast<float4 *>(&lds.b[r * LDF + lc]) = wb[i];
             } else {
                 uint2 hi, lo;
-                split4(v, hi, lo);
-                *reinterpret_cast<uint2 *>(&lds.ah[r * LDH + lc]) = hi;
-                *reinterpret_cast<uint2 *>(&lds.al[r * LDH + lc]) = lo;
-                split4(wb[i], hi, lo);
-                *reinterpret_cast<uint2 *>(&lds.bh[r * LDH + lc]) = hi;
-                *reinterpret_cast<uint2 *>(&lds.bl[r * LDH + lc]) = lo;
+                if (i < PA) {
+                    split4(v, hi, lo);
+                    *reinterpret_cast<uint2 *>(&lds.ah[r * LDH + lc]) = hi;
+                    *reinterpret_cast<uint2 *>(&lds.al[r * LDH + lc]) = lo;
+                }
+                if (i < PB) {
+                    split4(wb[i], hi, lo);
+                    *reinterpret_cast<uint2 *>(&lds.bh[r * LDH + lc]) = hi;
+                    *reinterpret_cast<uint2 *>(&lds.bl[r * LDH + lc]) = lo;
+                }
             }
         }
     };
 
-    f32x16 acc[2][2];
+    f32x16 acc[WM][WN];
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < WM; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n)
+        for (int n = 0; n < WN; ++n)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
 
@@ -159,11 +191,11 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
         const bool more = c + 1 < chunks;
         if (more) gload((c + 1) * KC);
         if constexpr (MATH == STGCN_MATH_F32) {
-            float a[2][16], b[2][16];
+            float a[WM][16], b[WN][16];
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const float4 *ap = reinterpret_cast<const float4 *>(&lds.a[(wm * 64 + m * 32 + l31) * LDF + half * 16]);
-                const float4 *bp = reinterpret_cast<const float4 *>(&lds.b[(wn * 64 + m * 32 + l31) * LDF + half * 16]);
+            for (int m = 0; m < WM; ++m) {   // WM == WN: one loop reads both operands' fragments
+                const float4 *ap = reinterpret_cast<const float4 *>(&lds.a[(wm * (32 * WM) + m * 32 + l31) * LDF + half * 16]);
+                const float4 *bp = reinterpret_cast<const float4 *>(&lds.b[(wn * (32 * WN) + m * 32 + l31) * LDF + half * 16]);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float4 va = ap[j], vb = bp[j];
@@ -174,24 +206,25 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
 #pragma unroll
             for (int s = 0; s < 16; ++s)
 #pragma unroll
-                for (int m = 0; m < 2; ++m)
+                for (int m = 0; m < WM; ++m)
 #pragma unroll
-                    for (int n = 0; n < 2; ++n)
+                    for (int n = 0; n < WN; ++n)
                         acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][s], b[n][s], acc[m][n], 0, 0, 0);
         } else {
 #pragma unroll
             for (int ks = 0; ks < KC / 16; ++ks) {
-                Frag2<3> fa, fb;
+                FragB<3, WM> fa;
+                FragB<3, WN> fb;
 #pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const int ao = (wm * 64 + m * 32 + l31) * LDH + ks * 16 + half * 8;
-                    const int bo = (wn * 64 + m * 32 + l31) * LDH + ks * 16 + half * 8;
+                for (int m = 0; m < WM; ++m) {   // WM == WN: one loop reads both operands' fragments
+                    const int ao = (wm * (32 * WM) + m * 32 + l31) * LDH + ks * 16 + half * 8;
+                    const int bo = (wn * (32 * WN) + m * 32 + l31) * LDH + ks * 16 + half * 8;
                     fa.hi[m] = *reinterpret_cast<const uint4 *>(&lds.ah[ao]);
                     fa.lo[m] = *reinterpret_cast<const uint4 *>(&lds.al[ao]);
                     fb.hi[m] = *reinterpret_cast<const uint4 *>(&lds.bh[bo]);
                     fb.lo[m] = *reinterpret_cast<const uint4 *>(&lds.bl[bo]);
                 }
-                bf16k::mfma_kstep_bf16<3>(acc, fa, fb);
+                bf16k::mfma_kstep_bf16<3, WM, WN>(acc, fa, fb);
             }
         }
         __syncthreads();
@@ -204,15 +237,15 @@ __global__ __launch_bounds__(256) void vit_linear_kernel(const float *__restrict
     // epilogue: lane holds column n = l31 of each 32 x 32 block, rows 8 (i / 4) + 4 half + i % 4
     constexpr float kRsqrt2 = 0.70710678118654752440f;
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int col = n0 + wn * 64 + n * 32 + l31;
+    for (int n = 0; n < WN; ++n) {
+        const int col = n0 + wn * (32 * WN) + n * 32 + l31;
         if (col >= Nout) continue;
         const float bv = bias != nullptr ? bias[col] : 0.f;
 #pragma unroll
-        for (int m = 0; m < 2; ++m) {
+        for (int m = 0; m < WM; ++m) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int row = m0 + wm * 64 + m * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                const int row = m0 + wm * (32 * WM) + m * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
                 if (row >= M) continue;
                 float v = acc[m][n][i] + bv;
                 const size_t idx = (size_t)row * Nout + col;
@@ -237,20 +270,39 @@ int launch_linear(const float *X, const float *W, const float *bias, const float
     return launch_linear_ex(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, math, LinearExtra{}, st);
 }
 
+namespace {
+
+template <int MATH, class F>
+int launch_form(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta, float eps,
+                float *Y, int M, int K, int Nout, bool gelu, const LinearExtra &ex, hipStream_t st) {
+    const int tiles_n = ceil_div(Nout, F::BN);
+    const long long tiles = (long long)tiles_n * ceil_div(M, F::BM);
+    if (tiles > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit linear: %lld tiles", tiles);
+    vit_linear_kernel<MATH, F><<<dim3((unsigned)tiles), dim3(F::THREADS), 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout,
+                                                                                 tiles_n, gelu, ex);
+    STGCN_LAUNCH_CHECK("vit_linear_kernel");
+    return STGCN_OK;
+}
+
+template <int MATH>
+int launch_math(const LinearTile t, const float *X, const float *W, const float *bias, const float *R, const float *gamma,
+                const float *beta, float eps, float *Y, int M, int K, int Nout, bool gelu, const LinearExtra &ex, hipStream_t st) {
+    static_assert(Form128::BM == 128 && Form128::BN == 128 && Form64::BM == 64 && Form64::BN == 64 && Form32::BM == 32 &&
+                  Form32::BN == 64, "the forms linear_tile (vit.h) plans with");
+    if (t.bm == Form128::BM) return launch_form<MATH, Form128>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    if (t.bm == Form64::BM) return launch_form<MATH, Form64>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    return launch_form<MATH, Form32>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+}
+
+}  // namespace
+
 int launch_linear_ex(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
                      float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, const LinearExtra &ex,
                      hipStream_t st) {
-    const int tiles_n = ceil_div(Nout, BN);
-    const long long tiles = (long long)tiles_n * ceil_div(M, BM);
-    if (tiles > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit linear: %lld tiles", tiles);
-    const dim3 grid((unsigned)tiles), block(256);
-    if (math == STGCN_MATH_F32)
-        vit_linear_kernel<STGCN_MATH_F32><<<grid, block, 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, tiles_n, gelu, ex);
-    else
-        vit_linear_kernel<STGCN_MATH_BF16X3><<<grid, block, 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, tiles_n,
-                                                                     gelu, ex);
-    STGCN_LAUNCH_CHECK("vit_linear_kernel");
-    return STGCN_OK;
+    const LinearTile t = linear_tile(M, K, Nout, math);
+    if ((math & STGCN_MATH_MASK) == STGCN_MATH_F32)
+        return launch_math<STGCN_MATH_F32>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    return launch_math<STGCN_MATH_BF16X3>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
 }
 
 }  // namespace vit

@@ -33,6 +33,10 @@ VIT_GELU = 0x1000  # stgcn_vit_linear: exact GELU after the bias
 VIT_QKV_F32 = 0x2000  # stgcn_vit_block_forward: the qkv linear in f32 whatever the math bits say
 VIT_DGELU = 0x4000  # stgcn_vit_linear_backward: dx times GELU'(h_pre)
 VIT_ACCUMULATE = 0x8000  # stgcn_vit_linear_backward: dx += instead of dx =
+VIT_TILE_MASK = 0x30000  # stgcn_vit_linear / stgcn_vit_block_forward: tile form of the linears (0: 128 x 128)
+VIT_TILE_AUTO = 0x10000  # the plan picks by workgroup count (stgcn_vit_linear_tile tells)
+VIT_TILE_64 = 0x20000  # force 64 x 64
+VIT_TILE_32 = 0x30000  # force the 32-row form (32 x 64)
 MATH_F16MX = MATH_BF16X3 | STEM_F16MX   # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
 
 STATUS = {0: "STGCN_OK", -1: "STGCN_ERR_ARG", -2: "STGCN_ERR_UNSUPPORTED",
@@ -78,6 +82,7 @@ PROTOTYPES = {
                                          + [c_uint, _P]),
     "stgcn_st_attention_backward": (c_int, [_P] * 24 + [c_size_t] + [c_int] * 7 + [c_uint, _P]),
     "stgcn_vit_linear_supported": (c_int, [c_int] * 3 + [c_uint]),
+    "stgcn_vit_linear_tile": (c_int, [c_int] * 3 + [c_uint]),
     "stgcn_vit_linear": (c_int, [_P] * 5 + [c_float] + [_P] * 2 + [c_int] * 3 + [c_uint, _P]),
     "stgcn_vit_attention_supported": (c_int, [c_int] * 3),
     "stgcn_vit_attention": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),

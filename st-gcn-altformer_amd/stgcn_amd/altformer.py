@@ -20,6 +20,14 @@ Two paths, one result:
   with the torch path's calls in its order (same seed, same masks) and the kernels apply them per sequence.  The parameters
   are taken by attribute, so an ``nn.DataParallel`` replica's gradients reach its master.  ``Block.trains_on_hip(x)`` tells.
   Default arithmetic ``'f32'`` (``DEFAULT_TRAIN_MATH``, env ``STGCN_VIT_TRAIN_MATH``; ``set_head_math`` overrides both paths).
+* HIP, low latency (``set_low_latency(model, min_tokens=0)``): the inference path above for small calls, down to one clip.
+  Each ``Block`` gets ``small_tiles`` (its four linears run the tile form ``VIT_TILE_AUTO`` picks for their size: 64 x 64 or
+  32 x 64 tiles where 128 x 128 ones would leave most of the part idle) and the inference threshold ``min_tokens``.  Without
+  ``min_tokens`` the threshold is ``LOW_LATENCY_MIN_TOKENS`` (see there for what has been measured).  Every form
+  computes an output element with the same instructions in the same order, so the result is bit-identical to the
+  128 x 128 form's.  The forward launches on one stream and takes its workspace from torch's allocator, so it captures under
+  ``torch.cuda.graph`` as one sequential graph.  Not covered: training (the training kernels always run 128 x 128 tiles and
+  ``hip_train_min_tokens`` is never touched), and the attention kernel, which at one clip has one workgroup per head.
 * torch ops: everything else - CPU tensors, shapes the kernels do not cover, active dropout, calls under the thresholds,
   ``force_torch``.  This is the reference's arithmetic op for op, so its training scripts keep working unchanged.
 
@@ -41,7 +49,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import functional as F
-from ._capi import MATH_BF16X3, MATH_F32, VIT_QKV_F32
+from ._capi import MATH_BF16X3, MATH_F32, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK
 from .modules import Unit2D, enable_stem_fusion, import_class, unit_agcn
 
 HEAD_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32}
@@ -69,6 +77,25 @@ HIP_TRAIN_MIN_TOKENS = 13200   # forward + backward of a block (tools/time_altfo
 HIP_MIN_TOKENS = 4096   # below this many tokens (B * L) per call a block's five launches are latency-bound and the library's
 #                         small GEMMs are as fast or faster (measured at batch 32: the TS head's spatial stage, 1472 and 704
 #                         tokens, 0.32 against 0.27 ms per block): the block then takes its torch path
+
+
+LOW_LATENCY_MIN_TOKENS = HIP_MIN_TOKENS   # the token count from which the auto-tile HIP block beats the torch path: NOT MEASURED yet
+#                                          (tools/time_altformer.py --tiles sweep --batch 1 is the run), so it stays where the
+#                                          128 x 128 measurement put it; set_low_latency(model, min_tokens=0) runs one clip on HIP
+
+
+def set_low_latency(module: nn.Module, enabled: bool = True, min_tokens=None) -> None:
+    """Small inference calls (down to one clip) of every ``Block`` below on the HIP kernels: ``small_tiles`` (the linears'
+    tile form picked per call size, same result bit for bit) and the inference threshold ``min_tokens``
+    (``LOW_LATENCY_MIN_TOKENS`` when None).  ``enabled=False`` restores ``small_tiles = False`` and ``HIP_MIN_TOKENS``.
+    The training threshold is not touched."""
+    for sub in module.modules():
+        if isinstance(sub, Block):
+            sub.small_tiles = bool(enabled)
+            if not enabled:
+                sub.hip_min_tokens = HIP_MIN_TOKENS
+            else:
+                sub.hip_min_tokens = LOW_LATENCY_MIN_TOKENS if min_tokens is None else int(min_tokens)
 
 
 def set_hip_min_tokens(module: nn.Module, tokens: int) -> None:
@@ -200,6 +227,7 @@ class Block(nn.Module):
         self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
         self.hip_min_tokens = HIP_MIN_TOKENS   # set_hip_min_tokens
         self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
+        self.small_tiles = False               # set_low_latency: the inference linears pick their tile form by call size
 
     def _weights(self):
         """The parameters by attribute (an nn.DataParallel replica has no ``parameters()``)."""
@@ -259,6 +287,8 @@ class Block(nn.Module):
         if self.uses_hip(x):
             a, m = self.attn, self.mlp
             math = _default_head_math() if self.math_mode is None else self.math_mode
+            if self.small_tiles and not math & VIT_TILE_MASK:   # a form forced through math_mode stands
+                math |= VIT_TILE_AUTO
             with torch.no_grad():
                 return F.vit_block_forward(x.contiguous(), (self.norm1.weight, self.norm1.bias), (a.qkv.weight, a.qkv.bias),
                                            (a.proj.weight, a.proj.bias), (self.norm2.weight, self.norm2.bias),
@@ -266,7 +296,7 @@ class Block(nn.Module):
                                            a.scale, math)
         if self.trains_on_hip(x):
             s1, s2 = self.draw_drop_path(x)
-            math = _default_train_math() if self.math_mode is None else self.math_mode
+            math = _default_train_math() if self.math_mode is None else self.math_mode & ~VIT_TILE_MASK   # tile forms: inference only
             return _BlockTrain.apply(x, None if s1 is None else s1.reshape(-1), None if s2 is None else s2.reshape(-1),
                                      self.attn.num_heads, self.norm1.eps, self.attn.scale, math, *self._weights())
         x = x + self.drop_path(self.attn(self.norm1(x)))

@@ -519,7 +519,7 @@ def st_attention_backward(x, dbn_weight, dbn_bias, Wqkv, Wout, bn_weight, bn_bia
 
 # ---- AltFormer heads: transformer block (stgcn_vit_*) ---------------------------------------------------------------------
 def _vit_flags(math: int) -> int:
-    return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32)
+    return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32 | _capi.VIT_TILE_MASK)
 
 
 def _bytes(dev, nbytes):
@@ -530,9 +530,17 @@ def vit_linear_supported(M, K, Nout, math=MATH_F32) -> bool:
     return bool(_capi.lib().stgcn_vit_linear_supported(M, K, Nout, math & _capi.MATH_MASK))
 
 
-def vit_linear(x, weight, bias=None, ln=None, residual=None, gelu=False, math=MATH_F32) -> torch.Tensor:
+def vit_linear_tile(M, K, Nout, math=MATH_F32):
+    """The tile ``(BM, BN)`` of the linear kernel that ``math`` (its ``VIT_TILE_*`` field) gives this shape; None if the linear
+    does not cover it.  A host function: no GPU needed."""
+    t = _capi.lib().stgcn_vit_linear_tile(M, K, Nout, math & (_capi.MATH_MASK | _capi.VIT_TILE_MASK))
+    return (t >> 16, t & 0xFFFF) if t else None
+
+
+def vit_linear(x, weight, bias=None, ln=None, residual=None, gelu=False, math=MATH_F32, y=None) -> torch.Tensor:
     """``act(LN?(x) W^T + b) (+ residual)`` on the last axis of x (..., K); weight (Nout, K) as nn.Linear stores it.
-    ``ln`` = (weight, bias, eps) of a LayerNorm over K applied to x's rows first, or None; ``gelu``: exact GELU."""
+    ``ln`` = (weight, bias, eps) of a LayerNorm over K applied to x's rows first, or None; ``gelu``: exact GELU.
+    ``math`` may carry a ``VIT_TILE_*`` field (the result does not depend on it).  ``y``: write here (may be ``residual``)."""
     dev = x.device
     K = x.shape[-1]
     M = x.numel() // K
@@ -541,13 +549,18 @@ def vit_linear(x, weight, bias=None, ln=None, residual=None, gelu=False, math=MA
         raise ValueError(f"weight is {tuple(weight.shape)}, x has {K} features")
     if residual is not None and residual.numel() != M * Nout:
         raise ValueError(f"residual has {residual.numel()} elements, expected {M * Nout}")
-    y = torch.empty(x.shape[:-1] + (Nout,), device=dev, dtype=torch.float32)
+    if y is None:
+        y = torch.empty(x.shape[:-1] + (Nout,), device=dev, dtype=torch.float32)
+    elif y.shape != x.shape[:-1] + (Nout,):
+        raise ValueError(f"y is {tuple(y.shape)}, expected {tuple(x.shape[:-1]) + (Nout,)}")
+    elif y.data_ptr() == x.data_ptr():
+        raise ValueError("y must not alias x")
     lnw, lnb, eps = ln if ln is not None else (None, None, 0.0)
-    fl = (math & _capi.MATH_MASK) | (_capi.VIT_GELU if gelu else 0)
+    fl = (math & (_capi.MATH_MASK | _capi.VIT_TILE_MASK)) | (_capi.VIT_GELU if gelu else 0)
     with torch.cuda.device(dev):
         _capi.call("stgcn_vit_linear", _dev_ptr(x, "x", dev), _dev_ptr(weight, "weight", dev), _dev_ptr(bias, "bias", dev),
                    _dev_ptr(lnw, "ln weight", dev), _dev_ptr(lnb, "ln bias", dev), c_float(eps),
-                   _dev_ptr(residual, "residual", dev), _dev_ptr(y, "y"), c_int(M), c_int(K), c_int(Nout), c_uint(fl), _stream(dev))
+                   _dev_ptr(residual, "residual", dev), _dev_ptr(y, "y", dev), c_int(M), c_int(K), c_int(Nout), c_uint(fl), _stream(dev))
     return y
 
 
@@ -578,7 +591,7 @@ def vit_block_supported(L, D, heads, hidden) -> bool:
 def vit_block_forward(x, norm1, qkv, proj, norm2, fc1, fc2, heads, eps, scale, math=MATH_F32) -> torch.Tensor:
     """Eval forward of one transformer Block on x (B, L, D).  ``norm1`` / ``norm2`` = (weight, bias) of the LayerNorms (one
     ``eps``), ``qkv`` / ``proj`` / ``fc1`` / ``fc2`` = (weight, bias or None) of the nn.Linears as stored.  ``math``: MATH_F32
-    or MATH_BF16X3, optionally | VIT_QKV_F32."""
+    or MATH_BF16X3, optionally | VIT_QKV_F32, optionally | a VIT_TILE_* form for the four linears (same result, bit for bit)."""
     dev = x.device
     B, L, D = x.shape
     hidden = fc1[0].shape[0]
@@ -617,7 +630,7 @@ def vit_linear_backward(dy, a, weight, h_pre=None, dx_accumulate=None, need_dx=T
     db = torch.empty(Nout, device=dev, dtype=torch.float32) if need_dw and need_db else None
     nbytes = _capi.lib().stgcn_vit_linear_backward_ws_bytes(M, K, Nout)
     ws = _bytes(dev, nbytes)
-    fl = (math & _capi.MATH_MASK) | (_capi.VIT_DGELU if h_pre is not None and need_dx else 0) \
+    fl = (math & (_capi.MATH_MASK | _capi.VIT_TILE_MASK)) | (_capi.VIT_DGELU if h_pre is not None and need_dx else 0) \
         | (_capi.VIT_ACCUMULATE if dx_accumulate is not None else 0)
     with torch.cuda.device(dev):
         _capi.call("stgcn_vit_linear_backward", _dev_ptr(dy, "dy", dev), _dev_ptr(a if need_dw else None, "a", dev),

@@ -2,7 +2,8 @@
 """Time the AltFormer heads: the HIP path of every stage's transformer block and of the whole ST / TS models against the
 torch-op path of the same module, in one process, alternating, with device events.
 
-    python tools/time_altformer.py [--batch 32] [--repeats 7] [--warmup 2] [--out profiles/altformer_times.json]
+    python tools/time_altformer.py [--batch 32] [--repeats 7] [--warmup 2] [--tiles 128|auto|64|32|sweep]
+                                   [--out profiles/altformer_times.json]
 
 Prints ONE JSON line.  Per stage (a Block at the stage's shape, batch ``--batch``): ms of the HIP path (default arithmetic,
 and 'f32' / 'bf16x3' for comparison) and of the torch path (min, median, max over the repeats; ``spread`` = (max - min) / min of
@@ -10,6 +11,12 @@ the torch path and of the HIP path, the noise the comparison has to be read agai
 shapes, and per launch (the four linears in the arithmetic the default uses for them, the attention) ms, achieved TFLOP/s and
 the share of the relevant peak: 155 TFLOP/s for the fp32 matrix cores (measured), 2500 / 3 for bf16x3.  Whole models: the
 reference's SHREC configuration (14 classes, 180 frames, 22 joints) from skeleton clips to logits, stem + head, clips/s.
+
+``--tiles`` sets the tile form of the linears (STGCN_VIT_TILE_*) on every HIP row; ``sweep`` times all four forms of every
+stage and launch in the same alternation (``tiles`` per stage: block ms per form, the forms ``auto`` picked for the four
+linears, ms per launch per form, the attention's share of the ``auto`` block) and adds ``low_latency`` per model: the
+default policy (at one clip: every block on torch ops), ``set_low_latency`` eager, and the same forward captured in a graph
+and replayed.
 """
 import argparse
 import json
@@ -70,6 +77,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--tiles", choices=["128", "auto", "64", "32", "sweep"], default="128")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
@@ -81,9 +89,13 @@ def main():
     norm = partial(torch.nn.LayerNorm, eps=1e-6)
     res = {"batch": args.batch, "repeats": args.repeats, "default_math": DEFAULT_HEAD_MATH, "device": torch.cuda.get_device_name(0),
            "stages": {}, "models": {}}
+    TILE = {"128": 0, "auto": F._capi.VIT_TILE_AUTO, "64": F._capi.VIT_TILE_64, "32": F._capi.VIT_TILE_32}
+    sweep = args.tiles == "sweep"
+    tile = TILE["128" if sweep else args.tiles]
+    res["tiles"] = args.tiles
     flags = HEAD_MATH[DEFAULT_HEAD_MATH]
-    math_rest = flags & F._capi.MATH_MASK
-    math_qkv = F.MATH_F32 if flags & F._capi.VIT_QKV_F32 else math_rest
+    math_rest = flags & F._capi.MATH_MASK | tile
+    math_qkv = (F.MATH_F32 | tile) if flags & F._capi.VIT_QKV_F32 else math_rest
     with torch.no_grad():
         for name, (per_clip, L, D) in STAGES.items():
             B = args.batch * per_clip
@@ -97,10 +109,18 @@ def main():
             def run(mode):
                 blk.force_torch = mode == "torch"
                 if mode != "torch":
-                    set_head_math(blk, mode)
+                    set_head_math(blk, HEAD_MATH[mode] | tile)
                 return blk(x)
             ts = alternate({m: partial(run, m) for m in ("torch", DEFAULT_HEAD_MATH, "f32", "bf16x3")}, args.repeats, args.warmup)
             blk.force_torch = False
+            if sweep:
+                def run_form(form):
+                    blk.force_torch = form == "torch"
+                    if form != "torch":
+                        set_head_math(blk, flags | TILE[form])
+                    return blk(x)
+                form_ts = alternate({f: partial(run_form, f) for f in ("torch", "128", "auto", "64", "32")}, args.repeats, args.warmup)
+                blk.force_torch = False
             a, m = blk.attn, blk.mlp
             ln1, ln2 = (blk.norm1.weight, blk.norm1.bias, 1e-6), (blk.norm2.weight, blk.norm2.bias, 1e-6)
             qkv = F.vit_linear(x, a.qkv.weight, a.qkv.bias, ln=ln1, math=math_qkv)
@@ -123,12 +143,34 @@ def main():
                                "arithmetic": "f32" if f32 else "bf16x3",
                                "share_of_peak": round(tf / (PEAK_F32 if f32 else PEAK_BF16X3), 3)}
             hip, tor = ts[DEFAULT_HEAD_MATH], ts["torch"]
+            swept = None
+            if sweep:
+                lin = {"qkv": (x, a.qkv.weight, a.qkv.bias, dict(ln=ln1), math_qkv), "proj": (att, a.proj.weight, a.proj.bias, dict(residual=x), math_rest),
+                       "fc1": (x, m.fc1.weight, m.fc1.bias, dict(ln=ln2, gelu=True), math_rest), "fc2": (h, m.fc2.weight, m.fc2.bias, dict(residual=x), math_rest)}
+                fns = {f"{k} {f}": partial(F.vit_linear, xi, W, b, math=mt | TILE[f], **kw) for k, (xi, W, b, kw, mt) in lin.items()
+                       for f in ("128", "auto", "64", "32")}
+                fns["attention"] = lambda: F.vit_attention(qkv, heads, a.scale)
+                lt = alternate(fns, args.repeats, args.warmup)
+                slab_m = min(B, max(1, 32768 // L)) * L     # the block walks slabs of whole sequences; the plan sees a slab's rows
+                med = {f: statistics.median(form_ts[f]) for f in form_ts}
+                # the margin of a comparison of two medians: the larger of the two spreads (as hip_not_slower above)
+                swept = {"block_ms": {f: summary(t) for f, t in form_ts.items()},
+                         "auto_forms": {k: "x".join(map(str, F.vit_linear_tile(slab_m, W.shape[1], W.shape[0], TILE["auto"])))
+                                        for k, (xi, W, b, kw, mt) in lin.items()},
+                         "launch_ms": {k: summary(t) for k, t in lt.items()},
+                         "auto_vs_128": round(med["128"] / med["auto"], 3),
+                         "auto_not_slower_than_128": med["auto"] <= med["128"] * (1 + max(summary(form_ts["auto"])["spread"], summary(form_ts["128"])["spread"])),
+                         "auto_vs_torch": round(med["torch"] / med["auto"], 3),
+                         "auto_beats_torch": med["auto"] * (1 + max(summary(form_ts["auto"])["spread"], summary(form_ts["torch"])["spread"])) < med["torch"],
+                         "attention_share_of_auto_block": round(statistics.median(lt["attention"]) / med["auto"], 3)}
             res["stages"][name] = {
                 "B": B, "L": L, "D": D, "tokens": M, "module_chooses": chooses, "gflop": round(sum(flops.values()) / 1e9, 2),
                 "hip_ms": summary(hip), "torch_ms": summary(tor), "hip_f32_ms": summary(ts["f32"]),
                 "hip_bf16x3_ms": summary(ts["bf16x3"]), "speedup_median": round(statistics.median(tor) / statistics.median(hip), 3),
                 "hip_not_slower": statistics.median(hip) <= statistics.median(tor) * (1 + summary(hip)["spread"]),
                 "tflops_block": round(sum(flops.values()) / (min(hip) * 1e-3) / 1e12, 1), "launches": launches}
+            if swept:
+                res["stages"][name]["tiles"] = swept
         for style in ("ST", "TS"):
             torch.manual_seed(1)
             model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=22, style=style,
@@ -139,6 +181,8 @@ def main():
             def run_model(torch_path):
                 for b in blocks:
                     b.force_torch = torch_path
+                    if not torch_path and not sweep:
+                        set_head_math(b, flags | tile)
                 return model(clips)
             ts = alternate({"torch": partial(run_model, True), "hip": partial(run_model, False)}, args.repeats, args.warmup)
             stem = alternate({"stem": lambda: model.tcn0(model.gcn0(clips.permute(0, 3, 1, 2)))}, args.repeats, args.warmup)["stem"]
@@ -146,6 +190,42 @@ def main():
                                     "speedup_median": round(statistics.median(ts["torch"]) / statistics.median(ts["hip"]), 3),
                                     "clips_per_s_hip": round(args.batch / (statistics.median(ts["hip"]) * 1e-3), 1),
                                     "clips_per_s_torch": round(args.batch / (statistics.median(ts["torch"]) * 1e-3), 1)}
+            if sweep:
+                # the module's own policies (force_torch off): default thresholds, set_low_latency eager, and that forward as a graph
+                # low latency with min_tokens=0: the rows that LOW_LATENCY_MIN_TOKENS is read from must not depend on it
+                def run_policy(low):
+                    for b in blocks:
+                        b.force_torch = False
+                    stgcn_amd.set_low_latency(model, low, min_tokens=0 if low else None)
+                    return model(clips)
+
+                def blocks_on_hip(low):
+                    calls = []
+                    hooks = [b.register_forward_pre_hook(lambda mod, a: calls.append(bool(mod.uses_hip(a[0])))) for b in blocks]
+                    run_policy(low)
+                    for hk in hooks:
+                        hk.remove()
+                    return sum(calls), len(calls)
+                on_default, on_low = blocks_on_hip(False), blocks_on_hip(True)
+                assert on_low[0] == on_low[1], f"low latency left blocks on the torch path: {on_low}"
+                torch.cuda.synchronize()
+                static_in = clips.clone()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    static_out = model(static_in)
+                graph.replay()
+                torch.cuda.synchronize()
+                same = torch.equal(static_out, run_policy(True))
+                tl = alternate({"default": partial(run_policy, False), "low_latency": partial(run_policy, True), "captured": graph.replay},
+                               args.repeats, args.warmup)
+                stgcn_amd.set_low_latency(model, False)
+                med = {k: statistics.median(t) for k, t in tl.items()}
+                res["models"][style]["low_latency"] = {
+                    "default_policy_ms": summary(tl["default"]), "low_latency_eager_ms": summary(tl["low_latency"]),
+                    "low_latency_captured_ms": summary(tl["captured"]), "replay_equals_eager": same,
+                    "blocks_on_hip_default": on_default[0], "blocks_on_hip_low_latency": on_low[0], "blocks": on_low[1],
+                    "eager_vs_default": round(med["default"] / med["low_latency"], 3),
+                    "captured_vs_default": round(med["default"] / med["captured"], 3)}
     line = json.dumps(res)
     if args.out:
         with open(args.out, "w") as f:
