@@ -297,11 +297,13 @@ int stgcn_agcn_forward_train(const float *x, const float *A_eff, const float *Wa
         return fail(STGCN_ERR_ARG, "agcn_forward_train: down branch given without its bias / BatchNorm tensors");
     if (!has_down && Cin != Cout)
         return fail(STGCN_ERR_ARG, "agcn_forward_train: identity residual needs Cin == Cout (got %d, %d)", Cin, Cout);
-    int rc = stgcn_agcn_attention(x, A_eff, Wa, ba, Wb, bb, P_ws, N, Cin, T, V, inter_c, subsets, stream);
-    if (rc != STGCN_OK) return rc;
+    REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(subsets);
     const bool frozen = (flags & STGCN_BN_FROZEN) != 0;     // running statistics: the branches are materialised
     const AgcnTrainPlan pl = plan_agcn_train(N, Cin, Cout, T, V, subsets, frozen || !has_down || save_zm || save_zd, has_down, frozen);
+    // (before the attention launch: a refused call writes nothing, P included)
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "agcn_forward_train: workspace %zu B too small", ws_bytes);
+    int rc = stgcn_agcn_attention(x, A_eff, Wa, ba, Wb, bb, P_ws, N, Cin, T, V, inter_c, subsets, stream);
+    if (rc != STGCN_OK) return rc;
     return launch_agcn_forward_train(pl, x, P_ws, Wd, bd, Wdown, bdown, bn_weight, bn_bias, bn_running_mean, bn_running_var,
                                      dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, momentum, eps, ws, y, save_zm,
                                      save_zd, save_stats, N, Cin, Cout, T, V, subsets, (hipStream_t)stream);

@@ -1,4 +1,5 @@
-"""Shared helpers for the tests: golden loading and the parity gate."""
+"""Shared helpers for the tests: golden loading, the parity gate and the hostile allocator."""
+import math
 import os
 
 import numpy as np
@@ -42,3 +43,109 @@ def parity_gate(out, ref, rel=1e-4, what="", strict=True):
 
 def gather_flat(t, idx):
     return torch.as_tensor(t).reshape(-1)[torch.as_tensor(idx)]
+
+
+class hostile_allocations:
+    """While active, ``torch.empty`` / ``torch.empty_like`` (the module attributes: every allocation of
+    stgcn_amd.functional) hand out poisoned, guard-banded memory on the listed device types.
+
+    A request of ``nbytes`` becomes ``guard + nbytes + guard`` bytes of uint8 filled with the byte ``fill``; the caller gets the
+    middle as a view of the dtype and shape it asked for, the upper guard starting at the first byte behind it.  ``check()``
+    (also run on a clean exit) asserts that every guard byte of every allocation made so far still holds ``fill``.
+
+    ``fill`` is a condition, not a measurement: 0xFF reads as NaN in fp32, fp64 and bf16 (a result that depends on what a
+    buffer held before turns non-finite), 0x7F as a huge finite positive number (3.4e38 / 1.4e306 / 3.4e38) that wins a
+    ``max`` or a compare-and-select, where the hardware drops a NaN.  Method forms (``x.new_empty``) are left alone; the
+    patch is process-wide, so nothing else may allocate from another thread meanwhile."""
+
+    ALIGN = 256
+
+    def __init__(self, fill, guard=1 << 20, devices=("cuda",)):
+        assert 0 <= fill <= 0xFF and guard > 0 and guard % 512 == 0, "guard: a positive multiple of 512 (keeps the 256-byte alignment)"
+        self.fill, self.guard, self.devices = fill, guard, tuple(devices)
+        self.records = []                 # (backing uint8 tensor, nbytes, shape, dtype) in order of creation
+        self._real = None
+
+    # -- the two replacements -------------------------------------------------------------------------------------------------
+    def _guarded(self, shape, dtype, device, strides=None):
+        real_empty = self._real[0]
+        dtype = dtype or torch.get_default_dtype()
+        shape = tuple(int(s) for s in shape)
+        item = real_empty((), dtype=dtype).element_size()
+        nbytes = math.prod(shape) * item
+        raw = real_empty(self.guard + nbytes + self.guard, dtype=torch.uint8, device=device)
+        if (raw.data_ptr() + self.guard) % self.ALIGN and raw.device.type == "cpu":
+            # the host allocator aligns to 64 bytes only: take the aligned window of a slightly larger block
+            raw = real_empty(raw.numel() + self.ALIGN, dtype=torch.uint8, device=device)
+            off = -(raw.data_ptr() + self.guard) % self.ALIGN
+            raw = raw[off:off + self.guard + nbytes + self.guard]
+        raw.fill_(self.fill)
+        mid = raw[self.guard:self.guard + nbytes].view(dtype)
+        out = mid.view(shape) if strides is None else mid.as_strided(shape, strides)
+        assert out.data_ptr() % self.ALIGN == 0, f"guarded allocation {len(self.records)} is not {self.ALIGN}-byte aligned"
+        assert out.data_ptr() == raw.data_ptr() + self.guard or nbytes == 0       # (torch reports no address for zero elements)
+        self.records.append((raw, nbytes, shape, dtype))
+        return out
+
+    @staticmethod
+    def _dense(t):
+        expect = 1
+        for size, stride in sorted(zip(t.shape, t.stride()), key=lambda p: p[1]):
+            if size != 1 and stride != expect:
+                return False
+            expect *= size
+        return t.numel() > 0
+
+    def _wants(self, device):
+        return torch.device(device if device is not None else "cpu").type in self.devices
+
+    def _empty(self, *size, dtype=None, device=None, **kw):
+        if not self._wants(device) or kw.get("out") is not None or kw.get("layout", torch.strided) is not torch.strided \
+                or kw.get("memory_format", torch.contiguous_format) is not torch.contiguous_format:
+            return self._real[0](*size, dtype=dtype, device=device, **kw)
+        if "size" in kw:
+            size = (kw.pop("size"),)
+        if len(size) == 1 and not isinstance(size[0], int):
+            size = tuple(size[0])                      # a tuple, a list or a torch.Size (also a sum of them)
+        out = self._guarded(size, dtype, device)
+        return out.requires_grad_() if kw.get("requires_grad") else out
+
+    def _empty_like(self, t, *, dtype=None, device=None, **kw):
+        device = t.device if device is None else device
+        fmt = kw.get("memory_format", torch.preserve_format)
+        if not self._wants(device) or kw.get("layout", torch.strided) is not torch.strided \
+                or fmt not in (torch.preserve_format, torch.contiguous_format):
+            return self._real[1](t, dtype=dtype, device=device, **kw)
+        # preserve_format: a dense, non-overlapping tensor keeps its strides (torch's own rule), anything else is contiguous
+        strides = t.stride() if fmt is torch.preserve_format and not t.is_contiguous() and self._dense(t) else None
+        out = self._guarded(t.shape, dtype or t.dtype, device, strides)
+        return out.requires_grad_() if kw.get("requires_grad") else out
+
+    # -- the checks --------------------------------------------------------------------------------------------------------------
+    def check(self):
+        """Every guard byte of every allocation made so far still holds the fill."""
+        for i, (raw, nbytes, shape, dtype) in enumerate(self.records):
+            for lo, hi, side in ((0, self.guard, "before"), (self.guard + nbytes, raw.numel(), "after")):
+                bad = raw[lo:hi] != self.fill
+                if bool(bad.any()):
+                    at = lo + int(bad.to(torch.uint8).argmax())
+                    where = f"at start-{self.guard - at}" if side == "before" else f"at end+{at - self.guard - nbytes}"
+                    raise AssertionError(f"guard overwritten: allocation #{i} (shape {shape}, {dtype}, {nbytes} bytes), first changed "
+                                         f"byte {where} of the buffer (value 0x{int(raw[at]):02X}, fill 0x{self.fill:02X})")
+
+    def holds_only_fill(self, t):
+        """True if every byte of ``t`` (a tensor handed out here, still dense) is the fill: nothing was written to it."""
+        return bool((t.contiguous().reshape(-1).view(torch.uint8) == self.fill).all())
+
+    def __enter__(self):
+        assert self._real is None, "hostile_allocations is not re-entrant"
+        self._real = (torch.empty, torch.empty_like)
+        torch.empty, torch.empty_like = self._empty, self._empty_like
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        torch.empty, torch.empty_like = self._real
+        self._real = None
+        if exc_type is None:
+            self.check()
+        return False
