@@ -368,14 +368,30 @@ int stgcn_vit_linear(const float *x, const float *W, const float *bias, const fl
                      float ln_eps, const float *residual, float *y, int M, int K, int Nout, unsigned flags,
                      void *stream);
 /* out (B, L, heads*head_dim) = concatenated heads of softmax(scale * q k^T) v, qkv (B, L, 3, heads, head_dim).
- * Covered: head_dim in {32, 64}, 1 <= L <= 256, any B and heads (else STGCN_ERR_UNSUPPORTED).  One launch. */
+ * The resident form: K and V of a (sequence, head) pair stay in LDS, a query's score row in registers.
+ * Covered: head_dim in {32, 64}, 1 <= L <= 256, any B and heads (else STGCN_ERR_UNSUPPORTED).  One launch.
+ * stgcn_vit_attention_supported describes this form (and the length the training entry points cover), not the streaming one. */
 int stgcn_vit_attention_supported(int L, int heads, int head_dim);
 int stgcn_vit_attention(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream);
-/* One block.  Covered: head_dim = D / heads in {32, 64}, L <= 256, D and hidden multiples of 64, D <= 4096, any B (else
- * STGCN_ERR_UNSUPPORTED).  bqkv may be NULL (qkv_bias=False); bproj, b1, b2 may be NULL too.  eps: both LayerNorms.
+/* The streaming form (additive to ABI 11): the same layouts and fp32-exact products, K and V streamed through LDS in tiles of
+ * 64 keys under a running soft-max, 128 queries of a pair per workgroup.  Covered: head_dim in {32, 64},
+ * 1 <= L <= STGCN_VIT_MAX_STREAM_L, any B and heads; it runs the streaming kernel at every covered length, the short ones
+ * included.  Agrees with the resident form within rounding (another summation order), bit-identical from run to run.
+ * One launch on the caller's stream, no workspace, no allocation, no synchronisation. */
+#define STGCN_VIT_MAX_STREAM_L 4096
+int stgcn_vit_attention_stream_supported(int L, int heads, int head_dim);
+int stgcn_vit_attention_stream(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale,
+                               void *stream);
+/* One block.  Covered: head_dim = D / heads in {32, 64}, L <= STGCN_VIT_MAX_STREAM_L (a slab of 32768 tokens holds whole
+ * sequences), D and hidden multiples of 64, D <= 4096, any B (else STGCN_ERR_UNSUPPORTED): stgcn_vit_block_forward_supported
+ * tells.  The attention launch is the resident form for L <= 256 and the streaming form above.
+ * stgcn_vit_block_supported describes the resident form only (L <= 256): it is the coverage of the training entry points
+ * below and answers 0 for longer sequences that stgcn_vit_block_forward runs.
+ * bqkv may be NULL (qkv_bias=False); bproj, b1, b2 may be NULL too.  eps: both LayerNorms.
  * ws: stgcn_vit_block_ws_bytes(B, L, D, hidden) bytes (bounded: the input is walked in slabs of whole sequences).
  * y must not alias x.  Five launches per slab, no atomics: results are bit-identical from run to run. */
 int stgcn_vit_block_supported(int L, int D, int heads, int hidden);
+int stgcn_vit_block_forward_supported(int L, int D, int heads, int hidden);
 size_t stgcn_vit_block_ws_bytes(int B, int L, int D, int hidden);
 int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
                             const float *bqkv, const float *Wproj, const float *bproj, const float *norm2_weight,
@@ -402,7 +418,7 @@ size_t stgcn_vit_linear_backward_ws_bytes(int M, int K, int Nout);
 int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, const float *h_pre, float *dx, float *dW,
                               float *db, void *ws, size_t ws_bytes, int M, int K, int Nout, unsigned flags, void *stream);
 /* dqkv (B,L,3,heads,head_dim) from the packed qkv, the forward's output `out` and its gradient dout (both (B,L,heads*head_dim));
- * S and P are recomputed on chip.  Same coverage as the forward.  One launch, no workspace. */
+ * S and P are recomputed on chip.  Same coverage as the resident forward (L <= 256).  One launch, no workspace. */
 int stgcn_vit_attention_backward_supported(int L, int heads, int head_dim);
 int stgcn_vit_attention_backward(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int heads,
                                  int head_dim, float scale, void *stream);
@@ -411,7 +427,7 @@ int stgcn_vit_attention_backward(const float *qkv, const float *out, const float
 size_t stgcn_vit_layernorm_backward_ws_bytes(int M, int D);
 int stgcn_vit_layernorm_backward(const float *x, const float *dn, const float *weight, float eps, const float *dres, float *dx,
                                  float *dweight, float *dbias, void *ws, size_t ws_bytes, int M, int D, void *stream);
-/* One block, training.  Coverage = stgcn_vit_block_supported.  The size queries return 0 for shapes outside it. */
+/* One block, training.  Coverage = stgcn_vit_block_supported (the resident form: L <= 256).  The size queries return 0 for shapes outside it. */
 int stgcn_vit_block_train_supported(int L, int D, int heads, int hidden);
 size_t stgcn_vit_block_saved_bytes(int B, int L, int D, int hidden);
 size_t stgcn_vit_block_backward_ws_bytes(int B, int L, int D, int hidden);

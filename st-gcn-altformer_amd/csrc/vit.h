@@ -8,7 +8,10 @@
 namespace stgcn {
 namespace vit {
 
-constexpr int kMaxL = 256;      // longest sequence the attention kernel keeps on chip
+constexpr int kMaxL = 256;      // longest sequence the resident attention kernel keeps on chip (and the training kernels' limit)
+constexpr int kMaxStreamL = STGCN_VIT_MAX_STREAM_L;   // longest sequence of the streaming attention kernel: a slab holds 8 of them
+constexpr int kStreamKeys = 64;       // keys per LDS stage of the streaming kernel (vit_attention_stream.hip)
+constexpr int kStreamQueries = 128;   // queries per workgroup there: four waves of 32
 
 // ---- what the entry points cover (vit_block.hip, vit_block_train.hip) ----
 // Long inputs are walked in slabs of whole sequences of about this many tokens (forward and backward alike).
@@ -53,10 +56,26 @@ inline LinearTile linear_tile(int M, int K, int Nout, unsigned flags) {
     }
 }
 
+// The resident form: what the training entry points and stgcn_vit_block_supported cover.
 inline bool block_ok(int L, int D, int heads, int hidden) {
     if (L < 1 || D < 1 || heads < 1 || hidden < 1 || D % heads != 0) return false;
     const int hd = D / heads;
     return (hd == 32 || hd == 64) && L <= kMaxL && D % 64 == 0 && hidden % 64 == 0 && D <= kMaxLnDim;
+}
+
+inline bool attention_stream_ok(int L, int heads, int hd) {
+    return L >= 1 && L <= kMaxStreamL && heads >= 1 && (hd == 32 || hd == 64);
+}
+
+// ---- the inference block's attention launch, chosen here and nowhere else (stgcn_vit_block_forward and
+// stgcn_vit_block_forward_supported read it) ----
+// resident up to kMaxL, exactly as before the streaming kernel existed (bit-identical results); streaming above, up to
+// kMaxStreamL: kSlabRows / kMaxStreamL = 8 whole sequences still fit a slab.  Everything else about the block is length-agnostic.
+enum class BlockAttention { none, resident, stream };
+inline BlockAttention plan_block_forward(int L, int D, int heads, int hidden) {
+    if (block_ok(L, D, heads, hidden)) return BlockAttention::resident;
+    if (L > kMaxL && L <= kMaxStreamL && block_ok(kMaxL, D, heads, hidden)) return BlockAttention::stream;
+    return BlockAttention::none;
 }
 
 inline int slab_seqs(int B, int L) {
@@ -88,8 +107,11 @@ int launch_linear_ex(const float *X, const float *W, const float *bias, const fl
                      hipStream_t st);
 
 // out (B, L, H*hd) = softmax(scale * q k^T) v per (sequence, head) of the packed qkv (B, L, 3, H, hd); hd in {32, 64},
-// L <= kMaxL.
+// L <= kMaxL: K and V of a pair resident in LDS, the whole score row in registers (vit_attention.hip).
 int launch_attention_packed(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
+// The same result up to the summation order for L <= kMaxStreamL: K and V streamed through LDS in tiles of kStreamKeys keys
+// under a running soft-max, kStreamQueries queries of a pair per workgroup (vit_attention_stream.hip).
+int launch_attention_stream(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
 
 // ---- backward (vit_backward.hip) ----------------------------------------------------------------------------------------
 // Wt (cols, rows_pad) = W (rows, cols)^T, the columns from `rows` to rows_pad zero-filled: the dgrad dX = dY W is the

@@ -1,5 +1,6 @@
 // C entry points of the AltFormer heads' transformer block (include/stgcn_hip.h, "ViT block", ABI 10): the linear and the
-// attention on their own, and the eval forward of one Block = five launches on one stream from a caller workspace:
+// attention (resident and streaming form) on their own, and the eval forward of one Block = five launches on one stream from
+// a caller workspace:
 //   qkv = LN1(x) Wqkv^T + b -> attention -> x1 = a Wproj^T + b + x -> h = GELU(LN2(x1) W1^T + b1) -> y = h W2^T + b2 + x1
 // (both LayerNorms inside the linear that consumes them).  A STGCN_VIT_TILE_* field in `flags` goes to the four linears.
 // Long inputs are walked in slabs of whole sequences (kSlabRows tokens): the four intermediates of a slab (about 7 KB per
@@ -71,7 +72,24 @@ int stgcn_vit_attention(const float *qkv, float *out, int B, int L, int heads, i
     return launch_attention_packed(qkv, out, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
 }
 
+int stgcn_vit_attention_stream_supported(int L, int heads, int head_dim) {
+    return attention_stream_ok(L, heads, head_dim) ? 1 : 0;
+}
+
+int stgcn_vit_attention_stream(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream) {
+    REQUIRE_PTR(qkv); REQUIRE_PTR(out);
+    REQUIRE_POS(B); REQUIRE_POS(L); REQUIRE_POS(heads);
+    if (!attention_stream_ok(L, heads, head_dim))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention_stream: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)",
+                    L, head_dim, kMaxStreamL);
+    return launch_attention_stream(qkv, out, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
+}
+
 int stgcn_vit_block_supported(int L, int D, int heads, int hidden) { return block_ok(L, D, heads, hidden) ? 1 : 0; }
+
+int stgcn_vit_block_forward_supported(int L, int D, int heads, int hidden) {
+    return plan_block_forward(L, D, heads, hidden) != BlockAttention::none ? 1 : 0;
+}
 
 size_t stgcn_vit_block_ws_bytes(int B, int L, int D, int hidden) {
     if (B < 1 || L < 1 || D < 1 || hidden < 1) return 0;
@@ -87,10 +105,12 @@ int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const flo
         return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: null pointer");
     if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: B = %d", B);
     if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: y must not alias x");
-    if (!block_ok(L, D, heads, hidden) || !math_ok(flags))
+    const BlockAttention attention = plan_block_forward(L, D, heads, hidden);
+    if (attention == BlockAttention::none || !math_ok(flags))
         return fail(STGCN_ERR_UNSUPPORTED,
                     "stgcn_vit_block_forward: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
-                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxL);
+                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK,
+                    kMaxStreamL);
     const BlockWs w(ws, B, L, D, hidden);
     if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward: workspace %zu < %zu bytes", ws_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -107,7 +127,9 @@ int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const flo
         int rc;
         if ((rc = launch_linear(xs, Wqkv, bqkv, nullptr, norm1_weight, norm1_bias, eps, qkv, M, D, 3 * D, false, math_qkv, st)))
             return rc;
-        if ((rc = launch_attention_packed(qkv, att, nb, L, heads, D / heads, scale, st))) return rc;
+        if ((rc = attention == BlockAttention::stream ? launch_attention_stream(qkv, att, nb, L, heads, D / heads, scale, st)
+                                                      : launch_attention_packed(qkv, att, nb, L, heads, D / heads, scale, st)))
+            return rc;
         if ((rc = launch_linear(att, Wproj, bproj, xs, nullptr, nullptr, 0.f, x1, M, D, D, false, math, st))) return rc;
         if ((rc = launch_linear(x1, W1, b1, nullptr, norm2_weight, norm2_bias, eps, hid, M, D, hidden, true, math, st)))
             return rc;

@@ -86,7 +86,10 @@ PROTOTYPES = {
     "stgcn_vit_linear": (c_int, [_P] * 5 + [c_float] + [_P] * 2 + [c_int] * 3 + [c_uint, _P]),
     "stgcn_vit_attention_supported": (c_int, [c_int] * 3),
     "stgcn_vit_attention": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
+    "stgcn_vit_attention_stream_supported": (c_int, [c_int] * 3),
+    "stgcn_vit_attention_stream": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
     "stgcn_vit_block_supported": (c_int, [c_int] * 4),
+    "stgcn_vit_block_forward_supported": (c_int, [c_int] * 4),
     "stgcn_vit_block_ws_bytes": (c_size_t, [c_int] * 4),
     "stgcn_vit_block_forward": (c_int, [_P] * 13 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
     "stgcn_vit_linear_backward_supported": (c_int, [c_int] * 3 + [c_uint]),

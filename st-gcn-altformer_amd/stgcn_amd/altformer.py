@@ -8,15 +8,16 @@ constructor arguments, attribute names, ``state_dict`` keys, shapes and order, a
 
 Two paths, one result:
 
-* HIP (``stgcn_vit_block_forward``): CUDA float32 input of a covered shape while autograd records nothing that concerns the
-  block (``torch.no_grad()``, or no input and no parameter requires a gradient), no dropout / stochastic depth is active, and
-  the call has at least ``HIP_MIN_TOKENS`` tokens (smaller calls are latency-bound; ``set_hip_min_tokens(model, 0)`` lifts it).
+* HIP (``stgcn_vit_block_forward``): CUDA float32 input of a covered shape (sequences of up to 4096 tokens: the attention
+  kernel keeps K and V on chip up to 256 and streams them in key tiles under a running soft-max above) while autograd records
+  nothing that concerns the block (``torch.no_grad()``, or no input and no parameter requires a gradient), no dropout /
+  stochastic depth is active, and the call has at least ``HIP_MIN_TOKENS`` tokens (smaller calls are latency-bound; ``set_hip_min_tokens(model, 0)`` lifts it).
   The head's first patch embedding then runs through ``functional.patch_embed`` on the stem output (contiguous or
   channels-last, consumed in place); pooling, the second embedding and ``mlp_head`` are torch ops.
 * HIP, training (``stgcn_vit_block_forward_train`` / ``stgcn_vit_block_backward`` behind one ``autograd.Function``): the same
   input conditions while autograd IS recording something that concerns the block (``.train()``, or ``.eval()`` with gradients),
-  no ``nn.Dropout`` active, at least ``HIP_TRAIN_MIN_TOKENS`` tokens (``set_hip_train_min_tokens``; ``set_hip_min_tokens`` sets
-  both thresholds), env ``STGCN_VIT_TRAIN`` not ``0``.  Stochastic depth is covered: ``Block.draw_drop_path`` draws the two masks
+  sequences of up to 256 tokens (longer ones train on torch ops), no ``nn.Dropout`` active, at least ``HIP_TRAIN_MIN_TOKENS``
+  tokens (``set_hip_train_min_tokens``; ``set_hip_min_tokens`` sets both thresholds), env ``STGCN_VIT_TRAIN`` not ``0``.  Stochastic depth is covered: ``Block.draw_drop_path`` draws the two masks
   with the torch path's calls in its order (same seed, same masks) and the kernels apply them per sequence.  The parameters
   are taken by attribute, so an ``nn.DataParallel`` replica's gradients reach its master.  ``Block.trains_on_hip(x)`` tells.
   Default arithmetic ``'f32'`` (``DEFAULT_TRAIN_MATH``, env ``STGCN_VIT_TRAIN_MATH``; ``set_head_math`` overrides both paths).
@@ -235,8 +236,9 @@ class Block(nn.Module):
             yield lin.weight
             yield lin.bias
 
-    def _kernels_cover(self, x: torch.Tensor) -> bool:
-        """CUDA float32 (B, L, D) input and a module the kernels implement (LayerNorms with affine, exact GELU, covered sizes)."""
+    def _kernels_cover(self, x: torch.Tensor, train: bool) -> bool:
+        """CUDA float32 (B, L, D) input and a module the kernels implement (LayerNorms with affine, exact GELU, covered sizes).
+        The sizes differ: inference reaches 4096 tokens per sequence (the streaming attention kernel above 256), training 256."""
         if self.force_torch or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
             return False
         if not (type(self.norm1) is nn.LayerNorm and type(self.norm2) is nn.LayerNorm and isinstance(self.mlp.act, nn.GELU)
@@ -247,7 +249,8 @@ class Block(nn.Module):
         B, L, D = x.shape
         if B < 1 or D != self.norm1.normalized_shape[0] or self.mlp.fc2.out_features != D:
             return False
-        return F.vit_block_supported(L, D, self.attn.num_heads, self.mlp.fc1.out_features)
+        covered = F.vit_block_train_supported if train else F.vit_block_forward_supported
+        return covered(L, D, self.attn.num_heads, self.mlp.fc1.out_features)
 
     def _records_grad(self, x: torch.Tensor) -> bool:
         return torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in self._weights()))
@@ -256,7 +259,7 @@ class Block(nn.Module):
         """Whether this call can run on the inference kernels (see the module docstring)."""
         if x.dim() != 3 or self._records_grad(x) or _drop_active(self):
             return False
-        return self._kernels_cover(x)
+        return self._kernels_cover(x, train=False)
 
     def trains_on_hip(self, x: torch.Tensor) -> bool:
         """Whether this call runs on the HIP training kernels (forward that saves for the backward, backward on
@@ -270,7 +273,7 @@ class Block(nn.Module):
             return False
         if not isinstance(self.drop_path, (DropPath, nn.Identity)):
             return False
-        return self._kernels_cover(x)
+        return self._kernels_cover(x, train=True)
 
     def draw_drop_path(self, x: torch.Tensor):
         """The stochastic-depth factors of this call, attention branch first, then the MLP branch - the order, shapes and

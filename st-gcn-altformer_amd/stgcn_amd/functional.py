@@ -565,12 +565,16 @@ def vit_linear(x, weight, bias=None, ln=None, residual=None, gelu=False, math=MA
 
 
 def vit_attention_supported(L, heads, head_dim) -> bool:
+    """The resident kernel's coverage (L <= 256), which is also the training entry points'."""
     return bool(_capi.lib().stgcn_vit_attention_supported(L, heads, head_dim))
 
 
-def vit_attention(qkv, heads, scale=None) -> torch.Tensor:
-    """Multi-head attention over the packed qkv (B, L, 3*D) = (B, L, 3, heads, D/heads) as the qkv nn.Linear writes it;
-    returns (B, L, D), heads concatenated.  ``scale`` defaults to head_dim ** -0.5."""
+def vit_attention_stream_supported(L, heads, head_dim) -> bool:
+    """The streaming kernel's coverage (L <= 4096)."""
+    return bool(_capi.lib().stgcn_vit_attention_stream_supported(L, heads, head_dim))
+
+
+def _vit_attention(entry, qkv, heads, scale):
     dev = qkv.device
     B, L, D3 = qkv.shape
     D = D3 // 3
@@ -579,13 +583,34 @@ def vit_attention(qkv, heads, scale=None) -> torch.Tensor:
         raise ValueError(f"qkv is {tuple(qkv.shape)}: the last axis must be 3 * heads * head_dim (heads = {heads})")
     out = torch.empty(B, L, D, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _capi.call("stgcn_vit_attention", _dev_ptr(qkv, "qkv", dev), _dev_ptr(out, "out"), c_int(B), c_int(L), c_int(heads),
+        _capi.call(entry, _dev_ptr(qkv, "qkv", dev), _dev_ptr(out, "out"), c_int(B), c_int(L), c_int(heads),
                    c_int(hd), c_float(hd ** -0.5 if scale is None else scale), _stream(dev))
     return out
 
 
+def vit_attention(qkv, heads, scale=None) -> torch.Tensor:
+    """Multi-head attention over the packed qkv (B, L, 3*D) = (B, L, 3, heads, D/heads) as the qkv nn.Linear writes it;
+    returns (B, L, D), heads concatenated.  ``scale`` defaults to head_dim ** -0.5.  Sequences of up to 256 tokens run the
+    resident kernel, longer ones (up to 4096) the streaming one."""
+    L, hd = qkv.shape[1], qkv.shape[2] // 3 // heads
+    stream = not vit_attention_supported(L, heads, hd) and vit_attention_stream_supported(L, heads, hd)
+    return _vit_attention("stgcn_vit_attention_stream" if stream else "stgcn_vit_attention", qkv, heads, scale)
+
+
+def vit_attention_stream(qkv, heads, scale=None) -> torch.Tensor:
+    """``vit_attention`` on the streaming kernel (K and V in key tiles through LDS, running soft-max) at every covered
+    length, the short ones included: the same result up to the summation order."""
+    return _vit_attention("stgcn_vit_attention_stream", qkv, heads, scale)
+
+
 def vit_block_supported(L, D, heads, hidden) -> bool:
+    """Coverage of the resident form (L <= 256): what the training entry points take."""
     return bool(_capi.lib().stgcn_vit_block_supported(L, D, heads, hidden))
+
+
+def vit_block_forward_supported(L, D, heads, hidden) -> bool:
+    """What ``vit_block_forward`` runs: the resident coverage plus 256 < L <= 4096 on the streaming attention kernel."""
+    return bool(_capi.lib().stgcn_vit_block_forward_supported(L, D, heads, hidden))
 
 
 def vit_block_forward(x, norm1, qkv, proj, norm2, fc1, fc2, heads, eps, scale, math=MATH_F32) -> torch.Tensor:

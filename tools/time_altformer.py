@@ -4,6 +4,7 @@ torch-op path of the same module, in one process, alternating, with device event
 
     python tools/time_altformer.py [--batch 32] [--repeats 7] [--warmup 2] [--tiles 128|auto|64|32|sweep]
                                    [--out profiles/altformer_times.json]
+    python tools/time_altformer.py --frames 500 [--batch 32] [--out profiles/altformer_long_times.json]
 
 Prints ONE JSON line.  Per stage (a Block at the stage's shape, batch ``--batch``): ms of the HIP path (default arithmetic,
 and 'f32' / 'bf16x3' for comparison) and of the torch path (min, median, max over the repeats; ``spread`` = (max - min) / min of
@@ -17,6 +18,12 @@ stage and launch in the same alternation (``tiles`` per stage: block ms per form
 linears, ms per launch per form, the attention's share of the ``auto`` block) and adds ``low_latency`` per model: the
 default policy (at one clip: every block on torch ops), ``set_low_latency`` eager, and the same forward captured in a graph
 and replayed.
+
+``--frames T`` (T > 256) times the long-clip stages instead, where the attention is the streaming kernel: the ST temporal stage
+(``batch`` sequences of T, D = 512) and the TS temporal stage for 22 and 46 joints (``batch`` x V sequences of T, D = 256),
+HIP against torch path with ``torch.cuda.max_memory_allocated`` of each; per launch the streaming kernel at L = T for head_dim
+32 and 64 next to the resident kernel at L = 256 in the same alternation (ms, TFLOP/s, their ratio); and the whole ST and TS
+models at ``num_frame = T``.
 """
 import argparse
 import json
@@ -72,15 +79,117 @@ def summary(ts):
             "spread": round((max(ts) - min(ts)) / min(ts), 4)}
 
 
+def peak_bytes(fn):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def faster_by_more_than_the_spread(fast, slow):
+    return statistics.median(fast) * (1 + max(summary(fast)["spread"], summary(slow)["spread"])) < statistics.median(slow)
+
+
+def long_clips(args):
+    """The ``--frames`` run (see the module docstring)."""
+    import stgcn_amd
+    from stgcn_amd import functional as F
+    from stgcn_amd.altformer import DEFAULT_HEAD_MATH, Block
+    from functools import partial
+    T, dev = args.frames, torch.device("cuda:0")
+    assert T > 256, "--frames is for sequences the resident attention kernel does not take"
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    res = {"frames": T, "batch": args.batch, "repeats": args.repeats, "default_math": DEFAULT_HEAD_MATH,
+           "device": torch.cuda.get_device_name(0), "stages": {}, "attention": {}, "models": {}}
+    stages = {f"ST temporal {T}": (1, 512), f"TS temporal (22 x {T})": (22, 256), f"TS temporal two-hand (46 x {T})": (46, 256)}
+    with torch.no_grad():
+        for name, (per_clip, D) in stages.items():
+            B, heads = args.batch * per_clip, 8
+            torch.manual_seed(0)
+            blk = Block(D, heads, mlp_ratio=2., qkv_bias=True, norm_layer=norm).to(dev).eval()
+            x = torch.randn(B, T, D, device=dev)
+            chooses = "hip" if blk.uses_hip(x) else "torch"
+            blk.hip_min_tokens = 0
+
+            def run(torch_path):
+                blk.force_torch = torch_path
+                return blk(x)
+            ts = alternate({"torch": partial(run, True), "hip": partial(run, False)}, args.repeats, args.warmup)
+            mem = {k: peak_bytes(partial(run, k == "torch")) for k in ("torch", "hip")}
+            blk.force_torch = False
+            M, hd = B * T, D // heads
+            flops = 2 * M * D * 3 * D + 4 * B * heads * T * T * hd + 2 * M * D * D + 2 * 2 * M * D * 2 * D
+            res["stages"][name] = {
+                "B": B, "L": T, "D": D, "tokens": M, "module_chooses": chooses, "gflop": round(flops / 1e9, 2),
+                "attention_gflop": round(4 * B * heads * T * T * hd / 1e9, 2),
+                "hip_ms": summary(ts["hip"]), "torch_ms": summary(ts["torch"]),
+                "speedup_median": round(statistics.median(ts["torch"]) / statistics.median(ts["hip"]), 3),
+                "hip_faster_by_more_than_the_spread": faster_by_more_than_the_spread(ts["hip"], ts["torch"]),
+                "peak_mib_hip": round(mem["hip"] / 2 ** 20, 1), "peak_mib_torch": round(mem["torch"] / 2 ** 20, 1)}
+            del x, blk
+            torch.cuda.empty_cache()
+        # per launch: the streaming kernel at L = T and the resident kernel at L = 256, the same number of (sequence, head) pairs
+        B, heads = args.batch * 22, 8
+        for hd in (32, 64):
+            qs, qr = (torch.randn(B, L, 3 * heads * hd, device=dev) for L in (T, 256))
+            lt = alternate({"stream": lambda: F.vit_attention_stream(qs, heads), "resident": lambda: F.vit_attention(qr, heads),
+                            "stream_at_256": lambda: F.vit_attention_stream(qr, heads)}, args.repeats, args.warmup)
+            tf = {k: 4 * B * heads * L * L * hd / (statistics.median(lt[k]) * 1e-3) / 1e12
+                  for k, L in (("stream", T), ("resident", 256), ("stream_at_256", 256))}
+            res["attention"][f"head_dim {hd}"] = {
+                "B": B, "heads": heads, "stream_L": T, "resident_L": 256, "ms": {k: summary(t) for k, t in lt.items()},
+                "tflops": {k: round(v, 1) for k, v in tf.items()}, "share_of_peak": {k: round(v / PEAK_F32, 3) for k, v in tf.items()},
+                "stream_over_resident_tflops": round(tf["stream"] / tf["resident"], 3),
+                "stream_over_resident_tflops_at_256": round(tf["stream_at_256"] / tf["resident"], 3)}
+            del qs, qr
+        for style in ("ST", "TS"):
+            torch.manual_seed(1)
+            model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=T, num_joints=22, style=style,
+                                               graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).eval()
+            clips = torch.randn(args.batch, T, 22, 3, device=dev)
+            blocks = [b for b in model.modules() if isinstance(b, Block)]
+
+            def run_model(torch_path):
+                for b in blocks:
+                    b.force_torch = torch_path
+                return model(clips)
+            calls = []
+            hooks = [b.register_forward_pre_hook(lambda mod, a: calls.append(bool(mod.uses_hip(a[0])))) for b in blocks]
+            run_model(False)
+            for hk in hooks:
+                hk.remove()
+            ts = alternate({"torch": partial(run_model, True), "hip": partial(run_model, False)}, args.repeats, args.warmup)
+            mem = {k: peak_bytes(partial(run_model, k == "torch")) for k in ("torch", "hip")}
+            res["models"][style] = {"hip_ms": summary(ts["hip"]), "torch_ms": summary(ts["torch"]),
+                                    "blocks_on_hip_default_policy": sum(calls), "blocks": len(calls),
+                                    "speedup_median": round(statistics.median(ts["torch"]) / statistics.median(ts["hip"]), 3),
+                                    "clips_per_s_hip": round(args.batch / (statistics.median(ts["hip"]) * 1e-3), 1),
+                                    "clips_per_s_torch": round(args.batch / (statistics.median(ts["torch"]) * 1e-3), 1),
+                                    "peak_mib_hip": round(mem["hip"] / 2 ** 20, 1), "peak_mib_torch": round(mem["torch"] / 2 ** 20, 1)}
+            del model, clips
+            torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tiles", choices=["128", "auto", "64", "32", "sweep"], default="128")
+    ap.add_argument("--frames", type=int, default=None, help="time the long-clip stages at this many frames (> 256) instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
+    if args.frames is not None:
+        line = json.dumps(long_clips(args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     import stgcn_amd
     from stgcn_amd import functional as F
     from stgcn_amd.altformer import DEFAULT_HEAD_MATH, HEAD_MATH, Block, set_head_math
