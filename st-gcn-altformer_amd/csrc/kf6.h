@@ -100,6 +100,8 @@ __device__ __forceinline__ float relu1(float x) {
 // The loop is written per PERIOD of 9 pairs = 2 chunks (static taps, static buffers), periods in a dynamic loop:
 //   pairs 0-2 produce chunk 2p+1 into buf1, pair 4 straddles, pairs 5-7 produce chunk 2p+2 into buf0 — one pair before
 //   the chunk's first reader, so that the reader's activation fragments can be prefetched across the barrier.
+//   A wave produces 3 + 3 + 2 sixteen-pixel blocks per window from the image's first row or, where the host plan has shown
+//   that no tile's taps read more than 28 blocks (v6_blocks_read), 3 + 2 + 2 from the block of the tile's first pixel (NPBW).
 // Weights: repacked per pair ([16-channel block][pair][hi|lo][lane] x 16 B, stgcn_stem_prepare), ring of 3 pair slots
 // (16 KiB each) filled by LDS-DMA two pairs ahead — issued early in a pair, waited for (vmcnt(0)) at its end, so that at a
 // pair's start BOTH the current and the next pair are resident and published: the next pair's first fragments are read
@@ -136,7 +138,11 @@ __device__ __forceinline__ void st_out4(float *p, const float4 &v) {
 }
 
 // WIDE: V0 = joints of the first half, tpc1 = tiles of a clip's second half (tiles_per_clip counts both halves)
-template <int TERMS, bool BF16OUT, bool WIDE>
+// NPBW: producer blocks per wave and chunk.  8 (3 + 3 + 2 per window) covers every image the plan admits, counted from the
+// image's first row; 7 (3 + 2 + 2) counts from the first block a tap of the tile reads (pb0) and is chosen by the host plan
+// for the shapes in which no tile's taps read more than 28 blocks from there on (v6_blocks_read): what the frame-aligned image
+// holds behind them is then not produced either.
+template <int TERMS, bool BF16OUT, bool WIDE, int NPBW = 8>
 __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
     const uint4 *__restrict__ pfrag, const float *__restrict__ x, int xsc, int xsp, const float *__restrict__ W12,
     const uint4 *__restrict__ Wp, const float *__restrict__ shift, void *y, int C, int T, int V, int ROWS,
@@ -448,14 +454,40 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
         const int Vh = ti.Vh;
         const int nblk = (g.span + 15) >> 4;
         const int next_tile = tile + gridDim.x;
+        // NPBW == 7: the wave's first producer block.  The image starts at the tile's first FRAME, the tile's first pixel sits
+        // s = q0 - t_first * Vh rows into it (0 <= s < Vh) and no tap reads a row in front of it: blocks below s >> 4 are not
+        // produced (their rows keep the previous tile's data), nor are blocks behind pb0 + 27, which the host plan has shown to
+        // lie behind the last row read.  The wave's k-th block is pbw + 4k, clamped to the image's last one.
+        const int pbw = NPBW == 8 ? wave : ((g.q0 - g.t_first * Vh) >> 4) + wave;
 
         V6_STAMP(t_0)
         // chunk 0 of this tile
-        for (int b = wave; b < nblk; b += 4) {
-            Prod pr;
-            prod_load(pr, 0, b);
-            prod_mfma(pr);
-            prod_finish(buf0, pr);
+        if constexpr (NPBW == 8) {
+            for (int b = wave; b < nblk; b += 4) {
+                Prod pr;
+                prod_load(pr, 0, b);
+                prod_mfma(pr);
+                prod_finish(buf0, pr);
+            }
+        } else {
+#ifdef V6_CHUNK0_SERIAL   // (A/B variant: one block after the other, as the 8-block form)
+            for (int b = pbw; b < nblk; b += 4) {
+                Prod pr;
+                prod_load(pr, 0, b);
+                prod_mfma(pr);
+                prod_finish(buf0, pr);
+            }
+#else
+            // the wave's blocks as loads, then MFMAs, then finishes: one LDS round trip and one MFMA latency per tile instead of
+            // one per block (a clamped slot produces the last block again: same rows, same values)
+            Prod pr[NPBW];
+#pragma unroll
+            for (int k = 0; k < NPBW; ++k) prod_load(pr[k], 0, min(pbw + 4 * k, nblk - 1));
+#pragma unroll
+            for (int k = 0; k < NPBW; ++k) prod_mfma(pr[k]);
+#pragma unroll
+            for (int k = 0; k < NPBW; ++k) prod_finish(buf0, pr[k]);
+#endif
         }
         // LDS offsets of this lane's activation rows per tap, for the wave's FIRST 16-pixel block: block nb sits exactly
         // nb * 16 * PXB bytes further (16 more pixels leave the swizzle bit (row >> 3) & 1 alone), which rides in the
@@ -503,10 +535,12 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
             static_for<0, 9>([&](auto pi_c) {
                 constexpr int pi = decltype(pi_c)::value;
                 constexpr int l0 = 2 * pi;
-                // production: pairs 0-2 -> chunk 2per+1 into buf1; pairs 5-7 -> chunk 2per+2 into buf0 (3, 3, 2 blocks)
+                // production: pairs 0-2 -> chunk 2per+1 into buf1; pairs 5-7 -> chunk 2per+2 into buf0 (3, 3, 2 blocks per
+                // wave; NPBW == 7: 3, 2, 2)
                 constexpr int win = pi <= 2 ? 0 : (pi >= 5 && pi <= 7 ? 1 : -1);
                 constexpr int wpi = win == 0 ? pi : pi - 5;
-                constexpr int npb = win < 0 ? 0 : (wpi < 2 ? 3 : 2);
+                constexpr int npb = win < 0 ? 0 : (wpi < NPBW - 6 ? 3 : 2);
+                constexpr int pk0 = wpi < NPBW - 6 ? 3 * wpi : 2 * wpi + NPBW - 6;   // the pair's first block among the wave's NPBW
                 char *pbuf = win == 0 ? buf1 : buf0;
                 const int pch = min(2 * per + 1 + (win == 1 ? 1 : 0), nch - 1);
                 const int slot1 = slot0 == 2 ? 0 : slot0 + 1;
@@ -544,7 +578,7 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
                         constexpr int b = (v - 8) / 28, w = (v - 8) % 28;
                         auto piece = [&]() {
                             if constexpr (w == 0) {
-                                pr.p = min(wave + 4 * (3 * wpi + b), nblk - 1) * 16 + pl;
+                                pr.p = min(pbw + 4 * (pk0 + b), nblk - 1) * 16 + pl;
                                 pr.wh = W12q[(size_t)(pg & 1) * C + pch * CCB + pl];
                             }
                             if constexpr (w == 1) pr.wl = W12q[(size_t)(2 + (pg & 1)) * C + pch * CCB + pl];
@@ -881,6 +915,7 @@ struct V6Plan {
     int rows = 0, tiles_per_clip = 0;
     size_t lds = 0;
     int v0 = 0, tpc1 = 0;                     // wide form: joints of the first half, tiles of a clip's second half
+    int npbw = 8;                             // producer blocks per wave and chunk (narrow three-term KF6: 7 where v6_blocks_read allows)
 };
 
 // rows of the image one (pixel space of Vh joints) tile needs; 0 when the producer cannot cover it
@@ -888,8 +923,26 @@ inline int v6_rows(int T, int Vh, int K) {
     int dt = ceil_div(NP6 - 1, Vh);
     if (dt > T - 1) dt = T - 1;
     const int span = (dt + K) * Vh;
-    if (ceil_div(ceil_div(span, 16), 4) > 8) return 0;       // producer: 3 + 3 + 2 blocks per wave and chunk
+    if (ceil_div(ceil_div(span, 16), 4) > 8) return 0;       // producer: at most 3 + 3 + 2 blocks per wave and chunk
     return (span + 15) / 16 * 16;
+}
+
+// The most 16-row blocks of its image from which the taps of one tile of a (T, V) clip read: the image starts at frame
+// t_first - 4 (tile_geom_b), the tile's first pixel sits s = q0 - t_first * V rows into it, and the pixels that are stored read
+// the rows s .. s + (q_last - q0) + (K - 1) V — blocks s >> 4 (the kernel's pb0) up to that row's.  Blocks in front of pb0, and
+// what the frame-aligned span holds behind the last row read, feed no result.  Full tiles repeat with s = 256 i mod V, a period
+// of at most V tiles; the clip's last tile is walked as it is.  At most 28: seven producer blocks per wave and chunk, counted
+// from pb0, cover every tile.
+inline int v6_blocks_read(int T, int V, int K) {
+    const int TV = T * V, tpc = ceil_div(TV, NP6);
+    int most = 0;
+    for (int i = 0; i < tpc; ++i) {
+        if (i >= V && i < tpc - 1) i = tpc - 1;              // (the full tiles' geometry has come round)
+        const int q0 = i * NP6, q_last = (q0 + NP6 < TV ? q0 + NP6 : TV) - 1, s = q0 % V;
+        const int n = ((s + q_last - q0 + (K - 1) * V) >> 4) - (s >> 4) + 1;
+        if (n > most) most = n;
+    }
+    return most;
 }
 
 // narrow frames (V <= 32); terms = 3: two images per chunk buffer (KF6 bf16 hi + lo; KF7 fp16 + two e4m3 = 64 B per row)
@@ -903,6 +956,7 @@ inline bool plan_v6_narrow(int C, int T, int V, int K, int terms, V6Plan &pl) {
     if (pl.lds > (size_t)kLdsBytes) return false;
     pl.rows = rows;
     pl.tiles_per_clip = ceil_div(T * V, NP6);
+    pl.npbw = v6_blocks_read(T, V, K) <= 28 ? 7 : 8;         // (read by KF6's three-term launch only)
     return true;
 }
 
@@ -941,6 +995,8 @@ int launch_v6(const uint4 *pf, const float *x, int xsc, int xsp, const float *W1
     const int ntiles = N * pl.tiles_per_clip;
     const dim3 grid(ntiles < num_cu ? ntiles : num_cu, C / 128, 1);
     auto kern = bf16out ? stem_bf16_v6_kernel<TERMS, true, WIDE> : stem_bf16_v6_kernel<TERMS, false, WIDE>;
+    if constexpr (TERMS == 3 && !WIDE)        // (the one-term and the wide forms stay on 8 blocks: not measured on 7)
+        if (pl.npbw == 7) kern = bf16out ? stem_bf16_v6_kernel<3, true, false, 7> : stem_bf16_v6_kernel<3, false, false, 7>;
     STGCN_HIP_CHECK(allow_lds(kern, pl.lds));
     hipLaunchKernelGGL(kern, grid, dim3(NT6), pl.lds, st, pf, x, xsc, xsp, W12, Wq, shift, y, C, T, V, pl.rows,
                        pl.tiles_per_clip, ntiles, opt, debug_buffer(), pl.v0, pl.tpc1);
