@@ -422,15 +422,32 @@ int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, c
 int stgcn_vit_attention_backward_supported(int L, int heads, int head_dim);
 int stgcn_vit_attention_backward(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int heads,
                                  int head_dim, float scale, void *stream);
+/* The same gradient (up to the summation order) for every 1 <= L <= STGCN_VIT_MAX_STREAM_L: two kernels that stream the other
+ * side of each product through LDS under the forward's running soft-max, whose statistics they recompute (nothing but `out`
+ * is needed from the forward).  It runs the streaming kernels at every covered length, the short ones included.
+ * ws: stgcn_vit_attention_backward_stream_ws_bytes(B, L, heads) bytes, 16 per (sequence, head, query); 0 if uncovered. */
+int stgcn_vit_attention_backward_stream_supported(int L, int heads, int head_dim);
+size_t stgcn_vit_attention_backward_stream_ws_bytes(int B, int L, int heads);
+int stgcn_vit_attention_backward_stream(const float *qkv, const float *out, const float *dout, float *dqkv, void *ws,
+                                        size_t ws_bytes, int B, int L, int heads, int head_dim, float scale, void *stream);
 /* LayerNorm backward over the rows of x (M,D), dn = gradient of the LayerNorm's output: dx = rstd (g - mean(g) - xhat
  * mean(g xhat)) (+ dres), g = dn * weight;  dweight = sum dn xhat,  dbias = sum dn.  D % 4 == 0.  dx may alias dn or dres. */
 size_t stgcn_vit_layernorm_backward_ws_bytes(int M, int D);
 int stgcn_vit_layernorm_backward(const float *x, const float *dn, const float *weight, float eps, const float *dres, float *dx,
                                  float *dweight, float *dbias, void *ws, size_t ws_bytes, int M, int D, void *stream);
-/* One block, training.  Coverage = stgcn_vit_block_supported (the resident form: L <= 256).  The size queries return 0 for shapes outside it. */
+/* One block, training.  stgcn_vit_block_forward_train and stgcn_vit_block_backward cover what stgcn_vit_block_forward covers:
+ * L <= 256 on the resident attention kernels, 256 < L <= STGCN_VIT_MAX_STREAM_L on the streaming ones (forward and backward).
+ * These three queries describe the resident form only (= stgcn_vit_block_supported) and answer 0 for L > 256; the three
+ * `_long` queries below cover both ranges and are the ones to size buffers with. */
 int stgcn_vit_block_train_supported(int L, int D, int heads, int hidden);
 size_t stgcn_vit_block_saved_bytes(int B, int L, int D, int hidden);
 size_t stgcn_vit_block_backward_ws_bytes(int B, int L, int D, int hidden);
+/* Both ranges.  At L <= 256 they answer what the three above answer.  Above: `saved` is the same layout (the streaming
+ * backward recomputes its soft-max statistics, nothing new is saved); the workspace is the resident one plus the attention
+ * statistics of one slab of sequences. */
+int stgcn_vit_block_train_long_supported(int L, int D, int heads, int hidden);
+size_t stgcn_vit_block_train_long_saved_bytes(int B, int L, int D, int hidden);
+size_t stgcn_vit_block_train_long_ws_bytes(int B, int L, int D, int heads, int hidden);
 int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
                                   const float *bqkv, const float *Wproj, const float *bproj, const float *norm2_weight,
                                   const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,

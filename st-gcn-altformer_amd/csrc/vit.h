@@ -1,4 +1,4 @@
-// Launchers of the AltFormer heads' transformer-block kernels (vit_linear.hip, vit_attention.hip, vit_backward.hip) and the
+// Launchers of the AltFormer heads' transformer-block kernels (vit_linear.hip, vit_attention*.hip, vit_backward.hip) and the
 // coverage rules, shared by the entry points in vit_block.hip (inference) and vit_block_train.hip (training).
 // All launchers enqueue on `st` and return a stgcn_status.
 #pragma once
@@ -78,6 +78,14 @@ inline BlockAttention plan_block_forward(int L, int D, int heads, int hidden) {
     return BlockAttention::none;
 }
 
+// ---- the training block's attention launches, chosen here and nowhere else (stgcn_vit_block_forward_train,
+// stgcn_vit_block_backward and the stgcn_vit_block_train_long_* queries read it) ----
+// One form for the forward and the backward of a block: resident (launch_attention_packed, launch_attention_backward) up to
+// kMaxL, exactly as before the streaming backward existed; stream (launch_attention_stream,
+// launch_attention_backward_stream) above.  Today the cut is the inference block's; it is a function of its own because
+// it decides other kernels, and a measurement may move one cut without the other.
+inline BlockAttention plan_block_train(int L, int D, int heads, int hidden) { return plan_block_forward(L, D, heads, hidden); }
+
 inline int slab_seqs(int B, int L) {
     const int s = kSlabRows / L;
     return s < 1 ? 1 : (s > B ? B : s);
@@ -140,6 +148,13 @@ int launch_ln_param_grad(const float *x, const float *dn, const float *stats, fl
 // dqkv (B, L, 3, H, hd) from the packed qkv, the forward's output `out` and its gradient `dout` (both (B, L, H*hd)).
 int launch_attention_backward(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int H, int hd,
                               float scale, hipStream_t st);
+
+// The same gradient up to the summation order for L <= kMaxStreamL (vit_attention_bwd_stream.hip): a query kernel (soft-max
+// statistics, dQ) and a key kernel (dK, dV) that stream the other side through LDS.  `stats`: attention_stats_floats(B, L, H)
+// floats, (m, 1 / l, delta, 0) per (sequence, head, query), written by the first kernel and read by the second.
+inline size_t attention_stats_floats(int B, int L, int H) { return (size_t)B * H * L * 4; }
+int launch_attention_backward_stream(const float *qkv, const float *out, const float *dout, float *dqkv, float *stats, int B,
+                                     int L, int H, int hd, float scale, hipStream_t st);
 
 }  // namespace vit
 }  // namespace stgcn

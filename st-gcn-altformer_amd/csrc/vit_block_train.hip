@@ -7,7 +7,7 @@
 //   dn   = dhid W1                              LN2 backward: dx1 = dy + ...,  a = LN2(x1),  dnorm2
 //                                               dW1, db1   = dhid^T a
 //   datt = (s1 dx1) Wproj                       dWproj, dbproj = (s1 dx1)^T att
-//   dqkv = attention backward(qkv, att, datt)
+//   dqkv = attention backward(qkv, att, datt)     resident up to 256 tokens, streaming above (plan_block_train)
 //   dn   = dqkv Wqkv                            LN1 backward: dx = dx1 + ...,  a = LN1(x),   dnorm1
 //                                               dWqkv, dbqkv = dqkv^T a
 // The dgrads are the forward linear kernel on weights transposed once per call (f32 or bf16x3 like the forward); the
@@ -63,6 +63,19 @@ struct BackwardWs {
         p = max2(p, (size_t)ln_param_splits(M) * 2 * D);
         part = c.take<float>(p);
         tmp = c.take<float>(max2((size_t)3 * D * D, (size_t)D * hidden) + max2((size_t)3 * D, (size_t)hidden));
+        total = c.off;
+    }
+};
+
+// the whole workspace of stgcn_vit_block_backward: the streaming attention backward's statistics of one slab behind BackwardWs
+struct TrainWs {
+    BackwardWs w;
+    float *att_stats = nullptr;
+    size_t total;
+    TrainWs(void *base, BlockAttention plan, int B, int L, int D, int heads, int hidden) : w(base, B, L, D, hidden) {
+        Carve c(base);
+        c.off = w.total;
+        if (plan == BlockAttention::stream) att_stats = c.take<float>(attention_stats_floats(slab_seqs(B, L), L, heads));
         total = c.off;
     }
 };
@@ -157,6 +170,30 @@ int stgcn_vit_attention_backward(const float *qkv, const float *out, const float
     return launch_attention_backward(qkv, out, dout, dqkv, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
 }
 
+int stgcn_vit_attention_backward_stream_supported(int L, int heads, int head_dim) {
+    return attention_stream_ok(L, heads, head_dim) ? 1 : 0;
+}
+
+size_t stgcn_vit_attention_backward_stream_ws_bytes(int B, int L, int heads) {
+    if (B < 1 || heads < 1 || L < 1 || L > kMaxStreamL) return 0;
+    Carve c(nullptr);
+    c.take<float>(attention_stats_floats(B, L, heads));
+    return c.off;
+}
+
+int stgcn_vit_attention_backward_stream(const float *qkv, const float *out, const float *dout, float *dqkv, void *ws,
+                                        size_t ws_bytes, int B, int L, int heads, int head_dim, float scale, void *stream) {
+    if (!qkv || !out || !dout || !dqkv || !ws || B < 1 || L < 1 || heads < 1)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_attention_backward_stream: null pointer or empty shape");
+    if (!attention_stream_ok(L, heads, head_dim))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention_backward_stream: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)",
+                    L, head_dim, kMaxStreamL);
+    const size_t need = stgcn_vit_attention_backward_stream_ws_bytes(B, L, heads);
+    if (ws_bytes < need) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_attention_backward_stream: workspace %zu < %zu bytes", ws_bytes, need);
+    return launch_attention_backward_stream(qkv, out, dout, dqkv, static_cast<float *>(ws), B, L, heads, head_dim, scale,
+                                            static_cast<hipStream_t>(stream));
+}
+
 size_t stgcn_vit_layernorm_backward_ws_bytes(int M, int D) {
     if (M < 1 || D < 1 || D % 4 != 0) return 0;
     return LnBwdWs(nullptr, M, D).total;
@@ -187,6 +224,21 @@ size_t stgcn_vit_block_backward_ws_bytes(int B, int L, int D, int hidden) {
     return BackwardWs(nullptr, B, L, D, hidden).total;
 }
 
+int stgcn_vit_block_train_long_supported(int L, int D, int heads, int hidden) {
+    return plan_block_train(L, D, heads, hidden) != BlockAttention::none ? 1 : 0;
+}
+
+size_t stgcn_vit_block_train_long_saved_bytes(int B, int L, int D, int hidden) {
+    if (B < 1 || L < 1 || D < 1 || hidden < 1 || D % 64 != 0 || hidden % 64 != 0 || L > kMaxStreamL) return 0;
+    return BlockSaved(nullptr, B, L, D, hidden).total;
+}
+
+size_t stgcn_vit_block_train_long_ws_bytes(int B, int L, int D, int heads, int hidden) {
+    const BlockAttention plan = plan_block_train(L, D, heads, hidden);
+    if (B < 1 || plan == BlockAttention::none) return 0;
+    return TrainWs(nullptr, plan, B, L, D, heads, hidden).total;
+}
+
 int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
                                   const float *bqkv, const float *Wproj, const float *bproj, const float *norm2_weight,
                                   const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,
@@ -198,10 +250,11 @@ int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, con
         return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: null pointer");
     if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: B = %d", B);
     if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: y must not alias x");
-    if (!block_ok(L, D, heads, hidden) || !math_ok(flags))
+    const BlockAttention plan = plan_block_train(L, D, heads, hidden);
+    if (plan == BlockAttention::none || !math_ok(flags))
         return fail(STGCN_ERR_UNSUPPORTED,
                     "stgcn_vit_block_forward_train: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
-                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxL);
+                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxStreamL);
     const BlockSaved sv(saved, B, L, D, hidden);
     if (saved_bytes < sv.total)
         return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward_train: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
@@ -223,7 +276,9 @@ int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, con
         int rc;
         if ((rc = launch_linear(xs, Wqkv, bqkv, nullptr, norm1_weight, norm1_bias, eps, qkv, M, D, 3 * D, false, math_qkv, st)))
             return rc;
-        if ((rc = launch_attention_packed(qkv, att, nb, L, heads, D / heads, scale, st))) return rc;
+        rc = plan == BlockAttention::stream ? launch_attention_stream(qkv, att, nb, L, heads, D / heads, scale, st)
+                                            : launch_attention_packed(qkv, att, nb, L, heads, D / heads, scale, st);
+        if (rc) return rc;
         if ((rc = launch_linear_ex(att, Wproj, bproj, xs, nullptr, nullptr, 0.f, x1, M, D, D, false, math, e1, st))) return rc;
         if ((rc = launch_linear_ex(x1, W1, b1, nullptr, norm2_weight, norm2_bias, eps, sv.hid + r0 * hidden, M, D, hidden, true, math,
                                    eh, st)))
@@ -249,15 +304,17 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
         return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: null pointer");
     if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: B = %d", B);
     if (dx == dy || dx == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: dx must not alias dy or x");
-    if (!block_ok(L, D, heads, hidden) || !math_ok(flags))
+    const BlockAttention plan = plan_block_train(L, D, heads, hidden);
+    if (plan == BlockAttention::none || !math_ok(flags))
         return fail(STGCN_ERR_UNSUPPORTED,
                     "stgcn_vit_block_backward: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
-                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxL);
+                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxStreamL);
     const BlockSaved sv(const_cast<void *>(saved), B, L, D, hidden);
     if (saved_bytes < sv.total)
         return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
-    const BackwardWs w(ws, B, L, D, hidden);
-    if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: workspace %zu < %zu bytes", ws_bytes, w.total);
+    const TrainWs tw(ws, plan, B, L, D, heads, hidden);
+    if (ws_bytes < tw.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: workspace %zu < %zu bytes", ws_bytes, tw.total);
+    const BackwardWs &w = tw.w;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned math = flags & STGCN_MATH_MASK;
     const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : math;
@@ -294,7 +351,10 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
         if ((rc = launch_linear_ex(w.dx1, w.wt_proj, nullptr, nullptr, nullptr, nullptr, 0.f, w.datt, M, D, D, false, math, e1, st)))
             return rc;
         if ((rc = launch_wgrad(w.dx1, att, s1, L, dWproj, dbproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
-        if ((rc = launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st))) return rc;
+        rc = plan == BlockAttention::stream
+                 ? launch_attention_backward_stream(qkv, att, w.datt, w.dqkv, tw.att_stats, nb, L, heads, D / heads, scale, st)
+                 : launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st);
+        if (rc) return rc;
         if ((rc = launch_linear(w.dqkv, w.wt_qkv, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, 3 * D, D, false, math_qkv, st)))
             return rc;
         if ((rc = launch_ln_backward(xs, w.dn, norm1_weight, norm1_bias, eps, w.dx1, dx + r0 * D, w.a, w.stats, M, D, st))) return rc;

@@ -97,11 +97,17 @@ PROTOTYPES = {
     "stgcn_vit_linear_backward": (c_int, [_P] * 8 + [c_size_t] + [c_int] * 3 + [c_uint, _P]),
     "stgcn_vit_attention_backward_supported": (c_int, [c_int] * 3),
     "stgcn_vit_attention_backward": (c_int, [_P] * 4 + [c_int] * 4 + [c_float, _P]),
+    "stgcn_vit_attention_backward_stream_supported": (c_int, [c_int] * 3),
+    "stgcn_vit_attention_backward_stream_ws_bytes": (c_size_t, [c_int] * 3),
+    "stgcn_vit_attention_backward_stream": (c_int, [_P] * 5 + [c_size_t] + [c_int] * 4 + [c_float, _P]),
     "stgcn_vit_layernorm_backward_ws_bytes": (c_size_t, [c_int] * 2),
     "stgcn_vit_layernorm_backward": (c_int, [_P] * 3 + [c_float] + [_P] * 5 + [c_size_t, c_int, c_int, _P]),
     "stgcn_vit_block_train_supported": (c_int, [c_int] * 4),
     "stgcn_vit_block_saved_bytes": (c_size_t, [c_int] * 4),
     "stgcn_vit_block_backward_ws_bytes": (c_size_t, [c_int] * 4),
+    "stgcn_vit_block_train_long_supported": (c_int, [c_int] * 4),
+    "stgcn_vit_block_train_long_saved_bytes": (c_size_t, [c_int] * 4),
+    "stgcn_vit_block_train_long_ws_bytes": (c_size_t, [c_int] * 5),
     "stgcn_vit_block_forward_train": (c_int, [_P] * 15 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
     "stgcn_vit_block_backward": (c_int, [_P] * 12 + [c_size_t] + [_P] * 14 + [c_float, c_float, _P, c_size_t] + [c_int] * 5
                                  + [c_uint, _P]),

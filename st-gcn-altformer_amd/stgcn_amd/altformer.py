@@ -16,7 +16,8 @@ Two paths, one result:
   channels-last, consumed in place); pooling, the second embedding and ``mlp_head`` are torch ops.
 * HIP, training (``stgcn_vit_block_forward_train`` / ``stgcn_vit_block_backward`` behind one ``autograd.Function``): the same
   input conditions while autograd IS recording something that concerns the block (``.train()``, or ``.eval()`` with gradients),
-  sequences of up to 256 tokens (longer ones train on torch ops), no ``nn.Dropout`` active, at least ``HIP_TRAIN_MIN_TOKENS``
+  sequences of up to 256 tokens (longer ones train on torch ops unless ``set_long_training(model)`` opts in: then up to
+  4096, on the streaming attention forward and the two streaming backward kernels), no ``nn.Dropout`` active, at least ``HIP_TRAIN_MIN_TOKENS``
   tokens (``set_hip_train_min_tokens``; ``set_hip_min_tokens`` sets both thresholds), env ``STGCN_VIT_TRAIN`` not ``0``.  Stochastic depth is covered: ``Block.draw_drop_path`` draws the two masks
   with the torch path's calls in its order (same seed, same masks) and the kernels apply them per sequence.  The parameters
   are taken by attribute, so an ``nn.DataParallel`` replica's gradients reach its master.  ``Block.trains_on_hip(x)`` tells.
@@ -97,6 +98,21 @@ def set_low_latency(module: nn.Module, enabled: bool = True, min_tokens=None) ->
                 sub.hip_min_tokens = HIP_MIN_TOKENS
             else:
                 sub.hip_min_tokens = LOW_LATENCY_MIN_TOKENS if min_tokens is None else int(min_tokens)
+
+
+HIP_TRAIN_MAX_LEN = 256        # longest sequence a Block trains on HIP by default: the resident attention kernels' limit
+HIP_TRAIN_LONG_MAX_LEN = 4096  # with set_long_training: the streaming kernels' limit.  Opt-in because the measurement at 500
+#                                frames, batch 32 (tools/time_altformer_train.py --frames 500, DESIGN section 15 "long sequences")
+#                                is mixed: the TS temporal stage 1.50 x faster than torch ops, the ST temporal stage a tie
+
+
+def set_long_training(module: nn.Module, enabled: bool = True) -> None:
+    """Sequences of 257 to 4096 tokens of every ``Block`` below train on the HIP kernels (the streaming attention forward
+    and backward) instead of torch ops: ``hip_train_max_len`` = 4096, or back to 256 with ``enabled=False``.  Shorter
+    sequences and both token thresholds are not touched."""
+    for sub in module.modules():
+        if isinstance(sub, Block):
+            sub.hip_train_max_len = HIP_TRAIN_LONG_MAX_LEN if enabled else HIP_TRAIN_MAX_LEN
 
 
 def set_hip_min_tokens(module: nn.Module, tokens: int) -> None:
@@ -228,6 +244,7 @@ class Block(nn.Module):
         self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
         self.hip_min_tokens = HIP_MIN_TOKENS   # set_hip_min_tokens
         self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
+        self.hip_train_max_len = HIP_TRAIN_MAX_LEN         # set_long_training
         self.small_tiles = False               # set_low_latency: the inference linears pick their tile form by call size
 
     def _weights(self):
@@ -238,7 +255,8 @@ class Block(nn.Module):
 
     def _kernels_cover(self, x: torch.Tensor, train: bool) -> bool:
         """CUDA float32 (B, L, D) input and a module the kernels implement (LayerNorms with affine, exact GELU, covered sizes).
-        The sizes differ: inference reaches 4096 tokens per sequence (the streaming attention kernel above 256), training 256."""
+        The sizes differ: inference reaches 4096 tokens per sequence (the streaming attention kernel above 256), training
+        ``hip_train_max_len`` (256 unless ``set_long_training`` raised it)."""
         if self.force_torch or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
             return False
         if not (type(self.norm1) is nn.LayerNorm and type(self.norm2) is nn.LayerNorm and isinstance(self.mlp.act, nn.GELU)
@@ -249,8 +267,10 @@ class Block(nn.Module):
         B, L, D = x.shape
         if B < 1 or D != self.norm1.normalized_shape[0] or self.mlp.fc2.out_features != D:
             return False
-        covered = F.vit_block_train_supported if train else F.vit_block_forward_supported
-        return covered(L, D, self.attn.num_heads, self.mlp.fc1.out_features)
+        if train:
+            return L <= self.hip_train_max_len and F.vit_block_train_long_supported(L, D, self.attn.num_heads,
+                                                                                    self.mlp.fc1.out_features)
+        return F.vit_block_forward_supported(L, D, self.attn.num_heads, self.mlp.fc1.out_features)
 
     def _records_grad(self, x: torch.Tensor) -> bool:
         return torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in self._weights()))

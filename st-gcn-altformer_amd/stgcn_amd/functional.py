@@ -665,19 +665,48 @@ def vit_linear_backward(dy, a, weight, h_pre=None, dx_accumulate=None, need_dx=T
     return dx, dW, db
 
 
-def vit_attention_backward(qkv, out, dout, heads, scale=None) -> torch.Tensor:
-    """Gradient of the packed qkv (B, L, 3*D) from the forward's output ``out`` and its gradient ``dout`` (B, L, D)."""
+def vit_attention_backward_supported(L, heads, head_dim) -> bool:
+    """The resident backward's coverage (L <= 256)."""
+    return bool(_capi.lib().stgcn_vit_attention_backward_supported(L, heads, head_dim))
+
+
+def vit_attention_backward_stream_supported(L, heads, head_dim) -> bool:
+    """The streaming backward's coverage (L <= 4096)."""
+    return bool(_capi.lib().stgcn_vit_attention_backward_stream_supported(L, heads, head_dim))
+
+
+def _vit_attention_backward(stream, qkv, out, dout, heads, scale):
     dev = qkv.device
     B, L, D3 = qkv.shape
     hd = D3 // 3 // heads
     if hd * heads * 3 != D3 or out.shape != (B, L, D3 // 3) or dout.shape != out.shape:
         raise ValueError(f"qkv {tuple(qkv.shape)}, out {tuple(out.shape)}, dout {tuple(dout.shape)} with {heads} heads")
     dqkv = torch.empty_like(qkv)
+    ptrs = [_dev_ptr(qkv, "qkv", dev), _dev_ptr(out, "out", dev), _dev_ptr(dout, "dout", dev), _dev_ptr(dqkv, "dqkv")]
+    dims = [c_int(B), c_int(L), c_int(heads), c_int(hd), c_float(hd ** -0.5 if scale is None else scale), _stream(dev)]
     with torch.cuda.device(dev):
-        _capi.call("stgcn_vit_attention_backward", _dev_ptr(qkv, "qkv", dev), _dev_ptr(out, "out", dev), _dev_ptr(dout, "dout", dev),
-                   _dev_ptr(dqkv, "dqkv"), c_int(B), c_int(L), c_int(heads), c_int(hd),
-                   c_float(hd ** -0.5 if scale is None else scale), _stream(dev))
+        if stream:
+            nbytes = _capi.lib().stgcn_vit_attention_backward_stream_ws_bytes(B, L, heads)
+            ws = _bytes(dev, nbytes)
+            _capi.call("stgcn_vit_attention_backward_stream", *ptrs, c_void_p(ws.data_ptr()), c_size_t(nbytes), *dims)
+        else:
+            _capi.call("stgcn_vit_attention_backward", *ptrs, *dims)
     return dqkv
+
+
+def vit_attention_backward(qkv, out, dout, heads, scale=None) -> torch.Tensor:
+    """Gradient of the packed qkv (B, L, 3*D) from the forward's output ``out`` and its gradient ``dout`` (B, L, D).
+    Sequences of up to 256 tokens run the resident kernel, longer ones (up to 4096) the streaming kernels."""
+    L, hd = qkv.shape[1], qkv.shape[2] // 3 // heads
+    stream = not vit_attention_backward_supported(L, heads, hd) and vit_attention_backward_stream_supported(L, heads, hd)
+    return _vit_attention_backward(stream, qkv, out, dout, heads, scale)
+
+
+def vit_attention_backward_stream(qkv, out, dout, heads, scale=None) -> torch.Tensor:
+    """``vit_attention_backward`` on the streaming kernels (a query kernel for the soft-max statistics and dq, a key kernel
+    for dk and dv, their workspace allocated here) at every covered length, the short ones included: the same result up to
+    the summation order."""
+    return _vit_attention_backward(True, qkv, out, dout, heads, scale)
 
 
 def vit_layernorm_backward(x, dn, weight, eps, dres=None):
@@ -698,7 +727,23 @@ def vit_layernorm_backward(x, dn, weight, eps, dres=None):
 
 
 def vit_block_train_supported(L, D, heads, hidden) -> bool:
+    """Coverage of the resident form of the training entry points (L <= 256)."""
     return bool(_capi.lib().stgcn_vit_block_train_supported(L, D, heads, hidden))
+
+
+def vit_block_train_long_supported(L, D, heads, hidden) -> bool:
+    """What ``vit_block_forward_train`` / ``vit_block_backward`` run: the resident coverage plus 256 < L <= 4096 on the
+    streaming attention kernels."""
+    return bool(_capi.lib().stgcn_vit_block_train_long_supported(L, D, heads, hidden))
+
+
+def _vit_block_train_bytes(B, L, D, heads, hidden):
+    """(saved bytes, workspace bytes) of the training entry points.  The resident form's queries where they answer (L <= 256),
+    the ``_long`` queries, which cover both ranges and answer the same there, for what those leave at 0."""
+    lib = _capi.lib()
+    saved = lib.stgcn_vit_block_saved_bytes(B, L, D, hidden) or lib.stgcn_vit_block_train_long_saved_bytes(B, L, D, hidden)
+    ws = lib.stgcn_vit_block_backward_ws_bytes(B, L, D, hidden) or lib.stgcn_vit_block_train_long_ws_bytes(B, L, D, heads, hidden)
+    return saved, ws
 
 
 VIT_BLOCK_PARAMS = ("norm1.weight", "norm1.bias", "qkv.weight", "qkv.bias", "proj.weight", "proj.bias", "norm2.weight",
@@ -712,7 +757,7 @@ def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=
     dev = x.device
     B, L, D = x.shape
     hidden = params[8].shape[0]
-    nbytes = _capi.lib().stgcn_vit_block_saved_bytes(B, L, D, hidden)
+    nbytes, _ = _vit_block_train_bytes(B, L, D, heads, hidden)
     saved = _bytes(dev, nbytes)
     y = torch.empty_like(x)
     with torch.cuda.device(dev):
@@ -730,8 +775,7 @@ def vit_block_backward(x, params, saved, dy, heads, eps, scale, math=MATH_F32, s
     dev = x.device
     B, L, D = x.shape
     hidden = params[8].shape[0]
-    sbytes = _capi.lib().stgcn_vit_block_saved_bytes(B, L, D, hidden)
-    nbytes = _capi.lib().stgcn_vit_block_backward_ws_bytes(B, L, D, hidden)
+    sbytes, nbytes = _vit_block_train_bytes(B, L, D, heads, hidden)
     if saved.numel() * saved.element_size() < sbytes:
         raise ValueError("saved does not come from vit_block_forward_train of these shapes")
     ws = _bytes(dev, nbytes)

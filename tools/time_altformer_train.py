@@ -6,6 +6,14 @@ depth on - the HIP training path against the torch-op path of the same module, i
     python tools/time_altformer_train.py [--batch 32] [--repeats 7] [--warmup 2] [--out profiles/altformer_train_times.json]
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/time_altformer_train.py --stages-only --repeats 5
 
+    python tools/time_altformer_train.py --frames 500 [--batch 32] [--out profiles/altformer_long_train_times.json]
+
+``--frames T`` (T > 256) times training on long clips instead, where the blocks train on HIP only after
+``set_long_training`` (the streaming attention forward and backward): forward + backward of one block at the ST temporal stage
+(``batch`` sequences of T, D = 512) and the TS temporal stage (``batch`` x 22 sequences of T, D = 256), and one training step
+of the whole ST and TS models at ``num_frame = T``, each alternating ``set_long_training`` on and off in one process.  Off is
+the torch-op path such blocks take by default, with ``torch.cuda.max_memory_allocated`` of each.
+
 Prints ONE JSON line.  Per stage: ms of forward + backward (min, median, max, ``spread`` = (max - min) / min) of the torch
 path and of the HIP path in each arithmetic ('f32', 'mixed', 'bf16x3'), the speed-up of the default arithmetic, and
 ``hip_faster`` = the HIP median is below the torch median by more than the larger of the two spreads (the rule
@@ -24,9 +32,87 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "st-gcn-altformer_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from time_altformer import STAGES, alternate, summary   # noqa: E402  (same stages, same way of timing)
+from time_altformer import STAGES, alternate, faster_by_more_than_the_spread, peak_bytes, summary   # noqa: E402  (same stages, same way of timing)
 
 MODES = ("f32", "mixed", "bf16x3")
+
+
+def long_clips(args):
+    """The ``--frames`` run (see the module docstring)."""
+    import stgcn_amd
+    from stgcn_amd.altformer import DEFAULT_TRAIN_MATH, Block, set_long_training
+    T, dev = args.frames, torch.device("cuda:0")
+    assert T > 256, "--frames is for sequences the resident attention kernels do not take"
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    res = {"frames": T, "batch": args.batch, "repeats": args.repeats, "default_train_math": DEFAULT_TRAIN_MATH,
+           "device": torch.cuda.get_device_name(0), "stages": {}, "models": {}}
+
+    def entry(ts, mem, **more):
+        med = {k: statistics.median(v) for k, v in ts.items()}
+        return {**more, "hip_ms": summary(ts["hip"]), "torch_ms": summary(ts["torch"]),
+                "speedup_median": round(med["torch"] / med["hip"], 3),
+                "hip_faster": faster_by_more_than_the_spread(ts["hip"], ts["torch"]),
+                "peak_mib_hip": round(mem["hip"] / 2 ** 20, 1), "peak_mib_torch": round(mem["torch"] / 2 ** 20, 1)}
+
+    for name, (per_clip, D) in {f"ST temporal {T}": (1, 512), f"TS temporal (22 x {T})": (22, 256)}.items():
+        B = args.batch * per_clip
+        torch.manual_seed(0)
+        blk = Block(D, 8, mlp_ratio=2., qkv_bias=True, drop_path=0.1, norm_layer=norm).to(dev).train()
+        x = torch.randn(B, T, D, device=dev, requires_grad=True)
+        dy = torch.randn(B, T, D, device=dev)
+        chooses = "hip" if blk.trains_on_hip(x) else "torch"
+        blk.hip_train_min_tokens = 0
+
+        def run(long):
+            set_long_training(blk, long)
+            assert blk.trains_on_hip(x) == long
+            x.grad = None
+            for p in blk.parameters():
+                p.grad = None
+            blk(x).backward(dy)
+        ts = alternate({"torch": partial(run, False), "hip": partial(run, True)}, args.repeats, args.warmup)
+        mem = {k: peak_bytes(partial(run, k == "hip")) for k in ("torch", "hip")}
+        res["stages"][name] = entry(ts, mem, B=B, L=T, D=D, tokens=B * T, module_chooses=chooses)
+        del blk, x, dy
+        torch.cuda.empty_cache()
+    for style in () if args.stages_only else ("ST", "TS"):
+        torch.manual_seed(1)
+        model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=T, num_joints=22, style=style,
+                                           graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).train()
+        clips = torch.randn(args.batch, T, 22, 3, device=dev)
+        labels = torch.arange(args.batch, device=dev) % 14
+        ce = torch.nn.CrossEntropyLoss()
+        blocks = [b for b in model.modules() if isinstance(b, Block)]
+
+        def step(long):
+            set_long_training(model, long)
+            model.zero_grad(set_to_none=True)
+            ce(model(clips), labels).backward()
+        on_hip = {}
+        for long in (False, True):            # which blocks train on HIP under the default token threshold, off and on
+            calls = []
+            hooks = [b.register_forward_pre_hook(lambda mod, a: calls.append(bool(mod.trains_on_hip(a[0])))) for b in blocks]
+            step(long)
+            for hk in hooks:
+                hk.remove()
+            on_hip["on" if long else "off"] = sum(calls)
+        ts = alternate({"torch": partial(step, False), "hip": partial(step, True)}, args.repeats, args.warmup)
+        mem = {k: peak_bytes(partial(step, k == "hip")) for k in ("torch", "hip")}
+        med = {k: statistics.median(v) for k, v in ts.items()}
+        res["models"][style] = entry(ts, mem, blocks=len(blocks), blocks_on_hip=on_hip,
+                                     clips_per_s_hip=round(args.batch / (med["hip"] * 1e-3), 1),
+                                     clips_per_s_torch=round(args.batch / (med["torch"] * 1e-3), 1))
+        del model, clips
+        torch.cuda.empty_cache()
+    return res
+
+
+def emit(res, out):
+    line = json.dumps(res)
+    if out:
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
 
 
 def main():
@@ -35,9 +121,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--stages-only", action="store_true")
+    ap.add_argument("--frames", type=int, default=None, help="time training at this many frames (> 256) instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
+    if args.frames is not None:
+        return emit(long_clips(args), args.out)
     import stgcn_amd
     from stgcn_amd.altformer import DEFAULT_TRAIN_MATH, HIP_TRAIN_MIN_TOKENS, Block, set_head_math, set_hip_min_tokens
     dev = torch.device("cuda:0")
@@ -100,11 +189,7 @@ def main():
             "clips_per_s_torch": round(args.batch / (med["torch"] * 1e-3), 1)}
         del model
         torch.cuda.empty_cache()
-    line = json.dumps(res)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-    print(line)
+    emit(res, args.out)
 
 
 if __name__ == "__main__":
