@@ -339,7 +339,8 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
  *   y  = x1 + fc2(GELU(fc1(LN2(x1))))    softmax over keys of scale * q k^T; GELU in its exact erf form.
  * Weights are nn.Linear.weight as stored: (out_features, in_features), in_features contiguous.
  * `flags`: low 4 bits STGCN_MATH_F32 (v_mfma_f32_32x32x2_f32) or STGCN_MATH_BF16X3 (hi + lo split of both operands, three
- * bf16 MFMAs, fp32 accumulate) for the linears; the attention itself always runs on the fp32 matrix cores. */
+ * bf16 MFMAs, fp32 accumulate) for the linears; the attention itself always runs on the fp32 matrix cores.
+ * STGCN_VIT_BF16 (below, opt-in) runs the whole block, attention included, on bf16 operands instead. */
 #define STGCN_VIT_GELU 0x1000u    /* stgcn_vit_linear: exact GELU after the bias                                     */
 #define STGCN_VIT_QKV_F32 0x2000u /* stgcn_vit_block_forward: the qkv linear in f32 whatever the low bits say (an error
                                    * in q or k is multiplied by the size of the scores before the exponential)        */
@@ -398,6 +399,36 @@ int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const flo
                             const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,
                             float eps, float scale, void *ws, size_t ws_bytes, float *y, int B, int L, int D, int heads,
                             int hidden, unsigned flags, void *stream);
+
+/* ---- ViT block in bf16 (additive to ABI 11: new symbols and one flag bit; inference only) ----------------------------------
+ * STGCN_VIT_BF16 on stgcn_vit_block_forward runs the whole block with bf16 matrix operands: operands rounded to nearest-even
+ * bf16, products accumulated in fp32 (v_mfma_f32_32x32x16_bf16), everything that is not a matrix operand fp32:
+ *   qkv  : LN1(x) in fp32, rounded as the A operand; Wqkv rounded while staged; bias in fp32; the result STORED AS bf16;
+ *   attn : scores = bf16 q . bf16 k in fp32, times `scale` in fp32; max, exp and row sum in fp32 (the sum adds the unrounded
+ *          p = exp(s - max)); p rounded to bf16 as the operand of P V; O accumulated in fp32, divided by the sum, STORED AS bf16;
+ *   proj : bf16 attention output x rounded Wproj + bias + the fp32 residual x -> x1 in fp32;
+ *   fc1  : LN2(x1) in fp32, rounded; W1 rounded; bias and the exact erf GELU in fp32; the hidden tensor STORED AS bf16;
+ *   fc2  : bf16 hidden x rounded W2 + bias + x1 -> y in fp32.
+ * The low math bits are ignored, the STGCN_VIT_TILE_* field is honoured (same bits for every form); with STGCN_VIT_QKV_F32 the
+ * call answers STGCN_ERR_ARG.  Covered: the resident form (stgcn_vit_block_forward_bf16_supported: head_dim 32 / 64, L <= 256,
+ * D and hidden multiples of 64), STGCN_ERR_UNSUPPORTED elsewhere.  The workspace is stgcn_vit_block_ws_bytes' (the mode needs
+ * less of it).  The training entry points (stgcn_vit_block_forward_train, stgcn_vit_block_backward,
+ * stgcn_vit_linear_backward) answer STGCN_ERR_ARG to the bit.  Gate: 1e-2 of max|y| (the stem's bf16 gate). */
+#define STGCN_VIT_BF16 0x40000u
+int stgcn_vit_block_forward_bf16_supported(int L, int D, int heads, int hidden);
+/* stgcn_vit_linear in the bf16 arithmetic above.  x is fp32, or bf16 storage with STGCN_VIT_X_BF16 (no LayerNorm then:
+ * STGCN_ERR_UNSUPPORTED); y is fp32, or bf16 storage with STGCN_VIT_Y_BF16.  W, bias, residual and the LayerNorm vectors are
+ * fp32.  `flags`: the two storage bits, STGCN_VIT_GELU and a STGCN_VIT_TILE_* field.  Covered: any M and Nout, K % 32 == 0,
+ * with LayerNorm K <= 4096. */
+#define STGCN_VIT_X_BF16 0x80000u
+#define STGCN_VIT_Y_BF16 0x100000u
+int stgcn_vit_linear_bf16_supported(int M, int K, int Nout, unsigned flags);
+int stgcn_vit_linear_bf16(const void *x, const float *W, const float *bias, const float *ln_weight, const float *ln_bias,
+                          float ln_eps, const float *residual, void *y, int M, int K, int Nout, unsigned flags, void *stream);
+/* stgcn_vit_attention (the resident form) on bf16 qkv (B, L, 3, heads, head_dim) and bf16 out (B, L, heads*head_dim).
+ * Covered: head_dim in {32, 64}, 1 <= L <= 256, any B and heads.  One launch, K and V of a pair in LDS as bf16. */
+int stgcn_vit_attention_bf16_supported(int L, int heads, int head_dim);
+int stgcn_vit_attention_bf16(const void *qkv, void *out, int B, int L, int heads, int head_dim, float scale, void *stream);
 
 /* ---- ViT block: training (additive to ABI 10: new symbols and flag bits only) ------------------------------------------
  * The training forward is the eval forward's five launches with the tensors the backward reads written to the caller's

@@ -121,6 +121,25 @@ int launch_attention_packed(const float *qkv, float *out, int B, int L, int H, i
 // under a running soft-max, kStreamQueries queries of a pair per workgroup (vit_attention_stream.hip).
 int launch_attention_stream(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
 
+// ---- the bf16 mode of the inference block (STGCN_VIT_BF16; vit_block.hip) -------------------------------------------------
+// Operands rounded to nearest-even bf16, fp32 accumulate; qkv, the attention output and the fc1 hidden live in the workspace
+// as bf16 (each is read by one consumer, as a matrix-core operand only).  Inference, resident attention form only.
+inline bool block_bf16_ok(int L, int D, int heads, int hidden) { return block_ok(L, D, heads, hidden); }
+
+// The linear in the bf16 arithmetic (vit_linear.hip): X fp32 (rounded while staged, after the LayerNorm if any) or bf16
+// storage (no LayerNorm then), Y fp32 or bf16 storage; W, bias, R, gamma, beta fp32.  `tile`: a STGCN_VIT_TILE_* field.
+int launch_linear_bf16(const void *X, bool x_bf16, const float *W, const float *bias, const float *R, const float *gamma,
+                       const float *beta, float eps, void *Y, bool y_bf16, int M, int K, int Nout, bool gelu, unsigned tile,
+                       hipStream_t st);
+
+// The resident attention on bf16 qkv / out (vit_attention_bf16.hip); L <= kMaxL, hd in {32, 64}.  Its LDS per workgroup:
+// K as [keys][hd + 8] and V transposed as [hd][keys + 8], keys = L rounded up to 32, for the pairs a workgroup packs.
+inline size_t attention_bf16_lds_bytes(int L, int hd) {
+    const int nt = ceil_div(L, 32), g = nt >= 4 ? 1 : 4 / nt, rows = nt * 32;
+    return (size_t)g * ((size_t)rows * (hd + 8) + (size_t)hd * (rows + 8)) * 2;
+}
+int launch_attention_bf16(const void *qkv, void *out, int B, int L, int H, int hd, float scale, hipStream_t st);
+
 // ---- backward (vit_backward.hip) ----------------------------------------------------------------------------------------
 // Wt (cols, rows_pad) = W (rows, cols)^T, the columns from `rows` to rows_pad zero-filled: the dgrad dX = dY W is the
 // forward linear on the transposed weight, so it shares launch_linear's kernel, arithmetic modes and epilogues.

@@ -1,6 +1,6 @@
 // C entry points of the AltFormer heads' transformer block (include/stgcn_hip.h, "ViT block", ABI 10): the linear and the
-// attention (resident and streaming form) on their own, and the eval forward of one Block = five launches on one stream from
-// a caller workspace:
+// attention (resident and streaming form, and their bf16 forms) on their own, and the eval forward of one Block = five
+// launches on one stream from a caller workspace (STGCN_VIT_BF16: the same five on bf16 operands, block_forward_bf16):
 //   qkv = LN1(x) Wqkv^T + b -> attention -> x1 = a Wproj^T + b + x -> h = GELU(LN2(x1) W1^T + b1) -> y = h W2^T + b2 + x1
 // (both LayerNorms inside the linear that consumes them).  A STGCN_VIT_TILE_* field in `flags` goes to the four linears.
 // Long inputs are walked in slabs of whole sequences (kSlabRows tokens): the four intermediates of a slab (about 7 KB per
@@ -25,6 +25,51 @@ struct BlockWs {
         total = c.off;
     }
 };
+
+// The bf16 mode's plan: the same four pieces in the same order, the three that only feed matrix cores as bf16.  Every piece
+// is at most as large as BlockWs's, so the plan fits what stgcn_vit_block_ws_bytes sizes.
+struct BlockWsBf16 {
+    unsigned short *qkv, *att, *hid;
+    float *x1;
+    size_t total;
+    BlockWsBf16(void *base, int B, int L, int D, int hidden) {
+        const size_t rows = (size_t)slab_seqs(B, L) * L;
+        Carve c(base);
+        qkv = c.take<unsigned short>(rows * 3 * D);
+        att = c.take<unsigned short>(rows * D);
+        x1 = c.take<float>(rows * D);
+        hid = c.take<unsigned short>(rows * hidden);
+        total = c.off;
+    }
+};
+
+int block_forward_bf16(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv, const float *bqkv,
+                       const float *Wproj, const float *bproj, const float *norm2_weight, const float *norm2_bias,
+                       const float *W1, const float *b1, const float *W2, const float *b2, float eps, float scale, void *ws,
+                       size_t ws_bytes, float *y, int B, int L, int D, int heads, int hidden, unsigned tile, hipStream_t st) {
+    const BlockWsBf16 w(ws, B, L, D, hidden);
+    if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward: workspace %zu < %zu bytes", ws_bytes, w.total);
+    const int per = slab_seqs(B, L);
+    for (int b0 = 0; b0 < B; b0 += per) {
+        const int nb = B - b0 < per ? B - b0 : per;
+        const int M = nb * L;
+        const float *xs = x + (size_t)b0 * L * D;
+        float *ys = y + (size_t)b0 * L * D;
+        int rc;
+        if ((rc = launch_linear_bf16(xs, false, Wqkv, bqkv, nullptr, norm1_weight, norm1_bias, eps, w.qkv, true, M, D, 3 * D, false,
+                                     tile, st)))
+            return rc;
+        if ((rc = launch_attention_bf16(w.qkv, w.att, nb, L, heads, D / heads, scale, st))) return rc;
+        if ((rc = launch_linear_bf16(w.att, true, Wproj, bproj, xs, nullptr, nullptr, 0.f, w.x1, false, M, D, D, false, tile, st)))
+            return rc;
+        if ((rc = launch_linear_bf16(w.x1, false, W1, b1, nullptr, norm2_weight, norm2_bias, eps, w.hid, true, M, D, hidden, true,
+                                     tile, st)))
+            return rc;
+        if ((rc = launch_linear_bf16(w.hid, true, W2, b2, w.x1, nullptr, nullptr, 0.f, ys, false, M, hidden, D, false, tile, st)))
+            return rc;
+    }
+    return STGCN_OK;
+}
 
 }  // namespace
 }  // namespace vit
@@ -85,6 +130,40 @@ int stgcn_vit_attention_stream(const float *qkv, float *out, int B, int L, int h
     return launch_attention_stream(qkv, out, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
 }
 
+int stgcn_vit_linear_bf16_supported(int M, int K, int Nout, unsigned flags) {
+    (void)flags;   // storage bits, GELU and the tile field do not change the coverage (the query has no LayerNorm argument)
+    return M >= 1 && K >= 1 && linear_ok(K, Nout, false) ? 1 : 0;
+}
+
+int stgcn_vit_linear_bf16(const void *x, const float *W, const float *bias, const float *ln_weight, const float *ln_bias,
+                          float ln_eps, const float *residual, void *y, int M, int K, int Nout, unsigned flags, void *stream) {
+    if (!x || !W || !y || M < 1 || K < 1 || Nout < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_bf16: null pointer or empty shape");
+    if ((ln_weight == nullptr) != (ln_bias == nullptr))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_linear_bf16: ln_weight and ln_bias go together");
+    if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_bf16: y must not alias x");
+    const bool ln = ln_weight != nullptr, xb = (flags & STGCN_VIT_X_BF16) != 0, yb = (flags & STGCN_VIT_Y_BF16) != 0;
+    if (ln && xb) return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_linear_bf16: LayerNorm needs fp32 x (STGCN_VIT_X_BF16 set)");
+    if (!linear_ok(K, Nout, ln))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_linear_bf16: K = %d, Nout = %d (covered: K %% 32 == 0)", K, Nout);
+    return launch_linear_bf16(x, xb, W, bias, residual, ln_weight, ln_bias, ln_eps, y, yb, M, K, Nout, (flags & STGCN_VIT_GELU) != 0,
+                              flags & STGCN_VIT_TILE_MASK, static_cast<hipStream_t>(stream));
+}
+
+int stgcn_vit_attention_bf16_supported(int L, int heads, int head_dim) {
+    return L >= 1 && L <= kMaxL && heads >= 1 && (head_dim == 32 || head_dim == 64) ? 1 : 0;
+}
+
+int stgcn_vit_attention_bf16(const void *qkv, void *out, int B, int L, int heads, int head_dim, float scale, void *stream) {
+    REQUIRE_PTR(qkv); REQUIRE_PTR(out);
+    REQUIRE_POS(B); REQUIRE_POS(L); REQUIRE_POS(heads);
+    if (!stgcn_vit_attention_bf16_supported(L, heads, head_dim))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention_bf16: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)", L,
+                    head_dim, kMaxL);
+    return launch_attention_bf16(qkv, out, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
+}
+
+int stgcn_vit_block_forward_bf16_supported(int L, int D, int heads, int hidden) { return block_bf16_ok(L, D, heads, hidden) ? 1 : 0; }
+
 int stgcn_vit_block_supported(int L, int D, int heads, int hidden) { return block_ok(L, D, heads, hidden) ? 1 : 0; }
 
 int stgcn_vit_block_forward_supported(int L, int D, int heads, int hidden) {
@@ -101,10 +180,21 @@ int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const flo
                             const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,
                             float eps, float scale, void *ws, size_t ws_bytes, float *y, int B, int L, int D, int heads,
                             int hidden, unsigned flags, void *stream) {
+    if ((flags & STGCN_VIT_BF16) && (flags & STGCN_VIT_QKV_F32))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: STGCN_VIT_BF16 and STGCN_VIT_QKV_F32 exclude each other");
     if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !y || !ws)
         return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: null pointer");
     if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: B = %d", B);
     if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: y must not alias x");
+    if (flags & STGCN_VIT_BF16) {
+        if (!block_bf16_ok(L, D, heads, hidden))
+            return fail(STGCN_ERR_UNSUPPORTED,
+                        "stgcn_vit_block_forward: L = %d, D = %d, heads = %d, hidden = %d with STGCN_VIT_BF16 (covered: head_dim "
+                        "32 / 64, L <= %d, D and hidden multiples of 64)", L, D, heads, hidden, kMaxL);
+        return block_forward_bf16(x, norm1_weight, norm1_bias, Wqkv, bqkv, Wproj, bproj, norm2_weight, norm2_bias, W1, b1, W2, b2,
+                                  eps, scale, ws, ws_bytes, y, B, L, D, heads, hidden, flags & STGCN_VIT_TILE_MASK,
+                                  static_cast<hipStream_t>(stream));
+    }
     const BlockAttention attention = plan_block_forward(L, D, heads, hidden);
     if (attention == BlockAttention::none || !math_ok(flags))
         return fail(STGCN_ERR_UNSUPPORTED,

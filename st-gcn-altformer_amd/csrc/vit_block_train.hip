@@ -128,6 +128,7 @@ size_t stgcn_vit_linear_backward_ws_bytes(int M, int K, int Nout) {
 
 int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, const float *h_pre, float *dx, float *dW,
                               float *db, void *ws, size_t ws_bytes, int M, int K, int Nout, unsigned flags, void *stream) {
+    if (flags & STGCN_VIT_BF16) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)");
     if (flags & STGCN_VIT_TILE_MASK) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)");
     if (!dy || !ws || M < 1 || K < 1 || Nout < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: null pointer or empty shape");
     if ((dx != nullptr && !W) || (dW != nullptr && !a) || (db != nullptr && !dW))
@@ -245,6 +246,7 @@ int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, con
                                   const float *scale1, const float *scale2, float eps, float scale, void *saved,
                                   size_t saved_bytes, float *y, int B, int L, int D, int heads, int hidden, unsigned flags,
                                   void *stream) {
+    if (flags & STGCN_VIT_BF16) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)");
     if (flags & STGCN_VIT_TILE_MASK) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)");
     if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !y || !saved)
         return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: null pointer");
@@ -297,6 +299,7 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
                              float *dWproj, float *dbproj, float *dnorm2_weight, float *dnorm2_bias, float *dW1, float *db1,
                              float *dW2, float *db2, float eps, float scale, void *ws, size_t ws_bytes, int B, int L, int D,
                              int heads, int hidden, unsigned flags, void *stream) {
+    if (flags & STGCN_VIT_BF16) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)");
     if (flags & STGCN_VIT_TILE_MASK) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)");
     if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !saved || !dy || !dx ||
         !dnorm1_weight || !dnorm1_bias || !dWqkv || !dWproj || !dbproj || !dnorm2_weight || !dnorm2_bias || !dW1 || !db1 || !dW2 ||

@@ -6,11 +6,16 @@
 // loads in flight while the current one multiplies.  Tiles are numbered with the Nout tiles fastest, so the workgroups
 // that share a 128-row slab of X run together and the slab is read from HBM once.
 //
-// Two arithmetics (STGCN_MATH_*):
+// Three arithmetics (STGCN_MATH_*):
 //   f32    : v_mfma_f32_32x32x2_f32 on the fp32 tiles (exact products, fp32 accumulate);
 //   bf16x3 : both tiles are split into bf16 hi + lo while they are staged (the weights too: the split of a 128 x 32 weight
 //            chunk is 16 values per thread and hides under the 24 MFMAs of the chunk, so there is no packed weight format
-//            and nothing to cache on the host), then lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16.
+//            and nothing to cache on the host), then lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16;
+//   bf16   : (launch_linear_bf16, the inference block's STGCN_VIT_BF16 mode) both operands rounded to nearest-even bf16 while
+//            they are staged, one LDS tile per operand, one v_mfma_f32_32x32x16_bf16 per k-step and block, fp32 accumulate.
+//            X is fp32 (rounded after the LayerNorm) or already bf16 in memory (XB: 8-byte loads that go to LDS as they
+//            are), Y is stored as fp32 or as bf16 (YB); bias, GELU and residual stay fp32.  The k pairs, instructions and
+//            their order do not depend on the tile form here either, so the three forms agree bit for bit.
 // The k index inside a chunk is permuted the same way for both operands (a dot product does not care): lanes 0-31 of an
 // MFMA take the first half of the chunk / k-step and lanes 32-63 the second, so every fragment is a run of consecutive
 // LDS bytes read with 16-byte loads.  Row strides (36 floats, 40 bf16) make those loads bank-conflict free.
@@ -80,13 +85,24 @@ struct Tiles<STGCN_MATH_BF16X3, BM, BN> {
     unsigned short bh[BN * LDH], bl[BN * LDH];
 };
 
-template <int MATH, class F>
-__global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const float *__restrict__ X, const float *__restrict__ W,
+template <int BM, int BN>
+struct Tiles<STGCN_MATH_BF16, BM, BN> {
+    unsigned short ah[BM * LDH];
+    unsigned short bh[BN * LDH];
+};
+
+// XB / YB (bf16 arithmetic only): X / Y point at bf16 storage, not fp32.
+template <int MATH, class F, bool XB = false, bool YB = false>
+__global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const void *__restrict__ Xv, const float *__restrict__ W,
                                                         const float *__restrict__ bias, const float *R,
                                                         const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                        float eps, float *Y, int M, int K, int Nout, int tiles_n,
+                                                        float eps, void *Yv, int M, int K, int Nout, int tiles_n,
                                                         int gelu, const LinearExtra ex) {
+    static_assert(MATH == STGCN_MATH_BF16 || (!XB && !YB), "bf16 storage goes with the bf16 arithmetic");
     constexpr int BM = F::BM, BN = F::BN, RS = F::RS, PA = F::PA, PB = F::PB, WM = F::WM, WN = F::WN;
+    const float *__restrict__ X = static_cast<const float *>(Xv);                      // !XB
+    const unsigned short *__restrict__ Xh = static_cast<const unsigned short *>(Xv);   // XB
+    float *Y = static_cast<float *>(Yv);
     __shared__ __attribute__((aligned(16))) Tiles<MATH, BM, BN> lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -98,7 +114,7 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const float *__r
     // whole row; it is about to be read again for the A tiles, so this pass mostly primes the cache), sum x - c and
     // (x - c)^2 with c = the row's first element (no cancellation for rows with a large offset), and combine with three
     // exchanges in a fixed order.  Every workgroup of a row slab repeats this; it replaces a pre-pass and its buffer.
-    const bool ln = gamma != nullptr;
+    const bool ln = !XB && gamma != nullptr;   // (a LayerNorm of bf16 rows is refused at the entry point)
     float mean[PA], rstd[PA];
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
@@ -125,12 +141,16 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const float *__r
     }
 
     const int kx = ex.kx > 0 ? ex.kx : K;   // X's row length: K, or (backward) a length that is no multiple of KC, zero-padded
-    float4 xa[PA], wb[PB];
+    float4 xa[XB ? 1 : PA], wb[PB];
+    uint2 xh[XB ? PA : 1];   // XB: four bf16 of the row, as stored
     auto gload = [&](int k0) {
 #pragma unroll
         for (int i = 0; i < F::PMAX; ++i) {
             const int row = m0 + lr + RS * i, n = n0 + lr + RS * i;
-            if (i < PA)
+            if constexpr (XB) {
+                if (i < PA)
+                    xh[i] = row < M ? *reinterpret_cast<const uint2 *>(Xh + (size_t)row * K + k0 + lc) : make_uint2(0u, 0u);
+            } else if (i < PA)
                 xa[i] = row < M && k0 + lc < kx ? *reinterpret_cast<const float4 *>(X + (size_t)row * kx + k0 + lc)
                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
             if (i < PB)
@@ -146,8 +166,8 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const float *__r
 #pragma unroll
         for (int i = 0; i < F::PMAX; ++i) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < PA) {
-                v = xa[i];
+            if (!XB && i < PA) {
+                v = xa[XB ? 0 : i];
                 if (ln) {
                     v.x = (v.x - mean[i]) * rstd[i] * g.x + b.x;
                     v.y = (v.y - mean[i]) * rstd[i] * g.y + b.y;
@@ -159,6 +179,13 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const float *__r
             if constexpr (MATH == STGCN_MATH_F32) {
                 if (i < PA) *reinterpret_cast<float4 *>(&lds.a[r * LDF + lc]) = v;
                 if (i < PB) *reinterpret_cast<float4 *>(&lds.b[r * LDF + lc]) = wb[i];
+            } else if constexpr (MATH == STGCN_MATH_BF16) {
+                if (i < PA)
+                    *reinterpret_cast<uint2 *>(&lds.ah[r * LDH + lc]) =
+                        XB ? xh[XB ? i : 0] : make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+                if (i < PB)
+                    *reinterpret_cast<uint2 *>(&lds.bh[r * LDH + lc]) =
+                        make_uint2(pack_bf16x2(wb[i].x, wb[i].y), pack_bf16x2(wb[i].z, wb[i].w));
             } else {
                 uint2 hi, lo;
                 if (i < PA) {
@@ -210,6 +237,18 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const float *__r
 #pragma unroll
                     for (int n = 0; n < WN; ++n)
                         acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][s], b[n][s], acc[m][n], 0, 0, 0);
+        } else if constexpr (MATH == STGCN_MATH_BF16) {
+#pragma unroll
+            for (int ks = 0; ks < KC / 16; ++ks) {
+                FragB<1, WM> fa;
+                FragB<1, WN> fb;
+#pragma unroll
+                for (int m = 0; m < WM; ++m) {   // WM == WN: one loop reads both operands' fragments
+                    fa.hi[m] = *reinterpret_cast<const uint4 *>(&lds.ah[(wm * (32 * WM) + m * 32 + l31) * LDH + ks * 16 + half * 8]);
+                    fb.hi[m] = *reinterpret_cast<const uint4 *>(&lds.bh[(wn * (32 * WN) + m * 32 + l31) * LDH + ks * 16 + half * 8]);
+                }
+                bf16k::mfma_kstep_bf16<1, WM, WN>(acc, fa, fb);
+            }
         } else {
 #pragma unroll
             for (int ks = 0; ks < KC / 16; ++ks) {
@@ -250,14 +289,21 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const float *__r
                 float v = acc[m][n][i] + bv;
                 const size_t idx = (size_t)row * Nout + col;
                 if (ex.pre != nullptr) ex.pre[idx] = v;
-                if (gelu) v = 0.5f * v * (1.0f + erff(v * kRsqrt2));
+                if (gelu) {
+                    // bf16 arithmetic: the erfc form, accurate RELATIVE to the result in the negative tail too (1 + erff cancels
+                    // there: GELU(-4) = -1.3e-4 comes out with 1e-3 relative error), because a bf16 store rounds relative to
+                    // the value; the other arithmetics keep the form their results were pinned with
+                    if constexpr (MATH == STGCN_MATH_BF16) v = 0.5f * v * erfcf(-v * kRsqrt2);
+                    else v = 0.5f * v * (1.0f + erff(v * kRsqrt2));
+                }
                 if (ex.dgelu != nullptr) {   // d GELU / dh = Phi(h) + h phi(h)
                     const float h = ex.dgelu[idx];
                     v *= 0.5f * (1.0f + erff(h * kRsqrt2)) + h * 0.39894228040143267794f * __expf(-0.5f * h * h);
                 }
                 if (ex.rowscale != nullptr) v *= ex.rowscale[row / ex.L];
                 if (R != nullptr) v += R[idx];
-                Y[idx] = v;
+                if constexpr (YB) bf16k::store_out<true>(Yv, idx, v);
+                else Y[idx] = v;
             }
         }
     }
@@ -272,26 +318,26 @@ int launch_linear(const float *X, const float *W, const float *bias, const float
 
 namespace {
 
-template <int MATH, class F>
-int launch_form(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta, float eps,
-                float *Y, int M, int K, int Nout, bool gelu, const LinearExtra &ex, hipStream_t st) {
+template <int MATH, class F, bool XB = false, bool YB = false>
+int launch_form(const void *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta, float eps,
+                void *Y, int M, int K, int Nout, bool gelu, const LinearExtra &ex, hipStream_t st) {
     const int tiles_n = ceil_div(Nout, F::BN);
     const long long tiles = (long long)tiles_n * ceil_div(M, F::BM);
     if (tiles > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit linear: %lld tiles", tiles);
-    vit_linear_kernel<MATH, F><<<dim3((unsigned)tiles), dim3(F::THREADS), 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout,
+    vit_linear_kernel<MATH, F, XB, YB><<<dim3((unsigned)tiles), dim3(F::THREADS), 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout,
                                                                                  tiles_n, gelu, ex);
     STGCN_LAUNCH_CHECK("vit_linear_kernel");
     return STGCN_OK;
 }
 
-template <int MATH>
-int launch_math(const LinearTile t, const float *X, const float *W, const float *bias, const float *R, const float *gamma,
-                const float *beta, float eps, float *Y, int M, int K, int Nout, bool gelu, const LinearExtra &ex, hipStream_t st) {
+template <int MATH, bool XB = false, bool YB = false>
+int launch_math(const LinearTile t, const void *X, const float *W, const float *bias, const float *R, const float *gamma,
+                const float *beta, float eps, void *Y, int M, int K, int Nout, bool gelu, const LinearExtra &ex, hipStream_t st) {
     static_assert(Form128::BM == 128 && Form128::BN == 128 && Form64::BM == 64 && Form64::BN == 64 && Form32::BM == 32 &&
                   Form32::BN == 64, "the forms linear_tile (vit.h) plans with");
-    if (t.bm == Form128::BM) return launch_form<MATH, Form128>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
-    if (t.bm == Form64::BM) return launch_form<MATH, Form64>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
-    return launch_form<MATH, Form32>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    if (t.bm == Form128::BM) return launch_form<MATH, Form128, XB, YB>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    if (t.bm == Form64::BM) return launch_form<MATH, Form64, XB, YB>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    return launch_form<MATH, Form32, XB, YB>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
 }
 
 }  // namespace
@@ -303,6 +349,20 @@ int launch_linear_ex(const float *X, const float *W, const float *bias, const fl
     if ((math & STGCN_MATH_MASK) == STGCN_MATH_F32)
         return launch_math<STGCN_MATH_F32>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
     return launch_math<STGCN_MATH_BF16X3>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+}
+
+int launch_linear_bf16(const void *X, bool x_bf16, const float *W, const float *bias, const float *R, const float *gamma,
+                       const float *beta, float eps, void *Y, bool y_bf16, int M, int K, int Nout, bool gelu, unsigned tile,
+                       hipStream_t st) {
+    if (x_bf16 && gamma != nullptr) return fail(STGCN_ERR_UNSUPPORTED, "vit linear (bf16): LayerNorm needs fp32 rows");
+    const LinearTile t = linear_tile(M, K, Nout, tile);
+    const LinearExtra ex{};
+    constexpr int B = STGCN_MATH_BF16;
+    if (x_bf16)
+        return y_bf16 ? launch_math<B, true, true>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st)
+                      : launch_math<B, true, false>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    return y_bf16 ? launch_math<B, false, true>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st)
+                  : launch_math<B, false, false>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
 }
 
 }  // namespace vit

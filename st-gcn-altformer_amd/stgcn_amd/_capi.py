@@ -37,6 +37,9 @@ VIT_TILE_MASK = 0x30000  # stgcn_vit_linear / stgcn_vit_block_forward: tile form
 VIT_TILE_AUTO = 0x10000  # the plan picks by workgroup count (stgcn_vit_linear_tile tells)
 VIT_TILE_64 = 0x20000  # force 64 x 64
 VIT_TILE_32 = 0x30000  # force the 32-row form (32 x 64)
+VIT_BF16 = 0x40000  # stgcn_vit_block_forward: the whole block on bf16 operands (inference, L <= 256); low math bits ignored
+VIT_X_BF16 = 0x80000  # stgcn_vit_linear_bf16: x is bf16 storage
+VIT_Y_BF16 = 0x100000  # stgcn_vit_linear_bf16: y is bf16 storage
 MATH_F16MX = MATH_BF16X3 | STEM_F16MX   # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
 
 STATUS = {0: "STGCN_OK", -1: "STGCN_ERR_ARG", -2: "STGCN_ERR_UNSUPPORTED",
@@ -88,6 +91,11 @@ PROTOTYPES = {
     "stgcn_vit_attention": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
     "stgcn_vit_attention_stream_supported": (c_int, [c_int] * 3),
     "stgcn_vit_attention_stream": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
+    "stgcn_vit_block_forward_bf16_supported": (c_int, [c_int] * 4),
+    "stgcn_vit_linear_bf16_supported": (c_int, [c_int] * 3 + [c_uint]),
+    "stgcn_vit_linear_bf16": (c_int, [_P] * 5 + [c_float] + [_P] * 2 + [c_int] * 3 + [c_uint, _P]),
+    "stgcn_vit_attention_bf16_supported": (c_int, [c_int] * 3),
+    "stgcn_vit_attention_bf16": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
     "stgcn_vit_block_supported": (c_int, [c_int] * 4),
     "stgcn_vit_block_forward_supported": (c_int, [c_int] * 4),
     "stgcn_vit_block_ws_bytes": (c_size_t, [c_int] * 4),

@@ -36,6 +36,9 @@ Two paths, one result:
 Arithmetic of the block's linears (``set_head_math`` / env ``STGCN_VIT_MATH``): ``'f32'`` (fp32 matrix cores, exact products),
 ``'bf16x3'`` (three bf16 products per fp32 product, fp32 accumulate) or ``'mixed'`` (bf16x3 with the qkv linear in f32: an
 error in q or k is multiplied by the size of the scores before the exponential).  The attention itself is always fp32.
+``'bf16'`` (opt-in, inference, sequences of up to 256 tokens) runs the whole block, attention included, on operands rounded to
+bf16 with fp32 accumulation, and keeps qkv, the attention output and the fc1 hidden in bf16 between the launches: 1e-2 of
+max|y| instead of 1e-4.  Longer sequences and training calls of such a block run in the default arithmetic of their path.
 
 Nothing is packed or cached: the kernels read ``nn.Linear.weight`` as stored, so an ``nn.DataParallel`` replica (whose
 parameters are plain attributes, fresh clones on every call) needs no staging on its master.
@@ -51,10 +54,10 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import functional as F
-from ._capi import MATH_BF16X3, MATH_F32, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK
+from ._capi import MATH_BF16X3, MATH_F32, VIT_BF16, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK
 from .modules import Unit2D, enable_stem_fusion, import_class, unit_agcn
 
-HEAD_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32}
+HEAD_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32, "bf16": VIT_BF16}
 DEFAULT_HEAD_MATH = "mixed"
 
 
@@ -132,7 +135,8 @@ def set_hip_train_min_tokens(module: nn.Module, tokens: int) -> None:
 
 
 def set_head_math(module: nn.Module, mode) -> None:
-    """Arithmetic of the linears of every ``Block`` below: 'f32' | 'bf16x3' | 'mixed', or None for the default."""
+    """Arithmetic of the linears of every ``Block`` below: 'f32' | 'bf16x3' | 'mixed' | 'bf16' (the whole block on bf16
+    operands: inference and L <= 256 only, anything else of such a block runs its path's default), or None for the default."""
     m = None if mode is None else HEAD_MATH[mode] if isinstance(mode, str) else int(mode)
     for sub in module.modules():
         if isinstance(sub, Block):
@@ -310,6 +314,8 @@ class Block(nn.Module):
         if self.uses_hip(x):
             a, m = self.attn, self.mlp
             math = _default_head_math() if self.math_mode is None else self.math_mode
+            if math & VIT_BF16 and not F.vit_block_forward_bf16_supported(x.shape[1], x.shape[2], a.num_heads, m.fc1.out_features):
+                math = HEAD_MATH[DEFAULT_HEAD_MATH] | (math & VIT_TILE_MASK)   # L > 256: the default arithmetic, still on HIP
             if self.small_tiles and not math & VIT_TILE_MASK:   # a form forced through math_mode stands
                 math |= VIT_TILE_AUTO
             with torch.no_grad():
@@ -320,6 +326,8 @@ class Block(nn.Module):
         if self.trains_on_hip(x):
             s1, s2 = self.draw_drop_path(x)
             math = _default_train_math() if self.math_mode is None else self.math_mode & ~VIT_TILE_MASK   # tile forms: inference only
+            if math & VIT_BF16:                 # an inference mode: the bit never reaches a training entry point
+                math = _default_train_math()
             return _BlockTrain.apply(x, None if s1 is None else s1.reshape(-1), None if s2 is None else s2.reshape(-1),
                                      self.attn.num_heads, self.norm1.eps, self.attn.scale, math, *self._weights())
         x = x + self.drop_path(self.attn(self.norm1(x)))

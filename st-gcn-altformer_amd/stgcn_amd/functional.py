@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _capi
-from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16  # noqa: F401 (re-export)
+from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_BF16  # noqa: F401 (re-export)
 
 BN_EPS = 1e-5
 
@@ -519,7 +519,7 @@ def st_attention_backward(x, dbn_weight, dbn_bias, Wqkv, Wout, bn_weight, bn_bia
 
 # ---- AltFormer heads: transformer block (stgcn_vit_*) ---------------------------------------------------------------------
 def _vit_flags(math: int) -> int:
-    return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32 | _capi.VIT_TILE_MASK)
+    return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32 | _capi.VIT_TILE_MASK | _capi.VIT_BF16)
 
 
 def _bytes(dev, nbytes):
@@ -562,6 +562,63 @@ def vit_linear(x, weight, bias=None, ln=None, residual=None, gelu=False, math=MA
                    _dev_ptr(lnw, "ln weight", dev), _dev_ptr(lnb, "ln bias", dev), c_float(eps),
                    _dev_ptr(residual, "residual", dev), _dev_ptr(y, "y", dev), c_int(M), c_int(K), c_int(Nout), c_uint(fl), _stream(dev))
     return y
+
+
+def vit_linear_bf16(x, weight, bias=None, ln=None, residual=None, gelu=False, y_bf16=False, tile=0, y=None) -> torch.Tensor:
+    """``vit_linear`` in the bf16 arithmetic of the ``VIT_BF16`` block mode: x and the weight rounded to nearest-even bf16 as
+    matrix-core operands, fp32 accumulate, LayerNorm / bias / GELU / residual in fp32.  x is float32 or ``torch.bfloat16``
+    (bf16 storage, read as it is; no ``ln`` then); the result is ``torch.bfloat16`` with ``y_bf16`` (or a bfloat16 ``y``),
+    else float32.  ``tile``: a ``VIT_TILE_*`` field (the result does not depend on it)."""
+    dev = x.device
+    K = x.shape[-1]
+    M = x.numel() // K
+    Nout = weight.shape[0]
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"x must be float32 or bfloat16 (got {x.dtype})")
+    if weight.shape[1] != K:
+        raise ValueError(f"weight is {tuple(weight.shape)}, x has {K} features")
+    if residual is not None and residual.numel() != M * Nout:
+        raise ValueError(f"residual has {residual.numel()} elements, expected {M * Nout}")
+    if y is None:
+        y = torch.empty(x.shape[:-1] + (Nout,), device=dev, dtype=torch.bfloat16 if y_bf16 else torch.float32)
+    elif y.shape != x.shape[:-1] + (Nout,) or y.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"y is {tuple(y.shape)} {y.dtype}, expected {tuple(x.shape[:-1]) + (Nout,)} float32 or bfloat16")
+    elif y.data_ptr() == x.data_ptr():
+        raise ValueError("y must not alias x")
+    lnw, lnb, eps = ln if ln is not None else (None, None, 0.0)
+    fl = (tile & _capi.VIT_TILE_MASK) | (_capi.VIT_GELU if gelu else 0) \
+        | (_capi.VIT_X_BF16 if x.dtype == torch.bfloat16 else 0) | (_capi.VIT_Y_BF16 if y.dtype == torch.bfloat16 else 0)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_linear_bf16", _dev_ptr(x, "x", dev, x.dtype), _dev_ptr(weight, "weight", dev),
+                   _dev_ptr(bias, "bias", dev), _dev_ptr(lnw, "ln weight", dev), _dev_ptr(lnb, "ln bias", dev), c_float(eps),
+                   _dev_ptr(residual, "residual", dev), _dev_ptr(y, "y", dev, y.dtype), c_int(M), c_int(K), c_int(Nout),
+                   c_uint(fl), _stream(dev))
+    return y
+
+
+def vit_attention_bf16_supported(L, heads, head_dim) -> bool:
+    return bool(_capi.lib().stgcn_vit_attention_bf16_supported(L, heads, head_dim))
+
+
+def vit_attention_bf16(qkv, heads, scale=None) -> torch.Tensor:
+    """``vit_attention`` (the resident form, L <= 256) on a ``torch.bfloat16`` packed qkv (B, L, 3*D); returns bfloat16
+    (B, L, D).  Scores, soft-max and sums in fp32; exp(s - max) is rounded to bf16 as the operand of P V."""
+    dev = qkv.device
+    B, L, D3 = qkv.shape
+    D = D3 // 3
+    hd = D // heads
+    if D * 3 != D3 or hd * heads != D:
+        raise ValueError(f"qkv is {tuple(qkv.shape)}: the last axis must be 3 * heads * head_dim (heads = {heads})")
+    out = torch.empty(B, L, D, device=dev, dtype=torch.bfloat16)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_attention_bf16", _dev_ptr(qkv, "qkv", dev, torch.bfloat16), _dev_ptr(out, "out", None, torch.bfloat16),
+                   c_int(B), c_int(L), c_int(heads), c_int(hd), c_float(hd ** -0.5 if scale is None else scale), _stream(dev))
+    return out
+
+
+def vit_block_forward_bf16_supported(L, D, heads, hidden) -> bool:
+    """What ``vit_block_forward`` runs with ``VIT_BF16``: the resident coverage (L <= 256)."""
+    return bool(_capi.lib().stgcn_vit_block_forward_bf16_supported(L, D, heads, hidden))
 
 
 def vit_attention_supported(L, heads, head_dim) -> bool:
@@ -616,7 +673,8 @@ def vit_block_forward_supported(L, D, heads, hidden) -> bool:
 def vit_block_forward(x, norm1, qkv, proj, norm2, fc1, fc2, heads, eps, scale, math=MATH_F32) -> torch.Tensor:
     """Eval forward of one transformer Block on x (B, L, D).  ``norm1`` / ``norm2`` = (weight, bias) of the LayerNorms (one
     ``eps``), ``qkv`` / ``proj`` / ``fc1`` / ``fc2`` = (weight, bias or None) of the nn.Linears as stored.  ``math``: MATH_F32
-    or MATH_BF16X3, optionally | VIT_QKV_F32, optionally | a VIT_TILE_* form for the four linears (same result, bit for bit)."""
+    or MATH_BF16X3, optionally | VIT_QKV_F32, optionally | a VIT_TILE_* form for the four linears (same result, bit for bit);
+    or VIT_BF16 (optionally | a VIT_TILE_* form): the whole block on bf16 operands, L <= 256 (``vit_block_forward_bf16_supported``)."""
     dev = x.device
     B, L, D = x.shape
     hidden = fc1[0].shape[0]

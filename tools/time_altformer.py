@@ -5,6 +5,7 @@ torch-op path of the same module, in one process, alternating, with device event
     python tools/time_altformer.py [--batch 32] [--repeats 7] [--warmup 2] [--tiles 128|auto|64|32|sweep]
                                    [--out profiles/altformer_times.json]
     python tools/time_altformer.py --frames 500 [--batch 32] [--out profiles/altformer_long_times.json]
+    python tools/time_altformer.py --math bf16 [--batch 32] [--out profiles/altformer_bf16_times.json]
 
 Prints ONE JSON line.  Per stage (a Block at the stage's shape, batch ``--batch``): ms of the HIP path (default arithmetic,
 and 'f32' / 'bf16x3' for comparison) and of the torch path (min, median, max over the repeats; ``spread`` = (max - min) / min of
@@ -24,6 +25,11 @@ and replayed.
 HIP against torch path with ``torch.cuda.max_memory_allocated`` of each; per launch the streaming kernel at L = T for head_dim
 32 and 64 next to the resident kernel at L = 256 in the same alternation (ms, TFLOP/s, their ratio); and the whole ST and TS
 models at ``num_frame = T``.
+
+``--math bf16`` times the opt-in bf16 block mode (``set_head_math(m, 'bf16')``) against the default arithmetic ('mixed') in the
+same alternation: per stage the block in both, per launch the five launches of both (the bf16 ones on the bf16 tensors the
+mode keeps between them), and the whole ST and TS models under the module's default policy.  Every ratio is median over
+median and comes with ``spread``, the larger (max - min) / min of the two rows, and ``bf16_faster_by_more_than_the_spread``.
 """
 import argparse
 import json
@@ -173,6 +179,98 @@ def long_clips(args):
     return res
 
 
+def bf16_mode(args):
+    """The ``--math bf16`` run (see the module docstring)."""
+    import stgcn_amd
+    from stgcn_amd import functional as F
+    from stgcn_amd.altformer import DEFAULT_HEAD_MATH, HEAD_MATH, Block, set_head_math
+    from functools import partial
+    dev = torch.device("cuda:0")
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    assert DEFAULT_HEAD_MATH == "mixed"
+    res = {"math": "bf16", "against": DEFAULT_HEAD_MATH, "batch": args.batch, "repeats": args.repeats, "warmup": args.warmup,
+           "device": torch.cuda.get_device_name(0), "stages": {}, "models": {}}
+
+    def versus(base, bf16):
+        spread = max(summary(base)["spread"], summary(bf16)["spread"])
+        return {"mixed_ms": summary(base), "bf16_ms": summary(bf16),
+                "mixed_over_bf16": round(statistics.median(base) / statistics.median(bf16), 3), "spread": round(spread, 4),
+                "bf16_faster_by_more_than_the_spread": faster_by_more_than_the_spread(bf16, base)}
+    with torch.no_grad():
+        for name, (per_clip, L, D) in STAGES.items():
+            B = args.batch * per_clip
+            M, hidden, heads = B * L, 2 * D, 8
+            torch.manual_seed(0)
+            blk = Block(D, heads, mlp_ratio=2., qkv_bias=True, norm_layer=norm).to(dev).eval()
+            x = torch.randn(B, L, D, device=dev)
+            blk.hip_min_tokens = 0
+
+            def run(mode):
+                set_head_math(blk, mode)
+                return blk(x)
+            ts = alternate({m: partial(run, m) for m in ("mixed", "bf16")}, args.repeats, args.warmup)
+            err = (run("bf16") - run("mixed")).abs().max().item() / run("mixed").abs().max().item()
+            a, m = blk.attn, blk.mlp
+            ln1, ln2 = (blk.norm1.weight, blk.norm1.bias, 1e-6), (blk.norm2.weight, blk.norm2.bias, 1e-6)
+            qkv = F.vit_linear(x, a.qkv.weight, a.qkv.bias, ln=ln1, math=F.MATH_F32)
+            att = F.vit_attention(qkv, heads, a.scale)
+            h = F.vit_linear(x, m.fc1.weight, m.fc1.bias, ln=ln2, gelu=True, math=F.MATH_BF16X3)
+            qkv_b, att_b, h_b = qkv.bfloat16(), att.bfloat16(), h.bfloat16()
+            parts = alternate({
+                "qkv mixed": lambda: F.vit_linear(x, a.qkv.weight, a.qkv.bias, ln=ln1, math=F.MATH_F32),
+                "qkv bf16": lambda: F.vit_linear_bf16(x, a.qkv.weight, a.qkv.bias, ln=ln1, y_bf16=True),
+                "attention mixed": lambda: F.vit_attention(qkv, heads, a.scale),
+                "attention bf16": lambda: F.vit_attention_bf16(qkv_b, heads, a.scale),
+                "proj mixed": lambda: F.vit_linear(att, a.proj.weight, a.proj.bias, residual=x, math=F.MATH_BF16X3),
+                "proj bf16": lambda: F.vit_linear_bf16(att_b, a.proj.weight, a.proj.bias, residual=x),
+                "fc1 mixed": lambda: F.vit_linear(x, m.fc1.weight, m.fc1.bias, ln=ln2, gelu=True, math=F.MATH_BF16X3),
+                "fc1 bf16": lambda: F.vit_linear_bf16(x, m.fc1.weight, m.fc1.bias, ln=ln2, gelu=True, y_bf16=True),
+                "fc2 mixed": lambda: F.vit_linear(h, m.fc2.weight, m.fc2.bias, residual=x, math=F.MATH_BF16X3),
+                "fc2 bf16": lambda: F.vit_linear_bf16(h_b, m.fc2.weight, m.fc2.bias, residual=x),
+            }, args.repeats, args.warmup)
+            flops = {"qkv": 2 * M * D * 3 * D, "attention": 4 * B * heads * L * L * (D // heads), "proj": 2 * M * D * D,
+                     "fc1": 2 * M * D * hidden, "fc2": 2 * M * hidden * D}
+            launches = {}
+            for k, fl in flops.items():
+                launches[k] = versus(parts[k + " mixed"], parts[k + " bf16"])
+                launches[k]["gflop"] = round(fl / 1e9, 3)
+                launches[k]["bf16_tflops"] = round(fl / (min(parts[k + " bf16"]) * 1e-3) / 1e12, 1)
+            res["stages"][name] = dict(versus(ts["mixed"], ts["bf16"]), B=B, L=L, D=D, tokens=M,
+                                       gflop=round(sum(flops.values()) / 1e9, 2), bf16_vs_mixed_max_err=float(f"{err:.3e}"),
+                                       launches=launches)
+            del x, blk, qkv, att, h, qkv_b, att_b, h_b
+            torch.cuda.empty_cache()
+        for style in ("ST", "TS"):
+            torch.manual_seed(1)
+            model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=22, style=style,
+                                               graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).eval()
+            clips = torch.randn(args.batch, 180, 22, 3, device=dev)
+
+            def run_model(mode):
+                set_head_math(model, mode)
+                return model(clips)
+            blocks = [b for b in model.modules() if isinstance(b, Block)]
+            calls = []
+            hooks = [b.register_forward_pre_hook(lambda mod, a: calls.append(bool(mod.uses_hip(a[0])))) for b in blocks]
+            run_model("bf16")
+            for hk in hooks:
+                hk.remove()
+            ts = alternate({m: partial(run_model, m) for m in ("mixed", "bf16")}, args.repeats, args.warmup)
+            lm, lb = run_model("mixed"), run_model("bf16")
+            res["models"][style] = dict(versus(ts["mixed"], ts["bf16"]), blocks_on_hip_default_policy=sum(calls), blocks=len(calls),
+                                        clips_per_s_mixed=round(args.batch / (statistics.median(ts["mixed"]) * 1e-3), 1),
+                                        clips_per_s_bf16=round(args.batch / (statistics.median(ts["bf16"]) * 1e-3), 1),
+                                        bf16_vs_mixed_max_logit_err=float(f"{(lb - lm).abs().max().item() / lm.abs().max().item():.3e}"),
+                                        argmax_equal=bool(torch.equal(lb.argmax(1), lm.argmax(1))))
+            del model, clips
+            torch.cuda.empty_cache()
+    big = [v for v in res["stages"].values() if v["tokens"] >= 100000]
+    res["stages_of_100k_tokens_and_more"] = len(big)
+    res["bf16_faster_at_all_of_them"] = all(v["bf16_faster_by_more_than_the_spread"] for v in big)
+    assert HEAD_MATH["bf16"] == F.VIT_BF16
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -180,11 +278,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tiles", choices=["128", "auto", "64", "32", "sweep"], default="128")
     ap.add_argument("--frames", type=int, default=None, help="time the long-clip stages at this many frames (> 256) instead")
+    ap.add_argument("--math", choices=["bf16"], default=None, help="time the opt-in bf16 block mode against the default arithmetic")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
-    if args.frames is not None:
-        line = json.dumps(long_clips(args))
+    if args.frames is not None or args.math is not None:
+        line = json.dumps(long_clips(args) if args.frames is not None else bf16_mode(args))
         if args.out:
             with open(args.out, "w") as f:
                 f.write(line + "\n")
