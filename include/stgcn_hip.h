@@ -438,7 +438,8 @@ int stgcn_vit_attention_bf16(const void *qkv, void *out, int B, int L, int heads
  * No atomics anywhere: reductions over the tokens are partial slabs added in a fixed order, two runs are bit-identical.
  * Arithmetic: `flags` as in the forward select f32 / bf16x3 for the dgrads (which run the forward's linear kernel on
  * transposed weights) and STGCN_VIT_QKV_F32 keeps the qkv dgrad in f32; weight gradients, LayerNorm and attention
- * backward always run in fp32 (v_mfma_f32_32x32x2_f32 where they are products). */
+ * backward always run in fp32 (v_mfma_f32_32x32x2_f32 where they are products).  STGCN_VIT_TRAIN_BF16 (at the end of this
+ * header, opt-in) moves the linears' products, weight gradients included, to bf16 operands. */
 #define STGCN_VIT_DGELU 0x4000u      /* stgcn_vit_linear_backward: dx is multiplied by GELU'(h_pre) (exact erf form)    */
 #define STGCN_VIT_ACCUMULATE 0x8000u /* stgcn_vit_linear_backward: dx += instead of dx =                                 */
 /* Backward of y = a W^T + b:  dx (M,K) = dy W [* GELU'(h_pre (M,K))] [+ dx],  dW (Nout,K) = dy^T a,  db (Nout) = column sums
@@ -493,6 +494,33 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
                              float *dWproj, float *dbproj, float *dnorm2_weight, float *dnorm2_bias, float *dW1, float *db1,
                              float *dW2, float *db2, float eps, float scale, void *ws, size_t ws_bytes, int B, int L, int D,
                              int heads, int hidden, unsigned flags, void *stream);
+
+/* ---- ViT block: training on bf16 matrix operands (additive to ABI 11: one flag bit and two queries; opt-in) -----------------
+ * STGCN_VIT_TRAIN_BF16 is accepted by exactly stgcn_vit_block_forward_train, stgcn_vit_block_backward and
+ * stgcn_vit_linear_backward.  With it every matrix product of a linear takes both operands rounded to nearest-even bf16 while
+ * they are staged (no packed or cached weight format) and accumulates in fp32 (v_mfma_f32_32x32x16_bf16):
+ *   forward proj, fc1, fc2 : r(A) r(W)^T, A = the attention output, LN2(x1), the GELU output as they are in fp32;
+ *   every dgrad, qkv's too : r(dY) r(W), the forward kernel on the transposed weight; GELU' and the row factor stay in the fp32
+ *                            epilogue, after the product;
+ *   every wgrad, qkv's too : dW = r(s dY)^T r(A), the row factor s applied before the rounding; THE BIAS GRADIENT SUMS THE
+ *                            UNROUNDED fp32 s dY.
+ * The one exception is the qkv FORWARD linear: it runs in the arithmetic of the low math bits (bf16x3, or f32 where the low bits
+ * or STGCN_VIT_QKV_F32 say so), because an error in q or k is multiplied by the size of the scores before the exponential.
+ * Everything that is not a linear's matrix operand is fp32 and the kernel it is without the bit: both LayerNorms forward and
+ * backward, the attention forward and backward (resident and streaming), bias adds, GELU and GELU', the stochastic-depth
+ * factors, residuals, every stored tensor.  `saved` and the workspace keep layout and size: every *_bytes query above answers
+ * for the mode too.  Results are bit-identical from run to run (no atomics, fixed summation order), as without the bit.
+ * The low bits must be STGCN_MATH_F32 or STGCN_MATH_BF16X3 as ever (else STGCN_ERR_UNSUPPORTED); STGCN_VIT_BF16 and a
+ * STGCN_VIT_TILE_* field keep their STGCN_ERR_ARG answers on the three entry points and are checked first.
+ * stgcn_vit_block_forward and stgcn_vit_linear answer STGCN_ERR_ARG to the bit.
+ * The training forward of this mode is NOT an inference mode's forward: STGCN_VIT_BF16 inference also rounds the qkv linear's
+ * operands, the soft-max weights and the stored intermediates, this mode none of them; its y differs from the default
+ * inference result by about 3e-4 of max|y|.  There is no inference twin.  Gate: 1e-2 of max|.| per tensor.
+ * Coverage: stgcn_vit_block_train_bf16_supported = stgcn_vit_block_train_long_supported (streaming lengths included);
+ * stgcn_vit_linear_backward_bf16_supported = stgcn_vit_linear_backward_supported with covered low bits. */
+#define STGCN_VIT_TRAIN_BF16 0x200000u
+int stgcn_vit_block_train_bf16_supported(int L, int D, int heads, int hidden);
+int stgcn_vit_linear_backward_bf16_supported(int M, int K, int Nout);
 
 #ifdef __cplusplus
 }

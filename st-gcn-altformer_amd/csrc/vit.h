@@ -93,7 +93,9 @@ inline int slab_seqs(int B, int L) {
 
 // Y (M, Nout) = act(LN?(X) W^T + bias) (+ R).  X (M, K), W (Nout, K), K % 32 == 0.  gamma / beta / eps: LayerNorm of X's
 // rows applied while the A tile is staged (gamma == nullptr: none).  math: STGCN_MATH_F32 or STGCN_MATH_BF16X3, optionally
-// with a STGCN_VIT_TILE_* field for linear_tile (every other bit must be clear).
+// with a STGCN_VIT_TILE_* field for linear_tile (every other bit must be clear).  launch_linear_ex also takes STGCN_MATH_BF16
+// (both operands rounded to nearest-even bf16 while staged, fp32 in memory on both sides): the training mode
+// STGCN_VIT_TRAIN_BF16 (vit_block_train.hip) is its only caller, the entry points' math_ok never lets it in from outside.
 // Y may alias R (each element is read and written by one thread); it must not alias X.
 int launch_linear(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
                   float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, hipStream_t st);
@@ -149,10 +151,19 @@ int launch_transpose_pad(const float *W, float *Wt, int rows, int cols, int rows
 // s = rowscale[row / L] or 1.  The reduction over M is cut into wgrad_splits(M, K, Nout) row ranges; each writes one slab of
 // `part` ((Nout * K) floats per split, then Nout floats per split for the bias) and launch_sum_parts adds them in split order.
 // fp32 matrix cores (v_mfma_f32_32x32x2_f32), no atomics.  `accumulate`: add onto dW / db (sum in `tmp` first).
+constexpr int kWgradChunk = 32;                       // tokens per LDS chunk of both wgrad kernels
+int wgrad_rows_per_split(int M, int K, int Nout);   // a multiple of kWgradChunk
 int wgrad_splits(int M, int K, int Nout);
 size_t wgrad_part_floats(int M, int K, int Nout);   // floats of `part`, and of `tmp` = Nout * K + Nout
 int launch_wgrad(const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part, float *tmp,
                  int M, int K, int Nout, bool accumulate, hipStream_t st);
+// partial slabs of n floats -> dst, or (accumulate) dst += their sum taken in `tmp`; slab order, no atomics
+int reduce_parts(const float *part, int parts, size_t n, float *dst, float *tmp, bool accumulate, hipStream_t st);
+// The same gradient in the STGCN_VIT_TRAIN_BF16 arithmetic (vit_wgrad_bf16.hip): dW = r(s dY)^T r(A) with r = round to
+// nearest-even bf16 applied while the operands are staged (after the row factor), fp32 accumulate on
+// v_mfma_f32_32x32x16_bf16; db sums the unrounded fp32 s dY.  Same splits, slabs, workspace and reduction as launch_wgrad.
+int launch_wgrad_bf16(const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part,
+                      float *tmp, int M, int K, int Nout, bool accumulate, hipStream_t st);
 
 // LayerNorm backward over the rows of x (M, D):  dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ dres),  g = dn * gamma; also
 // writes a = LN(x) (the input of the linear behind the LayerNorm, for its wgrad; may be NULL) and the rows' (mean, rstd) to

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void transpose_pad_kernel(const float *__restr
 }
 
 // ---- wgrad ----------------------------------------------------------------------------------------------------------------
-constexpr int WT = 128, WC = 32, WLD = 160;   // tile edge, tokens per chunk, LDS row stride (floats)
+constexpr int WT = 128, WC = kWgradChunk, WLD = 160;   // tile edge, tokens per chunk, LDS row stride (floats)
 
 __device__ __forceinline__ float4 load_row4(const float *p, int c, int width, bool vec) {
     if (c >= width) return make_float4(0.f, 0.f, 0.f, 0.f);
@@ -500,6 +500,8 @@ int launch_bwd_hd(const float *qkv, const float *out, const float *dout, float *
     return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward: L = %d (covered: 1 .. %d)", L, kMaxL);
 }
 
+}  // namespace
+
 // partial slabs -> dst, or dst += their sum
 int reduce_parts(const float *part, int parts, size_t n, float *dst, float *tmp, bool accumulate, hipStream_t st) {
     int rc;
@@ -508,8 +510,6 @@ int reduce_parts(const float *part, int parts, size_t n, float *dst, float *tmp,
     return launch_add_inplace(dst, tmp, n, st);
 }
 
-}  // namespace
-
 int launch_transpose_pad(const float *W, float *Wt, int rows, int cols, int rows_pad, hipStream_t st) {
     transpose_pad_kernel<<<dim3(ceil_div(cols, 32), ceil_div(rows_pad, 32)), dim3(256), 0, st>>>(W, Wt, rows, cols, rows_pad);
     STGCN_LAUNCH_CHECK("transpose_pad_kernel");
@@ -517,7 +517,7 @@ int launch_transpose_pad(const float *W, float *Wt, int rows, int cols, int rows
 }
 
 // About 512 workgroups (two per CU) where the rows allow it, a split at least 256 rows long, ranges multiples of the chunk.
-static int wgrad_rows_per_split(int M, int K, int Nout) {
+int wgrad_rows_per_split(int M, int K, int Nout) {
     const int tiles = ceil_div(Nout, WT) * ceil_div(K, WT);
     int splits = ceil_div(512, tiles);
     const int most = ceil_div(M, 256);

@@ -93,6 +93,9 @@ int stgcn_vit_linear_tile(int M, int K, int Nout, unsigned flags) {
 int stgcn_vit_linear(const float *x, const float *W, const float *bias, const float *ln_weight, const float *ln_bias,
                      float ln_eps, const float *residual, float *y, int M, int K, int Nout, unsigned flags,
                      void *stream) {
+    if (flags & STGCN_VIT_TRAIN_BF16)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_linear: STGCN_VIT_TRAIN_BF16 is a training mode (stgcn_vit_block_forward_train, "
+                    "stgcn_vit_block_backward, stgcn_vit_linear_backward only)");
     if (!x || !W || !y || M < 1 || K < 1 || Nout < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: null pointer or empty shape");
     if ((ln_weight == nullptr) != (ln_bias == nullptr)) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: ln_weight and ln_bias go together");
     if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: y must not alias x");
@@ -180,6 +183,9 @@ int stgcn_vit_block_forward(const float *x, const float *norm1_weight, const flo
                             const float *norm2_bias, const float *W1, const float *b1, const float *W2, const float *b2,
                             float eps, float scale, void *ws, size_t ws_bytes, float *y, int B, int L, int D, int heads,
                             int hidden, unsigned flags, void *stream) {
+    if (flags & STGCN_VIT_TRAIN_BF16)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: STGCN_VIT_TRAIN_BF16 is a training mode (stgcn_vit_block_forward_train, "
+                    "stgcn_vit_block_backward, stgcn_vit_linear_backward only)");
     if ((flags & STGCN_VIT_BF16) && (flags & STGCN_VIT_QKV_F32))
         return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward: STGCN_VIT_BF16 and STGCN_VIT_QKV_F32 exclude each other");
     if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !y || !ws)

@@ -13,6 +13,13 @@
 // The dgrads are the forward linear kernel on weights transposed once per call (f32 or bf16x3 like the forward); the
 // weight gradients run on the fp32 matrix cores.  Parameter gradients of the second and later slabs are added onto the
 // first slab's in slab order, so the result does not depend on anything but the shapes.
+//
+// STGCN_VIT_TRAIN_BF16 (opt-in): every matrix product of a linear - proj, fc1, fc2 forward, all four dgrads, all four
+// wgrads - takes both operands rounded to nearest-even bf16 while they are staged and accumulates in fp32
+// (v_mfma_f32_32x32x16_bf16: the linear kernel's bf16 arithmetic on fp32 memory, launch_wgrad_bf16).  The one exception is
+// the qkv FORWARD linear, which keeps the arithmetic of the low math bits (an error in q or k is multiplied by the size of
+// the scores).  LayerNorm, attention, bias, GELU / GELU', row factors, residuals, bias gradients and every stored tensor stay
+// fp32, and `saved` and the workspace keep their layouts (TrainMath below is the only thing the bit changes).
 #include "vit.h"
 
 namespace stgcn {
@@ -106,6 +113,26 @@ struct LnBwdWs {
     }
 };
 
+// The arithmetic of a training call, decided here and nowhere else.  Without STGCN_VIT_TRAIN_BF16: the low math bits for
+// everything but the wgrads (fp32), STGCN_VIT_QKV_F32 moving the qkv linear and its dgrad to f32.  With it: bf16 operands
+// for every product but the qkv forward linear, which stays what it would be without the bit.
+struct TrainMath {
+    unsigned lin, qkv_fwd, qkv_dgrad;
+    bool wgrad_bf16;
+    explicit TrainMath(unsigned flags) {
+        const unsigned low = flags & STGCN_MATH_MASK;
+        wgrad_bf16 = (flags & STGCN_VIT_TRAIN_BF16) != 0;
+        qkv_fwd = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : low;
+        lin = wgrad_bf16 ? (unsigned)STGCN_MATH_BF16 : low;
+        qkv_dgrad = wgrad_bf16 ? (unsigned)STGCN_MATH_BF16 : qkv_fwd;
+    }
+    int wgrad(const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part, float *tmp, int M,
+              int K, int Nout, bool accumulate, hipStream_t st) const {
+        return wgrad_bf16 ? launch_wgrad_bf16(dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st)
+                          : launch_wgrad(dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st);
+    }
+};
+
 bool linear_bwd_ok(int M, int K, int Nout, unsigned flags) {
     return M >= 1 && K >= 1 && Nout >= 1 && K % 32 == 0 && Nout % 4 == 0 && math_ok(flags);
 }
@@ -120,6 +147,8 @@ using namespace stgcn::vit;
 extern "C" {
 
 int stgcn_vit_linear_backward_supported(int M, int K, int Nout, unsigned flags) { return linear_bwd_ok(M, K, Nout, flags) ? 1 : 0; }
+
+int stgcn_vit_linear_backward_bf16_supported(int M, int K, int Nout) { return linear_bwd_ok(M, K, Nout, 0) ? 1 : 0; }
 
 size_t stgcn_vit_linear_backward_ws_bytes(int M, int K, int Nout) {
     if (!linear_bwd_ok(M, K, Nout, 0)) return 0;
@@ -142,6 +171,7 @@ int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, c
     const LinearBwdWs w(ws, M, K, Nout);
     if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_linear_backward: workspace %zu < %zu bytes", ws_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const TrainMath tm(flags);
     int rc;
     if (dx != nullptr) {
         if ((rc = launch_transpose_pad(W, w.wt, Nout, K, w.nout_pad, st))) return rc;
@@ -149,11 +179,10 @@ int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, c
         ex.dgelu = h_pre;
         ex.kx = Nout;
         const float *R = (flags & STGCN_VIT_ACCUMULATE) ? dx : nullptr;
-        if ((rc = launch_linear_ex(dy, w.wt, nullptr, R, nullptr, nullptr, 0.f, dx, M, w.nout_pad, K, false, flags & STGCN_MATH_MASK,
-                                   ex, st)))
+        if ((rc = launch_linear_ex(dy, w.wt, nullptr, R, nullptr, nullptr, 0.f, dx, M, w.nout_pad, K, false, tm.lin, ex, st)))
             return rc;
     }
-    if (dW != nullptr && (rc = launch_wgrad(dy, a, nullptr, 1, dW, db, w.part, w.tmp, M, K, Nout, false, st))) return rc;
+    if (dW != nullptr && (rc = tm.wgrad(dy, a, nullptr, 1, dW, db, w.part, w.tmp, M, K, Nout, false, st))) return rc;
     return STGCN_OK;
 }
 
@@ -229,6 +258,10 @@ int stgcn_vit_block_train_long_supported(int L, int D, int heads, int hidden) {
     return plan_block_train(L, D, heads, hidden) != BlockAttention::none ? 1 : 0;
 }
 
+int stgcn_vit_block_train_bf16_supported(int L, int D, int heads, int hidden) {
+    return plan_block_train(L, D, heads, hidden) != BlockAttention::none ? 1 : 0;
+}
+
 size_t stgcn_vit_block_train_long_saved_bytes(int B, int L, int D, int hidden) {
     if (B < 1 || L < 1 || D < 1 || hidden < 1 || D % 64 != 0 || hidden % 64 != 0 || L > kMaxStreamL) return 0;
     return BlockSaved(nullptr, B, L, D, hidden).total;
@@ -261,8 +294,8 @@ int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, con
     if (saved_bytes < sv.total)
         return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward_train: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned math = flags & STGCN_MATH_MASK;
-    const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : math;
+    const TrainMath tm(flags);
+    const unsigned math = tm.lin, math_qkv = tm.qkv_fwd;
     const int per = slab_seqs(B, L);
     for (int b0 = 0; b0 < B; b0 += per) {
         const int nb = B - b0 < per ? B - b0 : per;
@@ -319,8 +352,8 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
     if (ws_bytes < tw.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: workspace %zu < %zu bytes", ws_bytes, tw.total);
     const BackwardWs &w = tw.w;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned math = flags & STGCN_MATH_MASK;
-    const unsigned math_qkv = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : math;
+    const TrainMath tm(flags);
+    const unsigned math = tm.lin, math_qkv = tm.qkv_dgrad;
     int rc;
     if ((rc = launch_transpose_pad(Wqkv, w.wt_qkv, 3 * D, D, 3 * D, st))) return rc;
     if ((rc = launch_transpose_pad(Wproj, w.wt_proj, D, D, D, st))) return rc;
@@ -344,16 +377,16 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
         // MLP branch
         if ((rc = launch_linear_ex(dys, w.wt_fc2, nullptr, nullptr, nullptr, nullptr, 0.f, w.dhid, M, D, hidden, false, math, e2, st)))
             return rc;
-        if ((rc = launch_wgrad(dys, hid, s2, L, dW2, db2, w.part, w.tmp, M, hidden, D, acc, st))) return rc;
+        if ((rc = tm.wgrad(dys, hid, s2, L, dW2, db2, w.part, w.tmp, M, hidden, D, acc, st))) return rc;
         if ((rc = launch_linear(w.dhid, w.wt_fc1, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, hidden, D, false, math, st)))
             return rc;
         if ((rc = launch_ln_backward(x1, w.dn, norm2_weight, norm2_bias, eps, dys, w.dx1, w.a, w.stats, M, D, st))) return rc;
         if ((rc = launch_ln_param_grad(x1, w.dn, w.stats, dnorm2_weight, dnorm2_bias, w.part, w.tmp, M, D, acc, st))) return rc;
-        if ((rc = launch_wgrad(w.dhid, w.a, nullptr, L, dW1, db1, w.part, w.tmp, M, D, hidden, acc, st))) return rc;
+        if ((rc = tm.wgrad(w.dhid, w.a, nullptr, L, dW1, db1, w.part, w.tmp, M, D, hidden, acc, st))) return rc;
         // attention branch
         if ((rc = launch_linear_ex(w.dx1, w.wt_proj, nullptr, nullptr, nullptr, nullptr, 0.f, w.datt, M, D, D, false, math, e1, st)))
             return rc;
-        if ((rc = launch_wgrad(w.dx1, att, s1, L, dWproj, dbproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
+        if ((rc = tm.wgrad(w.dx1, att, s1, L, dWproj, dbproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
         rc = plan == BlockAttention::stream
                  ? launch_attention_backward_stream(qkv, att, w.datt, w.dqkv, tw.att_stats, nb, L, heads, D / heads, scale, st)
                  : launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st);
@@ -362,7 +395,7 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
             return rc;
         if ((rc = launch_ln_backward(xs, w.dn, norm1_weight, norm1_bias, eps, w.dx1, dx + r0 * D, w.a, w.stats, M, D, st))) return rc;
         if ((rc = launch_ln_param_grad(xs, w.dn, w.stats, dnorm1_weight, dnorm1_bias, w.part, w.tmp, M, D, acc, st))) return rc;
-        if ((rc = launch_wgrad(w.dqkv, w.a, nullptr, L, dWqkv, dbqkv, w.part, w.tmp, M, D, 3 * D, acc, st))) return rc;
+        if ((rc = tm.wgrad(w.dqkv, w.a, nullptr, L, dWqkv, dbqkv, w.part, w.tmp, M, D, 3 * D, acc, st))) return rc;
     }
     return STGCN_OK;
 }

@@ -348,6 +348,8 @@ int launch_linear_ex(const float *X, const float *W, const float *bias, const fl
     const LinearTile t = linear_tile(M, K, Nout, math);
     if ((math & STGCN_MATH_MASK) == STGCN_MATH_F32)
         return launch_math<STGCN_MATH_F32>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    if ((math & STGCN_MATH_MASK) == STGCN_MATH_BF16)   // the training mode STGCN_VIT_TRAIN_BF16: fp32 in memory on both sides
+        return launch_math<STGCN_MATH_BF16>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
     return launch_math<STGCN_MATH_BF16X3>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
 }
 

@@ -40,6 +40,13 @@ error in q or k is multiplied by the size of the scores before the exponential).
 bf16 with fp32 accumulation, and keeps qkv, the attention output and the fc1 hidden in bf16 between the launches: 1e-2 of
 max|y| instead of 1e-4.  Longer sequences and training calls of such a block run in the default arithmetic of their path.
 
+Arithmetic of the training path (``set_train_math`` / env ``STGCN_VIT_TRAIN_MATH``; ``HEAD_TRAIN_MATH``): the three above, or
+``'bf16'`` (opt-in): every matrix product of the four linears - forward, dgrad and weight gradient - on operands rounded to
+bf16 with fp32 accumulation, except the qkv forward linear, which runs in f32 for the reason ``'mixed'`` exists.  LayerNorm,
+attention, GELU, bias gradients and every stored tensor stay fp32; gradients hold 1e-2 of max|.| per tensor instead of 1e-4.
+A ``Block.train_math_mode`` that is not None wins over ``math_mode`` and the environment in the training branch only; this
+``'bf16'`` is not the inference ``'bf16'`` (which also rounds qkv, the soft-max weights and the stored intermediates).
+
 Nothing is packed or cached: the kernels read ``nn.Linear.weight`` as stored, so an ``nn.DataParallel`` replica (whose
 parameters are plain attributes, fresh clones on every call) needs no staging on its master.
 """
@@ -54,11 +61,20 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import functional as F
-from ._capi import MATH_BF16X3, MATH_F32, VIT_BF16, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK
+from ._capi import MATH_BF16X3, MATH_F32, VIT_BF16, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK, VIT_TRAIN_BF16
 from .modules import Unit2D, enable_stem_fusion, import_class, unit_agcn
 
 HEAD_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32, "bf16": VIT_BF16}
 DEFAULT_HEAD_MATH = "mixed"
+# the training path's modes: the three shared with inference, and 'bf16' = bf16 operands in every linear product but the qkv
+# forward.  Not HEAD_MATH['bf16'], which is an inference mode that a training entry point refuses.
+# The qkv forward of 'bf16' runs in f32 (VIT_QKV_F32), not in the bf16x3 the low bits name: the entry points accept both, and
+# both hold 1e-2 of max|.| (measured 4.2e-3 at worst either way), but the 2^-17 of a bf16x3 product, multiplied by the size
+# of the scores, moves enough gradients of the attention across a bf16 rounding boundary of the next product that the result
+# sits 0.40-0.49 of the rounding error away from the mode's fp64 emulation, in the L2 norm, against 0.12-0.28 with exact
+# products (DESIGN section 15 "bf16": the emulation with a bf16x3 qkv forward reproduces the 0.49 on the CPU).
+HEAD_TRAIN_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32,
+                   "bf16": VIT_TRAIN_BF16 | MATH_BF16X3 | VIT_QKV_F32}
 
 
 def _default_head_math() -> int:
@@ -72,7 +88,7 @@ DEFAULT_TRAIN_MATH = "f32"   # the fastest arithmetic whose gradients hold both 
 
 
 def _default_train_math() -> int:
-    return HEAD_MATH[os.environ.get("STGCN_VIT_TRAIN_MATH", DEFAULT_TRAIN_MATH).lower()]
+    return HEAD_TRAIN_MATH[os.environ.get("STGCN_VIT_TRAIN_MATH", DEFAULT_TRAIN_MATH).lower()]
 
 
 HIP_TRAIN_MIN_TOKENS = 13200   # forward + backward of a block (tools/time_altformer_train.py at batch 2, 4, 8, 32): every measured
@@ -141,6 +157,16 @@ def set_head_math(module: nn.Module, mode) -> None:
     for sub in module.modules():
         if isinstance(sub, Block):
             sub.math_mode = m
+
+
+def set_train_math(module: nn.Module, mode) -> None:
+    """Arithmetic of the HIP training path of every ``Block`` below: 'f32' | 'bf16x3' | 'mixed' | 'bf16' (``HEAD_TRAIN_MATH``;
+    'bf16': every linear product but the qkv forward on bf16 operands, opt-in, 1e-2 of max|.| per gradient tensor), or None
+    for what ``set_head_math`` / ``STGCN_VIT_TRAIN_MATH`` / ``DEFAULT_TRAIN_MATH`` give.  Inference is not touched."""
+    m = None if mode is None else HEAD_TRAIN_MATH[mode] if isinstance(mode, str) else int(mode)
+    for sub in module.modules():
+        if isinstance(sub, Block):
+            sub.train_math_mode = m
 
 
 class DropPath(nn.Module):
@@ -245,6 +271,7 @@ class Block(nn.Module):
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self.math_mode = None                  # None: _default_head_math() at call time
+        self.train_math_mode = None            # set_train_math: the training branch's arithmetic; None: as math_mode decides
         self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
         self.hip_min_tokens = HIP_MIN_TOKENS   # set_hip_min_tokens
         self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
@@ -328,6 +355,8 @@ class Block(nn.Module):
             math = _default_train_math() if self.math_mode is None else self.math_mode & ~VIT_TILE_MASK   # tile forms: inference only
             if math & VIT_BF16:                 # an inference mode: the bit never reaches a training entry point
                 math = _default_train_math()
+            if self.train_math_mode is not None:   # set_train_math wins
+                math = self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16)
             return _BlockTrain.apply(x, None if s1 is None else s1.reshape(-1), None if s2 is None else s2.reshape(-1),
                                      self.attn.num_heads, self.norm1.eps, self.attn.scale, math, *self._weights())
         x = x + self.drop_path(self.attn(self.norm1(x)))

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _capi
-from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_BF16  # noqa: F401 (re-export)
+from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_BF16, VIT_TRAIN_BF16  # noqa: F401 (re-export)
 
 BN_EPS = 1e-5
 
@@ -522,6 +522,11 @@ def _vit_flags(math: int) -> int:
     return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32 | _capi.VIT_TILE_MASK | _capi.VIT_BF16)
 
 
+def _vit_train_flags(math: int) -> int:
+    """What the training entry points read of ``math``: the inference bits (which they refuse by name) and VIT_TRAIN_BF16."""
+    return _vit_flags(math) | (math & _capi.VIT_TRAIN_BF16)
+
+
 def _bytes(dev, nbytes):
     return torch.empty((max(nbytes, 8) + 7) // 8, device=dev, dtype=torch.float64)
 
@@ -698,11 +703,17 @@ def vit_linear_backward_supported(M, K, Nout, math=MATH_F32) -> bool:
     return bool(_capi.lib().stgcn_vit_linear_backward_supported(M, K, Nout, math & _capi.MATH_MASK))
 
 
+def vit_linear_backward_bf16_supported(M, K, Nout) -> bool:
+    """What ``vit_linear_backward`` covers with ``VIT_TRAIN_BF16``."""
+    return bool(_capi.lib().stgcn_vit_linear_backward_bf16_supported(M, K, Nout))
+
+
 def vit_linear_backward(dy, a, weight, h_pre=None, dx_accumulate=None, need_dx=True, need_dw=True, need_db=True,
                         math=MATH_F32):
     """Backward of ``y = a W^T + b`` on the last axis: returns ``(dx, dW, db)`` (None where not asked for).
     ``dx = dy W``, multiplied by ``GELU'(h_pre)`` when ``h_pre`` (shape of ``a``) is given - the dgrad of the linear behind
-    a GELU whose input was ``h_pre`` - and added onto ``dx_accumulate`` (in place, returned) when that is given."""
+    a GELU whose input was ``h_pre`` - and added onto ``dx_accumulate`` (in place, returned) when that is given.
+    ``math | VIT_TRAIN_BF16``: both products on operands rounded to nearest-even bf16 (``db`` sums the unrounded ``dy``)."""
     dev = dy.device
     Nout, K = weight.shape
     M = dy.numel() // Nout
@@ -713,8 +724,8 @@ def vit_linear_backward(dy, a, weight, h_pre=None, dx_accumulate=None, need_dx=T
     db = torch.empty(Nout, device=dev, dtype=torch.float32) if need_dw and need_db else None
     nbytes = _capi.lib().stgcn_vit_linear_backward_ws_bytes(M, K, Nout)
     ws = _bytes(dev, nbytes)
-    fl = (math & (_capi.MATH_MASK | _capi.VIT_TILE_MASK)) | (_capi.VIT_DGELU if h_pre is not None and need_dx else 0) \
-        | (_capi.VIT_ACCUMULATE if dx_accumulate is not None else 0)
+    fl = (math & (_capi.MATH_MASK | _capi.VIT_TILE_MASK | _capi.VIT_TRAIN_BF16)) \
+        | (_capi.VIT_DGELU if h_pre is not None and need_dx else 0) | (_capi.VIT_ACCUMULATE if dx_accumulate is not None else 0)
     with torch.cuda.device(dev):
         _capi.call("stgcn_vit_linear_backward", _dev_ptr(dy, "dy", dev), _dev_ptr(a if need_dw else None, "a", dev),
                    _dev_ptr(weight, "weight", dev), _dev_ptr(h_pre if need_dx else None, "h_pre", dev), _dev_ptr(dx, "dx", dev),
@@ -795,6 +806,12 @@ def vit_block_train_long_supported(L, D, heads, hidden) -> bool:
     return bool(_capi.lib().stgcn_vit_block_train_long_supported(L, D, heads, hidden))
 
 
+def vit_block_train_bf16_supported(L, D, heads, hidden) -> bool:
+    """What ``vit_block_forward_train`` / ``vit_block_backward`` cover with ``VIT_TRAIN_BF16``: both ranges of
+    ``vit_block_train_long_supported``."""
+    return bool(_capi.lib().stgcn_vit_block_train_bf16_supported(L, D, heads, hidden))
+
+
 def _vit_block_train_bytes(B, L, D, heads, hidden):
     """(saved bytes, workspace bytes) of the training entry points.  The resident form's queries where they answer (L <= 256),
     the ``_long`` queries, which cover both ranges and answer the same there, for what those leave at 0."""
@@ -811,7 +828,9 @@ VIT_BLOCK_PARAMS = ("norm1.weight", "norm1.bias", "qkv.weight", "qkv.bias", "pro
 def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=None, scale2=None):
     """Training forward of one Block on x (B, L, D): returns ``(y, saved)``.  ``params``: the twelve tensors in the order of
     ``VIT_BLOCK_PARAMS`` (qkv.bias may be None).  ``scale1`` / ``scale2`` (B,): stochastic depth's per-sequence factors of the
-    attention and the MLP branch (None = 1).  ``saved`` is an opaque buffer for ``vit_block_backward``."""
+    attention and the MLP branch (None = 1).  ``saved`` is an opaque buffer for ``vit_block_backward``.
+    ``math``: MATH_F32 or MATH_BF16X3, optionally | VIT_QKV_F32, optionally | VIT_TRAIN_BF16 (every linear product but the qkv
+    forward on operands rounded to bf16; hand the same value to ``vit_block_backward``)."""
     dev = x.device
     B, L, D = x.shape
     hidden = params[8].shape[0]
@@ -823,7 +842,7 @@ def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=
                    *[_dev_ptr(p, n, dev) for n, p in zip(VIT_BLOCK_PARAMS, params)],
                    _dev_ptr(scale1, "scale1", dev), _dev_ptr(scale2, "scale2", dev), c_float(eps), c_float(scale),
                    c_void_p(saved.data_ptr()), c_size_t(nbytes), _dev_ptr(y, "y"), c_int(B), c_int(L), c_int(D), c_int(heads),
-                   c_int(hidden), c_uint(_vit_flags(math)), _stream(dev))
+                   c_int(hidden), c_uint(_vit_train_flags(math)), _stream(dev))
     return y, saved
 
 
@@ -848,5 +867,5 @@ def vit_block_backward(x, params, saved, dy, heads, eps, scale, math=MATH_F32, s
                    _dev_ptr(scale1, "scale1", dev), _dev_ptr(scale2, "scale2", dev), c_void_p(saved.data_ptr()), c_size_t(sbytes),
                    _dev_ptr(dy, "dy", dev), _dev_ptr(grads["x"], "dx"), *[_dev_ptr(grads[n], "d" + n) for n in VIT_BLOCK_PARAMS],
                    c_float(eps), c_float(scale), c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(B), c_int(L), c_int(D),
-                   c_int(heads), c_int(hidden), c_uint(_vit_flags(math)), _stream(dev))
+                   c_int(heads), c_int(hidden), c_uint(_vit_train_flags(math)), _stream(dev))
     return grads

@@ -14,6 +14,15 @@ depth on - the HIP training path against the torch-op path of the same module, i
 of the whole ST and TS models at ``num_frame = T``, each alternating ``set_long_training`` on and off in one process.  Off is
 the torch-op path such blocks take by default, with ``torch.cuda.max_memory_allocated`` of each.
 
+    python tools/time_altformer_train.py --train-math bf16 [--batch 32] [--out profiles/altformer_train_bf16_times.json]
+
+``--train-math bf16`` times the opt-in bf16 training arithmetic (``set_train_math(model, 'bf16')``) against the two it would
+replace, all three on the HIP training path, alternating in one process: forward + backward of one block at every stage and one
+training step of the whole ST and TS models in 'f32' (the default), 'bf16x3' and 'bf16', with medians, spread and
+``torch.cuda.max_memory_allocated``; and, per launch, the weight gradient (fp32 and bf16 kernel) and the dgrad (f32, bf16x3,
+bf16 form of the linear kernel) of the four linears of every stage through ``functional.vit_linear_backward``.
+``bf16_faster``: the bf16 median is below BOTH other medians by more than the largest of the three spreads.
+
 Prints ONE JSON line.  Per stage: ms of forward + backward (min, median, max, ``spread`` = (max - min) / min) of the torch
 path and of the HIP path in each arithmetic ('f32', 'mixed', 'bf16x3'), the speed-up of the default arithmetic, and
 ``hip_faster`` = the HIP median is below the torch median by more than the larger of the two spreads (the rule
@@ -107,6 +116,87 @@ def long_clips(args):
     return res
 
 
+TRAIN_MATH_MODES = ("f32", "bf16x3", "bf16")
+
+
+def train_math_bf16(args):
+    """The ``--train-math bf16`` run (see the module docstring)."""
+    import stgcn_amd
+    from stgcn_amd import functional as F
+    from stgcn_amd.altformer import DEFAULT_TRAIN_MATH, HEAD_TRAIN_MATH, Block, set_train_math
+    dev = torch.device("cuda:0")
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    res = {"train_math": "bf16", "batch": args.batch, "repeats": args.repeats, "default_train_math": DEFAULT_TRAIN_MATH,
+           "bf16_flags": HEAD_TRAIN_MATH["bf16"], "device": torch.cuda.get_device_name(0), "stages": {}, "launches": {}, "models": {}}
+
+    def entry(ts, mem, **more):
+        med = {k: statistics.median(v) for k, v in ts.items()}
+        margin = max(summary(v)["spread"] for v in ts.values())
+        return {**more, **{f"{m}_ms": summary(ts[m]) for m in TRAIN_MATH_MODES},
+                **{f"peak_mib_{m}": round(mem[m] / 2 ** 20, 1) for m in TRAIN_MATH_MODES},
+                "bf16_vs_f32": round(med["f32"] / med["bf16"], 3), "bf16_vs_bf16x3": round(med["bf16x3"] / med["bf16"], 3),
+                "bf16_faster": med["bf16"] * (1 + margin) < min(med["f32"], med["bf16x3"])}
+
+    for name, (per_clip, L, D) in STAGES.items():
+        B = args.batch * per_clip
+        torch.manual_seed(0)
+        blk = Block(D, 8, mlp_ratio=2., qkv_bias=True, drop_path=0.1, norm_layer=norm).to(dev).train()
+        blk.hip_train_min_tokens = 0
+        x = torch.randn(B, L, D, device=dev, requires_grad=True)
+        dy = torch.randn(B, L, D, device=dev)
+
+        def run(mode):
+            set_train_math(blk, mode)
+            assert blk.trains_on_hip(x)
+            x.grad = None
+            for p in blk.parameters():
+                p.grad = None
+            blk(x).backward(dy)
+        ts = alternate({m: partial(run, m) for m in TRAIN_MATH_MODES}, args.repeats, args.warmup)
+        mem = {m: peak_bytes(partial(run, m)) for m in TRAIN_MATH_MODES}
+        res["stages"][name] = entry(ts, mem, B=B, L=L, D=D, tokens=B * L)
+        del blk, x, dy
+        # the launches on their own: (M, K, Nout) of qkv, proj, fc1, fc2
+        M, per = B * L, {}
+        for lin, (K, Nout) in {"qkv": (D, 3 * D), "proj": (D, D), "fc1": (D, 2 * D), "fc2": (2 * D, D)}.items():
+            g = torch.Generator(device=dev).manual_seed(K + Nout)
+            gy = torch.randn(M, Nout, device=dev, generator=g)
+            a = torch.randn(M, K, device=dev, generator=g)
+            W = torch.randn(Nout, K, device=dev, generator=g) / K ** 0.5
+            h = torch.randn(M, K, device=dev, generator=g) if lin == "fc2" else None      # fc2's dgrad carries GELU'
+            forms = {"f32": F.MATH_F32, "bf16x3": F.MATH_BF16X3, "bf16": F.MATH_BF16X3 | F.VIT_TRAIN_BF16}
+            wg = alternate({m: partial(F.vit_linear_backward, gy, a, W, need_dx=False, math=forms[m]) for m in ("f32", "bf16")},
+                           args.repeats, args.warmup)
+            dg = alternate({m: partial(F.vit_linear_backward, gy, a, W, h_pre=h, need_dw=False, math=forms[m]) for m in forms},
+                           args.repeats, args.warmup)
+            per[lin] = {"M": M, "K": K, "Nout": Nout, **{f"wgrad_{m}_ms": summary(v) for m, v in wg.items()},
+                        **{f"dgrad_{m}_ms": summary(v) for m, v in dg.items()},
+                        "wgrad_bf16_vs_f32": round(statistics.median(wg["f32"]) / statistics.median(wg["bf16"]), 3),
+                        "dgrad_bf16_vs_f32": round(statistics.median(dg["f32"]) / statistics.median(dg["bf16"]), 3)}
+            del gy, a, W, h
+        res["launches"][name] = per
+        torch.cuda.empty_cache()
+    for style in () if args.stages_only else ("ST", "TS"):
+        torch.manual_seed(1)
+        model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=22, style=style,
+                                           graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).train()
+        clips = torch.randn(args.batch, 180, 22, 3, device=dev)
+        labels = torch.arange(args.batch, device=dev) % 14
+        ce = torch.nn.CrossEntropyLoss()
+
+        def step(mode):
+            set_train_math(model, mode)
+            model.zero_grad(set_to_none=True)
+            ce(model(clips), labels).backward()
+        ts = alternate({m: partial(step, m) for m in TRAIN_MATH_MODES}, args.repeats, args.warmup)
+        mem = {m: peak_bytes(partial(step, m)) for m in TRAIN_MATH_MODES}
+        res["models"][style] = entry(ts, mem, clips_per_s={m: round(args.batch / (statistics.median(ts[m]) * 1e-3), 1)
+                                                           for m in TRAIN_MATH_MODES})
+        del model, clips
+        torch.cuda.empty_cache()
+    return res
+
+
 def emit(res, out):
     line = json.dumps(res)
     if out:
@@ -122,9 +212,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--stages-only", action="store_true")
     ap.add_argument("--frames", type=int, default=None, help="time training at this many frames (> 256) instead")
+    ap.add_argument("--train-math", choices=["bf16"], default=None,
+                    help="time this opt-in training arithmetic against 'f32' and 'bf16x3' instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
+    if args.train_math is not None:
+        return emit(train_math_bf16(args), args.out)
     if args.frames is not None:
         return emit(long_clips(args), args.out)
     import stgcn_amd
