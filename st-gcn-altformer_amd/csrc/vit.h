@@ -1,5 +1,7 @@
-// Launchers of the AltFormer heads' transformer-block kernels (vit_linear.hip, vit_attention*.hip, vit_backward.hip) and the
-// coverage rules, shared by the entry points in vit_block.hip (inference) and vit_block_train.hip (training).
+// What the AltFormer heads' transformer block shares between its entry points (vit_block.hip: inference, vit_block_train.hip:
+// training): the plan of a block call (plan_block: what every entry point and every query reads to learn whether the flags are
+// legal, whether the shape is covered, and which kernels, arithmetic and storage the call runs), the forward's slab walker
+// (block_forward), and the launchers of the kernels (vit_linear.hip, vit_attention*.hip, vit_backward.hip, vit_wgrad_bf16.hip).
 // All launchers enqueue on `st` and return a stgcn_status.
 #pragma once
 
@@ -8,16 +10,23 @@
 namespace stgcn {
 namespace vit {
 
-constexpr int kMaxL = 256;      // longest sequence the resident attention kernel keeps on chip (and the training kernels' limit)
-constexpr int kMaxStreamL = STGCN_VIT_MAX_STREAM_L;   // longest sequence of the streaming attention kernel: a slab holds 8 of them
+constexpr int kMaxL = 256;      // longest sequence the resident attention kernels keep on chip
+constexpr int kMaxStreamL = STGCN_VIT_MAX_STREAM_L;   // longest sequence of the streaming attention kernels: a slab holds 8 of them
 constexpr int kStreamKeys = 64;       // keys per LDS stage of the streaming kernel (vit_attention_stream.hip)
 constexpr int kStreamQueries = 128;   // queries per workgroup there: four waves of 32
 
-// ---- what the entry points cover (vit_block.hip, vit_block_train.hip) ----
-// Long inputs are walked in slabs of whole sequences of about this many tokens (forward and backward alike).
+// Long inputs are walked in slabs of whole sequences of about this many tokens (forward and backward alike): the
+// intermediates of a slab (about 7 KB per token at D = 256) then stay within reach of the caches between the launches that
+// write and read them, and the inference workspace does not grow with the batch.
 constexpr int kSlabRows = 32768;
 constexpr int kMaxLnDim = 4096;   // longest row a LayerNorm is fused over
 
+inline int slab_seqs(int B, int L) {
+    const int s = kSlabRows / L;
+    return s < 1 ? 1 : (s > B ? B : s);
+}
+
+// ---- what the primitives cover ----
 inline bool math_ok(unsigned flags) {
     const unsigned m = flags & STGCN_MATH_MASK;
     return m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3;
@@ -25,7 +34,13 @@ inline bool math_ok(unsigned flags) {
 
 inline bool linear_ok(int K, int Nout, bool ln) { return K % 32 == 0 && Nout >= 1 && (!ln || K <= kMaxLnDim); }
 
-// ---- the linear's tile form, chosen here and nowhere else (launch_linear_ex and stgcn_vit_linear_tile read it) ----
+// the resident attention kernels (forward, bf16 forward, backward) and the streaming ones (forward, backward)
+inline bool attention_resident_ok(int L, int heads, int hd) { return L >= 1 && L <= kMaxL && heads >= 1 && (hd == 32 || hd == 64); }
+inline bool attention_stream_ok(int L, int heads, int hd) {
+    return L >= 1 && L <= kMaxStreamL && heads >= 1 && (hd == 32 || hd == 64);
+}
+
+// ---- the linear's tile form, chosen here and nowhere else (launch_linear and stgcn_vit_linear_tile read it) ----
 // vit_linear.hip has three forms of one kernel: 128 x 128 (4 waves, 2 x 2 blocks of 32 x 32 each), 64 x 64 (4 waves, one
 // block each) and 32 x 64 (2 waves, one block each).  All compute an element of Y with the same instructions in the same
 // order, so the choice moves time, never a bit of the result.
@@ -42,7 +57,7 @@ inline long long linear_tiles(int M, int Nout, LinearTile t) {
     return (long long)ceil_div(M, t.bm) * ceil_div(Nout, t.bn);
 }
 
-// `flags`: only the STGCN_VIT_TILE_MASK field is read (0: 128 x 128, today's behaviour and what training always runs).
+// `flags`: only the STGCN_VIT_TILE_MASK field is read (0: 128 x 128, what training always runs).
 inline LinearTile linear_tile(int M, int K, int Nout, unsigned flags) {
     (void)K;   // every form walks all of K in one workgroup
     switch (flags & STGCN_VIT_TILE_MASK) {
@@ -56,51 +71,128 @@ inline LinearTile linear_tile(int M, int K, int Nout, unsigned flags) {
     }
 }
 
-// The resident form: what the training entry points and stgcn_vit_block_supported cover.
-inline bool block_ok(int L, int D, int heads, int hidden) {
-    if (L < 1 || D < 1 || heads < 1 || hidden < 1 || D % heads != 0) return false;
-    const int hd = D / heads;
-    return (hd == 32 || hd == 64) && L <= kMaxL && D % 64 == 0 && hidden % 64 == 0 && D <= kMaxLnDim;
+// ---- the plan of a block call, decided here and nowhere else ----
+// A plain host function of (entry point, L, D, heads, hidden, flags).  The four entry points below and every stgcn_vit_block_*
+// query read it; none of them looks at a flag bit or compares a length again.
+enum class BlockEntry { forward, forward_train, backward, linear_backward };
+constexpr const char *kBlockEntryName[] = {"stgcn_vit_block_forward", "stgcn_vit_block_forward_train", "stgcn_vit_block_backward",
+                                           "stgcn_vit_linear_backward"};
+// resident (launch_attention_packed, launch_attention_backward): K and V of a (sequence, head) on chip, up to kMaxL tokens;
+// stream (launch_attention_stream, launch_attention_backward_stream): K and V in key tiles through LDS, above kMaxL and up to
+// kMaxStreamL; resident_bf16 (launch_attention_bf16): the resident form on bf16 qkv / out, STGCN_VIT_BF16 only.
+enum class BlockAttention { none, resident, stream, resident_bf16 };
+
+struct BlockPlan {
+    BlockEntry entry;
+    // The flags are not legal for this entry point (STGCN_ERR_ARG, answered before the pointers are looked at): why, or nullptr.
+    const char *refusal = nullptr;
+    // L, D and hidden fit the layouts (what a size query without `heads` can tell); `resident`: L is a length of the resident
+    // kernels, which is all that the older queries (stgcn_vit_block_supported, .._train_supported, .._saved_bytes,
+    // .._backward_ws_bytes) cover.
+    bool sized = false, resident = false;
+    // The shape and the low math bits are covered (else STGCN_ERR_UNSUPPORTED, answered after the pointers).  For
+    // linear_backward: the low math bits alone (its shape is the linear's own, L, D, heads and hidden are not read).
+    bool covered = false;
+    int max_len = 0;                 // the longest sequence this entry point takes with these flags
+    BlockAttention attention = BlockAttention::none;
+    // The arithmetic (a STGCN_MATH_* value) of each product of the four linears: the qkv forward, the three other forwards,
+    // the qkv dgrad, the three other dgrads; and whether the weight gradients take bf16 operands (launch_wgrad_bf16).
+    unsigned qkv_fwd = 0, lin_fwd = 0, qkv_dgrad = 0, lin_dgrad = 0;
+    bool wgrad_bf16 = false;
+    bool bf16_store = false;         // qkv, the attention output and the fc1 hidden are bf16 storage between the launches
+    unsigned tile = 0;               // the STGCN_VIT_TILE_* field the forward's linears get (training: 0, 128 x 128 only)
+};
+
+inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidden, unsigned flags) {
+    BlockPlan p;
+    p.entry = entry;
+    const unsigned low = flags & STGCN_MATH_MASK;
+    const bool inference = entry == BlockEntry::forward, bf16 = inference && (flags & STGCN_VIT_BF16) != 0;
+    if (inference) {
+        if (flags & STGCN_VIT_TRAIN_BF16)
+            p.refusal = "STGCN_VIT_TRAIN_BF16 is a training mode (stgcn_vit_block_forward_train, stgcn_vit_block_backward, "
+                        "stgcn_vit_linear_backward only)";
+        else if (bf16 && (flags & STGCN_VIT_QKV_F32))
+            p.refusal = "STGCN_VIT_BF16 and STGCN_VIT_QKV_F32 exclude each other";
+    } else if (flags & STGCN_VIT_BF16) {
+        p.refusal = "STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)";
+    } else if (flags & STGCN_VIT_TILE_MASK) {
+        p.refusal = "training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)";
+    }
+    // Arithmetic.  STGCN_VIT_QKV_F32 moves the qkv linear (and its dgrad) to f32: an error in q or k is multiplied by the size
+    // of the scores before the exponential.  STGCN_VIT_BF16 (inference): every product on operands rounded to bf16, the three
+    // intermediates that only feed matrix cores stored as bf16; the low bits are not read.  STGCN_VIT_TRAIN_BF16: bf16
+    // operands for every product of a linear (fp32 in memory on both sides) but the qkv FORWARD, which stays what it is
+    // without the bit, for the reason above.
+    p.wgrad_bf16 = !inference && (flags & STGCN_VIT_TRAIN_BF16) != 0;
+    p.bf16_store = bf16;
+    p.tile = inference ? flags & STGCN_VIT_TILE_MASK : 0;
+    p.qkv_fwd = bf16 ? (unsigned)STGCN_MATH_BF16 : (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : low;
+    p.lin_fwd = p.lin_dgrad = bf16 || p.wgrad_bf16 ? (unsigned)STGCN_MATH_BF16 : low;
+    p.qkv_dgrad = p.wgrad_bf16 ? (unsigned)STGCN_MATH_BF16 : p.qkv_fwd;
+    const bool low_ok = bf16 || math_ok(flags);
+    if (entry == BlockEntry::linear_backward) {
+        p.covered = low_ok;
+        return p;
+    }
+    // Coverage.  Everything about the block but its attention is length-agnostic; kSlabRows / kMaxStreamL = 8 whole sequences
+    // fit a slab.  The bf16 attention has a resident form only.
+    p.max_len = bf16 ? kMaxL : kMaxStreamL;
+    p.resident = L <= kMaxL;
+    p.sized = L >= 1 && L <= p.max_len && D >= 1 && hidden >= 1 && D % 64 == 0 && hidden % 64 == 0;
+    const bool heads_ok = heads >= 1 && D % heads == 0 && (D / heads == 32 || D / heads == 64) && D <= kMaxLnDim;
+    if (p.sized && heads_ok)
+        p.attention = bf16 ? BlockAttention::resident_bf16 : p.resident ? BlockAttention::resident : BlockAttention::stream;
+    p.covered = p.attention != BlockAttention::none && low_ok;
+    return p;
 }
 
-inline bool attention_stream_ok(int L, int heads, int hd) {
-    return L >= 1 && L <= kMaxStreamL && heads >= 1 && (hd == 32 || hd == 64);
+// The two answers an entry point gives from the plan alone: before its pointer checks, and after them.
+inline int block_refused(const BlockPlan &p) { return fail(STGCN_ERR_ARG, "%s: %s", kBlockEntryName[(int)p.entry], p.refusal); }
+inline int block_unsupported(const BlockPlan &p, int L, int D, int heads, int hidden, unsigned flags) {
+    if (p.bf16_store)
+        return fail(STGCN_ERR_UNSUPPORTED, "%s: L = %d, D = %d, heads = %d, hidden = %d with STGCN_VIT_BF16 (covered: head_dim "
+                    "32 / 64, L <= %d, D and hidden multiples of 64)", kBlockEntryName[(int)p.entry], L, D, heads, hidden, p.max_len);
+    return fail(STGCN_ERR_UNSUPPORTED, "%s: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, L <= %d, "
+                "D and hidden multiples of 64, f32 / bf16x3)", kBlockEntryName[(int)p.entry], L, D, heads, hidden,
+                flags & STGCN_MATH_MASK, p.max_len);
 }
 
-// ---- the inference block's attention launch, chosen here and nowhere else (stgcn_vit_block_forward and
-// stgcn_vit_block_forward_supported read it) ----
-// resident up to kMaxL, exactly as before the streaming kernel existed (bit-identical results); streaming above, up to
-// kMaxStreamL: kSlabRows / kMaxStreamL = 8 whole sequences still fit a slab.  Everything else about the block is length-agnostic.
-enum class BlockAttention { none, resident, stream };
-inline BlockAttention plan_block_forward(int L, int D, int heads, int hidden) {
-    if (block_ok(L, D, heads, hidden)) return BlockAttention::resident;
-    if (L > kMaxL && L <= kMaxStreamL && block_ok(kMaxL, D, heads, hidden)) return BlockAttention::stream;
-    return BlockAttention::none;
-}
+// The parameters of a block as the forward reads them (nn.Linear.weight as stored; a bias may be NULL).
+struct BlockWeights {
+    const float *norm1_weight, *norm1_bias, *Wqkv, *bqkv, *Wproj, *bproj, *norm2_weight, *norm2_bias, *W1, *b1, *W2, *b2;
+    bool present() const { return norm1_weight && norm1_bias && Wqkv && Wproj && norm2_weight && norm2_bias && W1 && W2; }
+};
 
-// ---- the training block's attention launches, chosen here and nowhere else (stgcn_vit_block_forward_train,
-// stgcn_vit_block_backward and the stgcn_vit_block_train_long_* queries read it) ----
-// One form for the forward and the backward of a block: resident (launch_attention_packed, launch_attention_backward) up to
-// kMaxL, exactly as before the streaming backward existed; stream (launch_attention_stream,
-// launch_attention_backward_stream) above.  Today the cut is the inference block's; it is a function of its own because
-// it decides other kernels, and a measurement may move one cut without the other.
-inline BlockAttention plan_block_train(int L, int D, int heads, int hidden) { return plan_block_forward(L, D, heads, hidden); }
+// Where the forward's intermediates live: one slab's rows in the caller's workspace, reused by every slab (inference), or the
+// whole batch's in `saved`, where the backward reads them (training: 9 D floats per token at hidden = 2 D, h_pre = the fc1
+// output before the GELU included).  One carve for both, in this order; run on a NULL base it sizes the buffer.  The bf16
+// pieces are at most as large as the fp32 ones, so the bf16 mode fits what stgcn_vit_block_ws_bytes sizes.
+struct BlockStore {
+    void *qkv, *att, *hid;      // fp32, or bf16 storage where the plan says so
+    float *x1, *hpre;           // hpre: NULL in the workspace
+    bool per_slab;
+    size_t total;
+    BlockStore(void *base, const BlockPlan &plan, int B, int L, int D, int hidden) : per_slab(plan.entry == BlockEntry::forward) {
+        const size_t rows = (size_t)(per_slab ? slab_seqs(B, L) : B) * L, es = plan.bf16_store ? 2 : 4;
+        Carve c(base);
+        qkv = c.take<char>(rows * 3 * D * es);
+        att = c.take<char>(rows * D * es);
+        x1 = c.take<float>(rows * D);
+        hpre = per_slab ? nullptr : c.take<float>(rows * hidden);
+        hid = c.take<char>(rows * hidden * es);
+        total = c.off;
+    }
+};
 
-inline int slab_seqs(int B, int L) {
-    const int s = kSlabRows / L;
-    return s < 1 ? 1 : (s > B ? B : s);
-}
+// The forward of one block, the one loop that every forward entry point runs: five launches per slab of whole sequences,
+//   qkv = LN1(x) Wqkv^T + b -> attention -> x1 = s1 (a Wproj^T + b) + x -> h = GELU(LN2(x1) W1^T + b1) -> y = s2 (h W2^T + b2) + x1
+// (both LayerNorms inside the linear that consumes them), with the kernels, arithmetic and storage of `plan`, the
+// intermediates in `store`, and stochastic depth's per-sequence factors scale1 / scale2 (B floats each, or NULL = 1).
+int block_forward(const BlockPlan &plan, const float *x, const BlockWeights &w, const BlockStore &store, const float *scale1,
+                  const float *scale2, float eps, float scale, float *y, int B, int L, int D, int heads, int hidden, hipStream_t st);
 
-// Y (M, Nout) = act(LN?(X) W^T + bias) (+ R).  X (M, K), W (Nout, K), K % 32 == 0.  gamma / beta / eps: LayerNorm of X's
-// rows applied while the A tile is staged (gamma == nullptr: none).  math: STGCN_MATH_F32 or STGCN_MATH_BF16X3, optionally
-// with a STGCN_VIT_TILE_* field for linear_tile (every other bit must be clear).  launch_linear_ex also takes STGCN_MATH_BF16
-// (both operands rounded to nearest-even bf16 while staged, fp32 in memory on both sides): the training mode
-// STGCN_VIT_TRAIN_BF16 (vit_block_train.hip) is its only caller, the entry points' math_ok never lets it in from outside.
-// Y may alias R (each element is read and written by one thread); it must not alias X.
-int launch_linear(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
-                  float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, hipStream_t st);
-
-// What the training forward and the backward add to the linear (all optional, zero-initialised = the plain linear above):
+// What the training forward and the backward add to the linear (all optional, zero-initialised = the plain linear):
 //   pre      : the value before the activation, acc + bias, is also stored here (M, Nout)           [forward_train: h_pre]
 //   dgelu    : the result is multiplied by GELU'(dgelu[row][col]), exact erf form                   [dgrad of fc2]
 //   rowscale : then by rowscale[row / L] (stochastic depth: one factor per sequence), before R is added
@@ -112,9 +204,16 @@ struct LinearExtra {
     int L = 1;
     int kx = 0;
 };
-int launch_linear_ex(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
-                     float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, const LinearExtra &ex,
-                     hipStream_t st);
+// Y (M, Nout) = act(LN?(X) W^T + bias) (+ R).  X (M, K), W (Nout, K), K % 32 == 0.  gamma / beta / eps: LayerNorm of X's
+// rows applied while the A tile is staged (gamma == nullptr: none).  The one host launcher of vit_linear.hip.  `mode`:
+//   a STGCN_MATH_* value: F32, BF16X3, or BF16 (both operands rounded to nearest-even bf16 while staged, fp32 accumulate;
+//     only the plan's two bf16 modes and stgcn_vit_linear_bf16 hand it in, the entry points' math_ok never lets it in from outside)
+//   | a STGCN_VIT_TILE_* field for linear_tile
+//   | STGCN_VIT_X_BF16, STGCN_VIT_Y_BF16 (BF16 arithmetic only): X (no LayerNorm then) / Y is bf16 storage, else fp32.
+// W, bias, R, gamma, beta are fp32.  Y may alias R (each element is read and written by one thread); it must not alias X.
+int launch_linear(const void *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
+                  float eps, void *Y, int M, int K, int Nout, bool gelu, unsigned mode, hipStream_t st,
+                  const LinearExtra &ex = LinearExtra{});
 
 // out (B, L, H*hd) = softmax(scale * q k^T) v per (sequence, head) of the packed qkv (B, L, 3, H, hd); hd in {32, 64},
 // L <= kMaxL: K and V of a pair resident in LDS, the whole score row in registers (vit_attention.hip).
@@ -122,17 +221,6 @@ int launch_attention_packed(const float *qkv, float *out, int B, int L, int H, i
 // The same result up to the summation order for L <= kMaxStreamL: K and V streamed through LDS in tiles of kStreamKeys keys
 // under a running soft-max, kStreamQueries queries of a pair per workgroup (vit_attention_stream.hip).
 int launch_attention_stream(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
-
-// ---- the bf16 mode of the inference block (STGCN_VIT_BF16; vit_block.hip) -------------------------------------------------
-// Operands rounded to nearest-even bf16, fp32 accumulate; qkv, the attention output and the fc1 hidden live in the workspace
-// as bf16 (each is read by one consumer, as a matrix-core operand only).  Inference, resident attention form only.
-inline bool block_bf16_ok(int L, int D, int heads, int hidden) { return block_ok(L, D, heads, hidden); }
-
-// The linear in the bf16 arithmetic (vit_linear.hip): X fp32 (rounded while staged, after the LayerNorm if any) or bf16
-// storage (no LayerNorm then), Y fp32 or bf16 storage; W, bias, R, gamma, beta fp32.  `tile`: a STGCN_VIT_TILE_* field.
-int launch_linear_bf16(const void *X, bool x_bf16, const float *W, const float *bias, const float *R, const float *gamma,
-                       const float *beta, float eps, void *Y, bool y_bf16, int M, int K, int Nout, bool gelu, unsigned tile,
-                       hipStream_t st);
 
 // The resident attention on bf16 qkv / out (vit_attention_bf16.hip); L <= kMaxL, hd in {32, 64}.  Its LDS per workgroup:
 // K as [keys][hd + 8] and V transposed as [hd][keys + 8], keys = L rounded up to 32, for the pairs a workgroup packs.

@@ -7,19 +7,14 @@
 //   dn   = dhid W1                              LN2 backward: dx1 = dy + ...,  a = LN2(x1),  dnorm2
 //                                               dW1, db1   = dhid^T a
 //   datt = (s1 dx1) Wproj                       dWproj, dbproj = (s1 dx1)^T att
-//   dqkv = attention backward(qkv, att, datt)     resident up to 256 tokens, streaming above (plan_block_train)
+//   dqkv = attention backward(qkv, att, datt)     resident up to 256 tokens, streaming above
 //   dn   = dqkv Wqkv                            LN1 backward: dx = dx1 + ...,  a = LN1(x),   dnorm1
 //                                               dWqkv, dbqkv = dqkv^T a
-// The dgrads are the forward linear kernel on weights transposed once per call (f32 or bf16x3 like the forward); the
-// weight gradients run on the fp32 matrix cores.  Parameter gradients of the second and later slabs are added onto the
-// first slab's in slab order, so the result does not depend on anything but the shapes.
-//
-// STGCN_VIT_TRAIN_BF16 (opt-in): every matrix product of a linear - proj, fc1, fc2 forward, all four dgrads, all four
-// wgrads - takes both operands rounded to nearest-even bf16 while they are staged and accumulates in fp32
-// (v_mfma_f32_32x32x16_bf16: the linear kernel's bf16 arithmetic on fp32 memory, launch_wgrad_bf16).  The one exception is
-// the qkv FORWARD linear, which keeps the arithmetic of the low math bits (an error in q or k is multiplied by the size of
-// the scores).  LayerNorm, attention, bias, GELU / GELU', row factors, residuals, bias gradients and every stored tensor stay
-// fp32, and `saved` and the workspace keep their layouts (TrainMath below is the only thing the bit changes).
+// The dgrads are the forward linear kernel on weights transposed once per call; the weight gradients run on the fp32
+// matrix cores, or on bf16 operands with STGCN_VIT_TRAIN_BF16.  Which arithmetic each product takes and which attention form
+// runs is vit.h's plan_block; LayerNorm, attention, bias, GELU / GELU', row factors, residuals, bias gradients and every
+// stored tensor are fp32 in every mode, so `saved` and the workspace have one layout.  Parameter gradients of the second and
+// later slabs are added onto the first slab's in slab order, so the result does not depend on anything but the shapes.
 #include "vit.h"
 
 namespace stgcn {
@@ -27,22 +22,6 @@ namespace vit {
 namespace {
 
 size_t max2(size_t a, size_t b) { return a > b ? a : b; }
-
-// what the training forward keeps for the backward, whole batch: 9 D floats per token at hidden = 2 D
-struct BlockSaved {
-    float *qkv, *att, *x1, *hpre, *hid;
-    size_t total;
-    BlockSaved(void *base, int B, int L, int D, int hidden) {
-        const size_t rows = (size_t)B * L;
-        Carve c(base);
-        qkv = c.take<float>(rows * 3 * D);
-        att = c.take<float>(rows * D);
-        x1 = c.take<float>(rows * D);
-        hpre = c.take<float>(rows * hidden);
-        hid = c.take<float>(rows * hidden);
-        total = c.off;
-    }
-};
 
 // the backward's temporaries: one slab of gradients, the four transposed weights, the partial sums of one reduction
 struct BackwardWs {
@@ -79,10 +58,10 @@ struct TrainWs {
     BackwardWs w;
     float *att_stats = nullptr;
     size_t total;
-    TrainWs(void *base, BlockAttention plan, int B, int L, int D, int heads, int hidden) : w(base, B, L, D, hidden) {
+    TrainWs(void *base, const BlockPlan &plan, int B, int L, int D, int heads, int hidden) : w(base, B, L, D, hidden) {
         Carve c(base);
         c.off = w.total;
-        if (plan == BlockAttention::stream) att_stats = c.take<float>(attention_stats_floats(slab_seqs(B, L), L, heads));
+        if (plan.attention == BlockAttention::stream) att_stats = c.take<float>(attention_stats_floats(slab_seqs(B, L), L, heads));
         total = c.off;
     }
 };
@@ -113,29 +92,14 @@ struct LnBwdWs {
     }
 };
 
-// The arithmetic of a training call, decided here and nowhere else.  Without STGCN_VIT_TRAIN_BF16: the low math bits for
-// everything but the wgrads (fp32), STGCN_VIT_QKV_F32 moving the qkv linear and its dgrad to f32.  With it: bf16 operands
-// for every product but the qkv forward linear, which stays what it would be without the bit.
-struct TrainMath {
-    unsigned lin, qkv_fwd, qkv_dgrad;
-    bool wgrad_bf16;
-    explicit TrainMath(unsigned flags) {
-        const unsigned low = flags & STGCN_MATH_MASK;
-        wgrad_bf16 = (flags & STGCN_VIT_TRAIN_BF16) != 0;
-        qkv_fwd = (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : low;
-        lin = wgrad_bf16 ? (unsigned)STGCN_MATH_BF16 : low;
-        qkv_dgrad = wgrad_bf16 ? (unsigned)STGCN_MATH_BF16 : qkv_fwd;
-    }
-    int wgrad(const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part, float *tmp, int M,
-              int K, int Nout, bool accumulate, hipStream_t st) const {
-        return wgrad_bf16 ? launch_wgrad_bf16(dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st)
-                          : launch_wgrad(dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st);
-    }
-};
-
-bool linear_bwd_ok(int M, int K, int Nout, unsigned flags) {
-    return M >= 1 && K >= 1 && Nout >= 1 && K % 32 == 0 && Nout % 4 == 0 && math_ok(flags);
+// the weight gradient in the arithmetic of the plan
+int wgrad(const BlockPlan &plan, const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part,
+          float *tmp, int M, int K, int Nout, bool accumulate, hipStream_t st) {
+    return plan.wgrad_bf16 ? launch_wgrad_bf16(dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st)
+                           : launch_wgrad(dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st);
 }
+
+bool linear_bwd_ok(int M, int K, int Nout) { return M >= 1 && K >= 1 && Nout >= 1 && K % 32 == 0 && Nout % 4 == 0; }
 
 }  // namespace
 }  // namespace vit
@@ -146,32 +110,33 @@ using namespace stgcn::vit;
 
 extern "C" {
 
-int stgcn_vit_linear_backward_supported(int M, int K, int Nout, unsigned flags) { return linear_bwd_ok(M, K, Nout, flags) ? 1 : 0; }
+int stgcn_vit_linear_backward_supported(int M, int K, int Nout, unsigned flags) {
+    return linear_bwd_ok(M, K, Nout) && math_ok(flags) ? 1 : 0;
+}
 
-int stgcn_vit_linear_backward_bf16_supported(int M, int K, int Nout) { return linear_bwd_ok(M, K, Nout, 0) ? 1 : 0; }
+int stgcn_vit_linear_backward_bf16_supported(int M, int K, int Nout) { return linear_bwd_ok(M, K, Nout) ? 1 : 0; }
 
 size_t stgcn_vit_linear_backward_ws_bytes(int M, int K, int Nout) {
-    if (!linear_bwd_ok(M, K, Nout, 0)) return 0;
+    if (!linear_bwd_ok(M, K, Nout)) return 0;
     return LinearBwdWs(nullptr, M, K, Nout).total;
 }
 
 int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, const float *h_pre, float *dx, float *dW,
                               float *db, void *ws, size_t ws_bytes, int M, int K, int Nout, unsigned flags, void *stream) {
-    if (flags & STGCN_VIT_BF16) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)");
-    if (flags & STGCN_VIT_TILE_MASK) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)");
+    const BlockPlan plan = plan_block(BlockEntry::linear_backward, 0, 0, 0, 0, flags);   // the flags' part of it: no block shape here
+    if (plan.refusal) return block_refused(plan);
     if (!dy || !ws || M < 1 || K < 1 || Nout < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: null pointer or empty shape");
     if ((dx != nullptr && !W) || (dW != nullptr && !a) || (db != nullptr && !dW))
         return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: dx needs W, dW needs a, db goes with dW");
     if (((flags & STGCN_VIT_DGELU) != 0) != (h_pre != nullptr))
         return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: h_pre and STGCN_VIT_DGELU go together");
     if (dx == dy) return fail(STGCN_ERR_ARG, "stgcn_vit_linear_backward: dx must not alias dy");
-    if (!linear_bwd_ok(M, K, Nout, flags))
+    if (!linear_bwd_ok(M, K, Nout) || !plan.covered)
         return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_linear_backward: K = %d, Nout = %d, math %u (covered: K %% 32 == 0, Nout %% 4 == 0, "
                     "f32 / bf16x3)", K, Nout, flags & STGCN_MATH_MASK);
     const LinearBwdWs w(ws, M, K, Nout);
     if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_linear_backward: workspace %zu < %zu bytes", ws_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const TrainMath tm(flags);
     int rc;
     if (dx != nullptr) {
         if ((rc = launch_transpose_pad(W, w.wt, Nout, K, w.nout_pad, st))) return rc;
@@ -179,15 +144,15 @@ int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, c
         ex.dgelu = h_pre;
         ex.kx = Nout;
         const float *R = (flags & STGCN_VIT_ACCUMULATE) ? dx : nullptr;
-        if ((rc = launch_linear_ex(dy, w.wt, nullptr, R, nullptr, nullptr, 0.f, dx, M, w.nout_pad, K, false, tm.lin, ex, st)))
+        if ((rc = launch_linear(dy, w.wt, nullptr, R, nullptr, nullptr, 0.f, dx, M, w.nout_pad, K, false, plan.lin_dgrad, st, ex)))
             return rc;
     }
-    if (dW != nullptr && (rc = tm.wgrad(dy, a, nullptr, 1, dW, db, w.part, w.tmp, M, K, Nout, false, st))) return rc;
+    if (dW != nullptr && (rc = wgrad(plan, dy, a, nullptr, 1, dW, db, w.part, w.tmp, M, K, Nout, false, st))) return rc;
     return STGCN_OK;
 }
 
 int stgcn_vit_attention_backward_supported(int L, int heads, int head_dim) {
-    return L >= 1 && L <= kMaxL && heads >= 1 && (head_dim == 32 || head_dim == 64) ? 1 : 0;
+    return attention_resident_ok(L, heads, head_dim) ? 1 : 0;
 }
 
 int stgcn_vit_attention_backward(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int heads,
@@ -242,35 +207,39 @@ int stgcn_vit_layernorm_backward(const float *x, const float *dn, const float *w
     return launch_ln_param_grad(x, dn, w.stats, dweight, dbias, w.part, w.tmp, M, D, false, st);
 }
 
-int stgcn_vit_block_train_supported(int L, int D, int heads, int hidden) { return block_ok(L, D, heads, hidden) ? 1 : 0; }
+// The size queries without `heads` ask the plan with none: they read what L, D and hidden alone decide.  The _long queries
+// answer what the older, resident-only ones answer at L <= 256, and go on where those answer 0.
+int stgcn_vit_block_train_supported(int L, int D, int heads, int hidden) {
+    const BlockPlan p = plan_block(BlockEntry::forward_train, L, D, heads, hidden, 0);
+    return p.covered && p.resident ? 1 : 0;
+}
 
 size_t stgcn_vit_block_saved_bytes(int B, int L, int D, int hidden) {
-    if (B < 1 || L < 1 || D < 1 || hidden < 1 || D % 64 != 0 || hidden % 64 != 0 || L > kMaxL) return 0;
-    return BlockSaved(nullptr, B, L, D, hidden).total;
+    const BlockPlan p = plan_block(BlockEntry::forward_train, L, D, 0, hidden, 0);
+    return B >= 1 && p.sized && p.resident ? BlockStore(nullptr, p, B, L, D, hidden).total : 0;
 }
 
 size_t stgcn_vit_block_backward_ws_bytes(int B, int L, int D, int hidden) {
-    if (B < 1 || L < 1 || D < 1 || hidden < 1 || D % 64 != 0 || hidden % 64 != 0 || L > kMaxL) return 0;
-    return BackwardWs(nullptr, B, L, D, hidden).total;
+    const BlockPlan p = plan_block(BlockEntry::backward, L, D, 0, hidden, 0);
+    return B >= 1 && p.sized && p.resident ? BackwardWs(nullptr, B, L, D, hidden).total : 0;
 }
 
 int stgcn_vit_block_train_long_supported(int L, int D, int heads, int hidden) {
-    return plan_block_train(L, D, heads, hidden) != BlockAttention::none ? 1 : 0;
+    return plan_block(BlockEntry::forward_train, L, D, heads, hidden, 0).covered ? 1 : 0;
 }
 
 int stgcn_vit_block_train_bf16_supported(int L, int D, int heads, int hidden) {
-    return plan_block_train(L, D, heads, hidden) != BlockAttention::none ? 1 : 0;
+    return plan_block(BlockEntry::forward_train, L, D, heads, hidden, STGCN_VIT_TRAIN_BF16).covered ? 1 : 0;
 }
 
 size_t stgcn_vit_block_train_long_saved_bytes(int B, int L, int D, int hidden) {
-    if (B < 1 || L < 1 || D < 1 || hidden < 1 || D % 64 != 0 || hidden % 64 != 0 || L > kMaxStreamL) return 0;
-    return BlockSaved(nullptr, B, L, D, hidden).total;
+    const BlockPlan p = plan_block(BlockEntry::forward_train, L, D, 0, hidden, 0);
+    return B >= 1 && p.sized ? BlockStore(nullptr, p, B, L, D, hidden).total : 0;
 }
 
 size_t stgcn_vit_block_train_long_ws_bytes(int B, int L, int D, int heads, int hidden) {
-    const BlockAttention plan = plan_block_train(L, D, heads, hidden);
-    if (B < 1 || plan == BlockAttention::none) return 0;
-    return TrainWs(nullptr, plan, B, L, D, heads, hidden).total;
+    const BlockPlan p = plan_block(BlockEntry::backward, L, D, heads, hidden, 0);
+    return B >= 1 && p.covered ? TrainWs(nullptr, p, B, L, D, heads, hidden).total : 0;
 }
 
 int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
@@ -279,50 +248,17 @@ int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, con
                                   const float *scale1, const float *scale2, float eps, float scale, void *saved,
                                   size_t saved_bytes, float *y, int B, int L, int D, int heads, int hidden, unsigned flags,
                                   void *stream) {
-    if (flags & STGCN_VIT_BF16) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)");
-    if (flags & STGCN_VIT_TILE_MASK) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)");
-    if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !y || !saved)
-        return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: null pointer");
+    const BlockPlan plan = plan_block(BlockEntry::forward_train, L, D, heads, hidden, flags);
+    if (plan.refusal) return block_refused(plan);
+    const BlockWeights w{norm1_weight, norm1_bias, Wqkv, bqkv, Wproj, bproj, norm2_weight, norm2_bias, W1, b1, W2, b2};
+    if (!x || !w.present() || !y || !saved) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: null pointer");
     if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: B = %d", B);
     if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: y must not alias x");
-    const BlockAttention plan = plan_block_train(L, D, heads, hidden);
-    if (plan == BlockAttention::none || !math_ok(flags))
-        return fail(STGCN_ERR_UNSUPPORTED,
-                    "stgcn_vit_block_forward_train: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
-                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxStreamL);
-    const BlockSaved sv(saved, B, L, D, hidden);
+    if (!plan.covered) return block_unsupported(plan, L, D, heads, hidden, flags);
+    const BlockStore sv(saved, plan, B, L, D, hidden);
     if (saved_bytes < sv.total)
         return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward_train: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const TrainMath tm(flags);
-    const unsigned math = tm.lin, math_qkv = tm.qkv_fwd;
-    const int per = slab_seqs(B, L);
-    for (int b0 = 0; b0 < B; b0 += per) {
-        const int nb = B - b0 < per ? B - b0 : per;
-        const int M = nb * L;
-        const size_t r0 = (size_t)b0 * L;
-        const float *xs = x + r0 * D;
-        float *qkv = sv.qkv + r0 * 3 * D, *att = sv.att + r0 * D, *x1 = sv.x1 + r0 * D;
-        LinearExtra e1, eh, e2;
-        e1.rowscale = scale1 != nullptr ? scale1 + b0 : nullptr;
-        e2.rowscale = scale2 != nullptr ? scale2 + b0 : nullptr;
-        e1.L = e2.L = L;
-        eh.pre = sv.hpre + r0 * hidden;
-        int rc;
-        if ((rc = launch_linear(xs, Wqkv, bqkv, nullptr, norm1_weight, norm1_bias, eps, qkv, M, D, 3 * D, false, math_qkv, st)))
-            return rc;
-        rc = plan == BlockAttention::stream ? launch_attention_stream(qkv, att, nb, L, heads, D / heads, scale, st)
-                                            : launch_attention_packed(qkv, att, nb, L, heads, D / heads, scale, st);
-        if (rc) return rc;
-        if ((rc = launch_linear_ex(att, Wproj, bproj, xs, nullptr, nullptr, 0.f, x1, M, D, D, false, math, e1, st))) return rc;
-        if ((rc = launch_linear_ex(x1, W1, b1, nullptr, norm2_weight, norm2_bias, eps, sv.hid + r0 * hidden, M, D, hidden, true, math,
-                                   eh, st)))
-            return rc;
-        if ((rc = launch_linear_ex(sv.hid + r0 * hidden, W2, b2, x1, nullptr, nullptr, 0.f, y + r0 * D, M, hidden, D, false, math, e2,
-                                   st)))
-            return rc;
-    }
-    return STGCN_OK;
+    return block_forward(plan, x, w, sv, scale1, scale2, eps, scale, y, B, L, D, heads, hidden, static_cast<hipStream_t>(stream));
 }
 
 int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
@@ -332,28 +268,23 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
                              float *dWproj, float *dbproj, float *dnorm2_weight, float *dnorm2_bias, float *dW1, float *db1,
                              float *dW2, float *db2, float eps, float scale, void *ws, size_t ws_bytes, int B, int L, int D,
                              int heads, int hidden, unsigned flags, void *stream) {
-    if (flags & STGCN_VIT_BF16) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)");
-    if (flags & STGCN_VIT_TILE_MASK) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)");
+    const BlockPlan plan = plan_block(BlockEntry::backward, L, D, heads, hidden, flags);
+    if (plan.refusal) return block_refused(plan);
     if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !saved || !dy || !dx ||
         !dnorm1_weight || !dnorm1_bias || !dWqkv || !dWproj || !dbproj || !dnorm2_weight || !dnorm2_bias || !dW1 || !db1 || !dW2 ||
         !db2 || !ws)
         return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: null pointer");
     if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: B = %d", B);
     if (dx == dy || dx == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: dx must not alias dy or x");
-    const BlockAttention plan = plan_block_train(L, D, heads, hidden);
-    if (plan == BlockAttention::none || !math_ok(flags))
-        return fail(STGCN_ERR_UNSUPPORTED,
-                    "stgcn_vit_block_backward: L = %d, D = %d, heads = %d, hidden = %d, math %u (covered: head_dim 32 / 64, "
-                    "L <= %d, D and hidden multiples of 64, f32 / bf16x3)", L, D, heads, hidden, flags & STGCN_MATH_MASK, kMaxStreamL);
-    const BlockSaved sv(const_cast<void *>(saved), B, L, D, hidden);
+    if (!plan.covered) return block_unsupported(plan, L, D, heads, hidden, flags);
+    const BlockStore sv(const_cast<void *>(saved), plan, B, L, D, hidden);
     if (saved_bytes < sv.total)
         return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
     const TrainWs tw(ws, plan, B, L, D, heads, hidden);
     if (ws_bytes < tw.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: workspace %zu < %zu bytes", ws_bytes, tw.total);
     const BackwardWs &w = tw.w;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const TrainMath tm(flags);
-    const unsigned math = tm.lin, math_qkv = tm.qkv_dgrad;
+    const unsigned math = plan.lin_dgrad, math_qkv = plan.qkv_dgrad;
     int rc;
     if ((rc = launch_transpose_pad(Wqkv, w.wt_qkv, 3 * D, D, 3 * D, st))) return rc;
     if ((rc = launch_transpose_pad(Wproj, w.wt_proj, D, D, D, st))) return rc;
@@ -366,8 +297,8 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
         const size_t r0 = (size_t)b0 * L;
         const bool acc = b0 > 0;
         const float *xs = x + r0 * D, *dys = dy + r0 * D;
-        const float *qkv = sv.qkv + r0 * 3 * D, *att = sv.att + r0 * D, *x1 = sv.x1 + r0 * D;
-        const float *hpre = sv.hpre + r0 * hidden, *hid = sv.hid + r0 * hidden;
+        const float *qkv = (const float *)sv.qkv + r0 * 3 * D, *att = (const float *)sv.att + r0 * D, *x1 = sv.x1 + r0 * D;
+        const float *hpre = sv.hpre + r0 * hidden, *hid = (const float *)sv.hid + r0 * hidden;
         const float *s1 = scale1 != nullptr ? scale1 + b0 : nullptr, *s2 = scale2 != nullptr ? scale2 + b0 : nullptr;
         LinearExtra e2, e1;
         e2.dgelu = hpre;
@@ -375,19 +306,19 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
         e1.rowscale = s1;
         e1.L = e2.L = L;
         // MLP branch
-        if ((rc = launch_linear_ex(dys, w.wt_fc2, nullptr, nullptr, nullptr, nullptr, 0.f, w.dhid, M, D, hidden, false, math, e2, st)))
+        if ((rc = launch_linear(dys, w.wt_fc2, nullptr, nullptr, nullptr, nullptr, 0.f, w.dhid, M, D, hidden, false, math, st, e2)))
             return rc;
-        if ((rc = tm.wgrad(dys, hid, s2, L, dW2, db2, w.part, w.tmp, M, hidden, D, acc, st))) return rc;
+        if ((rc = wgrad(plan, dys, hid, s2, L, dW2, db2, w.part, w.tmp, M, hidden, D, acc, st))) return rc;
         if ((rc = launch_linear(w.dhid, w.wt_fc1, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, hidden, D, false, math, st)))
             return rc;
         if ((rc = launch_ln_backward(x1, w.dn, norm2_weight, norm2_bias, eps, dys, w.dx1, w.a, w.stats, M, D, st))) return rc;
         if ((rc = launch_ln_param_grad(x1, w.dn, w.stats, dnorm2_weight, dnorm2_bias, w.part, w.tmp, M, D, acc, st))) return rc;
-        if ((rc = tm.wgrad(w.dhid, w.a, nullptr, L, dW1, db1, w.part, w.tmp, M, D, hidden, acc, st))) return rc;
+        if ((rc = wgrad(plan, w.dhid, w.a, nullptr, L, dW1, db1, w.part, w.tmp, M, D, hidden, acc, st))) return rc;
         // attention branch
-        if ((rc = launch_linear_ex(w.dx1, w.wt_proj, nullptr, nullptr, nullptr, nullptr, 0.f, w.datt, M, D, D, false, math, e1, st)))
+        if ((rc = launch_linear(w.dx1, w.wt_proj, nullptr, nullptr, nullptr, nullptr, 0.f, w.datt, M, D, D, false, math, st, e1)))
             return rc;
-        if ((rc = tm.wgrad(w.dx1, att, s1, L, dWproj, dbproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
-        rc = plan == BlockAttention::stream
+        if ((rc = wgrad(plan, w.dx1, att, s1, L, dWproj, dbproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
+        rc = plan.attention == BlockAttention::stream
                  ? launch_attention_backward_stream(qkv, att, w.datt, w.dqkv, tw.att_stats, nb, L, heads, D / heads, scale, st)
                  : launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st);
         if (rc) return rc;
@@ -395,7 +326,7 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
             return rc;
         if ((rc = launch_ln_backward(xs, w.dn, norm1_weight, norm1_bias, eps, w.dx1, dx + r0 * D, w.a, w.stats, M, D, st))) return rc;
         if ((rc = launch_ln_param_grad(xs, w.dn, w.stats, dnorm1_weight, dnorm1_bias, w.part, w.tmp, M, D, acc, st))) return rc;
-        if ((rc = tm.wgrad(w.dqkv, w.a, nullptr, L, dWqkv, dbqkv, w.part, w.tmp, M, D, 3 * D, acc, st))) return rc;
+        if ((rc = wgrad(plan, w.dqkv, w.a, nullptr, L, dWqkv, dbqkv, w.part, w.tmp, M, D, 3 * D, acc, st))) return rc;
     }
     return STGCN_OK;
 }

@@ -11,7 +11,7 @@
 //   bf16x3 : both tiles are split into bf16 hi + lo while they are staged (the weights too: the split of a 128 x 32 weight
 //            chunk is 16 values per thread and hides under the 24 MFMAs of the chunk, so there is no packed weight format
 //            and nothing to cache on the host), then lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16;
-//   bf16   : (launch_linear_bf16, the inference block's STGCN_VIT_BF16 mode) both operands rounded to nearest-even bf16 while
+//   bf16   : (the block's STGCN_VIT_BF16 and STGCN_VIT_TRAIN_BF16 modes) both operands rounded to nearest-even bf16 while
 //            they are staged, one LDS tile per operand, one v_mfma_f32_32x32x16_bf16 per k-step and block, fp32 accumulate.
 //            X is fp32 (rounded after the LayerNorm) or already bf16 in memory (XB: 8-byte loads that go to LDS as they
 //            are), Y is stored as fp32 or as bf16 (YB); bias, GELU and residual stay fp32.  The k pairs, instructions and
@@ -309,15 +309,6 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const void *__re
     }
 }
 
-}  // namespace
-
-int launch_linear(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
-                  float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, hipStream_t st) {
-    return launch_linear_ex(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, math, LinearExtra{}, st);
-}
-
-namespace {
-
 template <int MATH, class F, bool XB = false, bool YB = false>
 int launch_form(const void *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta, float eps,
                 void *Y, int M, int K, int Nout, bool gelu, const LinearExtra &ex, hipStream_t st) {
@@ -342,29 +333,21 @@ int launch_math(const LinearTile t, const void *X, const float *W, const float *
 
 }  // namespace
 
-int launch_linear_ex(const float *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
-                     float eps, float *Y, int M, int K, int Nout, bool gelu, unsigned math, const LinearExtra &ex,
-                     hipStream_t st) {
-    const LinearTile t = linear_tile(M, K, Nout, math);
-    if ((math & STGCN_MATH_MASK) == STGCN_MATH_F32)
-        return launch_math<STGCN_MATH_F32>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
-    if ((math & STGCN_MATH_MASK) == STGCN_MATH_BF16)   // the training mode STGCN_VIT_TRAIN_BF16: fp32 in memory on both sides
-        return launch_math<STGCN_MATH_BF16>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
-    return launch_math<STGCN_MATH_BF16X3>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
-}
-
-int launch_linear_bf16(const void *X, bool x_bf16, const float *W, const float *bias, const float *R, const float *gamma,
-                       const float *beta, float eps, void *Y, bool y_bf16, int M, int K, int Nout, bool gelu, unsigned tile,
-                       hipStream_t st) {
-    if (x_bf16 && gamma != nullptr) return fail(STGCN_ERR_UNSUPPORTED, "vit linear (bf16): LayerNorm needs fp32 rows");
-    const LinearTile t = linear_tile(M, K, Nout, tile);
-    const LinearExtra ex{};
-    constexpr int B = STGCN_MATH_BF16;
-    if (x_bf16)
-        return y_bf16 ? launch_math<B, true, true>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st)
-                      : launch_math<B, true, false>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
-    return y_bf16 ? launch_math<B, false, true>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st)
-                  : launch_math<B, false, false>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+int launch_linear(const void *X, const float *W, const float *bias, const float *R, const float *gamma, const float *beta,
+                  float eps, void *Y, int M, int K, int Nout, bool gelu, unsigned mode, hipStream_t st, const LinearExtra &ex) {
+    const unsigned math = mode & STGCN_MATH_MASK;
+    const bool xb = (mode & STGCN_VIT_X_BF16) != 0, yb = (mode & STGCN_VIT_Y_BF16) != 0;
+    if ((xb || yb) && math != STGCN_MATH_BF16) return fail(STGCN_ERR_UNSUPPORTED, "vit linear: bf16 storage needs the bf16 arithmetic");
+    if (xb && gamma != nullptr) return fail(STGCN_ERR_UNSUPPORTED, "vit linear (bf16): LayerNorm needs fp32 rows");
+    const LinearTile t = linear_tile(M, K, Nout, mode);
+    if (math == STGCN_MATH_F32) return launch_math<STGCN_MATH_F32>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    if (math != STGCN_MATH_BF16) return launch_math<STGCN_MATH_BF16X3>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    constexpr int B = STGCN_MATH_BF16;   // fp32 or bf16 storage on either side
+    if (xb)
+        return yb ? launch_math<B, true, true>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st)
+                  : launch_math<B, true, false>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
+    return yb ? launch_math<B, false, true>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st)
+              : launch_math<B, false, false>(t, X, W, bias, R, gamma, beta, eps, Y, M, K, Nout, gelu, ex, st);
 }
 
 }  // namespace vit

@@ -337,28 +337,40 @@ class Block(nn.Module):
         """``hip_applies`` and the call is large enough for the HIP path to be the faster one (``hip_min_tokens``)."""
         return x.dim() == 3 and x.shape[0] * x.shape[1] >= self.hip_min_tokens and self.hip_applies(x)
 
+    def _hip_flags(self, x: torch.Tensor, train: bool) -> int:
+        """The flag word this call hands to its HIP path, resolved here and nowhere else.  Training: ``train_math_mode``
+        (``set_train_math`` wins), else ``math_mode``, else ``_default_train_math()``; tile forms and ``HEAD_MATH['bf16']`` are
+        inference modes that never reach a training entry point (a block set to the latter trains in its path's default).
+        Inference: ``math_mode``, else ``_default_head_math()``; ``'bf16'`` only where its resident form covers the length
+        (longer sequences run the default arithmetic, still on HIP); ``small_tiles`` adds ``VIT_TILE_AUTO`` unless
+        ``math_mode`` forces a form."""
+        if train:
+            if self.train_math_mode is not None:
+                return self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16)
+            if self.math_mode is None or self.math_mode & VIT_BF16:
+                return _default_train_math()
+            return self.math_mode & ~VIT_TILE_MASK
+        math = _default_head_math() if self.math_mode is None else self.math_mode
+        if math & VIT_BF16 and not F.vit_block_forward_bf16_supported(x.shape[1], x.shape[2], self.attn.num_heads,
+                                                                      self.mlp.fc1.out_features):
+            math = HEAD_MATH[DEFAULT_HEAD_MATH] | (math & VIT_TILE_MASK)
+        if self.small_tiles and not math & VIT_TILE_MASK:
+            math |= VIT_TILE_AUTO
+        return math
+
     def forward(self, x):
         if self.uses_hip(x):
             a, m = self.attn, self.mlp
-            math = _default_head_math() if self.math_mode is None else self.math_mode
-            if math & VIT_BF16 and not F.vit_block_forward_bf16_supported(x.shape[1], x.shape[2], a.num_heads, m.fc1.out_features):
-                math = HEAD_MATH[DEFAULT_HEAD_MATH] | (math & VIT_TILE_MASK)   # L > 256: the default arithmetic, still on HIP
-            if self.small_tiles and not math & VIT_TILE_MASK:   # a form forced through math_mode stands
-                math |= VIT_TILE_AUTO
             with torch.no_grad():
                 return F.vit_block_forward(x.contiguous(), (self.norm1.weight, self.norm1.bias), (a.qkv.weight, a.qkv.bias),
                                            (a.proj.weight, a.proj.bias), (self.norm2.weight, self.norm2.bias),
                                            (m.fc1.weight, m.fc1.bias), (m.fc2.weight, m.fc2.bias), a.num_heads, self.norm1.eps,
-                                           a.scale, math)
+                                           a.scale, self._hip_flags(x, train=False))
         if self.trains_on_hip(x):
             s1, s2 = self.draw_drop_path(x)
-            math = _default_train_math() if self.math_mode is None else self.math_mode & ~VIT_TILE_MASK   # tile forms: inference only
-            if math & VIT_BF16:                 # an inference mode: the bit never reaches a training entry point
-                math = _default_train_math()
-            if self.train_math_mode is not None:   # set_train_math wins
-                math = self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16)
             return _BlockTrain.apply(x, None if s1 is None else s1.reshape(-1), None if s2 is None else s2.reshape(-1),
-                                     self.attn.num_heads, self.norm1.eps, self.attn.scale, math, *self._weights())
+                                     self.attn.num_heads, self.norm1.eps, self.attn.scale, self._hip_flags(x, train=True),
+                                     *self._weights())
         x = x + self.drop_path(self.attn(self.norm1(x)))
         return x + self.drop_path(self.mlp(self.norm2(x)))
 

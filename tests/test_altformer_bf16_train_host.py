@@ -55,7 +55,7 @@ def test_the_two_new_queries(lib):
     from stgcn_amd import functional as F
     for L, D, hidden in STAGES:
         assert lib.stgcn_vit_block_train_bf16_supported(L, D, 8, hidden) == 1 and F.vit_block_train_bf16_supported(L, D, 8, hidden)
-    for L in (1, 256, 257, 300, 4096, 4097, 0):       # the streaming lengths are covered: the coverage of plan_block_train
+    for L in (1, 256, 257, 300, 4096, 4097, 0):       # the streaming lengths are covered: the coverage of the training plan
         for D, heads, hidden in ((256, 8, 512), (512, 8, 1024), (384, 8, 768), (256, 8, 500), (256, 4, 512), (256, 3, 512)):
             assert lib.stgcn_vit_block_train_bf16_supported(L, D, heads, hidden) == \
                 lib.stgcn_vit_block_train_long_supported(L, D, heads, hidden), (L, D, heads, hidden)

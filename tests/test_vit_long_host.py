@@ -65,7 +65,7 @@ def test_old_and_training_queries_keep_their_answers(lib):
 
 
 def carve(B, L, D, hidden):
-    """BlockWs by hand: qkv, attention output, first residual and hidden activations of one slab of whole sequences, each piece
+    """BlockStore by hand: qkv, attention output, first residual and hidden activations of one slab of whole sequences, each piece
     padded to 256 bytes."""
     rows = min(B, max(1, SLAB // L)) * L
     up = lambda n: (n + 255) // 256 * 256     # noqa: E731
