@@ -117,6 +117,13 @@ int stgcn_agcn_forward(const float *x, const float *A_eff, const float *Wa, cons
                        const float *bn_shift, const float *down_scale, const float *down_shift,
                        float *P_ws, float *y, int N, int Cin, int Cout, int T, int V, int inter_c,
                        int subsets, void *stream);
+/* Names, with template arguments, of the kernels that compute P and y for a shape ("attention_folded_kernel<4,16>",
+ * "agcn_expand_mfma_kernel<1,16>", ...; "" when the call is refused) — for profilers and benchmarks that match kernel
+ * names in rocprofv3 output.  extra: what the attention writes besides P — 0 nothing (stgcn_agcn_attention and the
+ * forwards), 1 the fused stem's features, 2 its attention fragments, 3 the fragments of a wide frame's joint split.
+ * has_down: Wdown is given.  (additive, ABI 11) */
+const char *stgcn_agcn_attention_kernel_name(int N, int Cin, int T, int V, int inter_c, int subsets, int extra);
+const char *stgcn_agcn_expand_kernel_name(int N, int Cin, int Cout, int T, int V, int subsets, int has_down);
 
 /* ---- temporal conv block (Unit2D, dim=2) -----------------------------------------------
  * W (Cout,Cin,K) = conv.weight with the trailing 1 squeezed; pad = (K-1)/2; T_out = (T+2*pad-K)/stride+1.

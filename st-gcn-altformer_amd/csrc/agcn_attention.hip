@@ -14,6 +14,8 @@
 //
 // Both are HBM-read-bound in principle (x is read once: 4*Cin*T*V bytes per clip) and tiny next to
 // the temporal conv; P (N,S,V,V) is written once.
+#include <algorithm>
+
 #include "bf16_common.h"
 
 namespace stgcn {
@@ -773,160 +775,125 @@ __global__ __launch_bounds__(512) void attention_generic_mfma_kernel(
 
 }  // namespace
 
-// true when launch_attention can also emit the (N, T*V, 16) feature tensor (folded kernel, Cin = 3, S = 3)
-// launch geometry of the folded kernel (shared by the capability query and the launcher)
-struct FoldedPlan {
-    bool ok = false;
-    int maxb = 0, nw = 0, TC = 0, Rp = 0, slice_off = 0, sq_behind = 0;
-    size_t lds = 0;
-};
-
-// nw = waves per workgroup (16 or 8)
-static FoldedPlan plan_folded_nw(int Cin, int T, int V, int inter_c, int S, bool with_features, int nw, bool sq_behind = false) {
-    FoldedPlan pl;
+// geometry of the folded kernel with nw waves per workgroup (16 or 8); t.maxb: Gram blocks (accumulators) per wave
+static bool folded_covers_nw(int Cin, int T, int V, int inter_c, int S, bool with_features, int nw, bool sq_behind, AttentionTile &t) {
     const int C1 = Cin + 1, R = Cin * V + 1;
     const int nb = ceil_div(R, GB), nblk = nb * (nb + 1) / 2;
     const size_t gs_floats = (size_t)R * R + (size_t)S * V * V + (sq_behind ? (size_t)4 * V * V + 4 : 0);
-    pl.sq_behind = sq_behind ? 1 : 0;
-    if (Cin > 4 || S * C1 * C1 > MS_FLOATS || V > 64) return pl;
-    if (with_features && (Cin != 3 || S != 3)) return pl;
-    pl.maxb = ceil_div(nblk, nw);                            // Gram blocks (accumulators) per wave
-    if (pl.maxb > 12) return pl;
-    pl.nw = nw;
-    pl.Rp = (nb | 1) * GB;                                   // >= nb*16 and = 16 (mod 32) floats: conflict-free fragment reads
+    t = AttentionTile{};
+    t.sq_behind = sq_behind ? 1 : 0;
+    if (Cin > 4 || S * C1 * C1 > MS_FLOATS || V > kAttentionMaxV) return false;
+    if (with_features && !agcn_stem_class(Cin, S)) return false;
+    t.maxb = ceil_div(nblk, nw);
+    if (t.maxb > 12) return false;
+    t.nw = nw;
+    t.pitch = (nb | 1) * GB;                                 // >= nb*16 and = 16 (mod 32) floats: conflict-free fragment reads
     const size_t slices = with_features ? (size_t)nw * 4096 : 0;   // 4 KiB per wave for the coalesced feature rows
     // chunk of frames held in LDS: the whole clip when it fits in ~96 KiB, else as many frames as do (multiple of 4:
     // one MFMA step contracts 4 frames)
     size_t budget = (size_t)96 * 1024 / 4;
     if (gs_floats > budget) budget = gs_floats;
     if ((MS_FLOATS + budget) * 4 + slices > (size_t)kLdsBytes) budget = ((size_t)kLdsBytes - slices) / 4 - MS_FLOATS;
-    if (budget < gs_floats) return pl;                       // Gram + attention matrices must fit
-    int TC = (int)(budget / pl.Rp) & ~3;
+    if (budget < gs_floats) return false;                    // Gram + attention matrices must fit
+    int TC = (int)(budget / t.pitch) & ~3;
     if (TC > (T + 3) / 4 * 4) TC = (T + 3) / 4 * 4;
-    if (TC < 4) return pl;
-    size_t u_floats = (size_t)TC * pl.Rp;
+    if (TC < 4) return false;
+    size_t u_floats = (size_t)TC * t.pitch;
     if (u_floats < gs_floats) u_floats = gs_floats;
     const size_t wl_floats = (size_t)2 * S * inter_c * C1;   // LDS copy of the embedding weights
     if (u_floats < wl_floats) u_floats = wl_floats;
     u_floats = (u_floats + 3) / 4 * 4;                       // keep the feature slices 16-B aligned
-    pl.TC = TC;
-    pl.slice_off = (int)(MS_FLOATS + u_floats);              // in floats
-    pl.lds = (MS_FLOATS + u_floats) * 4 + slices;
-    pl.ok = pl.lds <= (size_t)kLdsBytes;
-    return pl;
+    t.TC = TC;
+    t.slice_off = (int)(MS_FLOATS + u_floats);               // in floats
+    t.lds = (MS_FLOATS + u_floats) * 4 + slices;
+    return t.lds <= (size_t)kLdsBytes;
 }
 
-// 1024 threads where LDS allows, else 512 (wide frames: V = 46 with the feature slices)
-static FoldedPlan plan_folded(int Cin, int T, int V, int inter_c, int S, bool with_features) {
-    if (with_features) {   // the interleaved P behind the Gram matrix: longer frame chunks in the feature pass
-        const FoldedPlan p16b = plan_folded_nw(Cin, T, V, inter_c, S, true, 16, true);
-        if (p16b.ok && p16b.maxb <= 4) return p16b;
-    }
-    const FoldedPlan p16 = plan_folded_nw(Cin, T, V, inter_c, S, with_features, 16);
-    if (p16.ok && p16.maxb <= 4) return p16;
-    return plan_folded_nw(Cin, T, V, inter_c, S, with_features, 8);
+// 1024 threads where LDS allows, else 512 (wide frames: V = 46 with the feature slices); with features first the form with
+// the interleaved P behind the Gram matrix (longer frame chunks in the feature pass).  t.maxb leaves as the template argument.
+bool attention_folded_covers(int N, int Cin, int T, int V, int inter_c, int S, bool features, AttentionTile &t) {
+    const bool ok = (features && folded_covers_nw(Cin, T, V, inter_c, S, true, 16, true, t) && t.maxb <= 4) ||
+                    (folded_covers_nw(Cin, T, V, inter_c, S, features, 16, false, t) && t.maxb <= 4) ||
+                    folded_covers_nw(Cin, T, V, inter_c, S, features, 8, false, t);
+    if (t.nw == 16) t.maxb = t.maxb <= 1 ? 1 : t.maxb <= 2 ? 2 : 4;
+    else t.maxb = t.maxb <= 2 ? 2 : t.maxb <= 6 ? 6 : 12;
+    t.gx = N, t.gy = 1;
+    return ok;
 }
 
-// true when launch_attention can also emit the (N, T*V, 16) feature tensor (folded kernel, Cin = 3, S = 3)
-bool attention_emits_features(int Cin, int V, int S) {
-    return plan_folded(Cin, 1 << 20, V, 32, S, true).ok;
-}
+static int frames_in(size_t budget, size_t frame, int T) { return (int)std::min<size_t>(std::max<size_t>(budget / frame, 1), T); }
 
-int launch_attention(const float *x, const float *A_eff, const float *Wa, const float *ba,
-                     const float *Wb, const float *bb, float *P, float *feat, int N, int Cin, int T, int V,
-                     int inter_c, int S, hipStream_t st, bool x_ntvc, float *xcopy, void *pfrag, int pf_v0, float *ybound) {
-    const int xsc = x_ntvc ? 1 : T * V, xsp = x_ntvc ? Cin : 1;
-    if (pfrag != nullptr && (Cin != 3 || S != 3 || (pf_v0 == 0 && V > 32) || feat != nullptr))
-        return fail(STGCN_ERR_UNSUPPORTED, "attention: fragment output covers Cin=3, 3 subsets, V<=32 (got %d, %d, %d)", Cin, S, V);
-    if (pfrag != nullptr && pf_v0 != 0 && (pf_v0 < 1 || pf_v0 > 32 || V - pf_v0 < 1 || V - pf_v0 > 32))
-        return fail(STGCN_ERR_UNSUPPORTED, "attention: joint split %d | %d outside 1..32 per half", pf_v0, V - pf_v0);
-    if (feat != nullptr && (Cin != 3 || S != 3))
-        return fail(STGCN_ERR_UNSUPPORTED, "attention: the feature pass covers Cin=3, 3 subsets (got %d, %d)", Cin, S);
-    const FoldedPlan pl = plan_folded(Cin, T, V, inter_c, S, feat != nullptr);
-    if (feat != nullptr && !pl.ok)
-        return fail(STGCN_ERR_UNSUPPORTED, "attention: V=%d too large for the feature pass", V);
-    if (pfrag != nullptr && !pl.ok) return fail(STGCN_ERR_UNSUPPORTED, "attention: V=%d outside the folded kernel", V);
-    if (ybound != nullptr && (!pl.ok || S * V > 512)) return fail(STGCN_ERR_UNSUPPORTED, "attention: no bound output for V=%d", V);
-    if (pl.ok) {
-        const int TC = pl.TC, Rp = pl.Rp, slice_off = pl.slice_off;
-        const size_t lds = pl.lds;
-#define LAUNCH_FOLDED(MI, TSL)                                                                          \
-    do {                                                                                               \
-        STGCN_HIP_CHECK(allow_lds((attention_folded_kernel<MI, TSL>), lds));                           \
-        hipLaunchKernelGGL((attention_folded_kernel<MI, TSL>), dim3(N), dim3(64 * TSL), lds, st, x, A_eff, \
-                           Wa, ba, Wb, bb, P, feat, (uint4 *)pfrag, Cin, T, V, inter_c, S, TC, Rp, slice_off, pl.sq_behind, xsc, xsp, xcopy, debug_buffer(), pf_v0, ybound); \
-    } while (0)
-        if (pl.nw == 16) {
-            if (pl.maxb <= 1) LAUNCH_FOLDED(1, 16);
-            else if (pl.maxb <= 2) LAUNCH_FOLDED(2, 16);
-            else LAUNCH_FOLDED(4, 16);
-        } else {
-            if (pl.maxb <= 2) LAUNCH_FOLDED(2, 8);
-            else if (pl.maxb <= 6) LAUNCH_FOLDED(6, 8);
-            else LAUNCH_FOLDED(12, 8);
-        }
-#undef LAUNCH_FOLDED
-        STGCN_LAUNCH_CHECK("attention_folded_kernel");
-        return STGCN_OK;
-    }
-    // generic path: on the matrix cores when the shapes tile (every TCN_GCN_unit layer of the reference does)
+// on the matrix cores when the shapes tile (every TCN_GCN_unit layer of the reference does)
+bool attention_generic_mfma_covers(int N, int Cin, int T, int V, int inter_c, int S, AttentionTile &t) {
     const bool ic_ok = inter_c == 8 || inter_c == 16 || inter_c == 32 || inter_c == 64;
-    if (Cin % 4 == 0 && Cin <= 256 && ic_ok && S <= 3 && V <= 64 && !(ablate_mask() & 2048)) {   // (diagnostic builds: 2048 = the VALU kernel)
-        const size_t budget = (size_t)128 * 1024 / 4;
-        int TC = (int)(budget / ((size_t)V * (Cin + 2 * inter_c)));
-        if (TC > T) TC = T;
-        if (TC < 1) TC = 1;
-        auto pitch = [&](int tc) { return ((tc * V + 63) & ~63) + 16; };
-        while (TC > 1 && (size_t)pitch(TC) * (Cin + 2 * inter_c) > budget) --TC;
-        const int PXC = pitch(TC);
-        const int nvb = (V + 15) / 16, nblk = nvb * nvb, KSP = nblk >= 8 ? 1 : 8 / nblk;
-        size_t fl = (size_t)PXC * (Cin + 2 * inter_c) + (size_t)inter_c * TC + 4;
-        const size_t tail = (size_t)S * (KSP + 1) * V * V;
-        if (fl < tail) fl = tail;
-        const size_t lds = fl * 4;
-        if (lds <= (size_t)kLdsBytes) {
-            const int per_wave = ceil_div(nblk * KSP, 8), ks = Cin / 4;
-#define LAUNCH_GMFMA(KSN, MB)                                                                                \
-    do {                                                                                                     \
-        STGCN_HIP_CHECK(allow_lds((attention_generic_mfma_kernel<KSN, MB>), lds));                           \
-        hipLaunchKernelGGL((attention_generic_mfma_kernel<KSN, MB>), dim3(N, N * 2 <= 256 ? S : 1), dim3(512), lds, st, x, A_eff, Wa, ba, Wb, bb, P, \
-                           Cin, T, V, inter_c, S, TC, PXC, xsc, xsp, xcopy, debug_buffer());                 \
-    } while (0)
-            if (per_wave <= 1) {
-                if (ks <= 16) LAUNCH_GMFMA(16, 1); else if (ks <= 32) LAUNCH_GMFMA(32, 1); else LAUNCH_GMFMA(64, 1);
-            } else {
-                if (ks <= 16) LAUNCH_GMFMA(16, 2); else if (ks <= 32) LAUNCH_GMFMA(32, 2); else LAUNCH_GMFMA(64, 2);
-            }
-#undef LAUNCH_GMFMA
-            STGCN_LAUNCH_CHECK("attention_generic_mfma_kernel");
-            return STGCN_OK;
-        }
-    }
+    if (Cin % 4 != 0 || Cin > 256 || !ic_ok || S > 3 || V > kAttentionMaxV) return false;
+    const size_t budget = (size_t)128 * 1024 / 4;
+    int TC = frames_in(budget, (size_t)V * (Cin + 2 * inter_c), T);
+    auto pitch = [&](int tc) { return ((tc * V + 63) & ~63) + 16; };
+    while (TC > 1 && (size_t)pitch(TC) * (Cin + 2 * inter_c) > budget) --TC;
+    const int nvb = (V + 15) / 16, nblk = nvb * nvb, KSP = nblk >= 8 ? 1 : 8 / nblk;
+    size_t fl = (size_t)pitch(TC) * (Cin + 2 * inter_c) + (size_t)inter_c * TC + 4;
+    const size_t tail = (size_t)S * (KSP + 1) * V * V;
+    if (fl < tail) fl = tail;
+    t = AttentionTile{};
+    t.TC = TC, t.pitch = pitch(TC), t.lds = fl * 4;
+    t.ks = Cin <= 64 ? 16 : Cin <= 128 ? 32 : 64;            // k-steps of 4 channels
+    t.mb = ceil_div(nblk * KSP, 8) <= 1 ? 1 : 2;             // (block, K part) units per wave
+    t.gx = N, t.gy = N * 2 <= 256 ? S : 1;
+    return t.lds <= (size_t)kLdsBytes;
+}
+
+// any shape up to kAttentionMaxV joints that fits LDS; false with t.lds set: it does not
+bool attention_generic_valu_covers(int N, int Cin, int T, int V, int inter_c, int S, AttentionTile &t) {
     const int maxit = ceil_div(V * V, 256);
-    if (maxit > 16) return fail(STGCN_ERR_UNSUPPORTED, "attention: V=%d too large (max 64)", V);
-    const size_t budget = (size_t)96 * 1024 / 4;
-    int TC = (int)(budget / ((size_t)V * (Cin + 2 * inter_c)));
-    if (TC > T) TC = T;
-    if (TC < 1) TC = 1;
+    const int TC = frames_in((size_t)96 * 1024 / 4, (size_t)V * (Cin + 2 * inter_c), T);
     size_t fl = (size_t)TC * V * (Cin + 2 * inter_c);
     if (fl < (size_t)V * V) fl = (size_t)V * V;
-    const size_t lds = fl * 4;
-    if (lds > (size_t)kLdsBytes)
-        return fail(STGCN_ERR_UNSUPPORTED, "attention: Cin=%d inter_c=%d V=%d needs %zu B of LDS", Cin,
-                    inter_c, V, lds);
-#define LAUNCH_GENERIC(MI)                                                                       \
-    do {                                                                                         \
-        STGCN_HIP_CHECK(allow_lds(attention_generic_kernel<MI>, lds));                           \
-        hipLaunchKernelGGL(attention_generic_kernel<MI>, dim3(S, N), dim3(256), lds, st, x, A_eff, \
-                           Wa, ba, Wb, bb, P, Cin, T, V, inter_c, S, TC, xsc, xsp, xcopy);     \
-    } while (0)
-    if (maxit <= 2) LAUNCH_GENERIC(2);
-    else if (maxit <= 4) LAUNCH_GENERIC(4);
-    else if (maxit <= 9) LAUNCH_GENERIC(9);
-    else LAUNCH_GENERIC(16);
-#undef LAUNCH_GENERIC
-    STGCN_LAUNCH_CHECK("attention_generic_kernel");
-    return STGCN_OK;
+    t = AttentionTile{};
+    t.TC = TC, t.lds = fl * 4;
+    t.maxit = maxit <= 2 ? 2 : maxit <= 4 ? 4 : maxit <= 9 ? 9 : 16;
+    t.gx = S, t.gy = N;
+    return V <= kAttentionMaxV && t.lds <= (size_t)kLdsBytes;
+}
+
+int launch_attention(const AttentionPlan &p, const AttentionIO &io, const float *A_eff, const float *Wa, const float *ba,
+                     const float *Wb, const float *bb, hipStream_t st) {
+    const AttentionTile &t = p.tile;
+    const int xsc = io.x_ntvc ? 1 : p.T * p.V, xsp = io.x_ntvc ? p.Cin : 1;
+    const dim3 grid(t.gx, t.gy);
+#define LAUNCH(COND, KERNEL, THREADS, ...)                                                                                 \
+    if (COND) {                                                                                                            \
+        STGCN_HIP_CHECK(allow_lds((KERNEL), t.lds));                                                                       \
+        hipLaunchKernelGGL((KERNEL), grid, dim3(THREADS), t.lds, st, io.x, A_eff, Wa, ba, Wb, bb, io.P, __VA_ARGS__);      \
+    }
+#define FOLDED(MB, NW)                                                                                                     \
+    LAUNCH(t.maxb == MB && t.nw == NW, (attention_folded_kernel<MB, NW>), 64 * NW, io.feat, (uint4 *)io.pfrag, p.Cin, p.T, p.V, \
+           p.inter_c, p.S, t.TC, t.pitch, t.slice_off, t.sq_behind, xsc, xsp, io.xcopy, debug_buffer(), p.out.split, io.ybound)
+#define GMFMA(KS, MB)                                                                                                      \
+    LAUNCH(t.ks == KS && t.mb == MB, (attention_generic_mfma_kernel<KS, MB>), 512, p.Cin, p.T, p.V, p.inter_c, p.S, t.TC,  \
+           t.pitch, xsc, xsp, io.xcopy, debug_buffer())
+#define GVALU(MI) \
+    LAUNCH(t.maxit == MI, attention_generic_kernel<MI>, 256, p.Cin, p.T, p.V, p.inter_c, p.S, t.TC, xsc, xsp, io.xcopy)
+    switch (p.kernel) {
+    case AttentionKernel::folded:
+        FOLDED(1, 16) FOLDED(2, 16) FOLDED(4, 16) FOLDED(2, 8) FOLDED(6, 8) FOLDED(12, 8)
+        STGCN_LAUNCH_CHECK("attention_folded_kernel");
+        return STGCN_OK;
+    case AttentionKernel::generic_mfma:
+        GMFMA(16, 1) GMFMA(32, 1) GMFMA(64, 1) GMFMA(16, 2) GMFMA(32, 2) GMFMA(64, 2)
+        STGCN_LAUNCH_CHECK("attention_generic_mfma_kernel");
+        return STGCN_OK;
+    case AttentionKernel::generic_valu:
+        GVALU(2) GVALU(4) GVALU(9) GVALU(16)
+        STGCN_LAUNCH_CHECK("attention_generic_kernel");
+        return STGCN_OK;
+    case AttentionKernel::none: break;
+    }
+#undef GVALU
+#undef GMFMA
+#undef FOLDED
+#undef LAUNCH
+    return refused(p.why);
 }
 
 }  // namespace stgcn

@@ -13,6 +13,7 @@
 //    live in registers and every output channel is F FMAs + bias + ReLU, stored coalesced along
 //    the pixel axis (each wave writes 256 contiguous bytes per channel).
 //  * agcn_expand_generic_kernel: any Cin/Cout (used by the deeper TCN_GCN_unit layers).
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -553,79 +554,85 @@ __global__ __launch_bounds__(512, (NOW == 1 ? 4 : 2)) void agcn_expand_mfma_kern
 
 }  // namespace
 
-int launch_agcn_expand(const float *x, const float *P, const float *Wd, const float *bd,
-                       const float *Wdown, const float *bdown, const float *bn_scale,
-                       const float *bn_shift, const float *down_scale, const float *down_shift,
-                       float *y, int N, int Cin, int Cout, int T, int V, int S, int mode, hipStream_t st) {
-    if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "agcn: N=%d > 65535 clips per call", N);
-    if (Cin == 3 && S == 3 && Wdown != nullptr && V <= 256) {
-        constexpr int F = 12, FP = 16;
-        (void)F;
-        int TF = 256 / V;
-        if (TF < 1) TF = 1;
-        if (TF > T) TF = T;
-        if ((T * V) % 4 == 0) {                // 16-byte stores: four pixels per thread, chunks of ~1024 pixels
-            const int gran = V % 4 == 0 ? 1 : (V % 2 == 0 ? 2 : 4);      // frames per chunk such that chunk*V % 4 == 0
-            int TF4 = 1024 / V / gran * gran;
-            if (TF4 < gran) TF4 = gran;
-            if (TF4 > T) TF4 = T;               // (T*V % 4 == 0: the single chunk is aligned as well)
-            const size_t lds4 = ((size_t)Cout * FP + (size_t)S * V * V + (size_t)3 * TF4 * V) * 4;
-            if (lds4 <= (size_t)kLdsBytes) {
-                STGCN_HIP_CHECK(allow_lds(agcn_expand_small4_kernel<3, 3>, lds4));
-                hipLaunchKernelGGL((agcn_expand_small4_kernel<3, 3>), dim3(ceil_div(T, TF4), N), dim3(256), lds4, st, x, P, Wd, bd,
-                                   Wdown, bdown, bn_scale, bn_shift, down_scale, down_shift, y, Cout, T, V, TF4, mode);
-                STGCN_LAUNCH_CHECK("agcn_expand_small4_kernel");
-                return STGCN_OK;
-            }
-        }
-        const size_t lds = ((size_t)Cout * FP + (size_t)S * V * V + (size_t)3 * TF * V) * 4;
-        if (lds <= (size_t)kLdsBytes) {
-            STGCN_HIP_CHECK(allow_lds(agcn_expand_small_kernel<3, 3>, lds));
-            hipLaunchKernelGGL((agcn_expand_small_kernel<3, 3>), dim3(ceil_div(T, TF), N), dim3(256), lds,
-                               st, x, P, Wd, bd, Wdown, bdown, bn_scale, bn_shift, down_scale, down_shift,
-                               y, Cout, T, V, TF, mode);
-            STGCN_LAUNCH_CHECK("agcn_expand_small_kernel");
-            return STGCN_OK;
-        }
-    }
-    // generic shapes on the matrix cores
-    if (S == 3 && Cin % 16 == 0 && Cout % 16 == 0 && V <= 64 && (Cout == 64 || Cout == 128 || Cout == 256) && !(ablate_mask() & 4096)) {
-        int TF = 256 / V;
-        if (TF < 1) TF = 1;
-        if (TF > T) TF = T;
-        const int PXP = 256 + 16;
-        const size_t lds = ((size_t)3 * V * V + (size_t)64 * PXP) * 4;
-        const dim3 grid(ceil_div(T, TF), N);
-#define LAUNCH_EXP(NOW_, NPB_)                                                                                         \
-    do {                                                                                                               \
-        STGCN_HIP_CHECK(allow_lds((agcn_expand_mfma_kernel<NOW_, NPB_>), lds));                                        \
-        hipLaunchKernelGGL((agcn_expand_mfma_kernel<NOW_, NPB_>), grid, dim3(512), lds, st, x, P, Wd, bd, Wdown, bdown, bn_scale, \
-                           bn_shift, down_scale, down_shift, y, Cin, Cout, T, V, TF, PXP, mode, debug_buffer());      \
-    } while (0)
-        if (Cout == 64) LAUNCH_EXP(1, 8);          // 4 o-blocks x 2 waves each: 8 of the 16 pixel blocks per wave
-        else if (Cout == 128) LAUNCH_EXP(1, 16);   // 8 o-blocks, one wave each
-        else LAUNCH_EXP(2, 16);                    // 16 o-blocks, two per wave
-#undef LAUNCH_EXP
-        STGCN_LAUNCH_CHECK("agcn_expand_mfma_kernel");
-        return STGCN_OK;
-    }
-    // generic, any shape (plain FMAs)
-    const size_t budget = (size_t)96 * 1024 / 4;
-    const size_t pfl = (size_t)S * V * V;
-    if (pfl + (size_t)Cin * V > (size_t)kLdsBytes / 4)
-        return fail(STGCN_ERR_UNSUPPORTED, "agcn: Cin=%d V=%d does not fit LDS", Cin, V);
+static int frames_per_chunk(int px, int T, int V) { return std::min(std::max(px / V, 1), T); }
+static size_t small_lds(int Cout, int TF, int V) { return ((size_t)Cout * 16 + (size_t)3 * V * V + (size_t)3 * TF * V) * 4; }   // FP = 16
+
+// 16-byte stores: four pixels per thread, chunks of ~1024 pixels
+bool agcn_expand_small4_covers(int N, int Cin, int Cout, int T, int V, int S, bool has_down, ExpandTile &t) {
+    if (!agcn_stem_class(Cin, S) || !has_down || V > 256 || (T * V) % 4 != 0) return false;
+    const int gran = V % 4 == 0 ? 1 : (V % 2 == 0 ? 2 : 4);      // frames per chunk such that chunk*V % 4 == 0
+    const int TF = std::min(std::max(1024 / V / gran * gran, gran), T);   // (T*V % 4 == 0: the single chunk is aligned as well)
+    t = ExpandTile{0, 0, TF, ceil_div(T, TF), N, small_lds(Cout, TF, V)};
+    return t.lds <= (size_t)kLdsBytes;
+}
+
+bool agcn_expand_small_covers(int N, int Cin, int Cout, int T, int V, int S, bool has_down, ExpandTile &t) {
+    if (!agcn_stem_class(Cin, S) || !has_down || V > 256) return false;
+    const int TF = frames_per_chunk(256, T, V);
+    t = ExpandTile{0, 0, TF, ceil_div(T, TF), N, small_lds(Cout, TF, V)};
+    return t.lds <= (size_t)kLdsBytes;
+}
+
+constexpr int MFMA_PXP = 256 + 16;   // pixel pitch of the matrix-core kernel's x tile
+
+// generic shapes on the matrix cores
+bool agcn_expand_mfma_covers(int N, int Cin, int Cout, int T, int V, int S, ExpandTile &t) {
+    if (S != 3 || Cin % 16 != 0 || V > kAttentionMaxV || (Cout != 64 && Cout != 128 && Cout != 256)) return false;
+    const int TF = frames_per_chunk(256, T, V);
+    // 64: 4 o-blocks x 2 waves each, 8 of the 16 pixel blocks per wave; 128: 8 o-blocks, one wave each; 256: 16, two per wave
+    t = ExpandTile{Cout == 256 ? 2 : 1, Cout == 64 ? 8 : 16, TF, ceil_div(T, TF), N, ((size_t)3 * V * V + (size_t)64 * MFMA_PXP) * 4};
+    return true;
+}
+
+// any shape whose attention matrices and one frame fit LDS (plain FMAs)
+bool agcn_expand_generic_covers(int N, int Cin, int T, int V, int S, ExpandTile &t) {
+    const size_t budget = (size_t)96 * 1024 / 4, pfl = (size_t)S * V * V;
+    if (pfl + (size_t)Cin * V > (size_t)kLdsBytes / 4) return false;
     int TF = 1;
     if (budget > pfl) TF = (int)((budget - pfl) / ((size_t)Cin * V));
-    if (TF > 256 / V) TF = 256 / V;
-    if (TF < 1) TF = 1;
-    if (TF > T) TF = T;
-    const size_t lds = (pfl + (size_t)Cin * TF * V) * 4;
-    STGCN_HIP_CHECK(allow_lds(agcn_expand_generic_kernel, lds));
-    hipLaunchKernelGGL(agcn_expand_generic_kernel, dim3(ceil_div(T, TF), N), dim3(256), lds, st, x, P, Wd,
-                       bd, Wdown, bdown, bn_scale, bn_shift, down_scale, down_shift, y, Cin, Cout, T, V, S,
-                       TF, mode);
-    STGCN_LAUNCH_CHECK("agcn_expand_generic_kernel");
-    return STGCN_OK;
+    TF = std::min(std::max(std::min(TF, 256 / V), 1), T);
+    t = ExpandTile{0, 0, TF, ceil_div(T, TF), N, (pfl + (size_t)Cin * TF * V) * 4};
+    return true;
+}
+
+int launch_agcn_expand(const ExpandPlan &p, const float *x, const float *P, const float *Wd, const float *bd,
+                       const float *Wdown, const float *bdown, const float *bn_scale, const float *bn_shift,
+                       const float *down_scale, const float *down_shift, float *y, int mode, hipStream_t st) {
+    const ExpandTile &t = p.tile;
+    const dim3 grid(t.gx, t.gy);
+#define LAUNCH(KERNEL, THREADS, ...)                                                                                       \
+    do {                                                                                                                   \
+        STGCN_HIP_CHECK(allow_lds((KERNEL), t.lds));                                                                       \
+        hipLaunchKernelGGL((KERNEL), grid, dim3(THREADS), t.lds, st, x, P, Wd, bd, Wdown, bdown, bn_scale, bn_shift, down_scale, \
+                           down_shift, y, __VA_ARGS__);                                                                    \
+    } while (0)
+#define MFMA(NOW_, NPB_)                                                                                                   \
+    if (t.now == NOW_ && t.npb == NPB_)                                                                                    \
+        LAUNCH((agcn_expand_mfma_kernel<NOW_, NPB_>), 512, p.Cin, p.Cout, p.T, p.V, t.TF, MFMA_PXP, mode, debug_buffer())
+    switch (p.kernel) {
+    case ExpandKernel::small4:
+        LAUNCH((agcn_expand_small4_kernel<3, 3>), 256, p.Cout, p.T, p.V, t.TF, mode);
+        STGCN_LAUNCH_CHECK("agcn_expand_small4_kernel");
+        return STGCN_OK;
+    case ExpandKernel::small:
+        LAUNCH((agcn_expand_small_kernel<3, 3>), 256, p.Cout, p.T, p.V, t.TF, mode);
+        STGCN_LAUNCH_CHECK("agcn_expand_small_kernel");
+        return STGCN_OK;
+    case ExpandKernel::mfma:
+        MFMA(1, 8);
+        MFMA(1, 16);
+        MFMA(2, 16);
+        STGCN_LAUNCH_CHECK("agcn_expand_mfma_kernel");
+        return STGCN_OK;
+    case ExpandKernel::generic:
+        LAUNCH(agcn_expand_generic_kernel, 256, p.Cin, p.Cout, p.T, p.V, p.S, t.TF, mode);
+        STGCN_LAUNCH_CHECK("agcn_expand_generic_kernel");
+        return STGCN_OK;
+    case ExpandKernel::none: break;
+    }
+#undef MFMA
+#undef LAUNCH
+    return refused(p.why);
 }
 
 }  // namespace stgcn

@@ -194,7 +194,7 @@ inline int moments_grid(int N) { return N < 256 ? N : 256; }
 }  // namespace
 
 static bool agcn_moments_supported(int Cin, int V, int S) {
-    return Cin == 3 && S == 3 && ((size_t)S * V * V + (size_t)Cin * (MOM_NT / V > 0 ? MOM_NT / V : 1) * V) * 4 <= (size_t)kLdsBytes && V <= MOM_NT;
+    return agcn_stem_class(Cin, S) && ((size_t)S * V * V + (size_t)Cin * (MOM_NT / V > 0 ? MOM_NT / V : 1) * V) * 4 <= (size_t)kLdsBytes && V <= MOM_NT;
 }
 
 // part: moments_grid(N) * NMOM doubles of scratch.  Writes s_m, t_m, s_d, t_d (Cout each) and updates the running buffers.
@@ -250,10 +250,15 @@ AgcnTrainPlan plan_agcn_train(int N, int Cin, int Cout, int T, int V, int S, boo
     p.frozen = frozen;
     p.has_down = has_down;
     p.moments = !materialise && agcn_moments_supported(Cin, V, S);
-    // Outside the stem class the residual rows are left out of the main branch's contraction altogether (no Wdown: "identity"
-    // with the residual term off, mode bit 1) and conv_down runs as one plain product — the expansion kernel run a second time
-    // with the main scales at zero did the whole work of both branches again (2 x 208 us at 64 -> 128 channels, 64 clips).
+    // Outside Cin = 3 the residual rows are left out of the main branch's contraction altogether (no Wdown: "identity" with
+    // EXPAND_NO_RESIDUAL) and conv_down runs as one plain product — the expansion kernel run a second time with the main scales
+    // at zero did the whole work of both branches again (2 x 208 us at 64 -> 128 channels, 64 clips).  This is NOT "no folded
+    // expansion kernel serves the shape" (!expand_is_folded(p.down.kernel)): Cin = 3 with S != 3, V > 256 or a folded weight image
+    // beyond LDS has no folded kernel either and still runs the generic expansion twice; taking the plan's answer there would
+    // move the bits of zd, its statistics and y, so the shape test stays.
     p.down_as_gemm = has_down && Cin != 3;
+    p.down = plan_agcn_expand(N, Cin, Cout, T, V, S, true);
+    p.main = p.down_as_gemm || !has_down ? plan_agcn_expand(N, Cin, Cout, T, V, S, false) : p.down;
     p.ws_bytes = carve_agcn_train(nullptr, p.moments, N, Cout, T, V).bytes;
     return p;
 }
@@ -275,7 +280,7 @@ int launch_agcn_forward_train(const AgcnTrainPlan &p, const float *x, const floa
                                       dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, momentum, eps, s1, t1, s2, t2,
                                       save_stats, N, Cin, Cout, T, V, S, st)))
             return rc;
-        return launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, s1, t1, s2, t2, y, N, Cin, Cout, T, V, S, 0, st);
+        return launch_agcn_expand(p.main, x, P, Wd, bd, Wdown, bdown, s1, t1, s2, t2, y, 0, st);
     }
     float *zm = save_zm ? save_zm : w.zm, *zd = save_zd ? save_zd : w.zd;
     const size_t plane = (size_t)T * V, total = (size_t)N * Cout * plane;
@@ -291,10 +296,9 @@ int launch_agcn_forward_train(const AgcnTrainPlan &p, const float *x, const floa
         STGCN_HIP_CHECK(hipMemsetAsync(save_stats + 4 * Cout, 0, 128 * sizeof(float), st));
     if ((rc = launch_fill_ones_zeros(ones, zeros, Cout, st))) return rc;
     // main branch, pre-BN: sum_s conv_d_s(x P_s)   (unit scale on the main path, zero on the residual path, no ReLU)
-    rc = p.down_as_gemm ? launch_agcn_expand(x, P, Wd, bd, nullptr, nullptr, ones, zeros, nullptr, nullptr, zm, N, Cin, Cout, T, V,
-                                             S, 1 | 2, st)
-                        : launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, ones, zeros, p.has_down ? zeros : nullptr,
-                                             p.has_down ? zeros : nullptr, zm, N, Cin, Cout, T, V, S, 1 | 2, st);
+    const bool with_down = p.has_down && !p.down_as_gemm;
+    rc = launch_agcn_expand(p.main, x, P, Wd, bd, with_down ? Wdown : nullptr, with_down ? bdown : nullptr, ones, zeros,
+                            with_down ? zeros : nullptr, with_down ? zeros : nullptr, zm, EXPAND_RAW | EXPAND_NO_RESIDUAL, st);
     if (rc != STGCN_OK) return rc;
     if ((rc = finalize(zm, w.v.sums1, bn_weight, bn_bias, bn_running_mean, bn_running_var, s1, t1, save_stats))) return rc;
     if (!p.has_down) return launch_bn_apply(zm, s1, t1, x, nullptr, nullptr, y, total, Cout, plane, st);  // identity residual: + x
@@ -303,7 +307,7 @@ int launch_agcn_forward_train(const AgcnTrainPlan &p, const float *x, const floa
         GemmArgs g{Wdown, x, zd, bdown, Cout, (int)plane, Cin, Cin, 1, 0, Pl, 1, (long long)Cin * Pl, Pl, 1, (long long)Cout * Pl, 1.f, 0};
         rc = launch_gemm_f32(g, N, st);
     } else {
-        rc = launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, zeros, zeros, ones, zeros, zd, N, Cin, Cout, T, V, S, 1, st);
+        rc = launch_agcn_expand(p.down, x, P, Wd, bd, Wdown, bdown, zeros, zeros, ones, zeros, zd, EXPAND_RAW, st);
     }
     if (rc != STGCN_OK) return rc;
     if ((rc = finalize(zd, w.v.sums2, dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, s2, t2,
@@ -349,12 +353,13 @@ AgcnBackwardPlan plan_agcn_backward(int N, int Cin, int Cout, int T, int V, int 
     AgcnBackwardPlan p;
     p.frozen = frozen;
     p.has_down = has_down;
-    if (V > 64) return p;
+    if (V > kAttentionMaxV) return p;
     const size_t fused_bytes = agcn_bwd_ws_bytes(N, Cin, Cout, T, V, S);      // 0: the moment form does not cover the shape
     p.fused = !generic && fused_bytes != 0;
     p.ws_bytes = fused_bytes;                                                 // the moment form needs neither branch
     if (p.fused) return p;
     p.recompute = recompute;
+    if (recompute) p.expand = plan_agcn_expand(N, Cin, Cout, T, V, S, has_down);
     p.inter_c_max = Cout / 4 > 0 ? Cout / 4 : 1;   // upper bound used for sizing: unit_agcn's coff_embedding = 4
     // (a workspace sized for the chain also serves the moment form, should the entry point take that after all)
     p.ws_bytes = std::max(carve_agcn_backward(nullptr, p, N, Cin, Cout, T, V, S).bytes, fused_bytes);
@@ -380,13 +385,12 @@ int launch_agcn_backward_train(const AgcnBackwardPlan &p, const float *x, const 
     int rc;
     if (p.recompute) {   // the forward kept no branches (moments path): rebuild them with the raw-mode expansion kernel
         if ((rc = launch_fill_ones_zeros(w.ones, w.zeros, Cout, st))) return rc;
-        if ((rc = launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, w.ones, w.zeros, has_down ? w.zeros : nullptr,
-                                     has_down ? w.zeros : nullptr, w.zm, N, Cin, Cout, T, V, S, 1 | 2, st)))
+        if ((rc = launch_agcn_expand(p.expand, x, P, Wd, bd, Wdown, bdown, w.ones, w.zeros, has_down ? w.zeros : nullptr,
+                                     has_down ? w.zeros : nullptr, w.zm, EXPAND_RAW | EXPAND_NO_RESIDUAL, st)))
             return rc;
         zm = w.zm;
         if (has_down) {
-            if ((rc = launch_agcn_expand(x, P, Wd, bd, Wdown, bdown, w.zeros, w.zeros, w.ones, w.zeros, w.zd, N, Cin, Cout, T, V, S,
-                                         1, st)))
+            if ((rc = launch_agcn_expand(p.expand, x, P, Wd, bd, Wdown, bdown, w.zeros, w.zeros, w.ones, w.zeros, w.zd, EXPAND_RAW, st)))
                 return rc;
             zd = w.zd;
         }

@@ -124,15 +124,30 @@ int stgcn_bn_fold(const float *weight, const float *bias, const float *running_m
                           (hipStream_t)stream);
 }
 
+// what the three graph-conv forwards check of their attention's arguments before they plan it
+#define REQUIRE_ATTENTION_ARGS(P)                                                                                          \
+    REQUIRE_PTR(x); REQUIRE_PTR(A_eff); REQUIRE_PTR(Wa); REQUIRE_PTR(ba); REQUIRE_PTR(Wb); REQUIRE_PTR(bb); REQUIRE_PTR(P); \
+    REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(inter_c); REQUIRE_POS(subsets)
+
 int stgcn_agcn_attention(const float *x, const float *A_eff, const float *Wa, const float *ba,
                          const float *Wb, const float *bb, float *P, int N, int Cin, int T, int V,
                          int inter_c, int subsets, void *stream) {
-    REQUIRE_PTR(x); REQUIRE_PTR(A_eff); REQUIRE_PTR(Wa); REQUIRE_PTR(ba); REQUIRE_PTR(Wb); REQUIRE_PTR(bb);
-    REQUIRE_PTR(P);
-    REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(inter_c); REQUIRE_POS(subsets);
-    if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "attention: N=%d > 65535 clips per call", N);
-    return launch_attention(x, A_eff, Wa, ba, Wb, bb, P, nullptr, N, Cin, T, V, inter_c, subsets,
-                            (hipStream_t)stream);
+    REQUIRE_ATTENTION_ARGS(P);
+    return launch_attention(plan_attention(N, Cin, T, V, inter_c, subsets, AttentionOut{}), AttentionIO{x, false, P}, A_eff, Wa, ba,
+                            Wb, bb, (hipStream_t)stream);
+}
+
+const char *stgcn_agcn_attention_kernel_name(int N, int Cin, int T, int V, int inter_c, int subsets, int extra) {
+    if (N <= 0 || Cin <= 0 || T <= 0 || V <= 0 || inter_c <= 0 || subsets <= 0 || extra < 0 || extra > 3) return "";
+    AttentionOut want;
+    want.kind = extra == 0 ? AttentionOut::none : extra == 1 ? AttentionOut::features : AttentionOut::frags;
+    want.split = extra == 3 ? stem_wide_split(V) : 0;
+    return attention_kernel_name(plan_attention(N, Cin, T, V, inter_c, subsets, want));
+}
+
+const char *stgcn_agcn_expand_kernel_name(int N, int Cin, int Cout, int T, int V, int subsets, int has_down) {
+    if (N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || subsets <= 0) return "";
+    return expand_kernel_name(plan_agcn_expand(N, Cin, Cout, T, V, subsets, has_down != 0));
 }
 
 int stgcn_agcn_forward(const float *x, const float *A_eff, const float *Wa, const float *ba,
@@ -148,10 +163,15 @@ int stgcn_agcn_forward(const float *x, const float *A_eff, const float *Wa, cons
         return fail(STGCN_ERR_ARG, "agcn_forward: Wdown/bdown/down_scale/down_shift must be all set or all NULL");
     if (Wdown == nullptr && Cin != Cout)
         return fail(STGCN_ERR_ARG, "agcn_forward: identity residual needs Cin == Cout (got %d, %d)", Cin, Cout);
-    int rc = stgcn_agcn_attention(x, A_eff, Wa, ba, Wb, bb, P_ws, N, Cin, T, V, inter_c, subsets, stream);
+    REQUIRE_ATTENTION_ARGS(P_ws);
+    const AttentionPlan at = plan_attention(N, Cin, T, V, inter_c, subsets, AttentionOut{});
+    const ExpandPlan ex = plan_agcn_expand(N, Cin, Cout, T, V, subsets, Wdown != nullptr);
+    if (at.kernel == AttentionKernel::none) return refused(at.why);     // (both before the first launch: a refused call
+    if (ex.kernel == ExpandKernel::none) return refused(ex.why);        //  writes nothing, P included)
+    int rc = launch_attention(at, AttentionIO{x, false, P_ws}, A_eff, Wa, ba, Wb, bb, (hipStream_t)stream);
     if (rc != STGCN_OK) return rc;
-    return launch_agcn_expand(x, P_ws, Wd, bd, Wdown, bdown, bn_scale, bn_shift, down_scale, down_shift, y, N,
-                              Cin, Cout, T, V, subsets, 0, (hipStream_t)stream);
+    return launch_agcn_expand(ex, x, P_ws, Wd, bd, Wdown, bdown, bn_scale, bn_shift, down_scale, down_shift, y, 0,
+                              (hipStream_t)stream);
 }
 
 size_t stgcn_tcn_packed_bytes(int Cin, int Cout, int K, unsigned flags) {
@@ -243,15 +263,17 @@ int stgcn_stem_attention(const float *x, const float *A_eff, const float *Wa, co
     REQUIRE_PTR(ws);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(C); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(inter_c);
     REQUIRE_POS(subsets); REQUIRE_POS(K);
-    if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "stem: N=%d > 65535 clips per call", N);
     const StemPlan pl = plan_stem(N, Cin, C, T, V, K, subsets, flags);
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "stem: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);
     char *w = (char *)ws;
     float *part = (float *)(w + pl.part_off);
-    return launch_attention(x, A_eff, Wa, ba, Wb, bb, (float *)ws, pl.part == StemPart::features ? part : nullptr, N, Cin, T, V,
-                            inter_c, subsets, (hipStream_t)stream, (flags & STGCN_IN_NTVC) != 0,
-                            pl.part == StemPart::xcopy ? part : nullptr, pl.part == StemPart::frags ? part : nullptr, pl.split,
-                            pl.bounds_off ? (float *)(w + pl.bounds_off) : nullptr);
+    AttentionOut want;
+    want.kind = pl.part == StemPart::features ? AttentionOut::features : pl.part == StemPart::frags ? AttentionOut::frags : AttentionOut::none;
+    want.split = pl.split, want.bounds = pl.bounds_off != 0;
+    const AttentionIO io{x, (flags & STGCN_IN_NTVC) != 0, (float *)ws, pl.part == StemPart::features ? part : nullptr,
+                         pl.part == StemPart::frags ? part : nullptr, pl.part == StemPart::xcopy ? part : nullptr,
+                         want.bounds ? (float *)(w + pl.bounds_off) : nullptr};
+    return launch_attention(plan_attention(N, Cin, T, V, inter_c, subsets, want), io, A_eff, Wa, ba, Wb, bb, (hipStream_t)stream);
 }
 
 int stgcn_stem_tail_prepared(const float *x, const void *ws, size_t ws_bytes, const void *prep, const float *t_shift,
@@ -297,12 +319,15 @@ int stgcn_agcn_forward_train(const float *x, const float *A_eff, const float *Wa
         return fail(STGCN_ERR_ARG, "agcn_forward_train: down branch given without its bias / BatchNorm tensors");
     if (!has_down && Cin != Cout)
         return fail(STGCN_ERR_ARG, "agcn_forward_train: identity residual needs Cin == Cout (got %d, %d)", Cin, Cout);
-    REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(subsets);
+    REQUIRE_ATTENTION_ARGS(P_ws);
     const bool frozen = (flags & STGCN_BN_FROZEN) != 0;     // running statistics: the branches are materialised
     const AgcnTrainPlan pl = plan_agcn_train(N, Cin, Cout, T, V, subsets, frozen || !has_down || save_zm || save_zd, has_down, frozen);
     // (before the attention launch: a refused call writes nothing, P included)
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "agcn_forward_train: workspace %zu B too small", ws_bytes);
-    int rc = stgcn_agcn_attention(x, A_eff, Wa, ba, Wb, bb, P_ws, N, Cin, T, V, inter_c, subsets, stream);
+    const AttentionPlan at = plan_attention(N, Cin, T, V, inter_c, subsets, AttentionOut{});
+    if (at.kernel == AttentionKernel::none) return refused(at.why);
+    if (pl.main.kernel == ExpandKernel::none) return refused(pl.main.why);
+    int rc = launch_attention(at, AttentionIO{x, false, P_ws}, A_eff, Wa, ba, Wb, bb, (hipStream_t)stream);
     if (rc != STGCN_OK) return rc;
     return launch_agcn_forward_train(pl, x, P_ws, Wd, bd, Wdown, bdown, bn_weight, bn_bias, bn_running_mean, bn_running_var,
                                      dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, momentum, eps, ws, y, save_zm,
@@ -338,8 +363,8 @@ int stgcn_agcn_backward_train(const float *x, const float *A_eff, const float *W
     } else if (Cin != Cout) {
         return fail(STGCN_ERR_ARG, "agcn_backward: identity residual needs Cin == Cout (got %d, %d)", Cin, Cout);
     }
-    if (V > 64) return fail(STGCN_ERR_UNSUPPORTED, "agcn_backward: V=%d > 64", V);
-    if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "agcn_backward: N=%d > 65535 clips per call", N);
+    if (V > kAttentionMaxV) return fail(STGCN_ERR_UNSUPPORTED, "agcn_backward: V=%d > %d", V, kAttentionMaxV);
+    if (N > kMaxGridClips) return fail(STGCN_ERR_UNSUPPORTED, "agcn_backward: N=%d > %d clips per call", N, kMaxGridClips);
     // the moment form wants what a moments-path forward leaves (no saved branches, the output y, the moments), batch
     // statistics, a down branch and no input gradient
     const bool frozen = (flags & STGCN_BN_FROZEN) != 0;
@@ -350,6 +375,7 @@ int stgcn_agcn_backward_train(const float *x, const float *A_eff, const float *W
     if (has_down ? ((zm == nullptr) != (zd == nullptr)) : (zd != nullptr))
         return fail(STGCN_ERR_ARG, "agcn_backward: give both saved branches or neither (zd only with a down branch)");
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "agcn_backward: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);
+    if (pl.recompute && pl.expand.kernel == ExpandKernel::none) return refused(pl.expand.why);
     return launch_agcn_backward_train(pl, x, A_eff, Wa, ba, Wb, bb, Wd, bd, Wdown, bdown, P, zm, zd, bn_weight, bn_bias, dbn_weight,
                                       dbn_bias, save_stats, y, dy, dWa, dba, dWb, dbb, dWd, dbd, dWdown, dbdown, dgamma, dbeta,
                                       ddgamma, ddbeta, dPA, dx, ws, N, Cin, Cout, T, V, inter_c, subsets, (hipStream_t)stream);

@@ -135,17 +135,69 @@ static inline int bn_chunks(int N, size_t plane, int C = 0) {
 int launch_bn_fold(const float *w, const float *b, const float *rm, const float *rv,
                    const float *cb, float eps, float *scale, float *shift, int C, hipStream_t st);
 
-int launch_attention(const float *x, const float *A_eff, const float *Wa, const float *ba,
-                     const float *Wb, const float *bb, float *P, float *feat, int N, int Cin, int T,
-                     int V, int inter_c, int S, hipStream_t st, bool x_ntvc = false, float *xcopy = nullptr,
-                     void *pfrag = nullptr,    // pfrag: (N,12,64) x 16 B attention B-fragments instead of features
-                     int pf_v0 = 0,            // > 0: wide frames, (N,48,64) x 16 B fragments for the joint split V0 | V - V0
-                     float *ybound = nullptr); // (N,4): max|x| and max|x| * largest column abs-sum of P_s per clip (KF7's scales)
+// graph conv forward (unit_agcn): the plans every entry point reads (agcn.hip) — which kernel and instantiation serve a
+// shape, its launch geometry and, where none does, the status and text of the refusal
+constexpr int kMaxGridClips = 65535;   // the clip index rides in a 16-bit grid dimension
+constexpr int kAttentionMaxV = 64;     // joints the attention kernels (and with them the graph conv) cover
+static inline bool agcn_stem_class(int Cin, int S) { return Cin == 3 && S == 3; }   // what the folded forms are written for
+struct Refusal { stgcn_status status = STGCN_OK; char msg[160] = ""; };   // of a plan whose kernel is `none`
+static inline int refused(const Refusal &r) { return fail(r.status, "%s", r.msg); }
 
-int launch_agcn_expand(const float *x, const float *P, const float *Wd, const float *bd,
-                       const float *Wdown, const float *bdown, const float *bn_scale,
-                       const float *bn_shift, const float *down_scale, const float *down_shift,
-                       float *y, int N, int Cin, int Cout, int T, int V, int S, int mode, hipStream_t st);
+enum class AttentionKernel { none, folded, generic_mfma, generic_valu };
+struct AttentionOut {                  // what a call produces besides P
+    enum Kind { none, features, frags } kind = none;   // features: (N, T*V, 16); frags: P as bf16 hi/lo MFMA B fragments
+    int split = 0;                     // frags of wide frames: (N,48,64) x 16 B for the joint split V0 | V - V0, else (N,12,64)
+    bool bounds = false;               // (N,4): max|x| and max|x| * largest column abs-sum of P_s per clip (KF7's scales)
+};
+struct AttentionTile {                 // the chosen kernel's geometry: written by its *_covers, read by launch_attention
+    int maxb = 0, nw = 0, ks = 0, mb = 0, maxit = 0;   // folded<MAXB,NW>, generic_mfma<KS,MAXB>, generic_valu<MAXIT>
+    int TC = 0, pitch = 0, slice_off = 0, sq_behind = 0, gx = 0, gy = 0;
+    size_t lds = 0;
+};
+struct AttentionPlan {
+    AttentionKernel kernel = AttentionKernel::none;
+    AttentionTile tile;
+    AttentionOut out;
+    int N = 0, Cin = 0, T = 0, V = 0, inter_c = 0, S = 0;
+    Refusal why;
+};
+AttentionPlan plan_attention(int N, int Cin, int T, int V, int inter_c, int S, AttentionOut want);
+const char *attention_kernel_name(const AttentionPlan &p);   // with its template arguments; "" for none
+bool attention_emits_features(int Cin, int V, int S);
+struct AttentionIO {                   // x is (N,Cin,T,V), or (N,T,V,Cin) with x_ntvc; the outputs AttentionOut names, or NULL;
+    const float *x;                    // xcopy (optional): channel-major copy of x for kernels downstream
+    bool x_ntvc;
+    float *P, *feat = nullptr;
+    void *pfrag = nullptr;
+    float *xcopy = nullptr, *ybound = nullptr;
+};
+// its kernels (agcn_attention.hip): one coverage predicate each, called by plan_attention only, and the launcher
+bool attention_folded_covers(int N, int Cin, int T, int V, int inter_c, int S, bool features, AttentionTile &t);
+bool attention_generic_mfma_covers(int N, int Cin, int T, int V, int inter_c, int S, AttentionTile &t);
+bool attention_generic_valu_covers(int N, int Cin, int T, int V, int inter_c, int S, AttentionTile &t);
+int launch_attention(const AttentionPlan &p, const AttentionIO &io, const float *A_eff, const float *Wa, const float *ba,
+                     const float *Wb, const float *bb, hipStream_t st);
+
+enum class ExpandKernel { none, small4, small, mfma, generic };
+struct ExpandTile { int now = 0, npb = 0, TF = 0, gx = 0, gy = 0; size_t lds = 0; };   // mfma<NOW,NPB>
+struct ExpandPlan {
+    ExpandKernel kernel = ExpandKernel::none;
+    ExpandTile tile;
+    int N = 0, Cin = 0, Cout = 0, T = 0, V = 0, S = 0;
+    Refusal why;
+};
+ExpandPlan plan_agcn_expand(int N, int Cin, int Cout, int T, int V, int S, bool has_down);
+const char *expand_kernel_name(const ExpandPlan &p);
+constexpr int EXPAND_RAW = 1;           // `mode` of the expansion: no ReLU (the pre-activation value) ...
+constexpr int EXPAND_NO_RESIDUAL = 2;   // ... and the identity residual left out
+// its kernels (agcn_expand.hip), as above; has_down (Wdown is given) only decides between the folded forms and the rest
+bool agcn_expand_small4_covers(int N, int Cin, int Cout, int T, int V, int S, bool has_down, ExpandTile &t);
+bool agcn_expand_small_covers(int N, int Cin, int Cout, int T, int V, int S, bool has_down, ExpandTile &t);
+bool agcn_expand_mfma_covers(int N, int Cin, int Cout, int T, int V, int S, ExpandTile &t);
+bool agcn_expand_generic_covers(int N, int Cin, int T, int V, int S, ExpandTile &t);
+int launch_agcn_expand(const ExpandPlan &p, const float *x, const float *P, const float *Wd, const float *bd,
+                       const float *Wdown, const float *bdown, const float *bn_scale, const float *bn_shift,
+                       const float *down_scale, const float *down_shift, float *y, int mode, hipStream_t st);
 
 // temporal conv (Unit2D): the plan every entry point reads (tcn.hip; the packed blob's layout is described there)
 enum class TcnKernel { none, valu, valu_joint_axis, mfma_f32, bf16_small, v4, v6 };
@@ -200,7 +252,6 @@ int launch_stem_bf16_small(const float *x, const float *P, const float *W12, con
                            int C, int T, int V, int K, unsigned flags, hipStream_t st);
 
 // large-tile persistent bf16 stem, eight waves (stem_bf16_v4.hip); *frags: the 256-pixel tile (features from fragments)
-bool attention_emits_features(int Cin, int V, int S);
 bool stem_v4_supported(int Cin, int C, int T, int V, int K, int S, unsigned flags, bool *frags = nullptr);
 int launch_stem_v4(const float *x, bool x_ntvc, const float *feat, const void *prep_w12, const void *Wp, const float *shift,
                    void *out, int N, int C, int T, int V, int K, unsigned flags, hipStream_t st);  // honours STGCN_OUT_NTVC
@@ -319,7 +370,8 @@ int launch_tcn_backward_train(const TcnBackwardPlan &p, const float *x, const fl
 struct AgcnTrainPlan {
     bool frozen = false, has_down = false;
     bool moments = false;        // batch statistics from the feature moments: the two pre-BatchNorm branches are never written
-    bool down_as_gemm = false;   // materialising path: conv_down as one plain product (outside the stem class)
+    bool down_as_gemm = false;   // materialising path: conv_down as one plain product (outside Cin = 3)
+    ExpandPlan main, down;       // the expansion that writes y (moments) or the main branch; the one that writes the down branch
     size_t ws_bytes = 0;
 };
 // materialise: the branches are to be saved, the statistics are frozen or there is no down branch (the size query's hint)
@@ -335,7 +387,8 @@ struct AgcnBackwardPlan {
     bool fused = false;          // the moment form (agcn_backward.hip); else the generic GEMM chain
     bool recompute = false;      // generic: the forward kept no branches, they are rebuilt in the workspace
     int inter_c_max = 0;         // generic: the embedding width the workspace is sized for
-    size_t ws_bytes = 0;         // 0: V > 64
+    ExpandPlan expand;           // recompute: the expansion that rebuilds either branch
+    size_t ws_bytes = 0;         // 0: V > kAttentionMaxV
 };
 // generic: the caller wants the GEMM chain (input gradient, identity residual, saved branches, frozen statistics)
 AgcnBackwardPlan plan_agcn_backward(int N, int Cin, int Cout, int T, int V, int S, bool recompute, bool generic, bool has_down,

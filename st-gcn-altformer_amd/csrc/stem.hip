@@ -66,7 +66,7 @@ StemPlan plan_stem(int N, int Cin, int C, int T, int V, int K, int S, unsigned f
         p.part_off = p.ws_bytes;
         p.ws_bytes += (size_t)N * Cin * T * V * sizeof(float);
     }
-    if (Cin != 3 || S != 3 || T < 1) return p;
+    if (!agcn_stem_class(Cin, S) || T < 1) return p;
     if (math == STGCN_MATH_BF16X3 || math == STGCN_MATH_BF16) {
         if (stem_bf16_small_supported(C, T, V, K, flags)) p.kernel = StemKernel::bf16_small;
     } else if (math == STGCN_MATH_F32 && stem_f32_supported(C, T, V, K)) {
@@ -104,7 +104,7 @@ int launch_stem_prepare(const float *Wd, const float *bd, const float *Wdown, co
 
 int launch_stem(const StemPlan &p, const float *x, const void *ws, const void *prep, const float *t_shift, void *out, int N,
                 int Cin, int C, int T, int V, int S, int K, unsigned flags, hipStream_t st) {
-    if (N > 65535) return fail(STGCN_ERR_UNSUPPORTED, "stem: N=%d > 65535 clips per call", N);
+    if (N > kMaxGridClips) return fail(STGCN_ERR_UNSUPPORTED, "stem: N=%d > %d clips per call", N, kMaxGridClips);
     const char *w = (const char *)ws, *b = (const char *)prep;
     const float *part = (const float *)(w + p.part_off), *P = (const float *)ws;
     const bool x_ntvc = (flags & STGCN_IN_NTVC) != 0;

@@ -54,6 +54,8 @@ PROTOTYPES = {
     "stgcn_bn_fold": (c_int, [_P, _P, _P, _P, _P, c_float, _P, _P, c_int, _P]),
     "stgcn_agcn_attention": (c_int, [_P] * 7 + [c_int] * 6 + [_P]),
     "stgcn_agcn_forward": (c_int, [_P] * 16 + [c_int] * 7 + [_P]),
+    "stgcn_agcn_attention_kernel_name": (c_char_p, [c_int] * 7),
+    "stgcn_agcn_expand_kernel_name": (c_char_p, [c_int] * 7),
     "stgcn_tcn_packed_bytes": (c_size_t, [c_int, c_int, c_int, c_uint]),
     "stgcn_tcn_supported": (c_int, [c_int] * 6 + [c_uint]),
     "stgcn_tcn_kernel_name": (c_char_p, [c_int] * 6 + [c_uint]),

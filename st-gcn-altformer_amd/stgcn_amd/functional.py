@@ -93,6 +93,15 @@ def agcn_forward(x, A_eff, Wa, ba, Wb, bb, Wd, bd, Wdown, bdown, bn_scale, bn_sh
     return y, P
 
 
+def agcn_attention_kernel_name(N, Cin, T, V, inter_c, S, extra=0) -> str:
+    """Kernel (with template arguments) that computes P; extra: 1 features, 2 fragments, 3 fragments of a wide frame."""
+    return _capi.lib().stgcn_agcn_attention_kernel_name(N, Cin, T, V, inter_c, S, extra).decode()
+
+
+def agcn_expand_kernel_name(N, Cin, Cout, T, V, S, has_down=True) -> str:
+    return _capi.lib().stgcn_agcn_expand_kernel_name(N, Cin, Cout, T, V, S, int(has_down)).decode()
+
+
 def tcn_supported(Cin, Cout, T, V, K, stride, math=MATH_F32) -> bool:
     return bool(_capi.lib().stgcn_tcn_supported(Cin, Cout, T, V, K, stride, _flags(math, False)))
 

@@ -28,4 +28,5 @@ for m in ("0", "2048"):
     for _ in range(20): run()
     e1.record(); torch.cuda.synchronize()
     res[m] = (e0.elapsed_time(e1) / 20 * 1e3, P)
+    print(f"STGCN_ABLATE={m}: {F.agcn_attention_kernel_name(a.clips, a.cin, a.frames, a.joints, ic, 3)}")
 print(f"matrix cores: {res['0'][0]:.1f} us   VALU kernel (diagnostic library only): {res['2048'][0]:.1f} us   max |dP| {float((res['0'][1]-res['2048'][1]).abs().max()):.2e}")
