@@ -446,7 +446,8 @@ int stgcn_vit_attention_bf16(const void *qkv, void *out, int B, int L, int heads
  * Arithmetic: `flags` as in the forward select f32 / bf16x3 for the dgrads (which run the forward's linear kernel on
  * transposed weights) and STGCN_VIT_QKV_F32 keeps the qkv dgrad in f32; weight gradients, LayerNorm and attention
  * backward always run in fp32 (v_mfma_f32_32x32x2_f32 where they are products).  STGCN_VIT_TRAIN_BF16 (at the end of this
- * header, opt-in) moves the linears' products, weight gradients included, to bf16 operands. */
+ * header, opt-in) moves the linears' products, weight gradients included, to bf16 operands, and
+ * STGCN_VIT_TRAIN_ATTN_BF16 (there too, opt-in) the attention forward and backward of sequences of up to 256 tokens. */
 #define STGCN_VIT_DGELU 0x4000u      /* stgcn_vit_linear_backward: dx is multiplied by GELU'(h_pre) (exact erf form)    */
 #define STGCN_VIT_ACCUMULATE 0x8000u /* stgcn_vit_linear_backward: dx += instead of dx =                                 */
 /* Backward of y = a W^T + b:  dx (M,K) = dy W [* GELU'(h_pre (M,K))] [+ dx],  dW (Nout,K) = dy^T a,  db (Nout) = column sums
@@ -528,6 +529,38 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
 #define STGCN_VIT_TRAIN_BF16 0x200000u
 int stgcn_vit_block_train_bf16_supported(int L, int D, int heads, int hidden);
 int stgcn_vit_linear_backward_bf16_supported(int M, int K, int Nout);
+
+/* ---- ViT block: training attention on bf16 matrix operands (additive to ABI 11: one flag bit, two entry points, two queries;
+ * opt-in) ----
+ * STGCN_VIT_TRAIN_ATTN_BF16 is accepted by exactly stgcn_vit_block_forward_train and stgcn_vit_block_backward, with every flag
+ * combination that is legal without it (with or without STGCN_VIT_TRAIN_BF16, low bits f32 or bf16x3).  Where L <= 256 the
+ * attention forward and backward of the call then run on v_mfma_f32_32x32x16_bf16 instead of the fp32 matrix cores; above,
+ * the call runs the fp32 streaming kernels it runs without the bit, bit for bit.  With r = round to nearest-even bf16 and every
+ * sum in fp32, per (sequence, head):
+ *   s = scale * (qh kh^T + qh kl^T + ql kh^T), qh = r(q), ql = r(q - qh), kh and kl alike, of the unscaled fp32 q and k as they
+ *       lie in the packed qkv (a rounded q or k is multiplied by the size of the scores: the score product takes three terms);
+ *   m = max s, p = exp(s - m), l = sum p (of the unrounded p), keys past L score -inf;
+ *   forward : out = (r(p) r(v)) / l, stored fp32;
+ *   backward: P = p / l recomputed as above, dP = r(dO) r(v)^T, delta_i = sum_j P_ij dP_ij (NOT rowsum(dO * out): `out` is an
+ *             argument and is not read), dS = P (dP - delta), dV = r(P)^T r(dO), dQ = scale r(dS) r(k), dK = scale r(dS)^T r(q),
+ *             dqkv stored fp32, packed as qkv.
+ * LayerNorm, GELU, residuals, row factors and the linears are what they are without the bit; `saved` and the workspace keep
+ * layout and size, so every *_bytes query answers for the mode too.  Results are bit-identical from run to run.  Gate with
+ * STGCN_VIT_TRAIN_BF16: 1e-2 of max|.| per tensor, as that mode alone.
+ * stgcn_vit_block_forward, stgcn_vit_linear and stgcn_vit_linear_backward answer STGCN_ERR_ARG to the bit, after their older
+ * flag refusals and before the pointers are looked at.
+ * The value is 0x800000: 0x400000 stays unassigned (the host test of STGCN_VIT_TRAIN_BF16 uses it as its unknown bit).
+ * stgcn_vit_attention_train_bf16 / stgcn_vit_attention_backward_bf16: the two kernels alone, arguments as stgcn_vit_attention /
+ * stgcn_vit_attention_backward; covered (stgcn_vit_attention_train_bf16_supported): 1 <= L <= 256, head_dim 32 / 64.
+ * stgcn_vit_block_train_attn_bf16_supported: 1 where a block call with the bit runs these kernels, 0 where the bit changes
+ * nothing (256 < L) or the shape is not covered. */
+#define STGCN_VIT_TRAIN_ATTN_BF16 (STGCN_VIT_TRAIN_BF16 << 2)
+int stgcn_vit_attention_train_bf16_supported(int L, int heads, int head_dim);
+int stgcn_vit_attention_train_bf16(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale,
+                                   void *stream);
+int stgcn_vit_attention_backward_bf16(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L,
+                                      int heads, int head_dim, float scale, void *stream);
+int stgcn_vit_block_train_attn_bf16_supported(int L, int D, int heads, int hidden);
 
 #ifdef __cplusplus
 }

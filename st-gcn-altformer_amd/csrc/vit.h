@@ -34,7 +34,7 @@ inline bool math_ok(unsigned flags) {
 
 inline bool linear_ok(int K, int Nout, bool ln) { return K % 32 == 0 && Nout >= 1 && (!ln || K <= kMaxLnDim); }
 
-// the resident attention kernels (forward, bf16 forward, backward) and the streaming ones (forward, backward)
+// the resident attention kernels (forward, bf16 forward, backward, the training bf16 pair) and the streaming ones (forward, backward)
 inline bool attention_resident_ok(int L, int heads, int hd) { return L >= 1 && L <= kMaxL && heads >= 1 && (hd == 32 || hd == 64); }
 inline bool attention_stream_ok(int L, int heads, int hd) {
     return L >= 1 && L <= kMaxStreamL && heads >= 1 && (hd == 32 || hd == 64);
@@ -79,8 +79,10 @@ constexpr const char *kBlockEntryName[] = {"stgcn_vit_block_forward", "stgcn_vit
                                            "stgcn_vit_linear_backward"};
 // resident (launch_attention_packed, launch_attention_backward): K and V of a (sequence, head) on chip, up to kMaxL tokens;
 // stream (launch_attention_stream, launch_attention_backward_stream): K and V in key tiles through LDS, above kMaxL and up to
-// kMaxStreamL; resident_bf16 (launch_attention_bf16): the resident form on bf16 qkv / out, STGCN_VIT_BF16 only.
-enum class BlockAttention { none, resident, stream, resident_bf16 };
+// kMaxStreamL; resident_bf16 (launch_attention_bf16): the resident form on bf16 qkv / out, STGCN_VIT_BF16 only;
+// resident_train_bf16 (launch_attention_train_bf16, launch_attention_backward_bf16): the resident form on fp32 qkv / out with
+// bf16 matrix operands, the two training entries with STGCN_VIT_TRAIN_ATTN_BF16 up to kMaxL tokens.
+enum class BlockAttention { none, resident, stream, resident_bf16, resident_train_bf16 };
 
 struct BlockPlan {
     BlockEntry entry;
@@ -114,10 +116,14 @@ inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidde
                         "stgcn_vit_linear_backward only)";
         else if (bf16 && (flags & STGCN_VIT_QKV_F32))
             p.refusal = "STGCN_VIT_BF16 and STGCN_VIT_QKV_F32 exclude each other";
+        else if (flags & STGCN_VIT_TRAIN_ATTN_BF16)
+            p.refusal = "STGCN_VIT_TRAIN_ATTN_BF16 is a training mode (stgcn_vit_block_forward_train, stgcn_vit_block_backward only)";
     } else if (flags & STGCN_VIT_BF16) {
         p.refusal = "STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)";
     } else if (flags & STGCN_VIT_TILE_MASK) {
         p.refusal = "training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)";
+    } else if (entry == BlockEntry::linear_backward && (flags & STGCN_VIT_TRAIN_ATTN_BF16)) {
+        p.refusal = "STGCN_VIT_TRAIN_ATTN_BF16 is a mode of the block (stgcn_vit_block_forward_train, stgcn_vit_block_backward only)";
     }
     // Arithmetic.  STGCN_VIT_QKV_F32 moves the qkv linear (and its dgrad) to f32: an error in q or k is multiplied by the size
     // of the scores before the exponential.  STGCN_VIT_BF16 (inference): every product on operands rounded to bf16, the three
@@ -141,8 +147,13 @@ inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidde
     p.resident = L <= kMaxL;
     p.sized = L >= 1 && L <= p.max_len && D >= 1 && hidden >= 1 && D % 64 == 0 && hidden % 64 == 0;
     const bool heads_ok = heads >= 1 && D % heads == 0 && (D / heads == 32 || D / heads == 64) && D <= kMaxLnDim;
+    // STGCN_VIT_TRAIN_ATTN_BF16 moves the resident attention of the two training entries to bf16 operands; the streaming
+    // lengths run the fp32 kernels they run without it.
+    const bool attn_bf16 = !inference && (flags & STGCN_VIT_TRAIN_ATTN_BF16) != 0;
     if (p.sized && heads_ok)
-        p.attention = bf16 ? BlockAttention::resident_bf16 : p.resident ? BlockAttention::resident : BlockAttention::stream;
+        p.attention = bf16 ? BlockAttention::resident_bf16
+                      : !p.resident ? BlockAttention::stream
+                      : attn_bf16 ? BlockAttention::resident_train_bf16 : BlockAttention::resident;
     p.covered = p.attention != BlockAttention::none && low_ok;
     return p;
 }
@@ -229,6 +240,28 @@ inline size_t attention_bf16_lds_bytes(int L, int hd) {
     return (size_t)g * ((size_t)rows * (hd + 8) + (size_t)hd * (rows + 8)) * 2;
 }
 int launch_attention_bf16(const void *qkv, void *out, int B, int L, int H, int hd, float scale, hipStream_t st);
+
+// The resident attention for training on bf16 matrix operands (vit_attention_train_bf16.hip): fp32 qkv, out, dout and dqkv,
+// L <= kMaxL, hd in {32, 64}.  Scores scale * (qh kh^T + qh kl^T + ql kh^T) of the split q and k, every other product on
+// operands rounded once; the backward's delta is sum P dP of its own products and `out` is not read.  LDS per workgroup, for
+// the pairs it packs, keys = L rounded up to 32: forward K hi, K lo as [keys][hd + 8] and V^T as [hd][keys + 8]; backward
+// three row tiles, two transposed ones (one where the five would not fit: `split`) and 16 bytes of statistics per query.
+constexpr int attention_train_bf16_pairs(int L) { return (L + 31) / 32 >= 4 ? 1 : 4 / ((L + 31) / 32); }
+constexpr size_t attention_train_bf16_lds_bytes(int L, int hd) {
+    const size_t rows = (size_t)((L + 31) / 32) * 32;
+    return (size_t)attention_train_bf16_pairs(L) * (2 * rows * (hd + 8) + (size_t)hd * (rows + 8)) * 2;
+}
+constexpr size_t attention_bwd_bf16_bytes(int L, int hd, int transposed) {
+    const size_t rows = (size_t)((L + 31) / 32) * 32;
+    return (size_t)attention_train_bf16_pairs(L) * ((3 * rows * (hd + 8) + (size_t)transposed * hd * (rows + 8)) * 2 + rows * 16);
+}
+constexpr bool attention_bwd_bf16_split(int L, int hd) { return attention_bwd_bf16_bytes(L, hd, 2) > (size_t)kLdsBytes; }
+constexpr size_t attention_bwd_bf16_lds_bytes(int L, int hd) {
+    return attention_bwd_bf16_bytes(L, hd, attention_bwd_bf16_split(L, hd) ? 1 : 2);
+}
+int launch_attention_train_bf16(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
+int launch_attention_backward_bf16(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int H, int hd,
+                                   float scale, hipStream_t st);
 
 // ---- backward (vit_backward.hip) ----------------------------------------------------------------------------------------
 // Wt (cols, rows_pad) = W (rows, cols)^T, the columns from `rows` to rows_pad zero-filled: the dgrad dX = dY W is the

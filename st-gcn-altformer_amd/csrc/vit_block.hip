@@ -33,6 +33,9 @@ int block_forward(const BlockPlan &plan, const float *x, const BlockWeights &w, 
             case BlockAttention::resident: rc = launch_attention_packed((float *)qkv, (float *)att, nb, L, heads, hd, scale, st); break;
             case BlockAttention::stream: rc = launch_attention_stream((float *)qkv, (float *)att, nb, L, heads, hd, scale, st); break;
             case BlockAttention::resident_bf16: rc = launch_attention_bf16(qkv, att, nb, L, heads, hd, scale, st); break;
+            case BlockAttention::resident_train_bf16:
+                rc = launch_attention_train_bf16((float *)qkv, (float *)att, nb, L, heads, hd, scale, st);
+                break;
             case BlockAttention::none: rc = fail(STGCN_ERR_UNSUPPORTED, "vit block: no attention form planned"); break;
         }
         if (rc) return rc;
@@ -72,6 +75,9 @@ int stgcn_vit_linear(const float *x, const float *W, const float *bias, const fl
     if (flags & STGCN_VIT_TRAIN_BF16)
         return fail(STGCN_ERR_ARG, "stgcn_vit_linear: STGCN_VIT_TRAIN_BF16 is a training mode (stgcn_vit_block_forward_train, "
                     "stgcn_vit_block_backward, stgcn_vit_linear_backward only)");
+    if (flags & STGCN_VIT_TRAIN_ATTN_BF16)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_linear: STGCN_VIT_TRAIN_ATTN_BF16 is a training mode of the block "
+                    "(stgcn_vit_block_forward_train, stgcn_vit_block_backward only)");
     if (!x || !W || !y || M < 1 || K < 1 || Nout < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: null pointer or empty shape");
     if ((ln_weight == nullptr) != (ln_bias == nullptr)) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: ln_weight and ln_bias go together");
     if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: y must not alias x");

@@ -7,13 +7,15 @@
 //   dn   = dhid W1                              LN2 backward: dx1 = dy + ...,  a = LN2(x1),  dnorm2
 //                                               dW1, db1   = dhid^T a
 //   datt = (s1 dx1) Wproj                       dWproj, dbproj = (s1 dx1)^T att
-//   dqkv = attention backward(qkv, att, datt)     resident up to 256 tokens, streaming above
+//   dqkv = attention backward(qkv, att, datt)     resident up to 256 tokens (fp32, or on bf16 operands with
+//                                               STGCN_VIT_TRAIN_ATTN_BF16), streaming above
 //   dn   = dqkv Wqkv                            LN1 backward: dx = dx1 + ...,  a = LN1(x),   dnorm1
 //                                               dWqkv, dbqkv = dqkv^T a
 // The dgrads are the forward linear kernel on weights transposed once per call; the weight gradients run on the fp32
 // matrix cores, or on bf16 operands with STGCN_VIT_TRAIN_BF16.  Which arithmetic each product takes and which attention form
-// runs is vit.h's plan_block; LayerNorm, attention, bias, GELU / GELU', row factors, residuals, bias gradients and every
-// stored tensor are fp32 in every mode, so `saved` and the workspace have one layout.  Parameter gradients of the second and
+// runs is vit.h's plan_block; LayerNorm, the soft-max, bias, GELU / GELU', row factors, residuals, bias gradients and every
+// stored tensor are fp32 in every mode (the attention's products too, unless STGCN_VIT_TRAIN_ATTN_BF16 moves the resident
+// form to bf16 operands), so `saved` and the workspace have one layout.  Parameter gradients of the second and
 // later slabs are added onto the first slab's in slab order, so the result does not depend on anything but the shapes.
 #include "vit.h"
 
@@ -189,6 +191,29 @@ int stgcn_vit_attention_backward_stream(const float *qkv, const float *out, cons
                                             static_cast<hipStream_t>(stream));
 }
 
+int stgcn_vit_attention_train_bf16_supported(int L, int heads, int head_dim) {
+    return attention_resident_ok(L, heads, head_dim) ? 1 : 0;
+}
+
+int stgcn_vit_attention_train_bf16(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream) {
+    REQUIRE_PTR(qkv); REQUIRE_PTR(out);
+    REQUIRE_POS(B); REQUIRE_POS(L); REQUIRE_POS(heads);
+    if (!stgcn_vit_attention_train_bf16_supported(L, heads, head_dim))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention_train_bf16: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)",
+                    L, head_dim, kMaxL);
+    return launch_attention_train_bf16(qkv, out, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
+}
+
+int stgcn_vit_attention_backward_bf16(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int heads,
+                                      int head_dim, float scale, void *stream) {
+    REQUIRE_PTR(qkv); REQUIRE_PTR(out); REQUIRE_PTR(dout); REQUIRE_PTR(dqkv);
+    REQUIRE_POS(B); REQUIRE_POS(L); REQUIRE_POS(heads);
+    if (!stgcn_vit_attention_train_bf16_supported(L, heads, head_dim))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention_backward_bf16: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)",
+                    L, head_dim, kMaxL);
+    return launch_attention_backward_bf16(qkv, out, dout, dqkv, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
+}
+
 size_t stgcn_vit_layernorm_backward_ws_bytes(int M, int D) {
     if (M < 1 || D < 1 || D % 4 != 0) return 0;
     return LnBwdWs(nullptr, M, D).total;
@@ -230,6 +255,11 @@ int stgcn_vit_block_train_long_supported(int L, int D, int heads, int hidden) {
 
 int stgcn_vit_block_train_bf16_supported(int L, int D, int heads, int hidden) {
     return plan_block(BlockEntry::forward_train, L, D, heads, hidden, STGCN_VIT_TRAIN_BF16).covered ? 1 : 0;
+}
+
+int stgcn_vit_block_train_attn_bf16_supported(int L, int D, int heads, int hidden) {
+    const BlockPlan p = plan_block(BlockEntry::forward_train, L, D, heads, hidden, STGCN_VIT_TRAIN_ATTN_BF16);
+    return p.covered && p.attention == BlockAttention::resident_train_bf16 ? 1 : 0;
 }
 
 size_t stgcn_vit_block_train_long_saved_bytes(int B, int L, int D, int hidden) {
@@ -318,9 +348,15 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
         if ((rc = launch_linear(w.dx1, w.wt_proj, nullptr, nullptr, nullptr, nullptr, 0.f, w.datt, M, D, D, false, math, st, e1)))
             return rc;
         if ((rc = wgrad(plan, w.dx1, att, s1, L, dWproj, dbproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
-        rc = plan.attention == BlockAttention::stream
-                 ? launch_attention_backward_stream(qkv, att, w.datt, w.dqkv, tw.att_stats, nb, L, heads, D / heads, scale, st)
-                 : launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st);
+        switch (plan.attention) {
+            case BlockAttention::stream:
+                rc = launch_attention_backward_stream(qkv, att, w.datt, w.dqkv, tw.att_stats, nb, L, heads, D / heads, scale, st);
+                break;
+            case BlockAttention::resident_train_bf16:
+                rc = launch_attention_backward_bf16(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st);
+                break;
+            default: rc = launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st); break;
+        }
         if (rc) return rc;
         if ((rc = launch_linear(w.dqkv, w.wt_qkv, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, 3 * D, D, false, math_qkv, st)))
             return rc;

@@ -47,6 +47,13 @@ attention, GELU, bias gradients and every stored tensor stay fp32; gradients hol
 A ``Block.train_math_mode`` that is not None wins over ``math_mode`` and the environment in the training branch only; this
 ``'bf16'`` is not the inference ``'bf16'`` (which also rounds qkv, the soft-max weights and the stored intermediates).
 
+Arithmetic of the training path's attention (``set_train_attention_math`` / env ``STGCN_VIT_TRAIN_ATTENTION``): ``'f32'`` (the
+default: the fp32 kernels in every training arithmetic above) or ``'bf16'`` (opt-in): for sequences of up to 256 tokens the
+attention forward and backward on bf16 matrix cores, the scores as three bf16 products of q and k split into a high and a low
+part, every other product on operands rounded once, sums and everything stored in fp32.  It adds ``VIT_TRAIN_ATTN_BF16`` to
+whatever ``set_train_math`` chose (meant to go with ``'bf16'`` there) and never reaches the inference path; longer sequences
+run the fp32 streaming kernels either way.
+
 Nothing is packed or cached: the kernels read ``nn.Linear.weight`` as stored, so an ``nn.DataParallel`` replica (whose
 parameters are plain attributes, fresh clones on every call) needs no staging on its master.
 """
@@ -61,7 +68,8 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import functional as F
-from ._capi import MATH_BF16X3, MATH_F32, VIT_BF16, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK, VIT_TRAIN_BF16
+from ._capi import (MATH_BF16X3, MATH_F32, VIT_BF16, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK, VIT_TRAIN_ATTN_BF16,
+                    VIT_TRAIN_BF16)
 from .modules import Unit2D, enable_stem_fusion, import_class, unit_agcn
 
 HEAD_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32, "bf16": VIT_BF16}
@@ -157,6 +165,27 @@ def set_head_math(module: nn.Module, mode) -> None:
     for sub in module.modules():
         if isinstance(sub, Block):
             sub.math_mode = m
+
+
+TRAIN_ATTENTION_MATH = ("f32", "bf16")
+
+
+def _default_train_attention() -> str:
+    mode = os.environ.get("STGCN_VIT_TRAIN_ATTENTION", "f32").lower()
+    if mode not in TRAIN_ATTENTION_MATH:
+        raise KeyError(mode)
+    return mode
+
+
+def set_train_attention_math(module: nn.Module, mode) -> None:
+    """Arithmetic of the attention in the HIP training path of every ``Block`` below: 'f32' (the fp32 kernels) | 'bf16' (forward
+    and backward on bf16 matrix operands for sequences of up to 256 tokens, opt-in; see the module docstring), or None for what
+    env ``STGCN_VIT_TRAIN_ATTENTION`` gives, else 'f32'.  ``set_train_math`` and inference are not touched."""
+    if mode is not None and mode not in TRAIN_ATTENTION_MATH:
+        raise KeyError(mode)
+    for sub in module.modules():
+        if isinstance(sub, Block):
+            sub.train_attention_mode = mode
 
 
 def set_train_math(module: nn.Module, mode) -> None:
@@ -272,6 +301,7 @@ class Block(nn.Module):
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self.math_mode = None                  # None: _default_head_math() at call time
         self.train_math_mode = None            # set_train_math: the training branch's arithmetic; None: as math_mode decides
+        self.train_attention_mode = None       # set_train_attention_math: 'f32' | 'bf16'; None: env STGCN_VIT_TRAIN_ATTENTION, else 'f32'
         self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
         self.hip_min_tokens = HIP_MIN_TOKENS   # set_hip_min_tokens
         self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
@@ -340,16 +370,20 @@ class Block(nn.Module):
     def _hip_flags(self, x: torch.Tensor, train: bool) -> int:
         """The flag word this call hands to its HIP path, resolved here and nowhere else.  Training: ``train_math_mode``
         (``set_train_math`` wins), else ``math_mode``, else ``_default_train_math()``; tile forms and ``HEAD_MATH['bf16']`` are
-        inference modes that never reach a training entry point (a block set to the latter trains in its path's default).
+        inference modes that never reach a training entry point (a block set to the latter trains in its path's default);
+        ``train_attention_mode`` (``set_train_attention_math``), else env ``STGCN_VIT_TRAIN_ATTENTION``, adds
+        ``VIT_TRAIN_ATTN_BF16`` on top of any of them when it says ``'bf16'``, and nothing otherwise.
         Inference: ``math_mode``, else ``_default_head_math()``; ``'bf16'`` only where its resident form covers the length
         (longer sequences run the default arithmetic, still on HIP); ``small_tiles`` adds ``VIT_TILE_AUTO`` unless
         ``math_mode`` forces a form."""
         if train:
+            attn = self.train_attention_mode if self.train_attention_mode is not None else _default_train_attention()
+            bit = VIT_TRAIN_ATTN_BF16 if attn == "bf16" else 0
             if self.train_math_mode is not None:
-                return self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16)
+                return self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16) | bit
             if self.math_mode is None or self.math_mode & VIT_BF16:
-                return _default_train_math()
-            return self.math_mode & ~VIT_TILE_MASK
+                return _default_train_math() | bit
+            return self.math_mode & ~VIT_TILE_MASK | bit
         math = _default_head_math() if self.math_mode is None else self.math_mode
         if math & VIT_BF16 and not F.vit_block_forward_bf16_supported(x.shape[1], x.shape[2], self.attn.num_heads,
                                                                       self.mlp.fc1.out_features):

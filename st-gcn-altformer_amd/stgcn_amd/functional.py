@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _capi
-from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_BF16, VIT_TRAIN_BF16  # noqa: F401 (re-export)
+from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_BF16, VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16  # noqa: F401 (re-export)
 
 BN_EPS = 1e-5
 
@@ -532,8 +532,9 @@ def _vit_flags(math: int) -> int:
 
 
 def _vit_train_flags(math: int) -> int:
-    """What the training entry points read of ``math``: the inference bits (which they refuse by name) and VIT_TRAIN_BF16."""
-    return _vit_flags(math) | (math & _capi.VIT_TRAIN_BF16)
+    """What the training entry points read of ``math``: the inference bits (which they refuse by name), VIT_TRAIN_BF16 and
+    VIT_TRAIN_ATTN_BF16."""
+    return _vit_flags(math) | (math & (_capi.VIT_TRAIN_BF16 | _capi.VIT_TRAIN_ATTN_BF16))
 
 
 def _bytes(dev, nbytes):
@@ -668,6 +669,17 @@ def vit_attention(qkv, heads, scale=None) -> torch.Tensor:
     return _vit_attention("stgcn_vit_attention_stream" if stream else "stgcn_vit_attention", qkv, heads, scale)
 
 
+def vit_attention_train_bf16_supported(L, heads, head_dim) -> bool:
+    """Coverage of ``vit_attention_train_bf16`` / ``vit_attention_backward_bf16``: the resident lengths (L <= 256)."""
+    return bool(_capi.lib().stgcn_vit_attention_train_bf16_supported(L, heads, head_dim))
+
+
+def vit_attention_train_bf16(qkv, heads, scale=None) -> torch.Tensor:
+    """The training forward's attention of ``VIT_TRAIN_ATTN_BF16`` on a float32 packed qkv (B, L, 3*D); returns float32
+    (B, L, D).  Scores as three bf16 products of the split q and k, exp(s - max) and v rounded to bf16 for P V, sums in fp32."""
+    return _vit_attention("stgcn_vit_attention_train_bf16", qkv, heads, scale)
+
+
 def vit_attention_stream(qkv, heads, scale=None) -> torch.Tensor:
     """``vit_attention`` on the streaming kernel (K and V in key tiles through LDS, running soft-max) at every covered
     length, the short ones included: the same result up to the summation order."""
@@ -763,7 +775,9 @@ def _vit_attention_backward(stream, qkv, out, dout, heads, scale):
     ptrs = [_dev_ptr(qkv, "qkv", dev), _dev_ptr(out, "out", dev), _dev_ptr(dout, "dout", dev), _dev_ptr(dqkv, "dqkv")]
     dims = [c_int(B), c_int(L), c_int(heads), c_int(hd), c_float(hd ** -0.5 if scale is None else scale), _stream(dev)]
     with torch.cuda.device(dev):
-        if stream:
+        if stream == "bf16":
+            _capi.call("stgcn_vit_attention_backward_bf16", *ptrs, *dims)
+        elif stream:
             nbytes = _capi.lib().stgcn_vit_attention_backward_stream_ws_bytes(B, L, heads)
             ws = _bytes(dev, nbytes)
             _capi.call("stgcn_vit_attention_backward_stream", *ptrs, c_void_p(ws.data_ptr()), c_size_t(nbytes), *dims)
@@ -785,6 +799,12 @@ def vit_attention_backward_stream(qkv, out, dout, heads, scale=None) -> torch.Te
     for dk and dv, their workspace allocated here) at every covered length, the short ones included: the same result up to
     the summation order."""
     return _vit_attention_backward(True, qkv, out, dout, heads, scale)
+
+
+def vit_attention_backward_bf16(qkv, out, dout, heads, scale=None) -> torch.Tensor:
+    """``vit_attention_backward`` in the arithmetic of ``VIT_TRAIN_ATTN_BF16`` (L <= 256): the scores recomputed as in
+    ``vit_attention_train_bf16``, every other product on operands rounded to bf16, delta = sum P dP (``out`` is not read)."""
+    return _vit_attention_backward("bf16", qkv, out, dout, heads, scale)
 
 
 def vit_layernorm_backward(x, dn, weight, eps, dres=None):
@@ -821,6 +841,12 @@ def vit_block_train_bf16_supported(L, D, heads, hidden) -> bool:
     return bool(_capi.lib().stgcn_vit_block_train_bf16_supported(L, D, heads, hidden))
 
 
+def vit_block_train_attn_bf16_supported(L, D, heads, hidden) -> bool:
+    """Whether ``vit_block_forward_train`` / ``vit_block_backward`` with ``VIT_TRAIN_ATTN_BF16`` run the bf16 attention
+    kernels: covered shapes with L <= 256 (longer sequences run the fp32 streaming kernels whatever the bit says)."""
+    return bool(_capi.lib().stgcn_vit_block_train_attn_bf16_supported(L, D, heads, hidden))
+
+
 def _vit_block_train_bytes(B, L, D, heads, hidden):
     """(saved bytes, workspace bytes) of the training entry points.  The resident form's queries where they answer (L <= 256),
     the ``_long`` queries, which cover both ranges and answer the same there, for what those leave at 0."""
@@ -839,7 +865,8 @@ def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=
     ``VIT_BLOCK_PARAMS`` (qkv.bias may be None).  ``scale1`` / ``scale2`` (B,): stochastic depth's per-sequence factors of the
     attention and the MLP branch (None = 1).  ``saved`` is an opaque buffer for ``vit_block_backward``.
     ``math``: MATH_F32 or MATH_BF16X3, optionally | VIT_QKV_F32, optionally | VIT_TRAIN_BF16 (every linear product but the qkv
-    forward on operands rounded to bf16; hand the same value to ``vit_block_backward``)."""
+    forward on operands rounded to bf16), optionally | VIT_TRAIN_ATTN_BF16 (the attention forward and backward on bf16 operands
+    where L <= 256).  Hand the same value to ``vit_block_backward``."""
     dev = x.device
     B, L, D = x.shape
     hidden = params[8].shape[0]

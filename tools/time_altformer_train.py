@@ -23,6 +23,15 @@ training step of the whole ST and TS models in 'f32' (the default), 'bf16x3' and
 bf16 form of the linear kernel) of the four linears of every stage through ``functional.vit_linear_backward``.
 ``bf16_faster``: the bf16 median is below BOTH other medians by more than the largest of the three spreads.
 
+    python tools/time_altformer_train.py --train-attention bf16 [--batch 32] [--out profiles/altformer_train_bf16_attn_times.json]
+
+``--train-attention bf16`` times the opt-in bf16 training attention (``set_train_attention_math(model, 'bf16')``) on top of the
+bf16 training arithmetic: 'bf16' training math without the switch (``base``: the code that runs without this mode, the baseline)
+and with it (``attn``), alternating in one process - forward + backward of one block at every stage, the attention forward and
+backward of every stage per launch (fp32 kernel against bf16 kernel), and one training step of the whole ST and TS models.
+``attn_faster`` / ``attn_slower``: the medians differ by more than the larger of the two spreads.  ``base_vs_recorded``
+compares the baseline's stage medians with profiles/altformer_train_bf16_times.json where that file is there.
+
 Prints ONE JSON line.  Per stage: ms of forward + backward (min, median, max, ``spread`` = (max - min) / min) of the torch
 path and of the HIP path in each arithmetic ('f32', 'mixed', 'bf16x3'), the speed-up of the default arithmetic, and
 ``hip_faster`` = the HIP median is below the torch median by more than the larger of the two spreads (the rule
@@ -197,6 +206,84 @@ def train_math_bf16(args):
     return res
 
 
+def train_attention_bf16(args):
+    """The ``--train-attention bf16`` run (see the module docstring)."""
+    import stgcn_amd
+    from stgcn_amd import functional as F
+    from stgcn_amd.altformer import HEAD_TRAIN_MATH, Block, set_train_attention_math, set_train_math
+    dev = torch.device("cuda:0")
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    res = {"train_attention": "bf16", "train_math": "bf16", "batch": args.batch, "repeats": args.repeats,
+           "base_flags": HEAD_TRAIN_MATH["bf16"], "attn_flags": HEAD_TRAIN_MATH["bf16"] | F.VIT_TRAIN_ATTN_BF16,
+           "device": torch.cuda.get_device_name(0), "stages": {}, "launches": {}, "models": {}}
+    recorded = {}
+    path = os.path.join(ROOT, "profiles", "altformer_train_bf16_times.json")
+    if os.path.exists(path):
+        with open(path) as f:
+            recorded = json.load(f).get("stages", {})
+
+    def entry(ts, **more):
+        med = {k: statistics.median(v) for k, v in ts.items()}
+        return {**more, "base_ms": summary(ts["base"]), "attn_ms": summary(ts["attn"]),
+                "speedup_median": round(med["base"] / med["attn"], 3),
+                "attn_faster": faster_by_more_than_the_spread(ts["attn"], ts["base"]),
+                "attn_slower": faster_by_more_than_the_spread(ts["base"], ts["attn"])}
+
+    for name, (per_clip, L, D) in STAGES.items():
+        B = args.batch * per_clip
+        torch.manual_seed(0)
+        blk = Block(D, 8, mlp_ratio=2., qkv_bias=True, drop_path=0.1, norm_layer=norm).to(dev).train()
+        blk.hip_train_min_tokens = 0
+        set_train_math(blk, "bf16")
+        x = torch.randn(B, L, D, device=dev, requires_grad=True)
+        dy = torch.randn(B, L, D, device=dev)
+
+        def run(mode):
+            set_train_attention_math(blk, mode)
+            assert blk.trains_on_hip(x)
+            x.grad = None
+            for p in blk.parameters():
+                p.grad = None
+            blk(x).backward(dy)
+        ts = alternate({"base": partial(run, "f32"), "attn": partial(run, "bf16")}, args.repeats, args.warmup)
+        more = {}
+        if name in recorded and recorded[name].get("B") == B:
+            more["base_vs_recorded"] = round(statistics.median(ts["base"]) / recorded[name]["bf16_ms"]["median"], 3)
+        res["stages"][name] = entry(ts, B=B, L=L, D=D, tokens=B * L, **more)
+        del blk, x, dy
+        # the two attention launches on their own
+        heads = 8
+        g = torch.Generator(device=dev).manual_seed(L + D)
+        qkv = torch.randn(B, L, 3 * D, device=dev, generator=g)
+        dout = torch.randn(B, L, D, device=dev, generator=g)
+        out = F.vit_attention(qkv, heads)
+        fw = alternate({"base": partial(F.vit_attention, qkv, heads), "attn": partial(F.vit_attention_train_bf16, qkv, heads)},
+                       args.repeats, args.warmup)
+        bw = alternate({"base": partial(F.vit_attention_backward, qkv, out, dout, heads),
+                        "attn": partial(F.vit_attention_backward_bf16, qkv, out, dout, heads)}, args.repeats, args.warmup)
+        res["launches"][name] = {"pairs": B * heads, "L": L, "head_dim": D // heads, "forward": entry(fw), "backward": entry(bw)}
+        del qkv, dout, out
+        torch.cuda.empty_cache()
+    for style in () if args.stages_only else ("ST", "TS"):
+        torch.manual_seed(1)
+        model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=22, style=style,
+                                           graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).train()
+        set_train_math(model, "bf16")
+        clips = torch.randn(args.batch, 180, 22, 3, device=dev)
+        labels = torch.arange(args.batch, device=dev) % 14
+        ce = torch.nn.CrossEntropyLoss()
+
+        def step(mode):
+            set_train_attention_math(model, mode)
+            model.zero_grad(set_to_none=True)
+            ce(model(clips), labels).backward()
+        ts = alternate({"base": partial(step, "f32"), "attn": partial(step, "bf16")}, args.repeats, args.warmup)
+        res["models"][style] = entry(ts, clips_per_s={m: round(args.batch / (statistics.median(ts[m]) * 1e-3), 1) for m in ts})
+        del model, clips
+        torch.cuda.empty_cache()
+    return res
+
+
 def emit(res, out):
     line = json.dumps(res)
     if out:
@@ -214,9 +301,13 @@ def main():
     ap.add_argument("--frames", type=int, default=None, help="time training at this many frames (> 256) instead")
     ap.add_argument("--train-math", choices=["bf16"], default=None,
                     help="time this opt-in training arithmetic against 'f32' and 'bf16x3' instead")
+    ap.add_argument("--train-attention", choices=["bf16"], default=None,
+                    help="time the opt-in bf16 training attention on top of 'bf16' training math, against that math alone")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
+    if args.train_attention is not None:
+        return emit(train_attention_bf16(args), args.out)
     if args.train_math is not None:
         return emit(train_math_bf16(args), args.out)
     if args.frames is not None:
