@@ -105,7 +105,8 @@ class gcn_unit_attention(nn.Module):
     ``attention_conv.qkv_conv.{weight,bias}`` and ``attention_conv.attn_out.{weight,bias}``; ``incidence`` is a plain
     attribute as in the reference.  Covered by the kernels: out_channels in {128, 256, 512} with the reference's
     dk_factor = 0.25 and Nh = 8 (any per-head split with (dk/Nh, dv/Nh) in {(4,16), (8,32), (16,64)}), any in_channels,
-    num_point <= 64; other shapes raise StgcnError (STGCN_ERR_UNSUPPORTED) at the first forward.
+    num_point <= 64; other shapes raise StgcnError (STGCN_ERR_UNSUPPORTED) at the first forward.  Batch statistics of a
+    single frame (N*T == 1) raise ValueError, as the reference's data_bn does.
     """
 
     def __init__(self, in_channels, out_channels, incidence, num, dv_factor, dk_factor, Nh, complete, relative,
@@ -235,6 +236,10 @@ class gcn_unit_attention(nn.Module):
             raise RuntimeError(f"gcn_unit_attention: expected {self.in_channels} input channels, got {C}")
         if V != self.num_point:
             raise RuntimeError(f"gcn_unit_attention: input has {V} joints, the unit was built for {self.num_point}")
+        if bn_training and N * T == 1:
+            # the reference's data_bn (BatchNorm1d over the (N, C*V, T) view) refuses one value per channel; the batch
+            # variance would be 0.  Raised before the drop-connect draw and before any buffer is touched.
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[N, C * V, T]}")
         x = x.contiguous()
         st = self._staged(x.device)
         mask = self._drop_mask(x)

@@ -608,6 +608,20 @@ for _s, _ma in itertools.product(TCN_TRAIN_SHAPES, ("bf16x3", "f32_valu")):
 
 
 # ---- training: ST-TR spatial attention --------------------------------------------------------------------------------------------
+def st_attention_train_gate(yr, g, dx, frozen):
+    """The gate of a gcn_unit_attention training step {"y", "dx", "d" + parameter name} against grads64's (yr, g, dx); shared
+    with tests/test_st_attention_edges_gpu.py."""
+    def gate(o, what):
+        parity_gate(o["y"], yr, what=f"{what} y")
+        for k in g:
+            if k in ZERO_GRAD and not frozen:
+                assert float(o["d" + k].abs().max()) <= 1e-4 * float(g["bn.bias"].abs().max()), f"{what} d{k}"
+            else:
+                parity_gate(o["d" + k], g[k], strict=False, what=f"{what} grad {k}")
+        parity_gate(o["dx"], dx, strict=False, what=f"{what} dx")
+    return gate
+
+
 def make_st_attention_train(N, cin, cout, T, V, frozen, dev):
     """test_gradients_vs_fp64_autograd_and_rng_state (drop-connect mask from the seeded generator) and
     test_without_drop_connect_and_frozen_batchnorm_under_autograd, through the module."""
@@ -632,15 +646,7 @@ def make_st_attention_train(N, cin, cout, T, V, frozen, dev):
         y.backward(dyd)
         return {"y": y.detach(), "dx": xg.grad, **{"d" + k: p.grad for k, p in m.named_parameters()}}
 
-    def gate(o, what):
-        parity_gate(o["y"], yr, what=f"{what} y")
-        for k in g:
-            if k in ZERO_GRAD and not frozen:
-                assert float(o["d" + k].abs().max()) <= 1e-4 * float(g["bn.bias"].abs().max()), f"{what} d{k}"
-            else:
-                parity_gate(o["d" + k], g[k], strict=False, what=f"{what} grad {k}")
-        parity_gate(o["dx"], dx, strict=False, what=f"{what} dx")
-    return run, gate
+    return run, st_attention_train_gate(yr, g, dx, frozen)
 
 
 add("st_attention_train-3x256x256x10x46-mask", True, make_st_attention_train, 3, 256, 256, 10, 46, False)
