@@ -233,32 +233,13 @@ int launch_attention_packed(const float *qkv, float *out, int B, int L, int H, i
 // under a running soft-max, kStreamQueries queries of a pair per workgroup (vit_attention_stream.hip).
 int launch_attention_stream(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
 
-// The resident attention on bf16 qkv / out (vit_attention_bf16.hip); L <= kMaxL, hd in {32, 64}.  Its LDS per workgroup:
-// K as [keys][hd + 8] and V transposed as [hd][keys + 8], keys = L rounded up to 32, for the pairs a workgroup packs.
-inline size_t attention_bf16_lds_bytes(int L, int hd) {
-    const int nt = ceil_div(L, 32), g = nt >= 4 ? 1 : 4 / nt, rows = nt * 32;
-    return (size_t)g * ((size_t)rows * (hd + 8) + (size_t)hd * (rows + 8)) * 2;
-}
+// The resident attention on bf16 qkv / out (vit_attention_bf16.hip); L <= kMaxL, hd in {32, 64}.
 int launch_attention_bf16(const void *qkv, void *out, int B, int L, int H, int hd, float scale, hipStream_t st);
 
 // The resident attention for training on bf16 matrix operands (vit_attention_train_bf16.hip): fp32 qkv, out, dout and dqkv,
 // L <= kMaxL, hd in {32, 64}.  Scores scale * (qh kh^T + qh kl^T + ql kh^T) of the split q and k, every other product on
-// operands rounded once; the backward's delta is sum P dP of its own products and `out` is not read.  LDS per workgroup, for
-// the pairs it packs, keys = L rounded up to 32: forward K hi, K lo as [keys][hd + 8] and V^T as [hd][keys + 8]; backward
-// three row tiles, two transposed ones (one where the five would not fit: `split`) and 16 bytes of statistics per query.
-constexpr int attention_train_bf16_pairs(int L) { return (L + 31) / 32 >= 4 ? 1 : 4 / ((L + 31) / 32); }
-constexpr size_t attention_train_bf16_lds_bytes(int L, int hd) {
-    const size_t rows = (size_t)((L + 31) / 32) * 32;
-    return (size_t)attention_train_bf16_pairs(L) * (2 * rows * (hd + 8) + (size_t)hd * (rows + 8)) * 2;
-}
-constexpr size_t attention_bwd_bf16_bytes(int L, int hd, int transposed) {
-    const size_t rows = (size_t)((L + 31) / 32) * 32;
-    return (size_t)attention_train_bf16_pairs(L) * ((3 * rows * (hd + 8) + (size_t)transposed * hd * (rows + 8)) * 2 + rows * 16);
-}
-constexpr bool attention_bwd_bf16_split(int L, int hd) { return attention_bwd_bf16_bytes(L, hd, 2) > (size_t)kLdsBytes; }
-constexpr size_t attention_bwd_bf16_lds_bytes(int L, int hd) {
-    return attention_bwd_bf16_bytes(L, hd, attention_bwd_bf16_split(L, hd) ? 1 : 2);
-}
+// operands rounded once; the backward's delta is sum P dP of its own products and `out` is not read.
+// (How the resident kernels pack pairs into workgroups and what LDS each takes: vit_attention_common.h.)
 int launch_attention_train_bf16(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
 int launch_attention_backward_bf16(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int H, int hd,
                                    float scale, hipStream_t st);

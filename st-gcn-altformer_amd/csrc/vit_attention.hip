@@ -1,26 +1,12 @@
-// Multi-head attention over the packed qkv of the AltFormer heads' blocks (model/AltFormer/model_ST.py:48-66):
-//     qkv (B, L, 3, H, hd) exactly as the qkv nn.Linear writes it  ->  out (B, L, H*hd) ready for proj.
-// No q / k / v permute copies and no L x L matrix in memory.  One kernel for every covered length (L <= 256):
-// a (sequence, head) pair gets NT = ceil(L / 32) waves, one per tile of 32 queries, and its K and V (NT*32 rows, the rows
-// past L zero-filled, never read from memory) in LDS; short sequences pack several pairs into a workgroup (L <= 32: one
-// wave per pair, four pairs per workgroup).  Everything runs on v_mfma_f32_32x32x2_f32, i.e. exact fp32 products:
-//
-//   S^T = K Q^T per key tile: A = K rows from LDS (row stride hd + 1 floats: the 32 rows of a fragment sit in 32 banks),
-//         B = the wave's 32 query rows, pre-scaled, held in registers.  The accumulator layout puts query j in lane
-//         j (and j + 32) and 16 keys of the tile in its 16 registers, so the whole score row of a query (up to 256 keys =
-//         8 x 16 registers) lives in two lanes: the soft-max is a plain two-pass one (max, then exp and sum) over
-//         registers in a fixed order plus one exchange with lane ^ 32.  Keys past L get -inf.
-//   O^T = V^T P^T: the accumulator registers of S^T are already a B operand (register i of lanes 0-31 / 32-63 holds keys
-//         a and a + 4 of the same query, the two k values of one MFMA), and A = V^T is read from LDS with lane = channel,
-//         so there is no transpose through LDS and P never leaves the registers.  O is divided by the row sum on store.
-// No atomics; every output element has one owner and a fixed summation order, so results are bit-identical run to run.
-#include "bf16_common.h"
-#include "vit.h"
+// Multi-head attention over the packed qkv of the AltFormer heads' blocks (model/AltFormer/model_ST.py:48-66), fp32, the
+// resident form (L <= 256): one kernel for every covered length, in the layout that vit_attention_common.h describes.
+// Specific to this file: everything runs on v_mfma_f32_32x32x2_f32, i.e. exact fp32 products; the wave's query rows are
+// pre-scaled in registers; K is staged as [rows][hd + 1] (read along a row per lane), V as [rows][hd] (lane = channel); keys
+// past L are masked in every tile; O is divided by the row sum on store.
+#include "vit_attention_common.h"
 
 namespace stgcn {
 namespace vit {
-
-using bf16k::f32x16;
 
 namespace {
 
@@ -28,7 +14,7 @@ template <int HD, int NT>
 __global__ __launch_bounds__(512) void vit_attention_kernel(const float *__restrict__ qkv, float *__restrict__ out,
                                                            int pairs, int L, int H, float scale, int G) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int ROWS = NT * 32, KS = HD + 1, HH = HD / 2;
+    constexpr int ROWS = NT * 32, KS = HD + kPadF32, HH = HD / 2;
     float *Ks = lds;                          // [G][ROWS][KS]
     float *Vs = lds + (size_t)G * ROWS * KS;  // [G][ROWS][HD]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -38,17 +24,16 @@ __global__ __launch_bounds__(512) void vit_attention_kernel(const float *__restr
     // stage K and V of the workgroup's pairs: float4 per thread, rows past L and pairs past the end zero-filled
     const int nvec = G * ROWS * (HD / 4);
     for (int e = tid; e < nvec; e += blockDim.x) {
-        const int d4 = e % (HD / 4), j = (e / (HD / 4)) % ROWS, g = e / ((HD / 4) * ROWS);
-        const int p = blockIdx.x * G + g;
+        const StageSlot s = stage_slot<HD, ROWS, 4>(e, G, pairs, L, H);
         float4 k = make_float4(0.f, 0.f, 0.f, 0.f), v = k;
-        if (p < pairs && j < L) {
-            const float *base = qkv + ((size_t)(p / H) * L + j) * tok + (size_t)(p % H) * HD + d4 * 4;
+        if (s.live) {
+            const float *base = qkv + s.tok * tok + s.col;
             k = *reinterpret_cast<const float4 *>(base + (size_t)H * HD);
             v = *reinterpret_cast<const float4 *>(base + (size_t)2 * H * HD);
         }
-        float *kd = Ks + ((size_t)g * ROWS + j) * KS + d4 * 4;
+        float *kd = Ks + ((size_t)s.g * ROWS + s.j) * KS + s.d0;
         kd[0] = k.x, kd[1] = k.y, kd[2] = k.z, kd[3] = k.w;
-        *reinterpret_cast<float4 *>(Vs + ((size_t)g * ROWS + j) * HD + d4 * 4) = v;
+        *reinterpret_cast<float4 *>(Vs + ((size_t)s.g * ROWS + s.j) * HD + s.d0) = v;
     }
     __syncthreads();
 
@@ -85,7 +70,7 @@ __global__ __launch_bounds__(512) void vit_attention_kernel(const float *__restr
         for (int s = 0; s < HH; ++s) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kp[s], qf[s], sc[kt], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int key = kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+            const int key = ACC_KEY(kt * 32, i, half);
             if (key >= L) sc[kt][i] = -INFINITY;
             mx = fmaxf(mx, sc[kt][i]);
         }
@@ -112,54 +97,24 @@ __global__ __launch_bounds__(512) void vit_attention_kernel(const float *__restr
         for (int kt = 0; kt < NT; ++kt)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int key = kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                const int key = ACC_KEY(kt * 32, i, half);
                 o = __builtin_amdgcn_mfma_f32_32x32x2f32(Vg[(size_t)key * HD + dt * 32 + l31], sc[kt][i], o, 0, 0, 0);
             }
-        if (qi < L) {
-            float *op = out + ((size_t)b * L + qi) * ((size_t)H * HD) + (size_t)h * HD + dt * 32 + 4 * half;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<float4 *>(op + 8 * r) =
-                    make_float4(o[4 * r] * inv, o[4 * r + 1] * inv, o[4 * r + 2] * inv, o[4 * r + 3] * inv);
-        }
+        if (qi < L) store_rows(out + ((size_t)b * L + qi) * ((size_t)H * HD) + (size_t)h * HD + dt * 32 + 4 * half, o, inv);
     }
 }
 
-template <int HD, int NT>
-int launch_one(const float *qkv, float *out, int B, int L, int H, float scale, hipStream_t st) {
-    const int G = NT >= 4 ? 1 : 4 / NT;       // waves per workgroup: 4 for L <= 64, NT (= 3, 4 .. 8) above
-    const long long pairs = (long long)B * H;
-    if (pairs > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention: %lld (sequence, head) pairs", pairs);
-    const size_t bytes = (size_t)G * NT * 32 * (2 * HD + 1) * sizeof(float);
-    if (bytes > (size_t)kLdsBytes) return fail(STGCN_ERR_UNSUPPORTED, "vit attention: %zu bytes of LDS", bytes);
-    auto kern = vit_attention_kernel<HD, NT>;
-    if (bytes > 64 * 1024) STGCN_HIP_CHECK(allow_lds(kern, bytes));
-    kern<<<dim3((unsigned)((pairs + G - 1) / G)), dim3(64 * G * NT), bytes, st>>>(qkv, out, (int)pairs, L, H, scale, G);
-    STGCN_LAUNCH_CHECK("vit_attention_kernel");
-    return STGCN_OK;
-}
-
-template <int HD>
-int launch_hd(const float *qkv, float *out, int B, int L, int H, float scale, hipStream_t st) {
-    switch (ceil_div(L, 32)) {
-        case 1: return launch_one<HD, 1>(qkv, out, B, L, H, scale, st);
-        case 2: return launch_one<HD, 2>(qkv, out, B, L, H, scale, st);
-        case 3: return launch_one<HD, 3>(qkv, out, B, L, H, scale, st);
-        case 4: return launch_one<HD, 4>(qkv, out, B, L, H, scale, st);
-        case 5: return launch_one<HD, 5>(qkv, out, B, L, H, scale, st);
-        case 6: return launch_one<HD, 6>(qkv, out, B, L, H, scale, st);
-        case 7: return launch_one<HD, 7>(qkv, out, B, L, H, scale, st);
-        case 8: return launch_one<HD, 8>(qkv, out, B, L, H, scale, st);
-    }
-    return fail(STGCN_ERR_UNSUPPORTED, "vit attention: L = %d (covered: 1 .. %d)", L, kMaxL);
-}
+struct Forward {
+    static constexpr const char *what = "vit attention", *kernel_name = "vit_attention_kernel";
+    static constexpr size_t lds_bytes(int nt, int hd) { return attention_f32_lds_bytes(nt, hd); }
+    template <int HD, int NT>
+    static auto kernel() { return vit_attention_kernel<HD, NT>; }
+};
 
 }  // namespace
 
 int launch_attention_packed(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st) {
-    if (hd == 32) return launch_hd<32>(qkv, out, B, L, H, scale, st);
-    if (hd == 64) return launch_hd<64>(qkv, out, B, L, H, scale, st);
-    return fail(STGCN_ERR_UNSUPPORTED, "vit attention: head_dim = %d (covered: 32, 64)", hd);
+    return launch_resident<Forward>(B, L, H, hd, scale, st, qkv, out);
 }
 
 }  // namespace vit

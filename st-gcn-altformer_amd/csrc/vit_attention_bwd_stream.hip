@@ -16,21 +16,18 @@
 //                  dS, dV^T += dO^T P, dK^T += (scale Q)^T dS.  It writes dK and dV.
 //
 // That is eight L x L x hd products against the resident kernel's seven: the extra one is pass 1.
-// v_mfma_f32_32x32x2_f32 with the operand layouts of the resident backward; the score accumulators are the B operand of the
-// products behind them, so P and dS never leave the registers.  Every staged row has the HD + 1 stride (it is read both
+// Built from vit_attention_common.h, which describes the operand layouts (those of the resident backward): the score
+// accumulators are the B operand of the products behind them.  Every staged row has the HD + 1 stride (it is read both
 // along a row per lane and across rows).  Staging as in the forward: the loads of tile t + 1 go into registers before the
 // products of tile t and into the other stage behind them, one barrier per tile; rows past L are zero-filled, never read.
 // Keys past L are masked to -inf before the exponent (P = 0).  Query rows past L reach the key kernel as zeros with
 // m = 0, 1 / l = 0, delta = 0, so they add exp(0) * 0 = 0 to dK / dV (never exp(-inf + inf)).  Idle waves of a short last
 // block still stage and meet the barriers.
-// fp32 throughout, no atomics; every output element has one owner and a fixed summation order: bit-identical run to run.
-#include "bf16_common.h"
-#include "vit.h"
+// fp32 throughout (v_mfma_f32_32x32x2_f32).
+#include "vit_attention_common.h"
 
 namespace stgcn {
 namespace vit {
-
-using bf16k::f32x16;
 
 namespace {
 
@@ -48,7 +45,7 @@ __global__ __launch_bounds__(kBwdThreads) void vit_attention_bwd_stream_q_kernel
                                                                                  float *__restrict__ stats, int L, int H,
                                                                                  float scale, int nqb) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int KT = kBwdRows, KS = HD + 1, HH = HD / 2;
+    constexpr int KT = kBwdRows, KS = HD + kPadF32, HH = HD / 2;
     constexpr int STAGE = 2 * KT * KS;                     // floats of one stage: K rows, then V rows
     constexpr int NV = KT * (HD / 4) / kBwdThreads;        // float4 of K (and of V) a thread moves per tile
     static_assert(KT * (HD / 4) % kBwdThreads == 0, "staging split");
@@ -133,7 +130,7 @@ __global__ __launch_bounds__(kBwdThreads) void vit_attention_bwd_stream_q_kernel
                 for (int s = 0; s < HH; ++s) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kp[s], qf[s], sc[kt], 0, 0, 0);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int key = t * KT + kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                    const int key = ACC_KEY(t * KT + kt * 32, i, half);
                     if (key >= L) sc[kt][i] = -INFINITY;
                     tmax = fmaxf(tmax, sc[kt][i]);
                 }
@@ -173,7 +170,7 @@ __global__ __launch_bounds__(kBwdThreads) void vit_attention_bwd_stream_q_kernel
                     for (int kt = 0; kt < KT / 32; ++kt)
 #pragma unroll
                         for (int i = 0; i < 16; ++i) {
-                            const int key = kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                            const int key = ACC_KEY(kt * 32, i, half);
                             dq[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Kb[key * KS + dt * 32 + l31], sc[kt][i], dq[dt], 0, 0, 0);
                         }
             }
@@ -185,13 +182,8 @@ __global__ __launch_bounds__(kBwdThreads) void vit_attention_bwd_stream_q_kernel
     if (!active || qi >= L) return;
     if (half == 0) *reinterpret_cast<float4 *>(stats + ((size_t)p * L + qi) * 4) = make_float4(m, inv, delta, 0.f);
 #pragma unroll
-    for (int dt = 0; dt < HD / 32; ++dt) {
-        float *qo = dqkv + ((size_t)b * L + qi) * tok + (size_t)h * HD + dt * 32 + 4 * half;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            *reinterpret_cast<float4 *>(qo + 8 * r) = make_float4(dq[dt][4 * r] * scale, dq[dt][4 * r + 1] * scale,
-                                                                  dq[dt][4 * r + 2] * scale, dq[dt][4 * r + 3] * scale);
-    }
+    for (int dt = 0; dt < HD / 32; ++dt)
+        store_rows(dqkv + ((size_t)b * L + qi) * tok + (size_t)h * HD + dt * 32 + 4 * half, dq[dt], scale);
 }
 
 template <int HD>
@@ -201,7 +193,7 @@ __global__ __launch_bounds__(kBwdThreads) void vit_attention_bwd_stream_k_kernel
                                                                                  float *__restrict__ dqkv, int L, int H,
                                                                                  float scale, int nkb) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int QT = kBwdRows, KS = HD + 1, HH = HD / 2;
+    constexpr int QT = kBwdRows, KS = HD + kPadF32, HH = HD / 2;
     constexpr int STAGE = 2 * QT * KS + QT * 4;            // floats of one stage: scale * Q rows, dO rows, (m, 1 / l, delta, -)
     constexpr int NV = QT * (HD / 4) / kBwdThreads;        // float4 of Q (and of dO) a thread moves per tile
     static_assert(QT * (HD / 4) % kBwdThreads == 0 && (2 * QT * KS) % 4 == 0 && STAGE % 4 == 0 && QT <= kBwdThreads,
@@ -285,7 +277,7 @@ __global__ __launch_bounds__(kBwdThreads) void vit_attention_bwd_stream_k_kernel
                 }
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int q = qt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                    const int q = ACC_KEY(qt * 32, i, half);
                     const float4 st = *reinterpret_cast<const float4 *>(&Sb[q * 4]);   // (max, 1 / sum, delta, -); 1 / sum = 0 past L
                     const float pr = ki < L ? __expf(s[i] - st.x) * st.y : 0.f;
                     s[i] = pr;
@@ -295,7 +287,7 @@ __global__ __launch_bounds__(kBwdThreads) void vit_attention_bwd_stream_k_kernel
                 for (int dt = 0; dt < HD / 32; ++dt)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const int q = qt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                        const int q = ACC_KEY(qt * 32, i, half);
                         dv[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ob[q * KS + dt * 32 + l31], s[i], dv[dt], 0, 0, 0);
                         dk[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Qb[q * KS + dt * 32 + l31], dp[i], dk[dt], 0, 0, 0);
                     }
@@ -308,14 +300,10 @@ __global__ __launch_bounds__(kBwdThreads) void vit_attention_bwd_stream_k_kernel
     if (!active || ki >= L) return;
     float *base = dqkv + ((size_t)b * L + ki) * tok + (size_t)h * HD + 4 * half;
 #pragma unroll
-    for (int dt = 0; dt < HD / 32; ++dt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            *reinterpret_cast<float4 *>(base + (size_t)H * HD + dt * 32 + 8 * r) =
-                make_float4(dk[dt][4 * r], dk[dt][4 * r + 1], dk[dt][4 * r + 2], dk[dt][4 * r + 3]);
-            *reinterpret_cast<float4 *>(base + (size_t)2 * H * HD + dt * 32 + 8 * r) =
-                make_float4(dv[dt][4 * r], dv[dt][4 * r + 1], dv[dt][4 * r + 2], dv[dt][4 * r + 3]);
-        }
+    for (int dt = 0; dt < HD / 32; ++dt) {
+        store_rows(base + (size_t)H * HD + dt * 32, dk[dt]);
+        store_rows(base + (size_t)2 * H * HD + dt * 32, dv[dt]);
+    }
 }
 
 template <int HD>
@@ -324,7 +312,7 @@ int launch_hd(const float *qkv, const float *out, const float *dout, float *dqkv
     const int nb = ceil_div(L, kStreamQueries);            // blocks of 128 queries, and of 128 keys, per pair
     const long long blocks = (long long)B * H * nb;
     if (blocks > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward (stream): %lld workgroups", blocks);
-    const size_t qbytes = (size_t)2 * 2 * kBwdRows * (HD + 1) * sizeof(float);
+    const size_t qbytes = (size_t)2 * 2 * kBwdRows * (HD + kPadF32) * sizeof(float);
     const size_t kbytes = qbytes + (size_t)2 * kBwdRows * 4 * sizeof(float);
     auto qkern = vit_attention_bwd_stream_q_kernel<HD>;
     auto kkern = vit_attention_bwd_stream_k_kernel<HD>;

@@ -1,5 +1,6 @@
 // The same attention as vit_attention.hip for sequences it cannot keep on chip (256 < L <= kMaxStreamL, and every shorter
-// length on request):  qkv (B, L, 3, H, hd) as the qkv nn.Linear writes it  ->  out (B, L, H*hd).
+// length on request):  qkv (B, L, 3, H, hd) as the qkv nn.Linear writes it  ->  out (B, L, H*hd).  Built from
+// vit_attention_common.h, which describes the operand layout; specific to this file:
 // K and V are streamed through LDS in tiles of kStreamKeys = 64 keys and the soft-max is a running one, so neither the
 // LDS nor the registers grow with L.  A workgroup of four waves owns kStreamQueries = 128 queries of one (sequence, head)
 // pair (a wave 32 of them, its query rows pre-scaled in registers for the whole kernel) and walks all key tiles:
@@ -7,21 +8,15 @@
 //   staging   two LDS stages of [64][hd + 1] K rows and [64][hd] V rows (hd = 64: 33,024 B each).  The global loads of tile
 //             t + 1 are issued into registers before the products of tile t and written to the other stage behind them:
 //             one barrier per tile.  Rows past L are zero-filled, never read from memory.
-//   S^T = K Q^T  and  O^T = V^T P^T  on v_mfma_f32_32x32x2_f32 with the resident kernel's operand layout: the score
-//             accumulators are the B operand of the second product, so P never leaves the registers.
 //   soft-max  query j lives in lanes j and j + 32.  Per tile: the tile's maximum (one lane ^ 32 exchange), m' = max(m, that),
 //             alpha = exp(m - m'), the output accumulators (query = lane: a per-lane scalar) and the running sum times alpha,
-//             p = exp(s - m') added.  Every tile holds at least one valid key (only the last is short, and ceil(L / 64)
-//             leaves it one), so m' is finite and the first tile's alpha is exp(-inf) = 0, never exp(-inf + inf).
+//             p = exp(s - m') added.  Every tile holds at least one valid key (only the last is short, and
+//             ceil(L / 64) leaves it one), so m' is finite and the first tile's alpha is exp(-inf) = 0, never exp(-inf + inf).
 //             The two lanes' partial sums meet once, after the last tile; O / l on store.
-// No atomics; every output element has one owner and a fixed summation order, so results are bit-identical run to run.
-#include "bf16_common.h"
-#include "vit.h"
+#include "vit_attention_common.h"
 
 namespace stgcn {
 namespace vit {
-
-using bf16k::f32x16;
 
 namespace {
 
@@ -32,7 +27,7 @@ __global__ __launch_bounds__(kStreamThreads) void vit_attention_stream_kernel(co
                                                                               float *__restrict__ out, int L, int H,
                                                                               float scale, int nqb) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int KT = kStreamKeys, KS = HD + 1, HH = HD / 2;
+    constexpr int KT = kStreamKeys, KS = HD + kPadF32, HH = HD / 2;
     constexpr int STAGE = KT * KS + KT * HD;               // floats of one stage: K rows, then V rows
     constexpr int NV = KT * (HD / 4) / kStreamThreads;     // float4 of K (and of V) a thread moves per tile
     static_assert(KT * (HD / 4) % kStreamThreads == 0 && (KT * KS) % 4 == 0 && STAGE % 4 == 0, "staging split / alignment");
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(kStreamThreads) void vit_attention_stream_kernel(co
                 for (int s = 0; s < HH; ++s) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kp[s], qf[s], sc[kt], 0, 0, 0);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int key = t * KT + kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                    const int key = ACC_KEY(t * KT + kt * 32, i, half);
                     if (key >= L) sc[kt][i] = -INFINITY;
                     tmax = fmaxf(tmax, sc[kt][i]);
                 }
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(kStreamThreads) void vit_attention_stream_kernel(co
                 for (int kt = 0; kt < KT / 32; ++kt)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const int key = kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                        const int key = ACC_KEY(kt * 32, i, half);
                         o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vb[key * HD + dt * 32 + l31], sc[kt][i], o[dt], 0, 0, 0);
                     }
             }
@@ -149,13 +144,8 @@ __global__ __launch_bounds__(kStreamThreads) void vit_attention_stream_kernel(co
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;
 #pragma unroll
-    for (int dt = 0; dt < HD / 32; ++dt) {
-        float *op = out + ((size_t)b * L + qi) * ((size_t)H * HD) + (size_t)h * HD + dt * 32 + 4 * half;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            *reinterpret_cast<float4 *>(op + 8 * r) =
-                make_float4(o[dt][4 * r] * inv, o[dt][4 * r + 1] * inv, o[dt][4 * r + 2] * inv, o[dt][4 * r + 3] * inv);
-    }
+    for (int dt = 0; dt < HD / 32; ++dt)
+        store_rows(out + ((size_t)b * L + qi) * ((size_t)H * HD) + (size_t)h * HD + dt * 32 + 4 * half, o[dt], inv);
 }
 
 template <int HD>
@@ -163,7 +153,7 @@ int launch_hd(const float *qkv, float *out, int B, int L, int H, float scale, hi
     const int nqb = ceil_div(L, kStreamQueries);
     const long long blocks = (long long)B * H * nqb;
     if (blocks > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention (stream): %lld workgroups", blocks);
-    const size_t bytes = (size_t)2 * kStreamKeys * (2 * HD + 1) * sizeof(float);
+    const size_t bytes = (size_t)2 * kStreamKeys * (2 * HD + kPadF32) * sizeof(float);
     auto kern = vit_attention_stream_kernel<HD>;
     if (bytes > 64 * 1024) STGCN_HIP_CHECK(allow_lds(kern, bytes));
     kern<<<dim3((unsigned)blocks), dim3(kStreamThreads), bytes, st>>>(qkv, out, L, H, scale, nqb);

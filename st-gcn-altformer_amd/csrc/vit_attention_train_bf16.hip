@@ -1,17 +1,18 @@
 // Multi-head attention of the AltFormer heads' blocks for TRAINING on bf16 matrix operands (STGCN_VIT_TRAIN_ATTN_BF16 of
 // stgcn_vit_block_forward_train / stgcn_vit_block_backward): forward and backward of
 //     qkv (B, L, 3, H, hd) fp32 as the qkv linear stores it  ->  out (B, L, H*hd) fp32,  dout -> dqkv (packed as qkv, fp32)
-// on v_mfma_f32_32x32x16_bf16, resident form (L <= 256), head_dim 32 / 64.  Everything in memory is fp32; operands are split
-// or rounded (r = round to nearest-even bf16) while they are staged, every sum is fp32.
+// on v_mfma_f32_32x32x16_bf16, resident form (L <= 256), head_dim 32 / 64, built from vit_attention_common.h, which describes the
+// layout.  Everything in memory is fp32; operands are split or rounded (r = round to nearest-even bf16) while they are staged,
+// every sum is fp32.
 //
 // The arithmetic (DESIGN section 15 "bf16 attention"), per (sequence, head):
 //   s  = scale * (qh kh^T + qh kl^T + ql kh^T),  qh = r(q), ql = r(q - qh), kh, kl alike, of the UNSCALED q and k.  A rounded q
 //        or k is multiplied by the size of the scores before the exponential, so the score product alone takes three terms.
 //        Order into the fp32 accumulator, the same wherever a score is computed (forward, backward phase (a) and (b)):
-//        per key tile of 32, per k-step of 16 channels in ascending order: kl * qh, then kh * ql, then kh * qh.
+//        per key tile of 32, per k-step of 16 channels in ascending order: kl * qh, then kh * ql, then kh * qh (score_step).
 //        The products are exact in fp32 and the matrix core adds a k-step's 16 products in one order whichever operand is A
-//        and which is B, so the three places agree bit for bit.  (fp contraction is off in this file: s * scale - m is a
-//        multiply and a subtract everywhere.)
+//        and which is B, so the three places agree bit for bit.  fp contraction is OFF in this file, the shared pieces
+//        included below the pragma with it: s * scale - m is a multiply and a subtract everywhere.
 //   m  = max s,  p = exp(s - m),  l = sum p (of the unrounded fp32 p);  keys past L are zero-filled in LDS and score -inf.
 //   forward : out = (r(p) r(v)) / l
 //   backward: P = p / l,  dP = r(dO) r(v)^T,  delta_i = sum_j P_ij dP_ij (fp32, of the unrounded P and the kernel's own dP: each
@@ -19,7 +20,7 @@
 //             dV = r(P)^T r(dO),  dQ = scale * r(dS) r(k),  dK = scale * r(dS)^T r(q).
 //
 // Forward: vit_attention_bf16.hip with fp32 memory on both sides.  A pair gets NT = ceil(L / 32) waves, a wave 32 queries as hi
-//   and lo B fragments; K is staged as a hi and a lo tile [keys][hd + 8], V transposed and permuted [hd][keys + 8] (see there);
+//   and lo B fragments; K is staged as a hi and a lo tile [keys][hd + 8], V transposed and permuted [hd][keys + 8];
 //   the score accumulators, exponentiated, rounded and packed in place, are the B operand of O^T = V^T P^T.
 // Backward: the two phases of vit_attention_bwd_kernel (vit_backward.hip), a workgroup per pair (several for L <= 64):
 //   (a) LDS: K hi, K lo, V as rows [keys][hd + 8], K hi transposed and permuted [hd][keys + 8].  A wave per 32 queries: S^T, the
@@ -32,18 +33,16 @@
 //   walks the query tiles twice.  The first walk has dO^T staged and computes S, P and dV^T; then, between two barriers, Q^T
 //   is written over dO^T (from the Q hi rows in LDS), and the second walk computes S and P again, dP, dS and dK^T.  Every
 //   output sees the same products in the same order as in the other instantiations; the price is the score product twice.
-// LDS reads and writes, banks: a row tile has a stride of hd + 8 elements = 80 / 144 bytes, a transposed one of keys + 8
-//   elements = 16 bytes more than a multiple of 64.  A fragment read is 16 bytes per lane, lane = row; the hardware serves it
-//   in four groups of 16 lanes of one lane half (256 bytes = all 64 banks once), and the rows of a group are one of each
-//   residue mod 16.  The strides are 20, 36 and 16 NT + 4 dwords = 4 x an odd number, so the 16 rows of a group start at 16
-//   distinct multiples of 4 banks and their four-bank spans do not overlap: conflict-free.  Row tiles are written 16 bytes per
-//   thread, consecutive threads consecutive pieces of a row: 8 lanes cover 128 contiguous bytes at hd = 64 (conflict-free); at
-//   hd = 32 they cover two rows 80 bytes apart, whose last and first pieces share a bank (2-way on one pair of 8).
+// LDS reads and writes, banks: a fragment read is 16 bytes per lane, lane = row; the hardware serves it in four groups of 16
+//   lanes of one lane half (256 bytes = all 64 banks once), and the rows of a group are one of each residue mod 16.  The
+//   strides are 20, 36 and 16 NT + 4 dwords = 4 x an odd number, so the 16 rows of a group start at 16 distinct multiples of 4
+//   banks and their four-bank spans do not overlap: conflict-free.  Row tiles are written 16 bytes per thread, consecutive
+//   threads consecutive pieces of a row: 8 lanes cover 128 contiguous bytes at hd = 64 (conflict-free); at hd = 32 they cover
+//   two rows 80 bytes apart, whose last and first pieces share a bank (2-way on one pair of 8).
 //   The transposed tiles are NOT conflict-free to write: 2 bytes per thread and channel row, and the threads of one token
 //   are 8 channel rows = 128 NT + 32 dwords = 0 mod 32 banks apart, so the hd / 8 threads of a token collide, and four
-//   neighbouring tokens share two dwords: up to 16-way.  vit_attention_bf16.hip stages V the same way; the scatter runs once
-//   per tile (one tile in the forward, three in a backward), not in the product loops.
-// No atomics; every output element has one owner and a fixed summation order: two runs are bit-identical.
+//   neighbouring tokens share two dwords: up to 16-way.  The scatter runs once per tile (one tile in a forward, three in a
+//   backward), not in the product loops.
 #include <type_traits>
 
 #include "bf16_common.h"
@@ -51,69 +50,19 @@
 
 #pragma clang fp contract(off)
 
+#include "vit_attention_common.h"
+
 namespace stgcn {
 namespace vit {
 
-using bf16k::bf16x8;
-using bf16k::f32x16;
-using bf16k::pack_bf16x2;
-using bf16k::split8;
-
 namespace {
-
-__device__ __forceinline__ void load8(const float *p, float (&v)[8]) {
-    const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
-}
-__device__ __forceinline__ void zero8(float (&v)[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = 0.f;
-}
-__device__ __forceinline__ uint4 round8(const float (&v)[8]) {
-    return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
-}
-// token j of its tile -> its place in a transposed tile: slot 8 h + j' of its group of 16 (vit_attention_bf16.hip's header)
-__device__ __forceinline__ int perm16(int j) {
-    const int o = j & 15;
-    return (j & ~15) + (((o >> 2) & 1) << 3) + ((o >> 3) << 2) + (o & 3);
-}
-// eight channels d0 .. d0 + 7 of one token (already bf16) into a transposed tile at column `pos`
-__device__ __forceinline__ void scatter8(unsigned short *t, int stride, int pos, uint4 v) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        t[(size_t)(2 * c) * stride + pos] = (unsigned short)(w[c] & 0xffffu);
-        t[(size_t)(2 * c + 1) * stride + pos] = (unsigned short)(w[c] >> 16);
-    }
-}
-__device__ __forceinline__ uint4 lds16B(const unsigned short *p) { return *reinterpret_cast<const uint4 *>(p); }
-__device__ __forceinline__ f32x16 mfma(uint4 a, uint4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// the three chains of a score k-step, in the one order of this file
-__device__ __forceinline__ f32x16 score_step(uint4 ah, uint4 al, uint4 bh, uint4 bl, f32x16 c, bool a_is_k) {
-    // a_is_k: A = K (forward, phase (a)); else A = Q (phase (b)).  Either way: kl * qh, kh * ql, kh * qh.
-    if (a_is_k) {
-        c = mfma(al, bh, c);
-        c = mfma(ah, bl, c);
-    } else {
-        c = mfma(ah, bl, c);
-        c = mfma(al, bh, c);
-    }
-    return mfma(ah, bh, c);
-}
-// a 16-register accumulator half -> B operand: registers 8 gk .. 8 gk + 7, rounded and packed in pairs
-__device__ __forceinline__ uint4 pack8(const float (&e)[16], int gk) {
-    return make_uint4(pack_bf16x2(e[8 * gk], e[8 * gk + 1]), pack_bf16x2(e[8 * gk + 2], e[8 * gk + 3]),
-                      pack_bf16x2(e[8 * gk + 4], e[8 * gk + 5]), pack_bf16x2(e[8 * gk + 6], e[8 * gk + 7]));
-}
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 template <int HD, int NT>
 __global__ __launch_bounds__(512) void vit_attention_train_bf16_kernel(const float *__restrict__ qkv, float *__restrict__ out,
                                                                       int pairs, int L, int H, float scale, int G) {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds16[];
-    constexpr int ROWS = NT * 32, KS = HD + 8, VS = ROWS + 8, KST = HD / 16;
+    constexpr int ROWS = NT * 32, KS = HD + kPad16, VS = ROWS + kPad16, KST = HD / 16;
     unsigned short *Kh = lds16;                              // [G][ROWS][KS]
     unsigned short *Kl = Kh + (size_t)G * ROWS * KS;         // [G][ROWS][KS]
     unsigned short *Vt = Kl + (size_t)G * ROWS * KS;         // [G][HD][VS]
@@ -123,21 +72,20 @@ __global__ __launch_bounds__(512) void vit_attention_train_bf16_kernel(const flo
 
     const int nvec = G * ROWS * (HD / 8);
     for (int e = tid; e < nvec; e += blockDim.x) {
-        const int d8 = e % (HD / 8), j = (e / (HD / 8)) % ROWS, g = e / ((HD / 8) * ROWS);
-        const int p = blockIdx.x * G + g;
+        const StageSlot s = stage_slot<HD, ROWS, 8>(e, G, pairs, L, H);
         float k[8], v[8];
         zero8(k);
         zero8(v);
-        if (p < pairs && j < L) {
-            const float *base = qkv + ((size_t)(p / H) * L + j) * tok + (size_t)(p % H) * HD + d8 * 8;
+        if (s.live) {
+            const float *base = qkv + s.tok * tok + s.col;
             load8(base + (size_t)H * HD, k);
             load8(base + (size_t)2 * H * HD, v);
         }
         uint4 hi, lo;
         split8(k, hi, lo);
-        *reinterpret_cast<uint4 *>(Kh + ((size_t)g * ROWS + j) * KS + d8 * 8) = hi;
-        *reinterpret_cast<uint4 *>(Kl + ((size_t)g * ROWS + j) * KS + d8 * 8) = lo;
-        scatter8(Vt + ((size_t)g * HD + d8 * 8) * VS, VS, perm16(j), round8(v));
+        *reinterpret_cast<uint4 *>(Kh + ((size_t)s.g * ROWS + s.j) * KS + s.d0) = hi;
+        *reinterpret_cast<uint4 *>(Kl + ((size_t)s.g * ROWS + s.j) * KS + s.d0) = lo;
+        scatter8(Vt + ((size_t)s.g * HD + s.d0) * VS, VS, perm16(s.j), round8(v));
     }
     __syncthreads();
 
@@ -172,7 +120,7 @@ __global__ __launch_bounds__(512) void vit_attention_train_bf16_kernel(const flo
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             sc[kt][i] *= scale;
-            if (kt == NT - 1 && kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3) >= L) sc[kt][i] = -INFINITY;
+            if (kt == NT - 1 && ACC_KEY(kt * 32, i, half) >= L) sc[kt][i] = -INFINITY;
             mx = fmaxf(mx, sc[kt][i]);
         }
     }
@@ -203,12 +151,7 @@ __global__ __launch_bounds__(512) void vit_attention_train_bf16_kernel(const flo
         for (int kt = 0; kt < NT; ++kt)
 #pragma unroll
             for (int gk = 0; gk < 2; ++gk) o = mfma(lds16B(vp + kt * 32 + gk * 16), pk[kt][gk], o);
-        if (qi < L) {
-            float *op = out + ((size_t)b * L + qi) * ((size_t)H * HD) + (size_t)h * HD + dt * 32 + 4 * half;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<float4 *>(op + 8 * r) = make_float4(o[4 * r] * inv, o[4 * r + 1] * inv, o[4 * r + 2] * inv, o[4 * r + 3] * inv);
-        }
+        if (qi < L) store_rows(out + ((size_t)b * L + qi) * ((size_t)H * HD) + (size_t)h * HD + dt * 32 + 4 * half, o, inv);
     }
 }
 
@@ -218,7 +161,7 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_bf16_kernel(const float
                                                                     float *__restrict__ dqkv, int pairs, int L, int H,
                                                                     float scale, int G) {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds16[];
-    constexpr int ROWS = NT * 32, KS = HD + 8, VS = ROWS + 8, KST = HD / 16;
+    constexpr int ROWS = NT * 32, KS = HD + kPad16, VS = ROWS + kPad16, KST = HD / 16;
     const size_t rt = (size_t)G * ROWS * KS, tt = (size_t)G * HD * VS;   // elements of a row tile, of a transposed tile
     unsigned short *R0 = lds16;          // [G][ROWS][KS]: K hi in (a), Q hi in (b)
     unsigned short *R1 = R0 + rt;        // K lo, Q lo
@@ -232,23 +175,22 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_bf16_kernel(const float
     const int nvec = G * ROWS * (HD / 8);
 
     for (int e = tid; e < nvec; e += blockDim.x) {
-        const int d8 = e % (HD / 8), j = (e / (HD / 8)) % ROWS, g = e / ((HD / 8) * ROWS);
-        const int p = blockIdx.x * G + g;
+        const StageSlot s = stage_slot<HD, ROWS, 8>(e, G, pairs, L, H);
         float k[8], v[8];
         zero8(k);
         zero8(v);
-        if (p < pairs && j < L) {
-            const float *base = qkv + ((size_t)(p / H) * L + j) * tok + (size_t)(p % H) * HD + d8 * 8;
+        if (s.live) {
+            const float *base = qkv + s.tok * tok + s.col;
             load8(base + (size_t)H * HD, k);
             load8(base + (size_t)2 * H * HD, v);
         }
         uint4 hi, lo;
         split8(k, hi, lo);
-        const size_t ro = ((size_t)g * ROWS + j) * KS + d8 * 8;
+        const size_t ro = ((size_t)s.g * ROWS + s.j) * KS + s.d0;
         *reinterpret_cast<uint4 *>(R0 + ro) = hi;
         *reinterpret_cast<uint4 *>(R1 + ro) = lo;
         *reinterpret_cast<uint4 *>(R2 + ro) = round8(v);
-        scatter8(T0 + ((size_t)g * HD + d8 * 8) * VS, VS, perm16(j), hi);
+        scatter8(T0 + ((size_t)s.g * HD + s.d0) * VS, VS, perm16(s.j), hi);
     }
     __syncthreads();
 
@@ -286,7 +228,7 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_bf16_kernel(const float
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     sc[kt][i] *= scale;
-                    if (kt == NT - 1 && kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3) >= L) sc[kt][i] = -INFINITY;
+                    if (kt == NT - 1 && ACC_KEY(kt * 32, i, half) >= L) sc[kt][i] = -INFINITY;
                     mx = fmaxf(mx, sc[kt][i]);
                 }
             }
@@ -379,25 +321,23 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_bf16_kernel(const float
 
     // ---- phase (b): LDS <- Q hi, Q lo, dO, dO^T (and Q hi^T), a wave per 32 keys ----
     for (int e = tid; e < nvec; e += blockDim.x) {
-        const int d8 = e % (HD / 8), j = (e / (HD / 8)) % ROWS, gg = e / ((HD / 8) * ROWS);
-        const int pp = blockIdx.x * G + gg;
+        const StageSlot s = stage_slot<HD, ROWS, 8>(e, G, pairs, L, H);
         float q[8], d[8];
         zero8(q);
         zero8(d);
-        if (pp < pairs && j < L) {
-            const size_t row = (size_t)(pp / H) * L + j;
-            load8(qkv + row * tok + (size_t)(pp % H) * HD + d8 * 8, q);
-            load8(dout + row * otok + (size_t)(pp % H) * HD + d8 * 8, d);
+        if (s.live) {
+            load8(qkv + s.tok * tok + s.col, q);
+            load8(dout + s.tok * otok + s.col, d);
         }
         uint4 hi, lo;
         split8(q, hi, lo);
         const uint4 dr = round8(d);
-        const size_t ro = ((size_t)gg * ROWS + j) * KS + d8 * 8;
+        const size_t ro = ((size_t)s.g * ROWS + s.j) * KS + s.d0;
         *reinterpret_cast<uint4 *>(R0 + ro) = hi;
         *reinterpret_cast<uint4 *>(R1 + ro) = lo;
         *reinterpret_cast<uint4 *>(R2 + ro) = dr;
-        scatter8(T0 + ((size_t)gg * HD + d8 * 8) * VS, VS, perm16(j), dr);
-        if constexpr (!SPLIT) scatter8(T1 + ((size_t)gg * HD + d8 * 8) * VS, VS, perm16(j), hi);
+        scatter8(T0 + ((size_t)s.g * HD + s.d0) * VS, VS, perm16(s.j), dr);
+        if constexpr (!SPLIT) scatter8(T1 + ((size_t)s.g * HD + s.d0) * VS, VS, perm16(s.j), hi);
     }
     __syncthreads();
 
@@ -439,7 +379,7 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_bf16_kernel(const float
             float pr[16], ds[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int q = qt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                const int q = ACC_KEY(qt * 32, i, half);
                 const float4 st = *reinterpret_cast<const float4 *>(&Sg[q * 4]);   // (max, 1 / sum, delta, -); 1 / sum = 0 past L
                 pr[i] = ri < L ? __expf(s[i] * scale - st.x) * st.y : 0.f;
                 ds[i] = pr[i] * (dp[i] - st.z);
@@ -468,8 +408,8 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_bf16_kernel(const float
     if constexpr (SPLIT) {
         __syncthreads();                           // every wave is done with dO^T
         for (int e = tid; e < nvec; e += blockDim.x) {
-            const int d8 = e % (HD / 8), j = (e / (HD / 8)) % ROWS, gg = e / ((HD / 8) * ROWS);
-            scatter8(T0 + ((size_t)gg * HD + d8 * 8) * VS, VS, perm16(j), lds16B(R0 + ((size_t)gg * ROWS + j) * KS + d8 * 8));
+            const StageSlot s = stage_slot<HD, ROWS, 8>(e, G, pairs, L, H);
+            scatter8(T0 + ((size_t)s.g * HD + s.d0) * VS, VS, perm16(s.j), lds16B(R0 + ((size_t)s.g * ROWS + s.j) * KS + s.d0));
         }
         __syncthreads();
         if (active) {
@@ -491,79 +431,29 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_bf16_kernel(const float
     }
 }
 
-template <int HD, int NT>
-int launch_fwd_one(const float *qkv, float *out, int B, int L, int H, float scale, hipStream_t st) {
-    const int G = attention_train_bf16_pairs(L);
-    const long long pairs = (long long)B * H;
-    if (pairs > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention (train bf16): %lld (sequence, head) pairs", pairs);
-    const size_t bytes = attention_train_bf16_lds_bytes(L, HD);
-    if (bytes > (size_t)kLdsBytes) return fail(STGCN_ERR_UNSUPPORTED, "vit attention (train bf16): %zu bytes of LDS", bytes);
-    auto kern = vit_attention_train_bf16_kernel<HD, NT>;
-    if (bytes > 64 * 1024) STGCN_HIP_CHECK(allow_lds(kern, bytes));
-    kern<<<dim3((unsigned)((pairs + G - 1) / G)), dim3(64 * G * NT), bytes, st>>>(qkv, out, (int)pairs, L, H, scale, G);
-    STGCN_LAUNCH_CHECK("vit_attention_train_bf16_kernel");
-    return STGCN_OK;
-}
-
-template <int HD, int NT>
-int launch_bwd_one(const float *qkv, const float *dout, float *dqkv, int B, int L, int H, float scale, hipStream_t st) {
-    constexpr bool SPLIT = attention_bwd_bf16_split(NT * 32, HD);
-    const int G = attention_train_bf16_pairs(L);
-    const long long pairs = (long long)B * H;
-    if (pairs > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward (bf16): %lld (sequence, head) pairs", pairs);
-    const size_t bytes = attention_bwd_bf16_lds_bytes(L, HD);
-    if (bytes > (size_t)kLdsBytes) return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward (bf16): %zu bytes of LDS", bytes);
-    auto kern = vit_attention_bwd_bf16_kernel<HD, NT, SPLIT>;
-    if (bytes > 64 * 1024) STGCN_HIP_CHECK(allow_lds(kern, bytes));
-    kern<<<dim3((unsigned)((pairs + G - 1) / G)), dim3(64 * G * NT), bytes, st>>>(qkv, dout, dqkv, (int)pairs, L, H, scale, G);
-    STGCN_LAUNCH_CHECK("vit_attention_bwd_bf16_kernel");
-    return STGCN_OK;
-}
-
-template <int HD>
-int launch_fwd_hd(const float *qkv, float *out, int B, int L, int H, float scale, hipStream_t st) {
-    switch (ceil_div(L, 32)) {
-        case 1: return launch_fwd_one<HD, 1>(qkv, out, B, L, H, scale, st);
-        case 2: return launch_fwd_one<HD, 2>(qkv, out, B, L, H, scale, st);
-        case 3: return launch_fwd_one<HD, 3>(qkv, out, B, L, H, scale, st);
-        case 4: return launch_fwd_one<HD, 4>(qkv, out, B, L, H, scale, st);
-        case 5: return launch_fwd_one<HD, 5>(qkv, out, B, L, H, scale, st);
-        case 6: return launch_fwd_one<HD, 6>(qkv, out, B, L, H, scale, st);
-        case 7: return launch_fwd_one<HD, 7>(qkv, out, B, L, H, scale, st);
-        case 8: return launch_fwd_one<HD, 8>(qkv, out, B, L, H, scale, st);
-    }
-    return fail(STGCN_ERR_UNSUPPORTED, "vit attention (train bf16): L = %d (covered: 1 .. %d)", L, kMaxL);
-}
-
-template <int HD>
-int launch_bwd_hd(const float *qkv, const float *dout, float *dqkv, int B, int L, int H, float scale, hipStream_t st) {
-    switch (ceil_div(L, 32)) {
-        case 1: return launch_bwd_one<HD, 1>(qkv, dout, dqkv, B, L, H, scale, st);
-        case 2: return launch_bwd_one<HD, 2>(qkv, dout, dqkv, B, L, H, scale, st);
-        case 3: return launch_bwd_one<HD, 3>(qkv, dout, dqkv, B, L, H, scale, st);
-        case 4: return launch_bwd_one<HD, 4>(qkv, dout, dqkv, B, L, H, scale, st);
-        case 5: return launch_bwd_one<HD, 5>(qkv, dout, dqkv, B, L, H, scale, st);
-        case 6: return launch_bwd_one<HD, 6>(qkv, dout, dqkv, B, L, H, scale, st);
-        case 7: return launch_bwd_one<HD, 7>(qkv, dout, dqkv, B, L, H, scale, st);
-        case 8: return launch_bwd_one<HD, 8>(qkv, dout, dqkv, B, L, H, scale, st);
-    }
-    return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward (bf16): L = %d (covered: 1 .. %d)", L, kMaxL);
-}
+struct ForwardTrainBf16 {
+    static constexpr const char *what = "vit attention (train bf16)", *kernel_name = "vit_attention_train_bf16_kernel";
+    static constexpr size_t lds_bytes(int nt, int hd) { return attention_bf16_lds_bytes(nt, hd, 2); }
+    template <int HD, int NT>
+    static auto kernel() { return vit_attention_train_bf16_kernel<HD, NT>; }
+};
+struct BackwardBf16 {
+    static constexpr const char *what = "vit attention backward (bf16)", *kernel_name = "vit_attention_bwd_bf16_kernel";
+    static constexpr size_t lds_bytes(int nt, int hd) { return attention_bwd_bf16_lds_bytes(nt, hd); }
+    template <int HD, int NT>
+    static auto kernel() { return vit_attention_bwd_bf16_kernel<HD, NT, attention_bwd_bf16_split(NT, HD)>; }
+};
 
 }  // namespace
 
 int launch_attention_train_bf16(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st) {
-    if (hd == 32) return launch_fwd_hd<32>(qkv, out, B, L, H, scale, st);
-    if (hd == 64) return launch_fwd_hd<64>(qkv, out, B, L, H, scale, st);
-    return fail(STGCN_ERR_UNSUPPORTED, "vit attention (train bf16): head_dim = %d (covered: 32, 64)", hd);
+    return launch_resident<ForwardTrainBf16>(B, L, H, hd, scale, st, qkv, out);
 }
 
 int launch_attention_backward_bf16(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int H, int hd,
                                    float scale, hipStream_t st) {
     (void)out;   // delta is sum P dP of the kernel's own products, not rowsum(dO * out)
-    if (hd == 32) return launch_bwd_hd<32>(qkv, dout, dqkv, B, L, H, scale, st);
-    if (hd == 64) return launch_bwd_hd<64>(qkv, dout, dqkv, B, L, H, scale, st);
-    return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward (bf16): head_dim = %d (covered: 32, 64)", hd);
+    return launch_resident<BackwardBf16>(B, L, H, hd, scale, st, qkv, dout, dqkv);
 }
 
 }  // namespace vit

@@ -10,7 +10,8 @@
 //   A workgroup of 4 waves owns a 128 x 128 tile of dW for one range of tokens; the column sums of dY (the bias gradient)
 //   ride in the workgroups of the first K tile, summed by the threads that stage dY.
 //
-// attention backward: one workgroup per (sequence, head) pair as in the forward (several pairs for L <= 64), two phases:
+// attention backward: built from vit_attention_common.h, which describes the layout it shares with the forward.  One
+//   workgroup per (sequence, head) pair as there (several pairs for L <= 64), two phases:
 //   (a) K and V in LDS, a wave per 32 queries with its Q (pre-scaled) and dO rows in registers: S^T = K Q^T, the soft-max
 //       row maximum and sum, P, delta = rowsum(dO * O), dP^T = V dO^T, dS = P (dP - delta), and dQ^T = K^T dS^T with the
 //       accumulator registers of dS^T as the B operand (the forward's O^T = V^T P^T form).  Row maximum, 1 / sum and delta
@@ -20,13 +21,10 @@
 //       dV^T = dO^T P and dK^T = (scale Q)^T dS, again with the accumulators as the B operand.
 //   Seven products instead of five; no sum across waves, no L x L matrix outside registers.
 //   LDS: ceil(L/32)*32 * (2 (hd + 1) + 4) * 4 bytes = 134 KiB at L = 256, hd 64.
-#include "bf16_common.h"
-#include "vit.h"
+#include "vit_attention_common.h"
 
 namespace stgcn {
 namespace vit {
-
-using bf16k::f32x16;
 
 namespace {
 
@@ -268,7 +266,7 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_kernel(const float *__r
                                                                const float *__restrict__ dout, float *__restrict__ dqkv,
                                                                int pairs, int L, int H, float scale, int G) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int ROWS = NT * 32, KS = HD + 1, HH = HD / 2;
+    constexpr int ROWS = NT * 32, KS = HD + kPadF32, HH = HD / 2;
     float *As = lds;                              // [G][ROWS][KS]: K in phase (a), scale * Q in phase (b)
     float *Bs = lds + (size_t)G * ROWS * KS;      // [G][ROWS][KS]: V in phase (a), dO in phase (b)
     float *Ss = lds + (size_t)2 * G * ROWS * KS;  // [G][ROWS][4]: row maximum, 1 / row sum, delta of every query
@@ -332,7 +330,7 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_kernel(const float *__r
             for (int s = 0; s < HH; ++s) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kp[s], qf[s], sc[kt], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int key = kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                const int key = ACC_KEY(kt * 32, i, half);
                 if (key >= L) sc[kt][i] = -INFINITY;
                 mx = fmaxf(mx, sc[kt][i]);
             }
@@ -376,7 +374,7 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_kernel(const float *__r
             for (int kt = 0; kt < NT; ++kt)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int key = kt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                    const int key = ACC_KEY(kt * 32, i, half);
                     o = __builtin_amdgcn_mfma_f32_32x32x2f32(Ag[(size_t)key * KS + dt * 32 + l31], sc[kt][i], o, 0, 0, 0);
                 }
             if (ri < L) {
@@ -440,7 +438,7 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_kernel(const float *__r
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int q = qt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+            const int q = ACC_KEY(qt * 32, i, half);
             const float4 st = *reinterpret_cast<const float4 *>(&Sg[q * 4]);   // (max, 1 / sum, delta, -); 1 / sum = 0 past L
             const float pr = ri < L ? __expf(s[i] - st.x) * st.y : 0.f;
             s[i] = pr;
@@ -450,7 +448,7 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_kernel(const float *__r
         for (int dt = 0; dt < HD / 32; ++dt)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int q = qt * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                const int q = ACC_KEY(qt * 32, i, half);
                 dv[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Bg[(size_t)q * KS + dt * 32 + l31], s[i], dv[dt], 0, 0, 0);
                 dk[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ag[(size_t)q * KS + dt * 32 + l31], dp[i], dk[dt], 0, 0, 0);
             }
@@ -469,36 +467,12 @@ __global__ __launch_bounds__(512) void vit_attention_bwd_kernel(const float *__r
     }
 }
 
-template <int HD, int NT>
-int launch_bwd_one(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int H, float scale,
-                   hipStream_t st) {
-    const int G = NT >= 4 ? 1 : 4 / NT;
-    const long long pairs = (long long)B * H;
-    if (pairs > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward: %lld (sequence, head) pairs", pairs);
-    const size_t bytes = (size_t)G * NT * 32 * (2 * (HD + 1) + 4) * sizeof(float);
-    if (bytes > (size_t)kLdsBytes) return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward: %zu bytes of LDS", bytes);
-    auto kern = vit_attention_bwd_kernel<HD, NT>;
-    if (bytes > 64 * 1024) STGCN_HIP_CHECK(allow_lds(kern, bytes));
-    kern<<<dim3((unsigned)((pairs + G - 1) / G)), dim3(64 * G * NT), bytes, st>>>(qkv, out, dout, dqkv, (int)pairs, L, H, scale, G);
-    STGCN_LAUNCH_CHECK("vit_attention_bwd_kernel");
-    return STGCN_OK;
-}
-
-template <int HD>
-int launch_bwd_hd(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int H, float scale,
-                  hipStream_t st) {
-    switch (ceil_div(L, 32)) {
-        case 1: return launch_bwd_one<HD, 1>(qkv, out, dout, dqkv, B, L, H, scale, st);
-        case 2: return launch_bwd_one<HD, 2>(qkv, out, dout, dqkv, B, L, H, scale, st);
-        case 3: return launch_bwd_one<HD, 3>(qkv, out, dout, dqkv, B, L, H, scale, st);
-        case 4: return launch_bwd_one<HD, 4>(qkv, out, dout, dqkv, B, L, H, scale, st);
-        case 5: return launch_bwd_one<HD, 5>(qkv, out, dout, dqkv, B, L, H, scale, st);
-        case 6: return launch_bwd_one<HD, 6>(qkv, out, dout, dqkv, B, L, H, scale, st);
-        case 7: return launch_bwd_one<HD, 7>(qkv, out, dout, dqkv, B, L, H, scale, st);
-        case 8: return launch_bwd_one<HD, 8>(qkv, out, dout, dqkv, B, L, H, scale, st);
-    }
-    return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward: L = %d (covered: 1 .. %d)", L, kMaxL);
-}
+struct AttentionBackward {
+    static constexpr const char *what = "vit attention backward", *kernel_name = "vit_attention_bwd_kernel";
+    static constexpr size_t lds_bytes(int nt, int hd) { return attention_bwd_f32_lds_bytes(nt, hd); }
+    template <int HD, int NT>
+    static auto kernel() { return vit_attention_bwd_kernel<HD, NT>; }
+};
 
 }  // namespace
 
@@ -565,9 +539,7 @@ int launch_ln_param_grad(const float *x, const float *dn, const float *stats, fl
 
 int launch_attention_backward(const float *qkv, const float *out, const float *dout, float *dqkv, int B, int L, int H, int hd,
                               float scale, hipStream_t st) {
-    if (hd == 32) return launch_bwd_hd<32>(qkv, out, dout, dqkv, B, L, H, scale, st);
-    if (hd == 64) return launch_bwd_hd<64>(qkv, out, dout, dqkv, B, L, H, scale, st);
-    return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward: head_dim = %d (covered: 32, 64)", hd);
+    return launch_resident<AttentionBackward>(B, L, H, hd, scale, st, qkv, out, dout, dqkv);
 }
 
 }  // namespace vit

@@ -29,17 +29,12 @@ namespace vit {
 
 using bf16k::bf16x8;
 using bf16k::f32x16;
-using bf16k::pack_bf16x2;
+using bf16k::round8;
 
 namespace {
 
 constexpr int WT = 128, WC = 32, WLH = WC + 8;   // tile edge, tokens per chunk, LDS row stride (bf16 elements)
 static_assert(WC == kWgradChunk, "wgrad_rows_per_split cuts ranges in multiples of the chunk");
-
-// eight tokens of one feature -> the eight bf16 of a fragment (RNE), token 0 in the low half of .x
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-    return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
-}
 
 // component-wise, so that the choice is four v_cndmask and not an indexed private array
 __device__ __forceinline__ uint4 pick(bool second, const uint4 a, const uint4 b) {
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(256) void vit_wgrad_bf16_kernel(const float *__rest
             fa[0][i] = in_r && in_k ? ga[i].x : 0.f;
             fa[1][i] = in_r && in_k ? ga[i].y : 0.f;
         }
-        const uint4 d0 = pack8(fd[0]), d1 = pack8(fd[1]), a0 = pack8(fa[0]), a1 = pack8(fa[1]);
+        const uint4 d0 = round8(fd[0]), d1 = round8(fd[1]), a0 = round8(fa[0]), a1 = round8(fa[1]);   // eight tokens of one feature
         const int first = (sf + (swap ? 1 : 0)) * WLH + sq, second = (sf + (swap ? 0 : 1)) * WLH + sq;
         *reinterpret_cast<uint4 *>(&ld[first]) = pick(swap, d0, d1);
         *reinterpret_cast<uint4 *>(&la[first]) = pick(swap, a0, a1);
