@@ -562,6 +562,32 @@ int stgcn_vit_attention_backward_bf16(const float *qkv, const float *out, const 
                                       int heads, int head_dim, float scale, void *stream);
 int stgcn_vit_block_train_attn_bf16_supported(int L, int D, int heads, int hidden);
 
+/* ---- ViT block: the attention split over key tiles, for calls of a few clips (additive to ABI 11: one flag bit, two entry
+ * points, two queries; opt-in) ----
+ * The resident attention gives a (sequence, head) pair one workgroup, so one clip of 8 heads occupies 8 of the 256 CUs.
+ * stgcn_vit_attention_split computes the same fp32 attention with a workgroup per (pair, tile of 32 queries) whose
+ * NT = ceil(L / 32) waves each own one tile of 32 keys: per wave the scores of its keys, their maximum m_w, e = exp(s - m_w),
+ * l_w = sum e and the unnormalised O_w = V_w^T e; then, through LDS and in ascending w,
+ *   m = max m_w, f_w = exp(m_w - m), out = (sum f_w O_w) / (sum f_w l_w).
+ * The same instructions as stgcn_vit_attention (v_mfma_f32_32x32x2_f32, exact fp32 products), no atomics, no workspace, one
+ * launch; results are bit-identical from run to run and agree with the resident form within rounding (another summation
+ * order).  Arguments, checks and coverage (stgcn_vit_attention_split_supported: 1 <= L <= 256, head_dim 32 / 64) are
+ * stgcn_vit_attention's; the entry point runs the split kernel whatever B is.
+ * STGCN_VIT_ATTN_SPLIT is accepted by stgcn_vit_block_forward only.  The block's attention launch then takes the split form
+ * where it is the fp32 resident one (L <= 256, no STGCN_VIT_BF16), L > 32 (two key tiles or more) and the launch has fewer
+ * than 192 (sequence, head) pairs (a measured constant; stgcn_vit_block_attention_form tells); everywhere else the bit is
+ * legal and changes nothing (with STGCN_VIT_BF16, above 256 tokens, at L <= 32, from 192 pairs on).  Workspace sizes do not change.  stgcn_vit_block_forward_train,
+ * stgcn_vit_block_backward, stgcn_vit_linear_backward and stgcn_vit_linear answer STGCN_ERR_ARG to the bit, after their older
+ * flag refusals and before the pointers are looked at.
+ * The value is 0x2000000: 0x400000 and 0x1000000 stay unassigned (host tests use them as unknown bits).
+ * stgcn_vit_block_attention_form: the attention kernel stgcn_vit_block_forward runs for this call (of its first slab, which is
+ * the whole call up to 32768 tokens): 0 uncovered or refused, 1 resident, 2 streaming, 3 resident bf16, 4 resident split.
+ * A pure host function of its arguments. */
+#define STGCN_VIT_ATTN_SPLIT (0x2000000u)
+int stgcn_vit_attention_split_supported(int L, int heads, int head_dim);
+int stgcn_vit_attention_split(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream);
+int stgcn_vit_block_attention_form(int B, int L, int D, int heads, int hidden, unsigned flags);
+
 #ifdef __cplusplus
 }
 #endif

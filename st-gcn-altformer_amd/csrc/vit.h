@@ -81,8 +81,20 @@ constexpr const char *kBlockEntryName[] = {"stgcn_vit_block_forward", "stgcn_vit
 // stream (launch_attention_stream, launch_attention_backward_stream): K and V in key tiles through LDS, above kMaxL and up to
 // kMaxStreamL; resident_bf16 (launch_attention_bf16): the resident form on bf16 qkv / out, STGCN_VIT_BF16 only;
 // resident_train_bf16 (launch_attention_train_bf16, launch_attention_backward_bf16): the resident form on fp32 qkv / out with
-// bf16 matrix operands, the two training entries with STGCN_VIT_TRAIN_ATTN_BF16 up to kMaxL tokens.
-enum class BlockAttention { none, resident, stream, resident_bf16, resident_train_bf16 };
+// bf16 matrix operands, the two training entries with STGCN_VIT_TRAIN_ATTN_BF16 up to kMaxL tokens; resident_split
+// (launch_attention_split): the fp32 resident result with the keys of a (pair, query tile) split over the waves of a workgroup,
+// stgcn_vit_block_forward with STGCN_VIT_ATTN_SPLIT at two key tiles or more.  In a plan it means "where the launch is small
+// enough": block_attention below decides per launch between it and resident.
+enum class BlockAttention { none, resident, stream, resident_bf16, resident_train_bf16, resident_split };
+
+// The split form runs where a launch has fewer (sequence, head) pairs than this.  A compile-time constant, as kLinearTileCut
+// (the plan never asks the device).  It started at 256, the CU count of the MI355X (from there on the resident kernel has a
+// workgroup for every CU), and was MEASURED down to 192 by profiles/altformer_split_attention_times.json
+// (tools/time_altformer.py --attention split --batches 1,2,4,8,16,24,32; the launch-alone rows, DESIGN section 14 "small
+// calls"): at 8 to 128 pairs the split launch is never slower than the resident one by more than the spread (2.9 x faster at
+// 8 pairs of L = 180, head_dim 64), at 192 pairs of that shape it is (0.80 x), so 192 is the largest measured count beneath
+// which that never happens.
+constexpr int kAttentionSplitPairs = 192;
 
 struct BlockPlan {
     BlockEntry entry;
@@ -124,6 +136,8 @@ inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidde
         p.refusal = "training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)";
     } else if (entry == BlockEntry::linear_backward && (flags & STGCN_VIT_TRAIN_ATTN_BF16)) {
         p.refusal = "STGCN_VIT_TRAIN_ATTN_BF16 is a mode of the block (stgcn_vit_block_forward_train, stgcn_vit_block_backward only)";
+    } else if (flags & STGCN_VIT_ATTN_SPLIT) {
+        p.refusal = "STGCN_VIT_ATTN_SPLIT is an inference option (stgcn_vit_block_forward only)";
     }
     // Arithmetic.  STGCN_VIT_QKV_F32 moves the qkv linear (and its dgrad) to f32: an error in q or k is multiplied by the size
     // of the scores before the exponential.  STGCN_VIT_BF16 (inference): every product on operands rounded to bf16, the three
@@ -150,12 +164,23 @@ inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidde
     // STGCN_VIT_TRAIN_ATTN_BF16 moves the resident attention of the two training entries to bf16 operands; the streaming
     // lengths run the fp32 kernels they run without it.
     const bool attn_bf16 = !inference && (flags & STGCN_VIT_TRAIN_ATTN_BF16) != 0;
+    // STGCN_VIT_ATTN_SPLIT (inference) moves the fp32 resident attention to its split form where there are two key tiles or
+    // more to split; the bf16 and the streaming attention have no such form and run as they do without the bit.
+    const bool split = inference && (flags & STGCN_VIT_ATTN_SPLIT) != 0 && L > 32;
     if (p.sized && heads_ok)
         p.attention = bf16 ? BlockAttention::resident_bf16
                       : !p.resident ? BlockAttention::stream
-                      : attn_bf16 ? BlockAttention::resident_train_bf16 : BlockAttention::resident;
+                      : attn_bf16 ? BlockAttention::resident_train_bf16
+                      : split ? BlockAttention::resident_split : BlockAttention::resident;
     p.covered = p.attention != BlockAttention::none && low_ok;
     return p;
+}
+
+// The attention kernel of one launch of a planned call: the plan's, but for the one thing a plan cannot know, the launch's
+// sequence count.  block_forward and stgcn_vit_block_attention_form read this and nothing else.
+inline BlockAttention block_attention(const BlockPlan &p, int sequences, int heads) {
+    if (p.attention != BlockAttention::resident_split) return p.attention;
+    return (long long)sequences * heads < kAttentionSplitPairs ? BlockAttention::resident_split : BlockAttention::resident;
 }
 
 // The two answers an entry point gives from the plan alone: before its pointer checks, and after them.
@@ -232,6 +257,9 @@ int launch_attention_packed(const float *qkv, float *out, int B, int L, int H, i
 // The same result up to the summation order for L <= kMaxStreamL: K and V streamed through LDS in tiles of kStreamKeys keys
 // under a running soft-max, kStreamQueries queries of a pair per workgroup (vit_attention_stream.hip).
 int launch_attention_stream(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
+// The resident result up to the summation order for L <= kMaxL, for launches of few pairs: a workgroup per (pair, query tile of
+// 32), a wave per key tile, the waves' partial soft-maxes merged through LDS in a fixed order (vit_attention_split.hip).
+int launch_attention_split(const float *qkv, float *out, int B, int L, int H, int hd, float scale, hipStream_t st);
 
 // The resident attention on bf16 qkv / out (vit_attention_bf16.hip); L <= kMaxL, hd in {32, 64}.
 int launch_attention_bf16(const void *qkv, void *out, int B, int L, int H, int hd, float scale, hipStream_t st);

@@ -9,6 +9,8 @@
 //            NT = ceil(L / 32) waves are one workgroup next to K and V of the pair in LDS (NT*32 rows, the rows past L
 //            zero-filled, never read from memory); short sequences pack attention_pairs(NT) pairs into a workgroup so that it
 //            has at least four waves.  Streaming: four waves own 128 rows and the other side passes through two LDS stages.
+//            Split (vit_attention_split.hip, L <= kMaxL, few pairs): a workgroup per (pair, query tile), its NT waves one key
+//            tile each, operands from global memory, the partial soft-maxes merged through LDS.
 //   S^T = K Q^T  per key tile of 32: A = K rows from LDS, B = the wave's 32 query rows in registers.  The accumulator puts
 //            query j in lanes j and j + 32, and register i of lane half h holds key 8 (i / 4) + 4 h + i % 4 of the tile
 //            (ACC_KEY).  So a query's whole score row (resident: up to 8 x 16 registers) lives in two lanes, and the
@@ -62,6 +64,11 @@ constexpr size_t row_tile16(int nt, int hd) { return (size_t)nt * 32 * (hd + kPa
 constexpr size_t col_tile16(int nt, int hd) { return (size_t)hd * (nt * 32 + kPad16); }     // elements of [hd][keys + 8]
 // forward: K [rows][hd + 1], V [rows][hd]
 constexpr size_t attention_f32_lds_bytes(int nt, int hd) { return (size_t)attention_pairs(nt) * nt * 32 * (2 * hd + kPadF32) * 4; }
+// split forward (vit_attention_split.hip): K and V come from global memory, LDS holds the merge only: per wave (= key tile) a
+// partial [32][hd + 4] and (max, sum) per query.  70 KiB at L = 256, hd = 64
+constexpr int kPadSplit = 4;
+constexpr int attention_split_wave_floats(int hd) { return 32 * (hd + kPadSplit) + 2 * 32; }
+constexpr size_t attention_split_lds_bytes(int nt, int hd) { return (size_t)nt * attention_split_wave_floats(hd) * 4; }
 // backward: two tiles [rows][hd + 1] and (max, 1 / sum, delta, -) per row.  134 KiB at L = 256, hd = 64
 constexpr size_t attention_bwd_f32_lds_bytes(int nt, int hd) {
     return (size_t)attention_pairs(nt) * nt * 32 * (2 * (hd + kPadF32) + 4) * 4;

@@ -1,5 +1,5 @@
 // C entry points of the AltFormer heads' transformer block (include/stgcn_hip.h, "ViT block"): the linear and the attention
-// (resident and streaming form, and their bf16 forms) on their own, and the eval forward of one Block.  What a block call runs -
+// (resident, split and streaming form, and their bf16 forms) on their own, and the eval forward of one Block.  What a block call runs -
 // attention form, arithmetic per linear, bf16 or fp32 intermediates, tile field - is vit.h's plan_block; block_forward below
 // is the one loop that runs it, for the eval forward here (intermediates in a per-slab workspace) and for the training
 // forward in vit_block_train.hip (intermediates kept for the backward).
@@ -29,8 +29,9 @@ int block_forward(const BlockPlan &plan, const float *x, const BlockWeights &w, 
         if ((rc = launch_linear(xs, w.Wqkv, w.bqkv, nullptr, w.norm1_weight, w.norm1_bias, eps, qkv, M, D, 3 * D, false,
                                 plan.qkv_fwd | tile | yb, st)))
             return rc;
-        switch (plan.attention) {
+        switch (block_attention(plan, nb, heads)) {
             case BlockAttention::resident: rc = launch_attention_packed((float *)qkv, (float *)att, nb, L, heads, hd, scale, st); break;
+            case BlockAttention::resident_split: rc = launch_attention_split((float *)qkv, (float *)att, nb, L, heads, hd, scale, st); break;
             case BlockAttention::stream: rc = launch_attention_stream((float *)qkv, (float *)att, nb, L, heads, hd, scale, st); break;
             case BlockAttention::resident_bf16: rc = launch_attention_bf16(qkv, att, nb, L, heads, hd, scale, st); break;
             case BlockAttention::resident_train_bf16:
@@ -78,6 +79,9 @@ int stgcn_vit_linear(const float *x, const float *W, const float *bias, const fl
     if (flags & STGCN_VIT_TRAIN_ATTN_BF16)
         return fail(STGCN_ERR_ARG, "stgcn_vit_linear: STGCN_VIT_TRAIN_ATTN_BF16 is a training mode of the block "
                     "(stgcn_vit_block_forward_train, stgcn_vit_block_backward only)");
+    if (flags & STGCN_VIT_ATTN_SPLIT)
+        return fail(STGCN_ERR_ARG, "stgcn_vit_linear: STGCN_VIT_ATTN_SPLIT is an option of the block's attention "
+                    "(stgcn_vit_block_forward only)");
     if (!x || !W || !y || M < 1 || K < 1 || Nout < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: null pointer or empty shape");
     if ((ln_weight == nullptr) != (ln_bias == nullptr)) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: ln_weight and ln_bias go together");
     if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_linear: y must not alias x");
@@ -113,6 +117,18 @@ int stgcn_vit_attention_stream(const float *qkv, float *out, int B, int L, int h
         return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention_stream: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)",
                     L, head_dim, kMaxStreamL);
     return launch_attention_stream(qkv, out, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
+}
+
+int stgcn_vit_attention_split_supported(int L, int heads, int head_dim) {
+    return attention_resident_ok(L, heads, head_dim) ? 1 : 0;
+}
+
+int stgcn_vit_attention_split(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream) {
+    if (!qkv || !out || B < 1 || L < 1 || heads < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_attention_split: null pointer or empty shape");
+    if (!stgcn_vit_attention_split_supported(L, heads, head_dim))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_attention_split: L = %d, head_dim = %d (covered: L <= %d, head_dim 32 / 64)", L,
+                    head_dim, kMaxL);
+    return launch_attention_split(qkv, out, B, L, heads, head_dim, scale, static_cast<hipStream_t>(stream));
 }
 
 int stgcn_vit_linear_bf16_supported(int M, int K, int Nout, unsigned flags) {
@@ -159,6 +175,18 @@ int stgcn_vit_block_supported(int L, int D, int heads, int hidden) {
 
 int stgcn_vit_block_forward_supported(int L, int D, int heads, int hidden) {
     return plan_block(BlockEntry::forward, L, D, heads, hidden, 0).covered ? 1 : 0;
+}
+
+int stgcn_vit_block_attention_form(int B, int L, int D, int heads, int hidden, unsigned flags) {
+    const BlockPlan plan = plan_block(BlockEntry::forward, L, D, heads, hidden, flags);
+    if (B < 1 || plan.refusal || !plan.covered) return 0;
+    switch (block_attention(plan, slab_seqs(B, L), heads)) {   // the call's first slab (all of it up to kSlabRows tokens)
+        case BlockAttention::resident: return 1;
+        case BlockAttention::stream: return 2;
+        case BlockAttention::resident_bf16: return 3;
+        case BlockAttention::resident_split: return 4;
+        default: return 0;
+    }
 }
 
 size_t stgcn_vit_block_ws_bytes(int B, int L, int D, int hidden) {

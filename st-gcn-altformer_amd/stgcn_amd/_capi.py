@@ -42,7 +42,8 @@ VIT_X_BF16 = 0x80000  # stgcn_vit_linear_bf16: x is bf16 storage
 VIT_Y_BF16 = 0x100000  # stgcn_vit_linear_bf16: y is bf16 storage
 VIT_TRAIN_BF16 = 0x200000  # the three training entry points: every linear product but the qkv forward on bf16 operands
 VIT_TRAIN_ATTN_BF16 = 0x800000  # the block's two training entry points: the resident attention forward / backward on bf16 operands
-MATH_F16MX = MATH_BF16X3 | STEM_F16MX   # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
+VIT_ATTN_SPLIT = 0x2000000  # stgcn_vit_block_forward: the fp32 resident attention split over key tiles where the launch has few pairs
+MATH_F16MX = MATH_BF16X3 | STEM_F16MX  # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
 
 STATUS = {0: "STGCN_OK", -1: "STGCN_ERR_ARG", -2: "STGCN_ERR_UNSUPPORTED",
           -3: "STGCN_ERR_WORKSPACE", -4: "STGCN_ERR_HIP"}
@@ -126,6 +127,9 @@ PROTOTYPES = {
     "stgcn_vit_attention_train_bf16": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
     "stgcn_vit_attention_backward_bf16": (c_int, [_P] * 4 + [c_int] * 4 + [c_float, _P]),
     "stgcn_vit_block_train_attn_bf16_supported": (c_int, [c_int] * 4),
+    "stgcn_vit_attention_split_supported": (c_int, [c_int] * 3),
+    "stgcn_vit_attention_split": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
+    "stgcn_vit_block_attention_form": (c_int, [c_int] * 5 + [c_uint]),
     "stgcn_vit_block_forward_train": (c_int, [_P] * 15 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
     "stgcn_vit_block_backward": (c_int, [_P] * 12 + [c_size_t] + [_P] * 14 + [c_float, c_float, _P, c_size_t] + [c_int] * 5
                                  + [c_uint, _P]),

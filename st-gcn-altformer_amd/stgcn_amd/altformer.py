@@ -29,7 +29,11 @@ Two paths, one result:
   computes an output element with the same instructions in the same order, so the result is bit-identical to the
   128 x 128 form's.  The forward launches on one stream and takes its workspace from torch's allocator, so it captures under
   ``torch.cuda.graph`` as one sequential graph.  Not covered: training (the training kernels always run 128 x 128 tiles and
-  ``hip_train_min_tokens`` is never touched), and the attention kernel, which at one clip has one workgroup per head.
+  ``hip_train_min_tokens`` is never touched).  The attention kernel at one clip has one workgroup per head;
+  ``set_low_latency(model, min_tokens=0, split_attention=True)`` (opt-in) adds ``VIT_ATTN_SPLIT`` to the inference call: the
+  fp32 attention of a call with fewer than 192 (sequence, head) pairs and more than 32 tokens per sequence then runs split
+  over key tiles, one workgroup per (pair, 32 queries) - the same result up to the summation order, measured 1.07 - 1.08 x
+  on the one-clip ``ST`` model and level on ``TS``.
 * torch ops: everything else - CPU tensors, shapes the kernels do not cover, active dropout, calls under the thresholds,
   ``force_torch``.  This is the reference's arithmetic op for op, so its training scripts keep working unchanged.
 
@@ -68,8 +72,8 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import functional as F
-from ._capi import (MATH_BF16X3, MATH_F32, VIT_BF16, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK, VIT_TRAIN_ATTN_BF16,
-                    VIT_TRAIN_BF16)
+from ._capi import (MATH_BF16X3, MATH_F32, VIT_ATTN_SPLIT, VIT_BF16, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK,
+                    VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16)
 from .modules import Unit2D, enable_stem_fusion, import_class, unit_agcn
 
 HEAD_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32, "bf16": VIT_BF16}
@@ -113,14 +117,17 @@ LOW_LATENCY_MIN_TOKENS = HIP_MIN_TOKENS   # the token count from which the auto-
 #                                          128 x 128 measurement put it; set_low_latency(model, min_tokens=0) runs one clip on HIP
 
 
-def set_low_latency(module: nn.Module, enabled: bool = True, min_tokens=None) -> None:
+def set_low_latency(module: nn.Module, enabled: bool = True, min_tokens=None, split_attention: bool = False) -> None:
     """Small inference calls (down to one clip) of every ``Block`` below on the HIP kernels: ``small_tiles`` (the linears'
     tile form picked per call size, same result bit for bit) and the inference threshold ``min_tokens``
-    (``LOW_LATENCY_MIN_TOKENS`` when None).  ``enabled=False`` restores ``small_tiles = False`` and ``HIP_MIN_TOKENS``.
+    (``LOW_LATENCY_MIN_TOKENS`` when None).  ``split_attention`` (opt-in) sets ``Block.split_attention``: the fp32 attention
+    of a call with few (sequence, head) pairs runs split over key tiles (``VIT_ATTN_SPLIT``; the same result up to the
+    summation order).  ``enabled=False`` restores ``small_tiles = False``, ``split_attention = False`` and ``HIP_MIN_TOKENS``.
     The training threshold is not touched."""
     for sub in module.modules():
         if isinstance(sub, Block):
             sub.small_tiles = bool(enabled)
+            sub.split_attention = bool(enabled) and bool(split_attention)
             if not enabled:
                 sub.hip_min_tokens = HIP_MIN_TOKENS
             else:
@@ -307,6 +314,7 @@ class Block(nn.Module):
         self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
         self.hip_train_max_len = HIP_TRAIN_MAX_LEN         # set_long_training
         self.small_tiles = False               # set_low_latency: the inference linears pick their tile form by call size
+        self.split_attention = False           # set_low_latency(split_attention=True): VIT_ATTN_SPLIT on the inference word
 
     def _weights(self):
         """The parameters by attribute (an nn.DataParallel replica has no ``parameters()``)."""
@@ -375,21 +383,23 @@ class Block(nn.Module):
         ``VIT_TRAIN_ATTN_BF16`` on top of any of them when it says ``'bf16'``, and nothing otherwise.
         Inference: ``math_mode``, else ``_default_head_math()``; ``'bf16'`` only where its resident form covers the length
         (longer sequences run the default arithmetic, still on HIP); ``small_tiles`` adds ``VIT_TILE_AUTO`` unless
-        ``math_mode`` forces a form."""
+        ``math_mode`` forces a form; ``split_attention`` adds ``VIT_ATTN_SPLIT`` (the training word never carries it)."""
         if train:
             attn = self.train_attention_mode if self.train_attention_mode is not None else _default_train_attention()
             bit = VIT_TRAIN_ATTN_BF16 if attn == "bf16" else 0
             if self.train_math_mode is not None:
-                return self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16) | bit
+                return self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16 | VIT_ATTN_SPLIT) | bit
             if self.math_mode is None or self.math_mode & VIT_BF16:
                 return _default_train_math() | bit
-            return self.math_mode & ~VIT_TILE_MASK | bit
+            return self.math_mode & ~(VIT_TILE_MASK | VIT_ATTN_SPLIT) | bit
         math = _default_head_math() if self.math_mode is None else self.math_mode
         if math & VIT_BF16 and not F.vit_block_forward_bf16_supported(x.shape[1], x.shape[2], self.attn.num_heads,
                                                                       self.mlp.fc1.out_features):
             math = HEAD_MATH[DEFAULT_HEAD_MATH] | (math & VIT_TILE_MASK)
         if self.small_tiles and not math & VIT_TILE_MASK:
             math |= VIT_TILE_AUTO
+        if self.split_attention:
+            math |= VIT_ATTN_SPLIT
         return math
 
     def forward(self, x):

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _capi
-from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_BF16, VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16  # noqa: F401 (re-export)
+from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_ATTN_SPLIT, VIT_BF16, VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16  # noqa: F401 (re-export)
 
 BN_EPS = 1e-5
 
@@ -528,7 +528,7 @@ def st_attention_backward(x, dbn_weight, dbn_bias, Wqkv, Wout, bn_weight, bn_bia
 
 # ---- AltFormer heads: transformer block (stgcn_vit_*) ---------------------------------------------------------------------
 def _vit_flags(math: int) -> int:
-    return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32 | _capi.VIT_TILE_MASK | _capi.VIT_BF16)
+    return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32 | _capi.VIT_TILE_MASK | _capi.VIT_BF16 | _capi.VIT_ATTN_SPLIT)
 
 
 def _vit_train_flags(math: int) -> int:
@@ -686,6 +686,27 @@ def vit_attention_stream(qkv, heads, scale=None) -> torch.Tensor:
     return _vit_attention("stgcn_vit_attention_stream", qkv, heads, scale)
 
 
+def vit_attention_split_supported(L, heads, head_dim) -> bool:
+    """Coverage of ``vit_attention_split``: the resident lengths (L <= 256)."""
+    return bool(_capi.lib().stgcn_vit_attention_split_supported(L, heads, head_dim))
+
+
+def vit_attention_split(qkv, heads, scale=None) -> torch.Tensor:
+    """``vit_attention`` (L <= 256) on the split kernel, whatever the batch: a workgroup per (sequence, head, 32 queries), a
+    wave per tile of 32 keys, the waves' partial soft-maxes merged in a fixed order.  The same result up to the summation
+    order; made for calls of a few clips, where the resident kernel leaves most of the device idle."""
+    return _vit_attention("stgcn_vit_attention_split", qkv, heads, scale)
+
+
+ATTENTION_FORMS = {0: None, 1: "resident", 2: "stream", 3: "resident_bf16", 4: "resident_split"}
+
+
+def vit_block_attention_form(B, L, D, heads, hidden, math=MATH_F32):
+    """The attention kernel ``vit_block_forward`` runs for this call with ``math`` (an ``ATTENTION_FORMS`` value; None: not
+    covered, or the flags are refused).  A host function: no GPU needed."""
+    return ATTENTION_FORMS[_capi.lib().stgcn_vit_block_attention_form(B, L, D, heads, hidden, _vit_flags(math))]
+
+
 def vit_block_supported(L, D, heads, hidden) -> bool:
     """Coverage of the resident form (L <= 256): what the training entry points take."""
     return bool(_capi.lib().stgcn_vit_block_supported(L, D, heads, hidden))
@@ -700,7 +721,9 @@ def vit_block_forward(x, norm1, qkv, proj, norm2, fc1, fc2, heads, eps, scale, m
     """Eval forward of one transformer Block on x (B, L, D).  ``norm1`` / ``norm2`` = (weight, bias) of the LayerNorms (one
     ``eps``), ``qkv`` / ``proj`` / ``fc1`` / ``fc2`` = (weight, bias or None) of the nn.Linears as stored.  ``math``: MATH_F32
     or MATH_BF16X3, optionally | VIT_QKV_F32, optionally | a VIT_TILE_* form for the four linears (same result, bit for bit);
-    or VIT_BF16 (optionally | a VIT_TILE_* form): the whole block on bf16 operands, L <= 256 (``vit_block_forward_bf16_supported``)."""
+    or VIT_BF16 (optionally | a VIT_TILE_* form): the whole block on bf16 operands, L <= 256 (``vit_block_forward_bf16_supported``).
+    Any of them optionally | VIT_ATTN_SPLIT: the fp32 resident attention in its split form where the call has few
+    (sequence, head) pairs (``vit_block_attention_form`` tells)."""
     dev = x.device
     B, L, D = x.shape
     hidden = fc1[0].shape[0]

@@ -6,6 +6,7 @@ torch-op path of the same module, in one process, alternating, with device event
                                    [--out profiles/altformer_times.json]
     python tools/time_altformer.py --frames 500 [--batch 32] [--out profiles/altformer_long_times.json]
     python tools/time_altformer.py --math bf16 [--batch 32] [--out profiles/altformer_bf16_times.json]
+    python tools/time_altformer.py --attention split [--out profiles/altformer_split_attention_times.json]
 
 Prints ONE JSON line.  Per stage (a Block at the stage's shape, batch ``--batch``): ms of the HIP path (default arithmetic,
 and 'f32' / 'bf16x3' for comparison) and of the torch path (min, median, max over the repeats; ``spread`` = (max - min) / min of
@@ -30,6 +31,14 @@ models at ``num_frame = T``.
 same alternation: per stage the block in both, per launch the five launches of both (the bf16 ones on the bf16 tensors the
 mode keeps between them), and the whole ST and TS models under the module's default policy.  Every ratio is median over
 median and comes with ``spread``, the larger (max - min) / min of the two rows, and ``bf16_faster_by_more_than_the_spread``.
+
+``--attention split`` times the split attention kernel (``STGCN_VIT_ATTN_SPLIT``) against the resident one in the same
+alternation, at every batch of ``--batches`` (1, 2, 4, 8, 32) for the three stage shapes with two key tiles or more (L 180 at
+head_dim 64 and 32, L 46 at head_dim 64; ``batch`` sequences of 8 heads): the attention launch alone
+(``stgcn_vit_attention`` / ``stgcn_vit_attention_split``), the block with and without the flag ('mixed', auto tiles), and the
+whole one-clip ST and TS models under ``set_low_latency(min_tokens=0)``, eager and captured, with and without
+``split_attention``.  A launch or block sample is ``--inner`` (20) calls between two events, reported per call.  Every row
+has ``spread`` and ``split_faster_by_more_than_the_spread`` / ``split_slower_by_more_than_the_spread``.
 """
 import argparse
 import json
@@ -271,8 +280,107 @@ def bf16_mode(args):
     return res
 
 
+def split_attention(args):
+    """The ``--attention split`` run (see the module docstring)."""
+    import stgcn_amd
+    from stgcn_amd import functional as F
+    from stgcn_amd.altformer import DEFAULT_HEAD_MATH, HEAD_MATH, Block
+    from functools import partial
+    dev = torch.device("cuda:0")
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    batches = [int(b) for b in args.batches.split(",")]
+    heads, n = 8, args.inner
+    shapes = {"ST temporal (L 180, head_dim 64)": (180, 512), "TS temporal (L 180, head_dim 32)": (180, 256),
+              "TS spatial LMDHG (L 46, head_dim 64)": (46, 512)}
+    res = {"attention": "split", "batches": batches, "repeats": args.repeats, "warmup": args.warmup, "launches_per_sample": n,
+           "device": torch.cuda.get_device_name(0), "block_math": DEFAULT_HEAD_MATH + " | VIT_TILE_AUTO", "launch": {}, "block": {},
+           "models": {}}
+
+    def versus(base, split, per=1):
+        spread = max(summary(base)["spread"], summary(split)["spread"])
+        return {"resident_ms": summary([t / per for t in base]), "split_ms": summary([t / per for t in split]),
+                "resident_over_split": round(statistics.median(base) / statistics.median(split), 3), "spread": round(spread, 4),
+                "split_faster_by_more_than_the_spread": faster_by_more_than_the_spread(split, base),
+                "split_slower_by_more_than_the_spread": faster_by_more_than_the_spread(base, split)}
+
+    def times(fn):
+        for _ in range(n):
+            fn()
+    with torch.no_grad():
+        for name, (L, D) in shapes.items():
+            hd = D // heads
+            res["launch"][name], res["block"][name] = {}, {}
+            torch.manual_seed(0)
+            blk = Block(D, heads, mlp_ratio=2., qkv_bias=True, norm_layer=norm).to(dev).eval()
+            a, m = blk.attn, blk.mlp
+            params = ((blk.norm1.weight, blk.norm1.bias), (a.qkv.weight, a.qkv.bias), (a.proj.weight, a.proj.bias),
+                      (blk.norm2.weight, blk.norm2.bias), (m.fc1.weight, m.fc1.bias), (m.fc2.weight, m.fc2.bias))
+            math = HEAD_MATH[DEFAULT_HEAD_MATH] | F._capi.VIT_TILE_AUTO
+            for B in batches:
+                qkv = torch.randn(B, L, 3 * D, device=dev)
+                lt = alternate({"resident": partial(times, lambda: F.vit_attention(qkv, heads)),
+                                "split": partial(times, lambda: F.vit_attention_split(qkv, heads))}, args.repeats, args.warmup)
+                res["launch"][name][f"batch {B}"] = dict(versus(lt["resident"], lt["split"], n), pairs=B * heads,
+                                                         workgroups_resident=-(-B * heads // max(1, 4 // -(-L // 32))),
+                                                         workgroups_split=B * heads * -(-L // 32))
+                x = torch.randn(B, L, D, device=dev)
+                form = F.vit_block_attention_form(B, L, D, heads, 2 * D, math | F.VIT_ATTN_SPLIT)
+                bt = alternate({"resident": partial(times, lambda: F.vit_block_forward(x, *params, heads, 1e-6, a.scale, math)),
+                                "split": partial(times, lambda: F.vit_block_forward(x, *params, heads, 1e-6, a.scale, math | F.VIT_ATTN_SPLIT))},
+                               args.repeats, args.warmup)
+                res["block"][name][f"batch {B}"] = dict(versus(bt["resident"], bt["split"], n), pairs=B * heads, flagged_call_runs=form)
+                del qkv, x
+            del blk
+        for style in ("ST", "TS"):
+            torch.manual_seed(1)
+            model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=22, style=style,
+                                               graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).eval()
+            clip = torch.randn(1, 180, 22, 3, device=dev)
+
+            def run_eager(split):
+                stgcn_amd.set_low_latency(model, min_tokens=0, split_attention=split)
+                return model(clip)
+            graphs, ins, outs = {}, {}, {}               # a graph's static input lives as long as the graph is replayed
+            for split in (False, True):
+                want = run_eager(split).clone()          # also warms the modules' caches
+                torch.cuda.synchronize()
+                ins[split] = clip.clone()
+                graphs[split] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[split]):
+                    outs[split] = model(ins[split])
+                graphs[split].replay()
+                torch.cuda.synchronize()
+                assert torch.equal(outs[split], want), f"{style}: the replay differs from the eager result (split {split})"
+            blocks = [b for b in model.modules() if isinstance(b, Block)]
+            forms = []
+            hooks = [b.register_forward_pre_hook(lambda mod, ar: forms.append(F.vit_block_attention_form(
+                ar[0].shape[0], ar[0].shape[1], ar[0].shape[2], mod.attn.num_heads, mod.mlp.fc1.out_features,
+                mod._hip_flags(ar[0], train=False)))) for b in blocks]
+            run_eager(True)
+            for hk in hooks:
+                hk.remove()
+            tl = alternate({"eager": partial(run_eager, False), "eager_split": partial(run_eager, True),
+                            "captured": graphs[False].replay, "captured_split": graphs[True].replay}, args.repeats, args.warmup)
+            err = (outs[True] - outs[False]).abs().max().item() / outs[False].abs().max().item()
+            res["models"][style] = {"clips": 1, "blocks": len(forms), "blocks_on_the_split_kernel": forms.count("resident_split"),
+                                    "eager": versus(tl["eager"], tl["eager_split"]), "captured": versus(tl["captured"], tl["captured_split"]),
+                                    "split_vs_resident_max_logit_err": float(f"{err:.3e}"),
+                                    "argmax_equal": bool(torch.equal(outs[True].argmax(1), outs[False].argmax(1)))}
+            stgcn_amd.set_low_latency(model, False)
+            del model, graphs, ins, outs
+            torch.cuda.empty_cache()
+    below = [v for rows in res["launch"].values() for v in rows.values() if v["pairs"] < 256]
+    res["split_faster_at_every_launch_below_256_pairs"] = all(v["split_faster_by_more_than_the_spread"] for v in below)
+    res["split_slower_at_some_launch_below_256_pairs"] = any(v["split_slower_by_more_than_the_spread"] for v in below)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--attention", choices=["split"], default=None,
+                    help="time the split attention kernel against the resident one: launch, block and one-clip models")
+    ap.add_argument("--batches", default="1,2,4,8,32", help="--attention split: the batches of the launch and block rows")
+    ap.add_argument("--inner", type=int, default=20, help="--attention split: launches (or block calls) per timed sample")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
@@ -282,8 +390,9 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
-    if args.frames is not None or args.math is not None:
-        line = json.dumps(long_clips(args) if args.frames is not None else bf16_mode(args))
+    if args.frames is not None or args.math is not None or args.attention is not None:
+        line = json.dumps(long_clips(args) if args.frames is not None else bf16_mode(args) if args.math is not None
+                          else split_attention(args))
         if args.out:
             with open(args.out, "w") as f:
                 f.write(line + "\n")
