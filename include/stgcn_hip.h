@@ -588,6 +588,69 @@ int stgcn_vit_attention_split_supported(int L, int heads, int head_dim);
 int stgcn_vit_attention_split(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream);
 int stgcn_vit_block_attention_form(int B, int L, int D, int heads, int hidden, unsigned flags);
 
+/* ---- The whole AltFormer head: stem output to logits in one call (additive to ABI 11: one flag bit, three structs, three
+ * entry points, four queries; inference only) ----
+ * model/AltFormer/model_ST.py (ST) and model_TS.py (TS) after the stem, eval forward:
+ *   ST: first embedding (C -> E1, + pos1 per joint) -> depth1 blocks over the V joints of each of the N*T frames -> MEAN over the
+ *       joints -> second embedding (E1 -> E2, + pos2 per frame) -> depth2 blocks over the T frames of each clip -> MAX over the
+ *       frames -> LayerNorm(E2) -> Linear(E2 -> classes);
+ *   TS: first embedding (+ pos1 per frame) -> depth1 blocks over the T frames of each of the N*V joints -> MAX over the frames ->
+ *       second embedding (+ pos2 per joint) -> depth2 blocks over the V joints of each clip -> MEAN over the joints -> the same
+ *       LayerNorm and Linear.
+ * Two kernels of their own, both fp32, without atomics and with a fixed summation order (bit-identical from run to run):
+ *   stgcn_vit_pool         : out (S, D) = the mean (sum / L) or, with STGCN_VIT_POOL_MAX, the maximum over the L tokens of the
+ *                            dense x (S, L, D).  The maximum is a selection that starts from a token of the sequence: on finite
+ *                            input it is the largest element bit for bit.  Covered: D % 4 == 0, any S < 2^31 and L.  x and out
+ *                            16-byte aligned.  One launch, no workspace.
+ *   stgcn_vit_pool_classify: logits (N, classes) = LayerNorm(pool over L of x (N, L, D)) W^T + bias; the LayerNorm is affine with
+ *                            the biased variance and ln_eps inside the root; W is (classes, D) as nn.Linear stores it, bias may
+ *                            be NULL.  Covered: D % 64 == 0, D <= 4096, any N, L and classes >= 1.  One workgroup per clip, one
+ *                            launch, no workspace.
+ * The embeddings are stgcn_patch_embed's strided fp32 GEMM (the second one with one frame of L2 "joints" per clip: the pooled
+ * rows times embed2_weight^T, plus the bias, plus pos2 by row % L2).
+ *
+ * stgcn_altformer_head_forward covers the head only.  The stem keeps its own entry points and its prepared blob; the two
+ * compose as  stgcn_stem_* with STGCN_OUT_NTVC  ->  this call with STGCN_IN_NTVC in head_flags  (z is then the stem's (N,T,V,C)
+ * output, read in place; without the bit z is (N,C,T,V)).
+ * The structs are HOST structs of DEVICE pointers (blocks1 / blocks2: host arrays of depth1 / depth2 entries); the library
+ * copies nothing and keeps nothing after the call.  In a block's weights bqkv, bproj, b1, b2 may be NULL; pos1 and pos2 may be
+ * NULL (no position table); everything else is required.
+ * flags1 / flags2: the flag words of the two stages' blocks, exactly what stgcn_vit_block_forward takes (math bits,
+ * STGCN_VIT_QKV_F32, the STGCN_VIT_TILE_* field, STGCN_VIT_ATTN_SPLIT, STGCN_VIT_BF16); a stage whose word that entry point
+ * refuses (STGCN_ERR_ARG) or whose shape it does not cover (STGCN_ERR_UNSUPPORTED) makes the whole call answer that status.
+ * head_flags: STGCN_EMBED_TS (off: the ST order and pooling, on: TS) and STGCN_IN_NTVC; any other bit: STGCN_ERR_ARG.
+ * eps_blocks: the LayerNorms of every block; eps_head: the LayerNorm before the classifier (nn.LayerNorm's default 1e-5 in the
+ * reference, not the blocks' 1e-6); scale1 / scale2: the attention scale of the two stages (head_dim ** -0.5 by default).
+ * ws: stgcn_altformer_head_ws_bytes bytes (0 for a call the entry point would not run): the two activation buffers of each
+ * stage, the pooled rows and one block workspace (bounded, stgcn_vit_block_ws_bytes'); short: STGCN_ERR_WORKSPACE.
+ * Order of the answers: flags (STGCN_ERR_ARG), then pointers and dimensions (STGCN_ERR_ARG), then coverage
+ * (STGCN_ERR_UNSUPPORTED), then the workspace; nothing is launched before all four passed.
+ * Launches: 2 embeddings, 5 per block and slab, 1 pool, 1 pooled classifier; all on `stream`, no synchronisation. */
+#define STGCN_VIT_POOL_MAX (0x4000000u)
+typedef struct { const float *norm1_weight, *norm1_bias, *Wqkv, *bqkv, *Wproj, *bproj,
+                             *norm2_weight, *norm2_bias, *W1, *b1, *W2, *b2; } stgcn_vit_block_weights;
+typedef struct { int N, T, V, C, E1, E2, heads, hidden1, hidden2, depth1, depth2, classes; } stgcn_altformer_head_shape;
+typedef struct {
+    const float *embed1_weight, *embed1_bias, *pos1;          /* (E1,C) (E1) (V,E1) [ST] / (T,E1) [TS]; pos may be NULL */
+    const stgcn_vit_block_weights *blocks1;                   /* host array, depth1 entries                           */
+    const float *embed2_weight, *embed2_bias, *pos2;          /* (E2,E1) (E2) (T,E2) [ST] / (V,E2) [TS]               */
+    const stgcn_vit_block_weights *blocks2;                   /* host array, depth2 entries                           */
+    const float *head_norm_weight, *head_norm_bias, *head_weight, *head_bias;   /* (E2) (E2) (classes,E2) (classes)   */
+} stgcn_altformer_head_weights;
+int stgcn_vit_pool_supported(int S, int L, int D);
+int stgcn_vit_pool(const float *x, float *out, int S, int L, int D, unsigned flags, void *stream);
+int stgcn_vit_pool_classify_supported(int N, int L, int D, int classes);
+int stgcn_vit_pool_classify(const float *x, const float *ln_weight, const float *ln_bias, float ln_eps, const float *W,
+                            const float *bias, float *logits, int N, int L, int D, int classes, unsigned flags, void *stream);
+int stgcn_altformer_head_supported(const stgcn_altformer_head_shape *shape, unsigned flags1, unsigned flags2,
+                                   unsigned head_flags);
+size_t stgcn_altformer_head_ws_bytes(const stgcn_altformer_head_shape *shape, unsigned flags1, unsigned flags2,
+                                     unsigned head_flags);
+int stgcn_altformer_head_forward(const float *z, const stgcn_altformer_head_weights *weights,
+                                 const stgcn_altformer_head_shape *shape, float eps_blocks, float eps_head, float scale1,
+                                 float scale2, void *ws, size_t ws_bytes, float *logits, unsigned flags1, unsigned flags2,
+                                 unsigned head_flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 // What the AltFormer heads' transformer block shares between its entry points (vit_block.hip: inference, vit_block_train.hip:
 // training): the plan of a block call (plan_block: what every entry point and every query reads to learn whether the flags are
 // legal, whether the shape is covered, and which kernels, arithmetic and storage the call runs), the forward's slab walker
-// (block_forward), and the launchers of the kernels (vit_linear.hip, vit_attention*.hip, vit_backward.hip, vit_wgrad_bf16.hip).
+// (block_forward), the launchers of the kernels (vit_linear.hip, vit_attention*.hip, vit_backward.hip, vit_wgrad_bf16.hip), and
+// the plan and workspace of the whole head (plan_head, HeadStore: vit_head.hip), which hands each stage to plan_block.
 // All launchers enqueue on `st` and return a stgcn_status.
 #pragma once
 
@@ -315,6 +316,79 @@ int launch_attention_backward(const float *qkv, const float *out, const float *d
 inline size_t attention_stats_floats(int B, int L, int H) { return (size_t)B * H * L * 4; }
 int launch_attention_backward_stream(const float *qkv, const float *out, const float *dout, float *dqkv, float *stats, int B,
                                      int L, int H, int hd, float scale, hipStream_t st);
+
+// ---- the whole head (vit_head.hip) ------------------------------------------------------------------------------------------
+// out (S, D) = the mean (sum / L) or the maximum over the L tokens of every sequence of the dense x (S, L, D), D % 4 == 0:
+// a workgroup per (sequence, chunk of D), 16-byte loads along D, the token lanes of a workgroup joined through LDS in
+// ascending order.  The maximum starts from a token of the sequence, never from zero.
+inline bool pool_ok(long long S, int L, int D) { return S >= 1 && S < (1ll << 31) && L >= 1 && D >= 4 && D % 4 == 0; }
+int launch_pool(const float *x, float *out, long long S, int L, int D, bool max, hipStream_t st);
+// logits (N, classes) = LayerNorm_D(pool_L(x (N, L, D))) W^T + bias, one workgroup per clip: the pooled row and its LayerNorm
+// in LDS, a wave per class.  D % 64 == 0, D <= kMaxLnDim (the blocks' rule), any L and classes.  bias may be NULL.
+inline bool pool_classify_ok(int N, int L, int D, int classes) {
+    return N >= 1 && L >= 1 && classes >= 1 && D >= 64 && D % 64 == 0 && D <= kMaxLnDim;
+}
+int launch_pool_classify(const float *x, const float *gamma, const float *beta, float eps, const float *W, const float *bias,
+                         float *logits, int N, int L, int D, int classes, bool max, hipStream_t st);
+
+// The plan of a whole-head call, decided here and nowhere else: stgcn_altformer_head_supported, .._ws_bytes and .._forward read
+// it and none of them looks at a flag bit or compares a length again.  The two stages' blocks are plan_block's, unrestated.
+//   ST (STGCN_EMBED_TS off): N*T sequences of V joints at E1 -> mean over the joints -> N sequences of T frames at E2 -> max
+//   TS (STGCN_EMBED_TS on) : N*V sequences of T frames at E1 -> max over the frames  -> N sequences of V joints at E2 -> mean
+struct HeadPlan {
+    const char *refusal = nullptr;   // head_flags carries a bit this entry point does not know (STGCN_ERR_ARG)
+    bool shaped = false;             // every dimension is positive (else STGCN_ERR_ARG: nothing below is meaningful)
+    bool covered = false;            // both stages' plans are legal and covered, and so is the glue
+    unsigned embed_flags = 0;        // what launch_patch_embed gets for the first embedding
+    bool pool1_max = false, pool2_max = false;
+    int B1 = 0, L1 = 0, L2 = 0;      // sequences and tokens per sequence of stage 1; tokens per sequence of stage 2 (N sequences)
+    BlockPlan stage1, stage2;
+};
+
+inline HeadPlan plan_head(const stgcn_altformer_head_shape &s, unsigned flags1, unsigned flags2, unsigned head_flags) {
+    HeadPlan p;
+    if (head_flags & ~(unsigned)(STGCN_EMBED_TS | STGCN_IN_NTVC)) p.refusal = "head_flags: only STGCN_EMBED_TS and STGCN_IN_NTVC are read";
+    p.shaped = s.N >= 1 && s.T >= 1 && s.V >= 1 && s.C >= 1 && s.E1 >= 1 && s.E2 >= 1 && s.heads >= 1 && s.hidden1 >= 1 &&
+               s.hidden2 >= 1 && s.depth1 >= 1 && s.depth2 >= 1 && s.classes >= 1;
+    const bool ts = (head_flags & STGCN_EMBED_TS) != 0;
+    p.embed_flags = head_flags & (STGCN_EMBED_TS | STGCN_IN_NTVC);
+    p.pool1_max = ts;
+    p.pool2_max = !ts;
+    p.L1 = ts ? s.T : s.V;
+    p.L2 = ts ? s.V : s.T;
+    p.stage1 = plan_block(BlockEntry::forward, p.L1, s.E1, s.heads, s.hidden1, flags1);
+    p.stage2 = plan_block(BlockEntry::forward, p.L2, s.E2, s.heads, s.hidden2, flags2);
+    if (!p.shaped) return p;
+    const long long B1 = (long long)s.N * p.L2;
+    // 65535 clips: the embeddings put the clip on a grid axis (stgcn_patch_embed's own limit)
+    const bool glue = s.N <= 65535 && pool_ok(B1, p.L1, s.E1) && pool_classify_ok(s.N, p.L2, s.E2, s.classes);
+    p.B1 = glue ? (int)B1 : 0;
+    p.covered = glue && !p.stage1.refusal && !p.stage2.refusal && p.stage1.covered && p.stage2.covered;
+    return p;
+}
+
+// The workspace of a whole-head call, one carve: the two activation buffers of each stage (block_forward's y must not alias
+// its x), the pooled rows between the stages, and one block workspace, the larger stage's.  Run on a NULL base it sizes the
+// buffer; `block_bytes` is the one term that does not grow with the batch beyond a slab.
+struct HeadStore {
+    float *a1, *b1, *pooled, *a2, *b2;
+    void *block;
+    size_t block_bytes, total;
+    HeadStore(void *base, const HeadPlan &p, const stgcn_altformer_head_shape &s) {
+        const size_t rows1 = (size_t)p.B1 * p.L1, rows2 = (size_t)s.N * p.L2;
+        const size_t w1 = BlockStore(nullptr, p.stage1, p.B1, p.L1, s.E1, s.hidden1).total;
+        const size_t w2 = BlockStore(nullptr, p.stage2, s.N, p.L2, s.E2, s.hidden2).total;
+        block_bytes = w1 > w2 ? w1 : w2;
+        Carve c(base);
+        a1 = c.take<float>(rows1 * s.E1);
+        b1 = c.take<float>(rows1 * s.E1);
+        pooled = c.take<float>((size_t)p.B1 * s.E1);
+        a2 = c.take<float>(rows2 * s.E2);
+        b2 = c.take<float>(rows2 * s.E2);
+        block = c.take<char>(block_bytes);
+        total = c.off;
+    }
+};
 
 }  // namespace vit
 }  // namespace stgcn

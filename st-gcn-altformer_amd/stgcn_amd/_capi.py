@@ -43,12 +43,32 @@ VIT_Y_BF16 = 0x100000  # stgcn_vit_linear_bf16: y is bf16 storage
 VIT_TRAIN_BF16 = 0x200000  # the three training entry points: every linear product but the qkv forward on bf16 operands
 VIT_TRAIN_ATTN_BF16 = 0x800000  # the block's two training entry points: the resident attention forward / backward on bf16 operands
 VIT_ATTN_SPLIT = 0x2000000  # stgcn_vit_block_forward: the fp32 resident attention split over key tiles where the launch has few pairs
+VIT_POOL_MAX = 0x4000000  # stgcn_vit_pool / stgcn_vit_pool_classify: the maximum over the tokens instead of the mean
 MATH_F16MX = MATH_BF16X3 | STEM_F16MX  # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
 
 STATUS = {0: "STGCN_OK", -1: "STGCN_ERR_ARG", -2: "STGCN_ERR_UNSUPPORTED",
           -3: "STGCN_ERR_WORKSPACE", -4: "STGCN_ERR_HIP"}
 
 _P = c_void_p
+
+
+# the three host structs of the whole-head call (include/stgcn_hip.h, "The whole AltFormer head"): device pointers and sizes
+class VitBlockWeights(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("norm1_weight", "norm1_bias", "Wqkv", "bqkv", "Wproj", "bproj", "norm2_weight", "norm2_bias",
+                                  "W1", "b1", "W2", "b2")]
+
+
+class AltformerHeadShape(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("N", "T", "V", "C", "E1", "E2", "heads", "hidden1", "hidden2", "depth1", "depth2", "classes")]
+
+
+class AltformerHeadWeights(ctypes.Structure):
+    _fields_ = [("embed1_weight", _P), ("embed1_bias", _P), ("pos1", _P), ("blocks1", ctypes.POINTER(VitBlockWeights)),
+                ("embed2_weight", _P), ("embed2_bias", _P), ("pos2", _P), ("blocks2", ctypes.POINTER(VitBlockWeights)),
+                ("head_norm_weight", _P), ("head_norm_bias", _P), ("head_weight", _P), ("head_bias", _P)]
+
+
+_SHAPE_P = ctypes.POINTER(AltformerHeadShape)
 # name -> (restype, argtypes); one entry per symbol declared in include/stgcn_hip.h
 PROTOTYPES = {
     "stgcn_version": (c_int, []),
@@ -130,6 +150,14 @@ PROTOTYPES = {
     "stgcn_vit_attention_split_supported": (c_int, [c_int] * 3),
     "stgcn_vit_attention_split": (c_int, [_P] * 2 + [c_int] * 4 + [c_float, _P]),
     "stgcn_vit_block_attention_form": (c_int, [c_int] * 5 + [c_uint]),
+    "stgcn_vit_pool_supported": (c_int, [c_int] * 3),
+    "stgcn_vit_pool": (c_int, [_P] * 2 + [c_int] * 3 + [c_uint, _P]),
+    "stgcn_vit_pool_classify_supported": (c_int, [c_int] * 4),
+    "stgcn_vit_pool_classify": (c_int, [_P] * 3 + [c_float] + [_P] * 3 + [c_int] * 4 + [c_uint, _P]),
+    "stgcn_altformer_head_supported": (c_int, [_SHAPE_P, c_uint, c_uint, c_uint]),
+    "stgcn_altformer_head_ws_bytes": (c_size_t, [_SHAPE_P, c_uint, c_uint, c_uint]),
+    "stgcn_altformer_head_forward": (c_int, [_P, ctypes.POINTER(AltformerHeadWeights), _SHAPE_P] + [c_float] * 4
+                                     + [_P, c_size_t, _P] + [c_uint] * 3 + [_P]),
     "stgcn_vit_block_forward_train": (c_int, [_P] * 15 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
     "stgcn_vit_block_backward": (c_int, [_P] * 12 + [c_size_t] + [_P] * 14 + [c_float, c_float, _P, c_size_t] + [c_int] * 5
                                  + [c_uint, _P]),

@@ -13,7 +13,15 @@ Two paths, one result:
   nothing that concerns the block (``torch.no_grad()``, or no input and no parameter requires a gradient), no dropout /
   stochastic depth is active, and the call has at least ``HIP_MIN_TOKENS`` tokens (smaller calls are latency-bound; ``set_hip_min_tokens(model, 0)`` lifts it).
   The head's first patch embedding then runs through ``functional.patch_embed`` on the stem output (contiguous or
-  channels-last, consumed in place); pooling, the second embedding and ``mlp_head`` are torch ops.
+  channels-last, consumed in place); on this per-block path pooling, the second embedding and ``mlp_head`` are torch ops.
+* HIP, the whole head (``set_whole_head(model)``, opt-in; ``stgcn_altformer_head_forward``): one library call from the stem
+  output to the logits - both embeddings, every block under its stage's plan, the pooling between the stages
+  (``stgcn_vit_pool``) and the pooled LayerNorm + classifier (``stgcn_vit_pool_classify``) - on one workspace from torch's
+  allocator, so it captures under ``torch.cuda.graph``.  It runs under the inference conditions above for the whole head
+  (``_Head.runs_whole(z)`` tells) and does NOT consult the per-block token thresholds: the caller asked for the whole head.
+  Each stage runs under the flag word of its first block; a stage whose blocks disagree takes the per-block path.
+  Measured against the per-block path (DESIGN section 14 "the whole head"): 1.7 - 2.5 % faster at one clip under a captured
+  graph, level eager, and not faster (the ``TS`` head 6 - 10 % slower) at 32 clips, where the per-block default stays the one to use.
 * HIP, training (``stgcn_vit_block_forward_train`` / ``stgcn_vit_block_backward`` behind one ``autograd.Function``): the same
   input conditions while autograd IS recording something that concerns the block (``.train()``, or ``.eval()`` with gradients),
   sequences of up to 256 tokens (longer ones train on torch ops unless ``set_long_training(model)`` opts in: then up to
@@ -132,6 +140,17 @@ def set_low_latency(module: nn.Module, enabled: bool = True, min_tokens=None, sp
                 sub.hip_min_tokens = HIP_MIN_TOKENS
             else:
                 sub.hip_min_tokens = LOW_LATENCY_MIN_TOKENS if min_tokens is None else int(min_tokens)
+
+
+def set_whole_head(module: nn.Module, enabled: bool = True) -> None:
+    """Every ``ST`` / ``TS`` head below runs from the stem output to the logits in ONE library call
+    (``stgcn_altformer_head_forward``: both embeddings, every block, the pooling between the stages and the pooled LayerNorm +
+    classifier) wherever ``_Head.runs_whole(z)`` says it can; everywhere else, and with ``enabled=False`` (the default of a
+    new head), the forward is the per-block one.  The caller asks for the whole head: the per-block token thresholds
+    (``hip_min_tokens``) are NOT consulted, the blocks' arithmetic, tile and split-attention settings are."""
+    for sub in module.modules():
+        if isinstance(sub, _Head):
+            sub.whole_head = bool(enabled)
 
 
 HIP_TRAIN_MAX_LEN = 256        # longest sequence a Block trains on HIP by default: the resident attention kernels' limit
@@ -453,6 +472,76 @@ class _Head(nn.Module):
         self.mlp_head = nn.Sequential(nn.LayerNorm(embed_dim), nn.Linear(embed_dim, class_num))
         self.fcn = nn.Conv1d(512, class_num, kernel_size=1)
 
+    whole_head = False   # set_whole_head: the one-call forward where runs_whole(z) allows it
+
+    def _stages(self):
+        """(order, first embedding, its position table, its blocks, second embedding, its position table, its blocks)."""
+        raise NotImplementedError
+
+    def _whole_plan(self, z):
+        """The arguments of ``functional.altformer_head_forward`` for this call, taken by attribute (an nn.DataParallel
+        replica has no ``parameters()``), or None where the head takes the per-block forward."""
+        if not self.whole_head or not torch.is_tensor(z) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 4:
+            return None
+        if not (z.is_contiguous() or F._is_channels_last(z)):
+            return None
+        order, lin1, pos1, blocks1, lin2, pos2, blocks2 = self._stages()
+        head = self.mlp_head
+        if not (isinstance(head, nn.Sequential) and len(head) == 2 and type(head[0]) is nn.LayerNorm and type(head[1]) is nn.Linear
+                and head[0].elementwise_affine and head[0].bias is not None and type(lin1) is nn.Linear and type(lin2) is nn.Linear
+                and lin1.bias is not None and lin2.bias is not None and len(blocks1) and len(blocks2)
+                and all(type(b) is Block for b in list(blocks1) + list(blocks2))):
+            return None
+        glue = (lin1.weight, lin1.bias, pos1, lin2.weight, lin2.bias, pos2, head[0].weight, head[0].bias, head[1].weight, head[1].bias)
+        if torch.is_grad_enabled() and (z.requires_grad or any(t is not None and t.requires_grad for t in glue)):
+            return None
+        if _drop_active(self):
+            return None
+        N, C, T, V = z.shape
+        E1, E2 = lin1.out_features, lin2.out_features
+        L1, L2 = (T, V) if order == "TS" else (V, T)
+        if lin1.in_features != C or lin2.in_features != E1 or head[0].normalized_shape != (E2,) or head[1].in_features != E2:
+            return None
+        if pos1.numel() != L1 * E1 or pos2.numel() != L2 * E2:
+            return None
+        first = blocks1[0]
+        words = []
+        for blocks, B, L, D in ((blocks1, N * L2, L1, E1), (blocks2, N, L2, E2)):
+            probe = z.as_strided((B, L, D), (0, 0, 0))      # the stage's shape without its memory
+            b0 = blocks[0]
+            word = b0._hip_flags(probe, train=False)
+            for b in blocks:
+                if not b.hip_applies(probe) or b._hip_flags(probe, train=False) != word:
+                    return None
+                if (b.attn.num_heads != first.attn.num_heads or b.norm1.eps != first.norm1.eps or b.attn.scale != b0.attn.scale
+                        or b.mlp.fc1.out_features != b0.mlp.fc1.out_features):
+                    return None
+            words.append(word)
+        if not F.altformer_head_supported(N, T, V, C, E1, E2, first.attn.num_heads, blocks1[0].mlp.fc1.out_features,
+                                          blocks2[0].mlp.fc1.out_features, len(blocks1), len(blocks2), head[1].out_features,
+                                          order, words[0], words[1]):
+            return None
+        return dict(embed1=(lin1.weight, lin1.bias), pos1=pos1, blocks1=[tuple(b._weights()) for b in blocks1],
+                    embed2=(lin2.weight, lin2.bias), pos2=pos2, blocks2=[tuple(b._weights()) for b in blocks2],
+                    head_norm=(head[0].weight, head[0].bias), head_linear=(head[1].weight, head[1].bias),
+                    heads=first.attn.num_heads, eps_blocks=first.norm1.eps, eps_head=head[0].eps, scale1=blocks1[0].attn.scale,
+                    scale2=blocks2[0].attn.scale, order=order, math1=words[0], math2=words[1])
+
+    def runs_whole(self, z) -> bool:
+        """Whether ``forward(z)`` is the one library call: ``whole_head`` is on (``set_whole_head``), z is CUDA float32
+        (contiguous or channels-last), autograd records nothing that concerns the head, no dropout or stochastic depth is
+        active, every ``Block`` answers ``hip_applies`` for its stage's shape, the blocks of a stage agree on their flag word
+        (``Block._hip_flags`` of the stage's first block is the stage's) and ``stgcn_altformer_head_supported`` agrees."""
+        return self._whole_plan(z) is not None
+
+    def _forward_whole(self, z):
+        """The logits from the one call, or None where this call takes the per-block forward."""
+        plan = self._whole_plan(z)
+        if plan is None:
+            return None
+        with torch.no_grad():
+            return F.altformer_head_forward(z, **plan)
+
     def _first_stage(self, x, lin, pos, blocks, order):
         """Stem output (N, C, T, V) -> rows (N*T, V, E) ('ST') or (N*V, T, E) ('TS') through the first embedding and blocks."""
         if _embed_on_hip(x, lin):
@@ -507,7 +596,14 @@ class ST(_Head):
         feature = max_over_tokens(x)
         return self.mlp_head(feature), feature.unsqueeze(-1)
 
+    def _stages(self):
+        return ("ST", self.Spatial_patch_to_embedding, self.Spatial_pos_embed, self.Spatial_blocks,
+                self.Temporal_patch_to_embedding, self.Temporal_pos_embed, self.blocks)
+
     def forward(self, x):
+        whole = self._forward_whole(x)
+        if whole is not None:
+            return whole
         return self.forward_features(self.Spatial_forward_features(x))[0]
 
 
@@ -540,7 +636,14 @@ class TS(_Head):
         x = self._second_stage(x, self.Spatial_patch_to_embedding, self.Spatial_pos_embed, self.Spatial_blocks)
         return self.mlp_head(x.mean(dim=1))
 
+    def _stages(self):
+        return ("TS", self.temporal_patch_to_embedding, self.Temporal_pos_embed, self.blocks,
+                self.Spatial_patch_to_embedding, self.Spatial_pos_embed, self.Spatial_blocks)
+
     def forward(self, x):
+        whole = self._forward_whole(x)
+        if whole is not None:
+            return whole
         return self.Spatial_forward_features(self.Temporal_forward_features(x))
 
 

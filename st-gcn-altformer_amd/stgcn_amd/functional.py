@@ -742,6 +742,131 @@ def vit_block_forward(x, norm1, qkv, proj, norm2, fc1, fc2, heads, eps, scale, m
     return y
 
 
+# ---- AltFormer heads: the whole head (stgcn_vit_pool, stgcn_vit_pool_classify, stgcn_altformer_head_*) -----------------------
+def vit_pool_supported(S, L, D) -> bool:
+    return bool(_capi.lib().stgcn_vit_pool_supported(S, L, D))
+
+
+def vit_pool(x, mode="mean") -> torch.Tensor:
+    """The mean (``sum / L``) or the maximum over the tokens of every sequence of x (S, L, D) -> (S, D); ``mode``: 'mean' |
+    'max'.  The maximum equals ``x.max(dim=1).values`` bit for bit on finite input."""
+    if mode not in ("mean", "max"):
+        raise ValueError(f"mode must be 'mean' or 'max' (got {mode!r})")
+    dev = x.device
+    S, L, D = x.shape
+    out = torch.empty((S, D), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_pool", _dev_ptr(x, "x", dev), _dev_ptr(out, "out"), c_int(S), c_int(L), c_int(D),
+                   c_uint(_capi.VIT_POOL_MAX if mode == "max" else 0), _stream(dev))
+    return out
+
+
+def vit_pool_classify_supported(N, L, D, classes) -> bool:
+    return bool(_capi.lib().stgcn_vit_pool_classify_supported(N, L, D, classes))
+
+
+def vit_pool_classify(x, ln_weight, ln_bias, eps, weight, bias=None, mode="max", logits=None) -> torch.Tensor:
+    """``Linear(LayerNorm(pool(x)))`` on x (N, L, D) -> (N, classes): the pooling of ``vit_pool`` over L, an affine LayerNorm
+    over D (biased variance, ``eps`` inside the root), ``weight`` (classes, D) and ``bias`` as nn.Linear stores them."""
+    if mode not in ("mean", "max"):
+        raise ValueError(f"mode must be 'mean' or 'max' (got {mode!r})")
+    dev = x.device
+    N, L, D = x.shape
+    classes = weight.shape[0]
+    if weight.shape[1] != D or ln_weight.numel() != D or ln_bias.numel() != D:
+        raise ValueError(f"weight is {tuple(weight.shape)}, the LayerNorm has {ln_weight.numel()} features, x has {D}")
+    if logits is None:
+        logits = torch.empty((N, classes), device=dev, dtype=torch.float32)
+    elif logits.shape != (N, classes):
+        raise ValueError(f"logits is {tuple(logits.shape)}, expected {(N, classes)}")
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_pool_classify", _dev_ptr(x, "x", dev), _dev_ptr(ln_weight, "ln weight", dev),
+                   _dev_ptr(ln_bias, "ln bias", dev), c_float(eps), _dev_ptr(weight, "weight", dev), _dev_ptr(bias, "bias", dev),
+                   _dev_ptr(logits, "logits", dev), c_int(N), c_int(L), c_int(D), c_int(classes),
+                   c_uint(_capi.VIT_POOL_MAX if mode == "max" else 0), _stream(dev))
+    return logits
+
+
+def _head_shape(N, T, V, C, E1, E2, heads, hidden1, hidden2, depth1, depth2, classes):
+    return _capi.AltformerHeadShape(N, T, V, C, E1, E2, heads, hidden1, hidden2, depth1, depth2, classes)
+
+
+def _head_flags(order, channels_last=False) -> int:
+    if order not in ("ST", "TS"):
+        raise ValueError(f"order must be 'ST' or 'TS' (got {order!r})")
+    return (_capi.EMBED_TS if order == "TS" else 0) | (_capi.IN_NTVC if channels_last else 0)
+
+
+def altformer_head_supported(N, T, V, C, E1, E2, heads, hidden1, hidden2, depth1, depth2, classes, order="ST", math1=MATH_F32,
+                             math2=MATH_F32) -> bool:
+    """Whether ``altformer_head_forward`` runs this head (both stages' blocks under their flag words, and the glue).  A host
+    function: no GPU needed."""
+    shape = _head_shape(N, T, V, C, E1, E2, heads, hidden1, hidden2, depth1, depth2, classes)
+    return bool(_capi.lib().stgcn_altformer_head_supported(shape, _vit_flags(math1), _vit_flags(math2), _head_flags(order)))
+
+
+def _head_ws_bytes(shape, flags1, flags2, head_flags) -> int:
+    return int(_capi.lib().stgcn_altformer_head_ws_bytes(shape, flags1, flags2, head_flags))
+
+
+def _block_structs(blocks, dev):
+    arr = (_capi.VitBlockWeights * len(blocks))()
+    for dst, params in zip(arr, blocks):
+        if len(params) != len(VIT_BLOCK_PARAMS):
+            raise ValueError(f"a block has {len(params)} parameters, expected {len(VIT_BLOCK_PARAMS)}")
+        for (field, _), name, t in zip(_capi.VitBlockWeights._fields_, VIT_BLOCK_PARAMS, params):
+            setattr(dst, field, _dev_ptr(t, name, dev))
+    return arr
+
+
+def altformer_head_forward(z, embed1, pos1, blocks1, embed2, pos2, blocks2, head_norm, head_linear, heads, eps_blocks, eps_head,
+                           scale1, scale2, order="ST", math1=MATH_F32, math2=MATH_F32, logits=None) -> torch.Tensor:
+    """An AltFormer head from the stem output z (N, C, T, V) - contiguous, or channels-last strided as ``patch_embed`` takes it -
+    to the logits (N, classes) in one library call (stgcn_altformer_head_forward): both embeddings, every block of both stages,
+    the pooling between them and the pooled LayerNorm + classifier.
+
+    ``embed1`` / ``embed2`` / ``head_linear`` = (weight, bias) of the nn.Linears, ``head_norm`` = (weight, bias) of the
+    LayerNorm before the classifier (``eps_head``), ``pos1`` / ``pos2`` the position tables or None, ``blocks1`` / ``blocks2``
+    one sequence of the twelve tensors in ``VIT_BLOCK_PARAMS`` order per block (a bias may be None), ``math1`` / ``math2`` the
+    two stages' flag words as ``vit_block_forward`` takes them, ``order`` 'ST' (mean over joints, then max over frames) or 'TS'.
+    The structs are built from these tensors on every call - nothing is packed or cached - and the workspace comes from
+    torch's allocator, so the call captures under ``torch.cuda.graph``."""
+    dev = z.device
+    N, C, T, V = z.shape
+    channels_last = _is_channels_last(z)
+    if channels_last:
+        z = z.permute(0, 2, 3, 1)
+    E1, E2, classes = embed1[0].shape[0], embed2[0].shape[0], head_linear[0].shape[0]
+    L1, L2 = (T, V) if order == "TS" else (V, T)
+    if embed1[0].shape[1] != C or embed2[0].shape[1] != E1 or head_linear[0].shape[1] != E2 or head_norm[0].numel() != E2:
+        raise ValueError("the embeddings, the LayerNorm and the classifier do not chain")
+    for pos, want, name in ((pos1, L1 * E1, "pos1"), (pos2, L2 * E2, "pos2")):
+        if pos is not None and pos.numel() != want:
+            raise ValueError(f"{name} has {pos.numel()} elements, expected {want}")
+    if not blocks1 or not blocks2:
+        raise ValueError("each stage needs at least one block")
+    shape = _head_shape(N, T, V, C, E1, E2, heads, blocks1[0][8].shape[0], blocks2[0][8].shape[0], len(blocks1), len(blocks2),
+                        classes)
+    fl1, fl2, hf = _vit_flags(math1), _vit_flags(math2), _head_flags(order, channels_last)
+    b1, b2 = _block_structs(blocks1, dev), _block_structs(blocks2, dev)
+    w = _capi.AltformerHeadWeights(
+        _dev_ptr(embed1[0], "embed1.weight", dev), _dev_ptr(embed1[1], "embed1.bias", dev), _dev_ptr(pos1, "pos1", dev), b1,
+        _dev_ptr(embed2[0], "embed2.weight", dev), _dev_ptr(embed2[1], "embed2.bias", dev), _dev_ptr(pos2, "pos2", dev), b2,
+        _dev_ptr(head_norm[0], "head_norm.weight", dev), _dev_ptr(head_norm[1], "head_norm.bias", dev),
+        _dev_ptr(head_linear[0], "head.weight", dev), _dev_ptr(head_linear[1], "head.bias", dev))
+    nbytes = _head_ws_bytes(shape, fl1, fl2, hf)
+    ws = _bytes(dev, nbytes)
+    if logits is None:
+        logits = torch.empty((N, classes), device=dev, dtype=torch.float32)
+    elif logits.shape != (N, classes):
+        raise ValueError(f"logits is {tuple(logits.shape)}, expected {(N, classes)}")
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_altformer_head_forward", _dev_ptr(z, "z", dev), w, shape, c_float(eps_blocks), c_float(eps_head),
+                   c_float(scale1), c_float(scale2), c_void_p(ws.data_ptr()), c_size_t(nbytes), _dev_ptr(logits, "logits", dev),
+                   c_uint(fl1), c_uint(fl2), c_uint(hf), _stream(dev))
+    return logits
+
+
 # ---- AltFormer heads: training (stgcn_vit_*_backward, stgcn_vit_block_forward_train) ------------------------------------------
 def vit_linear_backward_supported(M, K, Nout, math=MATH_F32) -> bool:
     return bool(_capi.lib().stgcn_vit_linear_backward_supported(M, K, Nout, math & _capi.MATH_MASK))

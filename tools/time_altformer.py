@@ -7,6 +7,7 @@ torch-op path of the same module, in one process, alternating, with device event
     python tools/time_altformer.py --frames 500 [--batch 32] [--out profiles/altformer_long_times.json]
     python tools/time_altformer.py --math bf16 [--batch 32] [--out profiles/altformer_bf16_times.json]
     python tools/time_altformer.py --attention split [--out profiles/altformer_split_attention_times.json]
+    python tools/time_altformer.py --head whole [--batches 1,32] [--out profiles/altformer_whole_head_times.json]
 
 Prints ONE JSON line.  Per stage (a Block at the stage's shape, batch ``--batch``): ms of the HIP path (default arithmetic,
 and 'f32' / 'bf16x3' for comparison) and of the torch path (min, median, max over the repeats; ``spread`` = (max - min) / min of
@@ -39,6 +40,13 @@ head_dim 64 and 32, L 46 at head_dim 64; ``batch`` sequences of 8 heads): the at
 whole one-clip ST and TS models under ``set_low_latency(min_tokens=0)``, eager and captured, with and without
 ``split_attention``.  A launch or block sample is ``--inner`` (20) calls between two events, reported per call.  Every row
 has ``spread`` and ``split_faster_by_more_than_the_spread`` / ``split_slower_by_more_than_the_spread``.
+
+``--head whole`` times the one-call head (``set_whole_head``, ``stgcn_altformer_head_forward``) against the per-block path in
+the same alternation, at every batch of ``--batches`` (default 1,32), styles ST and TS: the head alone on a fixed stem output
+and the whole model from skeleton clips, each eager and captured in a graph.  The per-block arm is the policy a user has
+without the switch: ``set_low_latency(model, min_tokens=0)`` at fewer than 8 clips, the default thresholds from there on.  A
+sample is ``max(1, --inner // batch)`` forwards between two events, reported per forward.  Every row has ``spread`` and
+``whole_faster_by_more_than_the_spread`` / ``whole_slower_by_more_than_the_spread``.
 """
 import argparse
 import json
@@ -375,11 +383,81 @@ def split_attention(args):
     return res
 
 
+def whole_head(args):
+    """The ``--head whole`` run (see the module docstring)."""
+    import stgcn_amd
+    from functools import partial
+    dev = torch.device("cuda:0")
+    batches = [int(b) for b in args.batches.split(",")]
+    res = {"head": "whole", "batches": batches, "repeats": args.repeats, "warmup": args.warmup, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0), "rows": {}}
+
+    def versus(base, whole, per):
+        spread = max(summary(base)["spread"], summary(whole)["spread"])
+        return {"per_block_ms": summary([t / per for t in base]), "whole_ms": summary([t / per for t in whole]),
+                "per_block_over_whole": round(statistics.median(base) / statistics.median(whole), 3), "spread": round(spread, 4),
+                "whole_faster_by_more_than_the_spread": faster_by_more_than_the_spread(whole, base),
+                "whole_slower_by_more_than_the_spread": faster_by_more_than_the_spread(base, whole)}
+    with torch.no_grad():
+        for style in ("ST", "TS"):
+            torch.manual_seed(1)
+            model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=22, style=style,
+                                               graph="graph.SHRE", graph_args={"labeling_mode": "spatial"}).to(dev).eval()
+            head = model.modelA if style == "ST" else model.modelB
+            for N in batches:
+                n = max(1, args.inner // N)
+                stgcn_amd.set_low_latency(model, N < 8, min_tokens=0 if N < 8 else None)
+                clip = torch.randn(N, 180, 22, 3, device=dev)
+                stgcn_amd.set_whole_head(model, False)
+                z = model.tcn0(model.gcn0(clip.permute(0, 3, 1, 2))).clone()
+                subjects = {"head": (head, z), "model": (model, clip)}
+                row = {"clips": N, "forwards_per_sample": n,
+                       "per_block_policy": "set_low_latency(min_tokens=0)" if N < 8 else "default thresholds"}
+                for what, (mod, x) in subjects.items():
+                    def run_eager(whole, mod=mod, x=x):
+                        stgcn_amd.set_whole_head(model, whole)
+                        for _ in range(n):
+                            out = mod(x)
+                        return out
+                    graphs, ins, outs = {}, {}, {}
+                    for whole in (False, True):
+                        want = run_eager(whole).clone()
+                        assert head.runs_whole(z) == whole
+                        torch.cuda.synchronize()
+                        ins[whole] = x.clone()
+                        graphs[whole] = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(graphs[whole]):
+                            for _ in range(n):
+                                outs[whole] = mod(ins[whole])
+                        graphs[whole].replay()
+                        torch.cuda.synchronize()
+                        assert torch.equal(outs[whole], want), f"{style} {what}: the replay differs from the eager result"
+                    tl = alternate({"eager": partial(run_eager, False), "eager_whole": partial(run_eager, True),
+                                    "captured": graphs[False].replay, "captured_whole": graphs[True].replay}, args.repeats, args.warmup)
+                    err = (outs[True] - outs[False]).abs().max().item() / outs[False].abs().max().item()
+                    row[what] = {"eager": versus(tl["eager"], tl["eager_whole"], n),
+                                 "captured": versus(tl["captured"], tl["captured_whole"], n),
+                                 "whole_vs_per_block_max_logit_err": float(f"{err:.3e}"),
+                                 "argmax_equal": bool(torch.equal(outs[True].argmax(1), outs[False].argmax(1)))}
+                    del graphs, ins, outs
+                res["rows"][f"{style} batch {N}"] = row
+                stgcn_amd.set_whole_head(model, False)
+                stgcn_amd.set_low_latency(model, False)
+                del z, clip
+                torch.cuda.empty_cache()
+            del model, head
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--head", choices=["whole"], default=None,
+                    help="time the one-call head (set_whole_head) against the per-block path: head alone and whole model")
     ap.add_argument("--attention", choices=["split"], default=None,
                     help="time the split attention kernel against the resident one: launch, block and one-clip models")
-    ap.add_argument("--batches", default="1,2,4,8,32", help="--attention split: the batches of the launch and block rows")
+    ap.add_argument("--batches", default=None,
+                    help="--attention split: the batches of the launch and block rows (default 1,2,4,8,32); --head whole: the "
+                         "batches of every row (default 1,32)")
     ap.add_argument("--inner", type=int, default=20, help="--attention split: launches (or block calls) per timed sample")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=7)
@@ -390,9 +468,11 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
-    if args.frames is not None or args.math is not None or args.attention is not None:
+    if args.batches is None:
+        args.batches = "1,32" if args.head is not None else "1,2,4,8,32"
+    if args.frames is not None or args.math is not None or args.attention is not None or args.head is not None:
         line = json.dumps(long_clips(args) if args.frames is not None else bf16_mode(args) if args.math is not None
-                          else split_attention(args))
+                          else split_attention(args) if args.attention is not None else whole_head(args))
         if args.out:
             with open(args.out, "w") as f:
                 f.write(line + "\n")
