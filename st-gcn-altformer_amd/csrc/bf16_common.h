@@ -1,5 +1,10 @@
-// Helpers shared by the bf16 matrix-core kernels (tcn_bf16.hip, stem_bf16_v4.hip).
+// Helpers shared by the kernels that feed the bf16 matrix cores: packing and hi/lo splitting, the swizzled LDS image, the tile
+// geometry, and the one MFMA k-step of the 32x32x16 kernels.  Users of that k-step: tcn_bf16.hip, stem_bf16_v4.hip and
+// vit_linear.hip; the rest is also read by kf6.h (KF6, KF7, K3v6, the weight gradient), tcn_backward.hip, agcn_attention.hip
+// and the heads' bf16 attention and weight-gradient kernels.
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -16,6 +21,15 @@ using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
 #else
 #define STGCN_ABL(bit) false
 #endif
+
+// compile-time loop: f(std::integral_constant<int, I>{}) for I = I0 .. N-1
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
+}
 
 constexpr int CCB = 16;   // input channels per LDS chunk = one 16-deep k-step per tap
 constexpr int PXB = 32;   // bytes per pixel row of one image
@@ -67,92 +81,42 @@ __device__ __forceinline__ TileGeomB tile_geom_b(int tile, int V, int K, int str
     return g;
 }
 
-template <int TERMS>
-struct Frag2 {  // operands of one k-step for 2 MFMA blocks: [block] hi (+ lo)
-    uint4 hi[2];
-    uint4 lo[TERMS == 3 ? 2 : 1];
-};
-
-// 12 (or 4) MFMAs of one k-step: 2 channel blocks x 2 pixel blocks
-template <int TERMS>
-__device__ __forceinline__ void mfma_kstep_bf16(f32x16 (&acc)[2][2], const Frag2<TERMS> &a, const Frag2<TERMS> &b) {
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, a.hi[m]);
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            const bf16x8 bh = __builtin_bit_cast(bf16x8, b.hi[n]);
-            if constexpr (TERMS == 3) {
-                const bf16x8 al = __builtin_bit_cast(bf16x8, a.lo[m]);
-                const bf16x8 bl = __builtin_bit_cast(bf16x8, b.lo[n]);
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m][n], 0, 0, 0);
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m][n], 0, 0, 0);
-            }
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m][n], 0, 0, 0);
-        }
-    }
-}
-
-
-// the 6 (or 2) MFMAs of channel block m of one k-step (one half of mfma_kstep_bf16)
-template <int TERMS>
-__device__ __forceinline__ void mfma_half_bf16(f32x16 (&acc)[2][2], const Frag2<TERMS> &a, const Frag2<TERMS> &b, int m) {
-    const bf16x8 ah = __builtin_bit_cast(bf16x8, a.hi[m]);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const bf16x8 bh = __builtin_bit_cast(bf16x8, b.hi[n]);
-        if constexpr (TERMS == 3) {
-            const bf16x8 al = __builtin_bit_cast(bf16x8, a.lo[m]);
-            const bf16x8 bl = __builtin_bit_cast(bf16x8, b.lo[n]);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m][n], 0, 0, 0);
-        }
-        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m][n], 0, 0, 0);
-    }
-}
-
-// B-side operands of one k-step for NJ pixel blocks, and the half-step on a 2 x NJ accumulator tile
-template <int TERMS, int NJ>
+// Operands of one k-step (16 deep) for N 32-wide MFMA blocks of one side of the product: [block] hi, and lo under bf16x3
+template <int TERMS, int N>
 struct FragB {
-    uint4 hi[NJ];
-    uint4 lo[TERMS == 3 ? NJ : 1];
+    uint4 hi[N];
+    uint4 lo[TERMS == 3 ? N : 1];
 };
+template <int TERMS>
+using Frag2 = FragB<TERMS, 2>;
 
-template <int TERMS, int NJ>
-__device__ __forceinline__ void mfma_half_bf16(f32x16 (&acc)[2][NJ], const Frag2<TERMS> &a, const FragB<TERMS, NJ> &b, int m) {
+// One k-step on one 32 x 32 block: block m of a times block n of b.  The product order (hi * lo, lo * hi, then hi * hi) is
+// what makes tiles of different sizes agree bit for bit: it is stated here and nowhere else.
+template <int TERMS, int WM, int WN>
+__device__ __forceinline__ void mfma_block_bf16(f32x16 &acc, const FragB<TERMS, WM> &a, int m, const FragB<TERMS, WN> &b, int n) {
     const bf16x8 ah = __builtin_bit_cast(bf16x8, a.hi[m]);
-#pragma unroll
-    for (int n = 0; n < NJ; ++n) {
-        const bf16x8 bh = __builtin_bit_cast(bf16x8, b.hi[n]);
-        if constexpr (TERMS == 3) {
-            const bf16x8 al = __builtin_bit_cast(bf16x8, a.lo[m]);
-            const bf16x8 bl = __builtin_bit_cast(bf16x8, b.lo[n]);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m][n], 0, 0, 0);
-        }
-        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m][n], 0, 0, 0);
+    const bf16x8 bh = __builtin_bit_cast(bf16x8, b.hi[n]);
+    if constexpr (TERMS == 3) {
+        const bf16x8 al = __builtin_bit_cast(bf16x8, a.lo[m]);
+        const bf16x8 bl = __builtin_bit_cast(bf16x8, b.lo[n]);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
     }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
 }
 
-// One k-step on a WM x WN accumulator tile: mfma_kstep_bf16 above with the block counts as parameters, and the same product
-// order per block (hi * lo, lo * hi, then hi * hi), which is what makes tiles of different sizes agree bit for bit.
+// the 3 (or 1) x WN MFMAs of channel block m of one k-step on a WM x WN accumulator tile
+template <int TERMS, int WM, int WN>
+__device__ __forceinline__ void mfma_half_bf16(f32x16 (&acc)[WM][WN], const FragB<TERMS, WM> &a, const FragB<TERMS, WN> &b, int m) {
+#pragma unroll
+    for (int n = 0; n < WN; ++n) mfma_block_bf16<TERMS>(acc[m][n], a, m, b, n);
+}
+
+// the whole k-step: every channel block in turn
 template <int TERMS, int WM, int WN>
 __device__ __forceinline__ void mfma_kstep_bf16(f32x16 (&acc)[WM][WN], const FragB<TERMS, WM> &a, const FragB<TERMS, WN> &b) {
 #pragma unroll
-    for (int m = 0; m < WM; ++m) {
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, a.hi[m]);
-#pragma unroll
-        for (int n = 0; n < WN; ++n) {
-            const bf16x8 bh = __builtin_bit_cast(bf16x8, b.hi[n]);
-            if constexpr (TERMS == 3) {
-                const bf16x8 al = __builtin_bit_cast(bf16x8, a.lo[m]);
-                const bf16x8 bl = __builtin_bit_cast(bf16x8, b.lo[n]);
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m][n], 0, 0, 0);
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m][n], 0, 0, 0);
-            }
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m][n], 0, 0, 0);
-        }
-    }
+    for (int m = 0; m < WM; ++m) mfma_half_bf16<TERMS>(acc, a, b, m);
 }
 
 }  // namespace bf16k

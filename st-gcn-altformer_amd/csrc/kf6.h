@@ -2,8 +2,8 @@
 // v_mfma_f32_16x16x32_bf16 with a slot-structured main loop and a weight ring filled by LDS-DMA.  KF6 (the headline fused
 // stem, below), KF7 (stem_f16mx.hip), K3v6 (tcn_bf16_v6.hip) and the temporal conv's weight gradient (tcn_wgrad_v6.hip)
 // are built in this form.  This header holds:
-//   * what they share: the tile constants, the LDS-DMA helper, the vmcnt waits, FragB6, static_for, TileInfo6, relu1 and
-//     the cycle-stamp macros of the diagnostic builds;
+//   * what they share: the tile constants, the LDS-DMA helper, the vmcnt waits, FragB6, TileInfo6, relu1 and
+//     the cycle-stamp macros of the diagnostic builds (static_for comes from bf16_common.h);
 //   * the KF6 kernel template and the host plans of the fused stem (narrow and wide frames; KF7 runs the narrow plan with
 //     three terms).  stem_bf16_v6.hip instantiates KF6's narrow form, stem_bf16_v6w.hip its wide form: one translation
 //     unit per form, so that neither perturbs the other's code generation.
@@ -43,15 +43,6 @@ template <int N>
 __device__ __forceinline__ void vm_wait_keep() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct FragB6 { uint4 hi[4], lo[4]; };     // activations of one pair: 4 pixel blocks of 16
-
-// compile-time loop: f(std::integral_constant<int, I>{}) for I = I0 .. N-1
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 struct TileInfo6 {
     int n, Vh, j0, half;

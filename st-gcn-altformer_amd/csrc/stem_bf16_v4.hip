@@ -410,14 +410,14 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
                     if (tt + 1 < STG) load_a(a_nxt, aslot, tt + 1);
                     if (tap + 1 < KT4) load_b(b_nxt, cur, tap + 1);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!STGCN_ABL(2)) mfma_half_bf16<TERMS, NJ>(acc, a_cur, b_cur, 0);
+                    if (!STGCN_ABL(2)) mfma_half_bf16<TERMS>(acc, a_cur, b_cur, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     if (prod) prod_mfma(pr);
                     // next weight stage -> other ring slot (its readers passed the last barrier); issued behind the
                     // first MFMAs so the DMA's issue cost does not delay the start of the stage
                     if (tt == 0) dma_stage(gs + 1);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!STGCN_ABL(2)) mfma_half_bf16<TERMS, NJ>(acc, a_cur, b_cur, 1);
+                    if (!STGCN_ABL(2)) mfma_half_bf16<TERMS>(acc, a_cur, b_cur, 1);
                     __builtin_amdgcn_sched_barrier(0);
                     if (prod) prod_finish(nxt, pr);
                     a_cur = a_nxt;

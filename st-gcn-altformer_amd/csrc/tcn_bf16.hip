@@ -64,6 +64,137 @@ __global__ void tcn_pack_bf16_kernel(const float *__restrict__ W, const float *_
 }
 
 // -----------------------------------------------------------------------------------------------
+// The consumer of both kernels below: what a wave needs to turn chunk images and weight fragments into its 64 channels x 64
+// pixels of the tile, whoever fills the images.
+// -----------------------------------------------------------------------------------------------
+template <int TERMS>
+struct Consumer {
+    int prow[2];  // tile-local pixel row of the wave's 2 column blocks at tap 0
+    f32x16 acc[2][2];
+    // weight fragments: [m].hi/.lo of flat k index kidx = ch*K + tap at wpm[m][(kidx*2 + img)*64]
+    const uint4 *wpm0, *wpm1;
+    int nk, V, h, img_bytes, abl;
+
+    __device__ __forceinline__ Consumer(const TileGeomB &g, const uint4 *Wp, int mb0, int wn, int lane, int nk_, int V_, int stride,
+                                        int img_bytes_, int abl_)
+        : nk(nk_), V(V_), h(lane >> 5), img_bytes(img_bytes_), abl(abl_) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            int q = g.q0 + (wn * 2 + j) * 32 + (lane & 31);
+            q = min(q, g.q_last);
+            const int t = q / V, v = q - t * V;
+            prow[j] = (t - g.t_first) * stride * V + v;
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
+        wpm0 = Wp + (size_t)(mb0 + 0) * nk * 2 * 64 + lane;
+        wpm1 = Wp + (size_t)(mb0 + 1) * nk * 2 * 64 + lane;
+    }
+    __device__ __forceinline__ void load_a(Frag2<TERMS> &a, int kidx) const {
+        const int kc = min(kidx, nk - 1);  // past the end: re-read the last fragment (discarded)
+        if (STGCN_ABL(16)) return;
+        a.hi[0] = wpm0[(size_t)kc * 128];
+        a.hi[1] = wpm1[(size_t)kc * 128];
+        if constexpr (TERMS == 3) {
+            a.lo[0] = wpm0[(size_t)kc * 128 + 64];
+            a.lo[1] = wpm1[(size_t)kc * 128 + 64];
+        }
+    }
+    __device__ __forceinline__ void load_b(Frag2<TERMS> &b, const char *buf, int tap) const {
+        if (STGCN_ABL(8)) return;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int off = lds_off(prow[j] + tap * V, h);
+            b.hi[j] = *reinterpret_cast<const uint4 *>(buf + off);
+            if constexpr (TERMS == 3) b.lo[j] = *reinterpret_cast<const uint4 *>(buf + img_bytes + off);
+        }
+    }
+};
+
+// The chunk loop: chunk ch is consumed from one image buffer while the other is filled with chunk ch + 1.  DEPTH weight
+// fragments are in flight (the one of tap kidx + DEPTH - 1 is fetched in front of the MFMAs of tap kidx), the activation
+// fragments run one tap ahead.  What fills the next chunk is the caller's:
+//   begin_chunk(ch)             at the head of a chunk, in front of its first fragment reads
+//   fill_tap(tap_c, ch, nxt)    KT = 9: the tap loop is fully unrolled — one basic block per chunk — and this slice of the
+//                               staging, which gets the tap as a compile-time value, sits right behind the tap's MFMAs
+//   fill_between(ch, nxt)       KT = 0: any K, runtime tap loop, the whole staging between two chunks
+template <int DEPTH, int KT, int TERMS, class Begin, class FillTap, class FillBetween>
+__device__ __forceinline__ void consume_chunks(Consumer<TERMS> &c, int nch, int K, char *buf0, char *buf1, Begin &&begin_chunk,
+                                               FillTap &&fill_tap, FillBetween &&fill_between) {
+    [[maybe_unused]] const int abl = c.abl;
+    Frag2<TERMS> a[DEPTH] = {};  // weight fragments of taps kidx .. kidx + DEPTH - 1
+#pragma unroll
+    for (int i = 0; i + 1 < DEPTH; ++i) c.load_a(a[i], i);
+    int kidx = 0;
+    for (int ch = 0; ch < nch; ++ch) {
+        const char *cur = (ch & 1) ? buf1 : buf0;
+        char *nxt = (ch & 1) ? buf0 : buf1;
+        begin_chunk(ch);
+        Frag2<TERMS> b0 = {}, b1 = {};
+        c.load_b(b0, cur, 0);
+        auto fetch_and_multiply = [&](int next_tap) {
+            c.load_a(a[DEPTH - 1], kidx + DEPTH - 1);
+            c.load_b(b1, cur, next_tap);
+            if (!STGCN_ABL(2)) mfma_kstep_bf16<TERMS>(c.acc, a[0], b0);
+        };
+        auto advance = [&] {
+#pragma unroll
+            for (int i = 0; i + 1 < DEPTH; ++i) a[i] = a[i + 1];
+            b0 = b1;
+            ++kidx;
+        };
+        if constexpr (KT == 9) {
+            static_for<0, 9>([&](auto tap_c) {
+                constexpr int tap = decltype(tap_c)::value;
+                fetch_and_multiply(tap + 1 < 9 ? tap + 1 : tap);
+                if (!STGCN_ABL(1)) fill_tap(tap_c, ch, nxt);
+                advance();
+            });
+        } else {
+            for (int k = 0; k < K; ++k) {
+                fetch_and_multiply(k + 1 < K ? k + 1 : k);
+                advance();
+            }
+            if (ch + 1 < nch) fill_between(ch, nxt);
+        }
+        __syncthreads();
+    }
+}
+
+// epilogue: D[row = channel][col = pixel], col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).  Result = max(acc + shift,
+// act_lo); ntvc: stored as (N,T,V,C) instead of (N,C,T,V); ppc = pixels per clip of the output.
+template <bool BF16OUT, int TERMS>
+__device__ __forceinline__ void store_tile(const Consumer<TERMS> &c, const TileGeomB &g, const float *__restrict__ shift, void *y,
+                                           int n, int Cout, int ppc, int mb0, int wn, int lane, float act_lo, bool ntvc) {
+    // This lane's first pixel and first channel, as two opaque registers: every index below is one of them plus a constant.
+    // (Left visible, hipcc re-derives the terms from the lane per row or carries them through the chunk loop, and one or
+    //  the other instantiation then needs four more VGPRs than the two epilogues written out per kernel did; compare
+    //  KF4's epilogue in stem_bf16_v4.hip.)
+    int q_first = g.q0 + wn * 64 + (lane & 31), o_first = mb0 * 32 + 4 * (lane >> 5);
+    asm volatile("" : "+v"(q_first), "+v"(o_first));
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        if ((mb0 + m) * 32 >= Cout) continue;             // padded rows of a 64-channel layer (whole blocks: wave-uniform)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int o = o_first + m * 32 + (r & 3) + 8 * (r >> 2);
+            const float sh = shift[o];
+            const size_t base = ((size_t)n * Cout + o) * ppc;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int q = q_first + j * 32;
+                const size_t idx = ntvc ? ((size_t)n * ppc + q) * Cout + o : base + q;  // (N,T,V,C) | (N,C,T,V)
+                if (q <= g.q_last) store_out<BF16OUT>(y, idx, fmaxf(c.acc[m][j][r] + sh, act_lo));
+            }
+        }
+    }
+}
+
+// -----------------------------------------------------------------------------------------------
 // Stand-alone temporal conv block (Unit2D) on the bf16 matrix cores: x is the (N,Cin,T,V) fp32 input.
 // Each thread owns JPR tile pixels; it loads 8 channels of them (coalesced along pixels), splits them into bf16
 // hi/lo and stores one 16-byte group per image.  KT = 9: tap loop fully unrolled with that staging interleaved
@@ -126,23 +257,7 @@ __global__ __launch_bounds__(NT) void tcn_mfma_bf16_kernel(
         }
     };
 
-    // ---- consumer state ------------------------------------------------------------------
-    int prow[2];  // tile-local pixel row of the wave's 2 column blocks at tap 0
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        int q = g.q0 + (wn * 2 + j) * 32 + (lane & 31);
-        q = min(q, g.q_last);
-        const int t = q / V, v = q - t * V;
-        prow[j] = (t - g.t_first) * stride * V + v;
-    }
-    const int h = lane >> 5;
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
+    Consumer<TERMS> c(g, Wp, mb0, wn, lane, nch * K, V, stride, img_bytes, abl);
 
     load_unit(0, 0);
     store_unit(buf0, 0);
@@ -150,110 +265,30 @@ __global__ __launch_bounds__(NT) void tcn_mfma_bf16_kernel(
     store_unit(buf0, 1);
     __syncthreads();  // chunk 0 visible
 
-    // weight fragments: [m].hi/.lo of flat k index kidx = ch*K + tap at wpm[m][(kidx*2 + img)*64]
-    const int nk = nch * K;
-    const uint4 *wpm0 = Wp + (size_t)(mb0 + 0) * nk * 2 * 64 + lane;
-    const uint4 *wpm1 = Wp + (size_t)(mb0 + 1) * nk * 2 * 64 + lane;
-    auto load_a = [&](Frag2<TERMS> &a, int kidx) {
-        const int kc = min(kidx, nk - 1);  // past the end: re-read the last fragment (discarded)
-        if (STGCN_ABL(16)) return;
-        a.hi[0] = wpm0[(size_t)kc * 128];
-        a.hi[1] = wpm1[(size_t)kc * 128];
-        if constexpr (TERMS == 3) {
-            a.lo[0] = wpm0[(size_t)kc * 128 + 64];
-            a.lo[1] = wpm1[(size_t)kc * 128 + 64];
-        }
-    };
-    auto load_b = [&](Frag2<TERMS> &b, const char *buf, int tap) {
-        if (STGCN_ABL(8)) return;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int off = lds_off(prow[j] + tap * V, h);
-            b.hi[j] = *reinterpret_cast<const uint4 *>(buf + off);
-            if constexpr (TERMS == 3) b.lo[j] = *reinterpret_cast<const uint4 *>(buf + img_bytes + off);
-        }
-    };
-
-    Frag2<TERMS> a0 = {}, a1 = {}, a2 = {};  // taps kidx, kidx+1, kidx+2
-    load_a(a0, 0);
-    load_a(a1, 1);
-    int kidx = 0;
-    for (int ch = 0; ch < nch; ++ch) {
-        const char *cur = (ch & 1) ? buf1 : buf0;
-        char *nxt = (ch & 1) ? buf0 : buf1;
-        Frag2<TERMS> b0 = {}, b1 = {};
-        load_b(b0, cur, 0);
-        if constexpr (KT == 9) {
-            // ---- fully unrolled: one basic block per chunk, staging slices between the MFMAs ----
-#define STGCN_TAP(TAP)                                                                                   \
-    do {                                                                                                 \
-        load_a(a2, kidx + 2);                                                                            \
-        load_b(b1, cur, (TAP) + 1 < 9 ? (TAP) + 1 : (TAP));                                              \
-        if (!STGCN_ABL(2)) mfma_kstep_bf16<TERMS>(acc, a0, b0);                                          \
-        if (!STGCN_ABL(1)) {                                                                             \
-            if ((TAP) == 0) load_unit(ch + 1, 0);                                                        \
-            if ((TAP) == 3) {                                                                            \
-                store_unit(nxt, 0);                                                                      \
-                load_unit(ch + 1, 1);                                                                    \
-            }                                                                                            \
-            if ((TAP) == 7) store_unit(nxt, 1);                                                          \
-        }                                                                                                \
-        a0 = a1;                                                                                         \
-        a1 = a2;                                                                                         \
-        b0 = b1;                                                                                         \
-        ++kidx;                                                                                          \
-    } while (0)
-            STGCN_TAP(0);
-            STGCN_TAP(1);
-            STGCN_TAP(2);
-            STGCN_TAP(3);
-            STGCN_TAP(4);
-            STGCN_TAP(5);
-            STGCN_TAP(6);
-            STGCN_TAP(7);
-            STGCN_TAP(8);
-#undef STGCN_TAP
-        } else {
-            for (int k = 0; k < K; ++k, ++kidx) {
-                load_a(a2, kidx + 2);
-                load_b(b1, cur, k + 1 < K ? k + 1 : k);
-                if (!STGCN_ABL(2)) mfma_kstep_bf16<TERMS>(acc, a0, b0);
-                a0 = a1;
-                a1 = a2;
-                b0 = b1;
-            }
-            if (ch + 1 < nch) {
-                load_unit(ch + 1, 0);
+    consume_chunks<3, KT>(
+        c, nch, K, buf0, buf1, [](int) {},
+        [&](auto tap_c, int ch, char *nxt) {
+            constexpr int tap = decltype(tap_c)::value;
+            if constexpr (tap == 0) load_unit(ch + 1, 0);
+            if constexpr (tap == 3) {
                 store_unit(nxt, 0);
                 load_unit(ch + 1, 1);
-                store_unit(nxt, 1);
             }
-        }
-        __syncthreads();
-    }
+            if constexpr (tap == 7) store_unit(nxt, 1);
+        },
+        [&](int ch, char *nxt) {
+            load_unit(ch + 1, 0);
+            store_unit(nxt, 0);
+            load_unit(ch + 1, 1);
+            store_unit(nxt, 1);
+        });
 
-    // epilogue: D[row = channel][col = pixel], col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
     if (STGCN_ABL(4)) return;
-    const int ppc = Tout * V;
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = (mb0 + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (o >= Cout) continue;                      // padded rows of a 64-channel layer
-            const float sh = shift[o];
-            const size_t base = ((size_t)n * Cout + o) * ppc;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int q = g.q0 + (wn * 2 + j) * 32 + (lane & 31);
-                if (q <= g.q_last) store_out<BF16OUT>(y, base + q, fmaxf(acc[m][j][r] + sh, act_lo));
-            }
-        }
-    }
+    store_tile<BF16OUT>(c, g, shift, y, n, Cout, Tout * V, mb0, wn, lane, act_lo, false);
 }
 
 // -----------------------------------------------------------------------------------------------
-// Fused stem on the bf16 matrix cores.  Same consumer as above; the producer is itself an MFMA:
+// Fused stem on the bf16 matrix cores.  The same consumer; the producer is itself an MFMA:
 //   Fs   : LDS tile [tile pixel][16] fp32 = the 12 graph-conv features of the pixel, a validity flag
 //          (1 inside the clip, else the whole row is 0 -> the conv sees its zero padding), 3 zeros.
 //   y    = relu(W12[16 ch x 16] . Fs^T[16 x 16 px])  by 4 x v_mfma_f32_16x16x4_f32 (exact fp32) per
@@ -367,122 +402,29 @@ __global__ __launch_bounds__(NT) void stem_mfma_bf16_kernel(
         }
     };
 
-    // ---- consumer state ------------------------------------------------------------------
-    int prow[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        int q = g.q0 + (wn * 2 + j) * 32 + (lane & 31);
-        q = min(q, g.q_last);
-        const int t = q / V, v = q - t * V;
-        prow[j] = (t - g.t_first) * V + v;
-    }
-    const int h = lane >> 5;
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
+    Consumer<TERMS> c(g, Wp, mb0, wn, lane, nch * K, V, 1, img_bytes, abl);
 
     float4 wcur = load_w12(0);
     for (int b = wave; b < nblk; b += 4) produce_block(buf0, wcur, b);
     float4 wnext = load_w12(1);
     __syncthreads();  // chunk 0 visible
 
-    const int nk = nch * K;
-    const uint4 *wpm0 = Wp + (size_t)(mb0 + 0) * nk * 2 * 64 + lane;
-    const uint4 *wpm1 = Wp + (size_t)(mb0 + 1) * nk * 2 * 64 + lane;
-    auto load_a = [&](Frag2<TERMS> &a, int kidx) {
-        const int kc = min(kidx, nk - 1);
-        if (STGCN_ABL(16)) return;
-        a.hi[0] = wpm0[(size_t)kc * 128];
-        a.hi[1] = wpm1[(size_t)kc * 128];
-        if constexpr (TERMS == 3) {
-            a.lo[0] = wpm0[(size_t)kc * 128 + 64];
-            a.lo[1] = wpm1[(size_t)kc * 128 + 64];
-        }
-    };
-    auto load_b = [&](Frag2<TERMS> &b, const char *buf, int tap) {
-        if (STGCN_ABL(8)) return;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int off = lds_off(prow[j] + tap * V, h);
-            b.hi[j] = *reinterpret_cast<const uint4 *>(buf + off);
-            if constexpr (TERMS == 3) b.lo[j] = *reinterpret_cast<const uint4 *>(buf + img_bytes + off);
-        }
-    };
-
-    Frag2<TERMS> a0 = {}, a1 = {}, a2 = {}, a3 = {}, a4 = {};  // weight fragments of taps kidx .. kidx+4
-    load_a(a0, 0);
-    load_a(a1, 1);
-    load_a(a2, 2);
-    load_a(a3, 3);
-    int kidx = 0;
-    for (int ch = 0; ch < nch; ++ch) {
-        const char *cur = (ch & 1) ? buf1 : buf0;
-        char *nxt = (ch & 1) ? buf0 : buf1;
-        wcur = wnext;                 // W12 rows of chunk ch+1
-        wnext = load_w12(ch + 2);
-        Frag2<TERMS> b0 = {}, b1 = {};
-        load_b(b0, cur, 0);
-        if constexpr (KT == 9) {
-#define STGCN_TAP(TAP)                                                                                  \
-    do {                                                                                                \
-        load_a(a4, kidx + 4);                                                                           \
-        load_b(b1, cur, (TAP) + 1 < 9 ? (TAP) + 1 : (TAP));                                             \
-        if (!STGCN_ABL(2)) mfma_kstep_bf16<TERMS>(acc, a0, b0);                                         \
-        if ((TAP) < PB && !STGCN_ABL(1)) produce_block(nxt, wcur, min(wave + 4 * (TAP), nblk - 1));     \
-        a0 = a1;                                                                                        \
-        a1 = a2;                                                                                        \
-        a2 = a3;                                                                                        \
-        a3 = a4;                                                                                        \
-        b0 = b1;                                                                                        \
-        ++kidx;                                                                                         \
-    } while (0)
-            STGCN_TAP(0);
-            STGCN_TAP(1);
-            STGCN_TAP(2);
-            STGCN_TAP(3);
-            STGCN_TAP(4);
-            STGCN_TAP(5);
-            STGCN_TAP(6);
-            STGCN_TAP(7);
-            STGCN_TAP(8);
-#undef STGCN_TAP
-        } else {
-            for (int k = 0; k < K; ++k, ++kidx) {
-                load_a(a4, kidx + 4);
-                load_b(b1, cur, k + 1 < K ? k + 1 : k);
-                if (!STGCN_ABL(2)) mfma_kstep_bf16<TERMS>(acc, a0, b0);
-                a0 = a1;
-                a1 = a2;
-                a2 = a3;
-                a3 = a4;
-                b0 = b1;
-            }
-            if (ch + 1 < nch)
-                for (int b = wave; b < nblk; b += 4) produce_block(nxt, wcur, b);
-        }
-        __syncthreads();
-    }
+    consume_chunks<5, KT>(
+        c, nch, K, buf0, buf1,
+        [&](int ch) {
+            wcur = wnext;                 // W12 rows of chunk ch+1
+            wnext = load_w12(ch + 2);
+        },
+        [&](auto tap_c, int, char *nxt) {
+            constexpr int tap = decltype(tap_c)::value;
+            if constexpr (tap < PB) produce_block(nxt, wcur, min(wave + 4 * tap, nblk - 1));
+        },
+        [&](int, char *nxt) {
+            for (int b = wave; b < nblk; b += 4) produce_block(nxt, wcur, b);
+        });
 
     if (STGCN_ABL(4)) return;
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = (mb0 + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const float sh = shift[o];
-            const size_t base = ((size_t)n * C + o) * TV;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int q = g.q0 + (wn * 2 + j) * 32 + (lane & 31);
-                const size_t idx = (abl & OPT_OUT_NTVC) ? ((size_t)n * TV + q) * C + o : base + q;  // (N,T,V,C) | (N,C,T,V)
-                if (q <= g.q_last) store_out<BF16OUT>(y, idx, fmaxf(acc[m][j][r] + sh, 0.f));
-            }
-        }
-    }
+    store_tile<BF16OUT>(c, g, shift, y, n, C, TV, mb0, wn, lane, 0.f, (abl & OPT_OUT_NTVC) != 0);
 }
 
 struct Bf16StemTile {
