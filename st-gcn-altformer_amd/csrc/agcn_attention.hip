@@ -49,10 +49,15 @@ __device__ __forceinline__ void softmax_columns(float *Sm, const float *__restri
         }
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 16));
+        // A score that is not finite makes its whole column NaN (score * 0 is NaN for Inf and NaN, 0 otherwise).  The folded
+        // form needs this: where the embeddings of an Inf input cancel to NaN (inf - inf over the channels), x~^T M x~ gives a
+        // clean -inf, exp(-inf) = 0 would drop it, and the clip's Inf would be gone from its column of P.
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            val[i] = (sub + 16 * i < V) ? expf(val[i] - m) : 0.f;
+            const bool in = sub + 16 * i < V;
+            sum += in ? val[i] * 0.f : 0.f;
+            val[i] = in ? expf(val[i] - m) : 0.f;
             sum += val[i];
         }
 #pragma unroll

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(NTB) void agcn_bwd_gather_kernel(
                     const int r = wave * 4 + rr;
                     f32x4 g;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) g[j] = (ry[rr][j] > 0.f && 4 * lane + j < px) ? rd[rr][j] : 0.f;
+                    for (int j = 0; j < 4; ++j) g[j] = (!(ry[rr][j] <= 0.f) && 4 * lane + j < px) ? rd[rr][j] : 0.f;   // (a NaN y passes dy on)
                     *reinterpret_cast<f32x4 *>(Gt + (buf * 32 + r) * FP + 4 * lane) = g;
                     const float *wq = wda + (ob * 32 + r) * 12;      // wave-uniform: scalar loads, SGPR operands
 #pragma unroll

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void agcn_expand_small_kernel(
             float acc = wr[F];
 #pragma unroll
             for (int f = 0; f < F; ++f) acc = fmaf(wr[f], feat[f], acc);
-            yo[(size_t)o * T * V] = (mode & 1) ? acc : fmaxf(acc, 0.f);  // mode bit 0: raw (pre-activation) output
+            yo[(size_t)o * T * V] = (mode & 1) ? acc : max_nan(acc, 0.f);  // mode bit 0: raw (pre-activation) output
         }
     }
 }
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void agcn_expand_small4_kernel(
                 for (int f = 0; f < F; ++f) a[q] = fmaf(wv[f], feat[q][f], a[q]);
             }
             *reinterpret_cast<float4 *>(yo + (size_t)o * T * V) =
-                make_float4(fmaxf(a[0], lo), fmaxf(a[1], lo), fmaxf(a[2], lo), fmaxf(a[3], lo));
+                make_float4(max_nan(a[0], lo), max_nan(a[1], lo), max_nan(a[2], lo), max_nan(a[3], lo));
         }
     }
 }
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void agcn_expand_generic_kernel(
                     float val = fmaf(bn_scale[o], acc[j] + b, bn_shift[o]);
                     if (identity) { if (!(mode & 2)) val += Xs[o * PXM + p]; }  // mode bit 1: leave the residual out
                     else val += fmaf(down_scale[o], res[j] + bdown[o], down_shift[o]);
-                    yo[(size_t)o * T * V] = (mode & 1) ? val : fmaxf(val, 0.f);
+                    yo[(size_t)o * T * V] = (mode & 1) ? val : max_nan(val, 0.f);
                 }
             }
         }
@@ -516,7 +516,7 @@ __global__ __launch_bounds__(512, (NOW == 1 ? 4 : 2)) void agcn_expand_mfma_kern
                                 const float2 xv = *reinterpret_cast<const float2 *>(xn + off);
                                 v.x += xv.x; v.y += xv.y;
                             }
-                            *reinterpret_cast<float2 *>(yn + off) = make_float2(fmaxf(v.x, lo), fmaxf(v.y, lo));
+                            *reinterpret_cast<float2 *>(yn + off) = make_float2(max_nan(v.x, lo), max_nan(v.y, lo));
                         }
                     }
                 }
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(512, (NOW == 1 ? 4 : 2)) void agcn_expand_mfma_kern
                     if (p < px) {
                         float val = acc[a][b][i] + cst;
                         if (identity && !(mode & 2)) val += xn[(size_t)o * plane + p];   // mode bit 1: leave the residual out
-                        yn[(size_t)o * plane + p] = (mode & 1) ? val : fmaxf(val, 0.f);
+                        yn[(size_t)o * plane + p] = (mode & 1) ? val : max_nan(val, 0.f);
                     }
                 }
             }

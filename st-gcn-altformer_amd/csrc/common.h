@@ -70,6 +70,12 @@ static inline unsigned long long *debug_buffer() {
 #endif
 }
 
+// max(x, lo) that keeps a NaN (torch.relu's rule): one v_maximum3_f32 on gfx950.  fmaxf and v_max_f32 return the operand that
+// is not a NaN, so a ReLU written with them stores a NaN pre-activation as 0 (as -inf in the raw mode, lo = -inf).  Every
+// ReLU, raw-mode clamp and max-pool of the library goes through here; lo = -inf returns x unchanged.  On finite inputs the
+// result differs from fmaxf's in nothing but the sign of a zero (max_nan(-0, +0) = +0).
+__device__ __forceinline__ float max_nan(float x, float lo) { return __builtin_elementwise_maximum(x, lo); }
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 

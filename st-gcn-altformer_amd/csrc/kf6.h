@@ -49,12 +49,8 @@ struct TileInfo6 {
     TileGeomB g;
 };
 
-// max(x, 0) as ONE v_max_f32 (fmaxf canonicalises its operand first: a second v_max per element in the producer's slots)
-__device__ __forceinline__ float relu1(float x) {
-    float r;
-    asm("v_max_f32_e32 %0, 0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
+// max(x, 0) as ONE instruction in the producer's slots, and one that keeps a NaN (common.h: max_nan): v_maximum3_f32 x, 0, 0
+__device__ __forceinline__ float relu1(float x) { return max_nan(x, 0.f); }
 
 #ifdef STGCN_ABLATION  // in-kernel cycle stamps of KF6 and KF7 (diagnostic builds only; dbg == NULL otherwise)
 #define V6_STAMP(var) unsigned long long var = 0; if (dbg) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); }
@@ -671,8 +667,8 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
 #pragma unroll
                     for (int nb = 0; nb < 4; ++nb) {
                         const int px = nb * 16 + (lane & 15);
-                        const float4 v = make_float4(fmaxf(acc[mb][nb][0] + sh4.x, 0.f), fmaxf(acc[mb][nb][1] + sh4.y, 0.f),
-                                                     fmaxf(acc[mb][nb][2] + sh4.z, 0.f), fmaxf(acc[mb][nb][3] + sh4.w, 0.f));
+                        const float4 v = make_float4(max_nan(acc[mb][nb][0] + sh4.x, 0.f), max_nan(acc[mb][nb][1] + sh4.y, 0.f),
+                                                     max_nan(acc[mb][nb][2] + sh4.z, 0.f), max_nan(acc[mb][nb][3] + sh4.w, 0.f));
                         *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
                     }
                     const size_t tbase = (size_t)n * TV * C + ob;            // scalar
@@ -705,7 +701,7 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
                     for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(acc[mb][nb][r] + shv[r], 0.f);
+                            stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = max_nan(acc[mb][nb][r] + shv[r], 0.f);
                     const size_t tbase = ((size_t)n * C + ob) * TV;           // scalar
 #pragma unroll
                     for (int it = 0; it < 8; ++it) {
@@ -736,8 +732,8 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
 #pragma unroll
                         for (int nb = 0; nb < 4; ++nb) {
                             const int px = nb * 16 + (lane & 15);
-                            const float4 v = make_float4(fmaxf(acc[mb][nb][0] + sh4.x, 0.f), fmaxf(acc[mb][nb][1] + sh4.y, 0.f),
-                                                         fmaxf(acc[mb][nb][2] + sh4.z, 0.f), fmaxf(acc[mb][nb][3] + sh4.w, 0.f));
+                            const float4 v = make_float4(max_nan(acc[mb][nb][0] + sh4.x, 0.f), max_nan(acc[mb][nb][1] + sh4.y, 0.f),
+                                                         max_nan(acc[mb][nb][2] + sh4.z, 0.f), max_nan(acc[mb][nb][3] + sh4.w, 0.f));
                             *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
                         }
                         const size_t tbase = ((size_t)n * TV + qw) * C + ob;      // scalar
@@ -769,7 +765,7 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
                         for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
                             for (int r = 0; r < 4; ++r)
-                                stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(acc[mb][nb][r] + shv[r], 0.f);
+                                stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = max_nan(acc[mb][nb][r] + shv[r], 0.f);
                         const size_t tbase = ((size_t)n * C + ob) * TV + qw;      // scalar
                         const bool al16 = ((tbase & 3) == 0) && (TV % 4 == 0);    // 16-byte (8-byte for bf16) aligned rows
 #pragma unroll
@@ -818,8 +814,8 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
 #pragma unroll
                             for (int nb = 0; nb < 4; ++nb) {
                                 const int px = nb * 16 + (lane & 15);
-                                const float4 v = make_float4(fmaxf(acc[mb][nb][0] + shv[0], 0.f), fmaxf(acc[mb][nb][1] + shv[1], 0.f),
-                                                             fmaxf(acc[mb][nb][2] + shv[2], 0.f), fmaxf(acc[mb][nb][3] + shv[3], 0.f));
+                                const float4 v = make_float4(max_nan(acc[mb][nb][0] + shv[0], 0.f), max_nan(acc[mb][nb][1] + shv[1], 0.f),
+                                                             max_nan(acc[mb][nb][2] + shv[2], 0.f), max_nan(acc[mb][nb][3] + shv[3], 0.f));
                                 *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
                             }
                             const size_t tbase = ((size_t)n * TV + qw) * C + ob;      // scalar
@@ -857,7 +853,7 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
                             for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
                                 for (int r = 0; r < 4; ++r)
-                                    stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(acc[mb][nb][r] + shv[r], 0.f);
+                                    stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = max_nan(acc[mb][nb][r] + shv[r], 0.f);
                             const size_t tbase = tb0 + (size_t)(mb * 16) * TV;        // scalar
 #pragma unroll
                             for (int it = 0; it < 4; ++it) {

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
         pr.d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, pr.wl), f, pr.d, 0, 0, 0);
     };
     auto prod_finish = [&](char *buf, const Prod &pr) {
-        const float v0 = fmaxf(pr.d[0], 0.f), v1 = fmaxf(pr.d[1], 0.f), v2 = fmaxf(pr.d[2], 0.f), v3 = fmaxf(pr.d[3], 0.f);
+        const float v0 = max_nan(pr.d[0], 0.f), v1 = max_nan(pr.d[1], 0.f), v2 = max_nan(pr.d[2], 0.f), v3 = max_nan(pr.d[3], 0.f);
         const unsigned h0 = pack_bf16x2(v0, v1), h1 = pack_bf16x2(v2, v3);
         const int off = lds_off(pr.p, pg >> 1) + (pg & 1) * 8;
         *reinterpret_cast<uint2 *>(buf + off) = make_uint2(h0, h1);
@@ -464,8 +464,8 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
                         const int px = j * 32 + (lane_e & 31);
-                        const float4 v = make_float4(fmaxf(acc[m][j][4 * gq + 0] + sh4.x, 0.f), fmaxf(acc[m][j][4 * gq + 1] + sh4.y, 0.f),
-                                                     fmaxf(acc[m][j][4 * gq + 2] + sh4.z, 0.f), fmaxf(acc[m][j][4 * gq + 3] + sh4.w, 0.f));
+                        const float4 v = make_float4(max_nan(acc[m][j][4 * gq + 0] + sh4.x, 0.f), max_nan(acc[m][j][4 * gq + 1] + sh4.y, 0.f),
+                                                     max_nan(acc[m][j][4 * gq + 2] + sh4.z, 0.f), max_nan(acc[m][j][4 * gq + 3] + sh4.w, 0.f));
                         *reinterpret_cast<float4 *>(stg + px * 32 + (((2 * gq + hh) ^ (px & 7)) << 2)) = v;
                     }
                 }
@@ -497,7 +497,7 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
                     const int cr = (r & 3) + 8 * (r >> 2) + 4 * (lane_e >> 5);
                     const float sh = shift[ob + cr];
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) stg[cr * PW + j * 32 + (lane_e & 31)] = fmaxf(acc[m][j][r] + sh, 0.f);
+                    for (int j = 0; j < NJ; ++j) stg[cr * PW + j * 32 + (lane_e & 31)] = max_nan(acc[m][j][r] + sh, 0.f);
                 }
 #pragma unroll
                 for (int it = 0; it < 4 * NJ; ++it) {
@@ -717,8 +717,8 @@ __global__ __launch_bounds__(NT4) void tcn_bf16_v4_kernel(
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
                             const int px = j * 32 + (lane_e & 31);
-                            const float4 v = make_float4(fmaxf(acc[m][j][4 * gq + 0] + sh4.x, act_lo), fmaxf(acc[m][j][4 * gq + 1] + sh4.y, act_lo),
-                                                         fmaxf(acc[m][j][4 * gq + 2] + sh4.z, act_lo), fmaxf(acc[m][j][4 * gq + 3] + sh4.w, act_lo));
+                            const float4 v = make_float4(max_nan(acc[m][j][4 * gq + 0] + sh4.x, act_lo), max_nan(acc[m][j][4 * gq + 1] + sh4.y, act_lo),
+                                                         max_nan(acc[m][j][4 * gq + 2] + sh4.z, act_lo), max_nan(acc[m][j][4 * gq + 3] + sh4.w, act_lo));
                             *reinterpret_cast<float4 *>(stg + px * 32 + (((2 * gq + hh) ^ (px & 7)) << 2)) = v;
                         }
                     }
@@ -747,7 +747,7 @@ __global__ __launch_bounds__(NT4) void tcn_bf16_v4_kernel(
                         const int cr = (r & 3) + 8 * (r >> 2) + 4 * (lane_e >> 5);
                         const float sh = shift[ob + cr];
 #pragma unroll
-                        for (int j = 0; j < 2; ++j) stg[cr * 64 + j * 32 + (lane_e & 31)] = fmaxf(acc[m][j][r] + sh, act_lo);
+                        for (int j = 0; j < 2; ++j) stg[cr * 64 + j * 32 + (lane_e & 31)] = max_nan(acc[m][j][r] + sh, act_lo);
                     }
 #pragma unroll
                     for (int it = 0; it < 8; ++it) {

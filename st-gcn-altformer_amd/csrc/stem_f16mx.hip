@@ -522,8 +522,8 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb) {
                     const int px = nb * 16 + (lane & 15);
-                    const float4 v = make_float4(fmaxf(fmaf(acc[mb][nb][0], osc, sh4.x), 0.f), fmaxf(fmaf(acc[mb][nb][1], osc, sh4.y), 0.f),
-                                                 fmaxf(fmaf(acc[mb][nb][2], osc, sh4.z), 0.f), fmaxf(fmaf(acc[mb][nb][3], osc, sh4.w), 0.f));
+                    const float4 v = make_float4(max_nan(fmaf(acc[mb][nb][0], osc, sh4.x), 0.f), max_nan(fmaf(acc[mb][nb][1], osc, sh4.y), 0.f),
+                                                 max_nan(fmaf(acc[mb][nb][2], osc, sh4.z), 0.f), max_nan(fmaf(acc[mb][nb][3], osc, sh4.w), 0.f));
                     *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
                 }
                 const size_t tbase = ((size_t)n * TV + qw) * C + ob;      // scalar
@@ -555,7 +555,7 @@ __global__ __launch_bounds__(NT6) void stem_f16mx_kernel(
                 for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(fmaf(acc[mb][nb][r], osc, shv[r]), 0.f);
+                        stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = max_nan(fmaf(acc[mb][nb][r], osc, shv[r]), 0.f);
                 const size_t tbase = ((size_t)n * C + ob) * TV + qw;      // scalar
                 const bool al16 = ((tbase & 3) == 0) && (TV % 4 == 0);    // 16-byte (8-byte for bf16) aligned rows
 #pragma unroll

@@ -57,7 +57,7 @@ struct ChanCoef {
     __device__ __forceinline__ float masked(float za, float zb, float dy) const {   // the forward's own expression
         float v = fmaf(za, sa, ta);
         if (mode) v += fmaf(zb, sb, tb);
-        return v > 0.f ? dy : 0.f;
+        return v <= 0.f ? 0.f : dy;               // (a NaN pre-activation passes dy on, as torch's threshold_backward does)
     }
 };
 

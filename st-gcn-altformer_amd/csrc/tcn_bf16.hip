@@ -188,7 +188,7 @@ __device__ __forceinline__ void store_tile(const Consumer<TERMS> &c, const TileG
             for (int j = 0; j < 2; ++j) {
                 const int q = q_first + j * 32;
                 const size_t idx = ntvc ? ((size_t)n * ppc + q) * Cout + o : base + q;  // (N,T,V,C) | (N,C,T,V)
-                if (q <= g.q_last) store_out<BF16OUT>(y, idx, fmaxf(c.acc[m][j][r] + sh, act_lo));
+                if (q <= g.q_last) store_out<BF16OUT>(y, idx, max_nan(c.acc[m][j][r] + sh, act_lo));
             }
         }
     }
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(NT) void stem_mfma_bf16_kernel(
         d = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.z, fb.z, d, 0, 0, 0);
         d = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.w, fb.w, d, 0, 0, 0);
         // lane holds channels 4*pg .. 4*pg+3 of pixel p
-        const float v0 = fmaxf(d[0], 0.f), v1 = fmaxf(d[1], 0.f), v2 = fmaxf(d[2], 0.f), v3 = fmaxf(d[3], 0.f);
+        const float v0 = max_nan(d[0], 0.f), v1 = max_nan(d[1], 0.f), v2 = max_nan(d[2], 0.f), v3 = max_nan(d[3], 0.f);
         const unsigned h0 = pack_bf16x2(v0, v1), h1 = pack_bf16x2(v2, v3);
         const int off = lds_off(p, pg >> 1) + (pg & 1) * 8;
         *reinterpret_cast<uint2 *>(buf + off) = make_uint2(h0, h1);

@@ -299,8 +299,8 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb) {
                     const int px = nb * 16 + (lane & 15);
-                    const float4 v = make_float4(fmaxf(acc[mb][nb][0] + sh4.x, act_lo), fmaxf(acc[mb][nb][1] + sh4.y, act_lo),
-                                                 fmaxf(acc[mb][nb][2] + sh4.z, act_lo), fmaxf(acc[mb][nb][3] + sh4.w, act_lo));
+                    const float4 v = make_float4(max_nan(acc[mb][nb][0] + sh4.x, act_lo), max_nan(acc[mb][nb][1] + sh4.y, act_lo),
+                                                 max_nan(acc[mb][nb][2] + sh4.z, act_lo), max_nan(acc[mb][nb][3] + sh4.w, act_lo));
                     *reinterpret_cast<float4 *>(stg + px * 16 + (((lane >> 4) ^ (px & 3)) << 2)) = v;
                 }
                 const size_t tbase = ((size_t)n * TV + qw) * C + ob;      // scalar
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(NT6) void tcn_bf16_v6_kernel(const float *__restric
                 for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = fmaxf(acc[mb][nb][r] + shv[r], act_lo);
+                        stg[(4 * (lane >> 4) + r) * 64 + nb * 16 + (lane & 15)] = max_nan(acc[mb][nb][r] + shv[r], act_lo);
                 const size_t tbase = ((size_t)n * C + ob) * TV + qw;      // scalar
                 const bool al16 = ((tbase & 3) == 0) && (TV % 4 == 0);    // 16-byte (8-byte for bf16) aligned rows
                 [[maybe_unused]] float k1 = 0.f, k2 = 0.f;

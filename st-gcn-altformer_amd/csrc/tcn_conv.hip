@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void tcn_valu_kernel(const float *__restrict__
 #pragma unroll
     for (int j = 0; j < OBV; ++j)
         if (o0 + j < Cout)
-            store_out<BF16OUT>(y, ((size_t)n * Cout + o0 + j) * Tout * V + q, fmaxf(acc[j] + shift[o0 + j], lo));
+            store_out<BF16OUT>(y, ((size_t)n * Cout + o0 + j) * Tout * V + q, max_nan(acc[j] + shift[o0 + j], lo));
 }
 
 // The same along the JOINT axis (Unit2D(dim=3), model/net.py:28-36: Conv2d kernel (1,K), padding (0,pad), stride (1,stride)):
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void tcn_valu_joint_axis_kernel(const float *_
 #pragma unroll
     for (int j = 0; j < OBV; ++j)
         if (o0 + j < Cout)
-            store_out<BF16OUT>(y, ((size_t)n * Cout + o0 + j) * T * Vout + q, fmaxf(acc[j] + shift[o0 + j], lo));
+            store_out<BF16OUT>(y, ((size_t)n * Cout + o0 + j) * T * Vout + q, max_nan(acc[j] + shift[o0 + j], lo));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -243,7 +243,7 @@ __device__ __forceinline__ void epilogue_store(const f32x16 (&acc)[4], const Til
         for (int j = 0; j < 4; ++j) {
             const int q = g.q0 + j * 32 + (lane & 31);
             const size_t idx = ntvc ? ((size_t)n * pixels_per_clip + q) * Cout + o : base + q;
-            if (q <= g.q_last) store_out<BF16OUT>(y, idx, fmaxf(acc[j][r] + sh, lo));
+            if (q <= g.q_last) store_out<BF16OUT>(y, idx, max_nan(acc[j][r] + sh, lo));
         }
     }
 }
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void stem_mfma_f32_kernel(
             float a = w3.x;
 #pragma unroll
             for (int f = 0; f < F; ++f) a = fmaf(wv[f], feat[jj][f], a);
-            a = jok[jj] ? fmaxf(a, 0.f) : 0.f;  // outside the clip the temporal conv sees zero padding
+            a = jok[jj] ? max_nan(a, 0.f) : 0.f;  // outside the clip the temporal conv sees zero padding
             if (jwr[jj]) buf[c * ROW + jcol[jj]] = a;
         }
     };

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *__restrict__
     auto one = [&](float a, float b) {
         float v = fmaf(a, s_a, t_a);
         if (mode) v += fmaf(b, s_b, t_b);          // (mode 1: 1*b + 0, the same bits as v + b)
-        return fmaxf(v, 0.f);
+        return max_nan(v, 0.f);
     };
     for (int n = it.n_lo; n < it.n_hi; ++n) {
         const size_t base = ((size_t)n * C + c) * plane;

@@ -11,7 +11,7 @@ namespace {
 
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return float4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
 __device__ __forceinline__ float4 max4(float4 a, float4 b) {
-    return float4{fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)};
+    return float4{max_nan(a.x, b.x), max_nan(a.y, b.y), max_nan(a.z, b.z), max_nan(a.w, b.w)};
 }
 
 // The pooled float4 column `c4` of one sequence (`xs` = its first token, D4 = D / 4 columns per token) as token lane `ty` of
