@@ -651,6 +651,43 @@ int stgcn_altformer_head_forward(const float *z, const stgcn_altformer_head_weig
                                  float scale2, void *ws, size_t ws_bytes, float *logits, unsigned flags1, unsigned flags2,
                                  unsigned head_flags, void *stream);
 
+/* ---- The ST-ViT head: patch embedding with class token, class-token pooling (additive to ABI 11: one flag bit, one entry
+ * point, three queries; inference only) ----
+ * model/ST_Vit/trans.py (ViT) after the stem, eval forward: patch embedding -> class row -> + position table -> depth blocks
+ * (stgcn_vit_block_forward: the same pre-norm block, qkv without bias, LayerNorm eps 1e-5) -> class token or mean over the
+ * tokens -> LayerNorm -> Linear (stgcn_vit_pool_classify).
+ *
+ * stgcn_vit_patch_embed: z is the stem output, (N, C, T, V), or with STGCN_IN_NTVC (N, T, V, C) as the stem writes it with
+ * STGCN_OUT_NTVC, read in place.  T % p1 == 0 and V % p2 == 0; h = T / p1, w = V / p2, n = h w patches per clip.  Patch (a, b)
+ * of clip i is the vector of length K = p1 p2 C with element k = (f p2 + j) C + c equal to z[i][c][a p1 + f][b p2 + j] (f
+ * slowest, then j, then c).  x is (N, n + 1, E):
+ *     x[i][0]           = cls + pos[0]
+ *     x[i][1 + a w + b] = patch(a, b) . W^T + bias + pos[1 + a w + b]
+ * W (E, K) as nn.Linear stores it, bias (E) or NULL, cls (E), pos (n + 1, E) or NULL (with both NULL the patch rows are the
+ * plain product).
+ * In the (N, T, V, C) layout a patch is p1 runs of p2 C contiguous floats and the kernel stages its A operand straight from
+ * them: no rearranged (N, n, K) copy exists.  (N, C, T, V) input is first written as (N, T, V, C) into the workspace by one
+ * transposing pass (N C T V floats more).  Covered: (p2 C) % 32 == 0 (a K chunk of 32 never crosses a run), STGCN_MATH_F32 or
+ * STGCN_MATH_BF16X3, a clip and the output below 2^31 elements.
+ * The contraction is cut over workgroups (few rows, long K); each part's sums go to a slab of the workspace and one kernel adds
+ * the slabs in a fixed order with the bias and the position row and writes the class rows.  No atomics: bit-identical from run
+ * to run.  The cut is a host function of (N n, K, E): stgcn_vit_patch_embed_cut returns (tile rows << 16) | parts, 0 if the
+ * call is not covered; stgcn_vit_patch_embed_ws_bytes reads the same plan (0 if not covered).
+ * Order of the answers: flags (STGCN_ERR_ARG for any bit outside the math bits and STGCN_IN_NTVC), then pointers and
+ * dimensions (STGCN_ERR_ARG; z, W and ws 16-byte aligned), then coverage (STGCN_ERR_UNSUPPORTED), then the workspace
+ * (STGCN_ERR_WORKSPACE); nothing is launched before all four passed.  2 launches (3 for (N, C, T, V) input) on `stream`, the
+ * caller's buffers, no allocation, no synchronisation.
+ *
+ * STGCN_VIT_POOL_CLS on stgcn_vit_pool / stgcn_vit_pool_classify: the "pool" is token 0 of every sequence, bit for bit.
+ * Together with STGCN_VIT_POOL_MAX: STGCN_ERR_ARG.  Without the bit both behave as before.  (The ViT's pool = 'mean' is the
+ * plain mean: it includes the class token.) */
+#define STGCN_VIT_POOL_CLS (0x8000000u)
+int stgcn_vit_patch_embed_supported(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags);
+size_t stgcn_vit_patch_embed_ws_bytes(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags);
+int stgcn_vit_patch_embed_cut(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags);
+int stgcn_vit_patch_embed(const float *z, const float *W, const float *bias, const float *cls, const float *pos, float *x, int N,
+                          int C, int T, int V, int p1, int p2, int E, void *ws, size_t ws_bytes, unsigned flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -322,14 +322,88 @@ int launch_attention_backward_stream(const float *qkv, const float *out, const f
 // a workgroup per (sequence, chunk of D), 16-byte loads along D, the token lanes of a workgroup joined through LDS in
 // ascending order.  The maximum starts from a token of the sequence, never from zero.
 inline bool pool_ok(long long S, int L, int D) { return S >= 1 && S < (1ll << 31) && L >= 1 && D >= 4 && D % 4 == 0; }
-int launch_pool(const float *x, float *out, long long S, int L, int D, bool max, hipStream_t st);
+// `first` (STGCN_VIT_POOL_CLS): the "pool" is token 0 of every sequence - the selection over a sequence of one token, L apart.
+int launch_pool(const float *x, float *out, long long S, int L, int D, bool max, hipStream_t st, bool first = false);
 // logits (N, classes) = LayerNorm_D(pool_L(x (N, L, D))) W^T + bias, one workgroup per clip: the pooled row and its LayerNorm
 // in LDS, a wave per class.  D % 64 == 0, D <= kMaxLnDim (the blocks' rule), any L and classes.  bias may be NULL.
 inline bool pool_classify_ok(int N, int L, int D, int classes) {
     return N >= 1 && L >= 1 && classes >= 1 && D >= 64 && D % 64 == 0 && D <= kMaxLnDim;
 }
 int launch_pool_classify(const float *x, const float *gamma, const float *beta, float eps, const float *W, const float *bias,
-                         float *logits, int N, int L, int D, int classes, bool max, hipStream_t st);
+                         float *logits, int N, int L, int D, int classes, bool max, hipStream_t st, bool first = false);
+
+// ---- the ST-ViT head's patch embedding (vit_patch.hip) --------------------------------------------------------------------
+// x (N, n + 1, E) from the stem output z cut into p1 x p2 patches: row 0 of a clip is cls + pos[0], row 1 + a w + b is
+// patch (a, b) W^T + bias + pos[1 + a w + b] (include/stgcn_hip.h, "The ST-ViT head").  The product is vit_linear_kernel on
+// PatchRows: M = N n rows, K = p1 p2 C, read in place from z as (N, T, V, C).  M is small (99 rows per clip) and K long (5120),
+// so the contraction is cut into `splits` slabs of `cps` chunks of 32 over grid.y; the slabs' sums land in the workspace and
+// one kernel adds them in slab order, with the bias and the position row, and writes the class rows.  No atomics.
+// The plan, decided here and nowhere else (stgcn_vit_patch_embed, .._supported, .._ws_bytes and .._cut read it):
+//   tile  : the largest form whose tiles, each cut into as many slabs as kPatchMinChunks allows, still make kLinearTileCut
+//           workgroups (a large tile reads each operand element less often, the cut supplies the workgroups), else 32 x 64;
+//   splits: as many as bring tiles x splits to kLinearTileCut, while a slab keeps kPatchMinChunks chunks.
+// MEASURED against three other rules at 1 to 64 clips of the reference shape (profiles/stvit_patch_cut_ab.txt: the tile by
+// STGCN_VIT_TILE_AUTO's rule first and the cut second, and both rules aiming at 512 workgroups with slabs of 4 chunks): in
+// bf16x3 this one is the fastest or within 5 % of it at every count but 4 clips (0.049 against 0.044 ms) and 8 clips (0.063
+// against 0.057 ms), and 1.2 - 1.8 x faster than the tile-first rule from 2 to 64 clips.
+constexpr int kPatchMinChunks = 8;
+struct PatchPlan {
+    const char *refusal = nullptr;   // a flag bit this entry point does not know (STGCN_ERR_ARG)
+    bool shaped = false;             // positive dimensions, T % p1 == 0, V % p2 == 0 (else STGCN_ERR_ARG)
+    bool covered = false;            // (p2 C) % 32 == 0, f32 / bf16x3, sizes within the index types (else STGCN_ERR_UNSUPPORTED)
+    bool transpose = false;          // z is (N, C, T, V): one pass writes it as (N, T, V, C) into the workspace first
+    unsigned math = 0;
+    int n = 0, w = 0, K = 0, M = 0;
+    LinearTile tile{0, 0};
+    int splits = 0, cps = 0;
+};
+
+inline PatchPlan plan_patch(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags) {
+    PatchPlan p;
+    if (flags & ~(unsigned)(STGCN_MATH_MASK | STGCN_IN_NTVC)) p.refusal = "only the math bits and STGCN_IN_NTVC are read";
+    p.shaped = N >= 1 && C >= 1 && T >= 1 && V >= 1 && p1 >= 1 && p2 >= 1 && E >= 1 && T % p1 == 0 && V % p2 == 0;
+    if (!p.shaped) return p;
+    p.transpose = (flags & STGCN_IN_NTVC) == 0;
+    p.math = flags & STGCN_MATH_MASK;
+    p.w = V / p2;
+    p.n = (T / p1) * p.w;
+    const long long K = (long long)p1 * p2 * C, M = (long long)N * p.n, clip = (long long)T * V * C, lim = 1ll << 31;
+    if (!math_ok(flags) || ((long long)p2 * C) % 32 != 0 || clip >= lim || (M + N) * E >= lim) return p;
+    p.K = (int)K;
+    p.M = (int)M;
+    const int chunks = p.K / 32;
+    const long long most = chunks / kPatchMinChunks > 0 ? chunks / kPatchMinChunks : 1;
+    p.tile = kLinearTiles[2];
+    for (const LinearTile t : kLinearTiles)
+        if (linear_tiles(p.M, E, t) * most >= kLinearTileCut) {
+            p.tile = t;
+            break;
+        }
+    const long long tiles = linear_tiles(p.M, E, p.tile);
+    long long want = (kLinearTileCut + tiles - 1) / tiles;
+    if (want > most) want = most;
+    if (want < 1) want = 1;
+    p.cps = ceil_div(chunks, (int)want);
+    p.splits = ceil_div(chunks, p.cps);
+    p.covered = true;
+    return p;
+}
+
+// The workspace of a patch embedding, one carve: the transposed copy of z where it arrives as (N, C, T, V), and the slabs.
+// Nothing of the size of the rearranged patches (N n K floats) exists for (N, T, V, C) input.
+struct PatchStore {
+    float *zt, *part;
+    size_t total;
+    PatchStore(void *base, const PatchPlan &p, int N, int C, int T, int V, int E) {
+        Carve c(base);
+        zt = p.transpose ? c.take<float>((size_t)N * C * T * V) : nullptr;
+        part = c.take<float>((size_t)p.splits * p.M * E);
+        total = c.off;
+    }
+};
+int launch_patch_embed_vit(const PatchPlan &p, const PatchStore &store, const float *z, const float *W, const float *bias,
+                           const float *cls, const float *pos, float *x, int N, int C, int T, int V, int p1, int p2, int E,
+                           hipStream_t st);
 
 // The plan of a whole-head call, decided here and nowhere else: stgcn_altformer_head_supported, .._ws_bytes and .._forward read
 // it and none of them looks at a flag bit or compares a length again.  The two stages' blocks are plan_block's, unrestated.

@@ -32,14 +32,15 @@ __device__ __forceinline__ float4 pool_lane(const float4 *__restrict__ xs, int L
 // out (S, D) from x (S, L, D).  Workgroup (256 threads) = (sequence, chunk of CX float4 columns): CX lanes along D (16 bytes
 // each, CX * 16 contiguous bytes per token), 256 / CX token lanes, joined through LDS in ascending lane order.  CX = 64 reads
 // whole 1 KB rows; CX = 16 cuts D four times finer for calls of few sequences (launch_pool picks).
+// L: the tokens pooled, the first L of every sequence; Ls: the tokens a sequence has (L, or L = 1 for the class token).
 template <int CX, bool MAX>
-__global__ __launch_bounds__(256) void vit_pool_kernel(const float *__restrict__ x, float *__restrict__ out, int L, int D4,
+__global__ __launch_bounds__(256) void vit_pool_kernel(const float *__restrict__ x, float *__restrict__ out, int L, int Ls, int D4,
                                                        int chunks) {
     constexpr int TY = 256 / CX;
     __shared__ float4 part[TY][CX];
     const int s = blockIdx.x / chunks, c4 = (blockIdx.x % chunks) * CX + (threadIdx.x % CX), ty = threadIdx.x / CX;
     const bool live = c4 < D4;                       // the last chunk of a D that is no multiple of 4 CX
-    const float4 *xs = reinterpret_cast<const float4 *>(x) + (size_t)s * L * D4;
+    const float4 *xs = reinterpret_cast<const float4 *>(x) + (size_t)s * Ls * D4;
     if (live) part[ty][threadIdx.x % CX] = pool_lane<MAX>(xs, L, D4, c4, ty, TY);
     __syncthreads();
     if (ty == 0 && live) {
@@ -78,13 +79,14 @@ template <bool MAX>
 __global__ __launch_bounds__(kClsThreads) void vit_pool_classify_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
                                                                          const float *__restrict__ beta, float eps,
                                                                          const float *__restrict__ W, const float *__restrict__ bias,
-                                                                         float *__restrict__ logits, int L, int D, int classes) {
+                                                                         float *__restrict__ logits, int L, int Ls, int D,
+                                                                         int classes) {
     __shared__ float4 part[kClsThreads];
     __shared__ float4 row4[kMaxLnDim / 4];
     __shared__ float red[kClsWaves];
     float *row = reinterpret_cast<float *>(row4);
     const int n = blockIdx.x, tid = threadIdx.x, D4 = D / 4;
-    const float4 *xs = reinterpret_cast<const float4 *>(x) + (size_t)n * L * D4;
+    const float4 *xs = reinterpret_cast<const float4 *>(x) + (size_t)n * Ls * D4;   // L, Ls: as in vit_pool_kernel
     const int CX = D4 < kClsThreads ? D4 : kClsThreads, TY = kClsThreads / CX;   // D % 64 == 0: CX is a multiple of 16
     const int cx = tid % CX, ty = tid / CX;
     for (int c0 = 0; c0 < D4; c0 += CX) {            // one pass unless D = 4096 (CX = 1024 = D4 then: no tail)
@@ -129,10 +131,13 @@ __global__ __launch_bounds__(kClsThreads) void vit_pool_classify_kernel(const fl
 }
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+inline bool pool_flags_clash(unsigned flags) { return (flags & STGCN_VIT_POOL_MAX) && (flags & STGCN_VIT_POOL_CLS); }
 
 }  // namespace
 
-int launch_pool(const float *x, float *out, long long S, int L, int D, bool max, hipStream_t st) {
+int launch_pool(const float *x, float *out, long long S, int L, int D, bool max, hipStream_t st, bool first) {
+    const int Ls = L;
+    if (first) L = 1, max = true;   // the selection over one token: that token, bit for bit
     // Whole 1 KB rows per workgroup where that still gives every CU some workgroups; a quarter of that per workgroup below
     // (one clip of TS: 22 sequences of 180 tokens at D = 256 are 22 workgroups of the wide form and 88 of the narrow one).
     const int D4 = D / 4;
@@ -141,24 +146,26 @@ int launch_pool(const float *x, float *out, long long S, int L, int D, bool max,
     if (S * chunks >= (1ll << 31)) return fail(STGCN_ERR_UNSUPPORTED, "vit pool: %lld sequences of %d columns exceed the grid", S, D);
     const dim3 grid((unsigned)(S * chunks));
     if (wide) {
-        if (max) hipLaunchKernelGGL((vit_pool_kernel<64, true>), grid, dim3(256), 0, st, x, out, L, D4, chunks);
-        else hipLaunchKernelGGL((vit_pool_kernel<64, false>), grid, dim3(256), 0, st, x, out, L, D4, chunks);
+        if (max) hipLaunchKernelGGL((vit_pool_kernel<64, true>), grid, dim3(256), 0, st, x, out, L, Ls, D4, chunks);
+        else hipLaunchKernelGGL((vit_pool_kernel<64, false>), grid, dim3(256), 0, st, x, out, L, Ls, D4, chunks);
     } else {
-        if (max) hipLaunchKernelGGL((vit_pool_kernel<16, true>), grid, dim3(256), 0, st, x, out, L, D4, chunks);
-        else hipLaunchKernelGGL((vit_pool_kernel<16, false>), grid, dim3(256), 0, st, x, out, L, D4, chunks);
+        if (max) hipLaunchKernelGGL((vit_pool_kernel<16, true>), grid, dim3(256), 0, st, x, out, L, Ls, D4, chunks);
+        else hipLaunchKernelGGL((vit_pool_kernel<16, false>), grid, dim3(256), 0, st, x, out, L, Ls, D4, chunks);
     }
     STGCN_LAUNCH_CHECK("vit_pool_kernel");
     return STGCN_OK;
 }
 
 int launch_pool_classify(const float *x, const float *gamma, const float *beta, float eps, const float *W, const float *bias,
-                         float *logits, int N, int L, int D, int classes, bool max, hipStream_t st) {
+                         float *logits, int N, int L, int D, int classes, bool max, hipStream_t st, bool first) {
+    const int Ls = L;
+    if (first) L = 1, max = true;
     if (max)
         hipLaunchKernelGGL((vit_pool_classify_kernel<true>), dim3(N), dim3(kClsThreads), 0, st, x, gamma, beta, eps, W, bias,
-                           logits, L, D, classes);
+                           logits, L, Ls, D, classes);
     else
         hipLaunchKernelGGL((vit_pool_classify_kernel<false>), dim3(N), dim3(kClsThreads), 0, st, x, gamma, beta, eps, W, bias,
-                           logits, L, D, classes);
+                           logits, L, Ls, D, classes);
     STGCN_LAUNCH_CHECK("vit_pool_classify_kernel");
     return STGCN_OK;
 }
@@ -205,26 +212,31 @@ extern "C" {
 int stgcn_vit_pool_supported(int S, int L, int D) { return pool_ok(S, L, D) ? 1 : 0; }
 
 int stgcn_vit_pool(const float *x, float *out, int S, int L, int D, unsigned flags, void *stream) {
-    if (flags & ~(unsigned)STGCN_VIT_POOL_MAX) return fail(STGCN_ERR_ARG, "stgcn_vit_pool: unknown flag bits 0x%x", flags);
+    if (flags & ~(unsigned)(STGCN_VIT_POOL_MAX | STGCN_VIT_POOL_CLS)) return fail(STGCN_ERR_ARG, "stgcn_vit_pool: unknown flag bits 0x%x", flags);
+    if (pool_flags_clash(flags)) return fail(STGCN_ERR_ARG, "stgcn_vit_pool: STGCN_VIT_POOL_MAX and STGCN_VIT_POOL_CLS exclude each other");
     REQUIRE_PTR(x); REQUIRE_PTR(out);
     REQUIRE_POS(S); REQUIRE_POS(L); REQUIRE_POS(D);
     if (!aligned16(x) || !aligned16(out)) return fail(STGCN_ERR_ARG, "stgcn_vit_pool: x and out must be 16-byte aligned");
     if (!pool_ok(S, L, D)) return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_pool: D = %d (covered: D %% 4 == 0)", D);
-    return launch_pool(x, out, S, L, D, (flags & STGCN_VIT_POOL_MAX) != 0, static_cast<hipStream_t>(stream));
+    return launch_pool(x, out, S, L, D, (flags & STGCN_VIT_POOL_MAX) != 0, static_cast<hipStream_t>(stream),
+                       (flags & STGCN_VIT_POOL_CLS) != 0);
 }
 
 int stgcn_vit_pool_classify_supported(int N, int L, int D, int classes) { return pool_classify_ok(N, L, D, classes) ? 1 : 0; }
 
 int stgcn_vit_pool_classify(const float *x, const float *ln_weight, const float *ln_bias, float ln_eps, const float *W,
                             const float *bias, float *logits, int N, int L, int D, int classes, unsigned flags, void *stream) {
-    if (flags & ~(unsigned)STGCN_VIT_POOL_MAX) return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify: unknown flag bits 0x%x", flags);
+    if (flags & ~(unsigned)(STGCN_VIT_POOL_MAX | STGCN_VIT_POOL_CLS))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify: unknown flag bits 0x%x", flags);
+    if (pool_flags_clash(flags))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify: STGCN_VIT_POOL_MAX and STGCN_VIT_POOL_CLS exclude each other");
     REQUIRE_PTR(x); REQUIRE_PTR(ln_weight); REQUIRE_PTR(ln_bias); REQUIRE_PTR(W); REQUIRE_PTR(logits);
     REQUIRE_POS(N); REQUIRE_POS(L); REQUIRE_POS(D); REQUIRE_POS(classes);
     if (!aligned16(x) || !aligned16(W)) return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify: x and W must be 16-byte aligned");
     if (!pool_classify_ok(N, L, D, classes))
         return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_pool_classify: D = %d (covered: D %% 64 == 0, D <= %d)", D, kMaxLnDim);
     return launch_pool_classify(x, ln_weight, ln_bias, ln_eps, W, bias, logits, N, L, D, classes, (flags & STGCN_VIT_POOL_MAX) != 0,
-                                static_cast<hipStream_t>(stream));
+                                static_cast<hipStream_t>(stream), (flags & STGCN_VIT_POOL_CLS) != 0);
 }
 
 int stgcn_altformer_head_supported(const stgcn_altformer_head_shape *shape, unsigned flags1, unsigned flags2, unsigned head_flags) {

@@ -44,6 +44,7 @@ VIT_TRAIN_BF16 = 0x200000  # the three training entry points: every linear produ
 VIT_TRAIN_ATTN_BF16 = 0x800000  # the block's two training entry points: the resident attention forward / backward on bf16 operands
 VIT_ATTN_SPLIT = 0x2000000  # stgcn_vit_block_forward: the fp32 resident attention split over key tiles where the launch has few pairs
 VIT_POOL_MAX = 0x4000000  # stgcn_vit_pool / stgcn_vit_pool_classify: the maximum over the tokens instead of the mean
+VIT_POOL_CLS = 0x8000000  # stgcn_vit_pool / stgcn_vit_pool_classify: token 0 of every sequence (the ViT's class token)
 MATH_F16MX = MATH_BF16X3 | STEM_F16MX  # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
 
 STATUS = {0: "STGCN_OK", -1: "STGCN_ERR_ARG", -2: "STGCN_ERR_UNSUPPORTED",
@@ -158,6 +159,10 @@ PROTOTYPES = {
     "stgcn_altformer_head_ws_bytes": (c_size_t, [_SHAPE_P, c_uint, c_uint, c_uint]),
     "stgcn_altformer_head_forward": (c_int, [_P, ctypes.POINTER(AltformerHeadWeights), _SHAPE_P] + [c_float] * 4
                                      + [_P, c_size_t, _P] + [c_uint] * 3 + [_P]),
+    "stgcn_vit_patch_embed_supported": (c_int, [c_int] * 7 + [c_uint]),
+    "stgcn_vit_patch_embed_ws_bytes": (c_size_t, [c_int] * 7 + [c_uint]),
+    "stgcn_vit_patch_embed_cut": (c_int, [c_int] * 7 + [c_uint]),
+    "stgcn_vit_patch_embed": (c_int, [_P] * 6 + [c_int] * 7 + [_P, c_size_t, c_uint, _P]),
     "stgcn_vit_block_forward_train": (c_int, [_P] * 15 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
     "stgcn_vit_block_backward": (c_int, [_P] * 12 + [c_size_t] + [_P] * 14 + [c_float, c_float, _P, c_size_t] + [c_int] * 5
                                  + [c_uint, _P]),

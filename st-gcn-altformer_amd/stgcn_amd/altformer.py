@@ -130,16 +130,16 @@ def set_low_latency(module: nn.Module, enabled: bool = True, min_tokens=None, sp
     tile form picked per call size, same result bit for bit) and the inference threshold ``min_tokens``
     (``LOW_LATENCY_MIN_TOKENS`` when None).  ``split_attention`` (opt-in) sets ``Block.split_attention``: the fp32 attention
     of a call with few (sequence, head) pairs runs split over key tiles (``VIT_ATTN_SPLIT``; the same result up to the
-    summation order).  ``enabled=False`` restores ``small_tiles = False``, ``split_attention = False`` and ``HIP_MIN_TOKENS``.
-    The training threshold is not touched."""
+    summation order).  ``enabled=False`` restores ``small_tiles = False``, ``split_attention = False`` and ``HIP_MIN_TOKENS``
+    (for the ST-ViT head's modules: their own defaults, ``HipSwitches.DEFAULT_*``).  The training threshold is not touched."""
     for sub in module.modules():
-        if isinstance(sub, Block):
-            sub.small_tiles = bool(enabled)
+        if isinstance(sub, HipSwitches):
+            sub.small_tiles = bool(enabled) or sub.DEFAULT_SMALL_TILES
             sub.split_attention = bool(enabled) and bool(split_attention)
             if not enabled:
-                sub.hip_min_tokens = HIP_MIN_TOKENS
+                sub.hip_min_tokens = sub.DEFAULT_HIP_MIN_TOKENS
             else:
-                sub.hip_min_tokens = LOW_LATENCY_MIN_TOKENS if min_tokens is None else int(min_tokens)
+                sub.hip_min_tokens = min(LOW_LATENCY_MIN_TOKENS, sub.DEFAULT_HIP_MIN_TOKENS) if min_tokens is None else int(min_tokens)
 
 
 def set_whole_head(module: nn.Module, enabled: bool = True) -> None:
@@ -172,7 +172,7 @@ def set_hip_min_tokens(module: nn.Module, tokens: int) -> None:
     """The token count (B * L) from which every ``Block`` below uses the HIP path where it applies (0: always).  One knob for
     "always HIP": it sets the training threshold (``set_hip_train_min_tokens``) to the same value."""
     for sub in module.modules():
-        if isinstance(sub, Block):
+        if isinstance(sub, HipSwitches):
             sub.hip_min_tokens = int(tokens)
             sub.hip_train_min_tokens = int(tokens)
 
@@ -189,7 +189,7 @@ def set_head_math(module: nn.Module, mode) -> None:
     operands: inference and L <= 256 only, anything else of such a block runs its path's default), or None for the default."""
     m = None if mode is None else HEAD_MATH[mode] if isinstance(mode, str) else int(mode)
     for sub in module.modules():
-        if isinstance(sub, Block):
+        if isinstance(sub, HipSwitches):
             sub.math_mode = m
 
 
@@ -222,6 +222,39 @@ def set_train_math(module: nn.Module, mode) -> None:
     for sub in module.modules():
         if isinstance(sub, Block):
             sub.train_math_mode = m
+
+
+class HipSwitches:
+    """What a module that runs ``stgcn_vit_block_forward`` carries for ``set_head_math``, ``set_low_latency`` and
+    ``set_hip_min_tokens``, and the one place that turns it into the inference flag word: ``Block`` here, and the layers and
+    the front of the ST-ViT head (``stgcn_amd.vit``)."""
+
+    DEFAULT_HIP_MIN_TOKENS = HIP_MIN_TOKENS
+    DEFAULT_SMALL_TILES = False
+
+    def _init_switches(self):
+        self.math_mode = None                  # None: _default_head_math() at call time
+        self.train_math_mode = None            # set_train_math: the training branch's arithmetic; None: as math_mode decides
+        self.train_attention_mode = None       # set_train_attention_math: 'f32' | 'bf16'; None: env STGCN_VIT_TRAIN_ATTENTION, else 'f32'
+        self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
+        self.hip_min_tokens = self.DEFAULT_HIP_MIN_TOKENS   # set_hip_min_tokens
+        self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
+        self.hip_train_max_len = HIP_TRAIN_MAX_LEN         # set_long_training
+        self.small_tiles = self.DEFAULT_SMALL_TILES   # set_low_latency: the inference linears pick their tile form by call size
+        self.split_attention = False           # set_low_latency(split_attention=True): VIT_ATTN_SPLIT on the inference word
+
+    def _inference_flags(self, L: int, D: int, heads: int, hidden: int) -> int:
+        """The flag word of an inference call of a block of this shape: ``math_mode``, else ``_default_head_math()``;
+        ``'bf16'`` only where its resident form covers the length (longer sequences run the default arithmetic, still on HIP);
+        ``small_tiles`` adds ``VIT_TILE_AUTO`` unless ``math_mode`` forces a form; ``split_attention`` adds ``VIT_ATTN_SPLIT``."""
+        math = _default_head_math() if self.math_mode is None else self.math_mode
+        if math & VIT_BF16 and not F.vit_block_forward_bf16_supported(L, D, heads, hidden):
+            math = HEAD_MATH[DEFAULT_HEAD_MATH] | (math & VIT_TILE_MASK)
+        if self.small_tiles and not math & VIT_TILE_MASK:
+            math |= VIT_TILE_AUTO
+        if self.split_attention:
+            math |= VIT_ATTN_SPLIT
+        return math
 
 
 class DropPath(nn.Module):
@@ -313,7 +346,7 @@ class _BlockTrain(torch.autograd.Function):
         return (g["x"], None, None, None, None, None, None) + tuple(g[n] for n in F.VIT_BLOCK_PARAMS)
 
 
-class Block(nn.Module):
+class Block(nn.Module, HipSwitches):
     """``x + attn(norm1(x))`` then ``x + mlp(norm2(x))`` (each branch through ``drop_path``); x is (B, L, dim)."""
 
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
@@ -325,15 +358,7 @@ class Block(nn.Module):
         self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
-        self.math_mode = None                  # None: _default_head_math() at call time
-        self.train_math_mode = None            # set_train_math: the training branch's arithmetic; None: as math_mode decides
-        self.train_attention_mode = None       # set_train_attention_math: 'f32' | 'bf16'; None: env STGCN_VIT_TRAIN_ATTENTION, else 'f32'
-        self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
-        self.hip_min_tokens = HIP_MIN_TOKENS   # set_hip_min_tokens
-        self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
-        self.hip_train_max_len = HIP_TRAIN_MAX_LEN         # set_long_training
-        self.small_tiles = False               # set_low_latency: the inference linears pick their tile form by call size
-        self.split_attention = False           # set_low_latency(split_attention=True): VIT_ATTN_SPLIT on the inference word
+        self._init_switches()
 
     def _weights(self):
         """The parameters by attribute (an nn.DataParallel replica has no ``parameters()``)."""
@@ -400,9 +425,7 @@ class Block(nn.Module):
         inference modes that never reach a training entry point (a block set to the latter trains in its path's default);
         ``train_attention_mode`` (``set_train_attention_math``), else env ``STGCN_VIT_TRAIN_ATTENTION``, adds
         ``VIT_TRAIN_ATTN_BF16`` on top of any of them when it says ``'bf16'``, and nothing otherwise.
-        Inference: ``math_mode``, else ``_default_head_math()``; ``'bf16'`` only where its resident form covers the length
-        (longer sequences run the default arithmetic, still on HIP); ``small_tiles`` adds ``VIT_TILE_AUTO`` unless
-        ``math_mode`` forces a form; ``split_attention`` adds ``VIT_ATTN_SPLIT`` (the training word never carries it)."""
+        Inference: ``HipSwitches._inference_flags`` (the training word never carries a tile form or ``VIT_ATTN_SPLIT``)."""
         if train:
             attn = self.train_attention_mode if self.train_attention_mode is not None else _default_train_attention()
             bit = VIT_TRAIN_ATTN_BF16 if attn == "bf16" else 0
@@ -411,15 +434,7 @@ class Block(nn.Module):
             if self.math_mode is None or self.math_mode & VIT_BF16:
                 return _default_train_math() | bit
             return self.math_mode & ~(VIT_TILE_MASK | VIT_ATTN_SPLIT) | bit
-        math = _default_head_math() if self.math_mode is None else self.math_mode
-        if math & VIT_BF16 and not F.vit_block_forward_bf16_supported(x.shape[1], x.shape[2], self.attn.num_heads,
-                                                                      self.mlp.fc1.out_features):
-            math = HEAD_MATH[DEFAULT_HEAD_MATH] | (math & VIT_TILE_MASK)
-        if self.small_tiles and not math & VIT_TILE_MASK:
-            math |= VIT_TILE_AUTO
-        if self.split_attention:
-            math |= VIT_ATTN_SPLIT
-        return math
+        return self._inference_flags(x.shape[1], x.shape[2], self.attn.num_heads, self.mlp.fc1.out_features)
 
     def forward(self, x):
         if self.uses_hip(x):

@@ -747,17 +747,25 @@ def vit_pool_supported(S, L, D) -> bool:
     return bool(_capi.lib().stgcn_vit_pool_supported(S, L, D))
 
 
+_POOL_FLAGS = {"mean": 0, "max": _capi.VIT_POOL_MAX, "cls": _capi.VIT_POOL_CLS}
+
+
+def _pool_flags(mode) -> int:
+    if mode not in _POOL_FLAGS:
+        raise ValueError(f"mode must be 'mean', 'max' or 'cls' (got {mode!r})")
+    return _POOL_FLAGS[mode]
+
+
 def vit_pool(x, mode="mean") -> torch.Tensor:
-    """The mean (``sum / L``) or the maximum over the tokens of every sequence of x (S, L, D) -> (S, D); ``mode``: 'mean' |
-    'max'.  The maximum equals ``x.max(dim=1).values`` bit for bit on finite input."""
-    if mode not in ("mean", "max"):
-        raise ValueError(f"mode must be 'mean' or 'max' (got {mode!r})")
+    """The mean (``sum / L``), the maximum over the tokens, or token 0 of every sequence of x (S, L, D) -> (S, D); ``mode``:
+    'mean' | 'max' | 'cls'.  The maximum equals ``x.max(dim=1).values`` and 'cls' equals ``x[:, 0]`` bit for bit."""
+    fl = _pool_flags(mode)
     dev = x.device
     S, L, D = x.shape
     out = torch.empty((S, D), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
         _capi.call("stgcn_vit_pool", _dev_ptr(x, "x", dev), _dev_ptr(out, "out"), c_int(S), c_int(L), c_int(D),
-                   c_uint(_capi.VIT_POOL_MAX if mode == "max" else 0), _stream(dev))
+                   c_uint(fl), _stream(dev))
     return out
 
 
@@ -768,8 +776,7 @@ def vit_pool_classify_supported(N, L, D, classes) -> bool:
 def vit_pool_classify(x, ln_weight, ln_bias, eps, weight, bias=None, mode="max", logits=None) -> torch.Tensor:
     """``Linear(LayerNorm(pool(x)))`` on x (N, L, D) -> (N, classes): the pooling of ``vit_pool`` over L, an affine LayerNorm
     over D (biased variance, ``eps`` inside the root), ``weight`` (classes, D) and ``bias`` as nn.Linear stores them."""
-    if mode not in ("mean", "max"):
-        raise ValueError(f"mode must be 'mean' or 'max' (got {mode!r})")
+    fl = _pool_flags(mode)
     dev = x.device
     N, L, D = x.shape
     classes = weight.shape[0]
@@ -783,8 +790,66 @@ def vit_pool_classify(x, ln_weight, ln_bias, eps, weight, bias=None, mode="max",
         _capi.call("stgcn_vit_pool_classify", _dev_ptr(x, "x", dev), _dev_ptr(ln_weight, "ln weight", dev),
                    _dev_ptr(ln_bias, "ln bias", dev), c_float(eps), _dev_ptr(weight, "weight", dev), _dev_ptr(bias, "bias", dev),
                    _dev_ptr(logits, "logits", dev), c_int(N), c_int(L), c_int(D), c_int(classes),
-                   c_uint(_capi.VIT_POOL_MAX if mode == "max" else 0), _stream(dev))
+                   c_uint(fl), _stream(dev))
     return logits
+
+
+# ---- The ST-ViT head: patch embedding with the class row (stgcn_vit_patch_embed) ----------------------------------------------
+def _patch_flags(math: int, channels_last: bool) -> int:
+    """The embedding's arithmetic from a block's flag word: f32 stays f32, everything else - bf16x3, 'mixed', and the
+    blocks' bf16 mode, for which the embedding has no kernel - runs bf16x3."""
+    low = MATH_F32 if not (math & VIT_BF16) and (math & _capi.MATH_MASK) == MATH_F32 else MATH_BF16X3
+    return low | (_capi.IN_NTVC if channels_last else 0)
+
+
+def vit_patch_embed_supported(N, C, T, V, p1, p2, E, math=MATH_F32, channels_last=False) -> bool:
+    """Whether ``vit_patch_embed`` runs this shape.  A host function: no GPU needed."""
+    return bool(_capi.lib().stgcn_vit_patch_embed_supported(N, C, T, V, p1, p2, E, _patch_flags(math, channels_last)))
+
+
+def vit_patch_embed_ws_bytes(N, C, T, V, p1, p2, E, math=MATH_F32, channels_last=False) -> int:
+    return int(_capi.lib().stgcn_vit_patch_embed_ws_bytes(N, C, T, V, p1, p2, E, _patch_flags(math, channels_last)))
+
+
+def vit_patch_embed_cut(N, C, T, V, p1, p2, E, math=MATH_F32, channels_last=False):
+    """``(tile rows, parts of K)`` the plan gives this call, or None where it is not covered.  A host function."""
+    c = _capi.lib().stgcn_vit_patch_embed_cut(N, C, T, V, p1, p2, E, _patch_flags(math, channels_last))
+    return (c >> 16, c & 0xFFFF) if c else None
+
+
+def vit_patch_embed(z, weight, bias, cls, pos, p1, p2, math=MATH_F32) -> torch.Tensor:
+    """The ST-ViT head's patch embedding of the stem output z (N, C, T, V) - contiguous, or channels-last strided as the fused
+    stem writes it, consumed in place - with the class row and the position table: x (N, n + 1, E), n = (T / p1) (V / p2),
+
+        x[:, 0] = cls + pos[0],   x[:, 1 + a w + b] = patch(a, b) W^T + bias + pos[1 + a w + b],
+
+    patch(a, b)[(f p2 + j) C + c] = z[:, c, a p1 + f, b p2 + j].  ``weight`` (E, p1 p2 C) and ``bias`` (E or None) as
+    nn.Linear stores them, ``cls`` E elements, ``pos`` the first n + 1 rows of the position table ((n + 1) E elements) or
+    None.  ``math``: MATH_F32 or MATH_BF16X3 (a block's flag word is accepted: see ``_patch_flags``)."""
+    dev = z.device
+    N, C, T, V = z.shape
+    E = weight.shape[0]
+    if T % p1 or V % p2:
+        raise ValueError(f"T = {T}, V = {V} are not whole patches of {p1} x {p2}")
+    n = (T // p1) * (V // p2)
+    if weight.shape[1] != p1 * p2 * C or cls.numel() != E or (bias is not None and bias.numel() != E):
+        raise ValueError(f"weight is {tuple(weight.shape)}, cls has {cls.numel()} elements; expected ({E}, {p1 * p2 * C}) and {E}")
+    if pos is not None:
+        if pos.numel() != (n + 1) * E:
+            raise ValueError(f"pos has {pos.numel()} elements, expected {(n + 1) * E}")
+        pos = pos.reshape(n + 1, E)
+    channels_last = _is_channels_last(z)
+    if channels_last:
+        z = z.permute(0, 2, 3, 1)
+    fl = _patch_flags(math, channels_last)
+    nbytes = int(_capi.lib().stgcn_vit_patch_embed_ws_bytes(N, C, T, V, p1, p2, E, fl))
+    ws = _bytes(dev, nbytes)
+    x = torch.empty((N, n + 1, E), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_patch_embed", _dev_ptr(z, "z", dev), _dev_ptr(weight, "weight", dev), _dev_ptr(bias, "bias", dev),
+                   _dev_ptr(cls.reshape(-1), "cls", dev), _dev_ptr(pos, "pos", dev), _dev_ptr(x, "x"), c_int(N), c_int(C), c_int(T),
+                   c_int(V), c_int(p1), c_int(p2), c_int(E), c_void_p(ws.data_ptr()), c_size_t(nbytes), c_uint(fl), _stream(dev))
+    return x
 
 
 def _head_shape(N, T, V, C, E1, E2, heads, hidden1, hidden2, depth1, depth2, classes):

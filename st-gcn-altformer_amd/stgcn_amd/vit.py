@@ -1,0 +1,298 @@
+"""The ST-ViT head (``model/ST_Vit/trans.py`` of the reference: ``ViT`` and its parts), with the inference forward on
+libstgcn_hip.so.
+
+``PreNorm``, ``FeedForward``, ``Attention``, ``Transformer``, ``ViT`` keep the reference's constructor arguments, attribute
+names, ``state_dict`` keys, shapes and construction order (``torch.manual_seed(s)`` followed by construction gives the
+reference's initial parameters; checkpoints load strictly).  ``einops`` is not needed: the rearranges are reshapes and
+permutes, and index 0 of ``to_patch_embedding`` is the parameter-free ``Patchify`` so that the Linear stays ``.1``.
+
+Two paths, one result:
+
+* HIP: ``functional.vit_patch_embed`` (the patches read from the stem output in place - contiguous, or channels-last as the
+  fused stem writes it - times the ``patch_dim -> dim`` weight, with the class row and the position table), one
+  ``functional.vit_block_forward`` per layer (the block the AltFormer heads run: qkv without bias, the modules' LayerNorm
+  eps, scale ``dim_head ** -0.5``), and ``functional.vit_pool_classify`` (``pool='cls'``: token 0, ``'mean'``: the mean over
+  all tokens, class token included; LayerNorm; Linear).  Each of the three decides for itself: a piece runs on HIP when its
+  input is CUDA float32, autograd records nothing that concerns it, no dropout below it is active, its ``_supported`` query
+  agrees and the call has at least ``hip_min_tokens`` tokens (N times n + 1).  A layer needs ``heads * dim_head == dim`` and a
+  projecting ``to_out``; ``heads == 1 and dim_head == dim`` (``to_out`` is the identity) runs on torch ops.
+  ``ViT.uses_hip(z)`` says whether a call runs on HIP from the stem output to the logits.
+* torch ops: everything else, and everything under autograd (training the ViT on HIP is not covered).  This is the
+  reference's arithmetic op for op.
+
+The switches of ``stgcn_amd.altformer`` act here as they do on its ``Block``s (``ViT`` and every ``Layer`` are
+``HipSwitches``): ``set_head_math`` ('f32' | 'bf16x3' | 'mixed' | 'bf16'; the patch embedding has no bf16 form and runs bf16x3
+under 'bf16', f32 under 'f32', bf16x3 otherwise), ``set_low_latency`` (tile forms by call size, ``split_attention``) and
+``set_hip_min_tokens``.
+
+Defaults (``VIT_HIP_MIN_TOKENS``, ``VIT_SMALL_TILES``): see the comment there for what has been measured.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import functional as F
+from .altformer import HipSwitches, _default_head_math, _drop_active
+
+# The defaults of a new ViT: the token count (N * (n + 1)) from which its pieces run on HIP, and whether the layers' linears
+# pick their tile form by call size.  MEASURED (profiles/stvit_times.json, tools/time_stvit.py: stem + ViT at 180 x 22, batch
+# 1, 8, 32, 128, 'mixed'): with the small-tile forms the model is faster than the same module on torch ops by more than the
+# spread at batch 1, 8 and 128 (2.07 x, 1.74 x, 1.30 x) and level at batch 32 (1.10 x, inside the spread), so the forms are
+# on and there is no threshold; with 128 x 128 tiles it ties at batch 1 and 8 and loses at batch 32 (0.81 x), which is why
+# they are not the default here (the AltFormer blocks keep HIP_MIN_TOKENS = 4096 and 128 x 128).  Batches between the
+# measured ones are not measured.
+VIT_HIP_MIN_TOKENS = 0
+VIT_SMALL_TILES = True
+
+
+def _records_grad(x, tensors) -> bool:
+    return torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in tensors))
+
+
+class Patchify(nn.Module):
+    """(b, c, h p1, w p2) -> (b, h w, p1 p2 c): patch (a, b) is token a w + b, its elements ordered p1, then p2, then c."""
+
+    def __init__(self, p1, p2):
+        super().__init__()
+        self.p1, self.p2 = p1, p2
+
+    def forward(self, x):
+        b, c, T, V = x.shape
+        h, w = T // self.p1, V // self.p2
+        return x.reshape(b, c, h, self.p1, w, self.p2).permute(0, 2, 4, 3, 5, 1).reshape(b, h * w, self.p1 * self.p2 * c)
+
+    def extra_repr(self):
+        return f"p1={self.p1}, p2={self.p2}"
+
+
+class PreNorm(nn.Module):
+    def __init__(self, dim, fn):
+        super().__init__()
+        self.norm = nn.LayerNorm(dim)
+        self.fn = fn
+
+    def forward(self, x, **kwargs):
+        return self.fn(self.norm(x), **kwargs)
+
+
+class FeedForward(nn.Module):
+    def __init__(self, dim, hidden_dim, dropout=0.):
+        super().__init__()
+        self.net = nn.Sequential(nn.Linear(dim, hidden_dim), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden_dim, dim),
+                                 nn.Dropout(dropout))
+
+    def forward(self, x):
+        return self.net(x)
+
+
+class Attention(nn.Module):
+    def __init__(self, dim, heads=8, dim_head=64, dropout=0.):
+        super().__init__()
+        inner_dim = dim_head * heads
+        project_out = not (heads == 1 and dim_head == dim)
+        self.heads = heads
+        self.scale = dim_head ** -0.5
+        self.attend = nn.Softmax(dim=-1)
+        self.to_qkv = nn.Linear(dim, inner_dim * 3, bias=False)
+        self.to_out = nn.Sequential(nn.Linear(inner_dim, dim), nn.Dropout(dropout)) if project_out else nn.Identity()
+
+    def forward(self, x):
+        b, n, _ = x.shape
+        q, k, v = (t.reshape(b, n, self.heads, -1).transpose(1, 2) for t in self.to_qkv(x).chunk(3, dim=-1))
+        attn = self.attend(torch.matmul(q, k.transpose(-1, -2)) * self.scale)
+        return self.to_out(torch.matmul(attn, v).transpose(1, 2).reshape(b, n, -1))
+
+
+class Layer(nn.ModuleList, HipSwitches):
+    """One encoder layer, ``[PreNorm(Attention), PreNorm(FeedForward)]`` as the reference's ``ModuleList`` holds it (the keys
+    stay ``layers.{i}.0.*`` / ``layers.{i}.1.*`` and ``attn, ff = layer`` still unpacks), with the forward and the switches of
+    a block: ``x = attn(x) + x`` then ``x = ff(x) + x``."""
+
+    DEFAULT_HIP_MIN_TOKENS = VIT_HIP_MIN_TOKENS
+    DEFAULT_SMALL_TILES = VIT_SMALL_TILES
+
+    def __init__(self, attn, ff):
+        super().__init__([attn, ff])
+        self._init_switches()
+
+    def _parts(self):
+        """(norm1, attention, norm2, feed-forward net), or None where the layer is not the structure the kernels implement."""
+        if len(self) != 2 or type(self[0]) is not PreNorm or type(self[1]) is not PreNorm:
+            return None
+        a, f = self[0].fn, self[1].fn
+        if type(a) is not Attention or type(f) is not FeedForward or not isinstance(a.to_out, nn.Sequential):
+            return None
+        net = f.net
+        if not (len(net) == 5 and type(net[0]) is nn.Linear and isinstance(net[1], nn.GELU) and type(net[3]) is nn.Linear
+                and getattr(net[1], "approximate", "none") == "none" and type(a.to_out[0]) is nn.Linear and a.to_qkv.bias is None):
+            return None
+        n1, n2 = self[0].norm, self[1].norm
+        if not (type(n1) is nn.LayerNorm and type(n2) is nn.LayerNorm and n1.elementwise_affine and n2.elementwise_affine
+                and n1.bias is not None and n2.bias is not None and n1.eps == n2.eps):
+            return None
+        return n1, a, n2, net
+
+    def _weights(self, parts):
+        n1, a, n2, net = parts
+        return (n1.weight, n1.bias, a.to_qkv.weight, None, a.to_out[0].weight, a.to_out[0].bias, n2.weight, n2.bias,
+                net[0].weight, net[0].bias, net[3].weight, net[3].bias)
+
+    def hip_applies(self, x: torch.Tensor) -> bool:
+        """Whether this call can run on ``stgcn_vit_block_forward`` (see the module docstring)."""
+        if self.force_torch or not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
+            return False
+        parts = self._parts()
+        if parts is None:
+            return False
+        n1, a, n2, net = parts
+        B, L, D = x.shape
+        inner = a.to_out[0].in_features
+        if (B < 1 or n1.normalized_shape != (D,) or n2.normalized_shape != (D,) or inner != D or a.to_qkv.out_features != 3 * D
+                or inner % a.heads or net[3].out_features != D
+                or net[3].in_features != net[0].out_features):
+            return False
+        if _records_grad(x, self._weights(parts)) or _drop_active(self):
+            return False
+        return F.vit_block_forward_supported(L, D, a.heads, net[0].out_features)
+
+    def uses_hip(self, x: torch.Tensor) -> bool:
+        """``hip_applies`` and the call has at least ``hip_min_tokens`` tokens."""
+        return torch.is_tensor(x) and x.dim() == 3 and x.shape[0] * x.shape[1] >= self.hip_min_tokens and self.hip_applies(x)
+
+    def _hip_flags(self, x: torch.Tensor) -> int:
+        _, a, _, net = self._parts()
+        return self._inference_flags(x.shape[1], x.shape[2], a.heads, net[0].out_features)
+
+    def forward(self, x):
+        if self.uses_hip(x):
+            parts = self._parts()
+            w = self._weights(parts)
+            with torch.no_grad():
+                return F.vit_block_forward(x.contiguous(), w[0:2], w[2:4], w[4:6], w[6:8], w[8:10], w[10:12], parts[1].heads,
+                                           parts[0].eps, parts[1].scale, self._hip_flags(x))
+        attn, ff = self
+        x = attn(x) + x
+        return ff(x) + x
+
+
+class Transformer(nn.Module):
+    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout=0.):
+        super().__init__()
+        self.layers = nn.ModuleList([])
+        for _ in range(depth):
+            self.layers.append(Layer(PreNorm(dim, Attention(dim, heads=heads, dim_head=dim_head, dropout=dropout)),
+                                     PreNorm(dim, FeedForward(dim, mlp_dim, dropout=dropout))))
+
+    def forward(self, x):
+        for layer in self.layers:
+            x = layer(x)
+        return x
+
+
+class ViT(nn.Module, HipSwitches):
+    """Stem output (N, channels, time_len, joint) -> logits (N, num_classes): p1 x p2 patches, class token, ``depth`` layers,
+    the class token or the mean over the tokens, ``mlp_head``."""
+
+    DEFAULT_HIP_MIN_TOKENS = VIT_HIP_MIN_TOKENS
+    DEFAULT_SMALL_TILES = VIT_SMALL_TILES
+
+    def __init__(self, *, time_len, joint, p1, p2, num_classes, dim, depth, heads, mlp_dim, pool='cls', channels=128, dim_head=64,
+                 dropout=0., emb_dropout=0.):
+        super().__init__()
+        assert time_len % p1 == 0, 'Image dimensions must be divisible by the patch size.'
+        assert joint % p2 == 0
+        num_patches = (time_len // p1) * (joint // p2)
+        patch_dim = channels * p1 * p2
+        assert pool in {'cls', 'mean'}, 'pool type must be either cls (cls token) or mean (mean pooling)'
+        self.to_patch_embedding = nn.Sequential(Patchify(p1, p2), nn.Linear(patch_dim, dim))
+        self.pos_embedding = nn.Parameter(torch.zeros(1, num_patches + 1, dim))
+        self.cls_token = nn.Parameter(torch.randn(1, 1, dim))
+        self.dropout = nn.Dropout(emb_dropout)
+        self.transformer = Transformer(dim, depth, heads, dim_head, mlp_dim, dropout)
+        self.pool = pool
+        self.to_latent = nn.Identity()
+        self.mlp_head = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, num_classes))
+        self._init_switches()
+
+    # ---- the front: patches, class row, position table -------------------------------------------------------------------------
+    def _embed_tokens(self, z):
+        """n + 1 tokens per clip of this input, or None where it cannot be cut into whole patches."""
+        pat = self.to_patch_embedding[0]
+        if not torch.is_tensor(z) or z.dim() != 4 or type(pat) is not Patchify or z.shape[2] % pat.p1 or z.shape[3] % pat.p2:
+            return None
+        return (z.shape[2] // pat.p1) * (z.shape[3] // pat.p2) + 1
+
+    def _math(self) -> int:
+        """The flag word whose arithmetic the embedding follows (``functional._patch_flags`` maps it to f32 or bf16x3)."""
+        return _default_head_math() if self.math_mode is None else self.math_mode
+
+    def embed_on_hip(self, z) -> bool:
+        """Whether the patch embedding of this call runs on ``stgcn_vit_patch_embed``."""
+        tokens = self._embed_tokens(z)
+        emb = self.to_patch_embedding
+        if tokens is None or self.force_torch or not z.is_cuda or z.dtype != torch.float32 or len(emb) != 2 or type(emb[1]) is not nn.Linear:
+            return False
+        if not (z.is_contiguous() or F._is_channels_last(z)) or z.shape[0] * tokens < self.hip_min_tokens:
+            return False
+        lin = emb[1]
+        N, C, T, V = z.shape
+        pat = emb[0]
+        if (lin.in_features != pat.p1 * pat.p2 * C or self.cls_token.numel() != lin.out_features
+                or self.pos_embedding.dim() != 3 or self.pos_embedding.shape[1] < tokens
+                or self.pos_embedding.shape[2] != lin.out_features):
+            return False
+        if _records_grad(z, (lin.weight, lin.bias, self.cls_token, self.pos_embedding)) or _drop_active(self.dropout):
+            return False
+        return F.vit_patch_embed_supported(N, C, T, V, pat.p1, pat.p2, lin.out_features, self._math(), F._is_channels_last(z))
+
+    def embed(self, z):
+        """(N, n + 1, dim): patches times the weight, the class row in front, the first n + 1 position rows added."""
+        if self.embed_on_hip(z):
+            pat, lin = self.to_patch_embedding
+            n1 = self._embed_tokens(z)
+            with torch.no_grad():
+                return F.vit_patch_embed(z, lin.weight, lin.bias, self.cls_token, self.pos_embedding[0, :n1], pat.p1, pat.p2,
+                                         self._math())
+        x = self.to_patch_embedding(z)
+        b, n, _ = x.shape
+        x = torch.cat((self.cls_token.expand(b, -1, -1), x), dim=1)
+        x += self.pos_embedding[:, :(n + 1)]
+        return self.dropout(x)
+
+    # ---- the end: pooling, LayerNorm, classifier ----------------------------------------------------------------------------------
+    def head_on_hip(self, x) -> bool:
+        """Whether pooling and ``mlp_head`` of this call run on ``stgcn_vit_pool_classify``."""
+        head = self.mlp_head
+        if (self.force_torch or not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3
+                or self.pool not in ('cls', 'mean') or type(self.to_latent) is not nn.Identity):
+            return False
+        if not (isinstance(head, nn.Sequential) and len(head) == 2 and type(head[0]) is nn.LayerNorm and type(head[1]) is nn.Linear
+                and head[0].elementwise_affine and head[0].bias is not None):
+            return False
+        N, L, D = x.shape
+        if head[0].normalized_shape != (D,) or head[1].in_features != D or N * L < self.hip_min_tokens:
+            return False
+        if _records_grad(x, (head[0].weight, head[0].bias, head[1].weight, head[1].bias)):
+            return False
+        return F.vit_pool_classify_supported(N, L, D, head[1].out_features)
+
+    def classify(self, x):
+        if self.head_on_hip(x):
+            ln, lin = self.mlp_head
+            with torch.no_grad():
+                return F.vit_pool_classify(x.contiguous(), ln.weight, ln.bias, ln.eps, lin.weight, lin.bias, mode=self.pool)
+        x = x.mean(dim=1) if self.pool == 'mean' else x[:, 0]
+        return self.mlp_head(self.to_latent(x))
+
+    def uses_hip(self, z) -> bool:
+        """Whether ``forward(z)`` runs on the HIP kernels from the stem output to the logits: the embedding, every layer and
+        the pooled classifier."""
+        tokens = self._embed_tokens(z)
+        if tokens is None or not self.embed_on_hip(z):
+            return False
+        probe = z.as_strided((z.shape[0], tokens, self.to_patch_embedding[1].out_features), (0, 0, 0))   # the shape without memory
+        return all(isinstance(layer, Layer) and layer.uses_hip(probe) for layer in self.transformer.layers) and self.head_on_hip(probe)
+
+    def forward(self, img):
+        return self.classify(self.transformer(self.embed(img)))
