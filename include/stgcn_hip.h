@@ -356,7 +356,8 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
  * element of y with the same instructions in the same order, so results are bit-identical across forms; the smaller ones
  * spread a small call (one clip) over more workgroups.  stgcn_vit_linear and stgcn_vit_block_forward (all four linears)
  * honour the field; the training entry points (stgcn_vit_block_forward_train, stgcn_vit_block_backward,
- * stgcn_vit_linear_backward) always run 128 x 128 and answer STGCN_ERR_ARG to a non-zero field. */
+ * stgcn_vit_linear_backward) always run 128 x 128 and answer STGCN_ERR_ARG to a non-zero field; the training pair with
+ * dropout at the end of this header (stgcn_vit_block_forward_train_drop, stgcn_vit_block_backward_drop) honours it. */
 #define STGCN_VIT_TILE_MASK 0x30000u
 #define STGCN_VIT_TILE_AUTO 0x10000u /* the plan picks: the largest form that gives at least 256 tiles, else the smallest  */
 #define STGCN_VIT_TILE_64 0x20000u   /* force 64 x 64                                                                  */
@@ -687,6 +688,47 @@ size_t stgcn_vit_patch_embed_ws_bytes(int N, int C, int T, int V, int p1, int p2
 int stgcn_vit_patch_embed_cut(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags);
 int stgcn_vit_patch_embed(const float *z, const float *W, const float *bias, const float *cls, const float *pos, float *x, int N,
                           int C, int T, int V, int p1, int p2, int E, void *ws, size_t ws_bytes, unsigned flags, void *stream);
+
+/* ---- ViT block: training with dropout (additive to ABI 11: two structs, two entry points, two queries) ----
+ * The ST-ViT layers (model/ST_Vit/trans.py) are the block above with three live nn.Dropouts: behind the projection, behind
+ * the GELU and behind the second MLP linear.  stgcn_vit_block_forward_train_drop / stgcn_vit_block_backward_drop take what
+ * stgcn_vit_block_forward_train / stgcn_vit_block_backward take (the twelve parameters and the twelve gradients as structs of
+ * device pointers; bqkv, bproj, b1, b2 and the gradient bqkv may be NULL as there) plus `masks`: three fp32 tensors of factors,
+ * 0 or 1 / (1 - p), each optional (a NULL member, or masks == NULL, means 1):
+ *   m_proj (B, L, D)   m_act (B, L, hidden)   m_fc2 (B, L, D)
+ * With * elementwise and s1 / s2 the per-sequence factors scale1 / scale2:
+ *   forward   a     = att Wproj^T + bproj            x1 = x + s1[b] (m_proj * a)
+ *             h_pre = LN2(x1) W1^T + b1              h  = m_act * GELU(h_pre)          saved: h_pre unmasked, h masked
+ *             y     = x1 + s2[b] (m_fc2 * (h W2^T + b2))
+ *   backward  g2 = m_fc2 * dy     dW2 = (s2 g2)^T h     db2 = sum s2 g2     dh = (s2 g2 W2) * GELU'(h_pre) * m_act
+ *             LN2's residual gradient is the UNMASKED dy
+ *             g1 = m_proj * dx1   dWproj = (s1 g1)^T att   dbproj = sum s1 g1   datt = s1 g1 Wproj
+ *             everything else as stgcn_vit_block_backward.
+ * A mask is applied in fp32, in the epilogue of the linear that produces the masked tensor (after GELU / GELU', before the
+ * row factor and the residual), so before any bf16 rounding of STGCN_VIT_TRAIN_BF16; g2 and g1 are each written once by a small
+ * vector kernel into a workspace slab that is free at that point and read by a dgrad and a wgrad.  No atomics: two runs are
+ * bit-identical.  m_proj, m_fc2, dy and ws must be 16-byte aligned when m_proj or m_fc2 is given.
+ * `saved` keeps layout and size (stgcn_vit_block_train_long_saved_bytes); the workspace is
+ * stgcn_vit_block_train_drop_ws_bytes (= stgcn_vit_block_train_long_ws_bytes); stgcn_vit_block_train_drop_supported =
+ * stgcn_vit_block_train_long_supported.
+ * Flags: as the older pair (f32 / bf16x3 low bits, STGCN_VIT_QKV_F32, STGCN_VIT_TRAIN_BF16, STGCN_VIT_TRAIN_ATTN_BF16;
+ * STGCN_VIT_BF16 and STGCN_VIT_ATTN_SPLIT: STGCN_ERR_ARG before the pointers are looked at), with one difference: a
+ * STGCN_VIT_TILE_* field is accepted and selects the tile form of every forward and dgrad linear of the call (the weight
+ * gradient kernels have one form).  Results are bit-identical across the forms, as in inference.
+ * With no mask and no tile field the pair runs what the older pair runs, bit for bit: both are one forward and one backward. */
+typedef struct { const float *m_proj, *m_act, *m_fc2; } stgcn_vit_drop_masks;
+typedef struct { float *norm1_weight, *norm1_bias, *Wqkv, *bqkv, *Wproj, *bproj,
+                       *norm2_weight, *norm2_bias, *W1, *b1, *W2, *b2; } stgcn_vit_block_grads;
+int stgcn_vit_block_train_drop_supported(int L, int D, int heads, int hidden);
+size_t stgcn_vit_block_train_drop_ws_bytes(int B, int L, int D, int heads, int hidden);
+int stgcn_vit_block_forward_train_drop(const float *x, const stgcn_vit_block_weights *weights, const float *scale1,
+                                       const float *scale2, const stgcn_vit_drop_masks *masks, float eps, float scale,
+                                       void *saved, size_t saved_bytes, float *y, int B, int L, int D, int heads, int hidden,
+                                       unsigned flags, void *stream);
+int stgcn_vit_block_backward_drop(const float *x, const stgcn_vit_block_weights *weights, const float *scale1,
+                                  const float *scale2, const stgcn_vit_drop_masks *masks, const void *saved, size_t saved_bytes,
+                                  const float *dy, float *dx, const stgcn_vit_block_grads *grads, float eps, float scale, void *ws,
+                                  size_t ws_bytes, int B, int L, int D, int heads, int hidden, unsigned flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -75,9 +75,13 @@ inline LinearTile linear_tile(int M, int K, int Nout, unsigned flags) {
 // ---- the plan of a block call, decided here and nowhere else ----
 // A plain host function of (entry point, L, D, heads, hidden, flags).  The four entry points below and every stgcn_vit_block_*
 // query read it; none of them looks at a flag bit or compares a length again.
-enum class BlockEntry { forward, forward_train, backward, linear_backward };
+// forward_train_drop / backward_drop: the training pair with per-element dropout masks (stgcn_vit_block_forward_train_drop,
+// stgcn_vit_block_backward_drop).  They plan as forward_train / backward do, but for the one thing they add: a tile field.
+enum class BlockEntry { forward, forward_train, backward, linear_backward, forward_train_drop, backward_drop };
 constexpr const char *kBlockEntryName[] = {"stgcn_vit_block_forward", "stgcn_vit_block_forward_train", "stgcn_vit_block_backward",
-                                           "stgcn_vit_linear_backward"};
+                                           "stgcn_vit_linear_backward", "stgcn_vit_block_forward_train_drop",
+                                           "stgcn_vit_block_backward_drop"};
+inline bool block_entry_drop(BlockEntry e) { return e == BlockEntry::forward_train_drop || e == BlockEntry::backward_drop; }
 // resident (launch_attention_packed, launch_attention_backward): K and V of a (sequence, head) on chip, up to kMaxL tokens;
 // stream (launch_attention_stream, launch_attention_backward_stream): K and V in key tiles through LDS, above kMaxL and up to
 // kMaxStreamL; resident_bf16 (launch_attention_bf16): the resident form on bf16 qkv / out, STGCN_VIT_BF16 only;
@@ -115,7 +119,8 @@ struct BlockPlan {
     unsigned qkv_fwd = 0, lin_fwd = 0, qkv_dgrad = 0, lin_dgrad = 0;
     bool wgrad_bf16 = false;
     bool bf16_store = false;         // qkv, the attention output and the fc1 hidden are bf16 storage between the launches
-    unsigned tile = 0;               // the STGCN_VIT_TILE_* field the forward's linears get (training: 0, 128 x 128 only)
+    // the STGCN_VIT_TILE_* field the forward's linears get (and the dgrads of backward_drop); the older training pair: 0, 128 x 128 only
+    unsigned tile = 0;
 };
 
 inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidden, unsigned flags) {
@@ -133,7 +138,7 @@ inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidde
             p.refusal = "STGCN_VIT_TRAIN_ATTN_BF16 is a training mode (stgcn_vit_block_forward_train, stgcn_vit_block_backward only)";
     } else if (flags & STGCN_VIT_BF16) {
         p.refusal = "STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)";
-    } else if (flags & STGCN_VIT_TILE_MASK) {
+    } else if ((flags & STGCN_VIT_TILE_MASK) && !block_entry_drop(entry)) {
         p.refusal = "training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)";
     } else if (entry == BlockEntry::linear_backward && (flags & STGCN_VIT_TRAIN_ATTN_BF16)) {
         p.refusal = "STGCN_VIT_TRAIN_ATTN_BF16 is a mode of the block (stgcn_vit_block_forward_train, stgcn_vit_block_backward only)";
@@ -147,7 +152,7 @@ inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidde
     // without the bit, for the reason above.
     p.wgrad_bf16 = !inference && (flags & STGCN_VIT_TRAIN_BF16) != 0;
     p.bf16_store = bf16;
-    p.tile = inference ? flags & STGCN_VIT_TILE_MASK : 0;
+    p.tile = inference || block_entry_drop(entry) ? flags & STGCN_VIT_TILE_MASK : 0;
     p.qkv_fwd = bf16 ? (unsigned)STGCN_MATH_BF16 : (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : low;
     p.lin_fwd = p.lin_dgrad = bf16 || p.wgrad_bf16 ? (unsigned)STGCN_MATH_BF16 : low;
     p.qkv_dgrad = p.wgrad_bf16 ? (unsigned)STGCN_MATH_BF16 : p.qkv_fwd;
@@ -222,21 +227,33 @@ struct BlockStore {
     }
 };
 
+// Per-element dropout factors of a training call (0 or 1 / (1 - p), fp32; a NULL member = 1): behind the projection (B, L, D),
+// behind the GELU (B, L, hidden), behind the second MLP linear (B, L, D).  stgcn_vit_drop_masks of the C ABI, member for member.
+struct BlockDrop {
+    const float *proj = nullptr, *act = nullptr, *fc2 = nullptr;
+    bool any() const { return proj || act || fc2; }
+};
+
 // The forward of one block, the one loop that every forward entry point runs: five launches per slab of whole sequences,
 //   qkv = LN1(x) Wqkv^T + b -> attention -> x1 = s1 (a Wproj^T + b) + x -> h = GELU(LN2(x1) W1^T + b1) -> y = s2 (h W2^T + b2) + x1
 // (both LayerNorms inside the linear that consumes them), with the kernels, arithmetic and storage of `plan`, the
 // intermediates in `store`, and stochastic depth's per-sequence factors scale1 / scale2 (B floats each, or NULL = 1).
+// `drop` (the _drop training forward only): x1 = x + s1 (m_proj * a), h = m_act * GELU(h_pre), y = x1 + s2 (m_fc2 * (h W2^T + b2)),
+// each mask walked per slab as scale1 / scale2 are.
 int block_forward(const BlockPlan &plan, const float *x, const BlockWeights &w, const BlockStore &store, const float *scale1,
-                  const float *scale2, float eps, float scale, float *y, int B, int L, int D, int heads, int hidden, hipStream_t st);
+                  const float *scale2, float eps, float scale, float *y, int B, int L, int D, int heads, int hidden, hipStream_t st,
+                  const BlockDrop &drop = BlockDrop{});
 
 // What the training forward and the backward add to the linear (all optional, zero-initialised = the plain linear):
 //   pre      : the value before the activation, acc + bias, is also stored here (M, Nout)           [forward_train: h_pre]
 //   dgelu    : the result is multiplied by GELU'(dgelu[row][col]), exact erf form                   [dgrad of fc2]
+//   mask     : then by mask[row][col], an (M, Nout) fp32 factor (dropout: 0 or 1 / (1 - p)), after GELU / GELU'    [_drop entries]
 //   rowscale : then by rowscale[row / L] (stochastic depth: one factor per sequence), before R is added
 //   kx       : X's rows are kx long (kx <= K, kx % 4 == 0) and read as zero from kx to K            [dgrad with Nout % 32 != 0]
 struct LinearExtra {
     float *pre = nullptr;
     const float *dgelu = nullptr;
+    const float *mask = nullptr;
     const float *rowscale = nullptr;
     int L = 1;
     int kx = 0;
@@ -277,6 +294,10 @@ int launch_attention_backward_bf16(const float *qkv, const float *out, const flo
 // Wt (cols, rows_pad) = W (rows, cols)^T, the columns from `rows` to rows_pad zero-filled: the dgrad dX = dY W is the
 // forward linear on the transposed weight, so it shares launch_linear's kernel, arithmetic modes and epilogues.
 int launch_transpose_pad(const float *W, float *Wt, int rows, int cols, int rows_pad, hipStream_t st);
+
+// out (n floats) = a * m elementwise, n % 4 == 0 and all three 16-byte aligned: a masked gradient made once for the dgrad and
+// the wgrad that both read it (16-byte loads and stores, one owner per element).
+int launch_mask_mul(const float *a, const float *m, float *out, size_t n, hipStream_t st);
 
 // Weight / bias gradient of Y = A W^T + b over the rows [0, M):  dW (Nout, K) = (s dY)^T A,  db (Nout) = column sums of s dY,
 // s = rowscale[row / L] or 1.  The reduction over M is cut into wgrad_splits(M, K, Nout) row ranges; each writes one slab of

@@ -47,6 +47,16 @@ __global__ __launch_bounds__(256) void transpose_pad_kernel(const float *__restr
     }
 }
 
+// ---- masked gradient --------------------------------------------------------------------------------------------------------
+// out = a * m over n4 float4s, a grid-stride loop: one 16-byte load of each operand and one 16-byte store per step.
+__global__ __launch_bounds__(256) void mask_mul_kernel(const float4 *__restrict__ a, const float4 *__restrict__ m,
+                                                       float4 *__restrict__ out, size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const float4 va = a[i], vm = m[i];
+        out[i] = make_float4(va.x * vm.x, va.y * vm.y, va.z * vm.z, va.w * vm.w);
+    }
+}
+
 // ---- wgrad ----------------------------------------------------------------------------------------------------------------
 constexpr int WT = 128, WC = kWgradChunk, WLD = 160;   // tile edge, tokens per chunk, LDS row stride (floats)
 
@@ -487,6 +497,16 @@ int reduce_parts(const float *part, int parts, size_t n, float *dst, float *tmp,
 int launch_transpose_pad(const float *W, float *Wt, int rows, int cols, int rows_pad, hipStream_t st) {
     transpose_pad_kernel<<<dim3(ceil_div(cols, 32), ceil_div(rows_pad, 32)), dim3(256), 0, st>>>(W, Wt, rows, cols, rows_pad);
     STGCN_LAUNCH_CHECK("transpose_pad_kernel");
+    return STGCN_OK;
+}
+
+int launch_mask_mul(const float *a, const float *m, float *out, size_t n, hipStream_t st) {
+    if (n == 0 || n % 4 != 0 || (((uintptr_t)a | (uintptr_t)m | (uintptr_t)out) & 15) != 0)
+        return fail(STGCN_ERR_ARG, "vit mask: %zu elements, or an operand that is not 16-byte aligned", n);
+    const size_t n4 = n / 4, want = (n4 + 255) / 256;
+    mask_mul_kernel<<<dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st>>>(
+        reinterpret_cast<const float4 *>(a), reinterpret_cast<const float4 *>(m), reinterpret_cast<float4 *>(out), n4);
+    STGCN_LAUNCH_CHECK("mask_mul_kernel");
     return STGCN_OK;
 }
 

@@ -9,7 +9,8 @@ namespace stgcn {
 namespace vit {
 
 int block_forward(const BlockPlan &plan, const float *x, const BlockWeights &w, const BlockStore &store, const float *scale1,
-                  const float *scale2, float eps, float scale, float *y, int B, int L, int D, int heads, int hidden, hipStream_t st) {
+                  const float *scale2, float eps, float scale, float *y, int B, int L, int D, int heads, int hidden, hipStream_t st,
+                  const BlockDrop &drop) {
     const size_t es = plan.bf16_store ? 2 : 4;   // bytes per element of qkv, att and hid
     const unsigned tile = plan.tile, xb = plan.bf16_store ? STGCN_VIT_X_BF16 : 0, yb = plan.bf16_store ? STGCN_VIT_Y_BF16 : 0;
     const int per = slab_seqs(B, L), hd = D / heads;
@@ -25,6 +26,9 @@ int block_forward(const BlockPlan &plan, const float *x, const BlockWeights &w, 
         e2.rowscale = scale2 != nullptr ? scale2 + b0 : nullptr;
         e1.L = e2.L = L;
         eh.pre = store.hpre != nullptr ? store.hpre + s0 * hidden : nullptr;
+        e1.mask = drop.proj != nullptr ? drop.proj + r0 * D : nullptr;        // the masks cover the whole batch: first row r0
+        eh.mask = drop.act != nullptr ? drop.act + r0 * hidden : nullptr;
+        e2.mask = drop.fc2 != nullptr ? drop.fc2 + r0 * D : nullptr;
         int rc;
         if ((rc = launch_linear(xs, w.Wqkv, w.bqkv, nullptr, w.norm1_weight, w.norm1_bias, eps, qkv, M, D, 3 * D, false,
                                 plan.qkv_fwd | tile | yb, st)))

@@ -17,6 +17,15 @@
 // stored tensor are fp32 in every mode (the attention's products too, unless STGCN_VIT_TRAIN_ATTN_BF16 moves the resident
 // form to bf16 operands), so `saved` and the workspace have one layout.  Parameter gradients of the second and
 // later slabs are added onto the first slab's in slab order, so the result does not depend on anything but the shapes.
+//
+// Two pairs of entry points run the one forward_train and the one backward below: stgcn_vit_block_forward_train /
+// stgcn_vit_block_backward, and the _drop pair of the ST-ViT layers, which adds three per-element dropout masks (BlockDrop:
+// behind the projection, behind the GELU, behind fc2) and takes a tile field for its forward and dgrad linears.  A mask is
+// one more factor in the epilogue of the linear that makes the masked tensor (LinearExtra::mask, fp32, after GELU / GELU',
+// before the row factor, the residual and any later bf16 rounding); the two masked gradients that a dgrad AND a wgrad read,
+// g2 = m_fc2 * dy and g1 = m_proj * dx1, are each made once by launch_mask_mul into a slab that is free then (datt during the
+// MLP branch, dn between LN2's parameter gradient and the qkv dgrad).  Every mask pointer is advanced per slab by the
+// slab's first row, as x and dy are.
 #include "vit.h"
 
 namespace stgcn {
@@ -102,6 +111,131 @@ int wgrad(const BlockPlan &plan, const float *dY, const float *A, const float *r
 }
 
 bool linear_bwd_ok(int M, int K, int Nout) { return M >= 1 && K >= 1 && Nout >= 1 && K % 32 == 0 && Nout % 4 == 0; }
+
+// the twelve parameter gradients of a block (bqkv may be NULL: qkv_bias=False)
+struct BlockGrads {
+    float *norm1_weight, *norm1_bias, *Wqkv, *bqkv, *Wproj, *bproj, *norm2_weight, *norm2_bias, *W1, *b1, *W2, *b2;
+    bool present() const {
+        return norm1_weight && norm1_bias && Wqkv && Wproj && bproj && norm2_weight && norm2_bias && W1 && b1 && W2 && b2;
+    }
+};
+
+BlockWeights block_weights(const stgcn_vit_block_weights &b) {
+    return BlockWeights{b.norm1_weight, b.norm1_bias, b.Wqkv, b.bqkv, b.Wproj, b.bproj, b.norm2_weight, b.norm2_bias, b.W1, b.b1, b.W2, b.b2};
+}
+
+BlockDrop block_drop(const stgcn_vit_drop_masks *m) {
+    BlockDrop d;
+    if (m != nullptr) d.proj = m->m_proj, d.act = m->m_act, d.fc2 = m->m_fc2;
+    return d;
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// The training forward of both pairs: `entry` is forward_train (no masks, no tile field) or forward_train_drop.
+int forward_train(BlockEntry entry, const float *x, const BlockWeights &w, const float *scale1, const float *scale2,
+                  const BlockDrop &drop, float eps, float scale, void *saved, size_t saved_bytes, float *y, int B, int L, int D,
+                  int heads, int hidden, unsigned flags, void *stream) {
+    const BlockPlan plan = plan_block(entry, L, D, heads, hidden, flags);
+    const char *name = kBlockEntryName[(int)entry];
+    if (plan.refusal) return block_refused(plan);
+    if (!x || !w.present() || !y || !saved) return fail(STGCN_ERR_ARG, "%s: null pointer", name);
+    if (B < 1) return fail(STGCN_ERR_ARG, "%s: B = %d", name, B);
+    if (y == x) return fail(STGCN_ERR_ARG, "%s: y must not alias x", name);
+    if (!plan.covered) return block_unsupported(plan, L, D, heads, hidden, flags);
+    const BlockStore sv(saved, plan, B, L, D, hidden);
+    if (saved_bytes < sv.total) return fail(STGCN_ERR_WORKSPACE, "%s: saved buffer %zu < %zu bytes", name, saved_bytes, sv.total);
+    return block_forward(plan, x, w, sv, scale1, scale2, eps, scale, y, B, L, D, heads, hidden, static_cast<hipStream_t>(stream), drop);
+}
+
+// The backward of both pairs (the order of the header comment).  With masks, per slab: g2 = m_fc2 * dy is made once into the
+// datt slab, which nothing holds during the MLP branch, and read by the fc2 dgrad and wgrad; m_act rides in that dgrad's
+// epilogue, behind GELU'; LN2's residual gradient stays the unmasked dy; g1 = m_proj * dx1 is made once into the dn slab,
+// which is free between LN2's parameter gradient and the qkv dgrad, and read by the proj dgrad and wgrad, while dx1 itself
+// stays LN1's residual gradient.  A mask that is NULL costs no launch and no read.
+int backward(BlockEntry entry, const float *x, const BlockWeights &wt, const float *scale1, const float *scale2, const BlockDrop &drop,
+             const void *saved, size_t saved_bytes, const float *dy, float *dx, const BlockGrads &g, float eps, float scale, void *ws,
+             size_t ws_bytes, int B, int L, int D, int heads, int hidden, unsigned flags, void *stream) {
+    const BlockPlan plan = plan_block(entry, L, D, heads, hidden, flags);
+    const char *name = kBlockEntryName[(int)entry];
+    if (plan.refusal) return block_refused(plan);
+    if (!x || !wt.present() || !saved || !dy || !dx || !g.present() || !ws) return fail(STGCN_ERR_ARG, "%s: null pointer", name);
+    if (B < 1) return fail(STGCN_ERR_ARG, "%s: B = %d", name, B);
+    if (dx == dy || dx == x) return fail(STGCN_ERR_ARG, "%s: dx must not alias dy or x", name);
+    if ((drop.fc2 != nullptr || drop.proj != nullptr) && !(aligned16(drop.fc2) && aligned16(drop.proj) && aligned16(dy) && aligned16(ws)))
+        return fail(STGCN_ERR_ARG, "%s: with m_proj or m_fc2, both masks, dy and ws must be 16-byte aligned", name);
+    if (!plan.covered) return block_unsupported(plan, L, D, heads, hidden, flags);
+    const BlockStore sv(const_cast<void *>(saved), plan, B, L, D, hidden);
+    if (saved_bytes < sv.total) return fail(STGCN_ERR_WORKSPACE, "%s: saved buffer %zu < %zu bytes", name, saved_bytes, sv.total);
+    const TrainWs tw(ws, plan, B, L, D, heads, hidden);
+    if (ws_bytes < tw.total) return fail(STGCN_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", name, ws_bytes, tw.total);
+    const BackwardWs &w = tw.w;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned math = plan.lin_dgrad | plan.tile, math_qkv = plan.qkv_dgrad | plan.tile;
+    int rc;
+    if ((rc = launch_transpose_pad(wt.Wqkv, w.wt_qkv, 3 * D, D, 3 * D, st))) return rc;
+    if ((rc = launch_transpose_pad(wt.Wproj, w.wt_proj, D, D, D, st))) return rc;
+    if ((rc = launch_transpose_pad(wt.W1, w.wt_fc1, hidden, D, hidden, st))) return rc;
+    if ((rc = launch_transpose_pad(wt.W2, w.wt_fc2, D, hidden, D, st))) return rc;
+    const int per = slab_seqs(B, L);
+    for (int b0 = 0; b0 < B; b0 += per) {
+        const int nb = B - b0 < per ? B - b0 : per;
+        const int M = nb * L;
+        const size_t r0 = (size_t)b0 * L;
+        const bool acc = b0 > 0;
+        const float *xs = x + r0 * D, *dys = dy + r0 * D;
+        const float *qkv = (const float *)sv.qkv + r0 * 3 * D, *att = (const float *)sv.att + r0 * D, *x1 = sv.x1 + r0 * D;
+        const float *hpre = sv.hpre + r0 * hidden, *hid = (const float *)sv.hid + r0 * hidden;
+        const float *s1 = scale1 != nullptr ? scale1 + b0 : nullptr, *s2 = scale2 != nullptr ? scale2 + b0 : nullptr;
+        // the masks cover the whole batch, as x and dy do: this slab's first row is r0
+        const float *mproj = drop.proj != nullptr ? drop.proj + r0 * D : nullptr, *mfc2 = drop.fc2 != nullptr ? drop.fc2 + r0 * D : nullptr;
+        LinearExtra e2, e1;
+        e2.dgelu = hpre;
+        e2.mask = drop.act != nullptr ? drop.act + r0 * hidden : nullptr;
+        e2.rowscale = s2;
+        e1.rowscale = s1;
+        e1.L = e2.L = L;
+        // MLP branch
+        const float *g2 = dys;
+        if (mfc2 != nullptr) {
+            if ((rc = launch_mask_mul(dys, mfc2, w.datt, (size_t)M * D, st))) return rc;
+            g2 = w.datt;
+        }
+        if ((rc = launch_linear(g2, w.wt_fc2, nullptr, nullptr, nullptr, nullptr, 0.f, w.dhid, M, D, hidden, false, math, st, e2)))
+            return rc;
+        if ((rc = wgrad(plan, g2, hid, s2, L, g.W2, g.b2, w.part, w.tmp, M, hidden, D, acc, st))) return rc;
+        if ((rc = launch_linear(w.dhid, w.wt_fc1, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, hidden, D, false, math, st)))
+            return rc;
+        if ((rc = launch_ln_backward(x1, w.dn, wt.norm2_weight, wt.norm2_bias, eps, dys, w.dx1, w.a, w.stats, M, D, st))) return rc;
+        if ((rc = launch_ln_param_grad(x1, w.dn, w.stats, g.norm2_weight, g.norm2_bias, w.part, w.tmp, M, D, acc, st))) return rc;
+        if ((rc = wgrad(plan, w.dhid, w.a, nullptr, L, g.W1, g.b1, w.part, w.tmp, M, D, hidden, acc, st))) return rc;
+        // attention branch
+        const float *g1 = w.dx1;
+        if (mproj != nullptr) {
+            if ((rc = launch_mask_mul(w.dx1, mproj, w.dn, (size_t)M * D, st))) return rc;
+            g1 = w.dn;
+        }
+        if ((rc = launch_linear(g1, w.wt_proj, nullptr, nullptr, nullptr, nullptr, 0.f, w.datt, M, D, D, false, math, st, e1)))
+            return rc;
+        if ((rc = wgrad(plan, g1, att, s1, L, g.Wproj, g.bproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
+        switch (plan.attention) {
+            case BlockAttention::stream:
+                rc = launch_attention_backward_stream(qkv, att, w.datt, w.dqkv, tw.att_stats, nb, L, heads, D / heads, scale, st);
+                break;
+            case BlockAttention::resident_train_bf16:
+                rc = launch_attention_backward_bf16(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st);
+                break;
+            default: rc = launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st); break;
+        }
+        if (rc) return rc;
+        if ((rc = launch_linear(w.dqkv, w.wt_qkv, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, 3 * D, D, false, math_qkv, st)))
+            return rc;
+        if ((rc = launch_ln_backward(xs, w.dn, wt.norm1_weight, wt.norm1_bias, eps, w.dx1, dx + r0 * D, w.a, w.stats, M, D, st))) return rc;
+        if ((rc = launch_ln_param_grad(xs, w.dn, w.stats, g.norm1_weight, g.norm1_bias, w.part, w.tmp, M, D, acc, st))) return rc;
+        if ((rc = wgrad(plan, w.dqkv, w.a, nullptr, L, g.Wqkv, g.bqkv, w.part, w.tmp, M, D, 3 * D, acc, st))) return rc;
+    }
+    return STGCN_OK;
+}
 
 }  // namespace
 }  // namespace vit
@@ -278,17 +412,9 @@ int stgcn_vit_block_forward_train(const float *x, const float *norm1_weight, con
                                   const float *scale1, const float *scale2, float eps, float scale, void *saved,
                                   size_t saved_bytes, float *y, int B, int L, int D, int heads, int hidden, unsigned flags,
                                   void *stream) {
-    const BlockPlan plan = plan_block(BlockEntry::forward_train, L, D, heads, hidden, flags);
-    if (plan.refusal) return block_refused(plan);
     const BlockWeights w{norm1_weight, norm1_bias, Wqkv, bqkv, Wproj, bproj, norm2_weight, norm2_bias, W1, b1, W2, b2};
-    if (!x || !w.present() || !y || !saved) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: null pointer");
-    if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: B = %d", B);
-    if (y == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_forward_train: y must not alias x");
-    if (!plan.covered) return block_unsupported(plan, L, D, heads, hidden, flags);
-    const BlockStore sv(saved, plan, B, L, D, hidden);
-    if (saved_bytes < sv.total)
-        return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_forward_train: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
-    return block_forward(plan, x, w, sv, scale1, scale2, eps, scale, y, B, L, D, heads, hidden, static_cast<hipStream_t>(stream));
+    return forward_train(BlockEntry::forward_train, x, w, scale1, scale2, BlockDrop{}, eps, scale, saved, saved_bytes, y, B, L, D,
+                         heads, hidden, flags, stream);
 }
 
 int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const float *norm1_bias, const float *Wqkv,
@@ -298,73 +424,46 @@ int stgcn_vit_block_backward(const float *x, const float *norm1_weight, const fl
                              float *dWproj, float *dbproj, float *dnorm2_weight, float *dnorm2_bias, float *dW1, float *db1,
                              float *dW2, float *db2, float eps, float scale, void *ws, size_t ws_bytes, int B, int L, int D,
                              int heads, int hidden, unsigned flags, void *stream) {
-    const BlockPlan plan = plan_block(BlockEntry::backward, L, D, heads, hidden, flags);
-    if (plan.refusal) return block_refused(plan);
-    if (!x || !norm1_weight || !norm1_bias || !Wqkv || !Wproj || !norm2_weight || !norm2_bias || !W1 || !W2 || !saved || !dy || !dx ||
-        !dnorm1_weight || !dnorm1_bias || !dWqkv || !dWproj || !dbproj || !dnorm2_weight || !dnorm2_bias || !dW1 || !db1 || !dW2 ||
-        !db2 || !ws)
-        return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: null pointer");
-    if (B < 1) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: B = %d", B);
-    if (dx == dy || dx == x) return fail(STGCN_ERR_ARG, "stgcn_vit_block_backward: dx must not alias dy or x");
-    if (!plan.covered) return block_unsupported(plan, L, D, heads, hidden, flags);
-    const BlockStore sv(const_cast<void *>(saved), plan, B, L, D, hidden);
-    if (saved_bytes < sv.total)
-        return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: saved buffer %zu < %zu bytes", saved_bytes, sv.total);
-    const TrainWs tw(ws, plan, B, L, D, heads, hidden);
-    if (ws_bytes < tw.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_block_backward: workspace %zu < %zu bytes", ws_bytes, tw.total);
-    const BackwardWs &w = tw.w;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned math = plan.lin_dgrad, math_qkv = plan.qkv_dgrad;
-    int rc;
-    if ((rc = launch_transpose_pad(Wqkv, w.wt_qkv, 3 * D, D, 3 * D, st))) return rc;
-    if ((rc = launch_transpose_pad(Wproj, w.wt_proj, D, D, D, st))) return rc;
-    if ((rc = launch_transpose_pad(W1, w.wt_fc1, hidden, D, hidden, st))) return rc;
-    if ((rc = launch_transpose_pad(W2, w.wt_fc2, D, hidden, D, st))) return rc;
-    const int per = slab_seqs(B, L);
-    for (int b0 = 0; b0 < B; b0 += per) {
-        const int nb = B - b0 < per ? B - b0 : per;
-        const int M = nb * L;
-        const size_t r0 = (size_t)b0 * L;
-        const bool acc = b0 > 0;
-        const float *xs = x + r0 * D, *dys = dy + r0 * D;
-        const float *qkv = (const float *)sv.qkv + r0 * 3 * D, *att = (const float *)sv.att + r0 * D, *x1 = sv.x1 + r0 * D;
-        const float *hpre = sv.hpre + r0 * hidden, *hid = (const float *)sv.hid + r0 * hidden;
-        const float *s1 = scale1 != nullptr ? scale1 + b0 : nullptr, *s2 = scale2 != nullptr ? scale2 + b0 : nullptr;
-        LinearExtra e2, e1;
-        e2.dgelu = hpre;
-        e2.rowscale = s2;
-        e1.rowscale = s1;
-        e1.L = e2.L = L;
-        // MLP branch
-        if ((rc = launch_linear(dys, w.wt_fc2, nullptr, nullptr, nullptr, nullptr, 0.f, w.dhid, M, D, hidden, false, math, st, e2)))
-            return rc;
-        if ((rc = wgrad(plan, dys, hid, s2, L, dW2, db2, w.part, w.tmp, M, hidden, D, acc, st))) return rc;
-        if ((rc = launch_linear(w.dhid, w.wt_fc1, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, hidden, D, false, math, st)))
-            return rc;
-        if ((rc = launch_ln_backward(x1, w.dn, norm2_weight, norm2_bias, eps, dys, w.dx1, w.a, w.stats, M, D, st))) return rc;
-        if ((rc = launch_ln_param_grad(x1, w.dn, w.stats, dnorm2_weight, dnorm2_bias, w.part, w.tmp, M, D, acc, st))) return rc;
-        if ((rc = wgrad(plan, w.dhid, w.a, nullptr, L, dW1, db1, w.part, w.tmp, M, D, hidden, acc, st))) return rc;
-        // attention branch
-        if ((rc = launch_linear(w.dx1, w.wt_proj, nullptr, nullptr, nullptr, nullptr, 0.f, w.datt, M, D, D, false, math, st, e1)))
-            return rc;
-        if ((rc = wgrad(plan, w.dx1, att, s1, L, dWproj, dbproj, w.part, w.tmp, M, D, D, acc, st))) return rc;
-        switch (plan.attention) {
-            case BlockAttention::stream:
-                rc = launch_attention_backward_stream(qkv, att, w.datt, w.dqkv, tw.att_stats, nb, L, heads, D / heads, scale, st);
-                break;
-            case BlockAttention::resident_train_bf16:
-                rc = launch_attention_backward_bf16(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st);
-                break;
-            default: rc = launch_attention_backward(qkv, att, w.datt, w.dqkv, nb, L, heads, D / heads, scale, st); break;
-        }
-        if (rc) return rc;
-        if ((rc = launch_linear(w.dqkv, w.wt_qkv, nullptr, nullptr, nullptr, nullptr, 0.f, w.dn, M, 3 * D, D, false, math_qkv, st)))
-            return rc;
-        if ((rc = launch_ln_backward(xs, w.dn, norm1_weight, norm1_bias, eps, w.dx1, dx + r0 * D, w.a, w.stats, M, D, st))) return rc;
-        if ((rc = launch_ln_param_grad(xs, w.dn, w.stats, dnorm1_weight, dnorm1_bias, w.part, w.tmp, M, D, acc, st))) return rc;
-        if ((rc = wgrad(plan, w.dqkv, w.a, nullptr, L, dWqkv, dbqkv, w.part, w.tmp, M, D, 3 * D, acc, st))) return rc;
-    }
-    return STGCN_OK;
+    const BlockWeights w{norm1_weight, norm1_bias, Wqkv, nullptr, Wproj, nullptr, norm2_weight, norm2_bias, W1, nullptr, W2, nullptr};
+    const BlockGrads g{dnorm1_weight, dnorm1_bias, dWqkv, dbqkv, dWproj, dbproj, dnorm2_weight, dnorm2_bias, dW1, db1, dW2, db2};
+    return backward(BlockEntry::backward, x, w, scale1, scale2, BlockDrop{}, saved, saved_bytes, dy, dx, g, eps, scale, ws, ws_bytes,
+                    B, L, D, heads, hidden, flags, stream);
+}
+
+// ---- the pair with per-element dropout (include/stgcn_hip.h, "ViT block: training with dropout") ---------------------------
+// The same forward_train and backward as above under the two _drop entries of the plan, which differ in one thing: a
+// STGCN_VIT_TILE_* field is legal and reaches every forward and dgrad linear.  The masks ride in the linears' epilogues
+// (LinearExtra::mask) and, in the backward, in two launch_mask_mul passes; with no mask and no tile field nothing else runs
+// than what the older pair runs.
+int stgcn_vit_block_train_drop_supported(int L, int D, int heads, int hidden) {
+    return plan_block(BlockEntry::forward_train_drop, L, D, heads, hidden, 0).covered ? 1 : 0;
+}
+
+size_t stgcn_vit_block_train_drop_ws_bytes(int B, int L, int D, int heads, int hidden) {
+    const BlockPlan p = plan_block(BlockEntry::backward_drop, L, D, heads, hidden, 0);
+    return B >= 1 && p.covered ? TrainWs(nullptr, p, B, L, D, heads, hidden).total : 0;
+}
+
+int stgcn_vit_block_forward_train_drop(const float *x, const stgcn_vit_block_weights *weights, const float *scale1,
+                                       const float *scale2, const stgcn_vit_drop_masks *masks, float eps, float scale,
+                                       void *saved, size_t saved_bytes, float *y, int B, int L, int D, int heads, int hidden,
+                                       unsigned flags, void *stream) {
+    const BlockWeights w = weights != nullptr ? block_weights(*weights) : BlockWeights{};
+    return forward_train(BlockEntry::forward_train_drop, x, w, scale1, scale2, block_drop(masks), eps, scale, saved, saved_bytes, y,
+                         B, L, D, heads, hidden, flags, stream);
+}
+
+int stgcn_vit_block_backward_drop(const float *x, const stgcn_vit_block_weights *weights, const float *scale1,
+                                  const float *scale2, const stgcn_vit_drop_masks *masks, const void *saved, size_t saved_bytes,
+                                  const float *dy, float *dx, const stgcn_vit_block_grads *grads, float eps, float scale, void *ws,
+                                  size_t ws_bytes, int B, int L, int D, int heads, int hidden, unsigned flags, void *stream) {
+    const BlockWeights w = weights != nullptr ? block_weights(*weights) : BlockWeights{};
+    const BlockGrads g = grads != nullptr ? BlockGrads{grads->norm1_weight, grads->norm1_bias, grads->Wqkv, grads->bqkv, grads->Wproj,
+                                                       grads->bproj, grads->norm2_weight, grads->norm2_bias, grads->W1, grads->b1,
+                                                       grads->W2, grads->b2}
+                                          : BlockGrads{};
+    return backward(BlockEntry::backward_drop, x, w, scale1, scale2, block_drop(masks), saved, saved_bytes, dy, dx, g, eps, scale, ws,
+                    ws_bytes, B, L, D, heads, hidden, flags, stream);
 }
 
 }  // extern "C"

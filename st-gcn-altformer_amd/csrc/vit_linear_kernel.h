@@ -312,6 +312,7 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const void *__re
                     const float h = ex.dgelu[idx];
                     v *= 0.5f * (1.0f + erff(h * kRsqrt2)) + h * 0.39894228040143267794f * __expf(-0.5f * h * h);
                 }
+                if (ex.mask != nullptr) v *= ex.mask[idx];
                 if (ex.rowscale != nullptr) v *= ex.rowscale[row / ex.L];
                 if (R != nullptr) v += R[idx];
                 if constexpr (YB) bf16k::store_out<true>(Yv, idx, v);

@@ -59,6 +59,15 @@ class VitBlockWeights(ctypes.Structure):
                                   "W1", "b1", "W2", "b2")]
 
 
+# the structs of the training pair with dropout (include/stgcn_hip.h, "ViT block: training with dropout")
+class VitBlockGrads(ctypes.Structure):
+    _fields_ = VitBlockWeights._fields_
+
+
+class VitDropMasks(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("m_proj", "m_act", "m_fc2")]
+
+
 class AltformerHeadShape(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("N", "T", "V", "C", "E1", "E2", "heads", "hidden1", "hidden2", "depth1", "depth2", "classes")]
 
@@ -166,6 +175,13 @@ PROTOTYPES = {
     "stgcn_vit_block_forward_train": (c_int, [_P] * 15 + [c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
     "stgcn_vit_block_backward": (c_int, [_P] * 12 + [c_size_t] + [_P] * 14 + [c_float, c_float, _P, c_size_t] + [c_int] * 5
                                  + [c_uint, _P]),
+    "stgcn_vit_block_train_drop_supported": (c_int, [c_int] * 4),
+    "stgcn_vit_block_train_drop_ws_bytes": (c_size_t, [c_int] * 5),
+    "stgcn_vit_block_forward_train_drop": (c_int, [_P, ctypes.POINTER(VitBlockWeights), _P, _P, ctypes.POINTER(VitDropMasks),
+                                                   c_float, c_float, _P, c_size_t, _P] + [c_int] * 5 + [c_uint, _P]),
+    "stgcn_vit_block_backward_drop": (c_int, [_P, ctypes.POINTER(VitBlockWeights), _P, _P, ctypes.POINTER(VitDropMasks), _P, c_size_t,
+                                              _P, _P, ctypes.POINTER(VitBlockGrads), c_float, c_float, _P, c_size_t] + [c_int] * 5
+                                      + [c_uint, _P]),
 }
 
 _lib = None

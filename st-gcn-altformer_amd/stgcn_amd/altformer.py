@@ -178,9 +178,10 @@ def set_hip_min_tokens(module: nn.Module, tokens: int) -> None:
 
 
 def set_hip_train_min_tokens(module: nn.Module, tokens: int) -> None:
-    """The token count (B * L) from which every ``Block`` below trains on the HIP kernels where they apply (0: always)."""
+    """The token count (B * L) from which every ``Block`` (and ST-ViT ``Layer``) below trains on the HIP kernels where they
+    apply (0: always)."""
     for sub in module.modules():
-        if isinstance(sub, Block):
+        if isinstance(sub, HipSwitches):
             sub.hip_train_min_tokens = int(tokens)
 
 
@@ -210,7 +211,7 @@ def set_train_attention_math(module: nn.Module, mode) -> None:
     if mode is not None and mode not in TRAIN_ATTENTION_MATH:
         raise KeyError(mode)
     for sub in module.modules():
-        if isinstance(sub, Block):
+        if isinstance(sub, HipSwitches):
             sub.train_attention_mode = mode
 
 
@@ -220,7 +221,7 @@ def set_train_math(module: nn.Module, mode) -> None:
     for what ``set_head_math`` / ``STGCN_VIT_TRAIN_MATH`` / ``DEFAULT_TRAIN_MATH`` give.  Inference is not touched."""
     m = None if mode is None else HEAD_TRAIN_MATH[mode] if isinstance(mode, str) else int(mode)
     for sub in module.modules():
-        if isinstance(sub, Block):
+        if isinstance(sub, HipSwitches):
             sub.train_math_mode = m
 
 
@@ -230,6 +231,7 @@ class HipSwitches:
     the front of the ST-ViT head (``stgcn_amd.vit``)."""
 
     DEFAULT_HIP_MIN_TOKENS = HIP_MIN_TOKENS
+    DEFAULT_HIP_TRAIN_MIN_TOKENS = HIP_TRAIN_MIN_TOKENS
     DEFAULT_SMALL_TILES = False
 
     def _init_switches(self):
@@ -238,7 +240,7 @@ class HipSwitches:
         self.train_attention_mode = None       # set_train_attention_math: 'f32' | 'bf16'; None: env STGCN_VIT_TRAIN_ATTENTION, else 'f32'
         self.force_torch = False               # diagnostics / timing: take the torch-op path even where the HIP path applies
         self.hip_min_tokens = self.DEFAULT_HIP_MIN_TOKENS   # set_hip_min_tokens
-        self.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
+        self.hip_train_min_tokens = self.DEFAULT_HIP_TRAIN_MIN_TOKENS   # set_hip_train_min_tokens
         self.hip_train_max_len = HIP_TRAIN_MAX_LEN         # set_long_training
         self.small_tiles = self.DEFAULT_SMALL_TILES   # set_low_latency: the inference linears pick their tile form by call size
         self.split_attention = False           # set_low_latency(split_attention=True): VIT_ATTN_SPLIT on the inference word
@@ -255,6 +257,21 @@ class HipSwitches:
         if self.split_attention:
             math |= VIT_ATTN_SPLIT
         return math
+
+
+    def _train_flags(self, tiles: bool = False) -> int:
+        """The flag word of a training call (``Block._hip_flags`` describes the resolution).  ``tiles``: the caller's entry
+        points take a tile field (the ST-ViT ``Layer``'s ``_drop`` pair; a ``Block``'s refuse one), so ``small_tiles`` adds
+        ``VIT_TILE_AUTO`` to the word."""
+        attn = self.train_attention_mode if self.train_attention_mode is not None else _default_train_attention()
+        bit = VIT_TRAIN_ATTN_BF16 if attn == "bf16" else 0
+        if tiles and self.small_tiles:
+            bit |= VIT_TILE_AUTO
+        if self.train_math_mode is not None:
+            return self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16 | VIT_ATTN_SPLIT) | bit
+        if self.math_mode is None or self.math_mode & VIT_BF16:
+            return _default_train_math() | bit
+        return self.math_mode & ~(VIT_TILE_MASK | VIT_ATTN_SPLIT) | bit
 
 
 class DropPath(nn.Module):
@@ -326,24 +343,30 @@ def _drop_active(mod: nn.Module) -> bool:
 class _BlockTrain(torch.autograd.Function):
     """One Block on the HIP training kernels: ``stgcn_vit_block_forward_train`` / ``stgcn_vit_block_backward``.  The twelve
     parameters arrive as arguments (taken by attribute from the module), so the gradients of an ``nn.DataParallel`` replica's
-    clones flow back to its master through autograd like any other op's."""
+    clones flow back to its master through autograd like any other op's.  Three more tensors behind the twelve are the
+    per-element dropout factors (m_proj, m_act, m_fc2, each may be None) of an ST-ViT ``Layer`` (``stgcn_amd.vit``): the call then
+    goes to the ``_drop`` pair of entry points, which also takes a tile field in ``math``."""
 
     @staticmethod
     def forward(ctx, x, s1, s2, heads, eps, scale, math, *params):
+        twelve = len(F.VIT_BLOCK_PARAMS)
+        params, drop = params[:twelve], (tuple(params[twelve:]) if len(params) > twelve else None)
         x = x.contiguous()
-        y, saved = F.vit_block_forward_train(x, params, heads, eps, scale, math, s1, s2)
-        ctx.save_for_backward(x, s1, s2, *params)
+        y, saved = F.vit_block_forward_train(x, params, heads, eps, scale, math, s1, s2, drop=drop)
+        ctx.save_for_backward(x, s1, s2, *params, *(drop or ()))
         ctx.saved_buf, ctx.cfg = saved, (heads, eps, scale, math)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        x, s1, s2, *params = ctx.saved_tensors
+        twelve = len(F.VIT_BLOCK_PARAMS)
+        x, s1, s2, *rest = ctx.saved_tensors
+        params, drop = rest[:twelve], (tuple(rest[twelve:]) if len(rest) > twelve else None)
         heads, eps, scale, math = ctx.cfg
-        g = F.vit_block_backward(x, params, ctx.saved_buf, dy.contiguous(), heads, eps, scale, math, s1, s2)
+        g = F.vit_block_backward(x, params, ctx.saved_buf, dy.contiguous(), heads, eps, scale, math, s1, s2, drop=drop)
         ctx.saved_buf = None
-        return (g["x"], None, None, None, None, None, None) + tuple(g[n] for n in F.VIT_BLOCK_PARAMS)
+        return (g["x"], None, None, None, None, None, None) + tuple(g[n] for n in F.VIT_BLOCK_PARAMS) + (None,) * len(drop or ())
 
 
 class Block(nn.Module, HipSwitches):
@@ -427,13 +450,7 @@ class Block(nn.Module, HipSwitches):
         ``VIT_TRAIN_ATTN_BF16`` on top of any of them when it says ``'bf16'``, and nothing otherwise.
         Inference: ``HipSwitches._inference_flags`` (the training word never carries a tile form or ``VIT_ATTN_SPLIT``)."""
         if train:
-            attn = self.train_attention_mode if self.train_attention_mode is not None else _default_train_attention()
-            bit = VIT_TRAIN_ATTN_BF16 if attn == "bf16" else 0
-            if self.train_math_mode is not None:
-                return self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16 | VIT_ATTN_SPLIT) | bit
-            if self.math_mode is None or self.math_mode & VIT_BF16:
-                return _default_train_math() | bit
-            return self.math_mode & ~(VIT_TILE_MASK | VIT_ATTN_SPLIT) | bit
+            return self._train_flags()
         return self._inference_flags(x.shape[1], x.shape[2], self.attn.num_heads, self.mlp.fc1.out_features)
 
     def forward(self, x):

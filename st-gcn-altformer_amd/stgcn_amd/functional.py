@@ -6,6 +6,7 @@ outputs.  Nothing here computes on the host and nothing falls back to torch ops.
 """
 from __future__ import annotations
 
+import ctypes
 from ctypes import c_float, c_int, c_size_t, c_uint, c_void_p
 from typing import Optional, Tuple
 
@@ -1073,19 +1074,49 @@ VIT_BLOCK_PARAMS = ("norm1.weight", "norm1.bias", "qkv.weight", "qkv.bias", "pro
                     "norm2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
 
 
-def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=None, scale2=None):
+def vit_block_train_drop_supported(L, D, heads, hidden) -> bool:
+    """What ``vit_block_forward_train`` / ``vit_block_backward`` cover with ``drop``: ``vit_block_train_long_supported``."""
+    return bool(_capi.lib().stgcn_vit_block_train_drop_supported(L, D, heads, hidden))
+
+
+def _drop_struct(drop, x, hidden):
+    """``drop`` = (m_proj, m_act, m_fc2), each None or contiguous fp32 of (B, L, D) / (B, L, hidden) / (B, L, D), as the C struct."""
+    if len(drop) != 3:
+        raise ValueError("drop is (m_proj, m_act, m_fc2)")
+    B, L, D = x.shape
+    masks = _capi.VitDropMasks()
+    for (field, _), m, width in zip(_capi.VitDropMasks._fields_, drop, (D, hidden, D)):
+        if m is not None and (tuple(m.shape) != (B, L, width) or not m.is_contiguous()):
+            raise ValueError(f"{field}: expected a contiguous ({B}, {L}, {width}) tensor, got {tuple(m.shape)}")
+        setattr(masks, field, _dev_ptr(m, field, x.device))
+    return masks
+
+
+def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=None, scale2=None, drop=None):
     """Training forward of one Block on x (B, L, D): returns ``(y, saved)``.  ``params``: the twelve tensors in the order of
     ``VIT_BLOCK_PARAMS`` (qkv.bias may be None).  ``scale1`` / ``scale2`` (B,): stochastic depth's per-sequence factors of the
     attention and the MLP branch (None = 1).  ``saved`` is an opaque buffer for ``vit_block_backward``.
     ``math``: MATH_F32 or MATH_BF16X3, optionally | VIT_QKV_F32, optionally | VIT_TRAIN_BF16 (every linear product but the qkv
     forward on operands rounded to bf16), optionally | VIT_TRAIN_ATTN_BF16 (the attention forward and backward on bf16 operands
-    where L <= 256).  Hand the same value to ``vit_block_backward``."""
+    where L <= 256).  Hand the same value to ``vit_block_backward``.
+    ``drop`` = (m_proj, m_act, m_fc2): per-element dropout factors (0 or 1 / (1 - p), fp32, None = 1) behind the projection
+    (B, L, D), behind the GELU (B, L, hidden) and behind the second MLP linear (B, L, D).  With ``drop`` (a tuple, even of three
+    Nones) the call is ``stgcn_vit_block_forward_train_drop``, which also takes a VIT_TILE_* field in ``math`` (the tile form of
+    its linears; same result bit for bit); without, the older entry point, which refuses one."""
     dev = x.device
     B, L, D = x.shape
     hidden = params[8].shape[0]
     nbytes, _ = _vit_block_train_bytes(B, L, D, heads, hidden)
     saved = _bytes(dev, nbytes)
     y = torch.empty_like(x)
+    if drop is not None:
+        masks, weights = _drop_struct(drop, x, hidden), _block_structs([params], dev)
+        with torch.cuda.device(dev):
+            _capi.call("stgcn_vit_block_forward_train_drop", _dev_ptr(x, "x", dev), weights, _dev_ptr(scale1, "scale1", dev),
+                       _dev_ptr(scale2, "scale2", dev), ctypes.byref(masks), c_float(eps), c_float(scale),
+                       c_void_p(saved.data_ptr()), c_size_t(nbytes), _dev_ptr(y, "y"), c_int(B), c_int(L), c_int(D), c_int(heads),
+                       c_int(hidden), c_uint(_vit_train_flags(math)), _stream(dev))
+        return y, saved
     with torch.cuda.device(dev):
         _capi.call("stgcn_vit_block_forward_train", _dev_ptr(x, "x", dev),
                    *[_dev_ptr(p, n, dev) for n, p in zip(VIT_BLOCK_PARAMS, params)],
@@ -1095,19 +1126,33 @@ def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=
     return y, saved
 
 
-def vit_block_backward(x, params, saved, dy, heads, eps, scale, math=MATH_F32, scale1=None, scale2=None) -> dict:
-    """Backward of ``vit_block_forward_train`` (same arguments): ``{"x": dx, "norm1.weight": ..., ...}`` with a gradient for
-    ``x`` and for every entry of ``VIT_BLOCK_PARAMS`` (``qkv.bias``: None when the block has none)."""
+def vit_block_backward(x, params, saved, dy, heads, eps, scale, math=MATH_F32, scale1=None, scale2=None, drop=None) -> dict:
+    """Backward of ``vit_block_forward_train`` (same arguments, ``drop`` included): ``{"x": dx, "norm1.weight": ..., ...}`` with a
+    gradient for ``x`` and for every entry of ``VIT_BLOCK_PARAMS`` (``qkv.bias``: None when the block has none)."""
     dev = x.device
     B, L, D = x.shape
     hidden = params[8].shape[0]
     sbytes, nbytes = _vit_block_train_bytes(B, L, D, heads, hidden)
     if saved.numel() * saved.element_size() < sbytes:
         raise ValueError("saved does not come from vit_block_forward_train of these shapes")
+    if drop is not None:
+        nbytes = _capi.lib().stgcn_vit_block_train_drop_ws_bytes(B, L, D, heads, hidden)
     ws = _bytes(dev, nbytes)
     grads = {"x": torch.empty_like(x)}
     for n, p in zip(VIT_BLOCK_PARAMS, params):
         grads[n] = None if p is None else torch.empty_like(p)
+    if drop is not None:
+        masks, weights = _drop_struct(drop, x, hidden), _block_structs([params], dev)
+        gs = _capi.VitBlockGrads()
+        for (field, _), n in zip(_capi.VitBlockGrads._fields_, VIT_BLOCK_PARAMS):
+            setattr(gs, field, _dev_ptr(grads[n], "d" + n))
+        with torch.cuda.device(dev):
+            _capi.call("stgcn_vit_block_backward_drop", _dev_ptr(x, "x", dev), weights, _dev_ptr(scale1, "scale1", dev),
+                       _dev_ptr(scale2, "scale2", dev), ctypes.byref(masks), c_void_p(saved.data_ptr()), c_size_t(sbytes),
+                       _dev_ptr(dy, "dy", dev), _dev_ptr(grads["x"], "dx"), ctypes.byref(gs), c_float(eps), c_float(scale),
+                       c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(B), c_int(L), c_int(D), c_int(heads), c_int(hidden),
+                       c_uint(_vit_train_flags(math)), _stream(dev))
+        return grads
     w = dict(zip(VIT_BLOCK_PARAMS, params))
     with torch.cuda.device(dev):
         _capi.call("stgcn_vit_block_backward", _dev_ptr(x, "x", dev),

@@ -17,8 +17,19 @@ Two paths, one result:
   agrees and the call has at least ``hip_min_tokens`` tokens (N times n + 1).  A layer needs ``heads * dim_head == dim`` and a
   projecting ``to_out``; ``heads == 1 and dim_head == dim`` (``to_out`` is the identity) runs on torch ops.
   ``ViT.uses_hip(z)`` says whether a call runs on HIP from the stem output to the logits.
-* torch ops: everything else, and everything under autograd (training the ViT on HIP is not covered).  This is the
-  reference's arithmetic op for op.
+* HIP, training (``functional.vit_block_forward_train`` / ``vit_block_backward`` with ``drop=``, behind the blocks' one
+  ``autograd.Function``): a layer whose call autograd records, of the structure above with plain ``nn.Dropout``s, a covered
+  shape and at least ``hip_train_min_tokens`` tokens, env ``STGCN_VIT_TRAIN`` not ``0`` (``Layer.trains_on_hip(x)``;
+  ``ViT.trains_on_hip(z)``: every layer).  The layer's three dropouts - behind ``to_out``, behind the GELU, behind the second
+  MLP linear, all live in ``.train()`` at the reference's ``dropout = 0.1`` - are per-element fp32 factors that
+  ``Layer.draw_dropout`` draws with the torch path's generator calls in its order and the kernels apply, so a seed gives both
+  paths the same masks (held on the GPU by tests/test_stvit_train_gpu.py).  ``.eval()`` with gradients: the same branch, no
+  masks.  The flag word is the blocks' training word (``set_train_math``, ``set_train_attention_math``, the env defaults) plus
+  ``VIT_TILE_AUTO`` where ``small_tiles`` is set.  The embedding and the pooled classifier are torch ops under autograd (one
+  GEMM each, ``emb_dropout = 0``); ``uses_hip`` keeps meaning inference.  The parameters go by attribute, so an
+  ``nn.DataParallel`` replica's gradients reach its master.  By default a ViT call is under the threshold: see
+  ``VIT_HIP_TRAIN_MIN_TOKENS``.
+* torch ops: everything else.  This is the reference's arithmetic op for op.
 
 The switches of ``stgcn_amd.altformer`` act here as they do on its ``Block``s (``ViT`` and every ``Layer`` are
 ``HipSwitches``): ``set_head_math`` ('f32' | 'bf16x3' | 'mixed' | 'bf16'; the patch embedding has no bf16 form and runs bf16x3
@@ -29,11 +40,13 @@ Defaults (``VIT_HIP_MIN_TOKENS``, ``VIT_SMALL_TILES``): see the comment there fo
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
 from . import functional as F
-from .altformer import HipSwitches, _default_head_math, _drop_active
+from .altformer import HIP_TRAIN_MIN_TOKENS, HipSwitches, _BlockTrain, _default_head_math, _drop_active
 
 # The defaults of a new ViT: the token count (N * (n + 1)) from which its pieces run on HIP, and whether the layers' linears
 # pick their tile form by call size.  MEASURED (profiles/stvit_times.json, tools/time_stvit.py: stem + ViT at 180 x 22, batch
@@ -44,6 +57,16 @@ from .altformer import HipSwitches, _default_head_math, _drop_active
 # measured ones are not measured.
 VIT_HIP_MIN_TOKENS = 0
 VIT_SMALL_TILES = True
+# The token count from which a Layer TRAINS on HIP, and the tile forms it trains with.  MEASURED (profiles/stvit_train_times.json,
+# tools/time_stvit_train.py: stem + ViT at 180 x 22, dropout 0.1, .train(), one step = forward, CrossEntropyLoss, backward; batch
+# 8, 32, 128 = 800, 3,200, 12,800 tokens).  In the default training arithmetic 'f32' with the small-tile forms the step is
+# faster than torch ops by more than the spread at 800 tokens (1.39 x), and a tie at 3,200 (1.04 x) and at 12,800 (1.03 x); with
+# 128 x 128 tiles it is a tie, slower (0.78 x) and a tie.  No measured count from which every measured count wins, so by the
+# project's rule the threshold stays at the blocks' HIP_TRAIN_MIN_TOKENS and a ViT at any measured batch trains on torch ops
+# unless set_hip_min_tokens(model, 0) (or set_hip_train_min_tokens) lifts it.  Who lifts it gets the small forms, which are
+# never behind the 128 x 128 ones by more than the spread: VIT_SMALL_TILES holds for training too.  With
+# set_train_math(model, 'bf16') and the small forms the HIP step wins at every measured count (1.52 x, 1.19 x, 1.31 x).
+VIT_HIP_TRAIN_MIN_TOKENS = HIP_TRAIN_MIN_TOKENS
 
 
 def _records_grad(x, tensors) -> bool:
@@ -110,6 +133,7 @@ class Layer(nn.ModuleList, HipSwitches):
     a block: ``x = attn(x) + x`` then ``x = ff(x) + x``."""
 
     DEFAULT_HIP_MIN_TOKENS = VIT_HIP_MIN_TOKENS
+    DEFAULT_HIP_TRAIN_MIN_TOKENS = VIT_HIP_TRAIN_MIN_TOKENS
     DEFAULT_SMALL_TILES = VIT_SMALL_TILES
 
     def __init__(self, attn, ff):
@@ -138,23 +162,72 @@ class Layer(nn.ModuleList, HipSwitches):
         return (n1.weight, n1.bias, a.to_qkv.weight, None, a.to_out[0].weight, a.to_out[0].bias, n2.weight, n2.bias,
                 net[0].weight, net[0].bias, net[3].weight, net[3].bias)
 
-    def hip_applies(self, x: torch.Tensor) -> bool:
-        """Whether this call can run on ``stgcn_vit_block_forward`` (see the module docstring)."""
+    def _shaped(self, x):
+        """``_parts()`` where x is CUDA float32 (B, L, D) and the layer's sizes are the block's (one width D throughout,
+        ``heads * dim_head == D``), else None."""
         if self.force_torch or not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
-            return False
+            return None
         parts = self._parts()
         if parts is None:
-            return False
+            return None
         n1, a, n2, net = parts
         B, L, D = x.shape
         inner = a.to_out[0].in_features
         if (B < 1 or n1.normalized_shape != (D,) or n2.normalized_shape != (D,) or inner != D or a.to_qkv.out_features != 3 * D
                 or inner % a.heads or net[3].out_features != D
                 or net[3].in_features != net[0].out_features):
+            return None
+        return parts
+
+    def hip_applies(self, x: torch.Tensor) -> bool:
+        """Whether this call can run on ``stgcn_vit_block_forward`` (see the module docstring)."""
+        parts = self._shaped(x)
+        if parts is None:
             return False
+        _, a, _, net = parts
         if _records_grad(x, self._weights(parts)) or _drop_active(self):
             return False
-        return F.vit_block_forward_supported(L, D, a.heads, net[0].out_features)
+        return F.vit_block_forward_supported(x.shape[1], x.shape[2], a.heads, net[0].out_features)
+
+    def _dropouts(self, parts):
+        """The layer's three dropouts in the order the torch path runs them: behind ``to_out``, behind the GELU, behind the
+        second MLP linear."""
+        _, a, _, net = parts
+        return a.to_out[1], net[2], net[4]
+
+    def trains_on_hip(self, x: torch.Tensor) -> bool:
+        """Whether this call runs on the HIP training kernels (``stgcn_vit_block_forward_train_drop`` now,
+        ``stgcn_vit_block_backward_drop`` on ``loss.backward()``): autograd records something that concerns the layer, env
+        ``STGCN_VIT_TRAIN`` is not ``0``, the layer is the structure ``_parts()`` accepts with plain ``nn.Dropout``s (active or
+        not: the kernels apply their masks), the shape is covered and the call has at least ``hip_train_min_tokens`` tokens."""
+        if os.environ.get("STGCN_VIT_TRAIN", "1") == "0":
+            return False
+        parts = self._shaped(x)
+        if parts is None or not _records_grad(x, self._weights(parts)):
+            return False
+        if x.shape[0] * x.shape[1] < self.hip_train_min_tokens:
+            return False
+        if len(parts[1].to_out) != 2 or any(type(d) is not nn.Dropout for d in self._dropouts(parts)):
+            return False
+        return F.vit_block_train_drop_supported(x.shape[1], x.shape[2], parts[1].heads, parts[3][0].out_features)
+
+    def draw_dropout(self, x: torch.Tensor):
+        """The three dropout masks of this call, (m_proj (B, L, D), m_act (B, L, hidden), m_fc2 (B, L, D)): fp32 factors, 0 or
+        1 / (1 - p), each None where that ``nn.Dropout`` is not training or has ``p == 0``.  Each is
+        ``torch.nn.functional.dropout(ones, p, True)`` of the shape the torch path's dropout sees, drawn in the torch path's
+        order (``to_out[1]``, ``net[2]``, ``net[4]``), so after the same seed both paths use the same masks: on the CPU
+        ``dropout(t) == t * dropout(ones)`` holds exactly, and tests/test_stvit_train_gpu.py holds the two paths of a model
+        against each other on the GPU under one seed."""
+        parts = self._parts()
+        B, L, D = x.shape
+        hidden = parts[3][0].out_features
+        masks = []
+        for drop, width in zip(self._dropouts(parts), (D, hidden, D)):
+            if not drop.training or drop.p == 0:
+                masks.append(None)
+            else:
+                masks.append(nn.functional.dropout(torch.ones((B, L, width), device=x.device, dtype=x.dtype), drop.p, True))
+        return tuple(masks)
 
     def uses_hip(self, x: torch.Tensor) -> bool:
         """``hip_applies`` and the call has at least ``hip_min_tokens`` tokens."""
@@ -171,6 +244,10 @@ class Layer(nn.ModuleList, HipSwitches):
             with torch.no_grad():
                 return F.vit_block_forward(x.contiguous(), w[0:2], w[2:4], w[4:6], w[6:8], w[8:10], w[10:12], parts[1].heads,
                                            parts[0].eps, parts[1].scale, self._hip_flags(x))
+        if self.trains_on_hip(x):
+            parts = self._parts()
+            return _BlockTrain.apply(x, None, None, parts[1].heads, parts[0].eps, parts[1].scale, self._train_flags(tiles=True),
+                                     *self._weights(parts), *self.draw_dropout(x))
         attn, ff = self
         x = attn(x) + x
         return ff(x) + x
@@ -293,6 +370,18 @@ class ViT(nn.Module, HipSwitches):
             return False
         probe = z.as_strided((z.shape[0], tokens, self.to_patch_embedding[1].out_features), (0, 0, 0))   # the shape without memory
         return all(isinstance(layer, Layer) and layer.uses_hip(probe) for layer in self.transformer.layers) and self.head_on_hip(probe)
+
+    def trains_on_hip(self, z) -> bool:
+        """Whether every layer of ``forward(z)`` trains on the HIP kernels (``Layer.trains_on_hip``).  The embedding and the
+        pooled classifier are torch ops under autograd either way."""
+        tokens = self._embed_tokens(z)
+        if tokens is None or not len(self.transformer.layers):
+            return False
+        lin = self.to_patch_embedding[1]
+        probe = z.as_strided((z.shape[0], tokens, lin.out_features), (0, 0, 0))   # the shape without memory
+        if torch.is_grad_enabled() and any(p.requires_grad for p in (lin.weight, self.cls_token, self.pos_embedding)):
+            probe = probe.detach().requires_grad_()   # what the embedding hands the first layer under autograd
+        return all(isinstance(layer, Layer) and layer.trains_on_hip(probe) for layer in self.transformer.layers)
 
     def forward(self, img):
         return self.classify(self.transformer(self.embed(img)))
