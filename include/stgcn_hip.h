@@ -653,7 +653,7 @@ int stgcn_altformer_head_forward(const float *z, const stgcn_altformer_head_weig
                                  unsigned head_flags, void *stream);
 
 /* ---- The ST-ViT head: patch embedding with class token, class-token pooling (additive to ABI 11: one flag bit, one entry
- * point, three queries; inference only) ----
+ * point, three queries; inference - the backwards are further down, "training the two ends") ----
  * model/ST_Vit/trans.py (ViT) after the stem, eval forward: patch embedding -> class row -> + position table -> depth blocks
  * (stgcn_vit_block_forward: the same pre-norm block, qkv without bias, LayerNorm eps 1e-5) -> class token or mean over the
  * tokens -> LayerNorm -> Linear (stgcn_vit_pool_classify).
@@ -729,6 +729,53 @@ int stgcn_vit_block_backward_drop(const float *x, const stgcn_vit_block_weights 
                                   const float *scale2, const stgcn_vit_drop_masks *masks, const void *saved, size_t saved_bytes,
                                   const float *dy, float *dx, const stgcn_vit_block_grads *grads, float eps, float scale, void *ws,
                                   size_t ws_bytes, int B, int L, int D, int heads, int hidden, unsigned flags, void *stream);
+
+/* ---- The ST-ViT head: training the two ends (additive to ABI 11: two entry points, five queries) ----
+ * The backward of stgcn_vit_patch_embed and of stgcn_vit_pool_classify.  Their forwards in training are those two entry points
+ * themselves, unchanged; both backwards recompute what they need from the forward's inputs, so nothing is saved.
+ *
+ * stgcn_vit_patch_embed_backward: z, W, the dimensions and the flags are the forward's (STGCN_IN_NTVC: z and dz are
+ * (N, T, V, C), else (N, C, T, V)); dx (N, n + 1, E) is the gradient of the forward's x.  With dx_tokens the N n patch rows of dx
+ * (row i (n + 1) + 1 + p for patch p of clip i; the class rows reach dcls and dpos only) and patches the rows of the forward:
+ *     dW (E, K)       = dx_tokens^T . patches          dbias (E) = the column sums of dx_tokens
+ *     dz (as z)       = dx_tokens . W, element k of patch (a, b) stored where the forward read it
+ *     dpos (n + 1, E) = sum over the clips of dx[i]     dcls (E)  = sum over the clips of dx[i][0]
+ * Each of the five outputs is optional (NULL: not wanted); what an output holds does not depend on which others were asked for.
+ * dW: the fp32 weight-gradient kernel of the blocks (128 x 128 tiles of dW, chunks of 32 tokens, v_mfma_f32_32x32x2_f32, in
+ * every math mode) with its A operand read in place from the (N, T, V, C) tensor; the tokens are cut into
+ * stgcn_vit_patch_embed_backward_cut's splits (returns (tokens per split << 16) | splits; 0 if not covered, and for a split of
+ * 32,768 tokens or more, which the word cannot hold and the call still runs), whose slabs are added in split order.  dz: the linears' tile kernel on the weight transposed once into the workspace, f32 or bf16x3 as the
+ * math bits say, fp32 accumulate; every element of z belongs to exactly one patch, so dz is written whole - the caller
+ * zero-fills nothing.  No (N, n, K) tensor exists at any point; (N, C, T, V) input costs one transposing pass of z (for dW) and
+ * one of dz, through the workspace.  The sums over the clips run in clip order.  No atomics: two runs are bit-identical.
+ * Covered: what stgcn_vit_patch_embed covers, E % 4 == 0 and E K < 2^31.  z, W, dx and ws 16-byte aligned; dz must not be z.
+ * Order of the answers: flags, then pointers / dimensions / alignment (STGCN_ERR_ARG), then coverage (STGCN_ERR_UNSUPPORTED),
+ * then the workspace (STGCN_ERR_WORKSPACE; stgcn_vit_patch_embed_backward_ws_bytes, 0 if not covered, sized for all outputs);
+ * nothing is launched before all four passed.  At most 8 launches on `stream`, the caller's buffers, no allocation, no
+ * synchronisation.
+ *
+ * stgcn_vit_pool_classify_backward: x, the LayerNorm, W and the flags are the forward's; dlogits (N, classes).
+ *     p = x[:, 0] (STGCN_VIT_POOL_CLS) or the mean over the L tokens;  xhat = (p - mean(p)) rstd;  y = xhat ln_weight + ln_bias
+ *     g = dlogits W       dW (classes, D) = dlogits^T y       dbias (classes) = the column sums of dlogits
+ *     dln_weight = sum over the clips of g xhat                dln_bias = sum over the clips of g
+ *     dp = rstd (g ln_weight - mean(g ln_weight) - xhat mean(g ln_weight xhat))
+ *     dx (N, L, D): STGCN_VIT_POOL_CLS: row 0 of every clip = dp, rows 1 .. L - 1 written as zeros; mean: every row = dp / L
+ * Each of the five outputs is optional (NULL: not wanted).  dx is written whole by the kernel: the caller zero-fills nothing.
+ * fp32, one workgroup per clip recomputing the pooled row and its statistics, the sums over the clips in clip order, no
+ * atomics.  STGCN_VIT_POOL_MAX: STGCN_ERR_UNSUPPORTED (with STGCN_VIT_POOL_CLS: STGCN_ERR_ARG, as in the forward).  Covered:
+ * what the forward covers (D % 64 == 0, D <= 4096).  x, dx and ws 16-byte aligned; dx must not be x.  The answers come in the
+ * order above; ws: stgcn_vit_pool_classify_backward_ws_bytes (3 N D floats; 0 if not covered).  At most 4 launches. */
+int stgcn_vit_patch_embed_backward_supported(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags);
+size_t stgcn_vit_patch_embed_backward_ws_bytes(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags);
+int stgcn_vit_patch_embed_backward_cut(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags);
+int stgcn_vit_patch_embed_backward(const float *z, const float *W, const float *dx, float *dW, float *dbias, float *dcls,
+                                   float *dpos, float *dz, int N, int C, int T, int V, int p1, int p2, int E, void *ws,
+                                   size_t ws_bytes, unsigned flags, void *stream);
+int stgcn_vit_pool_classify_backward_supported(int N, int L, int D, int classes, unsigned flags);
+size_t stgcn_vit_pool_classify_backward_ws_bytes(int N, int L, int D, int classes, unsigned flags);
+int stgcn_vit_pool_classify_backward(const float *x, const float *ln_weight, const float *ln_bias, float ln_eps, const float *W,
+                                     const float *dlogits, float *dx, float *dln_weight, float *dln_bias, float *dW, float *dbias,
+                                     int N, int L, int D, int classes, void *ws, size_t ws_bytes, unsigned flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -425,6 +425,87 @@ struct PatchStore {
 int launch_patch_embed_vit(const PatchPlan &p, const PatchStore &store, const float *z, const float *W, const float *bias,
                            const float *cls, const float *pos, float *x, int N, int C, int T, int V, int p1, int p2, int E,
                            hipStream_t st);
+// zt (N, P, C) = z (N, C, P)^T per clip: the pass that brings (N, C, T, V) input to the layout the patches are read from
+// (P = T V), and, with C and P exchanged, the one that takes the patches' gradient back (vit_patch.hip).
+int launch_patch_transpose(const float *z, float *zt, int N, int C, int P, hipStream_t st);
+
+// ---- the backward of that embedding (vit_patch_backward.hip) ---------------------------------------------------------------
+// From dx (N, n + 1, E), the gradient of the embedding's output; each output optional:
+//   dW (E, K)   = dx_tokens^T patches      vit_wgrad_kernel on PatchWgradRows: the A operand read in place from z, the dY rows
+//   dbias (E)   = column sums of dx_tokens   skipping the class rows; token splits into slabs, launch_sum_parts adds them
+//   dz          = dx_tokens W              vit_linear_kernel on PatchGradRows: the weight transposed once into the workspace,
+//                                          the epilogue stores into z's (N, T, V, C) layout, every element written once
+//   dpos (n + 1, E), dcls (E)              sums over the clips in clip order, one thread per element
+// dx_tokens: the N n patch rows of dx.  No (N, n, K) tensor exists; (N, C, T, V) input is transposed into the workspace for
+// the wgrad and dz is transposed back from it, mirroring the forward.  The plan, decided here and nowhere else
+// (stgcn_vit_patch_embed_backward, .._supported, .._ws_bytes and .._cut read it): the forward's coverage plus E % 4 == 0 (the
+// dgrad reads dx's rows with 16-byte loads); the wgrad's token splits by wgrad_rows_per_split, the blocks' rule; the dgrad's
+// tile by STGCN_VIT_TILE_AUTO's rule (the forms agree bit for bit).
+struct PatchBackwardPlan {
+    const char *refusal = nullptr;   // a flag bit this entry point does not know (STGCN_ERR_ARG)
+    bool shaped = false;             // as PatchPlan
+    bool covered = false;
+    bool transpose = false;          // z and dz are (N, C, T, V)
+    unsigned math = 0;               // of the dgrad; the wgrad is fp32 matrix cores always
+    int n = 0, w = 0, K = 0, M = 0;
+    int Epad = 0;                    // E rounded up to the linear's chunk: the dgrad's contraction length
+    int rps = 0, splits = 0;         // the wgrad's tokens per split and splits
+    LinearTile tile{0, 0};           // the dgrad's
+};
+
+inline PatchBackwardPlan plan_patch_backward(int N, int C, int T, int V, int p1, int p2, int E, unsigned flags) {
+    PatchBackwardPlan b;
+    const PatchPlan f = plan_patch(N, C, T, V, p1, p2, E, flags);
+    b.refusal = f.refusal, b.shaped = f.shaped, b.transpose = f.transpose, b.math = f.math;
+    b.n = f.n, b.w = f.w, b.K = f.K, b.M = f.M;
+    if (!f.shaped || !f.covered || E % 4 != 0 || (long long)E * f.K >= (1ll << 31)) return b;
+    b.Epad = ceil_div(E, 32) * 32;
+    b.rps = wgrad_rows_per_split(b.M, b.K, E);
+    b.splits = ceil_div(b.M, b.rps);
+    b.tile = linear_tile(b.M, b.Epad, b.K, STGCN_VIT_TILE_AUTO);
+    b.covered = true;
+    return b;
+}
+
+// The workspace of the backward, one carve, sized for all outputs: for (N, C, T, V) input one buffer of z's size, which holds
+// the transposed copy of z while the wgrad reads it and then the gradient before it is transposed back (the launches follow
+// each other on one stream: the dgrad, which writes it whole, starts after the wgrad has finished); the transposed weight; the
+// wgrad's slabs (dW's, then dbias').
+struct PatchBackwardStore {
+    float *zt, *dzt, *Wt, *part;
+    size_t total;
+    PatchBackwardStore(void *base, const PatchBackwardPlan &p, int N, int C, int T, int V, int E) {
+        Carve c(base);
+        zt = dzt = p.transpose ? c.take<float>((size_t)N * C * T * V) : nullptr;
+        Wt = c.take<float>((size_t)p.K * p.Epad);
+        part = c.take<float>((size_t)p.splits * ((size_t)E * p.K + E));
+        total = c.off;
+    }
+};
+int launch_patch_embed_backward(const PatchBackwardPlan &p, const PatchBackwardStore &store, const float *z, const float *W,
+                                const float *dx, float *dW, float *dbias, float *dcls, float *dpos, float *dz, int N, int C, int T,
+                                int V, int p1, int p2, int E, hipStream_t st);
+
+// ---- the backward of the pooled classifier (vit_head.hip) -------------------------------------------------------------------
+// logits = LN(pooled) W^T + bias with pooled = x[:, 0] (`first`) or the mean over the L tokens.  Two launches and two ordered
+// sums: a workgroup per clip recomputes the pooled row and its statistics, takes g = dlogits[n] W, the LayerNorm backward of
+// it, writes dx of the clip whole (first: the pooled gradient in row 0 and zeros below; mean: the pooled gradient / L in every
+// row) and the clip's parts of dln_weight and dln_bias and its normalised row; a second kernel owns one element of dW each and
+// adds dlogits[n][c] * normalised[n][d] over the clips in clip order, as the sums of the parts and of dbias are.
+struct ClassifyBackwardStore {
+    float *normed, *gpart, *bpart;   // (N, D) each: LN(pooled) rows, the clips' dln_weight / dln_bias parts
+    size_t total;
+    ClassifyBackwardStore(void *base, int N, int D) {
+        Carve c(base);
+        normed = c.take<float>((size_t)N * D);
+        gpart = c.take<float>((size_t)N * D);
+        bpart = c.take<float>((size_t)N * D);
+        total = c.off;
+    }
+};
+int launch_pool_classify_backward(const ClassifyBackwardStore &store, const float *x, const float *gamma, const float *beta,
+                                  float eps, const float *W, const float *dlogits, float *dx, float *dgamma, float *dbeta,
+                                  float *dW, float *dbias, int N, int L, int D, int classes, bool first, hipStream_t st);
 
 // The plan of a whole-head call, decided here and nowhere else: stgcn_altformer_head_supported, .._ws_bytes and .._forward read
 // it and none of them looks at a flag bit or compares a length again.  The two stages' blocks are plan_block's, unrestated.

@@ -9,6 +9,7 @@
 //   take the two tokens of one v_mfma_f32_32x32x2_f32, and the row stride of 160 floats puts them 32 banks apart).
 //   A workgroup of 4 waves owns a 128 x 128 tile of dW for one range of tokens; the column sums of dY (the bias gradient)
 //   ride in the workgroups of the first K tile, summed by the threads that stage dY.
+//   (The kernel itself is in vit_wgrad_kernel.h: the ST-ViT head's patch embedding runs it on rows of its own.)
 //
 // attention backward: built from vit_attention_common.h, which describes the layout it shares with the forward.  One
 //   workgroup per (sequence, head) pair as there (several pairs for L <= 64), two phases:
@@ -22,6 +23,7 @@
 //   Seven products instead of five; no sum across waves, no L x L matrix outside registers.
 //   LDS: ceil(L/32)*32 * (2 (hd + 1) + 4) * 4 bytes = 134 KiB at L = 256, hd 64.
 #include "vit_attention_common.h"
+#include "vit_wgrad_kernel.h"
 
 namespace stgcn {
 namespace vit {
@@ -58,119 +60,8 @@ __global__ __launch_bounds__(256) void mask_mul_kernel(const float4 *__restrict_
 }
 
 // ---- wgrad ----------------------------------------------------------------------------------------------------------------
-constexpr int WT = 128, WC = kWgradChunk, WLD = 160;   // tile edge, tokens per chunk, LDS row stride (floats)
-
-__device__ __forceinline__ float4 load_row4(const float *p, int c, int width, bool vec) {
-    if (c >= width) return make_float4(0.f, 0.f, 0.f, 0.f);
-    if (vec) return *reinterpret_cast<const float4 *>(p + c);
-    float4 v;
-    v.x = p[c];
-    v.y = c + 1 < width ? p[c + 1] : 0.f;
-    v.z = c + 2 < width ? p[c + 2] : 0.f;
-    v.w = c + 3 < width ? p[c + 3] : 0.f;
-    return v;
-}
-
-__global__ __launch_bounds__(256) void vit_wgrad_kernel(const float *__restrict__ dY, const float *__restrict__ A,
-                                                       const float *__restrict__ rowscale, int L, float *__restrict__ part,
-                                                       float *__restrict__ bpart, int M, int K, int Nout, int tiles_n,
-                                                       int tiles_k, int rows_per_split) {
-    __shared__ __attribute__((aligned(16))) float ld[WC * WLD], la[WC * WLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
-    const int tile = (int)blockIdx.x % (tiles_n * tiles_k), split = (int)blockIdx.x / (tiles_n * tiles_k);
-    const int n0 = (tile / tiles_k) * WT, k0 = (tile % tiles_k) * WT;
-    const int r_lo = split * rows_per_split, r_hi = min(M, r_lo + rows_per_split);
-    const int sr = tid >> 5, sc = (tid & 31) * 4;       // staging: rows sr + 8 i of the chunk, floats sc .. sc + 3 of the tile
-    const bool vec_n = (Nout & 3) == 0;
-    const bool with_bias = bpart != nullptr && k0 == 0;
-
-    float4 gd[4], ga[4];
-    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto gload = [&](int r0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = r0 + sr + 8 * i;
-            if (row < r_hi) {
-                float4 d = load_row4(dY + (size_t)row * Nout, n0 + sc, Nout, vec_n);
-                if (rowscale != nullptr) {
-                    const float s = rowscale[row / L];
-                    d.x *= s, d.y *= s, d.z *= s, d.w *= s;
-                }
-                gd[i] = d;
-                ga[i] = load_row4(A + (size_t)row * K, k0 + sc, K, true);
-            } else {
-                gd[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                ga[i] = gd[i];
-            }
-        }
-    };
-    auto sstore = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<float4 *>(&ld[(sr + 8 * i) * WLD + sc]) = gd[i];
-            *reinterpret_cast<float4 *>(&la[(sr + 8 * i) * WLD + sc]) = ga[i];
-            bsum.x += gd[i].x, bsum.y += gd[i].y, bsum.z += gd[i].z, bsum.w += gd[i].w;
-        }
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
-
-    if (r_lo < r_hi) {
-        gload(r_lo);
-        sstore();
-    }
-    __syncthreads();
-    for (int r0 = r_lo; r0 < r_hi; r0 += WC) {
-        const bool more = r0 + WC < r_hi;
-        if (more) gload(r0 + WC);
-#pragma unroll
-        for (int s = 0; s < WC / 2; ++s) {
-            const float *dp = &ld[(2 * s + half) * WLD + wm * 64 + l31], *ap = &la[(2 * s + half) * WLD + wn * 64 + l31];
-            const float d0 = dp[0], d1 = dp[32], a0 = ap[0], a1 = ap[32];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d0, a0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d0, a1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d1, a0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d1, a1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-        if (more) {
-            sstore();
-            __syncthreads();
-        }
-    }
-
-    // lane holds column k = l31 of each 32 x 32 block, rows (= output features n) 8 (i / 4) + 4 half + i % 4
-    float *out = part + (size_t)split * Nout * K;
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int col = k0 + wn * 64 + n * 32 + l31;
-        if (col >= K) continue;
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = n0 + wm * 64 + m * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
-                if (row < Nout) out[(size_t)row * K + col] = acc[m][n][i];
-            }
-    }
-    if (with_bias) {   // (uniform over the workgroup) the 8 staging rows of a column, added in the order 0 .. 7
-        *reinterpret_cast<float4 *>(&ld[sr * WLD + sc]) = bsum;
-        __syncthreads();
-        if (tid < WT && n0 + tid < Nout) {
-            float t = ld[tid];
-#pragma unroll
-            for (int r = 1; r < 8; ++r) t += ld[r * WLD + tid];
-            bpart[(size_t)split * Nout + n0 + tid] = t;
-        }
-    }
-}
+// vit_wgrad_kernel.h holds the kernel: vit_patch_backward.hip runs it too, on the patch embedding's rows.
+using namespace wgrad_kernel;
 
 // ---- LayerNorm backward -----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
@@ -528,8 +419,8 @@ int launch_wgrad(const float *dY, const float *A, const float *rowscale, int L, 
     const int rps = wgrad_rows_per_split(M, K, Nout), splits = ceil_div(M, rps);
     const int tiles_n = ceil_div(Nout, WT), tiles_k = ceil_div(K, WT);
     float *bpart = db != nullptr ? part + (size_t)splits * Nout * K : nullptr;
-    vit_wgrad_kernel<<<dim3((unsigned)(tiles_n * tiles_k * splits)), dim3(256), 0, st>>>(dY, A, rowscale, L, part, bpart, M, K,
-                                                                                       Nout, tiles_n, tiles_k, rps);
+    vit_wgrad_kernel<DenseWgradRows><<<dim3((unsigned)(tiles_n * tiles_k * splits)), dim3(256), 0, st>>>(
+        dY, A, rowscale, L, part, bpart, M, K, Nout, tiles_n, tiles_k, rps, DenseWgradRows{});
     STGCN_LAUNCH_CHECK("vit_wgrad_kernel");
     int rc;
     if ((rc = reduce_parts(part, splits, (size_t)Nout * K, dW, tmp, accumulate, st))) return rc;

@@ -130,6 +130,96 @@ __global__ __launch_bounds__(kClsThreads) void vit_pool_classify_kernel(const fl
     }
 }
 
+// The backward of vit_pool_classify_kernel for one clip per workgroup (vit.h, "the backward of the pooled classifier"):
+//   pool, norm : the forward's phases again (the pooled row, its mean and rstd), xhat kept in LDS;
+//   g          : g[d] = sum_c dlogits[n][c] W[c][d], a thread per d, the classes in ascending order;
+//   LayerNorm  : dp = rstd (g gamma - mean(g gamma) - xhat mean(g gamma xhat)), the two means by block_sum;
+//   parts      : normed[n] = xhat gamma + beta (dW's operand), gpart[n] = g xhat, bpart[n] = g;
+//   dx         : the clip's L rows, all of them: FIRST: dp in row 0 and zeros below, else dp / L in every row.
+template <bool FIRST>
+__global__ __launch_bounds__(kClsThreads) void vit_pool_classify_bwd_kernel(
+    const float *__restrict__ x, const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
+    const float *__restrict__ W, const float *__restrict__ dlogits, float *__restrict__ dx, float *__restrict__ normed,
+    float *__restrict__ gpart, float *__restrict__ bpart, int L, int D, int classes) {
+    __shared__ float4 part[kClsThreads];
+    __shared__ float4 row4[kMaxLnDim / 4];
+    __shared__ float4 grad4[kMaxLnDim / 4];
+    __shared__ float red[kClsWaves];
+    float *row = reinterpret_cast<float *>(row4), *grad = reinterpret_cast<float *>(grad4);
+    const int n = blockIdx.x, tid = threadIdx.x, D4 = D / 4;
+    const int Lp = FIRST ? 1 : L;                                                    // the tokens pooled
+    const float4 *xs = reinterpret_cast<const float4 *>(x) + (size_t)n * L * D4;
+    const int CX = D4 < kClsThreads ? D4 : kClsThreads, TY = kClsThreads / CX;
+    const int cx = tid % CX, ty = tid / CX;
+    for (int c0 = 0; c0 < D4; c0 += CX) {
+        if (ty < TY) part[ty * CX + cx] = pool_lane<FIRST>(xs, Lp, D4, c0 + cx, ty, TY);   // FIRST: the selection over one token
+        __syncthreads();
+        if (ty == 0) {
+            float4 acc = part[cx];
+            for (int j = 1; j < TY; ++j) acc = FIRST ? max4(acc, part[j * CX + cx]) : add4(acc, part[j * CX + cx]);
+            if (!FIRST) {
+                const float len = (float)L;
+                acc = float4{acc.x / len, acc.y / len, acc.z / len, acc.w / len};
+            }
+            row4[c0 + cx] = acc;
+        }
+        __syncthreads();
+    }
+    float s = 0.f;
+    for (int d = tid; d < D; d += kClsThreads) s += row[d];
+    const float mean = block_sum(s, red) / (float)D;
+    float q = 0.f;
+    for (int d = tid; d < D; d += kClsThreads) {
+        const float c = row[d] - mean;
+        q = fmaf(c, c, q);
+    }
+    const float rstd = 1.f / sqrtf(block_sum(q, red) / (float)D + eps);
+    const float *dl = dlogits + (size_t)n * classes;
+    float s1 = 0.f, s2 = 0.f;
+    for (int d = tid; d < D; d += kClsThreads) {      // a thread owns its d from here to the store of dp
+        const float xh = (row[d] - mean) * rstd;
+        float g = 0.f;
+        for (int c = 0; c < classes; ++c) g = fmaf(dl[c], W[(size_t)c * D + d], g);
+        const float gw = g * gamma[d];
+        s1 += gw;
+        s2 = fmaf(gw, xh, s2);
+        row[d] = xh;
+        grad[d] = gw;
+        const size_t o = (size_t)n * D + d;
+        if (normed != nullptr) normed[o] = xh * gamma[d] + beta[d];
+        if (gpart != nullptr) gpart[o] = g * xh;
+        if (bpart != nullptr) bpart[o] = g;
+    }
+    const float m1 = block_sum(s1, red) / (float)D, m2 = block_sum(s2, red) / (float)D;
+    if (dx == nullptr) return;
+    for (int d = tid; d < D; d += kClsThreads) {
+        const float dp = rstd * (grad[d] - m1 - row[d] * m2);
+        grad[d] = FIRST ? dp : dp / (float)L;
+    }
+    __syncthreads();
+    float4 *dxs = reinterpret_cast<float4 *>(dx) + (size_t)n * L * D4;
+    const float4 zero = float4{0.f, 0.f, 0.f, 0.f};
+    for (int e = tid; e < L * D4; e += kClsThreads) dxs[e] = FIRST && e >= D4 ? zero : grad4[e % D4];
+}
+
+// One thread per element of dW (classes, D), then of dbias (classes): the clips in ascending order.
+__global__ __launch_bounds__(256) void vit_classify_wgrad_kernel(const float *__restrict__ dlogits, const float *__restrict__ normed,
+                                                                  float *__restrict__ dW, float *__restrict__ dbias, int N, int D,
+                                                                  int classes) {
+    const int idx = blockIdx.x * 256 + threadIdx.x, nw = dW != nullptr ? classes * D : 0;
+    if (idx < nw) {
+        const int c = idx / D, d = idx - c * D;
+        float a = 0.f;
+        for (int n = 0; n < N; ++n) a = fmaf(dlogits[(size_t)n * classes + c], normed[(size_t)n * D + d], a);
+        dW[idx] = a;
+    } else if (idx - nw < classes && dbias != nullptr) {
+        const int c = idx - nw;
+        float a = 0.f;
+        for (int n = 0; n < N; ++n) a += dlogits[(size_t)n * classes + c];
+        dbias[c] = a;
+    }
+}
+
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 inline bool pool_flags_clash(unsigned flags) { return (flags & STGCN_VIT_POOL_MAX) && (flags & STGCN_VIT_POOL_CLS); }
 
@@ -167,6 +257,32 @@ int launch_pool_classify(const float *x, const float *gamma, const float *beta, 
         hipLaunchKernelGGL((vit_pool_classify_kernel<false>), dim3(N), dim3(kClsThreads), 0, st, x, gamma, beta, eps, W, bias,
                            logits, L, Ls, D, classes);
     STGCN_LAUNCH_CHECK("vit_pool_classify_kernel");
+    return STGCN_OK;
+}
+
+int launch_pool_classify_backward(const ClassifyBackwardStore &store, const float *x, const float *gamma, const float *beta,
+                                  float eps, const float *W, const float *dlogits, float *dx, float *dgamma, float *dbeta,
+                                  float *dW, float *dbias, int N, int L, int D, int classes, bool first, hipStream_t st) {
+    int rc;
+    if (dx != nullptr || dgamma != nullptr || dbeta != nullptr || dW != nullptr) {
+        float *normed = dW != nullptr ? store.normed : nullptr, *gpart = dgamma != nullptr ? store.gpart : nullptr;
+        float *bpart = dbeta != nullptr ? store.bpart : nullptr;
+        if (first)
+            hipLaunchKernelGGL((vit_pool_classify_bwd_kernel<true>), dim3(N), dim3(kClsThreads), 0, st, x, gamma, beta, eps, W,
+                               dlogits, dx, normed, gpart, bpart, L, D, classes);
+        else
+            hipLaunchKernelGGL((vit_pool_classify_bwd_kernel<false>), dim3(N), dim3(kClsThreads), 0, st, x, gamma, beta, eps, W,
+                               dlogits, dx, normed, gpart, bpart, L, D, classes);
+        STGCN_LAUNCH_CHECK("vit_pool_classify_bwd_kernel");
+    }
+    if (dgamma != nullptr && (rc = launch_sum_parts(store.gpart, dgamma, N, (size_t)D, st))) return rc;
+    if (dbeta != nullptr && (rc = launch_sum_parts(store.bpart, dbeta, N, (size_t)D, st))) return rc;
+    if (dW != nullptr || dbias != nullptr) {
+        const long long total = (dW != nullptr ? (long long)classes * D : 0) + classes;
+        vit_classify_wgrad_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(dlogits, store.normed, dW, dbias, N, D,
+                                                                                              classes);
+        STGCN_LAUNCH_CHECK("vit_classify_wgrad_kernel");
+    }
     return STGCN_OK;
 }
 
@@ -237,6 +353,44 @@ int stgcn_vit_pool_classify(const float *x, const float *ln_weight, const float 
         return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_pool_classify: D = %d (covered: D %% 64 == 0, D <= %d)", D, kMaxLnDim);
     return launch_pool_classify(x, ln_weight, ln_bias, ln_eps, W, bias, logits, N, L, D, classes, (flags & STGCN_VIT_POOL_MAX) != 0,
                                 static_cast<hipStream_t>(stream), (flags & STGCN_VIT_POOL_CLS) != 0);
+}
+
+static bool classify_backward_ok(int N, int L, int D, int classes, unsigned flags) {
+    return !(flags & ~(unsigned)(STGCN_VIT_POOL_MAX | STGCN_VIT_POOL_CLS)) && !(flags & STGCN_VIT_POOL_MAX) &&
+           pool_classify_ok(N, L, D, classes) && (long long)classes * D + classes < (1ll << 31) && (long long)L * D < (1ll << 31);
+}
+
+int stgcn_vit_pool_classify_backward_supported(int N, int L, int D, int classes, unsigned flags) {
+    return classify_backward_ok(N, L, D, classes, flags) ? 1 : 0;
+}
+
+size_t stgcn_vit_pool_classify_backward_ws_bytes(int N, int L, int D, int classes, unsigned flags) {
+    return classify_backward_ok(N, L, D, classes, flags) ? ClassifyBackwardStore(nullptr, N, D).total : 0;
+}
+
+int stgcn_vit_pool_classify_backward(const float *x, const float *ln_weight, const float *ln_bias, float ln_eps, const float *W,
+                                     const float *dlogits, float *dx, float *dln_weight, float *dln_bias, float *dW, float *dbias,
+                                     int N, int L, int D, int classes, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
+    if (flags & ~(unsigned)(STGCN_VIT_POOL_MAX | STGCN_VIT_POOL_CLS))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify_backward: unknown flag bits 0x%x", flags);
+    if (pool_flags_clash(flags))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify_backward: STGCN_VIT_POOL_MAX and STGCN_VIT_POOL_CLS exclude each other");
+    REQUIRE_PTR(x); REQUIRE_PTR(ln_weight); REQUIRE_PTR(ln_bias); REQUIRE_PTR(W); REQUIRE_PTR(dlogits); REQUIRE_PTR(ws);
+    REQUIRE_POS(N); REQUIRE_POS(L); REQUIRE_POS(D); REQUIRE_POS(classes);
+    if (!aligned16(x) || !aligned16(ws) || (dx != nullptr && !aligned16(dx)))
+        return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify_backward: x, dx and ws must be 16-byte aligned");
+    if (dx == x) return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify_backward: dx must not alias x");
+    if (flags & STGCN_VIT_POOL_MAX)
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_pool_classify_backward: STGCN_VIT_POOL_MAX has no backward (covered: the "
+                    "class token and the mean)");
+    if (!classify_backward_ok(N, L, D, classes, flags))
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_pool_classify_backward: D = %d, classes = %d (covered: D %% 64 == 0, D <= %d, "
+                    "dW and a clip of dx below 2^31 elements)", D, classes, kMaxLnDim);
+    const ClassifyBackwardStore store(ws, N, D);
+    if (ws_bytes < store.total)
+        return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_pool_classify_backward: workspace %zu < %zu bytes", ws_bytes, store.total);
+    return launch_pool_classify_backward(store, x, ln_weight, ln_bias, ln_eps, W, dlogits, dx, dln_weight, dln_bias, dW, dbias, N, L,
+                                         D, classes, (flags & STGCN_VIT_POOL_CLS) != 0, static_cast<hipStream_t>(stream));
 }
 
 int stgcn_altformer_head_supported(const stgcn_altformer_head_shape *shape, unsigned flags1, unsigned flags2, unsigned head_flags) {

@@ -1,8 +1,9 @@
 // The tile kernel of the token-major linear (vit_linear.hip describes the tiling, the arithmetics and the tile forms), in a
-// header because two translation units launch it: vit_linear.hip on dense rows (every linear of the blocks) and
-// vit_patch.hip on the patches of the ST-ViT head's embedding, which it reads straight from the stem output.  What differs
-// between the two is where a row of the A operand lies and which part of the contraction a workgroup walks: the `Rows`
-// policy below.  Everything else - staging, LDS layout, fragments, MFMA order, epilogue - is one piece of code.
+// header because three translation units launch it: vit_linear.hip on dense rows (every linear of the blocks),
+// vit_patch.hip on the patches of the ST-ViT head's embedding, which it reads straight from the stem output, and
+// vit_patch_backward.hip for that embedding's input gradient, which it stores straight into the stem output's layout.  What
+// differs between them is where a row of the A operand lies, which part of the contraction a workgroup walks and where an
+// element of Y is stored: the `Rows` policy below.  Everything else - staging, LDS layout, fragments, MFMA order, epilogue - is one piece of code.
 #pragma once
 
 #include "bf16_common.h"
@@ -67,7 +68,7 @@ struct Tiles<STGCN_MATH_BF16, BM, BN> {
 // Where the rows of the A operand lie, and which part of the contraction and of Y a workgroup owns.
 // DenseRows: X is (M, kx) row-major, every workgroup walks all of K and writes Y as given (grid.y = 1).
 struct DenseRows {
-    static constexpr bool kPatch = false;
+    static constexpr bool kPatch = false, kPatchStore = false;
 };
 // PatchRows: row r = (clip i, patch a, b) of the (N, T, V, C) tensor X cut into p1 x p2 patches (n = h w of them per clip, w
 // along V); column k = (f p2 + j) C + c is X[i][a p1 + f][b p2 + j][c], so a patch is p1 runs of `run` = p2 C contiguous floats,
@@ -75,7 +76,7 @@ struct DenseRows {
 // cut over grid.y: workgroup y walks the chunks [y cps, (y + 1) cps) and writes its sums to slab y of Y (M Nout floats each),
 // which the caller adds up in slab order.  No LayerNorm, X fp32.
 struct PatchRows {
-    static constexpr bool kPatch = true;
+    static constexpr bool kPatch = true, kPatchStore = false;
     int n, w, run, frame, patch_rows, clip;   // patch_rows = p1 V C (one row of patches), clip = T V C
     int cps;                                   // chunks per slab
     __device__ __forceinline__ size_t row_base(int row) const {
@@ -88,6 +89,18 @@ struct PatchRows {
     }
 };
 
+// PatchGradRows: the input gradient of that embedding, dz = dx_tokens W, as this linear on the transposed weight.  Row
+// m = i n + p of the A operand is row i (n + 1) + 1 + p of the (N, n + 1, kx) gradient X (the class rows are skipped), every
+// workgroup walks all of K, and element (m, col) of Y is stored where column `col` of patch m lies in the (N, T, V, C) tensor
+// (`to`): 32 consecutive columns lie inside one run, so a half-wave's store stays 128 contiguous bytes, and every element of
+// that tensor belongs to exactly one (m, col), so the launch writes it whole.  No LayerNorm, fp32 on both sides, and none of
+// the epilogue's optional operands (bias, R, LinearExtra's pointers), which are indexed as a dense Y.
+struct PatchGradRows {
+    static constexpr bool kPatch = false, kPatchStore = true;
+    PatchRows to;
+    __device__ __forceinline__ size_t src_row(int m) const { return (size_t)m + m / to.n + 1; }
+};
+
 // XB / YB (bf16 arithmetic only): X / Y point at bf16 storage, not fp32.
 template <int MATH, class F, bool XB = false, bool YB = false, class A = DenseRows>
 __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const void *__restrict__ Xv, const float *__restrict__ W,
@@ -97,6 +110,7 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const void *__re
                                                         int gelu, const LinearExtra ex, const A rows) {
     static_assert(MATH == STGCN_MATH_BF16 || (!XB && !YB), "bf16 storage goes with the bf16 arithmetic");
     static_assert(!A::kPatch || !XB, "patches are read from fp32");
+    static_assert(!A::kPatchStore || (!XB && !YB), "the patches' gradient is fp32 on both sides");
     constexpr int BM = F::BM, BN = F::BN, RS = F::RS, PA = F::PA, PB = F::PB, WM = F::WM, WN = F::WN;
     const float *__restrict__ X = static_cast<const float *>(Xv);                      // !XB
     const unsigned short *__restrict__ Xh = static_cast<const unsigned short *>(Xv);   // XB
@@ -112,7 +126,7 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const void *__re
     // whole row; it is about to be read again for the A tiles, so this pass mostly primes the cache), sum x - c and
     // (x - c)^2 with c = the row's first element (no cancellation for rows with a large offset), and combine with three
     // exchanges in a fixed order.  Every workgroup of a row slab repeats this; it replaces a pre-pass and its buffer.
-    const bool ln = !XB && !A::kPatch && gamma != nullptr;   // (a LayerNorm of bf16 rows is refused at the entry point)
+    const bool ln = !XB && !A::kPatch && !A::kPatchStore && gamma != nullptr;   // (a LayerNorm of bf16 rows is refused at the entry point)
     float mean[PA], rstd[PA];
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
@@ -158,6 +172,10 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const void *__re
                 if (i < PA)
                     xa[i] = row < M ? *reinterpret_cast<const float4 *>(X + xrow[i] + rows.col(k0) + lc)
                                     : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else if constexpr (A::kPatchStore) {
+                if (i < PA)
+                    xa[i] = row < M && k0 + lc < kx ? *reinterpret_cast<const float4 *>(X + rows.src_row(row) * kx + k0 + lc)
+                                                    : make_float4(0.f, 0.f, 0.f, 0.f);
             } else if (i < PA)
                 xa[i] = row < M && k0 + lc < kx ? *reinterpret_cast<const float4 *>(X + (size_t)row * kx + k0 + lc)
                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -299,6 +317,10 @@ __global__ __launch_bounds__(F::THREADS) void vit_linear_kernel(const void *__re
                 const int row = m0 + wm * (32 * WM) + m * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
                 if (row >= M) continue;
                 float v = acc[m][n][i] + bv;
+                if constexpr (A::kPatchStore) {
+                    Y[rows.to.row_base(row) + rows.to.col(col)] = v;
+                    continue;
+                }
                 const size_t idx = (size_t)row * Nout + col;
                 if (ex.pre != nullptr) ex.pre[idx] = v;
                 if (gelu) {

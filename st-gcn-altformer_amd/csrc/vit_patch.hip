@@ -82,16 +82,21 @@ inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
+int launch_patch_transpose(const float *z, float *zt, int N, int C, int P, hipStream_t st) {
+    const int tiles_p = ceil_div(P, 32), tiles_c = ceil_div(C, 32);
+    const long long blocks = (long long)N * tiles_p * tiles_c;
+    if (blocks > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed: %lld transpose tiles", blocks);
+    vit_patch_transpose_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(z, zt, C, P, tiles_p, tiles_c);
+    STGCN_LAUNCH_CHECK("vit_patch_transpose_kernel");
+    return STGCN_OK;
+}
+
 int launch_patch_embed_vit(const PatchPlan &p, const PatchStore &store, const float *z, const float *W, const float *bias,
                            const float *cls, const float *pos, float *x, int N, int C, int T, int V, int p1, int p2, int E,
                            hipStream_t st) {
     int rc;
     if (p.transpose) {
-        const int P = T * V, tiles_p = ceil_div(P, 32), tiles_c = ceil_div(C, 32);
-        const long long blocks = (long long)N * tiles_p * tiles_c;
-        if (blocks > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed: %lld transpose tiles", blocks);
-        vit_patch_transpose_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(z, store.zt, C, P, tiles_p, tiles_c);
-        STGCN_LAUNCH_CHECK("vit_patch_transpose_kernel");
+        if ((rc = launch_patch_transpose(z, store.zt, N, C, T * V, st))) return rc;
         z = store.zt;
     }
     if (p.math == STGCN_MATH_F32) rc = launch_patch_math<STGCN_MATH_F32>(p, z, W, store.part, C, V, T, p1, p2, E, st);

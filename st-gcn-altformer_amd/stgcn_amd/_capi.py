@@ -182,6 +182,13 @@ PROTOTYPES = {
     "stgcn_vit_block_backward_drop": (c_int, [_P, ctypes.POINTER(VitBlockWeights), _P, _P, ctypes.POINTER(VitDropMasks), _P, c_size_t,
                                               _P, _P, ctypes.POINTER(VitBlockGrads), c_float, c_float, _P, c_size_t] + [c_int] * 5
                                       + [c_uint, _P]),
+    "stgcn_vit_patch_embed_backward_supported": (c_int, [c_int] * 7 + [c_uint]),
+    "stgcn_vit_patch_embed_backward_ws_bytes": (c_size_t, [c_int] * 7 + [c_uint]),
+    "stgcn_vit_patch_embed_backward_cut": (c_int, [c_int] * 7 + [c_uint]),
+    "stgcn_vit_patch_embed_backward": (c_int, [_P] * 8 + [c_int] * 7 + [_P, c_size_t, c_uint, _P]),
+    "stgcn_vit_pool_classify_backward_supported": (c_int, [c_int] * 4 + [c_uint]),
+    "stgcn_vit_pool_classify_backward_ws_bytes": (c_size_t, [c_int] * 4 + [c_uint]),
+    "stgcn_vit_pool_classify_backward": (c_int, [_P] * 3 + [c_float] + [_P] * 7 + [c_int] * 4 + [_P, c_size_t, c_uint, _P]),
 }
 
 _lib = None

@@ -853,6 +853,96 @@ def vit_patch_embed(z, weight, bias, cls, pos, p1, p2, math=MATH_F32) -> torch.T
     return x
 
 
+# ---- The ST-ViT head: training the two ends (stgcn_vit_patch_embed_backward, stgcn_vit_pool_classify_backward) ------------------
+def vit_patch_embed_backward_supported(N, C, T, V, p1, p2, E, math=MATH_F32, channels_last=False) -> bool:
+    """Whether ``vit_patch_embed_backward`` runs this shape.  A host function: no GPU needed."""
+    return bool(_capi.lib().stgcn_vit_patch_embed_backward_supported(N, C, T, V, p1, p2, E, _patch_flags(math, channels_last)))
+
+
+def vit_patch_embed_backward_ws_bytes(N, C, T, V, p1, p2, E, math=MATH_F32, channels_last=False) -> int:
+    return int(_capi.lib().stgcn_vit_patch_embed_backward_ws_bytes(N, C, T, V, p1, p2, E, _patch_flags(math, channels_last)))
+
+
+def vit_patch_embed_backward_cut(N, C, T, V, p1, p2, E, math=MATH_F32, channels_last=False):
+    """``(tokens per split, splits)`` of the weight gradient's reduction over the tokens, or None where the call is not covered."""
+    c = _capi.lib().stgcn_vit_patch_embed_backward_cut(N, C, T, V, p1, p2, E, _patch_flags(math, channels_last))
+    return (c >> 16, c & 0xFFFF) if c else None
+
+
+def vit_patch_embed_backward(z, weight, dx, p1, p2, math=MATH_F32, need_dw=True, need_dbias=True, need_dcls=True, need_dpos=True,
+                             need_dz=True) -> dict:
+    """Backward of ``vit_patch_embed``: from z (N, C, T, V) - contiguous, or channels-last strided, read in place - the weight
+    (E, p1 p2 C) and dx (N, n + 1, E), the gradient of the embedding's output, the dict of ``dW`` (E, K), ``dbias`` (E),
+    ``dcls`` (E), ``dpos`` (n + 1, E) and ``dz`` (the shape and strides of z), each None where ``need_*`` is off.  The patches
+    are read from z and the gradient is written into z's layout directly: no (N, n, K) tensor exists.  ``math``: f32 or bf16x3
+    for ``dz`` (a block's flag word is accepted: ``_patch_flags``); ``dW`` is fp32 matrix cores always."""
+    dev = z.device
+    N, C, T, V = z.shape
+    E, K = weight.shape
+    if T % p1 or V % p2:
+        raise ValueError(f"T = {T}, V = {V} are not whole patches of {p1} x {p2}")
+    n = (T // p1) * (V // p2)
+    if K != p1 * p2 * C or tuple(dx.shape) != (N, n + 1, E):
+        raise ValueError(f"weight is {tuple(weight.shape)}, dx is {tuple(dx.shape)}; expected ({E}, {p1 * p2 * C}) and {(N, n + 1, E)}")
+    channels_last = _is_channels_last(z)
+    zin = z.permute(0, 2, 3, 1) if channels_last else z
+    fl = _patch_flags(math, channels_last)
+    nbytes = int(_capi.lib().stgcn_vit_patch_embed_backward_ws_bytes(N, C, T, V, p1, p2, E, fl))
+    ws = _bytes(dev, nbytes)
+    out = {"dW": torch.empty((E, K), device=dev, dtype=torch.float32) if need_dw else None,
+           "dbias": torch.empty(E, device=dev, dtype=torch.float32) if need_dbias else None,
+           "dcls": torch.empty(E, device=dev, dtype=torch.float32) if need_dcls else None,
+           "dpos": torch.empty((n + 1, E), device=dev, dtype=torch.float32) if need_dpos else None, "dz": None}
+    dzin = None
+    if need_dz:
+        if channels_last:     # the strides of z: (N, T, V, C) memory seen as (N, C, T, V)
+            dzin = torch.empty((N, T, V, C), device=dev, dtype=torch.float32)
+            out["dz"] = dzin.permute(0, 3, 1, 2)
+        else:
+            dzin = out["dz"] = torch.empty((N, C, T, V), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_patch_embed_backward", _dev_ptr(zin, "z", dev), _dev_ptr(weight, "weight", dev),
+                   _dev_ptr(dx, "dx", dev), _dev_ptr(out["dW"], "dW"), _dev_ptr(out["dbias"], "dbias"), _dev_ptr(out["dcls"], "dcls"),
+                   _dev_ptr(out["dpos"], "dpos"), _dev_ptr(dzin, "dz"), c_int(N), c_int(C), c_int(T), c_int(V), c_int(p1), c_int(p2),
+                   c_int(E), c_void_p(ws.data_ptr()), c_size_t(nbytes), c_uint(fl), _stream(dev))
+    return out
+
+
+def vit_pool_classify_backward_supported(N, L, D, classes, mode="cls") -> bool:
+    """Whether ``vit_pool_classify_backward`` runs this shape and pooling ('max' has no backward).  A host function."""
+    return bool(_capi.lib().stgcn_vit_pool_classify_backward_supported(N, L, D, classes, _pool_flags(mode)))
+
+
+def vit_pool_classify_backward(x, ln_weight, ln_bias, eps, weight, dlogits, mode="cls", need_dx=True, need_dln=True, need_dw=True,
+                               need_dbias=True) -> dict:
+    """Backward of ``vit_pool_classify`` ('cls' or 'mean'): the dict of ``dx`` (N, L, D), written whole (for 'cls' the rows
+    below the class token are zeros), ``dln_weight``, ``dln_bias`` (D), ``dW`` (classes, D) and ``dbias`` (classes), each None
+    where ``need_*`` is off (``need_dln`` may be a pair, weight then bias).  The pooled row and its LayerNorm statistics are
+    recomputed from x.  fp32."""
+    fl = _pool_flags(mode)
+    dev = x.device
+    N, L, D = x.shape
+    classes = weight.shape[0]
+    if weight.shape[1] != D or ln_weight.numel() != D or ln_bias.numel() != D or tuple(dlogits.shape) != (N, classes):
+        raise ValueError(f"weight is {tuple(weight.shape)}, the LayerNorm has {ln_weight.numel()} features, x has {D}, dlogits is "
+                         f"{tuple(dlogits.shape)}")
+    need_dlw, need_dlb = need_dln if isinstance(need_dln, (tuple, list)) else (need_dln, need_dln)
+
+    def new(shape, need):
+        return torch.empty(shape, device=dev, dtype=torch.float32) if need else None
+    out = {"dx": new((N, L, D), need_dx), "dln_weight": new((D,), need_dlw), "dln_bias": new((D,), need_dlb),
+           "dW": new((classes, D), need_dw), "dbias": new((classes,), need_dbias)}
+    nbytes = int(_capi.lib().stgcn_vit_pool_classify_backward_ws_bytes(N, L, D, classes, fl))
+    ws = _bytes(dev, nbytes)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_vit_pool_classify_backward", _dev_ptr(x, "x", dev), _dev_ptr(ln_weight, "ln weight", dev),
+                   _dev_ptr(ln_bias, "ln bias", dev), c_float(eps), _dev_ptr(weight, "weight", dev), _dev_ptr(dlogits, "dlogits", dev),
+                   _dev_ptr(out["dx"], "dx"), _dev_ptr(out["dln_weight"], "dln_weight"), _dev_ptr(out["dln_bias"], "dln_bias"),
+                   _dev_ptr(out["dW"], "dW"), _dev_ptr(out["dbias"], "dbias"), c_int(N), c_int(L), c_int(D), c_int(classes),
+                   c_void_p(ws.data_ptr()), c_size_t(nbytes), c_uint(fl), _stream(dev))
+    return out
+
+
 def _head_shape(N, T, V, C, E1, E2, heads, hidden1, hidden2, depth1, depth2, classes):
     return _capi.AltformerHeadShape(N, T, V, C, E1, E2, heads, hidden1, hidden2, depth1, depth2, classes)
 

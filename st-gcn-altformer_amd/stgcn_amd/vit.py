@@ -1,5 +1,5 @@
-"""The ST-ViT head (``model/ST_Vit/trans.py`` of the reference: ``ViT`` and its parts), with the inference forward on
-libstgcn_hip.so.
+"""The ST-ViT head (``model/ST_Vit/trans.py`` of the reference: ``ViT`` and its parts), with the inference forward and
+the training of every piece on libstgcn_hip.so.
 
 ``PreNorm``, ``FeedForward``, ``Attention``, ``Transformer``, ``ViT`` keep the reference's constructor arguments, attribute
 names, ``state_dict`` keys, shapes and construction order (``torch.manual_seed(s)`` followed by construction gives the
@@ -25,10 +25,21 @@ Two paths, one result:
   ``Layer.draw_dropout`` draws with the torch path's generator calls in its order and the kernels apply, so a seed gives both
   paths the same masks (held on the GPU by tests/test_stvit_train_gpu.py).  ``.eval()`` with gradients: the same branch, no
   masks.  The flag word is the blocks' training word (``set_train_math``, ``set_train_attention_math``, the env defaults) plus
-  ``VIT_TILE_AUTO`` where ``small_tiles`` is set.  The embedding and the pooled classifier are torch ops under autograd (one
-  GEMM each, ``emb_dropout = 0``); ``uses_hip`` keeps meaning inference.  The parameters go by attribute, so an
-  ``nn.DataParallel`` replica's gradients reach its master.  By default a ViT call is under the threshold: see
-  ``VIT_HIP_TRAIN_MIN_TOKENS``.
+  ``VIT_TILE_AUTO`` where ``small_tiles`` is set.  ``uses_hip`` keeps meaning inference and ``trains_on_hip`` "every layer".
+  The parameters go by attribute, so an ``nn.DataParallel`` replica's gradients reach its master.  By default a ViT call is
+  under the threshold: see ``VIT_HIP_TRAIN_MIN_TOKENS``.
+* HIP, training, the two ends (``ViT.embed_trains_on_hip(z)``, ``ViT.head_trains_on_hip(x)``): under autograd the embedding's
+  forward is ``functional.vit_patch_embed`` and the classifier's ``functional.vit_pool_classify``, the inference kernels at
+  the same arithmetic, bit for bit, each behind an ``autograd.Function`` that saves only its inputs; the backwards are
+  ``functional.vit_patch_embed_backward`` (``dW``, ``dbias``, ``dcls``, ``dpos`` and ``dz`` in the strides of z, only those
+  autograd asks for; the patches are read from z and ``dz`` is written into its layout, no (N, n, K) copy either way) and
+  ``functional.vit_pool_classify_backward`` (the pooled row and its LayerNorm statistics recomputed from x).  A piece takes
+  this branch when autograd records something that concerns it, the structural checks of its inference branch hold,
+  ``emb_dropout`` is not active (the embedding), the call has at least ``ViT.hip_train_min_tokens`` tokens, and neither env
+  ``STGCN_VIT_TRAIN`` nor ``STGCN_VIT_TRAIN_ENDS`` is ``0`` (the second keeps the two ends on torch ops while the layers train
+  on HIP).  Arithmetic: the training word (``_train_flags``): 'f32' runs the embedding's forward and ``dz`` in f32, every other
+  word in bf16x3; ``dW`` and the classifier are fp32 always.  By default the ends stay on torch ops: see
+  ``VIT_ENDS_HIP_TRAIN_MIN_TOKENS``.
 * torch ops: everything else.  This is the reference's arithmetic op for op.
 
 The switches of ``stgcn_amd.altformer`` act here as they do on its ``Block``s (``ViT`` and every ``Layer`` are
@@ -41,6 +52,7 @@ Defaults (``VIT_HIP_MIN_TOKENS``, ``VIT_SMALL_TILES``): see the comment there fo
 from __future__ import annotations
 
 import os
+import sys
 
 import torch
 import torch.nn as nn
@@ -67,10 +79,71 @@ VIT_SMALL_TILES = True
 # never behind the 128 x 128 ones by more than the spread: VIT_SMALL_TILES holds for training too.  With
 # set_train_math(model, 'bf16') and the small forms the HIP step wins at every measured count (1.52 x, 1.19 x, 1.31 x).
 VIT_HIP_TRAIN_MIN_TOKENS = HIP_TRAIN_MIN_TOKENS
+# The token count from which the two ENDS of a ViT - patch embedding and pooled classifier - train on HIP
+# (``ViT.hip_train_min_tokens``).  MEASURED (profiles/stvit_train_ends_times.json, tools/time_stvit_train.py --ends both: the
+# model above with the layers on HIP and the small forms, batch 8, 32, 128, 160 = 800 to 16,000 tokens, against the same commit
+# with STGCN_VIT_TRAIN_ENDS=0).  In the default training arithmetic 'f32' the step with the
+# ends on HIP ties at 800, 3,200 and 16,000 tokens and is slower at 12,800 (0.98 x); the embedding alone, forward + backward, is
+# slower than rearrange + nn.Linear at 3,200, 12,800 and 16,000 tokens (0.76 x, 0.82 x, 0.85 x: large f32 GEMMs, and the training
+# stem's channels-first output costs a transposing pass each way).  Under set_train_math(model, 'bf16') the step is faster at
+# 800, 3,200 and 16,000 tokens (1.08 x, 1.01 x, 1.02 x) and ties at 12,800.
+# No measured count from which every measured count wins in the default arithmetic, the largest (16,000) included, so by the
+# project's rule the ends of a new ViT stay on torch ops at every token count until set_hip_min_tokens(model, 0) or
+# set_hip_train_min_tokens lifts the threshold (either reaches the ViT as it reaches its layers).
+VIT_ENDS_HIP_TRAIN_MIN_TOKENS = sys.maxsize
 
 
 def _records_grad(x, tensors) -> bool:
     return torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in tensors))
+
+
+def _ends_enabled() -> bool:
+    """Env ``STGCN_VIT_TRAIN`` and ``STGCN_VIT_TRAIN_ENDS``: ``0`` in either keeps the embedding and the pooled classifier on
+    torch ops under autograd (the second alone leaves the layers training on HIP)."""
+    return os.environ.get("STGCN_VIT_TRAIN", "1") != "0" and os.environ.get("STGCN_VIT_TRAIN_ENDS", "1") != "0"
+
+
+class _PatchEmbedTrain(torch.autograd.Function):
+    """The patch embedding under autograd: the forward is ``functional.vit_patch_embed`` as inference calls it, the backward
+    ``functional.vit_patch_embed_backward``.  Saved: z and the weight, nothing the forward made.  The parameters arrive as
+    arguments (taken by attribute from the module), ``pos`` already sliced to its first n + 1 rows."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, cls, pos, p1, p2, math):
+        ctx.save_for_backward(z, weight)
+        ctx.p1, ctx.p2, ctx.math = p1, p2, math
+        ctx.shapes = (cls.shape, pos.shape)
+        return F.vit_patch_embed(z, weight, bias, cls, pos, p1, p2, math)
+
+    @staticmethod
+    def backward(ctx, dx):
+        z, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = F.vit_patch_embed_backward(z, weight, dx.contiguous(), ctx.p1, ctx.p2, ctx.math, need_dz=need[0], need_dw=need[1],
+                                       need_dbias=need[2], need_dcls=need[3], need_dpos=need[4])
+        dcls = g["dcls"].reshape(ctx.shapes[0]) if need[3] else None
+        dpos = g["dpos"].reshape(ctx.shapes[1]) if need[4] else None
+        return g["dz"], g["dW"], g["dbias"], dcls, dpos, None, None, None
+
+
+class _ClassifyTrain(torch.autograd.Function):
+    """Pooling, LayerNorm and Linear under autograd: ``functional.vit_pool_classify`` forward, ``vit_pool_classify_backward``
+    backward, which recomputes the pooled row and its statistics from x.  Saved: the inputs."""
+
+    @staticmethod
+    def forward(ctx, x, ln_weight, ln_bias, weight, bias, eps, mode):
+        x = x.contiguous()
+        ctx.save_for_backward(x, ln_weight, ln_bias, weight)
+        ctx.eps, ctx.mode = eps, mode
+        return F.vit_pool_classify(x, ln_weight, ln_bias, eps, weight, bias, mode=mode)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        x, ln_weight, ln_bias, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = F.vit_pool_classify_backward(x, ln_weight, ln_bias, ctx.eps, weight, dlogits.contiguous(), mode=ctx.mode, need_dx=need[0],
+                                         need_dln=(need[1], need[2]), need_dw=need[3], need_dbias=need[4])
+        return g["dx"], g["dln_weight"], g["dln_bias"], g["dW"], g["dbias"], None, None
 
 
 class Patchify(nn.Module):
@@ -272,6 +345,7 @@ class ViT(nn.Module, HipSwitches):
     the class token or the mean over the tokens, ``mlp_head``."""
 
     DEFAULT_HIP_MIN_TOKENS = VIT_HIP_MIN_TOKENS
+    DEFAULT_HIP_TRAIN_MIN_TOKENS = VIT_ENDS_HIP_TRAIN_MIN_TOKENS
     DEFAULT_SMALL_TILES = VIT_SMALL_TILES
 
     def __init__(self, *, time_len, joint, p1, p2, num_classes, dim, depth, heads, mlp_dim, pool='cls', channels=128, dim_head=64,
@@ -304,24 +378,54 @@ class ViT(nn.Module, HipSwitches):
         """The flag word whose arithmetic the embedding follows (``functional._patch_flags`` maps it to f32 or bf16x3)."""
         return _default_head_math() if self.math_mode is None else self.math_mode
 
-    def embed_on_hip(self, z) -> bool:
-        """Whether the patch embedding of this call runs on ``stgcn_vit_patch_embed``."""
+    def _embed_shaped(self, z):
+        """n + 1 where z is CUDA float32 in one of the two layouts the kernels read and the front is the structure they
+        implement (``Patchify``, one ``nn.Linear``, a class token and a position table of its width), else None."""
         tokens = self._embed_tokens(z)
         emb = self.to_patch_embedding
         if tokens is None or self.force_torch or not z.is_cuda or z.dtype != torch.float32 or len(emb) != 2 or type(emb[1]) is not nn.Linear:
-            return False
-        if not (z.is_contiguous() or F._is_channels_last(z)) or z.shape[0] * tokens < self.hip_min_tokens:
-            return False
+            return None
+        if not (z.is_contiguous() or F._is_channels_last(z)):
+            return None
         lin = emb[1]
-        N, C, T, V = z.shape
         pat = emb[0]
-        if (lin.in_features != pat.p1 * pat.p2 * C or self.cls_token.numel() != lin.out_features
+        if (lin.in_features != pat.p1 * pat.p2 * z.shape[1] or self.cls_token.numel() != lin.out_features
                 or self.pos_embedding.dim() != 3 or self.pos_embedding.shape[1] < tokens
                 or self.pos_embedding.shape[2] != lin.out_features):
+            return None
+        return tokens
+
+    def _embed_params(self):
+        lin = self.to_patch_embedding[1]
+        return lin.weight, lin.bias, self.cls_token, self.pos_embedding
+
+    def embed_on_hip(self, z) -> bool:
+        """Whether the patch embedding of this call runs on ``stgcn_vit_patch_embed``."""
+        tokens = self._embed_shaped(z)
+        if tokens is None or z.shape[0] * tokens < self.hip_min_tokens:
             return False
-        if _records_grad(z, (lin.weight, lin.bias, self.cls_token, self.pos_embedding)) or _drop_active(self.dropout):
+        if _records_grad(z, self._embed_params()) or _drop_active(self.dropout):
             return False
+        pat, lin = self.to_patch_embedding
+        N, C, T, V = z.shape
         return F.vit_patch_embed_supported(N, C, T, V, pat.p1, pat.p2, lin.out_features, self._math(), F._is_channels_last(z))
+
+    def embed_trains_on_hip(self, z) -> bool:
+        """Whether the patch embedding of this call runs on ``stgcn_vit_patch_embed`` now and on
+        ``stgcn_vit_patch_embed_backward`` on ``loss.backward()``: autograd records something that concerns it, the structural
+        checks of ``embed_on_hip`` hold, ``emb_dropout`` is not active, the call has at least ``hip_train_min_tokens`` tokens,
+        and neither env ``STGCN_VIT_TRAIN`` nor ``STGCN_VIT_TRAIN_ENDS`` is ``0``."""
+        if not _ends_enabled():
+            return False
+        tokens = self._embed_shaped(z)
+        if tokens is None or not _records_grad(z, self._embed_params()) or _drop_active(self.dropout):
+            return False
+        if z.shape[0] * tokens < self.hip_train_min_tokens:
+            return False
+        pat, lin = self.to_patch_embedding
+        N, C, T, V = z.shape
+        return F.vit_patch_embed_backward_supported(N, C, T, V, pat.p1, pat.p2, lin.out_features, self._train_flags(),
+                                                    F._is_channels_last(z))
 
     def embed(self, z):
         """(N, n + 1, dim): patches times the weight, the class row in front, the first n + 1 position rows added."""
@@ -331,6 +435,11 @@ class ViT(nn.Module, HipSwitches):
             with torch.no_grad():
                 return F.vit_patch_embed(z, lin.weight, lin.bias, self.cls_token, self.pos_embedding[0, :n1], pat.p1, pat.p2,
                                          self._math())
+        if self.embed_trains_on_hip(z):
+            pat, lin = self.to_patch_embedding
+            n1 = self._embed_tokens(z)
+            return _PatchEmbedTrain.apply(z, lin.weight, lin.bias, self.cls_token, self.pos_embedding[:, :n1], pat.p1, pat.p2,
+                                          self._train_flags())
         x = self.to_patch_embedding(z)
         b, n, _ = x.shape
         x = torch.cat((self.cls_token.expand(b, -1, -1), x), dim=1)
@@ -338,8 +447,9 @@ class ViT(nn.Module, HipSwitches):
         return self.dropout(x)
 
     # ---- the end: pooling, LayerNorm, classifier ----------------------------------------------------------------------------------
-    def head_on_hip(self, x) -> bool:
-        """Whether pooling and ``mlp_head`` of this call run on ``stgcn_vit_pool_classify``."""
+    def _head_shaped(self, x) -> bool:
+        """x is CUDA float32 (N, L, D) and the end is the structure the kernels implement: 'cls' or 'mean', no ``to_latent``,
+        an affine ``nn.LayerNorm`` and one ``nn.Linear`` of x's width."""
         head = self.mlp_head
         if (self.force_torch or not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3
                 or self.pool not in ('cls', 'mean') or type(self.to_latent) is not nn.Identity):
@@ -347,18 +457,40 @@ class ViT(nn.Module, HipSwitches):
         if not (isinstance(head, nn.Sequential) and len(head) == 2 and type(head[0]) is nn.LayerNorm and type(head[1]) is nn.Linear
                 and head[0].elementwise_affine and head[0].bias is not None):
             return False
+        D = x.shape[2]
+        return head[0].normalized_shape == (D,) and head[1].in_features == D
+
+    def _head_params(self):
+        head = self.mlp_head
+        return head[0].weight, head[0].bias, head[1].weight, head[1].bias
+
+    def head_on_hip(self, x) -> bool:
+        """Whether pooling and ``mlp_head`` of this call run on ``stgcn_vit_pool_classify``."""
+        if not self._head_shaped(x):
+            return False
         N, L, D = x.shape
-        if head[0].normalized_shape != (D,) or head[1].in_features != D or N * L < self.hip_min_tokens:
+        if N * L < self.hip_min_tokens or _records_grad(x, self._head_params()):
             return False
-        if _records_grad(x, (head[0].weight, head[0].bias, head[1].weight, head[1].bias)):
+        return F.vit_pool_classify_supported(N, L, D, self.mlp_head[1].out_features)
+
+    def head_trains_on_hip(self, x) -> bool:
+        """Whether pooling and ``mlp_head`` of this call run on ``stgcn_vit_pool_classify`` now and on
+        ``stgcn_vit_pool_classify_backward`` on ``loss.backward()``: the conditions of ``embed_trains_on_hip``, for this end."""
+        if not _ends_enabled() or not self._head_shaped(x) or not _records_grad(x, self._head_params()):
             return False
-        return F.vit_pool_classify_supported(N, L, D, head[1].out_features)
+        N, L, D = x.shape
+        if N * L < self.hip_train_min_tokens:
+            return False
+        return F.vit_pool_classify_backward_supported(N, L, D, self.mlp_head[1].out_features, self.pool)
 
     def classify(self, x):
         if self.head_on_hip(x):
             ln, lin = self.mlp_head
             with torch.no_grad():
                 return F.vit_pool_classify(x.contiguous(), ln.weight, ln.bias, ln.eps, lin.weight, lin.bias, mode=self.pool)
+        if self.head_trains_on_hip(x):
+            ln, lin = self.mlp_head
+            return _ClassifyTrain.apply(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, self.pool)
         x = x.mean(dim=1) if self.pool == 'mean' else x[:, 0]
         return self.mlp_head(self.to_latent(x))
 
@@ -372,8 +504,8 @@ class ViT(nn.Module, HipSwitches):
         return all(isinstance(layer, Layer) and layer.uses_hip(probe) for layer in self.transformer.layers) and self.head_on_hip(probe)
 
     def trains_on_hip(self, z) -> bool:
-        """Whether every layer of ``forward(z)`` trains on the HIP kernels (``Layer.trains_on_hip``).  The embedding and the
-        pooled classifier are torch ops under autograd either way."""
+        """Whether every layer of ``forward(z)`` trains on the HIP kernels (``Layer.trains_on_hip``).  The two ends decide
+        for themselves (``embed_trains_on_hip``, ``head_trains_on_hip``)."""
         tokens = self._embed_tokens(z)
         if tokens is None or not len(self.transformer.layers):
             return False
