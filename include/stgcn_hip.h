@@ -171,6 +171,13 @@ size_t stgcn_stem_ws_bytes(int N, int Cin, int C, int T, int V, int K, int subse
  * "stem_bf16_v4_kernel", "stem_mfma_bf16_kernel", "stem_mfma_f32_kernel"; "" when no fused kernel covers it) — for
  * profilers and benchmarks that match kernel names in rocprofv3 output. */
 const char *stgcn_stem_kernel_name(int Cin, int C, int T, int V, int K, int subsets, unsigned flags);
+/* stem_bf16_v6_kernel in bf16x3 on narrow frames (V <= 32) gives a clip's last tile of at most 128 pixels a half-size form and
+ * then walks the tiles in contiguous runs balanced by cost (a full tile 2 units, a short one 1).  Two queries for tests and
+ * tools: the 16-row blocks of its image the taps of that short tile read (0 when the shape has no short form), and the run
+ * [*first, *end) of clip-major tile indices that workgroup wg of a launch on num_wg compute units walks over nclips clips
+ * of tiles_per_clip tiles (short_last = 0: every tile costs the same). */
+int stgcn_stem_short_tile_blocks(int C, int T, int V, int K);
+int stgcn_stem_walk_run(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *first, int *end);
 /* 1 when one of the large-tile kernels serves the shape (stem_bf16_v4/_v6/_f16mx_kernel): the workspace then holds,
  * behind P, graph-conv features or attention fragments that stgcn_stem_attention writes for the kernel */
 int stgcn_stem_features_used(int Cin, int C, int T, int V, int K, int subsets, unsigned flags);

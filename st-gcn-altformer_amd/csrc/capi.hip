@@ -250,6 +250,19 @@ const char *stgcn_stem_kernel_name(int Cin, int C, int T, int V, int K, int subs
     return stem_kernel_name(plan_stem(1, Cin, C, T, V, K, subsets, flags).kernel);
 }
 
+int stgcn_stem_short_tile_blocks(int C, int T, int V, int K) {
+    if (C <= 0 || T <= 0 || V <= 0 || K <= 0) return 0;
+    return stem_v6_short_tile_blocks(C, T, V, K);
+}
+
+int stgcn_stem_walk_run(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *first, int *end) {
+    REQUIRE_PTR(first); REQUIRE_PTR(end);
+    REQUIRE_POS(num_wg); REQUIRE_POS(nclips); REQUIRE_POS(tiles_per_clip);
+    if (wg < 0) return fail(STGCN_ERR_ARG, "%s: wg = %d must not be negative", __func__, wg);
+    stem_v6_walk_run(wg, num_wg, nclips, tiles_per_clip, short_last, first, end);
+    return STGCN_OK;
+}
+
 int stgcn_stem_features_used(int Cin, int C, int T, int V, int K, int subsets, unsigned flags) {
     if (Cin <= 0 || C <= 0 || T <= 0 || V <= 0 || K <= 0 || subsets <= 0) return 0;
     const StemPart part = plan_stem(1, Cin, C, T, V, K, subsets, flags).part;

@@ -265,6 +265,10 @@ int launch_stem_v4(const float *x, bool x_ntvc, const float *feat, const void *p
 // the same tile with ONE WAVE PER SIMD on v_mfma_f32_16x16x32_bf16 (kernel in kf6.h, narrow form instantiated by
 // stem_bf16_v6.hip: 256 threads, a wave owns all 128 channels of 64 pixels), on pair-order temporal weights
 bool stem_v6_supported(int C, int T, int V, int K, unsigned flags);
+// KF6's narrow three-term form (kf6.h): blocks the short form of a clip's last tile reads (0: the shape has none), and the run
+// [first, end) of tiles that workgroup wg of num_wg walks
+int stem_v6_short_tile_blocks(int C, int T, int V, int K);
+void stem_v6_walk_run(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *first, int *end);
 // ... and for wide frames (32 < V <= 64, V even: the two-hand graph) the same kernel over the two joint halves [0, V0) and
 // [V0, V), each handled like a narrow clip (stem_bf16_v6w.hip)
 static inline int stem_wide_split(int V) {     // V0 (a multiple of 4: 16-byte aligned half rows), or 0 when V does not split

@@ -36,6 +36,18 @@ __global__ void tcn_pack_bf16_pairs_kernel(const float *__restrict__ W, const fl
 
 bool stem_v6_supported(int C, int T, int V, int K, unsigned flags) { return stem_v6_form_supported<false>(C, T, V, K, flags); }
 
+int stem_v6_short_tile_blocks(int C, int T, int V, int K) {
+    V6Plan pl;
+    return T >= 1 && plan_v6_narrow(C, T, V, K, 3, pl) && pl.short_last ? pl.short_blocks : 0;
+}
+
+void stem_v6_walk_run(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *first, int *end) {
+    const int ntiles = nclips * tiles_per_clip, G = ntiles < num_wg ? ntiles : num_wg;   // (the launch's grid)
+    const V6Run r = wg < G ? v6_run(wg, G, nclips, tiles_per_clip, short_last) : V6Run{ntiles, ntiles};
+    *first = r.first;
+    *end = r.end;
+}
+
 // temporal weights (Cout,Cin,9) * scale -> KF6's pair order (same size as the 32x32x16 packing)
 int launch_tcn_pack_bf16_pairs(const float *W, const float *scale, void *Wq, int Cin, int Cout, hipStream_t st) {
     const size_t total = (size_t)Cin * Cout * KT6 * 2;
