@@ -1,4 +1,4 @@
-"""Shared helpers for the tests: golden loading, the parity gate and the hostile allocator."""
+"""Shared helpers for the tests: golden loading, the parity and gradient gates, the hostile allocator and the run under it."""
 import math
 import os
 
@@ -43,6 +43,23 @@ def parity_gate(out, ref, rel=1e-4, what="", strict=True):
 
 def gather_flat(t, idx):
     return torch.as_tensor(t).reshape(-1)[torch.as_tensor(idx)]
+
+
+def grad_gate(got, ref, rel, what):
+    got, ref = got.double().cpu(), ref.double().cpu()
+    assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
+    assert torch.isfinite(got).all(), f"{what}: non-finite gradient"
+    scale = ref.abs().max().item()
+    err = (got - ref).abs().max().item()
+    assert err <= rel * max(scale, 1e-30), f"{what}: max abs err {err:.3e} > {rel:g} * max|ref| ({scale:.3e})"
+
+
+def kink_free_cotangent(y_ref, gen):
+    """Random dL/dy that is zero where the reference output sits within 1e-4*max of the ReLU kink.  The gradient is
+    discontinuous there: an output of 1e-6 that the fp32 path rounds to 0 flips one mask bit and moves dbeta of its
+    channel by a whole |dL/dy| — a property of ReLU, not an arithmetic error — so those outputs carry no cotangent."""
+    G = torch.randn(y_ref.shape, generator=gen)
+    return G * (y_ref.detach() > 1e-4 * y_ref.detach().abs().max()).float()
 
 
 class hostile_allocations:
@@ -149,3 +166,58 @@ class hostile_allocations:
         if exc_type is None:
             self.check()
         return False
+
+
+# ---- a run under the hostile allocator --------------------------------------------------------------------------------------------
+FILLS = (0xFF, 0x7F)          # NaN in fp32 / fp64 / bf16; a huge finite positive number in all three
+
+
+class HostileCase:
+    """``make(dev)`` prepares inputs and references OUTSIDE the hostile block and returns ``(run, gate)``: ``run()`` calls the
+    entry point(s) and returns {name: output tensor}, ``gate(outputs)`` holds them to the existing test's reference and gate.
+    ``bitwise``: the outputs of the two runs must be identical."""
+
+    def __init__(self, id, make, bitwise):
+        self.id, self.make, self.bitwise = id, make, bitwise
+
+
+def _finite(out, what):
+    for k, t in out.items():
+        if t is not None and t.is_floating_point():
+            assert torch.isfinite(t).all(), f"{what}: {k} is not finite under poisoned buffers"
+
+
+def run_under_both_fills(case, dev):
+    run, gate = case.make(dev)
+    outs = []
+    for fill in FILLS:
+        with hostile_allocations(fill) as h:
+            out = run()
+            torch.cuda.synchronize()
+            h.check()
+        assert h.records, f"{case.id}: no allocation went through torch.empty - the case would test nothing"
+        what = f"{case.id} fill=0x{fill:02X}"
+        _finite(out, what)
+        gate(out, what)
+        outs.append(out)
+    if case.bitwise:
+        for k in outs[0]:
+            a, b = outs[0][k], outs[1][k]
+            assert (a is None) == (b is None), k
+            assert a is None or torch.equal(a, b), f"{case.id}: {k} differs between the NaN-filled and the huge-filled run"
+
+
+ZERO_GRAD = ("attention_conv.attn_out.bias",)     # gcn_unit_attention: analytically 0 behind a batch-statistics BatchNorm
+
+
+def st_attention_train_gate(yr, g, dx, frozen):
+    """The gate of a gcn_unit_attention training step {"y", "dx", "d" + parameter name} against grads64's (yr, g, dx)."""
+    def gate(o, what):
+        parity_gate(o["y"], yr, what=f"{what} y")
+        for k in g:
+            if k in ZERO_GRAD and not frozen:
+                assert float(o["d" + k].abs().max()) <= 1e-4 * float(g["bn.bias"].abs().max()), f"{what} d{k}"
+            else:
+                parity_gate(o["d" + k], g[k], strict=False, what=f"{what} grad {k}")
+        parity_gate(o["dx"], dx, strict=False, what=f"{what} dx")
+    return gate

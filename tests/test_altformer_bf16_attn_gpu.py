@@ -217,7 +217,7 @@ def make_block_train_attn_bf16(L, dev):
 def test_block_under_poisoned_guard_banded_buffers(L, dev):
     """Nothing outside ``saved``, the workspace and the outputs is written, and no poison is read into a result: the outputs are
     finite, inside the gate and bit-identical under a NaN fill and a huge-number fill."""
-    from test_buffer_discipline_gpu import Case, run_under_both_fills
+    from _util import HostileCase as Case, run_under_both_fills
     run_under_both_fills(Case(f"vit_block_train_attn_bf16-L{L}", functools.partial(make_block_train_attn_bf16, L), True), dev)
 
 

@@ -12,6 +12,7 @@ from torch.nn.parallel import parallel_apply
 
 import altformer_ref as ar
 from _util import MATH_GATES, gather_flat, load_golden, parity_gate, sub_state
+from entry_points import peaked_qkv, small_head
 
 pytestmark = pytest.mark.gpu
 REL = MATH_GATES["f32"][0]            # the project's 1e-4, both criteria, for f32 and for bf16x3
@@ -84,13 +85,6 @@ def test_linear_entry_point_vs_fp64(shape, math, dev):
 
 
 # ---- 6. the attention ---------------------------------------------------------------------------------------------------
-def peaked_qkv(B, L, heads, hd, seed, amp=2.3):
-    g = torch.Generator().manual_seed(seed)
-    qkv = torch.randn(B, L, 3, heads, hd, generator=g)
-    qkv[:, :, :2] *= amp                         # scores ~ N(0, amp^4): with 2.3 they reach about +-28 at head_dim ** -0.5
-    return qkv.reshape(B, L, 3 * heads * hd)
-
-
 @pytest.mark.parametrize("hd", [32, 64])
 @pytest.mark.parametrize("L", [1, 22, 46, 64, 65, 150, 180, 256])
 def test_attention_entry_point_vs_fp64(L, hd, dev):
@@ -235,22 +229,6 @@ def test_whole_model_logits_and_argmax(style, mode, layout, policy, dev):
 
 
 # ---- 9. paths, determinism, replicas ------------------------------------------------------------------------------------
-def small_head(dev, cls_name="ST", **kw):
-    from stgcn_amd import altformer
-    from stgcn_amd.altformer import set_hip_min_tokens
-    torch.manual_seed(11)
-    cfg = dict(num_frame=40, num_joints=22, in_chans=128, embed_dim_ratio=256, depth=2, num_heads=8, mlp_ratio=2.,
-               qkv_bias=True, drop_path_rate=0.1)
-    cfg.update(kw)
-    head = getattr(altformer, cls_name)(14, **cfg)
-    with torch.no_grad():
-        for n, p in head.named_parameters():
-            if n.endswith("pos_embed"):
-                p.copy_(0.05 * torch.randn(p.shape))
-    set_hip_min_tokens(head, 0)
-    return head.to(dev).eval()
-
-
 @pytest.mark.parametrize("cls_name", ["ST", "TS"])
 def test_two_runs_are_bit_identical_and_match_the_torch_path(cls_name, dev):
     from stgcn_amd.altformer import Block

@@ -15,13 +15,11 @@ from torch.nn.parallel import parallel_apply
 import altformer_ref as ar
 import altformer_train_ref as tr
 from _util import MATH_GATES, gather_flat, load_golden, parity_gate
+from entry_points import TRAIN_STRICT, attention_grad64, run_block
 from test_altformer_gpu import LINEAR_SHAPES, gate_on_device, peaked_qkv, small_head, whole_model
 
 pytestmark = pytest.mark.gpu
 REL = MATH_GATES["f32"][0]
-# The criterion each arithmetic of the training path holds on every gradient of every block case (DESIGN §15 has the
-# measured table): True = both criteria of parity_gate, False = the max-norm criterion only.
-TRAIN_STRICT = {"f32": True, "mixed": True, "bf16x3": False}
 MODES = sorted(TRAIN_STRICT)
 
 
@@ -71,13 +69,6 @@ def test_linear_backward_vs_fp64(shape, math, dev):
     assert none is None and torch.equal(dW, dW2), "the weight gradient is bit-identical from run to run"
 
 
-def attention_grad64(qkv, dout, heads, scale):
-    q = qkv.double().requires_grad_(True)
-    out = ar.attention64(q, heads, scale)
-    out.backward(dout.double())
-    return out.detach(), q.grad
-
-
 @pytest.mark.parametrize("hd", [32, 64])
 @pytest.mark.parametrize("L", [1, 22, 46, 64, 65, 150, 180, 256])
 def test_attention_backward_vs_fp64(L, hd, dev):
@@ -115,16 +106,6 @@ def test_layernorm_backward_vs_fp64(D, dev):
 # ---- 5.-7. one block --------------------------------------------------------------------------------------------------------
 def block_params(blk):
     return list(blk._weights())
-
-
-def run_block(blk, x, dy, mode, s1=None, s2=None):
-    from stgcn_amd import functional as F
-    from stgcn_amd.altformer import HEAD_MATH
-    ps = [None if p is None else p.detach() for p in block_params(blk)]
-    args = (blk.attn.num_heads, blk.norm1.eps, blk.attn.scale, HEAD_MATH[mode], s1, s2)
-    y, saved = F.vit_block_forward_train(x, ps, *args)
-    g = F.vit_block_backward(x, ps, saved, dy, *args)
-    return y, {"x": g["x"], **{k: g[n] for k, n in zip(tr.PARAMS, F.VIT_BLOCK_PARAMS)}}
 
 
 def gate_stored(out, ref, key, what, strict):

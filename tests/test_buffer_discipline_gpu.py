@@ -20,17 +20,15 @@ import torch.nn.functional as TF
 
 import altformer_ref as ar
 import altformer_train_ref as tr
+import entry_points as ep
 import st_attention_ref as R
-from _util import MATH_GATES, hostile_allocations, parity_gate
-from test_altformer_gpu import peaked_qkv
-from test_altformer_train_gpu import TRAIN_STRICT, attention_grad64, run_block
-from test_gpu_parity import (_agcn_module_grads, _agcn_oracle_leaves, _compare_grads, _grad_gate, _kink_free_cotangent,
-                             _random_stem)
-from test_st_attention_gpu import ZERO_GRAD, _unit
+from _util import (FILLS, MATH_GATES, HostileCase as Case, grad_gate, hostile_allocations, parity_gate, run_under_both_fills,
+                   st_attention_train_gate)
+from entry_points import (AGCN_SHAPES, STEM_KERNELS, STEM_MATHS, STEM_SHAPES, TCN_KERNELS, TCN_SHAPES, TILE_FORMS, TRAIN_STRICT,
+                          _stem_kernel, _tcn_mode, hipF as _F, math_flag as _math)
 
 pytestmark = pytest.mark.gpu
 REL = MATH_GATES["f32"][0]
-FILLS = (0xFF, 0x7F)          # NaN in fp32 / fp64 / bf16; a huge finite positive number in all three
 BF16_OUT_GATE = 4e-3          # test_large_tile_temporal_conv_kernel: half an ulp of the stored bf16 value, max-norm criterion
 
 
@@ -43,26 +41,9 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _F():
-    from stgcn_amd import functional as F
-    return F
-
-
-def _math(name):
-    F = _F()
-    return {"f32": F.MATH_F32, "bf16x3": F.MATH_BF16X3, "bf16": F.MATH_BF16, "f32_valu": F.MATH_F32_VALU, "f16mx": F.MATH_F16MX}[name]
-
-
 # ---- the table ------------------------------------------------------------------------------------------------------------------
-class Case:
-    """``make(dev)`` prepares inputs and references OUTSIDE the hostile block and returns ``(run, gate)``: ``run()`` calls the
-    entry point(s) and returns {name: output tensor}, ``gate(outputs)`` holds them to the existing test's reference and gate.
-    ``bitwise``: the outputs of the two runs must be identical."""
-
-    def __init__(self, id, make, bitwise):
-        self.id, self.make, self.bitwise = id, make, bitwise
-
-
+# A case (tests/_util.py::HostileCase): ``make(dev)`` prepares inputs and references OUTSIDE the hostile block - where a family is
+# shared with the non-finite contract, from its tests/entry_points.py setup - and returns ``(run, gate)``.
 CASES = []
 
 
@@ -70,57 +51,17 @@ def add(id, bitwise, make, *args):
     CASES.append(Case(id, functools.partial(make, *args), bitwise))
 
 
-def _finite(out, what):
-    for k, t in out.items():
-        if t is not None and t.is_floating_point():
-            assert torch.isfinite(t).all(), f"{what}: {k} is not finite under poisoned buffers"
-
-
-def run_under_both_fills(case, dev):
-    run, gate = case.make(dev)
-    outs = []
-    for fill in FILLS:
-        with hostile_allocations(fill) as h:
-            out = run()
-            torch.cuda.synchronize()
-            h.check()
-        assert h.records, f"{case.id}: no allocation went through torch.empty - the case would test nothing"
-        what = f"{case.id} fill=0x{fill:02X}"
-        _finite(out, what)
-        gate(out, what)
-        outs.append(out)
-    if case.bitwise:
-        for k in outs[0]:
-            a, b = outs[0][k], outs[1][k]
-            assert (a is None) == (b is None), k
-            assert a is None or torch.equal(a, b), f"{case.id}: {k} differs between the NaN-filled and the huge-filled run"
-
-
 # ---- inference: graph conv --------------------------------------------------------------------------------------------------------
-AGCN_SHAPES = [(2, 3, 64, 9, 25), (1, 64, 64, 7, 22), (1, 3, 128, 30, 64)]       # (N, Cin, Cout, T, V); the second: identity residual
-
-
 def make_agcn(N, cin, cout, T, V, dev):
-    from oracle import stgcn_oracle as so
-    F = _F()
-    gcn, _, gp, _, gen = _random_stem(V, None, 3000 + cin + cout + T + V, dev, cin=cin, c=cout)
-    x = torch.randn(N, cin, T, V, generator=gen)
-    aux = {}
-    yr = so.agcn_forward(x.double(), gp.to(torch.float64), aux=aux)
-    st = gcn._staged(dev)
-    gcn._folded(st)
-    xd = x.to(dev)
-
-    def run():
-        y, P = F.agcn_forward(xd, st["A_eff"], st["Wa"], st["ba"], st["Wb"], st["bb"], st["Wd"], st["bd"], st["Wdown"], st["bdown"],
-                              st["bn_scale"], st["bn_shift"], st["down_scale"], st["down_shift"])
-        return {"y": y, "P": P, "P_attention": F.agcn_attention(xd, st["A_eff"], st["Wa"], st["ba"], st["Wb"], st["bb"])}
+    s = ep.agcn(N, cin, cout, T, V)
+    ref = s.reference(s.x)
+    run, xd = s.on(dev), s.x.to(dev)
 
     def gate(o, what):
-        parity_gate(o["y"], yr, 1e-4, f"{what} y")
-        parity_gate(o["P"], aux["P"], 1e-4, f"{what} P")
-        parity_gate(o["P_attention"], aux["P"], 1e-4, f"{what} P (agcn_attention)")
-    return run, gate
+        parity_gate(o["y"], ref["y"], 1e-4, f"{what} y")
+        parity_gate(o["P"], ref["P"], 1e-4, f"{what} P")
+        parity_gate(o["P_attention"], ref["P_attention"], 1e-4, f"{what} P (agcn_attention)")
+    return (lambda: run(xd)), gate
 
 
 for _s in AGCN_SHAPES:
@@ -128,69 +69,17 @@ for _s in AGCN_SHAPES:
 
 
 # ---- inference: temporal conv -----------------------------------------------------------------------------------------------------
-# (Cin, Cout, K, stride, T, V, N, math, bf16 output, along V).  The last frame-axis shape is not in the five of the ragged test: it is
-# the smallest one the eight-wave kernel (tcn_bf16_v4_kernel) serves, so that all six kernels occur (test_tcn_cases_...).
-TCN_SHAPES = [(ci, co, K, s, T, V, 2, m, False, False)
-              for ci, co, K, s, T, V in [(128, 128, 9, 1, 41, 22), (32, 128, 9, 1, 23, 22), (64, 128, 9, 2, 40, 22), (48, 96, 9, 1, 20, 22),
-                                         (128, 128, 4, 1, 19, 22)] for m in ("f32", "bf16x3", "bf16")]
-TCN_SHAPES += [(3, 70, 9, 1, 7, 46, 3, "f32_valu", False, False),
-               (16, 16, 5, 2, 5, 25, 2, "f32_valu", False, True),
-               (64, 64, 9, 1, 33, 25, 5, "bf16x3", True, False), (128, 256, 9, 1, 70, 25, 6, "bf16x3", True, False),   # odd T*V, half-size y
-               (16, 128, 9, 1, 40, 7, 2, "bf16x3", False, False)]
-TCN_KERNELS = {"tcn_valu_kernel", "tcn_valu_joint_axis_kernel", "tcn_mfma_f32_kernel", "tcn_mfma_bf16_kernel", "tcn_bf16_v4_kernel",
-               "tcn_bf16_v6_kernel"}
-
-
-def _tcn_mode(cin, cout, K, stride, T, V, math, along_v):
-    """The arithmetic the call runs in (Unit2D's rule: what the matrix-core kernels do not cover goes to the VALU kernel) and the
-    kernel the library names for it."""
-    from stgcn_amd import _capi
-    F = _F()
-    mode = _math(math)
-    if not along_v and math != "f32_valu" and not F.tcn_supported(cin, cout, T, V, K, stride, mode):
-        mode = F.MATH_F32_VALU
-    fl = F._flags(mode, False) | (_capi.CONV_ALONG_V if along_v else 0)
-    return mode, _capi.lib().stgcn_tcn_kernel_name(cin, cout, T, V, K, stride, fl).decode()
-
-
 def make_tcn(cin, cout, K, stride, T, V, N, math, out_bf16, along_v, dev):
-    from stgcn_amd import Unit2D
-    from oracle import stgcn_oracle as so
-    F = _F()
-    gen = torch.Generator().manual_seed(cin + cout + K + T)
-    torch.manual_seed(5)
-    m = Unit2D(cin, cout, kernel_size=K, stride=stride, dim=3 if along_v else 2)
-    with torch.no_grad():
-        m.conv.bias.copy_(torch.randn(cout, generator=gen) * 0.1)
-        m.bn.weight.copy_(torch.rand(cout, generator=gen) + 0.5)
-        m.bn.bias.copy_(torch.randn(cout, generator=gen) * 0.2)
-        m.bn.running_mean.copy_(torch.randn(cout, generator=gen) * 0.3)
-        m.bn.running_var.copy_(torch.rand(cout, generator=gen) + 0.25)
-    x = torch.randn(N, cin, T, V, generator=gen)
-    sd = {k: v.clone() for k, v in m.state_dict().items()}
-    if along_v:                                                    # test_unit2d_dim3: the same op on the (T,V)-transposed tensor
-        sd["conv.weight"] = sd["conv.weight"].permute(0, 1, 3, 2)
-        tp = so.tcn_params_from_state(sd, stride=stride).to(torch.float64)
-        ref = so.tcn_forward(x.double().transpose(2, 3), tp).transpose(2, 3)
-    else:
-        ref = so.tcn_forward(x.double(), so.tcn_params_from_state(sd, stride=stride).to(torch.float64))
-    st = m.to(dev).eval()._staged(dev)
-    mode, _ = _tcn_mode(cin, cout, K, stride, T, V, math, along_v)
-    xd = x.to(dev)
-
-    def run():
-        Wp = F.tcn_pack(st["W"], st["scale"], mode)
-        out = {"y_packed": F.tcn_forward_packed(xd, Wp, st["shift"], cout, K, stride, mode, out_bf16, along_v=along_v)}
-        if not along_v:
-            out["y_one_shot"] = F.tcn_forward(xd, st["W"], st["scale"], st["shift"], stride, mode, out_bf16)
-        return out
+    s = ep.tcn(cin, cout, K, stride, T, V, N, math, out_bf16, along_v)
+    ref = s.reference(s.x)
+    run, xd = s.on(dev, pack_every_run=True), s.x.to(dev)
 
     def gate(o, what):
         rel, strict = (BF16_OUT_GATE, False) if out_bf16 else MATH_GATES[math]
         for k, y in o.items():
             assert y.dtype == (torch.bfloat16 if out_bf16 else torch.float32) and y.is_contiguous()
-            parity_gate(y.float(), ref, rel, f"{what} {k}", strict)
-    return run, gate
+            parity_gate(y.float(), ref[k], rel, f"{what} {k}", strict)
+    return (lambda: run(xd)), gate
 
 
 for _s in TCN_SHAPES:
@@ -202,38 +91,17 @@ def test_tcn_cases_reach_every_kernel():
 
 
 # ---- inference: the fused stem ----------------------------------------------------------------------------------------------------
-# (N, T, V, C).  (1, 30, 64) is in the list of the ragged test, where the modules fall back to two stages: no fused kernel covers
-# 64 joints, so stem_supported leaves it out here.  (2, 2, 52) is test_stem_layout_fusion_is_bit_exact's shape for the 128-pixel
-# kernel (stem_mfma_bf16_kernel), which no other shape of the list reaches.
-STEM_SHAPES = [(3, 37, 22, 128), (2, 9, 46, 128), (1, 1, 22, 128), (2, 23, 7, 128), (1, 30, 64, 128), (17, 20, 22, 128), (3, 40, 22, 256),
-               (2, 2, 52, 128)]
-STEM_MATHS = ("f32", "bf16x3", "bf16", "f16mx")
-STEM_KERNELS = {"stem_mfma_f32_kernel", "stem_mfma_bf16_kernel", "stem_bf16_v4_kernel", "stem_bf16_v6_kernel", "stem_f16mx_kernel"}
-
-
 def _stem_cases():
     F = _F()
     return [(s, m) for s in STEM_SHAPES for m in STEM_MATHS if F.stem_supported(3, s[3], s[1], s[2], 9, 3, _math(m))]
 
 
-def _stem_kernel(shape, math):
-    from stgcn_amd import _capi
-    F = _F()
-    N, T, V, C = shape
-    return _capi.lib().stgcn_stem_kernel_name(3, C, T, V, 9, 3, F._flags(_math(math), False)).decode()
-
-
 @functools.lru_cache(maxsize=None)
 def _stem_setup(N, T, V, C, dev):
-    """Modules, input and the fp64 oracle's result of one stem shape: computed once, shared by the arithmetic modes."""
-    from oracle import stgcn_oracle as so
-    gcn, tcn, gp, tp, gen = _random_stem(V, None, 100 + T + V, dev, c=C)
-    x = torch.randn(N, 3, T, V, generator=gen)
-    aux = {}
-    ref = so.stem_forward(x.double(), gp.to(torch.float64), tp.to(torch.float64), aux=aux)
-    st = gcn._staged(dev)
-    gcn._folded(st)
-    return st, tcn._staged(dev), x.to(dev), ref, aux["gcn"]["P"]
+    """The staged stem, the input on the device and the fp64 oracle's result of one stem shape: computed once, shared by the
+    arithmetic modes."""
+    s = ep.stem(N, T, V, C)
+    return s.on(dev), s.x.to(dev), s.reference(s.x)
 
 
 def _stem_one_call(F, x, st, prep, shift, C, K, fl, oshape, odt):
@@ -255,21 +123,20 @@ def make_stem(shape, math, dev):
     from stgcn_amd import _capi
     F = _F()
     N, T, V, C = shape
-    st, ts, xd, ref, P_ref = _stem_setup(N, T, V, C, dev)
+    staged, xd, ref = _stem_setup(N, T, V, C, dev)
+    ref, P_ref = ref["out"], ref["P"]
     mode = _math(math)
     variants = list(itertools.product((False, True), (False, True)))           # (channels-last output, bf16 output)
 
     def run():
         out = {}
-        prep = F.stem_prepare(st["Wd"], st["bd"], st["Wdown"], st["bdown"], st["bn_scale"], st["bn_shift"], st["down_scale"],
-                              st["down_shift"], ts["W"], ts["scale"], mode)
+        prep = staged.prepare(mode)
         for cl, b16 in variants:
             tag = f"[{'ntvc' if cl else 'nctv'},{'bf16' if b16 else 'f32'}]"
-            out["out" + tag], out["P" + tag] = F.stem_forward(xd, st["A_eff"], st["Wa"], st["ba"], st["Wb"], st["bb"], prep, ts["shift"],
-                                                              C, 9, mode, b16, channels_last_out=cl)
+            out["out" + tag], out["P" + tag] = staged.forward(xd, prep, mode, "nctv", "ntvc" if cl else "nctv", b16)
             fl = F._flags(mode, b16) | (_capi.OUT_NTVC if cl else 0)
-            o1, out["P_one_call" + tag] = _stem_one_call(F, xd, st, prep, ts["shift"], C, 9, fl, (N, T, V, C) if cl else (N, C, T, V),
-                                                         torch.bfloat16 if b16 else torch.float32)
+            o1, out["P_one_call" + tag] = _stem_one_call(F, xd, staged.st, prep, staged.ts["shift"], C, 9, fl,
+                                                         (N, T, V, C) if cl else (N, C, T, V), torch.bfloat16 if b16 else torch.float32)
             out["out_one_call" + tag] = o1.permute(0, 3, 1, 2) if cl else o1
         return out
 
@@ -307,26 +174,14 @@ def test_stem_cases_reach_every_kernel():
 
 # ---- inference: patch embedding, step statistics ----------------------------------------------------------------------------------
 def make_patch_embed(order, layout, dev):
-    F = _F()
-    N, C, T, V, E = 2, 128, 9, 25, 256
-    g = torch.Generator().manual_seed(61 + (order == "TS"))
-    z = torch.randn(N, C, T, V, generator=g)
-    W, b = torch.randn(E, C, generator=g) / C ** 0.5, torch.randn(E, generator=g) * 0.1
-    pos = torch.randn(1, T if order == "TS" else V, E, generator=g) * 0.05
-    tok = z.permute(0, 2, 3, 1).reshape(N * T, V, C) if order == "ST" else z.permute(0, 3, 2, 1).reshape(N * V, T, C)
-    ref = tok.double() @ W.double().T + b.double()
-    zd = z.to(dev)
-    if layout == "ntvc":
-        zd = zd.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    Wd, bd, pd = W.to(dev), b.to(dev), pos.to(dev)
-
-    def run():
-        return {"e": F.patch_embed(zd, Wd, bd, pd, order=order), "e_no_pos": F.patch_embed(zd, Wd, bd, None, order=order)}
+    s = ep.patch_embed(order, layout)
+    ref = s.reference(s.x)
+    run, zd = s.on(dev), s.x.to(dev)
 
     def gate(o, what):                          # test_patch_embedding_vs_reference: the max-norm criterion at 1e-4
-        parity_gate(o["e"], ref + pos.double(), 1e-4, f"{what} e", strict=False)
-        parity_gate(o["e_no_pos"], ref, 1e-4, f"{what} e without pos", strict=False)
-    return run, gate
+        parity_gate(o["e"], ref["e"], 1e-4, f"{what} e", strict=False)
+        parity_gate(o["e_no_pos"], ref["e_no_pos"], 1e-4, f"{what} e without pos", strict=False)
+    return (lambda: run(zd)), gate
 
 
 for _o, _l in itertools.product(("ST", "TS"), ("nctv", "ntvc")):
@@ -372,20 +227,13 @@ for _n, _c in ((300, 28), (1, 2)):
 
 # ---- inference: ST-TR spatial attention -------------------------------------------------------------------------------------------
 def make_st_attention(N, cin, cout, T, V, dev):
-    sd = R.make_state(cin, cout, V, 7)
-    x = R.make_input(N, cin, T, V, 8)
-    m = _unit(cin, cout, V, sd).eval()
-    m._folded(m._staged(dev))
-    ref, _ = R.forward64({k: v.double() if v.is_floating_point() else v for k, v in sd.items()}, x.double(), False)
-    xd = x.to(dev)
-
-    def run():
-        with torch.no_grad():
-            return {"y": m(xd)}
+    s = ep.st_attention(N, cin, cout, T, V)
+    run, xd = s.on(dev), s.x.to(dev)
+    ref = s.reference(s.x)["y"]
 
     def gate(o, what):
         parity_gate(o["y"], ref, what=f"{what} eval vs fp64")
-    return run, gate
+    return (lambda: run(xd)), gate
 
 
 for _s in [(2, 131, 128, 12, 22), (5, 64, 128, 33, 25), (2, 256, 512, 3, 46)]:
@@ -395,38 +243,21 @@ for _s in [(2, 131, 128, 12, 22), (5, 64, 128, 33, 25), (2, 256, 512, 3, 46)]:
 # ---- inference: the AltFormer heads -----------------------------------------------------------------------------------------------
 LINEAR_M = (1, 129, 300)
 LINEAR_KN = ((32, 64), (96, 100), (256, 200), (512, 1536))       # the first two are new: K below a k-step of the large tile, Nout off every tile
-TILE_FORMS = {(128, 128): 0, (64, 64): 0x20000, (32, 64): 0x30000}
 
 
 def make_vit_linear(M, K, Nout, math, dev):
     from stgcn_amd import _capi
-    F = _F()
     assert (_capi.VIT_TILE_64, _capi.VIT_TILE_32) == (TILE_FORMS[(64, 64)], TILE_FORMS[(32, 64)])
-    mode = _math(math)
-    assert F.vit_linear_supported(M, K, Nout, mode)
-    g = torch.Generator().manual_seed(M + K + Nout)
-    x = torch.randn(M, K, generator=g) * (0.25 + 3.75 * torch.rand(M, 1, generator=g)) + torch.randn(M, 1, generator=g)
-    W = (torch.rand(Nout, K, generator=g) * 2 - 1) / K ** 0.5
-    b = torch.randn(Nout, generator=g) * 0.5
-    Rr = torch.randn(M, Nout, generator=g)
-    lw, lb = 1 + 0.2 * torch.randn(K, generator=g), 0.1 * torch.randn(K, generator=g)
-    xn = TF.layer_norm(x.double(), (K,), lw.double(), lb.double(), ar.EPS)
-    want = {"off": x.double() @ W.double().T, "on": TF.gelu(xn @ W.double().T + b.double()) + Rr.double()}
-    xd, Wd, bd, Rd, lwd, lbd = (t.to(dev) for t in (x, W, b, Rr, lw, lb))
-
-    def run():
-        out = {}
-        for tile, fl in TILE_FORMS.items():
-            assert F.vit_linear_tile(M, K, Nout, mode | fl) == tile
-            out[f"on{tile}"] = F.vit_linear(xd, Wd, bd, ln=(lwd, lbd, ar.EPS), residual=Rd, gelu=True, math=mode | fl)
-            out[f"off{tile}"] = F.vit_linear(xd, Wd, None, math=mode | fl)
-        return out
+    assert _F().vit_linear_supported(M, K, Nout, _math(math))
+    s = ep.vit_linear(M, K, Nout, math)
+    want = s.reference(s.x)
+    run, xd = s.on(dev), s.x.to(dev)
 
     def gate(o, what):
         for k, y in o.items():
-            parity_gate(y, want[k[:2] if k.startswith("on") else "off"], REL, f"{what} {k}")
+            parity_gate(y, want[k], REL, f"{what} {k}")
             assert torch.equal(y, o[k.split("(")[0] + "(128, 128)"]), f"{what} {k}: a tile form changes the result"
-    return run, gate
+    return (lambda: run(xd)), gate
 
 
 for _m, (_k, _n), _ma in itertools.product(LINEAR_M, LINEAR_KN, ("f32", "bf16x3")):
@@ -441,54 +272,30 @@ def test_linear_cases_reach_every_tile_form():
 
 
 def make_vit_attention(L, hd, dev):
-    F = _F()
-    B, heads = 9, 8
-    qkv = peaked_qkv(B, L, heads, hd, 100 * L + hd)
-    want = ar.attention64(qkv, heads, hd ** -0.5)
-    qd = qkv.to(dev)
-
-    def run():
-        return {"out": F.vit_attention(qd, heads)}
+    s = ep.vit_attention("resident", 9, L, hd)
+    want = s.reference(s.x)["out"]
+    run, qd = s.on(dev), s.x.to(dev)
 
     def gate(o, what):
         parity_gate(o["out"], want, REL, what)
-    return run, gate
+    return (lambda: run(qd)), gate
 
 
 for _L, _hd in itertools.product((1, 33, 65, 256), (32, 64)):
     add(f"vit_attention-L{_L}-hd{_hd}", True, make_vit_attention, _L, _hd)
 
 
-def _block_inputs(B, L, D, hidden, dev):
-    sd = ar.random_block_state(D, hidden, True, seed=B + L + D)
-    g = torch.Generator().manual_seed(L)
-    x = torch.randn(B, L, D, generator=g) * (0.25 + 3.75 * torch.rand(B, L, 1, generator=g)) + torch.randn(B, L, 1, generator=g)
-    sdd = {k: v.to(dev) for k, v in sd.items()}
-    pair = lambda n: (sdd[n + ".weight"], sdd[n + ".bias"])       # noqa: E731
-    return x, sd, (pair("norm1"), pair("attn.qkv"), pair("attn.proj"), pair("norm2"), pair("mlp.fc1"), pair("mlp.fc2"))
-
-
 def make_vit_block(B, L, D, heads, hidden, mode, dev):
     from stgcn_amd import _capi
-    from stgcn_amd.altformer import HEAD_MATH
-    F = _F()
-    assert F.vit_block_supported(L, D, heads, hidden)
-    x, sd, params = _block_inputs(B, L, D, hidden, dev)
-    xd = x.to(dev)
-    if B * L > 4096:                           # the fp64 restatement on the device: the CPU would take tens of seconds
-        want = ar.block64(xd, {k: v.to(dev) for k, v in sd.items()}, heads=heads)[0].cpu()
-    else:
-        want = ar.block64(x, sd, heads=heads)[0]
-    math = HEAD_MATH[mode]
-
-    def run():
-        return {"y": F.vit_block_forward(xd, *params, heads, ar.EPS, (D // heads) ** -0.5, math),
-                "y_auto_tiles": F.vit_block_forward(xd, *params, heads, ar.EPS, (D // heads) ** -0.5, math | _capi.VIT_TILE_AUTO)}
+    assert _F().vit_block_supported(L, D, heads, hidden)
+    s = ep.vit_block(B, L, D, heads, hidden, mode)
+    run, xd = s.on(dev), s.x.to(dev)
+    want = s.reference(xd if B * L > 4096 else s.x)["y"]      # the fp64 restatement on the device: the CPU would take tens of seconds
 
     def gate(o, what):
         parity_gate(o["y"], want, REL, f"{what} y")
         assert torch.equal(o["y_auto_tiles"], o["y"]), f"{what}: VIT_TILE_AUTO changes the result"
-    return run, gate
+    return (lambda: {"y": run(xd)["y"], "y_auto_tiles": run(xd, _capi.VIT_TILE_AUTO)["y"]}), gate
 
 
 # the third: 33,000 tokens = two slabs of the block entry point, 1489 and 11 sequences - the last slab is short
@@ -500,46 +307,26 @@ for _s, _mo in itertools.product([(7, 1, 256, 8, 512), (3, 65, 512, 8, 1024), (1
 def make_agcn_train(cin, cout, N, T, V, want_dx, frozen, dev):
     """Through the module (autograd.Function -> agcn_forward_train -> agcn_backward_train), as test_unit_agcn_backward_vs_oracle,
     test_unit_agcn_generic_backward_vs_oracle and test_eval_mode_backward_unit_agcn_vs_oracle do."""
-    from oracle import stgcn_oracle as so
-    gcn, _, gp, _, gen = _random_stem(V, None, 2000 + cin + cout + T + V, dev, cin=cin, c=cout)
-    gp = gp.to(torch.float64)
-    leaves = _agcn_oracle_leaves(gp)
-    x = torch.randn(N, cin, T, V, generator=gen)
-    xr = x.double().requires_grad_(True)
-    yr = so.agcn_forward(xr, gp, training=not frozen)
-    G = _kink_free_cotangent(yr, gen)
-    names = sorted(leaves)
-    grads = torch.autograd.grad((yr * G.double()).sum(), [leaves[k] for k in names] + [xr])
-    ref = dict(zip(names, grads[:-1]))
-    gcn.train(not frozen)
-    Gd = G.to(dev)
-
-    def run():
-        for p in gcn.parameters():
-            p.grad = None
-        xg = x.to(dev).requires_grad_(want_dx)
-        y = gcn(xg)
-        (y * Gd).sum().backward()
-        out = {"y": y.detach(), "P": gcn.last_attention, **{"d" + k: v for k, v in _agcn_module_grads(gcn).items()}}
-        if want_dx:
-            out["dx"] = xg.grad
-        return out
+    s = ep.agcn_train(cin, cout, N, T, V, want_dx, kink_free=True, frozen=frozen)
+    want = s.reference(s.x)
+    ref = {k: want["d" + k] for k in s.leaves}
+    run = s.on(dev, fresh=False)
 
     def gate(o, what):
-        parity_gate(o["y"], yr.detach(), 1e-4, f"{what} forward")
+        parity_gate(o["y"], want["y"], 1e-4, f"{what} forward")
         got = {k[1:]: v for k, v in o.items() if k[1:] in ref}
         if not frozen:
-            _compare_grads(got, ref, 1e-4)
+            ep.agcn_compare_grads(got, ref, 1e-4)
         else:                                   # behind frozen statistics the conv_d / down biases have real gradients
-            for k in names:
+            for k in s.leaves:
                 scale = ref[k].abs().max().item()
                 if k.startswith("a_b"):
                     scale = max(scale, ref["a_w" + k[3:]].abs().max().item())
                 err = (got[k].reshape(ref[k].shape).double().cpu() - ref[k]).abs().max().item()
                 assert err <= 1e-4 * max(scale, 1e-30), f"{what} d{k}: err {err:.3e} vs 1e-4*{scale:.3e}"
         if want_dx:
-            _grad_gate(o["dx"], grads[-1], 1e-4, f"{what} dx")
-    return run, gate
+            grad_gate(o["dx"], want["dx"], 1e-4, f"{what} dx")
+    return (lambda: run(s.x)), gate
 
 
 # not bitwise: the BatchNorm batch sums are fp64 atomicAdd (train_bn.hip: sums[c], sums[C + c]) and the moment form adds its
@@ -556,49 +343,19 @@ TCN_TRAIN_SHAPES = [(128, 128, 9, 1, 3, 21, 22, True), (64, 128, 9, 2, 2, 21, 22
 
 def make_tcn_train(cin, cout, K, stride, N, T, V, bias, math, dev):
     """test_unit2d_backward_vs_oracle, through the module (tcn_forward_train -> tcn_backward_train)."""
-    from stgcn_amd import Unit2D, set_math_mode
-    from oracle import stgcn_oracle as so
-    torch.manual_seed(900 + cin + K + V)
-    gen = torch.Generator().manual_seed(901 + cin + K + V)
-    m = Unit2D(cin, cout, kernel_size=K, stride=stride, bias=bias)
-    with torch.no_grad():
-        m.bn.weight.copy_(torch.rand(cout, generator=gen) + 0.5)
-        m.bn.bias.copy_(torch.randn(cout, generator=gen) * 0.2)
-        if bias:
-            m.conv.bias.copy_(torch.randn(cout, generator=gen) * 0.1)
-    set_math_mode(m, math)
-    tp = so.tcn_params_from_state(m.state_dict(), stride=stride).to(torch.float64)
-    x = torch.randn(N, cin, T, V, generator=gen)
-    leaves = [tp.conv_w, tp.bn.weight, tp.bn.bias] + ([tp.conv_b] if bias else [])
-    for t in leaves:
-        t.requires_grad_(True)
-    xr = x.double().requires_grad_(True)
-    yr = so.tcn_forward(xr, tp, training=True)
-    G = _kink_free_cotangent(yr, gen)
-    grads = torch.autograd.grad((yr * G.double()).sum(), leaves + [xr])
-    m = m.to(dev).train()
-    Gd = G.to(dev)
-
-    def run():
-        for p in m.parameters():
-            p.grad = None
-        xd = x.to(dev).requires_grad_(True)
-        y = m(xd)
-        (y * Gd).sum().backward()
-        out = {"y": y.detach(), "dW": m.conv.weight.grad, "dgamma": m.bn.weight.grad, "dbeta": m.bn.bias.grad, "dx": xd.grad}
-        if bias:
-            out["dbias"] = m.conv.bias.grad
-        return out
+    s = ep.tcn_train(cin, cout, K, stride, N, T, V, math, bias=bias, kink_free=True)
+    want = s.reference(s.x)
+    run = s.on(dev, fresh=False)
 
     def gate(o, what):
-        parity_gate(o["y"], yr.detach(), 1e-4, f"{what} forward")
-        _grad_gate(o["dW"].reshape(cout, cin, K), grads[0], 1e-4, f"{what} dW")
-        _grad_gate(o["dgamma"], grads[1], 1e-4, f"{what} dgamma")
-        _grad_gate(o["dbeta"], grads[2], 1e-4, f"{what} dbeta")
-        _grad_gate(o["dx"], grads[-1], 1e-4, f"{what} dx")
+        parity_gate(o["y"], want["y"], 1e-4, f"{what} forward")
+        grad_gate(o["dW"], want["dW"], 1e-4, f"{what} dW")
+        grad_gate(o["dgamma"], want["dgamma"], 1e-4, f"{what} dgamma")
+        grad_gate(o["dbeta"], want["dbeta"], 1e-4, f"{what} dbeta")
+        grad_gate(o["dx"], want["dx"], 1e-4, f"{what} dx")
         if bias:       # analytically zero behind a batch-statistics BatchNorm: rounding noise
-            assert o["dbias"].abs().max().item() <= 1e-3 * grads[2].abs().max().item(), f"{what} dbias"
-    return run, gate
+            assert o["dbias"].abs().max().item() <= 1e-3 * want["dbeta"].abs().max().item(), f"{what} dbias"
+    return (lambda: run(s.x)), gate
 
 
 # not bitwise: float atomicAdd in the channel sums and the VALU weight gradient (tcn_backward.hip: sums, bsum, dW), fp64 atomicAdd
@@ -608,26 +365,12 @@ for _s, _ma in itertools.product(TCN_TRAIN_SHAPES, ("bf16x3", "f32_valu")):
 
 
 # ---- training: ST-TR spatial attention --------------------------------------------------------------------------------------------
-def st_attention_train_gate(yr, g, dx, frozen):
-    """The gate of a gcn_unit_attention training step {"y", "dx", "d" + parameter name} against grads64's (yr, g, dx); shared
-    with tests/test_st_attention_edges_gpu.py."""
-    def gate(o, what):
-        parity_gate(o["y"], yr, what=f"{what} y")
-        for k in g:
-            if k in ZERO_GRAD and not frozen:
-                assert float(o["d" + k].abs().max()) <= 1e-4 * float(g["bn.bias"].abs().max()), f"{what} d{k}"
-            else:
-                parity_gate(o["d" + k], g[k], strict=False, what=f"{what} grad {k}")
-        parity_gate(o["dx"], dx, strict=False, what=f"{what} dx")
-    return gate
-
-
 def make_st_attention_train(N, cin, cout, T, V, frozen, dev):
     """test_gradients_vs_fp64_autograd_and_rng_state (drop-connect mask from the seeded generator) and
     test_without_drop_connect_and_frozen_batchnorm_under_autograd, through the module."""
     sd = R.make_state(cin, cout, V, 21 if frozen else 11)
     x = R.make_input(N, cin, T, V, 22 if frozen else 12)
-    m = _unit(cin, cout, V, sd).train(not frozen)
+    m = ep.st_unit(cin, cout, V, sd).train(not frozen)
     mask = None
     if not frozen:
         torch.manual_seed(99)
@@ -697,9 +440,9 @@ for _s, _ma in itertools.product([(1, 256, 256), (129, 512, 512), (300, 256, 200
 def make_vit_attention_backward(L, hd, dev):
     F = _F()
     B, heads = 9, 8
-    qkv = peaked_qkv(B, L, heads, hd, 100 * L + hd)
+    qkv = ep.peaked_qkv(B, L, heads, hd, 100 * L + hd)
     dout = torch.randn(B, L, heads * hd, generator=torch.Generator().manual_seed(L + hd))
-    _, want = attention_grad64(qkv, dout, heads, hd ** -0.5)
+    _, want = ep.attention_grad64(qkv, dout, heads, hd ** -0.5)
     qd, dd = qkv.to(dev), dout.to(dev)
 
     def run():
@@ -777,7 +520,7 @@ def make_vit_block_train(name, B, mode, dev):
     assert F.vit_block_train_supported(L, D, ar.HEADS, 2 * D)
 
     def run():
-        y, g = run_block(blk, xd, dyd, mode, s1, s2)
+        y, g = ep.run_block(blk, xd, dyd, mode, s1, s2)
         return {"y": y, **{"d" + k: v for k, v in g.items()}}
 
     def gate(o, what):
@@ -811,10 +554,8 @@ def test_every_case_without_the_bitwise_flag_is_a_training_case_with_atomics():
 # check).  ``make(dev)`` prepares everything the call needs with the real queries and returns the call.
 def _stem_args(dev, N=2, T=9, V=22):
     F = _F()
-    st, ts, xd, _, _ = _stem_setup(3, 37, 22, 128, dev)
-    prep = F.stem_prepare(st["Wd"], st["bd"], st["Wdown"], st["bdown"], st["bn_scale"], st["bn_shift"], st["down_scale"], st["down_shift"],
-                          ts["W"], ts["scale"], F.MATH_BF16X3)
-    return F, st, ts, xd, prep
+    staged, xd, _ = _stem_setup(3, 37, 22, 128, dev)
+    return F, staged.st, staged.ts, xd, staged.prepare(F.MATH_BF16X3)
 
 
 def short_tcn_forward(dev):
@@ -832,7 +573,7 @@ def short_stem_forward(dev):
 
 
 def _agcn_train_args(dev, cin, cout):
-    gcn, _, _, _, gen = _random_stem(22, None, 77, dev, cin=cin, c=cout)
+    gcn, _, _, _, gen = ep.random_stem(22, None, 77, dev, cin=cin, c=cout)
     st = gcn.train()._staged(dev)
     bn, d = gcn.bn, gcn.down[1]
     x = torch.randn(2, cin, 12, 22, generator=gen).to(dev)
@@ -882,7 +623,7 @@ def short_tcn_backward_train(dev):
 
 def _st_args(dev):
     N, cin, cout, T, V = 2, 131, 128, 12, 22
-    m = _unit(cin, cout, V, R.make_state(cin, cout, V, 21)).train()
+    m = ep.st_unit(cin, cout, V, R.make_state(cin, cout, V, 21)).train()
     st = m._staged(dev)
     x = R.make_input(N, cin, T, V, 22).to(dev)
     tup = lambda b: (b.weight.detach(), b.bias.detach(), b.running_mean.clone(), b.running_var.clone())      # noqa: E731
@@ -914,8 +655,8 @@ def short_st_attention_backward(dev):
 
 def short_vit_block_forward(dev):
     F = _F()
-    x, _, params = _block_inputs(3, 22, 256, 512, dev)
-    xd = x.to(dev)
+    x, sd = ep.block_inputs(3, 22, 256, 512)
+    xd, params = x.to(dev), ep.block_params(sd, dev)
     return lambda: F.vit_block_forward(xd, *params, 8, ar.EPS, 32 ** -0.5, F.MATH_F32)
 
 
@@ -932,8 +673,8 @@ def short_vit_layernorm_backward(dev):
 
 
 def _block_train_args(dev):
-    x, _, params = _block_inputs(3, 22, 256, 512, dev)
-    return x.to(dev), [t for pair in params for t in pair]
+    x, sd = ep.block_inputs(3, 22, 256, 512)
+    return x.to(dev), [t for pair in ep.block_params(sd, dev) for t in pair]
 
 
 def short_vit_block_forward_train(dev):

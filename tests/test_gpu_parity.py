@@ -9,6 +9,9 @@ import pytest
 import torch
 
 from _util import MATH_GATES, gather_flat, load_golden, parity_gate, sub_state
+from _util import grad_gate as _grad_gate, kink_free_cotangent as _kink_free_cotangent
+from entry_points import (agcn_compare_grads as _compare_grads, agcn_module_grads as _agcn_module_grads,
+                          agcn_oracle_leaves as _agcn_oracle_leaves, random_stem as _random_stem)
 
 pytestmark = pytest.mark.gpu
 
@@ -132,32 +135,6 @@ def test_stem_vs_golden(case, fused, math, dev):
 # ---------------------------------------------------------------------------------------
 # seeded comparisons against the oracle at shapes the fixtures do not hold (ragged tiles, odd V)
 # ---------------------------------------------------------------------------------------
-def _random_stem(V, graph, seed, dev, cin=3, c=128):
-    from stgcn_amd import Unit2D, unit_agcn
-    from oracle import stgcn_oracle as so
-    torch.manual_seed(seed)
-    gen = torch.Generator().manual_seed(seed)
-    A = torch.rand(3, V, V, generator=gen) * (torch.rand(3, V, V, generator=gen) < 0.15) if graph is None else graph
-    gcn = unit_agcn(cin, c, A.clone())
-    tcn = Unit2D(c, c, kernel_size=9)
-    with torch.no_grad():
-        gcn.PA.data = torch.randn(3, V, V, generator=gen) * 0.05
-        for m in list(gcn.modules()) + list(tcn.modules()):
-            if isinstance(m, torch.nn.BatchNorm2d):
-                m.weight.copy_(torch.rand(m.num_features, generator=gen) + 0.5)
-                m.bias.copy_(torch.randn(m.num_features, generator=gen) * 0.2)
-                m.running_mean.copy_(torch.randn(m.num_features, generator=gen) * 0.3)
-                m.running_var.copy_(torch.rand(m.num_features, generator=gen) * 1.5 + 0.25)
-            if isinstance(m, torch.nn.Conv2d):
-                m.bias.copy_(torch.randn(m.bias.shape, generator=gen) * 0.1)
-        for cv in list(gcn.conv_a) + list(gcn.conv_b):
-            cv.weight.mul_(3.0)
-    gcn.A = A.clone()
-    gp = so.agcn_params_from_state(gcn.state_dict(), gcn.A)
-    tp = so.tcn_params_from_state(tcn.state_dict())
-    return gcn.to(dev).eval(), tcn.to(dev).eval(), gp, tp, gen
-
-
 @pytest.mark.parametrize("math", ["f32", "bf16x3"])
 @pytest.mark.parametrize("N,T,V", [(3, 37, 22), (2, 9, 46), (1, 5, 22), (2, 64, 25), (1, 1, 22), (2, 23, 7), (1, 30, 64)])
 @pytest.mark.parametrize("fused", [False, True])
@@ -659,23 +636,6 @@ def test_two_stage_path_accepts_channels_last_input(dev):
 # ---------------------------------------------------------------------------------------
 # SURVEY §8(f) rank 2 — backward of the training-mode blocks, against autograd through the fp64 oracle
 # ---------------------------------------------------------------------------------------
-def _grad_gate(got, ref, rel, what):
-    got, ref = got.double().cpu(), ref.double().cpu()
-    assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
-    assert torch.isfinite(got).all(), f"{what}: non-finite gradient"
-    scale = ref.abs().max().item()
-    err = (got - ref).abs().max().item()
-    assert err <= rel * max(scale, 1e-30), f"{what}: max abs err {err:.3e} > {rel:g} * max|ref| ({scale:.3e})"
-
-
-def _kink_free_cotangent(y_ref, gen):
-    """Random dL/dy that is zero where the reference output sits within 1e-4*max of the ReLU kink.  The gradient is
-    discontinuous there: an output of 1e-6 that the fp32 path rounds to 0 flips one mask bit and moves dbeta of its
-    channel by a whole |dL/dy| — a property of ReLU, not an arithmetic error — so those outputs carry no cotangent."""
-    G = torch.randn(y_ref.shape, generator=gen)
-    return G * (y_ref.detach() > 1e-4 * y_ref.detach().abs().max()).float()
-
-
 @pytest.mark.parametrize("math", ["bf16x3", "f32", "f32_valu"])
 @pytest.mark.parametrize("cin,cout,K,stride,N,T,V,bias", [
     (128, 128, 9, 1, 3, 21, 22, True),     # the stem's block: matrix-core wgrad + forward kernel as dgrad
@@ -732,50 +692,6 @@ def test_unit2d_backward_vs_oracle(cin, cout, K, stride, N, T, V, bias, math, de
     if bias:   # analytically zero behind a batch-statistics BatchNorm: both sides are rounding noise
         assert m.conv.bias.grad.abs().max().item() <= 1e-3 * grads[2].abs().max().item()
         assert grads[3].abs().max().item() <= 1e-6 * grads[2].abs().max().item()
-
-
-def _agcn_oracle_leaves(gp):
-    leaves = {"PA": gp.PA, "bn_w": gp.bn.weight, "bn_b": gp.bn.bias}
-    if gp.down_w is not None:
-        leaves.update({"down_w": gp.down_w, "down_b": gp.down_b, "dbn_w": gp.down_bn.weight, "dbn_b": gp.down_bn.bias})
-    for i in range(gp.num_subset):
-        leaves.update({f"a_w{i}": gp.conv_a_w[i], f"a_b{i}": gp.conv_a_b[i], f"b_w{i}": gp.conv_b_w[i],
-                       f"b_b{i}": gp.conv_b_b[i], f"d_w{i}": gp.conv_d_w[i], f"d_b{i}": gp.conv_d_b[i]})
-    for t in leaves.values():
-        t.requires_grad_(True)
-    return leaves
-
-
-def _agcn_module_grads(gcn):
-    g = {"PA": gcn.PA.grad, "bn_w": gcn.bn.weight.grad, "bn_b": gcn.bn.bias.grad}
-    if gcn._has_down():
-        g.update({"down_w": gcn.down[0].weight.grad.flatten(1), "down_b": gcn.down[0].bias.grad,
-                  "dbn_w": gcn.down[1].weight.grad, "dbn_b": gcn.down[1].bias.grad})
-    for i in range(gcn.num_subset):
-        g.update({f"a_w{i}": gcn.conv_a[i].weight.grad.flatten(1), f"a_b{i}": gcn.conv_a[i].bias.grad,
-                  f"b_w{i}": gcn.conv_b[i].weight.grad.flatten(1), f"b_b{i}": gcn.conv_b[i].bias.grad,
-                  f"d_w{i}": gcn.conv_d[i].weight.grad.flatten(1), f"d_b{i}": gcn.conv_d[i].bias.grad})
-    return g
-
-
-def _compare_grads(got, ref, rel):
-    """Every gradient within rel*max|ref| of its tensor.  Three bias gradients are structurally zero — conv_a's (a bias
-    on `a` shifts every column of the Gram matrix by a constant, which soft-max over that column ignores), conv_d's
-    and down's (a bias in front of a batch-statistics BatchNorm): both sides are rounding noise there, so those are
-    held against the scale of the matching weight gradient instead."""
-    bad = []
-    for k in sorted(ref):
-        g, r = got[k].reshape(ref[k].shape).double().cpu(), ref[k].double().cpu()
-        assert torch.isfinite(g).all(), f"d{k}: non-finite gradient"
-        scale = r.abs().max().item()
-        if k.startswith("a_b") or k.startswith("d_b"):       # (d_b, down_b: a bias in front of a batch-statistics
-            scale = max(scale, ref[k[0] + "_w" + k[3:]].abs().max().item())   # BatchNorm has zero gradient as well)
-        if k == "down_b":
-            scale = max(scale, ref["down_w"].abs().max().item())
-        err = (g - r).abs().max().item()
-        if err > rel * max(scale, 1e-30):
-            bad.append(f"d{k}: err {err:.3e} vs {rel:g}*{scale:.3e}")
-    assert not bad, "; ".join(bad)
 
 
 @pytest.mark.parametrize("N,T,V,cout", [(3, 20, 22, 128), (2, 50, 22, 128), (2, 12, 46, 128), (2, 9, 25, 64), (1, 7, 22, 256)])

@@ -25,7 +25,7 @@ def dev():
 @pytest.mark.parametrize("case", nc.CASES, ids=lambda c: c.id)
 def test_one_planted_value_is_neither_hidden_nor_leaked(case, dev):
     prep = case.prepare()
-    run = prep.device(dev)
+    run = prep.on(dev)
     clean = run(prep.x)
     for name, t in clean.items():
         assert bool(torch.isfinite(t.float()).all()), f"{case.id}: {name} of the clean input is not finite"
@@ -41,8 +41,8 @@ def test_one_planted_value_is_neither_hidden_nor_leaked(case, dev):
 
 
 def test_cases_reach_every_kernel_the_plans_can_name():
-    from test_buffer_discipline_gpu import STEM_KERNELS, TCN_KERNELS
-    F = nc._F()
+    from entry_points import STEM_KERNELS, TCN_KERNELS, hipF
+    F = hipF()
     assert {c.kernel for c in nc.CASES if c.id.startswith("tcn-")} == TCN_KERNELS
     assert {c.kernel for c in nc.CASES if c.id.startswith("stem_fused-")} == STEM_KERNELS
     agcn = [tuple(map(int, c.id.split("-")[1].split("x"))) for c in nc.CASES if c.id.startswith("agcn-")]

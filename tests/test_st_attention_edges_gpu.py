@@ -321,7 +321,7 @@ def test_mixed_batchnorm_modes_and_wrong_shapes_are_refused():
 
 # ---- poisoned buffers ----------------------------------------------------------------------------------------------------------------------
 def make_edge_train(name, dev):
-    from test_buffer_discipline_gpu import st_attention_train_gate
+    from _util import st_attention_train_gate
     c, sd, x, dy, mask, yr, _, g, dx = _ref(name)
     m = _case_module(c, sd)
     dyd = dy.to(dev)
@@ -333,5 +333,5 @@ def test_edge_steps_under_poisoned_guarded_buffers(name):
     """Every output and workspace pre-filled with NaN, then with 3.4e38, between guard bands: an empty split of
     cv_stats_kernel that left its ``parts`` unwritten, or a lane >= V that read or stored, shows as NaN or a trampled guard;
     the two runs agree bit for bit."""
-    from test_buffer_discipline_gpu import Case, run_under_both_fills
+    from _util import HostileCase as Case, run_under_both_fills
     run_under_both_fills(Case(f"st_attention_edge_train-{name}", functools.partial(make_edge_train, name), True), DEV)

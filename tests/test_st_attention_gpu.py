@@ -6,13 +6,13 @@ import torch
 import torch.nn as nn
 
 import st_attention_ref as R
-from _util import parity_gate
+from _util import ZERO_GRAD, parity_gate
+from entry_points import incidence as _incidence, st_unit as _unit  # noqa: F401 (_incidence: borrowed by the edge tests)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
 CASES = {"v22_256_256": (22, 256, 256, 6), "v46_131_256": (46, 131, 256, 4), "v46_256_512": (46, 256, 512, 2),
          "v22_512_512": (22, 512, 512, 2)}
-ZERO_GRAD = ("attention_conv.attn_out.bias",)     # analytically 0 behind a batch-statistics BatchNorm
 
 
 def _fixture():
@@ -20,19 +20,6 @@ def _fixture():
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "st_attention_reference.npz")
     with np.load(path, allow_pickle=False) as z:
         return {k: z[k] for k in z.files}
-
-
-def _incidence(V):
-    g = torch.Generator().manual_seed(V)
-    return (torch.rand(3, V, V, generator=g) > 0.8).float()
-
-
-def _unit(cin, cout, V, sd=None, drop_connect=True):
-    from stgcn_amd import gcn_unit_attention
-    m = gcn_unit_attention(cin, cout, _incidence(V), **R.unit_kwargs(V, drop_connect))
-    if sd is not None:
-        m.load_state_dict(sd, strict=True)
-    return m.to(DEV)
 
 
 def _pick(z, key, t):

@@ -145,6 +145,6 @@ def test_a_non_finite_pixel_inside_a_short_tile(index, value, dev):
     assert index[2] * 22 + index[3] >= 256 and _short_blocks(17, 22) > 0
     case = nc.Case("stem_fused-short_tile-2x17x22x128-bf16x3", functools.partial(nc.prepare_stem_fused, shape, "bf16x3"), "bf16x3")
     prep = case.prepare()
-    run = prep.device(dev)
+    run = prep.on(dev)
     xp = nc.plant(prep.x, index, value)
     nc.check(case, prep, index, value, run(xp), prep.reference(xp), f"{case.id} {value}@{index}")

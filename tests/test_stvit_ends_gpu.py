@@ -13,7 +13,7 @@ import stvit_ref as sr
 import stvit_train_ref as vr
 from _util import MATH_GATES, load_golden, parity_gate
 from test_altformer_train_gpu import TRAIN_STRICT, gate_stored
-from test_buffer_discipline_gpu import Case, run_under_both_fills
+from _util import HostileCase as Case, run_under_both_fills
 
 pytestmark = pytest.mark.gpu
 REL = MATH_GATES["f32"][0]

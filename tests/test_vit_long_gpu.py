@@ -8,6 +8,7 @@ import torch
 
 import altformer_ref as ar
 from _util import MATH_GATES, hostile_allocations, parity_gate
+from entry_points import peaked_qkv
 
 pytestmark = pytest.mark.gpu
 REL = MATH_GATES["f32"][0]
@@ -21,13 +22,6 @@ def dev():
     import stgcn_amd
     stgcn_amd.lib()          # fail loudly if the HIP library is missing
     return torch.device("cuda:0")
-
-
-def peaked_qkv(B, L, heads, hd, seed, amp=2.3):
-    g = torch.Generator().manual_seed(seed)
-    qkv = torch.randn(B, L, 3, heads, hd, generator=g)
-    qkv[:, :, :2] *= amp                         # scores ~ N(0, amp^4): with 2.3 they reach about +-28 at head_dim ** -0.5
-    return qkv.reshape(B, L, 3 * heads * hd)
 
 
 @functools.lru_cache(maxsize=None)

@@ -12,6 +12,7 @@ import torch.nn as nn
 import altformer_ref as ar
 import altformer_train_ref as tr
 from _util import MATH_GATES, hostile_allocations, parity_gate
+from entry_points import attention_grad64, peaked_qkv
 from test_altformer_train_gpu import TRAIN_STRICT, PinnedMax, compare_grads, set_force_torch, step
 from test_vit_long_gpu import PLANTED_B, PLANTED_HD, PLANTED_HEADS, PLANTED_L, planted_case
 
@@ -27,21 +28,6 @@ def dev():
     import stgcn_amd
     stgcn_amd.lib()          # fail loudly if the HIP library is missing
     return torch.device("cuda:0")
-
-
-def peaked_qkv(B, L, heads, hd, seed, amp=2.3):
-    g = torch.Generator().manual_seed(seed)
-    qkv = torch.randn(B, L, 3, heads, hd, generator=g)
-    qkv[:, :, :2] *= amp                         # scores ~ N(0, amp^4): with 2.3 they reach about +-28 at head_dim ** -0.5
-    return qkv.reshape(B, L, 3 * heads * hd)
-
-
-def attention_grad64(qkv, dout, heads, scale):
-    """(out, dqkv) by fp64 autograd of the restated attention, where the tensors are."""
-    q = qkv.double().requires_grad_(True)
-    out = ar.attention64(q, heads, scale)
-    out.backward(dout.double())
-    return out.detach(), q.grad
 
 
 @functools.lru_cache(maxsize=None)

@@ -5,7 +5,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "st-gcn-altformer_amd")); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
-from test_gpu_parity import _random_stem
+from entry_points import random_stem
 from stgcn_amd import enable_stem_fusion, set_math_mode
 from oracle import stgcn_oracle as so
 
@@ -14,7 +14,7 @@ print("mode      max|err|/max|ref|  rms(err)/rms(ref)   (fused stem, 8 clips, T=
 for math in ("f32", "bf16x3", "bf16"):
     worst, rms = 0.0, 0.0
     for seed in (1, 2, 3):
-        gcn, tcn, gp, tp, gen = _random_stem(22, None, seed, dev)
+        gcn, tcn, gp, tp, gen = random_stem(22, None, seed, dev)
         set_math_mode(tcn, math)
         enable_stem_fusion(gcn, tcn)
         x = torch.randn(8, 3, 180, 22, generator=gen)

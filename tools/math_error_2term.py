@@ -50,7 +50,7 @@ def split(v32, dt, ftz=False):
 
 
 def random_stem(V, seed):
-    """The CPU half of tests/test_gpu_parity.py::_random_stem (same generator sequence, no GPU modules)."""
+    """The CPU half of tests/entry_points.py::random_stem (same generator sequence, no GPU modules)."""
     import stgcn_amd
     torch.manual_seed(seed)
     gen = torch.Generator().manual_seed(seed)
