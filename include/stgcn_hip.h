@@ -346,6 +346,31 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
                                 float *dWqkv, float *dbqkv, float *dWout, float *dbout, float *dbn_weight_grad,
                                 float *dbn_bias_grad, void *ws, size_t ws_bytes, int N, int Cin, int Cout, int dk, int T,
                                 int V, int heads, unsigned flags, void *stream);
+/* Arithmetic of the unit's matrix products (additive to ABI 11).  The low 4 bits of `flags` of stgcn_st_attention_forward_train,
+ * stgcn_st_attention_backward and stgcn_st_attention_forward_math choose how the two 1x1 projections (qkv = Wqkv . xn,
+ * z = Wout . o) and their two input gradients (Wout^T . dz, Wqkv^T . dqkv) are computed: STGCN_MATH_F32 (0, the default: the
+ * fp32 matrix cores, what every caller got before) or STGCN_MATH_BF16X3 (both operands split into bf16 hi + lo, three
+ * v_mfma_f32_16x16x32_bf16 products, fp32 sums; the skip connection is read in that kernel's epilogue).  The weight-gradient
+ * products, the V x V attention and both BatchNorms are fp32 either way.  STGCN_MATH_BF16, STGCN_MATH_F32_VALU and unknown
+ * values return STGCN_ERR_UNSUPPORTED.  The forward and the backward of one step must be called with the SAME flags, the
+ * arithmetic bits like STGCN_BN_FROZEN.  stgcn_st_attention_ws_bytes holds for both arithmetics. */
+int stgcn_st_attention_math_supported(int Cin, int Cout, int dk, int V, int heads, unsigned flags);
+/* stgcn_st_attention_forward with the arithmetic in the low 4 bits of `flags` (0: exactly stgcn_st_attention_forward). */
+int stgcn_st_attention_forward_math(const float *x, const float *dbn_scale, const float *dbn_shift, const float *Wqkv,
+                                    const float *bqkv, const float *Wout, const float *bout, const float *bn_scale,
+                                    const float *bn_shift, void *ws, size_t ws_bytes, float *y, int N, int Cin, int Cout,
+                                    int dk, int T, int V, int heads, unsigned flags, void *stream);
+/* The product of those projections on its own: C[n][m][j] = sum_k W[m][k] X[n][k][j] (+ bias[m]) (+ R[n][m][j]) for n < N,
+ * m < M, j < TV.  W is (M,K) row-major, or (K,M) with w_transposed; X[n] (K,TV), C[n] and R[n] (M,TV) are dense with TV
+ * contiguous; bias and R may be NULL, R may not be C.  The low 4 bits of `flags`: STGCN_MATH_F32 (the strided fp32 GEMM; R is
+ * copied to C and the product accumulated onto it) or STGCN_MATH_BF16X3 (three-term split on the bf16 matrix cores; ragged M,
+ * K and TV are staged as zeros, never loaded; no alignment demand on TV).  Covered: M, K, TV >= 1 with max(M,K)*TV < 2^31, M*K < 2^29,
+ * TV <= 65535*64 and N <= 65535.  Bit-identical between runs.  `ws` may be NULL where the size query gives 0 (it does today). */
+int stgcn_wx_product_supported(int M, int K, long long TV, unsigned flags);   /* 1, or 0: other arithmetic or outside the limits */
+const char *stgcn_wx_product_kernel_name(int M, int K, long long TV, unsigned flags);   /* "" where unsupported */
+size_t stgcn_wx_product_ws_bytes(int M, int K, unsigned flags);
+int stgcn_wx_product(const float *W, const float *X, const float *bias, const float *R, float *C, void *ws, size_t ws_bytes,
+                     int N, int M, int K, long long TV, int w_transposed, unsigned flags, void *stream);
 
 /* ---- AltFormer heads: transformer block (Block of model/AltFormer/model_ST.py:18-88 = model_TS.py, ABI 10) -----------
  * Eval forward only (no dropout, no stochastic depth), tokens in rows, x (B, L, D) dense fp32:

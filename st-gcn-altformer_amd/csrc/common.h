@@ -466,6 +466,14 @@ int launch_rowmix(const float *in, const float *M, float *out, int R, int V, int
 int launch_softmax_bwd(const float *P, const float *A_eff, const float *dP, float *dS, int N, int V, int S, float alpha,
                        hipStream_t st);
 
+// weights times channel-first activations in the three-term split arithmetic (wx_bf16.hip):
+// C[n] = W . X[n] (+ bias per row) (+ R[n]); W (M,K), or (K,M) with w_transposed; X[n] (K,TV); C[n], R[n] (M,TV); R may not overlap C
+bool wx_bf16x3_covers(int M, int K, long long TV);
+int wx_bf16x3_tile_rows(int M);              // rows of the tile form that serves M: 128 or 64
+const char *wx_bf16x3_kernel_name(int M);
+int launch_wx_bf16x3(const float *W, const float *X, const float *bias, const float *R, float *C, int N, int M, int K,
+                     long long TV, bool w_transposed, hipStream_t st);
+
 // first patch embedding of the transformer heads on the stem output (gemm_f32.hip: one strided GEMM per clip)
 int launch_patch_embed(const float *z, const float *W, const float *b, const float *pos, float *out, int N, int C, int E,
                        int T, int V, unsigned flags, hipStream_t st);

@@ -12,7 +12,8 @@
 //   y    = relu(BatchNorm2d(z))
 //
 // Layout: every intermediate keeps the (clip, channel, frame, joint) order of x, so the two projections are plain per-clip
-// GEMMs on the strided fp32-MFMA GEMM (gemm_f32.hip, v_mfma_f32_32x32x2_f32) and the heads' channels are rows of V floats.
+// GEMMs on the strided fp32-MFMA GEMM (gemm_f32.hip, v_mfma_f32_32x32x2_f32) or, with STGCN_MATH_BF16X3 in the flags, on the
+// three-term bf16 kernel of wx_bf16.hip (the weight gradients stay on the former), and the heads' channels are rows of V floats.
 // The V x V part runs in one workgroup (one wave) per (frame, head): lane i owns query row i; the head's keys and values
 // are staged in LDS and read as broadcasts; logits, soft-max and o_h are exact fp32 FMAs in registers, and the V x V
 // weights never leave the chip.  The training forward saves per row (max, sum of exponentials, drop-connect sum) and the
@@ -445,6 +446,31 @@ int gemm_w_x(const float *W, const float *X, float *Cm, const float *bias, int M
     return launch_gemm_f32(g, N, st);
 }
 
+// The arithmetic of the unit's four W . X products, from the low 4 bits of `flags`: f32 (gemm_w_x) or bf16x3 (wx_bf16.hip)
+int check_math(const char *fn, unsigned flags) {
+    const unsigned m = flags & STGCN_MATH_MASK;
+    if (m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3) return STGCN_OK;
+    const char *name = m == STGCN_MATH_BF16 ? "STGCN_MATH_BF16" : m == STGCN_MATH_F32_VALU ? "STGCN_MATH_F32_VALU" : "unknown";
+    return fail(STGCN_ERR_UNSUPPORTED, "%s: arithmetic %u (%s) is not implemented for this product; STGCN_MATH_F32 and "
+                "STGCN_MATH_BF16X3 are", fn, m, name);
+}
+
+// what both arithmetics of the product cover: the f32 GEMM's 32-bit offsets inside a clip and its 64-column grid
+bool wx_covers(int M, int K, long long TV) {
+    if (M < 1 || K < 1 || TV < 1 || TV > 65535LL * 64) return false;
+    return (long long)(M > K ? M : K) * TV <= 0x7fffffffLL && wx_bf16x3_covers(M, K, TV);
+}
+
+// C[n] = W . X[n] (+ bias) (+ R[n]) in the arithmetic of `flags`.  f32: R is copied into C and the product accumulated onto
+// it (the skip connection as it always ran); bf16x3: R is read in the kernel's epilogue.
+int w_x(unsigned flags, const float *W, const float *X, float *Cm, const float *bias, const float *R, int M, int K, long long TV,
+        int N, bool w_transposed, hipStream_t st) {
+    if ((flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3) return launch_wx_bf16x3(W, X, bias, R, Cm, N, M, K, TV, w_transposed, st);
+    if (R && R != Cm)
+        STGCN_HIP_CHECK(hipMemcpyAsync(Cm, R, (size_t)N * M * TV * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return gemm_w_x(W, X, Cm, bias, M, K, TV, N, R ? 1 : 0, w_transposed, st);
+}
+
 // dW = sum_n G[n] . X[n]^T  (G[n] (M, TV), X[n] (K, TV)): per-clip products into `part`, summed in clip order
 int gemm_wgrad(const float *G, const float *X, float *part, float *dW, int M, int K, long long TV, int N, hipStream_t st) {
     GemmArgs g{};
@@ -533,6 +559,39 @@ int stgcn_st_attention_supported(int Cin, int Cout, int dk, int V, int heads) {
     return Cin >= 1 && V >= 1 && V <= kVP && heads_supported(Cout, dk, heads, &dkh, &dvh) ? 1 : 0;
 }
 
+int stgcn_st_attention_math_supported(int Cin, int Cout, int dk, int V, int heads, unsigned flags) {
+    const unsigned m = flags & STGCN_MATH_MASK;
+    return (m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3) && stgcn_st_attention_supported(Cin, Cout, dk, V, heads) ? 1 : 0;
+}
+
+int stgcn_wx_product_supported(int M, int K, long long TV, unsigned flags) {
+    const unsigned m = flags & STGCN_MATH_MASK;
+    return (m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3) && wx_covers(M, K, TV) ? 1 : 0;
+}
+
+const char *stgcn_wx_product_kernel_name(int M, int K, long long TV, unsigned flags) {
+    if (!stgcn_wx_product_supported(M, K, TV, flags)) return "";
+    return (flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3 ? wx_bf16x3_kernel_name(M) : "gemm_f32_kernel";
+}
+
+size_t stgcn_wx_product_ws_bytes(int M, int K, unsigned flags) {
+    (void)M; (void)K; (void)flags;
+    return 0;        // both arithmetics split or read their operands in place
+}
+
+int stgcn_wx_product(const float *W, const float *X, const float *bias, const float *R, float *C, void *ws, size_t ws_bytes,
+                     int N, int M, int K, long long TV, int w_transposed, unsigned flags, void *stream) {
+    REQUIRE_PTR(W); REQUIRE_PTR(X); REQUIRE_PTR(C);
+    (void)ws; (void)ws_bytes;
+    if (N < 1 || M < 1 || K < 1 || TV < 1)
+        return fail(STGCN_ERR_ARG, "wx_product: non-positive dimension (N=%d M=%d K=%d TV=%lld)", N, M, K, TV);
+    if (R == C) return fail(STGCN_ERR_ARG, "wx_product: R may not be C");
+    if (int rc = check_math("wx_product", flags)) return rc;
+    if (!wx_covers(M, K, TV) || N > 65535)
+        return fail(STGCN_ERR_UNSUPPORTED, "wx_product: N=%d M=%d K=%d TV=%lld exceed the grid or 2^31 elements a clip", N, M, K, TV);
+    return w_x(flags, W, X, C, bias, R, M, K, TV, N, w_transposed != 0, (hipStream_t)stream);
+}
+
 size_t stgcn_st_attention_ws_bytes(int N, int Cin, int Cout, int dk, int T, int V, int heads, int pass) {
     if (N < 1 || Cin < 1 || Cout < 1 || dk < 1 || T < 1 || V < 1 || heads < 1 || pass < 0 || pass > 2) return 0;
     const Dims d(N, Cin, Cout, dk, T, V, heads);
@@ -542,13 +601,14 @@ size_t stgcn_st_attention_ws_bytes(int N, int Cin, int Cout, int dk, int T, int 
     return bytes;
 }
 
-int stgcn_st_attention_forward(const float *x, const float *dbn_scale, const float *dbn_shift, const float *Wqkv,
-                               const float *bqkv, const float *Wout, const float *bout, const float *bn_scale,
-                               const float *bn_shift, void *ws, size_t ws_bytes, float *y, int N, int Cin, int Cout,
-                               int dk, int T, int V, int heads, void *stream) {
+int stgcn_st_attention_forward_math(const float *x, const float *dbn_scale, const float *dbn_shift, const float *Wqkv,
+                                    const float *bqkv, const float *Wout, const float *bout, const float *bn_scale,
+                                    const float *bn_shift, void *ws, size_t ws_bytes, float *y, int N, int Cin, int Cout,
+                                    int dk, int T, int V, int heads, unsigned flags, void *stream) {
     REQUIRE_PTR(x); REQUIRE_PTR(dbn_scale); REQUIRE_PTR(dbn_shift); REQUIRE_PTR(Wqkv); REQUIRE_PTR(bqkv);
     REQUIRE_PTR(Wout); REQUIRE_PTR(bout); REQUIRE_PTR(bn_scale); REQUIRE_PTR(bn_shift); REQUIRE_PTR(ws); REQUIRE_PTR(y);
     if (int rc = check_shape("st_attention_forward", N, Cin, Cout, dk, T, V, heads)) return rc;
+    if (int rc = check_math("st_attention_forward", flags)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Dims d(N, Cin, Cout, dk, T, V, heads);
     size_t need = 0;
@@ -556,12 +616,18 @@ int stgcn_st_attention_forward(const float *x, const float *dbn_scale, const flo
     if (ws_bytes < need) return fail(STGCN_ERR_WORKSPACE, "st_attention_forward: workspace %zu < %zu bytes", ws_bytes, need);
     int rc;
     if ((rc = launch_cv_apply(x, dbn_scale, dbn_shift, w.xn, N, Cin, T, V, st))) return rc;
-    if ((rc = gemm_w_x(Wqkv, w.xn, w.qkv, bqkv, d.Cq, Cin, d.TV, N, 0, false, st))) return rc;
+    if ((rc = w_x(flags, Wqkv, w.xn, w.qkv, bqkv, nullptr, d.Cq, Cin, d.TV, N, false, st))) return rc;
     if ((rc = launch_sta_fwd(w.qkv, nullptr, w.o, nullptr, N, T, V, heads, d.dkh, d.dvh, st))) return rc;
-    const bool skip = Cin == Cout;
-    if (skip) STGCN_HIP_CHECK(hipMemcpyAsync(y, x, d.act(Cout) * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if ((rc = gemm_w_x(Wout, w.o, y, bout, Cout, Cout, d.TV, N, skip ? 1 : 0, false, st))) return rc;
+    if ((rc = w_x(flags, Wout, w.o, y, bout, Cin == Cout ? x : nullptr, Cout, Cout, d.TV, N, false, st))) return rc;
     return launch_bn_apply(y, bn_scale, bn_shift, nullptr, nullptr, nullptr, y, d.act(Cout), Cout, d.TV, st);
+}
+
+int stgcn_st_attention_forward(const float *x, const float *dbn_scale, const float *dbn_shift, const float *Wqkv,
+                               const float *bqkv, const float *Wout, const float *bout, const float *bn_scale,
+                               const float *bn_shift, void *ws, size_t ws_bytes, float *y, int N, int Cin, int Cout,
+                               int dk, int T, int V, int heads, void *stream) {
+    return stgcn_st_attention_forward_math(x, dbn_scale, dbn_shift, Wqkv, bqkv, Wout, bout, bn_scale, bn_shift, ws, ws_bytes, y,
+                                           N, Cin, Cout, dk, T, V, heads, STGCN_MATH_F32, stream);
 }
 
 int stgcn_st_attention_forward_train(const float *x, const float *dbn_weight, const float *dbn_bias, float *dbn_running_mean,
@@ -577,6 +643,7 @@ int stgcn_st_attention_forward_train(const float *x, const float *dbn_weight, co
     REQUIRE_PTR(ws); REQUIRE_PTR(y); REQUIRE_PTR(save_qkv); REQUIRE_PTR(save_o); REQUIRE_PTR(save_z);
     REQUIRE_PTR(save_rowstats); REQUIRE_PTR(save_stats);
     if (int rc = check_shape("st_attention_forward_train", N, Cin, Cout, dk, T, V, heads)) return rc;
+    if (int rc = check_math("st_attention_forward_train", flags)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Dims d(N, Cin, Cout, dk, T, V, heads);
     size_t need = 0;
@@ -598,11 +665,9 @@ int stgcn_st_attention_forward_train(const float *x, const float *dbn_weight, co
     if (rc) return rc;
     if ((rc = launch_cv_apply(x, w.dscale, w.dshift, w.xn, N, Cin, T, V, st))) return rc;
     // attention
-    if ((rc = gemm_w_x(Wqkv, w.xn, save_qkv, bqkv, d.Cq, Cin, d.TV, N, 0, false, st))) return rc;
+    if ((rc = w_x(flags, Wqkv, w.xn, save_qkv, bqkv, nullptr, d.Cq, Cin, d.TV, N, false, st))) return rc;
     if ((rc = launch_sta_fwd(save_qkv, mask, save_o, save_rowstats, N, T, V, heads, d.dkh, d.dvh, st))) return rc;
-    const bool skip = Cin == Cout;
-    if (skip) STGCN_HIP_CHECK(hipMemcpyAsync(save_z, x, d.act(Cout) * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if ((rc = gemm_w_x(Wout, save_o, save_z, bout, Cout, Cout, d.TV, N, skip ? 1 : 0, false, st))) return rc;
+    if ((rc = w_x(flags, Wout, save_o, save_z, bout, Cin == Cout ? x : nullptr, Cout, Cout, d.TV, N, false, st))) return rc;
     // BatchNorm2d + ReLU
     if (frozen) {
         rc = launch_bn_frozen_finalize(bn_weight, bn_bias, bn_running_mean, bn_running_var, eps, w.bscale, w.bshift, Cout, st,
@@ -629,6 +694,7 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
     REQUIRE_PTR(dWqkv); REQUIRE_PTR(dbqkv); REQUIRE_PTR(dWout); REQUIRE_PTR(dbout); REQUIRE_PTR(dbn_weight_grad);
     REQUIRE_PTR(dbn_bias_grad); REQUIRE_PTR(ws);
     if (int rc = check_shape("st_attention_backward", N, Cin, Cout, dk, T, V, heads)) return rc;
+    if (int rc = check_math("st_attention_backward", flags)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Dims d(N, Cin, Cout, dk, T, V, heads);
     size_t need = 0;
@@ -648,7 +714,7 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
     // output projection
     if ((rc = gemm_wgrad(w.dz, save_o, w.part, dWout, Cout, Cout, d.TV, N, st))) return rc;
     if ((rc = bias_grad(w.dz, w.part, dbout, Cout, d.TV, N, st))) return rc;
-    if ((rc = gemm_w_x(Wout, w.dz, w.dout, nullptr, Cout, Cout, d.TV, N, 0, true, st))) return rc;
+    if ((rc = w_x(flags, Wout, w.dz, w.dout, nullptr, nullptr, Cout, Cout, d.TV, N, true, st))) return rc;
     // attention
     if ((rc = launch_sta_bwd(save_qkv, w.dout, mask, save_rowstats, w.dqkv, N, T, V, heads, d.dkh, d.dvh, st))) return rc;
     // qkv projection (on data_bn's output, rebuilt from x and the saved statistics)
@@ -657,12 +723,12 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
     if ((rc = gemm_wgrad(w.dqkv, w.xn, w.part, dWqkv, d.Cq, Cin, d.TV, N, st))) return rc;
     if ((rc = bias_grad(w.dqkv, w.part, dbqkv, d.Cq, d.TV, N, st))) return rc;
     if (dx == nullptr) {         // no input gradient: data_bn's parameter gradients still need d(xn)
-        if ((rc = gemm_w_x(Wqkv, w.dqkv, w.dxn, nullptr, Cin, d.Cq, d.TV, N, 0, true, st))) return rc;
+        if ((rc = w_x(flags, Wqkv, w.dqkv, w.dxn, nullptr, nullptr, Cin, d.Cq, d.TV, N, true, st))) return rc;
         if ((rc = launch_cv_stats(x, w.dxn, dmean, dinv, w.parts, w.sums, N, Cin, T, V, st))) return rc;
         return launch_bn_bwd_finalize(w.sums, 1, (double)N * T, dbn_weight, dinv, ddbn_weight, ddbn_bias, w.dcoef, d.CV, st,
                                       frozen);
     }
-    if ((rc = gemm_w_x(Wqkv, w.dqkv, w.dxn, nullptr, Cin, d.Cq, d.TV, N, 0, true, st))) return rc;
+    if ((rc = w_x(flags, Wqkv, w.dqkv, w.dxn, nullptr, nullptr, Cin, d.Cq, d.TV, N, true, st))) return rc;
     // data_bn backward (+ the skip connection's dz)
     if ((rc = launch_cv_stats(x, w.dxn, dmean, dinv, w.parts, w.sums, N, Cin, T, V, st))) return rc;
     if ((rc = launch_bn_bwd_finalize(w.sums, 1, (double)N * T, dbn_weight, dinv, ddbn_weight, ddbn_bias, w.dcoef, d.CV, st,

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_uint, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_long, c_longlong, c_size_t, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STGCN_LIB") or os.path.join(_HERE, "libstgcn_hip.so")   # STGCN_LIB: diagnostic builds
@@ -121,6 +121,12 @@ PROTOTYPES = {
     "stgcn_st_attention_forward_train": (c_int, [_P] * 14 + [c_float, c_float, _P, c_size_t] + [_P] * 6 + [c_int] * 7
                                          + [c_uint, _P]),
     "stgcn_st_attention_backward": (c_int, [_P] * 24 + [c_size_t] + [c_int] * 7 + [c_uint, _P]),
+    "stgcn_st_attention_math_supported": (c_int, [c_int] * 5 + [c_uint]),
+    "stgcn_st_attention_forward_math": (c_int, [_P] * 10 + [c_size_t, _P] + [c_int] * 7 + [c_uint, _P]),
+    "stgcn_wx_product_supported": (c_int, [c_int, c_int, c_longlong, c_uint]),
+    "stgcn_wx_product_kernel_name": (c_char_p, [c_int, c_int, c_longlong, c_uint]),
+    "stgcn_wx_product_ws_bytes": (c_size_t, [c_int, c_int, c_uint]),
+    "stgcn_wx_product": (c_int, [_P] * 6 + [c_size_t] + [c_int] * 3 + [c_longlong, c_int, c_uint, _P]),
     "stgcn_vit_linear_supported": (c_int, [c_int] * 3 + [c_uint]),
     "stgcn_vit_linear_tile": (c_int, [c_int] * 3 + [c_uint]),
     "stgcn_vit_linear": (c_int, [_P] * 5 + [c_float] + [_P] * 2 + [c_int] * 3 + [c_uint, _P]),

@@ -7,7 +7,7 @@ outputs.  Nothing here computes on the host and nothing falls back to torch ops.
 from __future__ import annotations
 
 import ctypes
-from ctypes import c_float, c_int, c_size_t, c_uint, c_void_p
+from ctypes import c_float, c_int, c_longlong, c_size_t, c_uint, c_void_p
 from typing import Optional, Tuple
 
 import torch
@@ -459,26 +459,63 @@ def _st_ws(dev, N, Cin, Cout, dk, T, V, heads, pass_):
     return torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64), nbytes
 
 
-def st_attention_forward(x, dbn_scale, dbn_shift, Wqkv, bqkv, Wout, bout, bn_scale, bn_shift, dk, heads) -> torch.Tensor:
+def st_attention_math_supported(Cin, Cout, dk, V, heads, math=MATH_F32) -> bool:
+    return bool(_capi.lib().stgcn_st_attention_math_supported(Cin, Cout, dk, V, heads, math & _capi.MATH_MASK))
+
+
+def wx_product_supported(M, K, TV, math=MATH_F32) -> bool:
+    return bool(_capi.lib().stgcn_wx_product_supported(M, K, TV, math))
+
+
+def wx_product_kernel_name(M, K, TV, math=MATH_F32) -> str:
+    return _capi.lib().stgcn_wx_product_kernel_name(M, K, TV, math).decode()
+
+
+def wx_product(W, X, bias=None, R=None, w_transposed=False, math=MATH_F32) -> torch.Tensor:
+    """C[n] = W . X[n] (+ bias per row) (+ R[n]): the product of gcn_unit_attention's 1x1 projections on its own.  X (N,K,TV),
+    W (M,K), or (K,M) with ``w_transposed``; R (N,M,TV) or None.  ``math``: MATH_F32 (the strided fp32 GEMM) or MATH_BF16X3
+    (three-term bf16 split, stgcn_wx_product).  Returns C (N,M,TV)."""
+    dev = X.device
+    N, K, TV = X.shape
+    M = W.shape[1] if w_transposed else W.shape[0]
+    nbytes = _capi.lib().stgcn_wx_product_ws_bytes(M, K, math)
+    ws = _bytes(dev, nbytes) if nbytes else None
+    C = torch.empty(N, M, TV, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _capi.call("stgcn_wx_product", _dev_ptr(W, "W", dev), _dev_ptr(X, "X", dev), _dev_ptr(bias, "bias", dev),
+                   _dev_ptr(R, "R", dev), _dev_ptr(C, "C"), c_void_p(ws.data_ptr() if ws is not None else None),
+                   c_size_t(nbytes), c_int(N), c_int(M), c_int(K), c_longlong(TV), c_int(1 if w_transposed else 0),
+                   c_uint(math), _stream(dev))
+    return C
+
+
+def st_attention_forward(x, dbn_scale, dbn_shift, Wqkv, bqkv, Wout, bout, bn_scale, bn_shift, dk, heads,
+                         math=MATH_F32) -> torch.Tensor:
     """Eval forward of gcn_unit_attention with both BatchNorms folded (data_bn over Cin*V channels).  Wqkv (2dk+Cout, Cin),
-    Wout (Cout, Cout).  Returns y (N,Cout,T,V)."""
+    Wout (Cout, Cout).  ``math``: MATH_F32, or MATH_BF16X3 for the two projections (stgcn_st_attention_forward_math).
+    Returns y (N,Cout,T,V)."""
     dev = x.device
     N, Cin, T, V = x.shape
     Cout = Wout.shape[0]
     ws, nbytes = _st_ws(dev, N, Cin, Cout, dk, T, V, heads, 0)
     y = torch.empty(N, Cout, T, V, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _capi.call("stgcn_st_attention_forward", _dev_ptr(x, "x", dev), _dev_ptr(dbn_scale, "dbn_scale", dev),
-                   _dev_ptr(dbn_shift, "dbn_shift", dev), _dev_ptr(Wqkv, "Wqkv", dev), _dev_ptr(bqkv, "bqkv", dev),
-                   _dev_ptr(Wout, "Wout", dev), _dev_ptr(bout, "bout", dev), _dev_ptr(bn_scale, "bn_scale", dev),
-                   _dev_ptr(bn_shift, "bn_shift", dev), c_void_p(ws.data_ptr()), c_size_t(nbytes), _dev_ptr(y, "y"),
-                   c_int(N), c_int(Cin), c_int(Cout), c_int(dk), c_int(T), c_int(V), c_int(heads), _stream(dev))
+        head = (_dev_ptr(x, "x", dev), _dev_ptr(dbn_scale, "dbn_scale", dev),
+                _dev_ptr(dbn_shift, "dbn_shift", dev), _dev_ptr(Wqkv, "Wqkv", dev), _dev_ptr(bqkv, "bqkv", dev),
+                _dev_ptr(Wout, "Wout", dev), _dev_ptr(bout, "bout", dev), _dev_ptr(bn_scale, "bn_scale", dev),
+                _dev_ptr(bn_shift, "bn_shift", dev), c_void_p(ws.data_ptr()), c_size_t(nbytes), _dev_ptr(y, "y"),
+                c_int(N), c_int(Cin), c_int(Cout), c_int(dk), c_int(T), c_int(V), c_int(heads))
+        if math == MATH_F32:
+            _capi.call("stgcn_st_attention_forward", *head, _stream(dev))
+        else:
+            _capi.call("stgcn_st_attention_forward_math", *head, c_uint(math), _stream(dev))
     return y
 
 
 def st_attention_forward_train(x, data_bn, Wqkv, bqkv, Wout, bout, bn, mask, dk, heads, momentum=0.1, eps=BN_EPS,
-                               frozen=False):
-    """Training forward (batch statistics, or running ones with ``frozen``).  ``data_bn`` / ``bn``: (weight, bias,
+                               frozen=False, math=MATH_F32):
+    """Training forward (batch statistics, or running ones with ``frozen``; ``math``: MATH_F32 or MATH_BF16X3 for the two
+    projections - the backward must be given the same).  ``data_bn`` / ``bn``: (weight, bias,
     running_mean, running_var); ``mask`` (N*T*heads*V) of 0 / 1, or None.  Returns (y, saved) with saved = dict of the
     tensors stgcn_st_attention_backward reads."""
     dev = x.device
@@ -498,13 +535,14 @@ def st_attention_forward_train(x, data_bn, Wqkv, bqkv, Wout, bout, bn, mask, dk,
                    _dev_ptr(mask, "mask", dev), c_float(momentum), c_float(eps), c_void_p(ws.data_ptr()), c_size_t(nbytes),
                    _dev_ptr(y, "y"), *[_dev_ptr(sv[k], k) for k in ("qkv", "o", "z", "rowstats", "stats")], c_int(N),
                    c_int(Cin), c_int(Cout), c_int(dk), c_int(T), c_int(V), c_int(heads),
-                   c_uint(_capi.BN_FROZEN if frozen else 0), _stream(dev))
+                   c_uint((_capi.BN_FROZEN if frozen else 0) | math), _stream(dev))
     return y, sv
 
 
 def st_attention_backward(x, dbn_weight, dbn_bias, Wqkv, Wout, bn_weight, bn_bias, mask, saved, dy, dk, heads,
-                          need_dx=True, frozen=False):
-    """Backward of st_attention_forward_train.  Returns a dict: dx (or None), ddbn_weight, ddbn_bias (Cin*V), dWqkv, dbqkv,
+                          need_dx=True, frozen=False, math=MATH_F32):
+    """Backward of st_attention_forward_train (same ``frozen`` and ``math``: the latter runs the two input-gradient products
+    in that arithmetic, the weight gradients stay fp32).  Returns a dict: dx (or None), ddbn_weight, ddbn_bias (Cin*V), dWqkv, dbqkv,
     dWout, dbout, dbn_weight, dbn_bias."""
     dev = x.device
     N, Cin, T, V = x.shape
@@ -523,7 +561,7 @@ def st_attention_backward(x, dbn_weight, dbn_bias, Wqkv, Wout, bn_weight, bn_bia
                    *[_dev_ptr(g[k], k) for k in ("dx", "ddbn_weight", "ddbn_bias", "dWqkv", "dbqkv", "dWout", "dbout",
                                                   "dbn_weight", "dbn_bias")],
                    c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(N), c_int(Cin), c_int(Cout), c_int(dk), c_int(T),
-                   c_int(V), c_int(heads), c_uint(_capi.BN_FROZEN if frozen else 0), _stream(dev))
+                   c_int(V), c_int(heads), c_uint((_capi.BN_FROZEN if frozen else 0) | math), _stream(dev))
     return g
 
 

@@ -739,7 +739,8 @@ def set_output_layout(module: nn.Module, layout: str) -> None:
 def set_math_mode(module: nn.Module, mode) -> None:
     """Set the temporal-conv arithmetic ('f32' | 'bf16x3' | 'bf16' | 'f32_valu') on every Unit2D below.  Transformer blocks
     of the AltFormer heads below follow as far as they have the arithmetic: 'f32' / 'f32_valu' select their f32 linears, every
-    other mode leaves them on their default (altformer.set_head_math chooses among theirs)."""
+    other mode leaves them on their default (altformer.set_head_math chooses among theirs).  ST-TR's attention units
+    (gcn_unit_attention) are left alone whatever the mode: st_attention.set_st_attention_math chooses theirs."""
     from .altformer import Block, set_head_math
     m = _MATH_NAMES[mode] if isinstance(mode, str) else int(mode)
     for sub in module.modules():

@@ -15,11 +15,40 @@ after this unit draw the same numbers.  The reference draws on the default ``cud
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
 from . import functional as F
+from ._capi import MATH_BF16X3, MATH_F32
 from .modules import _check_input, _master, _slot, _versions, _wants_grad
+
+# arithmetic of the unit's two 1x1 projections and of their two input gradients (everything else is fp32 either way)
+ST_ATTENTION_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3}
+DEFAULT_ST_ATTENTION_MATH = "f32"
+
+
+def _math_name(mode) -> str:
+    if not isinstance(mode, str) or mode.lower() not in ST_ATTENTION_MATH:
+        raise ValueError(f"gcn_unit_attention arithmetic {mode!r}: expected 'f32' or 'bf16x3'")
+    return mode.lower()
+
+
+def _default_math() -> str:
+    return _math_name(os.environ.get("STGCN_ST_ATTENTION_MATH", DEFAULT_ST_ATTENTION_MATH))
+
+
+def set_st_attention_math(module: nn.Module, mode) -> None:
+    """Arithmetic of the two 1x1 projections (and, in training, of their two input gradients) of every
+    ``gcn_unit_attention`` below: 'f32' (the fp32 matrix cores, the default) | 'bf16x3' (both operands split into bf16
+    hi + lo, three bf16 matrix-core products, fp32 sums; opt-in, holds the fp32 gate of 1e-4).  Anything else raises
+    ValueError.  The weight gradients, the V x V attention and the BatchNorms stay fp32.  Env ``STGCN_ST_ATTENTION_MATH``
+    sets the default of newly built units.  Nothing but these units is touched."""
+    name = _math_name(mode)
+    for sub in module.modules():
+        if isinstance(sub, gcn_unit_attention):
+            sub.math_mode = name
 
 
 class spatial_attention(nn.Module):
@@ -81,19 +110,19 @@ class _StAttentionTrainFn(torch.autograd.Function):
         y, sv = F.st_attention_forward_train(
             xd, (dbn.weight.detach(), dbn.bias.detach(), dbn.running_mean, dbn.running_var), st["Wqkv"], st["bqkv"],
             st["Wout"], st["bout"], (bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var), mask,
-            mod._dk, mod._heads, mod._momentum(), bn.eps, frozen=frozen)
+            mod._dk, mod._heads, mod._momentum(), bn.eps, frozen=frozen, math=mod._math_flags)
         ctx.save_for_backward(xd, dbn.weight.detach(), dbn.bias.detach(), st["Wqkv"], st["Wout"], bn.weight.detach(),
                               bn.bias.detach(), mask, sv["qkv"], sv["o"], sv["z"], sv["rowstats"], sv["stats"])
-        ctx.meta = (mod._dk, mod._heads, frozen, tuple(params[2].shape), tuple(params[4].shape))
+        ctx.meta = (mod._dk, mod._heads, frozen, tuple(params[2].shape), tuple(params[4].shape), mod._math_flags)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, dbw, dbb, Wqkv, Wout, bw, bb, mask, qkv, o, z, rowstats, stats = ctx.saved_tensors
-        dk, heads, frozen, qshape, oshape = ctx.meta
+        dk, heads, frozen, qshape, oshape, math = ctx.meta
         saved = {"qkv": qkv, "o": o, "z": z, "rowstats": rowstats, "stats": stats}
         g = F.st_attention_backward(x, dbw, dbb, Wqkv, Wout, bw, bb, mask, saved, dy.contiguous(), dk, heads,
-                                    need_dx=ctx.needs_input_grad[1], frozen=frozen)
+                                    need_dx=ctx.needs_input_grad[1], frozen=frozen, math=math)
         return (None, g["dx"], None, g["ddbn_weight"], g["ddbn_bias"], g["dWqkv"].view(qshape), g["dbqkv"],
                 g["dWout"].view(oshape), g["dbout"], g["dbn_weight"], g["dbn_bias"])
 
@@ -107,6 +136,9 @@ class gcn_unit_attention(nn.Module):
     dk_factor = 0.25 and Nh = 8 (any per-head split with (dk/Nh, dv/Nh) in {(4,16), (8,32), (16,64)}), any in_channels,
     num_point <= 64; other shapes raise StgcnError (STGCN_ERR_UNSUPPORTED) at the first forward.  Batch statistics of a
     single frame (N*T == 1) raise ValueError, as the reference's data_bn does.
+
+    ``math_mode`` ('f32' default | 'bf16x3'; ``set_st_attention_math``, env ``STGCN_ST_ATTENTION_MATH`` for new units) is
+    the arithmetic of the two projections and their input gradients; an nn.DataParallel replica reads its master's.
     """
 
     def __init__(self, in_channels, out_channels, incidence, num, dv_factor, dk_factor, Nh, complete, relative,
@@ -124,6 +156,7 @@ class gcn_unit_attention(nn.Module):
                                           "reference's scripts build only_attention=True, relative=False, adjacency=False, "
                                           "more_channels=False, data_normalization=True, skip_conn=True, bn_flag=True, "
                                           "kernel_size=1, stride=1)")
+        self._math_mode = _default_math()
         self.incidence = incidence
         self.relu = nn.ReLU()
         self.visualization = visualization
@@ -158,6 +191,19 @@ class gcn_unit_attention(nn.Module):
     @property
     def _heads(self):
         return self.attention_conv.Nh
+
+    @property
+    def math_mode(self) -> str:
+        """'f32' | 'bf16x3'; a replica answers for its master (a unit pickled before the setting existed: 'f32')."""
+        return _master(self).__dict__.get("_math_mode", DEFAULT_ST_ATTENTION_MATH)
+
+    @math_mode.setter
+    def math_mode(self, mode):
+        object.__setattr__(_master(self), "_math_mode", _math_name(mode))
+
+    @property
+    def _math_flags(self) -> int:
+        return ST_ATTENTION_MATH[self.math_mode]
 
     def _replicate_for_data_parallel(self):
         replica = super()._replicate_for_data_parallel()
@@ -256,11 +302,11 @@ class gcn_unit_attention(nn.Module):
                 y, _ = F.st_attention_forward_train(
                     x, (dbn.weight, dbn.bias, dbn.running_mean, dbn.running_var), st["Wqkv"], st["bqkv"], st["Wout"],
                     st["bout"], (bn.weight, bn.bias, bn.running_mean, bn.running_var), mask, self._dk, self._heads,
-                    self._momentum(), bn.eps, frozen=not bn_training)
+                    self._momentum(), bn.eps, frozen=not bn_training, math=self._math_flags)
             if bn_training:
                 with torch.no_grad():
                     torch._foreach_add_([dbn.num_batches_tracked, bn.num_batches_tracked], 1)
             return y
         dscale, dshift, bscale, bshift = self._folded(st)
         return F.st_attention_forward(x, dscale, dshift, st["Wqkv"], st["bqkv"], st["Wout"], st["bout"], bscale, bshift,
-                                      self._dk, self._heads)
+                                      self._dk, self._heads, math=self._math_flags)
