@@ -178,6 +178,10 @@ const char *stgcn_stem_kernel_name(int Cin, int C, int T, int V, int K, int subs
  * of tiles_per_clip tiles (short_last = 0: every tile costs the same). */
 int stgcn_stem_short_tile_blocks(int C, int T, int V, int K);
 int stgcn_stem_walk_run(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *first, int *end);
+/* The tiles of that run in the ORDER the workgroup walks them (two store phases: a workgroup with bit 3 of its index set walks
+ * the first short tile of its run first, then the rest in order).  *count = the number of tiles of the run; the first
+ * min(cap, *count) of them are written to tiles (which may be NULL with cap = 0).  Additive: the ABI version stays. */
+int stgcn_stem_walk_order(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *tiles, int cap, int *count);
 /* 1 when one of the large-tile kernels serves the shape (stem_bf16_v4/_v6/_f16mx_kernel): the workspace then holds,
  * behind P, graph-conv features or attention fragments that stgcn_stem_attention writes for the kernel */
 int stgcn_stem_features_used(int Cin, int C, int T, int V, int K, int subsets, unsigned flags);

@@ -263,6 +263,15 @@ int stgcn_stem_walk_run(int wg, int num_wg, int nclips, int tiles_per_clip, int 
     return STGCN_OK;
 }
 
+int stgcn_stem_walk_order(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *tiles, int cap, int *count) {
+    REQUIRE_PTR(count);
+    REQUIRE_POS(num_wg); REQUIRE_POS(nclips); REQUIRE_POS(tiles_per_clip);
+    if (wg < 0) return fail(STGCN_ERR_ARG, "%s: wg = %d must not be negative", __func__, wg);
+    if (cap < 0 || (cap > 0 && !tiles)) return fail(STGCN_ERR_ARG, "%s: cap = %d tiles at %p", __func__, cap, (void *)tiles);
+    *count = stem_v6_walk_order(wg, num_wg, nclips, tiles_per_clip, short_last, tiles, cap);
+    return STGCN_OK;
+}
+
 int stgcn_stem_features_used(int Cin, int C, int T, int V, int K, int subsets, unsigned flags) {
     if (Cin <= 0 || C <= 0 || T <= 0 || V <= 0 || K <= 0 || subsets <= 0) return 0;
     const StemPart part = plan_stem(1, Cin, C, T, V, K, subsets, flags).part;

@@ -269,6 +269,7 @@ bool stem_v6_supported(int C, int T, int V, int K, unsigned flags);
 // [first, end) of tiles that workgroup wg of num_wg walks
 int stem_v6_short_tile_blocks(int C, int T, int V, int K);
 void stem_v6_walk_run(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *first, int *end);
+int stem_v6_walk_order(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *tiles, int cap);
 // ... and for wide frames (32 < V <= 64, V even: the two-hand graph) the same kernel over the two joint halves [0, V0) and
 // [V0, V), each handled like a narrow clip (stem_bf16_v6w.hip)
 static inline int stem_wide_split(int V) {     // V0 (a multiple of 4: 16-byte aligned half rows), or 0 when V does not split

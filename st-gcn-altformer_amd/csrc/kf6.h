@@ -105,6 +105,29 @@ __host__ __device__ inline V6Run v6_run(int b, int G, int nclips, int tpc, int s
     return V6Run{(int)(q0 / P * tpc + q0 % P / 2), (int)(q1 / P * tpc + q1 % P / 2)};
 }
 
+// ---- the ORDER in which a workgroup walks its run: two store phases ---------------------------------------------------------
+// Every full tile costs every workgroup the same, so walked alike all workgroups reach their epilogues together and the chip
+// takes their result stores as one burst per tile ("Two store phases").  The workgroups are therefore split
+// into two classes, cls = (b >> 3) & 1: workgroups are dealt round-robin over the 8 XCDs, b and b + 8 share one, so a class that
+// is a function of b mod 2 / 4 / 8 would give all workgroups of an XCD the same phase; bit 3 puts half of every XCD's workgroups
+// into each class wherever workgroup 0 lands.  Class 0 walks its run in order.  Class 1 walks the first SHORT tile of its run
+// first and then the rest in order: a short tile costs 0.75 of a full one, so from its second tile on a class-1 workgroup stores
+// a quarter of a tile ahead of class 0, and both classes do the same work (no delay, no idle time, the same tiles, each with
+// its own accumulation order and bits).  A run without a short tile, or one that begins with it, is walked in order.
+// V6Order::ts = the short tile walked first, -1 where the run is walked in order; the walk is
+//     t = v6_order_start(run, o);  while (t < run.end) { ...; t = v6_order_next(t, run.first, o.ts); }
+// (next(ts) = first, next(ts - 1) = ts + 1, else t + 1: the walk always ends at exactly run.end).  The kernel and the host test
+// (stgcn_stem_walk_order) share these functions.
+struct V6Order { int ts; };
+__host__ __device__ inline int v6_store_class(int b) { return (b >> 3) & 1; }
+__host__ __device__ inline V6Order v6_order(int b, V6Run run, int tpc, int short_last) {
+    if (!short_last || !v6_store_class(b)) return V6Order{-1};
+    const int ts = run.first + (tpc - 1 - run.first % tpc);   // the first tile at or behind run.first that ends a clip
+    return V6Order{ts > run.first && ts < run.end ? ts : -1};
+}
+__host__ __device__ inline int v6_order_start(V6Run run, V6Order o) { return o.ts >= 0 ? o.ts : run.first; }
+__host__ __device__ inline int v6_order_next(int t, int first, int ts) { return t == ts ? first : (t == ts - 1 ? ts + 1 : t + 1); }
+
 #ifdef STGCN_ABLATION  // in-kernel cycle stamps of KF6 and KF7 (diagnostic builds only; dbg == NULL otherwise)
 #define V6_STAMP(var) unsigned long long var = 0; if (dbg) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); }
 #define V6_ACC(slot, a, b) if (dbg) { tsum[slot] += (b) - (a); }
@@ -459,23 +482,39 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
         sh_lo = shift[cg * 128 + lane];
         sh_hi = shift[cg * 128 + 64 + lane];
     }
-    // the workgroup's tiles: tile, tile + tile_step, ... below tile_end.  Grid-stride over all tiles, or (narrow three-term form
-    // of a shape with short last tiles) the contiguous run of v6_run
+    // the workgroup's tiles: tile, tile_next(tile), ... below tile_end.  Grid-stride over all tiles, or (narrow three-term form
+    // of a shape with short last tiles) the contiguous run of v6_run in the order of v6_order
     int tile = blockIdx.x;
     int tile_end = ntiles;
     unsigned run_step = 0;                    // 1 on a contiguous run, else 0: the stride is gridDim.x, read where it is used (the
                                               // other forms then keep their prologue and scalar registers as they were)
+    // ... walked in the order of v6_order: run_first / ord_ts are what v6_order_next needs (ord_ts = -1: in order)
+    [[maybe_unused]] int run_first = 0, ord_ts = -1;
     if constexpr (TERMS == 3 && !WIDE) {
         if (abl & OPT_V6_SHORT) {
             const V6Run run = v6_run(blockIdx.x, gridDim.x, ntiles / tiles_per_clip, tiles_per_clip, 1);
             tile = run.first;
             tile_end = run.end;
             run_step = 1u;
+#ifndef V6_ONE_STORE_PHASE   // (A/B variant: every workgroup walks its run in order, as before the two store phases)
+            const V6Order ord = v6_order(blockIdx.x, run, tiles_per_clip, 1);
+            run_first = run.first;
+            ord_ts = ord.ts;
+            tile = v6_order_start(run, ord);
+#endif
         }
     }
     auto tile_step = [&]() -> unsigned {
         if constexpr (TERMS == 3 && !WIDE) return run_step ? run_step : gridDim.x;
         else return gridDim.x;
+    };
+    // the tile behind tile t of the walk (a few scalar instructions per tile, outside the main loop's slots)
+    auto tile_next = [&](int t) -> int {
+#ifndef V6_ONE_STORE_PHASE
+        if constexpr (TERMS == 3 && !WIDE)
+            if (run_step) return v6_order_next(t, run_first, ord_ts);
+#endif
+        return t + tile_step();
     };
     {
         XRegs x0 = {}, x1 = {}, x2 = {};
@@ -502,7 +541,7 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
     // fillers per slot, five producer blocks per wave and chunk counted from the tile's first block, bounds-checked stores).
     // LDS carve, images, weight ring and its DMA schedule, MFMA and term order are the same; so is every stored value.
     // The body is kf6_tile.h, included once per form (it says why it is text and not a generic lambda).
-    for (; tile < tile_end; tile += tile_step()) {
+    for (; tile < tile_end; tile = tile_next(tile)) {
         if constexpr (TERMS == 3 && !WIDE) {
             // (scalar) the clip's last tile of a shape with short last tiles: one uniform branch per tile
             if ((abl & OPT_V6_SHORT) && (tile + 1) % tiles_per_clip == 0) {
@@ -521,7 +560,7 @@ __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
         }
     }
 #ifdef STGCN_ABLATION
-    if (dbg && lane == 0 && blockIdx.x < 8 && blockIdx.y == 0)
+    if (dbg && lane == 0 && blockIdx.x < 16 && blockIdx.y == 0)   // (16 workgroups x 8 rows x 8 slots: the tools size the buffer)
         for (int i = 0; i < 8; ++i) {         // rows 0-3 of a workgroup's eight: the waves' full tiles, rows 4-7: their short tiles
             dbg[(blockIdx.x * 8 + wave) * 8 + i] = tsum[i];
             dbg[(blockIdx.x * 8 + 4 + wave) * 8 + i] = tsum[8 + i];

@@ -23,7 +23,7 @@
         const TileGeomB g = ti.g;
         const int Vh = ti.Vh;
         const int nblk = (g.span + 15) >> 4;
-        const int next_tile = tile + tile_step();
+        const int next_tile = tile_next(tile);    // (the walk's order: the prefetches below and the loop's end test follow it)
         // NPBW == 7: the wave's first producer block.  The image starts at the tile's first FRAME, the tile's first pixel sits
         // s = q0 - t_first * Vh rows into it (0 <= s < Vh) and no tap reads a row in front of it: blocks below s >> 4 are not
         // produced (their rows keep the previous tile's data), nor are blocks behind pb0 + 27, which the host plan has shown to
@@ -432,8 +432,13 @@
                     const size_t tb0 = ((size_t)n * C + cg * 128) * TV + qw;      // scalar: the wave's pixels in channel row 0 of the group
                     // 16-byte (8-byte for bf16) aligned rows: the same for all eight blocks (a block is 16 rows of TV further)
                     const bool al16 = ((tb0 & 3) == 0) && (TV % 4 == 0);
-                    auto blocks = [&](auto fast_c) {
-                        constexpr bool FAST = decltype(fast_c)::value;
+                    // SHORT, aligned rows: a lane whose four pixels all lie inside the clip stores them as 16 bytes under its own
+                    // predicate (at T = 180, V = 22 all 30 groups of the 120 pixels are whole); a ragged last group and unaligned
+                    // rows keep the element form.  -DV6_SHORT_ELEMENT_STORES builds the element form alone (A/B).
+                    [[maybe_unused]] const bool whole = qw + c4l + 3 <= g.q_last;
+                    auto blocks = [&](auto form_c) {
+                        constexpr int FORM = decltype(form_c)::value;  // 1: every store 16 B; 0: element by element; 2: whole groups 16 B
+                        constexpr bool FAST = FORM == 1;
 #pragma unroll
                         for (int mb = 0; mb < 8; ++mb) {
                             float shv[4];
@@ -448,23 +453,31 @@
                             for (int it = 0; it < 16 / RPI; ++it) {
                                 const float4 v = *reinterpret_cast<const float4 *>(stg + (it * RPI + lane_t / LPR) * 64 + c4l);
                                 const size_t sbase = tbase + (size_t)(it * RPI) * TV;  // scalar
-                                if constexpr (FAST) {
+                                auto store16 = [&]() {
                                     if constexpr (BF16OUT)
                                         *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + sbase + lterm) =
                                             make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
                                     else
                                         st_out4<true>(reinterpret_cast<float *>(y) + sbase + lterm, v);
-                                } else {                                     // last tile of a clip / unaligned rows: element by element
+                                };
+                                auto store_elements = [&]() {               // element by element, each under its bounds check
                                     const float e4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                                     for (int e = 0; e < 4; ++e)
                                         if (qw + c4l + e <= g.q_last) store_out<BF16OUT>(y, sbase + lterm + e, e4[e]);
-                                }
+                                };
+                                if constexpr (FAST) store16();
+                                else if constexpr (FORM == 2) { if (whole) store16(); else store_elements(); }
+                                else store_elements();                       // last tile of a clip / unaligned rows
                             }
                         }
                     };
-                    if constexpr (SHORT) blocks(std::false_type{});
-                    else if (full && al16) blocks(std::true_type{}); else blocks(std::false_type{});
+#ifdef V6_SHORT_ELEMENT_STORES
+                    if constexpr (SHORT) blocks(std::integral_constant<int, 0>{});
+#else
+                    if constexpr (SHORT) { if (al16) blocks(std::integral_constant<int, 2>{}); else blocks(std::integral_constant<int, 0>{}); }
+#endif
+                    else if (full && al16) blocks(std::integral_constant<int, 1>{}); else blocks(std::integral_constant<int, 0>{});
                 }
             }
         }

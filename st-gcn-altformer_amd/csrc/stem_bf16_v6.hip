@@ -48,6 +48,22 @@ void stem_v6_walk_run(int wg, int num_wg, int nclips, int tiles_per_clip, int sh
     *end = r.end;
 }
 
+// the tiles of workgroup wg in the order the kernel walks them (v6_order: two store phases); returns their number and writes
+// the first `cap` of them
+int stem_v6_walk_order(int wg, int num_wg, int nclips, int tiles_per_clip, int short_last, int *tiles, int cap) {
+    const int ntiles = nclips * tiles_per_clip, G = ntiles < num_wg ? ntiles : num_wg;   // (the launch's grid)
+    const V6Run r = wg < G ? v6_run(wg, G, nclips, tiles_per_clip, short_last) : V6Run{ntiles, ntiles};
+#ifndef V6_ONE_STORE_PHASE
+    const V6Order o = v6_order(wg, r, tiles_per_clip, short_last);
+#else
+    const V6Order o = V6Order{-1};
+#endif
+    int n = 0;
+    for (int t = v6_order_start(r, o); t < r.end; t = v6_order_next(t, r.first, o.ts), ++n)
+        if (n < cap) tiles[n] = t;
+    return n;
+}
+
 // temporal weights (Cout,Cin,9) * scale -> KF6's pair order (same size as the 32x32x16 packing)
 int launch_tcn_pack_bf16_pairs(const float *W, const float *scale, void *Wq, int Cin, int Cout, hipStream_t st) {
     const size_t total = (size_t)Cin * Cout * KT6 * 2;

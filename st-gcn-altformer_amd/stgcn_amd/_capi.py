@@ -102,6 +102,7 @@ PROTOTYPES = {
     "stgcn_stem_kernel_name": (c_char_p, [c_int] * 6 + [c_uint]),
     "stgcn_stem_short_tile_blocks": (c_int, [c_int] * 4),
     "stgcn_stem_walk_run": (c_int, [c_int] * 5 + [_P] * 2),
+    "stgcn_stem_walk_order": (c_int, [c_int] * 5 + [_P, c_int, _P]),
     "stgcn_stem_attention": (c_int, [_P] * 7 + [c_size_t] + [c_int] * 8 + [c_uint, _P]),
     "stgcn_stem_tail_prepared": (c_int, [_P] * 2 + [c_size_t] + [_P] * 3 + [c_int] * 7 + [c_uint, _P]),
     "stgcn_stem_forward_prepared": (c_int, [_P] * 9 + [c_size_t] + [_P] + [c_int] * 8 + [c_uint, _P]),

@@ -21,14 +21,14 @@ x = bench.synthetic_clips(a.clips, 180, 22, 0).to(dev)
 gcn, tcn = bench.build_stem(22, "SHRE", a.math)
 gcn, tcn = gcn.to(dev).eval(), tcn.to(dev).eval()
 stgcn_amd.enable_stem_fusion(gcn, tcn)
-buf = torch.zeros(8 * 8 * 8, dtype=torch.int64, device=dev)
+buf = torch.zeros(16 * 8 * 8, dtype=torch.int64, device=dev)     # KF6 records workgroups 0-15, the v4 kernel 0-7
 with torch.no_grad():
     for _ in range(3): tcn(gcn(x))
     torch.cuda.synchronize()
     os.environ["STGCN_ABLATE"] = a.abl
     os.environ["STGCN_DBG_PTR"] = hex(buf.data_ptr())
     tcn(gcn(x)); torch.cuda.synchronize()
-t = buf.cpu().view(8, 8, 8).double()
+t = buf.cpu().view(16, 8, 8)[:8].double()        # workgroups 0-7, as the slot means below were always taken
 names = ["chunk0+bar", "main loop (KF6: incl. barrier waits; KF4: stage compute)", "stage barrier wait", "epilogue", "post-epilogue (features + bar)"]
 tot = t[:, :, :5].sum(-1)
 print(f"math={a.math} abl={a.abl}: per-wave total stamped cycles: mean {tot.mean():.0f}")
