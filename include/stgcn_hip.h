@@ -27,6 +27,12 @@
  *     calling thread is available from stgcn_last_error().  Nothing throws or exits.
  *   - `flags`: low 4 bits select the arithmetic of the temporal-conv contraction
  *     (stgcn_math); STGCN_OUT_BF16 stores the final activation as bf16.
+ *   - Extents: an entry point is correct at every size it accepts, tensors past 2^31 elements
+ *     included, or returns STGCN_ERR_UNSUPPORTED before anything is launched.  Two bounds hold
+ *     wherever nothing else is said: at most 65535 clips a call where the clip rides on a grid
+ *     axis (the graph conv, the stem, the temporal conv's inference and backward, the ST-TR
+ *     unit, stgcn_patch_embed, the whole head), and fewer than 2^32 work-items a launch
+ *     (workgroups times their threads), which bounds "any M / B / S" below: see each entry.
  */
 #ifndef STGCN_HIP_H
 #define STGCN_HIP_H
@@ -246,7 +252,8 @@ size_t stgcn_agcn_backward_ws_bytes(int N, int Cin, int Cout, int T, int V, int 
  *   - the stem's shape class (Cin = 3, 3 subsets, Cout in {64,128,256}, down branch, no dx) with zm == zd == NULL and
  *     y != NULL — i.e. after a moments-path forward whose save_stats carries the feature moments: ONE pass over dy / y
  *     (fp32 MFMA), everything else from moments (csrc/agcn_backward.hip; no branch is rebuilt, no statistics pass);
- *   - a chain of strided batched fp32-MFMA GEMMs for everything else (V <= 64, inter_c <= Cout/4); y is not read. */
+ *   - a chain of strided batched fp32-MFMA GEMMs for everything else (V <= 64, inter_c <= Cout/4, N * subsets <= 65535: a
+ *     batch entry per (clip, subset) pair; else STGCN_ERR_UNSUPPORTED before anything is launched); y is not read. */
 int stgcn_agcn_backward_train(const float *x, const float *A_eff, const float *Wa, const float *ba,
                               const float *Wb, const float *bb, const float *Wd, const float *bd,
                               const float *Wdown, const float *bdown, const float *P, const float *zm,
@@ -321,7 +328,9 @@ int stgcn_step_stats(const void *out, int out_is_bf16, float *stats, int N, int 
  *   o = heads of w . v_h^T concatenated (Cout channels);  z = Wout . o + bout (+ x when Cin == Cout), Wout (Cout, Cout)
  *   y = relu(BatchNorm2d(z))
  * x, y: (N,Cin,T,V) / (N,Cout,T,V).  dk = Cout/4 in the reference's configuration; covered: (dk/heads, Cout/heads) in
- * {(4,16), (8,32), (16,64)} — Cout in {128, 256, 512} with 8 heads — any Cin, V <= 64 (else STGCN_ERR_UNSUPPORTED). */
+ * {(4,16), (8,32), (16,64)} — Cout in {128, 256, 512} with 8 heads — any Cin, V <= 64, N <= 65535 clips with
+ * N*T < 2^26 frames and N*max(Cin,Cout) < 2^24 (its launches' 2^32 work-items: below 32768 clips at 512 channels; else
+ * STGCN_ERR_UNSUPPORTED). */
 int stgcn_st_attention_supported(int Cin, int Cout, int dk, int V, int heads);
 /* workspace bytes of pass 0 = stgcn_st_attention_forward, 1 = _forward_train, 2 = _backward (0 for invalid sizes) */
 size_t stgcn_st_attention_ws_bytes(int N, int Cin, int Cout, int dk, int T, int V, int heads, int pass);
@@ -406,7 +415,9 @@ int stgcn_wx_product(const float *W, const float *X, const float *bias, const fl
 int stgcn_vit_linear_tile(int M, int K, int Nout, unsigned flags);
 /* y (M, Nout) = act(LN?(x) W^T + bias) (+ residual).  x (M, K), W (Nout, K).  bias, residual may be NULL; LayerNorm over
  * the rows of x when ln_weight / ln_bias (K) are given (both or neither), biased variance, eps inside the root.
- * Covered: any M, any Nout, K % 32 == 0, with LayerNorm K <= 4096; f32 or bf16x3 (else STGCN_ERR_UNSUPPORTED).
+ * Covered: any M, any Nout, K % 32 == 0, with LayerNorm K <= 4096; f32 or bf16x3 (else STGCN_ERR_UNSUPPORTED); the tiles of
+ * stgcn_vit_linear_tile times their workgroup's threads (64 a wave) stay below 2^32 work-items (the same for
+ * stgcn_vit_linear_bf16).
  * y may alias residual, not x.  One launch: the row statistics are taken inside the workgroup that owns the rows. */
 int stgcn_vit_linear_supported(int M, int K, int Nout, unsigned flags);
 int stgcn_vit_linear(const float *x, const float *W, const float *bias, const float *ln_weight, const float *ln_bias,
@@ -414,7 +425,8 @@ int stgcn_vit_linear(const float *x, const float *W, const float *bias, const fl
                      void *stream);
 /* out (B, L, heads*head_dim) = concatenated heads of softmax(scale * q k^T) v, qkv (B, L, 3, heads, head_dim).
  * The resident form: K and V of a (sequence, head) pair stay in LDS, a query's score row in registers.
- * Covered: head_dim in {32, 64}, 1 <= L <= 256, any B and heads (else STGCN_ERR_UNSUPPORTED).  One launch.
+ * Covered: head_dim in {32, 64}, 1 <= L <= 256, B and heads with B*heads*ceil(L/32) < 2^26 (a wave per 32 queries of a
+ * pair: 2^32 work-items a launch; the split form: B*heads*ceil(L/32)^2 < 2^26) (else STGCN_ERR_UNSUPPORTED).  One launch.
  * stgcn_vit_attention_supported describes this form (and the length the training entry points cover), not the streaming one. */
 int stgcn_vit_attention_supported(int L, int heads, int head_dim);
 int stgcn_vit_attention(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale, void *stream);
@@ -422,7 +434,9 @@ int stgcn_vit_attention(const float *qkv, float *out, int B, int L, int heads, i
  * 64 keys under a running soft-max, 128 queries of a pair per workgroup.  Covered: head_dim in {32, 64},
  * 1 <= L <= STGCN_VIT_MAX_STREAM_L, any B and heads; it runs the streaming kernel at every covered length, the short ones
  * included.  Agrees with the resident form within rounding (another summation order), bit-identical from run to run.
- * One launch on the caller's stream, no workspace, no allocation, no synchronisation. */
+ * One launch on the caller's stream - one per 2^24 / (heads * ceil(L/128)) sequences, the most a launch of 2^32 work-items
+ * holds - no workspace, no allocation, no synchronisation.  (The streaming backward is one launch pair and refuses
+ * B*heads*ceil(L/128) >= 2^24.) */
 #define STGCN_VIT_MAX_STREAM_L 4096
 int stgcn_vit_attention_stream_supported(int L, int heads, int head_dim);
 int stgcn_vit_attention_stream(const float *qkv, float *out, int B, int L, int heads, int head_dim, float scale,
@@ -508,7 +522,8 @@ size_t stgcn_vit_attention_backward_stream_ws_bytes(int B, int L, int heads);
 int stgcn_vit_attention_backward_stream(const float *qkv, const float *out, const float *dout, float *dqkv, void *ws,
                                         size_t ws_bytes, int B, int L, int heads, int head_dim, float scale, void *stream);
 /* LayerNorm backward over the rows of x (M,D), dn = gradient of the LayerNorm's output: dx = rstd (g - mean(g) - xhat
- * mean(g xhat)) (+ dres), g = dn * weight;  dweight = sum dn xhat,  dbias = sum dn.  D % 4 == 0.  dx may alias dn or dres. */
+ * mean(g xhat)) (+ dres), g = dn * weight;  dweight = sum dn xhat,  dbias = sum dn.  D % 4 == 0, M < 2^26 rows (a wave per
+ * row: 2^32 work-items a launch).  dx may alias dn or dres. */
 size_t stgcn_vit_layernorm_backward_ws_bytes(int M, int D);
 int stgcn_vit_layernorm_backward(const float *x, const float *dn, const float *weight, float eps, const float *dres, float *dx,
                                  float *dweight, float *dbias, void *ws, size_t ws_bytes, int M, int D, void *stream);
@@ -637,12 +652,13 @@ int stgcn_vit_block_attention_form(int B, int L, int D, int heads, int hidden, u
  * Two kernels of their own, both fp32, without atomics and with a fixed summation order (bit-identical from run to run):
  *   stgcn_vit_pool         : out (S, D) = the mean (sum / L) or, with STGCN_VIT_POOL_MAX, the maximum over the L tokens of the
  *                            dense x (S, L, D).  The maximum is a selection that starts from a token of the sequence: on finite
- *                            input it is the largest element bit for bit.  Covered: D % 4 == 0, any S < 2^31 and L.  x and out
- *                            16-byte aligned.  One launch, no workspace.
+ *                            input it is the largest element bit for bit.  Covered: D % 4 == 0, any L, and S * ceil(D / 256) < 2^24
+ *                            sequences (a launch holds fewer than 2^32 work-items).  x and out 16-byte aligned.  One launch, no
+ *                            workspace.
  *   stgcn_vit_pool_classify: logits (N, classes) = LayerNorm(pool over L of x (N, L, D)) W^T + bias; the LayerNorm is affine with
  *                            the biased variance and ln_eps inside the root; W is (classes, D) as nn.Linear stores it, bias may
- *                            be NULL.  Covered: D % 64 == 0, D <= 4096, any N, L and classes >= 1.  One workgroup per clip, one
- *                            launch, no workspace.
+ *                            be NULL.  Covered: D % 64 == 0, D <= 4096, N < 2^22 clips, any L and classes >= 1.  One workgroup
+ *                            of 1024 threads per clip, one launch, no workspace.
  * The embeddings are stgcn_patch_embed's strided fp32 GEMM (the second one with one frame of L2 "joints" per clip: the pooled
  * rows times embed2_weight^T, plus the bias, plus pos2 by row % L2).
  *
@@ -705,7 +721,8 @@ int stgcn_altformer_head_forward(const float *z, const stgcn_altformer_head_weig
  * In the (N, T, V, C) layout a patch is p1 runs of p2 C contiguous floats and the kernel stages its A operand straight from
  * them: no rearranged (N, n, K) copy exists.  (N, C, T, V) input is first written as (N, T, V, C) into the workspace by one
  * transposing pass (N C T V floats more).  Covered: (p2 C) % 32 == 0 (a K chunk of 32 never crosses a run), STGCN_MATH_F32 or
- * STGCN_MATH_BF16X3, a clip and the output below 2^31 elements.
+ * STGCN_MATH_BF16X3, a clip and the output below 2^31 elements, and every launch below 2^32 work-items (the transposing
+ * pass: N ceil(T V / 32) ceil(C / 32) < 2^24 workgroups of 256 threads; the same holds for the backward's launches).
  * The contraction is cut over workgroups (few rows, long K); each part's sums go to a slab of the workspace and one kernel adds
  * the slabs in a fixed order with the bias and the position row and writes the class rows.  No atomics: bit-identical from run
  * to run.  The cut is a host function of (N n, K, E): stgcn_vit_patch_embed_cut returns (tile rows << 16) | parts, 0 if the

@@ -392,6 +392,11 @@ int stgcn_agcn_backward_train(const float *x, const float *A_eff, const float *W
     const bool frozen = (flags & STGCN_BN_FROZEN) != 0;
     const bool generic = frozen || !has_down || dx != nullptr || zm != nullptr || y == nullptr;
     const AgcnBackwardPlan pl = plan_agcn_backward(N, Cin, Cout, T, V, subsets, zm == nullptr, generic, has_down, frozen);
+    // the GEMM chain runs one batch entry per (clip, subset) pair on a 16-bit grid axis: refuse here, not at its first
+    // product - the expansion and the BatchNorm gradient have been launched by then
+    if (!pl.fused && (long long)N * subsets > kMaxGridClips)
+        return fail(STGCN_ERR_UNSUPPORTED, "agcn_backward: the GEMM chain covers N * subsets <= %d (N=%d, %d subsets)", kMaxGridClips,
+                    N, subsets);
     if (!pl.fused && inter_c > pl.inter_c_max)
         return fail(STGCN_ERR_UNSUPPORTED, "agcn_backward: inter_c=%d > Cout/4 (workspace is sized for coff_embedding >= 4)", inter_c);
     if (has_down ? ((zm == nullptr) != (zd == nullptr)) : (zd != nullptr))

@@ -106,6 +106,12 @@ static inline hipError_t allow_lds(K kernel, size_t bytes) {
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// A launch carries its size along an axis in work-items, a 32-bit number: gridDim.x * blockDim.x must stay below 2^32.  This
+// runtime does not reject a larger one: it runs the product modulo 2^32, and the workgroups past it never start (22.4 M
+// workgroups of 256 threads of the streaming attention left three quarters of their result unwritten: DESIGN, "Large
+// extents").  Every launch whose grid grows with the batch asks this before it goes; 2^31 - 1 workgroups bound nothing.
+static inline bool grid_fits(long long blocks, int threads) { return blocks >= 0 && blocks * threads <= 0xffffffffLL; }
+
 // Iteration shared by the elementwise kernels: workgroup (blockIdx.x, c = blockIdx.y) owns clips
 // [n_lo, n_hi) of channel c; a clip's plane of the channel is contiguous, so there is no division in the loop and,
 // when the plane is a multiple of 4 floats, every access is a 16-byte one.

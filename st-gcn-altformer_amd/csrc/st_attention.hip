@@ -370,8 +370,8 @@ int check_shape(const char *fn, int N, int Cin, int Cout, int dk, int T, int V, 
                     "{(4,16), (8,32), (16,64)} (Cout in {128, 256, 512} with dk = Cout/4, 8 heads)",
                     fn, Cout, dk, H, dk / H, Cout / H);
     if (V > kVP) return fail(STGCN_ERR_UNSUPPORTED, "%s: V=%d joints; the attention kernels cover V <= %d", fn, V, kVP);
-    if ((long long)N * T > 0x7fffffffLL || H > 65535) return fail(STGCN_ERR_UNSUPPORTED, "%s: grid too large", fn);
-    if ((long long)N * (Cin > Cout ? Cin : Cout) > 0x7fffffffLL || N > 65535)
+    if (!grid_fits((long long)N * T, 64) || H > 65535) return fail(STGCN_ERR_UNSUPPORTED, "%s: grid too large", fn);
+    if (!grid_fits((long long)N * (Cin > Cout ? Cin : Cout), 256) || N > 65535)
         return fail(STGCN_ERR_UNSUPPORTED, "%s: N=%d clips exceed the grid", fn, N);
     return STGCN_OK;
 }

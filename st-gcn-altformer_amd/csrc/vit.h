@@ -342,13 +342,16 @@ int launch_attention_backward_stream(const float *qkv, const float *out, const f
 // out (S, D) = the mean (sum / L) or the maximum over the L tokens of every sequence of the dense x (S, L, D), D % 4 == 0:
 // a workgroup per (sequence, chunk of D), 16-byte loads along D, the token lanes of a workgroup joined through LDS in
 // ascending order.  The maximum starts from a token of the sequence, never from zero.
-inline bool pool_ok(long long S, int L, int D) { return S >= 1 && S < (1ll << 31) && L >= 1 && D >= 4 && D % 4 == 0; }
+// (the grid: one workgroup of 256 threads per sequence and 64 float4 columns where there are many sequences - launch_pool)
+inline bool pool_ok(long long S, int L, int D) {
+    return S >= 1 && S < (1ll << 31) && L >= 1 && D >= 4 && D % 4 == 0 && grid_fits(S * ceil_div(D / 4, 64), 256);
+}
 // `first` (STGCN_VIT_POOL_CLS): the "pool" is token 0 of every sequence - the selection over a sequence of one token, L apart.
 int launch_pool(const float *x, float *out, long long S, int L, int D, bool max, hipStream_t st, bool first = false);
 // logits (N, classes) = LayerNorm_D(pool_L(x (N, L, D))) W^T + bias, one workgroup per clip: the pooled row and its LayerNorm
 // in LDS, a wave per class.  D % 64 == 0, D <= kMaxLnDim (the blocks' rule), any L and classes.  bias may be NULL.
 inline bool pool_classify_ok(int N, int L, int D, int classes) {
-    return N >= 1 && L >= 1 && classes >= 1 && D >= 64 && D % 64 == 0 && D <= kMaxLnDim;
+    return N >= 1 && L >= 1 && classes >= 1 && D >= 64 && D % 64 == 0 && D <= kMaxLnDim && grid_fits(N, 1024);   // (kClsThreads)
 }
 int launch_pool_classify(const float *x, const float *gamma, const float *beta, float eps, const float *W, const float *bias,
                          float *logits, int N, int L, int D, int classes, bool max, hipStream_t st, bool first = false);

@@ -311,7 +311,7 @@ int launch_hd(const float *qkv, const float *out, const float *dout, float *dqkv
               float scale, hipStream_t st) {
     const int nb = ceil_div(L, kStreamQueries);            // blocks of 128 queries, and of 128 keys, per pair
     const long long blocks = (long long)B * H * nb;
-    if (blocks > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward (stream): %lld workgroups", blocks);
+    if (!grid_fits(blocks, kBwdThreads)) return fail(STGCN_ERR_UNSUPPORTED, "vit attention backward (stream): %lld workgroups", blocks);
     const size_t qbytes = (size_t)2 * 2 * kBwdRows * (HD + kPadF32) * sizeof(float);
     const size_t kbytes = qbytes + (size_t)2 * kBwdRows * 4 * sizeof(float);
     auto qkern = vit_attention_bwd_stream_q_kernel<HD>;

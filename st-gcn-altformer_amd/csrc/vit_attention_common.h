@@ -95,7 +95,7 @@ template <class F, int HD, int NT, class... P>
 int launch_resident_one(int B, int L, int H, float scale, hipStream_t st, P... ptrs) {
     constexpr int G = attention_pairs(NT);
     const long long pairs = (long long)B * H;
-    if (pairs > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "%s: %lld (sequence, head) pairs", F::what, pairs);
+    if (pairs > 0x7fffffffLL || !grid_fits((pairs + G - 1) / G, 64 * G * NT)) return fail(STGCN_ERR_UNSUPPORTED, "%s: %lld (sequence, head) pairs", F::what, pairs);
     constexpr size_t bytes = F::lds_bytes(NT, HD);
     if (bytes > (size_t)kLdsBytes) return fail(STGCN_ERR_UNSUPPORTED, "%s: %zu bytes of LDS", F::what, bytes);
     auto kern = F::template kernel<HD, NT>();

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(64 * NT) void vit_attention_split_kernel(const floa
 template <int HD, int NT>
 int launch_split_one(const float *qkv, float *out, int B, int L, int H, float scale, hipStream_t st) {
     const long long groups = (long long)B * H * NT;
-    if (groups > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention split: %lld workgroups", groups);
+    if (!grid_fits(groups, 64 * NT)) return fail(STGCN_ERR_UNSUPPORTED, "vit attention split: %lld workgroups", groups);
     constexpr size_t bytes = attention_split_lds_bytes(NT, HD);
     static_assert(bytes <= (size_t)kLdsBytes, "the merge buffers fit the LDS");
     auto kern = vit_attention_split_kernel<HD, NT>;

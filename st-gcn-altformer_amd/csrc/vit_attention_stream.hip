@@ -151,13 +151,19 @@ __global__ __launch_bounds__(kStreamThreads) void vit_attention_stream_kernel(co
 template <int HD>
 int launch_hd(const float *qkv, float *out, int B, int L, int H, float scale, hipStream_t st) {
     const int nqb = ceil_div(L, kStreamQueries);
-    const long long blocks = (long long)B * H * nqb;
-    if (blocks > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit attention (stream): %lld workgroups", blocks);
+    const long long per_seq = (long long)H * nqb;          // workgroups of one sequence
+    if (!grid_fits(per_seq, kStreamThreads)) return fail(STGCN_ERR_UNSUPPORTED, "vit attention (stream): %lld workgroups a sequence", per_seq);
     const size_t bytes = (size_t)2 * kStreamKeys * (2 * HD + kPadF32) * sizeof(float);
     auto kern = vit_attention_stream_kernel<HD>;
     if (bytes > 64 * 1024) STGCN_HIP_CHECK(allow_lds(kern, bytes));
-    kern<<<dim3((unsigned)blocks), dim3(kStreamThreads), bytes, st>>>(qkv, out, L, H, scale, nqb);
-    STGCN_LAUNCH_CHECK("vit_attention_stream_kernel");
+    // sequences are independent: as many of them a launch as its 2^32 work-items hold (grid_fits), the pointers moved on
+    const long long seqs = 0xffffffffLL / kStreamThreads / per_seq;
+    for (long long b0 = 0; b0 < B; b0 += seqs) {
+        const long long nb = B - b0 < seqs ? B - b0 : seqs;
+        kern<<<dim3((unsigned)(nb * per_seq)), dim3(kStreamThreads), bytes, st>>>(qkv + (size_t)b0 * L * 3 * H * HD,
+                                                                                  out + (size_t)b0 * L * H * HD, L, H, scale, nqb);
+        STGCN_LAUNCH_CHECK("vit_attention_stream_kernel");
+    }
     return STGCN_OK;
 }
 

@@ -430,6 +430,7 @@ int launch_wgrad(const float *dY, const float *A, const float *rowscale, int L, 
 
 int launch_ln_backward(const float *x, const float *dn, const float *gamma, const float *beta, float eps, const float *dres,
                        float *dx, float *a, float *stats, int M, int D, hipStream_t st) {
+    if (!grid_fits(ceil_div(M, 4), 256)) return fail(STGCN_ERR_UNSUPPORTED, "vit layernorm backward: %d rows exceed the grid", M);
     vit_ln_backward_kernel<<<dim3(ceil_div(M, 4)), dim3(256), 0, st>>>(x, dn, gamma, beta, eps, dres, dx, a, stats, M, D);
     STGCN_LAUNCH_CHECK("vit_ln_backward_kernel");
     return STGCN_OK;

@@ -233,7 +233,7 @@ int launch_pool(const float *x, float *out, long long S, int L, int D, bool max,
     const int D4 = D / 4;
     const bool wide = S * ceil_div(D4, 64) >= 1024;
     const int chunks = ceil_div(D4, wide ? 64 : 16);
-    if (S * chunks >= (1ll << 31)) return fail(STGCN_ERR_UNSUPPORTED, "vit pool: %lld sequences of %d columns exceed the grid", S, D);
+    if (!grid_fits(S * chunks, 256)) return fail(STGCN_ERR_UNSUPPORTED, "vit pool: %lld sequences of %d columns exceed the grid", S, D);
     const dim3 grid((unsigned)(S * chunks));
     if (wide) {
         if (max) hipLaunchKernelGGL((vit_pool_kernel<64, true>), grid, dim3(256), 0, st, x, out, L, Ls, D4, chunks);
@@ -350,7 +350,8 @@ int stgcn_vit_pool_classify(const float *x, const float *ln_weight, const float 
     REQUIRE_POS(N); REQUIRE_POS(L); REQUIRE_POS(D); REQUIRE_POS(classes);
     if (!aligned16(x) || !aligned16(W)) return fail(STGCN_ERR_ARG, "stgcn_vit_pool_classify: x and W must be 16-byte aligned");
     if (!pool_classify_ok(N, L, D, classes))
-        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_pool_classify: D = %d (covered: D %% 64 == 0, D <= %d)", D, kMaxLnDim);
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_pool_classify: N = %d, D = %d (covered: D %% 64 == 0, D <= %d, N < 2^22 clips)",
+                    N, D, kMaxLnDim);
     return launch_pool_classify(x, ln_weight, ln_bias, ln_eps, W, bias, logits, N, L, D, classes, (flags & STGCN_VIT_POOL_MAX) != 0,
                                 static_cast<hipStream_t>(stream), (flags & STGCN_VIT_POOL_CLS) != 0);
 }

@@ -46,7 +46,7 @@ int launch_form(const void *X, const float *W, const float *bias, const float *R
                 void *Y, int M, int K, int Nout, bool gelu, const LinearExtra &ex, hipStream_t st) {
     const int tiles_n = ceil_div(Nout, F::BN);
     const long long tiles = (long long)tiles_n * ceil_div(M, F::BM);
-    if (tiles > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit linear: %lld tiles", tiles);
+    if (!grid_fits(tiles, F::THREADS)) return fail(STGCN_ERR_UNSUPPORTED, "vit linear: %lld tiles", tiles);
     vit_linear_kernel<MATH, F, XB, YB><<<dim3((unsigned)tiles), dim3(F::THREADS), 0, st>>>(X, W, bias, R, gamma, beta, eps, Y, M, K, Nout,
                                                                                  tiles_n, gelu, ex, DenseRows{});
     STGCN_LAUNCH_CHECK("vit_linear_kernel");

@@ -60,7 +60,7 @@ int launch_patch_form(const PatchPlan &p, const float *z, const float *W, float 
                       hipStream_t st) {
     const int tiles_n = ceil_div(E, F::BN);
     const long long tiles = (long long)tiles_n * ceil_div(p.M, F::BM);
-    if (tiles > 0x7fffffffLL || p.splits > 65535) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed: %lld tiles x %d slabs", tiles, p.splits);
+    if (!grid_fits(tiles, F::THREADS) || p.splits > 65535) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed: %lld tiles x %d slabs", tiles, p.splits);
     PatchRows rows;
     rows.n = p.n, rows.w = p.w, rows.run = p2 * C, rows.frame = V * C, rows.patch_rows = p1 * V * C, rows.clip = T * V * C;
     rows.cps = p.cps;
@@ -85,7 +85,7 @@ inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 int launch_patch_transpose(const float *z, float *zt, int N, int C, int P, hipStream_t st) {
     const int tiles_p = ceil_div(P, 32), tiles_c = ceil_div(C, 32);
     const long long blocks = (long long)N * tiles_p * tiles_c;
-    if (blocks > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed: %lld transpose tiles", blocks);
+    if (!grid_fits(blocks, 256)) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed: %lld transpose tiles", blocks);
     vit_patch_transpose_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(z, zt, C, P, tiles_p, tiles_c);
     STGCN_LAUNCH_CHECK("vit_patch_transpose_kernel");
     return STGCN_OK;

@@ -43,7 +43,7 @@ int launch_dgrad_form(const PatchBackwardPlan &p, const PatchGradRows &rows, con
                       hipStream_t st) {
     const int tiles_n = ceil_div(p.K, F::BN);
     const long long tiles = (long long)tiles_n * ceil_div(p.M, F::BM);
-    if (tiles > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed backward: %lld tiles", tiles);
+    if (!grid_fits(tiles, F::THREADS)) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed backward: %lld tiles", tiles);
     LinearExtra ex;
     ex.kx = E;   // dx's rows are E long; the transposed weight's are padded to Epad with zeros
     vit_linear_kernel<MATH, F, false, false, PatchGradRows><<<dim3((unsigned)tiles), dim3(F::THREADS), 0, st>>>(
@@ -77,7 +77,7 @@ int launch_patch_embed_backward(const PatchBackwardPlan &p, const PatchBackwardS
         // dbias alone: the workgroups of the first K tile, which sum dx's columns exactly as they do beside the others
         const int tiles_n = ceil_div(E, WT), tiles_k = dW != nullptr ? ceil_div(p.K, WT) : 1;
         const long long blocks = (long long)tiles_n * tiles_k * p.splits;
-        if (blocks > 0x7fffffffLL) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed backward: %lld wgrad workgroups", blocks);
+        if (!grid_fits(blocks, 256)) return fail(STGCN_ERR_UNSUPPORTED, "vit patch embed backward: %lld wgrad workgroups", blocks);
         float *bpart = dbias != nullptr ? store.part + (size_t)p.splits * E * p.K : nullptr;
         PatchWgradRows pol;
         pol.rows = rows;

@@ -295,8 +295,13 @@ def agcn_backward_train(x, A_eff, Wa, ba, Wb, bb, Wd, bd, Wdown, bdown, P, zm, z
     S, inter_c, _ = Wa.shape
     Cout = Wd.shape[1]
     has_down = Wdown is not None
-    # bit 1: size for the generic path whenever the call may take it (dx, identity residual, non-stem shapes)
-    nbytes = _capi.lib().stgcn_agcn_backward_ws_bytes(N, Cin, Cout, T, V, S, (1 if zm is None else 0) | 2)
+    # bit 1: size for the generic path whenever the call may take it (dx, identity residual, non-stem shapes).  The one call
+    # that cannot - the stem class's moment form, by stgcn_agcn_backward_train's own rule - asks for its own size: the
+    # GEMM chain's workspace grows with N*Cout*T*V (58 GiB at 63553 clips of 12 x 22), the moment form's does not.  (The
+    # shape test is belt and braces: the query itself answers the chain's size where the moment form does not cover the
+    # shape, and the entry point compares the size it is given with the plan it takes.)
+    moment_form = not (frozen or not has_down or need_dx or zm is not None or y is None) and Cin == 3 and S == 3
+    nbytes = _capi.lib().stgcn_agcn_backward_ws_bytes(N, Cin, Cout, T, V, S, (1 if zm is None else 0) | (0 if moment_form else 2))
     if nbytes == 0:
         raise NotImplementedError(f"unit_agcn backward: shape Cin={Cin} S={S} Cout={Cout} V={V} is not covered by the HIP path")
     ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)

@@ -94,7 +94,7 @@ def agcn(N, cin, cout, T, V):
                                   st["bn_scale"], st["bn_shift"], st["down_scale"], st["down_shift"])
             return {"y": y, "P": P, "P_attention": F.agcn_attention(xd, st["A_eff"], st["Wa"], st["ba"], st["Wb"], st["bb"])}
         return run
-    return Setup(x, reference, on)
+    return Setup(x, reference, on, module=gcn)
 
 
 # (N, T, V, C).  (1, 30, 64) is in the list of the ragged test, where the modules fall back to two stages: no fused kernel covers
@@ -198,7 +198,8 @@ def agcn_train(cin, cout, N, T, V, want_dx, kink_free=False, frozen=False):
     ``frozen`` statistics, test_eval_mode_backward_unit_agcn_vs_oracle; ``leaves`` names the parameter gradients "d" + leaf.
     ``kink_free``: the cotangent is _util.kink_free_cotangent of the first ``reference(x)`` - the clean input's.  ``on(dev, fresh)``:
     every run steps a fresh copy of the module and reports its running buffers after the step, or (``fresh=False``) the module
-    itself with its gradients cleared."""
+    itself with its gradients cleared; ``tile``: the cotangent repeated that often along the clips, for a tiled batch
+    (tests/large_extent.py)."""
     from oracle import stgcn_oracle as so
     gcn, _, gp, _, gen = random_stem(V, None, 2000 + cin + cout + T + V, CPU, cin=cin, c=cout)
     gp = gp.to(torch.float64)
@@ -223,9 +224,9 @@ def agcn_train(cin, cout, N, T, V, want_dx, kink_free=False, frozen=False):
             out["dx"] = grads[-1]
         return out
 
-    def on(dev, fresh=True):
+    def on(dev, fresh=True, tile=1):
         master = gcn.to(dev).train(not frozen)
-        Gd = G[0].to(dev)
+        Gd = G[0].to(dev).repeat(tile, 1, 1, 1)
 
         def run(x):
             m = master
@@ -246,7 +247,7 @@ def agcn_train(cin, cout, N, T, V, want_dx, kink_free=False, frozen=False):
                 out["dx"] = xg.grad
             return out
         return run
-    return Setup(x, reference, on, leaves=names)
+    return Setup(x, reference, on, leaves=names, module=gcn)
 
 
 # ---- the temporal conv ----------------------------------------------------------------------------------------------------------
@@ -320,7 +321,8 @@ def tcn(cin, cout, K, stride, T, V, N, math, out_bf16, along_v):
 
 def tcn_train(cin, cout, K, stride, N, T, V, math, bias=True, kink_free=False):
     """Unit2D's training step through the module (tcn_forward_train -> tcn_backward_train), as test_unit2d_backward_vs_oracle.
-    ``kink_free`` and ``on(dev, fresh)``: as agcn_train's."""
+    ``kink_free`` and ``on(dev, fresh)``: as agcn_train's.  ``module`` / ``cotangent`` ([G], filled by the first ``reference``):
+    for callers of the functional pair."""
     from stgcn_amd import Unit2D, set_math_mode
     from oracle import stgcn_oracle as so
     torch.manual_seed(900 + cin + K + V)
@@ -368,14 +370,13 @@ def tcn_train(cin, cout, K, stride, N, T, V, math, bias=True, kink_free=False):
                 out["dbias"] = m.conv.bias.grad
             return out
         return run
-    return Setup(x, reference, on)
+    return Setup(x, reference, on, module=master, cotangent=G)
 
 
 # ---- patch embedding, ST-TR's spatial attention unit ----------------------------------------------------------------------------
-def patch_embed(order, layout):
+def patch_embed(order, layout, N=2, C=128, T=9, V=25, E=256):
     """F.patch_embed with and without the positional embedding, from (N,C,T,V) or channels-last memory; outputs as (N, -1, L, E):
     axis 0 is the clip."""
-    N, C, T, V, E = 2, 128, 9, 25, 256
     g = torch.Generator().manual_seed(61 + (order == "TS"))
     z = torch.randn(N, C, T, V, generator=g)
     W, b = torch.randn(E, C, generator=g) / C ** 0.5, torch.randn(E, generator=g) * 0.1
@@ -395,8 +396,8 @@ def patch_embed(order, layout):
             zd = z.to(dev)
             if layout == "ntvc":
                 zd = zd.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-            return {"e": F.patch_embed(zd, Wd, bd, pd, order=order).reshape(N, -1, L, E),
-                    "e_no_pos": F.patch_embed(zd, Wd, bd, None, order=order).reshape(N, -1, L, E)}
+            return {"e": F.patch_embed(zd, Wd, bd, pd, order=order).reshape(len(zd), -1, L, E),
+                    "e_no_pos": F.patch_embed(zd, Wd, bd, None, order=order).reshape(len(zd), -1, L, E)}
         return run
     return Setup(z, reference, on)
 
@@ -443,7 +444,8 @@ TRAIN_STRICT = {"f32": True, "mixed": True, "bf16x3": False}
 
 
 def vit_linear(M, K, Nout, math):
-    """F.vit_linear in every tile form: "on" + tile with LayerNorm, bias, GELU and residual, "off" + tile the bare product."""
+    """F.vit_linear in every tile form: "on" + tile with LayerNorm, bias, GELU and residual, "off" + tile the bare product.
+    ``W``, ``b``, ``R``, ``ln``: the CPU operands, for callers that choose the epilogue themselves."""
     g = torch.Generator().manual_seed(M + K + Nout)
     x = torch.randn(M, K, generator=g) * (0.25 + 3.75 * torch.rand(M, 1, generator=g)) + torch.randn(M, 1, generator=g)
     W = (torch.rand(Nout, K, generator=g) * 2 - 1) / K ** 0.5
@@ -469,7 +471,7 @@ def vit_linear(M, K, Nout, math):
                 out[f"off{tile}"] = F.vit_linear(xd, Wd, None, math=mode | fl)
             return out
         return run
-    return Setup(x, reference, on)
+    return Setup(x, reference, on, W=W, b=b, R=Rr, ln=(lw, lb))
 
 
 def peaked_qkv(B, L, heads, hd, seed, amp=2.3):
