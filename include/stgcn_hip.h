@@ -767,7 +767,7 @@ int stgcn_vit_patch_embed(const float *z, const float *W, const float *bias, con
  * Flags: as the older pair (f32 / bf16x3 low bits, STGCN_VIT_QKV_F32, STGCN_VIT_TRAIN_BF16, STGCN_VIT_TRAIN_ATTN_BF16;
  * STGCN_VIT_BF16 and STGCN_VIT_ATTN_SPLIT: STGCN_ERR_ARG before the pointers are looked at), with one difference: a
  * STGCN_VIT_TILE_* field is accepted and selects the tile form of every forward and dgrad linear of the call (the weight
- * gradient kernels have one form).  Results are bit-identical across the forms, as in inference.
+ * gradients' form is not this field's: STGCN_VIT_WGRAD_SMALL, at the end of this header).  Results are bit-identical across the forms, as in inference.
  * With no mask and no tile field the pair runs what the older pair runs, bit for bit: both are one forward and one backward. */
 typedef struct { const float *m_proj, *m_act, *m_fc2; } stgcn_vit_drop_masks;
 typedef struct { float *norm1_weight, *norm1_bias, *Wqkv, *bqkv, *Wproj, *bproj,
@@ -829,6 +829,39 @@ size_t stgcn_vit_pool_classify_backward_ws_bytes(int N, int L, int D, int classe
 int stgcn_vit_pool_classify_backward(const float *x, const float *ln_weight, const float *ln_bias, float ln_eps, const float *W,
                                      const float *dlogits, float *dx, float *dln_weight, float *dln_bias, float *dW, float *dbias,
                                      int N, int L, int D, int classes, void *ws, size_t ws_bytes, unsigned flags, void *stream);
+
+/* ---- ViT block: small training calls (additive to ABI 11: one flag, five queries) ----
+ * The weight-gradient kernels (fp32, and bf16 operands under STGCN_VIT_TRAIN_BF16) have two forms: a workgroup owns a
+ * 128 x 128 tile of dW, or a 64 x 64 one (the same instruction, chunk of 32 tokens and staging; four times the workgroups per
+ * split).  Without the flag below every weight gradient runs the 128 form with the tokens cut into uniform splits of at least
+ * 256, as it always did.  STGCN_VIT_WGRAD_SMALL lets every weight gradient of the call pick per product (M tokens, dW (Nout, K)):
+ *   - where that 128 launch already has 256 workgroups or more: the 128 form, in as many splits as that rule aims at, cut evenly;
+ *   - else the 64 form in min(floor(256 / tiles64), chunks / 4) (at least 1) even splits, tiles64 = ceil(Nout / 64) ceil(K / 64),
+ *     chunks = ceil(M / 32), where that gives no fewer workgroups than the 128 launch; where it would, the 128 form as above.
+ * Splits are ranges of whole chunks of 32 tokens (the first chunks % splits of them one chunk longer), none empty, each at least
+ * 4 chunks long in the 64 form.  The workgroup count never falls as M grows and is never below the unflagged launch's.  The
+ * slabs are added in split order, no atomics: two runs are bit-identical.  Where a product has ONE split and the call does not
+ * accumulate onto dW (every call of stgcn_vit_linear_backward; the first slab of sequences of a block call), the kernel stores
+ * dW and db itself and the two summing launches are skipped.  Against the unflagged call the weight and bias gradients differ
+ * in summation order only (a bias gradient also between the forms); dx and everything else is the same bits.
+ * The flag is a bit of its own, not part of the STGCN_VIT_TILE_* field, which keeps selecting forward and dgrad forms only.
+ * Read by stgcn_vit_block_backward_drop and stgcn_vit_linear_backward; accepted and ignored by
+ * stgcn_vit_block_forward_train_drop (no weight gradient runs there); every other entry point that plans a block
+ * (stgcn_vit_block_forward, stgcn_vit_block_forward_train, stgcn_vit_block_backward) answers STGCN_ERR_ARG naming it, before the
+ * pointers are looked at.
+ * Queries (pure host functions; `flags`: only STGCN_VIT_WGRAD_SMALL is read; 0 for an empty shape):
+ *   stgcn_vit_wgrad_tile: 128 or 64;  stgcn_vit_wgrad_splits;  stgcn_vit_wgrad_writes_direct: 1 where the kernel stores dW
+ *   itself in a call that does not accumulate (always 0 without the flag: such calls keep their summing launches).
+ * Workspaces: more splits need more slab space, so the flagged calls have size queries of their own, which answer what the
+ * older ones answer without the flag and at least that with it: stgcn_vit_block_train_small_ws_bytes (for
+ * stgcn_vit_block_backward_drop) and stgcn_vit_linear_backward_small_ws_bytes.  Each entry point checks the workspace its own
+ * flags need and answers STGCN_ERR_WORKSPACE before any launch. */
+#define STGCN_VIT_WGRAD_SMALL (0x10000000u)
+int stgcn_vit_wgrad_tile(int M, int K, int Nout, unsigned flags);
+int stgcn_vit_wgrad_splits(int M, int K, int Nout, unsigned flags);
+int stgcn_vit_wgrad_writes_direct(int M, int K, int Nout, unsigned flags);
+size_t stgcn_vit_block_train_small_ws_bytes(int B, int L, int D, int heads, int hidden, unsigned flags);
+size_t stgcn_vit_linear_backward_small_ws_bytes(int M, int K, int Nout, unsigned flags);
 
 #ifdef __cplusplus
 }

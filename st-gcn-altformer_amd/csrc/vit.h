@@ -121,6 +121,9 @@ struct BlockPlan {
     bool bf16_store = false;         // qkv, the attention output and the fc1 hidden are bf16 storage between the launches
     // the STGCN_VIT_TILE_* field the forward's linears get (and the dgrads of backward_drop); the older training pair: 0, 128 x 128 only
     unsigned tile = 0;
+    // STGCN_VIT_WGRAD_SMALL (backward_drop, linear_backward): every weight gradient picks its form and cut per product
+    // (plan_wgrad below); without it all of them run the 128 form on wgrad_rows_per_split's cut.
+    bool wgrad_small = false;
 };
 
 inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidden, unsigned flags) {
@@ -136,10 +139,15 @@ inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidde
             p.refusal = "STGCN_VIT_BF16 and STGCN_VIT_QKV_F32 exclude each other";
         else if (flags & STGCN_VIT_TRAIN_ATTN_BF16)
             p.refusal = "STGCN_VIT_TRAIN_ATTN_BF16 is a training mode (stgcn_vit_block_forward_train, stgcn_vit_block_backward only)";
+        else if (flags & STGCN_VIT_WGRAD_SMALL)
+            p.refusal = "STGCN_VIT_WGRAD_SMALL is a training option (stgcn_vit_block_backward_drop, stgcn_vit_linear_backward)";
     } else if (flags & STGCN_VIT_BF16) {
         p.refusal = "STGCN_VIT_BF16 is an inference mode (stgcn_vit_block_forward only)";
     } else if ((flags & STGCN_VIT_TILE_MASK) && !block_entry_drop(entry)) {
         p.refusal = "training runs the 128 x 128 linear only (STGCN_VIT_TILE_* set)";
+    } else if ((flags & STGCN_VIT_WGRAD_SMALL) && !block_entry_drop(entry) && entry != BlockEntry::linear_backward) {
+        p.refusal = "STGCN_VIT_WGRAD_SMALL is read by stgcn_vit_block_forward_train_drop, stgcn_vit_block_backward_drop and "
+                    "stgcn_vit_linear_backward only";
     } else if (entry == BlockEntry::linear_backward && (flags & STGCN_VIT_TRAIN_ATTN_BF16)) {
         p.refusal = "STGCN_VIT_TRAIN_ATTN_BF16 is a mode of the block (stgcn_vit_block_forward_train, stgcn_vit_block_backward only)";
     } else if (flags & STGCN_VIT_ATTN_SPLIT) {
@@ -151,6 +159,7 @@ inline BlockPlan plan_block(BlockEntry entry, int L, int D, int heads, int hidde
     // operands for every product of a linear (fp32 in memory on both sides) but the qkv FORWARD, which stays what it is
     // without the bit, for the reason above.
     p.wgrad_bf16 = !inference && (flags & STGCN_VIT_TRAIN_BF16) != 0;
+    p.wgrad_small = (entry == BlockEntry::backward_drop || entry == BlockEntry::linear_backward) && (flags & STGCN_VIT_WGRAD_SMALL) != 0;
     p.bf16_store = bf16;
     p.tile = inference || block_entry_drop(entry) ? flags & STGCN_VIT_TILE_MASK : 0;
     p.qkv_fwd = bf16 ? (unsigned)STGCN_MATH_BF16 : (flags & STGCN_VIT_QKV_F32) ? (unsigned)STGCN_MATH_F32 : low;
@@ -300,22 +309,78 @@ int launch_transpose_pad(const float *W, float *Wt, int rows, int cols, int rows
 int launch_mask_mul(const float *a, const float *m, float *out, size_t n, hipStream_t st);
 
 // Weight / bias gradient of Y = A W^T + b over the rows [0, M):  dW (Nout, K) = (s dY)^T A,  db (Nout) = column sums of s dY,
-// s = rowscale[row / L] or 1.  The reduction over M is cut into wgrad_splits(M, K, Nout) row ranges; each writes one slab of
+// s = rowscale[row / L] or 1.  The reduction over M is cut into row ranges (plan_wgrad below); each writes one slab of
 // `part` ((Nout * K) floats per split, then Nout floats per split for the bias) and launch_sum_parts adds them in split order.
 // fp32 matrix cores (v_mfma_f32_32x32x2_f32), no atomics.  `accumulate`: add onto dW / db (sum in `tmp` first).
 constexpr int kWgradChunk = 32;                       // tokens per LDS chunk of both wgrad kernels
 int wgrad_rows_per_split(int M, int K, int Nout);   // a multiple of kWgradChunk
-int wgrad_splits(int M, int K, int Nout);
-size_t wgrad_part_floats(int M, int K, int Nout);   // floats of `part`, and of `tmp` = Nout * K + Nout
-int launch_wgrad(const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part, float *tmp,
-                 int M, int K, int Nout, bool accumulate, hipStream_t st);
+
+// ---- the form and the cut of one weight gradient, chosen here and nowhere else ----
+// Both kernels have two forms: a workgroup owns a 128 x 128 tile of dW (2 x 2 accumulator blocks per wave) or a 64 x 64 one
+// (one block per wave, four times the workgroups per split).  Split s covers the chunks [s cps + min(s, long_splits), ...),
+// cps + 1 of them for the first long_splits splits and cps for the rest: ranges are multiples of the chunk, none is empty.
+struct WgradPlan {
+    int tile = 128;                       // 128 or 64
+    int splits = 1, cps = 1, long_splits = 0;
+    bool may_direct = false;              // STGCN_VIT_WGRAD_SMALL only: calls without it keep their launch_sum_parts
+    long long workgroups(int K, int Nout) const { return (long long)ceil_div(Nout, tile) * ceil_div(K, tile) * splits; }
+    // one split that does not accumulate: the kernel stores dW and db itself, no slab and no launch_sum_parts
+    bool direct(bool accumulate) const { return may_direct && splits == 1 && !accumulate; }
+    size_t part_floats(int K, int Nout) const { return (size_t)splits * ((size_t)Nout * K + Nout); }
+};
+// A launch of the 128 form on today's cut hands over to nothing smaller from this many workgroups on: one per CU of the
+// MI355X, a compile-time constant as kLinearTileCut is (the plan never asks the device).
+constexpr int kWgradHandOver = 256;
+constexpr int kWgradSmallMinChunks = 4;   // a split of the small rule is at least this many chunks (128 tokens) long
+
+inline WgradPlan wgrad_cut(int tile, int chunks, int splits) {   // `splits` ranges of whole chunks, as even as they come
+    WgradPlan w;
+    w.tile = tile, w.splits = splits, w.cps = chunks / splits, w.long_splits = chunks % splits;
+    w.may_direct = true;
+    return w;
+}
+
+// small == false: the 128 form on wgrad_rows_per_split's uniform cut, what every call ran before there was a choice.
+// small == true (STGCN_VIT_WGRAD_SMALL), with u = the workgroups of that launch:
+//   u >= kWgradHandOver: the 128 form in as many splits as that rule aims at, min(ceil(512 / tiles128), ceil(M / 256)), cut
+//   evenly (the uniform cut rounds a split up to whole chunks and can so end a split or two short of its aim, 29 for 32
+//   at 8,193 tokens of D = 512: a count that falls while M grows);
+//   else the 64 form, in min(floor(kWgradHandOver / tiles64), chunks / kWgradSmallMinChunks) (at least one) even splits,
+//   where that gives at least u workgroups; where it does not (tiles64 so many that two splits would pass the hand-over
+//   count, while the 128 form's cut has grown past one split's worth), the 128 form as in the first case.
+// The 64 form's target is the hand-over count, one workgroup per CU, not the 128 rule's two: a count that stepped DOWN where
+// the rows grow into the 128 form would make a larger call the slower one.  With these pieces the workgroup count never
+// falls as M grows and is never below u.  A split of the 64 form is at least 4 chunks long: it reads 2 x 128 x 64 floats
+// (64 KB) of operands for a 16 KB slab that launch_sum_parts reads again, so slab traffic stays at half the operand
+// traffic or less; at 2 chunks the two would be level.
+inline WgradPlan plan_wgrad(int M, int K, int Nout, bool small) {
+    const int rps = wgrad_rows_per_split(M, K, Nout);
+    WgradPlan w;
+    w.splits = ceil_div(M, rps), w.cps = rps / kWgradChunk;
+    if (!small) return w;
+    const long long u = w.workgroups(K, Nout);
+    const int chunks = ceil_div(M, kWgradChunk), tiles128 = ceil_div(Nout, 128) * ceil_div(K, 128);
+    const int aim = ceil_div(512, tiles128) < ceil_div(M, 256) ? ceil_div(512, tiles128) : ceil_div(M, 256);
+    if (u >= kWgradHandOver) return wgrad_cut(128, chunks, aim);
+    const long long tiles64 = (long long)ceil_div(Nout, 64) * ceil_div(K, 64);
+    long long s = kWgradHandOver / tiles64;
+    if (s > chunks / kWgradSmallMinChunks) s = chunks / kWgradSmallMinChunks;
+    if (s < 1) s = 1;
+    if (tiles64 <= kWgradHandOver && tiles64 * s >= u) return wgrad_cut(64, chunks, (int)s);
+    return wgrad_cut(128, chunks, aim);
+}
+inline WgradPlan plan_wgrad(const BlockPlan &p, int M, int K, int Nout) { return plan_wgrad(M, K, Nout, p.wgrad_small); }
+
+// `wp`: plan_wgrad's answer for this product; `part` holds wp.part_floats(K, Nout) floats (not touched where wp.direct()).
+int launch_wgrad(const WgradPlan &wp, const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db,
+                 float *part, float *tmp, int M, int K, int Nout, bool accumulate, hipStream_t st);
 // partial slabs of n floats -> dst, or (accumulate) dst += their sum taken in `tmp`; slab order, no atomics
 int reduce_parts(const float *part, int parts, size_t n, float *dst, float *tmp, bool accumulate, hipStream_t st);
 // The same gradient in the STGCN_VIT_TRAIN_BF16 arithmetic (vit_wgrad_bf16.hip): dW = r(s dY)^T r(A) with r = round to
 // nearest-even bf16 applied while the operands are staged (after the row factor), fp32 accumulate on
 // v_mfma_f32_32x32x16_bf16; db sums the unrounded fp32 s dY.  Same splits, slabs, workspace and reduction as launch_wgrad.
-int launch_wgrad_bf16(const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part,
-                      float *tmp, int M, int K, int Nout, bool accumulate, hipStream_t st);
+int launch_wgrad_bf16(const WgradPlan &wp, const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db,
+                      float *part, float *tmp, int M, int K, int Nout, bool accumulate, hipStream_t st);
 
 // LayerNorm backward over the rows of x (M, D):  dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ dres),  g = dn * gamma; also
 // writes a = LN(x) (the input of the linear behind the LayerNorm, for its wgrad; may be NULL) and the rows' (mean, rstd) to

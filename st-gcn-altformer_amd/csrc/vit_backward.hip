@@ -10,6 +10,9 @@
 //   A workgroup of 4 waves owns a 128 x 128 tile of dW for one range of tokens; the column sums of dY (the bias gradient)
 //   ride in the workgroups of the first K tile, summed by the threads that stage dY.
 //   (The kernel itself is in vit_wgrad_kernel.h: the ST-ViT head's patch embedding runs it on rows of its own.)
+//   A second form of the same code owns a 64 x 64 tile (one accumulator block per wave, chunks of 32 x 64, a dense LDS image):
+//   four times the workgroups per split, for calls whose tokens cannot supply them.  plan_wgrad (vit.h) picks the form and
+//   the cut; where it says one split and the call does not accumulate, the slab the kernel writes is dW itself.
 //
 // attention backward: built from vit_attention_common.h, which describes the layout it shares with the forward.  One
 //   workgroup per (sequence, head) pair as there (several pairs for L <= 64), two phases:
@@ -402,6 +405,7 @@ int launch_mask_mul(const float *a, const float *m, float *out, size_t n, hipStr
 }
 
 // About 512 workgroups (two per CU) where the rows allow it, a split at least 256 rows long, ranges multiples of the chunk.
+// (The default cut of every weight gradient; plan_wgrad in vit.h builds STGCN_VIT_WGRAD_SMALL's rule next to it.)
 int wgrad_rows_per_split(int M, int K, int Nout) {
     const int tiles = ceil_div(Nout, WT) * ceil_div(K, WT);
     int splits = ceil_div(512, tiles);
@@ -410,21 +414,26 @@ int wgrad_rows_per_split(int M, int K, int Nout) {
     return ceil_div(ceil_div(M, splits), WC) * WC;
 }
 
-int wgrad_splits(int M, int K, int Nout) { return ceil_div(M, wgrad_rows_per_split(M, K, Nout)); }
-
-size_t wgrad_part_floats(int M, int K, int Nout) { return (size_t)wgrad_splits(M, K, Nout) * ((size_t)Nout * K + Nout); }
-
-int launch_wgrad(const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part, float *tmp,
-                 int M, int K, int Nout, bool accumulate, hipStream_t st) {
-    const int rps = wgrad_rows_per_split(M, K, Nout), splits = ceil_div(M, rps);
-    const int tiles_n = ceil_div(Nout, WT), tiles_k = ceil_div(K, WT);
-    float *bpart = db != nullptr ? part + (size_t)splits * Nout * K : nullptr;
-    vit_wgrad_kernel<DenseWgradRows><<<dim3((unsigned)(tiles_n * tiles_k * splits)), dim3(256), 0, st>>>(
-        dY, A, rowscale, L, part, bpart, M, K, Nout, tiles_n, tiles_k, rps, DenseWgradRows{});
+// The one launcher of both forms of the fp32 kernel.  Where the plan says one split and the caller does not accumulate, the
+// kernel's slab IS dW (and its bias slab db): no launch_sum_parts.
+int launch_wgrad(const WgradPlan &wp, const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db,
+                 float *part, float *tmp, int M, int K, int Nout, bool accumulate, hipStream_t st) {
+    const bool direct = wp.direct(accumulate);
+    const int tiles_n = ceil_div(Nout, wp.tile), tiles_k = ceil_div(K, wp.tile);
+    float *slab = direct ? dW : part;
+    float *bpart = db == nullptr ? nullptr : direct ? db : part + (size_t)wp.splits * Nout * K;
+    const dim3 grid((unsigned)(tiles_n * tiles_k * wp.splits));
+    if (wp.tile == 64)
+        vit_wgrad_kernel<DenseWgradRows, 64><<<grid, dim3(256), 0, st>>>(dY, A, rowscale, L, slab, bpart, M, K, Nout, tiles_n, tiles_k,
+                                                                         wp.cps, wp.long_splits, DenseWgradRows{});
+    else
+        vit_wgrad_kernel<DenseWgradRows, 128><<<grid, dim3(256), 0, st>>>(dY, A, rowscale, L, slab, bpart, M, K, Nout, tiles_n, tiles_k,
+                                                                          wp.cps, wp.long_splits, DenseWgradRows{});
     STGCN_LAUNCH_CHECK("vit_wgrad_kernel");
+    if (direct) return STGCN_OK;
     int rc;
-    if ((rc = reduce_parts(part, splits, (size_t)Nout * K, dW, tmp, accumulate, st))) return rc;
-    if (db != nullptr && (rc = reduce_parts(bpart, splits, (size_t)Nout, db, tmp, accumulate, st))) return rc;
+    if ((rc = reduce_parts(part, wp.splits, (size_t)Nout * K, dW, tmp, accumulate, st))) return rc;
+    if (db != nullptr && (rc = reduce_parts(bpart, wp.splits, (size_t)Nout, db, tmp, accumulate, st))) return rc;
     return STGCN_OK;
 }
 

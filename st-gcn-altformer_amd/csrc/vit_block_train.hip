@@ -34,11 +34,19 @@ namespace {
 
 size_t max2(size_t a, size_t b) { return a > b ? a : b; }
 
+// The slab space of one weight gradient.  `small` (the plan's wgrad_small): what plan_wgrad's cut needs and never less than the
+// default cut's, so that a workspace sized for a flagged call also serves the same call without the flag.
+size_t wgrad_part(int M, int K, int Nout, bool small) {
+    const size_t p = plan_wgrad(M, K, Nout, false).part_floats(K, Nout);
+    return small ? max2(p, plan_wgrad(M, K, Nout, true).part_floats(K, Nout)) : p;
+}
+
 // the backward's temporaries: one slab of gradients, the four transposed weights, the partial sums of one reduction
 struct BackwardWs {
     float *dhid, *dn, *dx1, *datt, *dqkv, *a, *stats, *wt_qkv, *wt_proj, *wt_fc1, *wt_fc2, *part, *tmp;
     size_t total;
-    BackwardWs(void *base, int B, int L, int D, int hidden) {
+    // `small`: the plan's wgrad_small, which sizes `part` for plan_wgrad's cut (never less than the default cut's)
+    BackwardWs(void *base, int B, int L, int D, int hidden, bool small = false) {
         const int M = slab_seqs(B, L) * L;
         const size_t rows = (size_t)M;
         Carve c(base);
@@ -53,10 +61,11 @@ struct BackwardWs {
         wt_proj = c.take<float>((size_t)D * D);
         wt_fc1 = c.take<float>((size_t)D * hidden);
         wt_fc2 = c.take<float>((size_t)D * hidden);
-        size_t p = wgrad_part_floats(M, D, 3 * D);
-        p = max2(p, wgrad_part_floats(M, D, D));
-        p = max2(p, wgrad_part_floats(M, D, hidden));
-        p = max2(p, wgrad_part_floats(M, hidden, D));
+        // (a shorter last slab needs no more under the small rule: its split count does not fall as the rows grow)
+        size_t p = wgrad_part(M, D, 3 * D, small);
+        p = max2(p, wgrad_part(M, D, D, small));
+        p = max2(p, wgrad_part(M, D, hidden, small));
+        p = max2(p, wgrad_part(M, hidden, D, small));
         p = max2(p, (size_t)ln_param_splits(M) * 2 * D);
         part = c.take<float>(p);
         tmp = c.take<float>(max2((size_t)3 * D * D, (size_t)D * hidden) + max2((size_t)3 * D, (size_t)hidden));
@@ -69,7 +78,7 @@ struct TrainWs {
     BackwardWs w;
     float *att_stats = nullptr;
     size_t total;
-    TrainWs(void *base, const BlockPlan &plan, int B, int L, int D, int heads, int hidden) : w(base, B, L, D, hidden) {
+    TrainWs(void *base, const BlockPlan &plan, int B, int L, int D, int heads, int hidden) : w(base, B, L, D, hidden, plan.wgrad_small) {
         Carve c(base);
         c.off = w.total;
         if (plan.attention == BlockAttention::stream) att_stats = c.take<float>(attention_stats_floats(slab_seqs(B, L), L, heads));
@@ -81,11 +90,11 @@ struct LinearBwdWs {
     float *wt, *part, *tmp;
     int nout_pad;
     size_t total;
-    LinearBwdWs(void *base, int M, int K, int Nout) {
+    LinearBwdWs(void *base, int M, int K, int Nout, bool small = false) {
         nout_pad = ceil_div(Nout, 32) * 32;
         Carve c(base);
         wt = c.take<float>((size_t)K * nout_pad);
-        part = c.take<float>(wgrad_part_floats(M, K, Nout));
+        part = c.take<float>(wgrad_part(M, K, Nout, small));
         tmp = c.take<float>((size_t)Nout * K + Nout);
         total = c.off;
     }
@@ -103,11 +112,12 @@ struct LnBwdWs {
     }
 };
 
-// the weight gradient in the arithmetic of the plan
+// the weight gradient in the arithmetic, form and cut of the plan
 int wgrad(const BlockPlan &plan, const float *dY, const float *A, const float *rowscale, int L, float *dW, float *db, float *part,
           float *tmp, int M, int K, int Nout, bool accumulate, hipStream_t st) {
-    return plan.wgrad_bf16 ? launch_wgrad_bf16(dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st)
-                           : launch_wgrad(dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st);
+    const WgradPlan wp = plan_wgrad(plan, M, K, Nout);
+    return plan.wgrad_bf16 ? launch_wgrad_bf16(wp, dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st)
+                           : launch_wgrad(wp, dY, A, rowscale, L, dW, db, part, tmp, M, K, Nout, accumulate, st);
 }
 
 bool linear_bwd_ok(int M, int K, int Nout) { return M >= 1 && K >= 1 && Nout >= 1 && K % 32 == 0 && Nout % 4 == 0; }
@@ -257,6 +267,24 @@ size_t stgcn_vit_linear_backward_ws_bytes(int M, int K, int Nout) {
     return LinearBwdWs(nullptr, M, K, Nout).total;
 }
 
+size_t stgcn_vit_linear_backward_small_ws_bytes(int M, int K, int Nout, unsigned flags) {
+    if (!linear_bwd_ok(M, K, Nout)) return 0;
+    return LinearBwdWs(nullptr, M, K, Nout, (flags & STGCN_VIT_WGRAD_SMALL) != 0).total;
+}
+
+// The three queries of plan_wgrad: `flags`: only STGCN_VIT_WGRAD_SMALL is read.  0 for an empty shape.
+int stgcn_vit_wgrad_tile(int M, int K, int Nout, unsigned flags) {
+    return M >= 1 && K >= 1 && Nout >= 1 ? plan_wgrad(M, K, Nout, (flags & STGCN_VIT_WGRAD_SMALL) != 0).tile : 0;
+}
+
+int stgcn_vit_wgrad_splits(int M, int K, int Nout, unsigned flags) {
+    return M >= 1 && K >= 1 && Nout >= 1 ? plan_wgrad(M, K, Nout, (flags & STGCN_VIT_WGRAD_SMALL) != 0).splits : 0;
+}
+
+int stgcn_vit_wgrad_writes_direct(int M, int K, int Nout, unsigned flags) {
+    return M >= 1 && K >= 1 && Nout >= 1 && plan_wgrad(M, K, Nout, (flags & STGCN_VIT_WGRAD_SMALL) != 0).direct(false) ? 1 : 0;
+}
+
 int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, const float *h_pre, float *dx, float *dW,
                               float *db, void *ws, size_t ws_bytes, int M, int K, int Nout, unsigned flags, void *stream) {
     const BlockPlan plan = plan_block(BlockEntry::linear_backward, 0, 0, 0, 0, flags);   // the flags' part of it: no block shape here
@@ -270,7 +298,7 @@ int stgcn_vit_linear_backward(const float *dy, const float *a, const float *W, c
     if (!linear_bwd_ok(M, K, Nout) || !plan.covered)
         return fail(STGCN_ERR_UNSUPPORTED, "stgcn_vit_linear_backward: K = %d, Nout = %d, math %u (covered: K %% 32 == 0, Nout %% 4 == 0, "
                     "f32 / bf16x3)", K, Nout, flags & STGCN_MATH_MASK);
-    const LinearBwdWs w(ws, M, K, Nout);
+    const LinearBwdWs w(ws, M, K, Nout, plan.wgrad_small);
     if (ws_bytes < w.total) return fail(STGCN_ERR_WORKSPACE, "stgcn_vit_linear_backward: workspace %zu < %zu bytes", ws_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc;
@@ -441,6 +469,11 @@ int stgcn_vit_block_train_drop_supported(int L, int D, int heads, int hidden) {
 
 size_t stgcn_vit_block_train_drop_ws_bytes(int B, int L, int D, int heads, int hidden) {
     const BlockPlan p = plan_block(BlockEntry::backward_drop, L, D, heads, hidden, 0);
+    return B >= 1 && p.covered ? TrainWs(nullptr, p, B, L, D, heads, hidden).total : 0;
+}
+
+size_t stgcn_vit_block_train_small_ws_bytes(int B, int L, int D, int heads, int hidden, unsigned flags) {
+    const BlockPlan p = plan_block(BlockEntry::backward_drop, L, D, heads, hidden, flags & STGCN_VIT_WGRAD_SMALL);
     return B >= 1 && p.covered ? TrainWs(nullptr, p, B, L, D, heads, hidden).total : 0;
 }
 

@@ -82,7 +82,7 @@ int launch_patch_embed_backward(const PatchBackwardPlan &p, const PatchBackwardS
         PatchWgradRows pol;
         pol.rows = rows;
         vit_wgrad_kernel<PatchWgradRows><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(dx, z, nullptr, 1, store.part, bpart, p.M, p.K,
-                                                                                      E, tiles_n, tiles_k, p.rps, pol);
+                                                                                      E, tiles_n, tiles_k, p.rps / WC, 0, pol);
         STGCN_LAUNCH_CHECK("vit_wgrad_kernel (patches)");
         if (dW != nullptr && (rc = launch_sum_parts(store.part, dW, p.splits, (size_t)E * p.K, st))) return rc;
         if (dbias != nullptr && (rc = launch_sum_parts(bpart, dbias, p.splits, (size_t)E, st))) return rc;

@@ -14,7 +14,17 @@ namespace wgrad_kernel {
 using bf16k::f32x16;
 using linear_kernel::PatchRows;
 
-constexpr int WT = 128, WC = kWgradChunk, WLD = 160;   // tile edge, tokens per chunk, LDS row stride (floats)
+constexpr int WT = 128, WC = kWgradChunk;   // the large form's tile edge, tokens per chunk
+// The LDS row stride (floats) of a form of tile edge T: 160 for the 128 form, as it always was, and 64, no padding, for the
+// 64 form.  Neither the fragment reads nor the staging stores depend on it (the bank rule is the one of the bf16 kernel's
+// header: 32 banks of 4 bytes for ds_read_b32 and every ds_write, conflicts only inside a lane group):
+//   reads : ds_read_b32 in two groups of 32 lanes; a group reads the 32 CONSECUTIVE floats row * stride + c + l31 of one
+//           chunk row (`half` picks the row and is constant in a group), 32 different banks whatever the stride;
+//   writes: ds_write_b128 in groups of eight consecutive lanes; T / 4 = 32 or 16 threads stage a row, a multiple of eight, so
+//           a group writes 128 contiguous bytes of one row: the 32 banks once each, for every stride that is a multiple of 4.
+// So the narrower image is dense: 2 x 32 x 64 floats = 16 KB against the 128 form's 40 KB.
+template <int T>
+constexpr int wld() { return T == 128 ? 160 : T; }
 
 __device__ __forceinline__ float4 load_row4(const float *p, int c, int width, bool vec) {
     if (c >= width) return make_float4(0.f, 0.f, 0.f, 0.f);
@@ -40,29 +50,37 @@ struct PatchWgradRows {
     __device__ __forceinline__ size_t dy_row(int m) const { return (size_t)m + m / rows.n + 1; }
 };
 
-template <class R>
+// `T`: the edge of the workgroup's tile of dW, 128 (each of the 4 waves holds 2 x 2 accumulator blocks of 32 x 32) or 64 (one
+// block each; four times the workgroups per split, for calls whose token count cannot supply them: plan_wgrad in vit.h).
+// Split `s` covers the chunks [s cps + min(s, long_splits), ...) of cps (+ 1 for the first long_splits splits) chunks:
+// long_splits = 0 is the uniform cut of wgrad_rows_per_split.
+template <class R, int T = WT>
 __global__ __launch_bounds__(256) void vit_wgrad_kernel(const float *__restrict__ dY, const float *__restrict__ A,
                                                        const float *__restrict__ rowscale, int L, float *__restrict__ part,
                                                        float *__restrict__ bpart, int M, int K, int Nout, int tiles_n,
-                                                       int tiles_k, int rows_per_split, const R pol) {
+                                                       int tiles_k, int cps, int long_splits, const R pol) {
+    static_assert(T == 128 || T == 64, "two forms");
+    constexpr int WLD = wld<T>(), NB = T / 64;          // LDS row stride; 32 x 32 blocks per wave and dimension
+    constexpr int TPR = T / 4, RS = 256 / TPR, NI = WC / RS;   // staging: threads per chunk row, rows per pass, passes
     __shared__ __attribute__((aligned(16))) float ld[WC * WLD], la[WC * WLD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
     const int tile = (int)blockIdx.x % (tiles_n * tiles_k), split = (int)blockIdx.x / (tiles_n * tiles_k);
-    const int n0 = (tile / tiles_k) * WT, k0 = (tile % tiles_k) * WT;
-    const int r_lo = split * rows_per_split, r_hi = min(M, r_lo + rows_per_split);
-    const int sr = tid >> 5, sc = (tid & 31) * 4;       // staging: rows sr + 8 i of the chunk, floats sc .. sc + 3 of the tile
+    const int n0 = (tile / tiles_k) * T, k0 = (tile % tiles_k) * T;
+    const int r_lo = (split * cps + min(split, long_splits)) * WC;
+    const int r_hi = min(M, r_lo + (cps + (split < long_splits ? 1 : 0)) * WC);
+    const int sr = tid / TPR, sc = (tid % TPR) * 4;     // staging: rows sr + RS i of the chunk, floats sc .. sc + 3 of the tile
     const bool vec_n = (Nout & 3) == 0;
     const bool with_bias = bpart != nullptr && k0 == 0;
     int acol = 0;                                       // PatchWgradRows: where the thread's four columns lie inside a patch
     if constexpr (R::kPatch) acol = k0 + sc < K ? pol.rows.col(k0 + sc) : 0;
 
-    float4 gd[4], ga[4];
+    float4 gd[NI], ga[NI];
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
     auto gload = [&](int r0) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = r0 + sr + 8 * i;
+        for (int i = 0; i < NI; ++i) {
+            const int row = r0 + sr + RS * i;
             if (row < r_hi) {
                 size_t drow = (size_t)row;
                 if constexpr (R::kPatch) drow = pol.dy_row(row);
@@ -85,18 +103,18 @@ __global__ __launch_bounds__(256) void vit_wgrad_kernel(const float *__restrict_
     };
     auto sstore = [&]() {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<float4 *>(&ld[(sr + 8 * i) * WLD + sc]) = gd[i];
-            *reinterpret_cast<float4 *>(&la[(sr + 8 * i) * WLD + sc]) = ga[i];
+        for (int i = 0; i < NI; ++i) {
+            *reinterpret_cast<float4 *>(&ld[(sr + RS * i) * WLD + sc]) = gd[i];
+            *reinterpret_cast<float4 *>(&la[(sr + RS * i) * WLD + sc]) = ga[i];
             bsum.x += gd[i].x, bsum.y += gd[i].y, bsum.z += gd[i].z, bsum.w += gd[i].w;
         }
     };
 
-    f32x16 acc[2][2];
+    f32x16 acc[NB][NB];
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < NB; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n)
+        for (int n = 0; n < NB; ++n)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
 
@@ -110,12 +128,14 @@ __global__ __launch_bounds__(256) void vit_wgrad_kernel(const float *__restrict_
         if (more) gload(r0 + WC);
 #pragma unroll
         for (int s = 0; s < WC / 2; ++s) {
-            const float *dp = &ld[(2 * s + half) * WLD + wm * 64 + l31], *ap = &la[(2 * s + half) * WLD + wn * 64 + l31];
-            const float d0 = dp[0], d1 = dp[32], a0 = ap[0], a1 = ap[32];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d0, a0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d0, a1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d1, a0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(d1, a1, acc[1][1], 0, 0, 0);
+            const float *dp = &ld[(2 * s + half) * WLD + wm * (T / 2) + l31], *ap = &la[(2 * s + half) * WLD + wn * (T / 2) + l31];
+            float d[NB], a[NB];
+#pragma unroll
+            for (int m = 0; m < NB; ++m) d[m] = dp[32 * m], a[m] = ap[32 * m];
+#pragma unroll
+            for (int m = 0; m < NB; ++m)
+#pragma unroll
+                for (int n = 0; n < NB; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[m], a[n], acc[m][n], 0, 0, 0);
         }
         __syncthreads();
         if (more) {
@@ -127,24 +147,24 @@ __global__ __launch_bounds__(256) void vit_wgrad_kernel(const float *__restrict_
     // lane holds column k = l31 of each 32 x 32 block, rows (= output features n) 8 (i / 4) + 4 half + i % 4
     float *out = part + (size_t)split * Nout * K;
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int col = k0 + wn * 64 + n * 32 + l31;
+    for (int n = 0; n < NB; ++n) {
+        const int col = k0 + wn * (T / 2) + n * 32 + l31;
         if (col >= K) continue;
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
+        for (int m = 0; m < NB; ++m)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int row = n0 + wm * 64 + m * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
+                const int row = n0 + wm * (T / 2) + m * 32 + 8 * (i >> 2) + 4 * half + (i & 3);
                 if (row < Nout) out[(size_t)row * K + col] = acc[m][n][i];
             }
     }
-    if (with_bias) {   // (uniform over the workgroup) the 8 staging rows of a column, added in the order 0 .. 7
+    if (with_bias) {   // (uniform over the workgroup) the RS staging rows of a column, added in the order 0 .. RS - 1
         *reinterpret_cast<float4 *>(&ld[sr * WLD + sc]) = bsum;
         __syncthreads();
-        if (tid < WT && n0 + tid < Nout) {
+        if (tid < T && n0 + tid < Nout) {
             float t = ld[tid];
 #pragma unroll
-            for (int r = 1; r < 8; ++r) t += ld[r * WLD + tid];
+            for (int r = 1; r < RS; ++r) t += ld[r * WLD + tid];
             bpart[(size_t)split * Nout + n0 + tid] = t;
         }
     }

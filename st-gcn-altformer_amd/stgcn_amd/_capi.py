@@ -45,6 +45,7 @@ VIT_TRAIN_ATTN_BF16 = 0x800000  # the block's two training entry points: the res
 VIT_ATTN_SPLIT = 0x2000000  # stgcn_vit_block_forward: the fp32 resident attention split over key tiles where the launch has few pairs
 VIT_POOL_MAX = 0x4000000  # stgcn_vit_pool / stgcn_vit_pool_classify: the maximum over the tokens instead of the mean
 VIT_POOL_CLS = 0x8000000  # stgcn_vit_pool / stgcn_vit_pool_classify: token 0 of every sequence (the ViT's class token)
+VIT_WGRAD_SMALL = 0x10000000  # stgcn_vit_block_backward_drop / stgcn_vit_linear_backward: every weight gradient picks its form (128 / 64) and cut
 MATH_F16MX = MATH_BF16X3 | STEM_F16MX  # as a "math mode" of the modules: bf16x3 everywhere, KF7 in the fused stem
 
 STATUS = {0: "STGCN_OK", -1: "STGCN_ERR_ARG", -2: "STGCN_ERR_UNSUPPORTED",
@@ -198,6 +199,11 @@ PROTOTYPES = {
     "stgcn_vit_pool_classify_backward_supported": (c_int, [c_int] * 4 + [c_uint]),
     "stgcn_vit_pool_classify_backward_ws_bytes": (c_size_t, [c_int] * 4 + [c_uint]),
     "stgcn_vit_pool_classify_backward": (c_int, [_P] * 3 + [c_float] + [_P] * 7 + [c_int] * 4 + [_P, c_size_t, c_uint, _P]),
+    "stgcn_vit_wgrad_tile": (c_int, [c_int] * 3 + [c_uint]),
+    "stgcn_vit_wgrad_splits": (c_int, [c_int] * 3 + [c_uint]),
+    "stgcn_vit_wgrad_writes_direct": (c_int, [c_int] * 3 + [c_uint]),
+    "stgcn_vit_block_train_small_ws_bytes": (c_size_t, [c_int] * 5 + [c_uint]),
+    "stgcn_vit_linear_backward_small_ws_bytes": (c_size_t, [c_int] * 3 + [c_uint]),
 }
 
 _lib = None

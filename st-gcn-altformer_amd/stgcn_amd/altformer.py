@@ -36,12 +36,22 @@ Two paths, one result:
   ``min_tokens`` the threshold is ``LOW_LATENCY_MIN_TOKENS`` (see there for what has been measured).  Every form
   computes an output element with the same instructions in the same order, so the result is bit-identical to the
   128 x 128 form's.  The forward launches on one stream and takes its workspace from torch's allocator, so it captures under
-  ``torch.cuda.graph`` as one sequential graph.  Not covered: training (the training kernels always run 128 x 128 tiles and
-  ``hip_train_min_tokens`` is never touched).  The attention kernel at one clip has one workgroup per head;
+  ``torch.cuda.graph`` as one sequential graph.  Training is not touched by these two keywords (see the next entry).  The
+  attention kernel at one clip has one workgroup per head;
   ``set_low_latency(model, min_tokens=0, split_attention=True)`` (opt-in) adds ``VIT_ATTN_SPLIT`` to the inference call: the
   fp32 attention of a call with fewer than 192 (sequence, head) pairs and more than 32 tokens per sequence then runs split
   over key tiles, one workgroup per (pair, 32 queries) - the same result up to the summation order, measured 1.07 - 1.08 x
   on the one-clip ``ST`` model and level on ``TS``.
+* HIP, small training calls (``set_low_latency_training(model)``, opt-in): each ``Block`` gets ``small_tiles_train``.  Its
+  training call then goes to the ``_drop`` pair of entry points with no masks (``stgcn_vit_block_forward_train_drop`` /
+  ``stgcn_vit_block_backward_drop``) under ``VIT_TILE_AUTO | VIT_WGRAD_SMALL``: the forward and dgrad linears pick their tile
+  form by call size (bit-identical to the 128 x 128 form), and every weight gradient picks between the 128 x 128 and the
+  64 x 64 form of its kernel and cuts the tokens to suit (``functional.vit_wgrad_plan`` tells; a product with one split
+  stores ``dW`` itself and skips its two summing launches).  ``y``, ``dx`` and the LayerNorm gradients are the bits of the
+  switch-off run, the eight weight and bias gradients differ from it in summation order only.  The training threshold
+  becomes ``LOW_LATENCY_TRAIN_MIN_TOKENS`` (see there for the measurement), or ``train_min_tokens``.  Stochastic depth,
+  ``nn.DataParallel`` replicas, ``set_train_math``, ``set_train_attention_math`` and ``set_long_training`` compose with it
+  as they do with the default path.
 * torch ops: everything else - CPU tensors, shapes the kernels do not cover, active dropout, calls under the thresholds,
   ``force_torch``.  This is the reference's arithmetic op for op, so its training scripts keep working unchanged.
 
@@ -81,7 +91,7 @@ from torch.autograd.function import once_differentiable
 
 from . import functional as F
 from ._capi import (MATH_BF16X3, MATH_F32, VIT_ATTN_SPLIT, VIT_BF16, VIT_QKV_F32, VIT_TILE_AUTO, VIT_TILE_MASK,
-                    VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16)
+                    VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16, VIT_WGRAD_SMALL)
 from .modules import Unit2D, enable_stem_fusion, import_class, unit_agcn
 
 HEAD_MATH = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "mixed": MATH_BF16X3 | VIT_QKV_F32, "bf16": VIT_BF16}
@@ -125,13 +135,26 @@ LOW_LATENCY_MIN_TOKENS = HIP_MIN_TOKENS   # the token count from which the auto-
 #                                          128 x 128 measurement put it; set_low_latency(model, min_tokens=0) runs one clip on HIP
 
 
+LOW_LATENCY_TRAIN_MIN_TOKENS = 6600   # forward + backward of a block with small_tiles_train (tools/time_altformer_train.py --small at
+#                                       batch 2, 8, 16, 32; profiles/altformer_train_small_times.json): the smallest measured stage
+#                                       from which every measured stage beats the torch path by more than the spread (1.33-1.73 x).
+#                                       Below it the picture is mixed by the width, not the size: every stage of up to 2,880
+#                                       tokens is faster (1.14-2.19 x, 44 to 2,880 tokens), the ST temporal stage at batch 32
+#                                       (4,800 and 5,760 tokens at D = 512) is not (0.93-1.05 x), so a threshold cannot admit
+#                                       the former without the latter; train_min_tokens=0 does, for batches of 16 and fewer
+
+
 def set_low_latency(module: nn.Module, enabled: bool = True, min_tokens=None, split_attention: bool = False) -> None:
     """Small inference calls (down to one clip) of every ``Block`` below on the HIP kernels: ``small_tiles`` (the linears'
     tile form picked per call size, same result bit for bit) and the inference threshold ``min_tokens``
     (``LOW_LATENCY_MIN_TOKENS`` when None).  ``split_attention`` (opt-in) sets ``Block.split_attention``: the fp32 attention
     of a call with few (sequence, head) pairs runs split over key tiles (``VIT_ATTN_SPLIT``; the same result up to the
     summation order).  ``enabled=False`` restores ``small_tiles = False``, ``split_attention = False`` and ``HIP_MIN_TOKENS``
-    (for the ST-ViT head's modules: their own defaults, ``HipSwitches.DEFAULT_*``).  The training threshold is not touched."""
+    (for the ST-ViT head's modules: their own defaults, ``HipSwitches.DEFAULT_*``).  The training threshold is not touched;
+    the training twin of this switch is ``set_low_latency_training``, and ``enabled=False`` here takes that one back too
+    (``set_low_latency_training(module, False)``: nothing moves where it was never set)."""
+    if not enabled:
+        set_low_latency_training(module, False)
     for sub in module.modules():
         if isinstance(sub, HipSwitches):
             sub.small_tiles = bool(enabled) or sub.DEFAULT_SMALL_TILES
@@ -140,6 +163,24 @@ def set_low_latency(module: nn.Module, enabled: bool = True, min_tokens=None, sp
                 sub.hip_min_tokens = sub.DEFAULT_HIP_MIN_TOKENS
             else:
                 sub.hip_min_tokens = min(LOW_LATENCY_MIN_TOKENS, sub.DEFAULT_HIP_MIN_TOKENS) if min_tokens is None else int(min_tokens)
+
+
+def set_low_latency_training(module: nn.Module, enabled: bool = True, train_min_tokens=None) -> None:
+    """Small TRAINING calls of every ``Block`` (and ST-ViT ``Layer``) below on the HIP kernels, opt-in: ``small_tiles_train``
+    (the training word gets ``VIT_TILE_AUTO | VIT_WGRAD_SMALL``: the linears' tile form and every weight gradient's form and
+    token cut picked per call size, the module docstring) and the training threshold ``train_min_tokens``
+    (``LOW_LATENCY_TRAIN_MIN_TOKENS`` when None, never above the module's own default; 0: every call).  ``enabled=False``
+    restores ``small_tiles_train = False`` and ``DEFAULT_HIP_TRAIN_MIN_TOKENS`` on the modules where the switch was on; a
+    threshold set by hand on a module whose switch is off stays.  Inference (``set_low_latency``) is not touched."""
+    for sub in module.modules():
+        if isinstance(sub, HipSwitches):
+            if enabled:
+                sub.small_tiles_train = True
+                sub.hip_train_min_tokens = (min(LOW_LATENCY_TRAIN_MIN_TOKENS, sub.DEFAULT_HIP_TRAIN_MIN_TOKENS)
+                                            if train_min_tokens is None else int(train_min_tokens))
+            elif sub.small_tiles_train:
+                sub.small_tiles_train = False
+                sub.hip_train_min_tokens = sub.DEFAULT_HIP_TRAIN_MIN_TOKENS
 
 
 def set_whole_head(module: nn.Module, enabled: bool = True) -> None:
@@ -244,6 +285,7 @@ class HipSwitches:
         self.hip_train_max_len = HIP_TRAIN_MAX_LEN         # set_long_training
         self.small_tiles = self.DEFAULT_SMALL_TILES   # set_low_latency: the inference linears pick their tile form by call size
         self.split_attention = False           # set_low_latency(split_attention=True): VIT_ATTN_SPLIT on the inference word
+        self.small_tiles_train = False         # set_low_latency_training: VIT_TILE_AUTO | VIT_WGRAD_SMALL on the training word
 
     def _inference_flags(self, L: int, D: int, heads: int, hidden: int) -> int:
         """The flag word of an inference call of a block of this shape: ``math_mode``, else ``_default_head_math()``;
@@ -261,12 +303,15 @@ class HipSwitches:
 
     def _train_flags(self, tiles: bool = False) -> int:
         """The flag word of a training call (``Block._hip_flags`` describes the resolution).  ``tiles``: the caller's entry
-        points take a tile field (the ST-ViT ``Layer``'s ``_drop`` pair; a ``Block``'s refuse one), so ``small_tiles`` adds
-        ``VIT_TILE_AUTO`` to the word."""
+        points take a tile field (the ST-ViT ``Layer``'s ``_drop`` pair always; a ``Block``'s older pair refuses one, so a
+        ``Block`` asks for this only with ``small_tiles_train``, when it calls the ``_drop`` pair too), so ``small_tiles`` adds
+        ``VIT_TILE_AUTO`` to the word and ``small_tiles_train`` adds ``VIT_TILE_AUTO | VIT_WGRAD_SMALL``."""
         attn = self.train_attention_mode if self.train_attention_mode is not None else _default_train_attention()
         bit = VIT_TRAIN_ATTN_BF16 if attn == "bf16" else 0
         if tiles and self.small_tiles:
             bit |= VIT_TILE_AUTO
+        if tiles and getattr(self, "small_tiles_train", False):
+            bit |= VIT_TILE_AUTO | VIT_WGRAD_SMALL
         if self.train_math_mode is not None:
             return self.train_math_mode & ~(VIT_TILE_MASK | VIT_BF16 | VIT_ATTN_SPLIT) | bit
         if self.math_mode is None or self.math_mode & VIT_BF16:
@@ -448,9 +493,11 @@ class Block(nn.Module, HipSwitches):
         inference modes that never reach a training entry point (a block set to the latter trains in its path's default);
         ``train_attention_mode`` (``set_train_attention_math``), else env ``STGCN_VIT_TRAIN_ATTENTION``, adds
         ``VIT_TRAIN_ATTN_BF16`` on top of any of them when it says ``'bf16'``, and nothing otherwise.
-        Inference: ``HipSwitches._inference_flags`` (the training word never carries a tile form or ``VIT_ATTN_SPLIT``)."""
+        ``small_tiles_train`` (``set_low_latency_training``) adds ``VIT_TILE_AUTO | VIT_WGRAD_SMALL``: the call then goes
+        to the ``_drop`` pair, which takes both; without it the word carries neither, whatever ``small_tiles`` says.
+        Inference: ``HipSwitches._inference_flags`` (the training word never carries ``VIT_ATTN_SPLIT``)."""
         if train:
-            return self._train_flags()
+            return self._train_flags(tiles=self.small_tiles_train)
         return self._inference_flags(x.shape[1], x.shape[2], self.attn.num_heads, self.mlp.fc1.out_features)
 
     def forward(self, x):
@@ -463,9 +510,10 @@ class Block(nn.Module, HipSwitches):
                                            a.scale, self._hip_flags(x, train=False))
         if self.trains_on_hip(x):
             s1, s2 = self.draw_drop_path(x)
+            # small_tiles_train: three absent dropout masks behind the twelve parameters send the call to the _drop pair
             return _BlockTrain.apply(x, None if s1 is None else s1.reshape(-1), None if s2 is None else s2.reshape(-1),
                                      self.attn.num_heads, self.norm1.eps, self.attn.scale, self._hip_flags(x, train=True),
-                                     *self._weights())
+                                     *self._weights(), *((None, None, None) if self.small_tiles_train else ()))
         x = x + self.drop_path(self.attn(self.norm1(x)))
         return x + self.drop_path(self.mlp(self.norm2(x)))
 

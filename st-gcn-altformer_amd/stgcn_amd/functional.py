@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _capi
-from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_ATTN_SPLIT, VIT_BF16, VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16  # noqa: F401 (re-export)
+from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_ATTN_SPLIT, VIT_BF16, VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16, VIT_WGRAD_SMALL  # noqa: F401 (re-export)
 
 BN_EPS = 1e-5
 
@@ -575,10 +575,20 @@ def _vit_flags(math: int) -> int:
     return math & (_capi.MATH_MASK | _capi.VIT_QKV_F32 | _capi.VIT_TILE_MASK | _capi.VIT_BF16 | _capi.VIT_ATTN_SPLIT)
 
 
-def _vit_train_flags(math: int) -> int:
+def _vit_train_flags(math: int, small: bool = False) -> int:
     """What the training entry points read of ``math``: the inference bits (which they refuse by name), VIT_TRAIN_BF16 and
-    VIT_TRAIN_ATTN_BF16."""
-    return _vit_flags(math) | (math & (_capi.VIT_TRAIN_BF16 | _capi.VIT_TRAIN_ATTN_BF16))
+    VIT_TRAIN_ATTN_BF16.  ``small``: the caller is the ``_drop`` pair (or ``vit_linear_backward``, which masks for itself), the
+    entry points that know VIT_WGRAD_SMALL; to the older pair the bit never travels."""
+    return _vit_flags(math) | (math & (_capi.VIT_TRAIN_BF16 | _capi.VIT_TRAIN_ATTN_BF16 | (_capi.VIT_WGRAD_SMALL if small else 0)))
+
+
+def vit_wgrad_plan(M, K, Nout, math=0):
+    """``(tile, splits, writes_direct)`` of the weight gradient of a linear over ``M`` tokens, ``dW`` (Nout, K): the form
+    (128 or 64) and the token splits the library picks, and whether the kernel stores ``dW`` itself.  Only VIT_WGRAD_SMALL
+    of ``math`` is read; without it the answer is the 128 form on the uniform cut.  A host function: no GPU needed."""
+    lib, fl = _capi.lib(), math & _capi.VIT_WGRAD_SMALL
+    return (lib.stgcn_vit_wgrad_tile(M, K, Nout, fl), lib.stgcn_vit_wgrad_splits(M, K, Nout, fl),
+            bool(lib.stgcn_vit_wgrad_writes_direct(M, K, Nout, fl)))
 
 
 def _bytes(dev, nbytes):
@@ -1081,7 +1091,8 @@ def vit_linear_backward(dy, a, weight, h_pre=None, dx_accumulate=None, need_dx=T
     """Backward of ``y = a W^T + b`` on the last axis: returns ``(dx, dW, db)`` (None where not asked for).
     ``dx = dy W``, multiplied by ``GELU'(h_pre)`` when ``h_pre`` (shape of ``a``) is given - the dgrad of the linear behind
     a GELU whose input was ``h_pre`` - and added onto ``dx_accumulate`` (in place, returned) when that is given.
-    ``math | VIT_TRAIN_BF16``: both products on operands rounded to nearest-even bf16 (``db`` sums the unrounded ``dy``)."""
+    ``math | VIT_TRAIN_BF16``: both products on operands rounded to nearest-even bf16 (``db`` sums the unrounded ``dy``).
+    ``math | VIT_WGRAD_SMALL``: the weight gradient picks its form and cut by the call's size (``vit_wgrad_plan``)."""
     dev = dy.device
     Nout, K = weight.shape
     M = dy.numel() // Nout
@@ -1090,9 +1101,12 @@ def vit_linear_backward(dy, a, weight, h_pre=None, dx_accumulate=None, need_dx=T
         dx = dx_accumulate if dx_accumulate is not None else torch.empty(dy.shape[:-1] + (K,), device=dev, dtype=torch.float32)
     dW = torch.empty_like(weight) if need_dw else None
     db = torch.empty(Nout, device=dev, dtype=torch.float32) if need_dw and need_db else None
-    nbytes = _capi.lib().stgcn_vit_linear_backward_ws_bytes(M, K, Nout)
+    if math & _capi.VIT_WGRAD_SMALL:     # its own cut of the tokens, its own size; without the bit the query every call has used
+        nbytes = _capi.lib().stgcn_vit_linear_backward_small_ws_bytes(M, K, Nout, _capi.VIT_WGRAD_SMALL)
+    else:
+        nbytes = _capi.lib().stgcn_vit_linear_backward_ws_bytes(M, K, Nout)
     ws = _bytes(dev, nbytes)
-    fl = (math & (_capi.MATH_MASK | _capi.VIT_TILE_MASK | _capi.VIT_TRAIN_BF16)) \
+    fl = (math & (_capi.MATH_MASK | _capi.VIT_TILE_MASK | _capi.VIT_TRAIN_BF16 | _capi.VIT_WGRAD_SMALL)) \
         | (_capi.VIT_DGELU if h_pre is not None and need_dx else 0) | (_capi.VIT_ACCUMULATE if dx_accumulate is not None else 0)
     with torch.cuda.device(dev):
         _capi.call("stgcn_vit_linear_backward", _dev_ptr(dy, "dy", dev), _dev_ptr(a if need_dw else None, "a", dev),
@@ -1248,7 +1262,7 @@ def vit_block_forward_train(x, params, heads, eps, scale, math=MATH_F32, scale1=
             _capi.call("stgcn_vit_block_forward_train_drop", _dev_ptr(x, "x", dev), weights, _dev_ptr(scale1, "scale1", dev),
                        _dev_ptr(scale2, "scale2", dev), ctypes.byref(masks), c_float(eps), c_float(scale),
                        c_void_p(saved.data_ptr()), c_size_t(nbytes), _dev_ptr(y, "y"), c_int(B), c_int(L), c_int(D), c_int(heads),
-                       c_int(hidden), c_uint(_vit_train_flags(math)), _stream(dev))
+                       c_int(hidden), c_uint(_vit_train_flags(math, small=True)), _stream(dev))
         return y, saved
     with torch.cuda.device(dev):
         _capi.call("stgcn_vit_block_forward_train", _dev_ptr(x, "x", dev),
@@ -1269,7 +1283,10 @@ def vit_block_backward(x, params, saved, dy, heads, eps, scale, math=MATH_F32, s
     if saved.numel() * saved.element_size() < sbytes:
         raise ValueError("saved does not come from vit_block_forward_train of these shapes")
     if drop is not None:
-        nbytes = _capi.lib().stgcn_vit_block_train_drop_ws_bytes(B, L, D, heads, hidden)
+        if math & _capi.VIT_WGRAD_SMALL:
+            nbytes = _capi.lib().stgcn_vit_block_train_small_ws_bytes(B, L, D, heads, hidden, _capi.VIT_WGRAD_SMALL)
+        else:
+            nbytes = _capi.lib().stgcn_vit_block_train_drop_ws_bytes(B, L, D, heads, hidden)
     ws = _bytes(dev, nbytes)
     grads = {"x": torch.empty_like(x)}
     for n, p in zip(VIT_BLOCK_PARAMS, params):
@@ -1284,7 +1301,7 @@ def vit_block_backward(x, params, saved, dy, heads, eps, scale, math=MATH_F32, s
                        _dev_ptr(scale2, "scale2", dev), ctypes.byref(masks), c_void_p(saved.data_ptr()), c_size_t(sbytes),
                        _dev_ptr(dy, "dy", dev), _dev_ptr(grads["x"], "dx"), ctypes.byref(gs), c_float(eps), c_float(scale),
                        c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(B), c_int(L), c_int(D), c_int(heads), c_int(hidden),
-                       c_uint(_vit_train_flags(math)), _stream(dev))
+                       c_uint(_vit_train_flags(math, small=True)), _stream(dev))
         return grads
     w = dict(zip(VIT_BLOCK_PARAMS, params))
     with torch.cuda.device(dev):

@@ -32,6 +32,20 @@ backward of every stage per launch (fp32 kernel against bf16 kernel), and one tr
 ``attn_faster`` / ``attn_slower``: the medians differ by more than the larger of the two spreads.  ``base_vs_recorded``
 compares the baseline's stage medians with profiles/altformer_train_bf16_times.json where that file is there.
 
+    python tools/time_altformer_train.py --small [--batch 32] [--joints 22] [--out FILE]
+
+``--small`` times the small training calls (``set_low_latency_training(model, train_min_tokens=0)``: tile forms picked by
+call size, both forms of the weight-gradient kernels) against the two paths they would replace, alternating in one process:
+``torch`` (the torch-op path), ``hip`` (the HIP path with the switch off: 128 x 128 forms everywhere, what ran before there was
+a switch) and ``small`` (the switch on).  Forward + backward of one block at every stage, with the form and split count of the
+stage's four weight gradients, and one training step of the whole ST and TS models with every block on the path under test, and on the two paths a user gets
+without lifting a threshold: ``default`` (the switch off, ``HIP_TRAIN_MIN_TOKENS``: smaller stages on torch ops) and
+``small_default`` (``set_low_latency_training(model)``: the switch on from ``LOW_LATENCY_TRAIN_MIN_TOKENS``).
+``--joints 46`` runs the whole models on the LMDHG shape (180 x 46).  ``small_faster_than_torch``, ``small_faster_than_hip`` /
+``small_slower_than_hip``: the medians differ by more than the larger of the two spreads.  ``low_latency_train_min_tokens``:
+the smallest stage from which every measured stage has ``small_faster_than_torch`` (what ``LOW_LATENCY_TRAIN_MIN_TOKENS``
+follows), null if the largest stage does not have it.
+
 Prints ONE JSON line.  Per stage: ms of forward + backward (min, median, max, ``spread`` = (max - min) / min) of the torch
 path and of the HIP path in each arithmetic ('f32', 'mixed', 'bf16x3'), the speed-up of the default arithmetic, and
 ``hip_faster`` = the HIP median is below the torch median by more than the larger of the two spreads (the rule
@@ -284,6 +298,91 @@ def train_attention_bf16(args):
     return res
 
 
+def small_calls(args):
+    """The ``--small`` run (see the module docstring)."""
+    import stgcn_amd
+    from stgcn_amd import functional as F
+    from stgcn_amd.altformer import DEFAULT_TRAIN_MATH, HIP_TRAIN_MIN_TOKENS, LOW_LATENCY_TRAIN_MIN_TOKENS, Block, set_low_latency_training
+    dev = torch.device("cuda:0")
+    norm = partial(torch.nn.LayerNorm, eps=1e-6)
+    res = {"small": True, "batch": args.batch, "joints": args.joints, "repeats": args.repeats, "default_train_math": DEFAULT_TRAIN_MATH,
+           "hip_train_min_tokens": HIP_TRAIN_MIN_TOKENS, "low_latency_train_min_tokens_constant": LOW_LATENCY_TRAIN_MIN_TOKENS,
+           "device": torch.cuda.get_device_name(0), "stages": {}, "models": {}}
+    PATHS = ("torch", "hip", "small")
+
+    def switch(module, path):
+        for b in module.modules():
+            if isinstance(b, Block):
+                b.force_torch = path == "torch"
+        set_low_latency_training(module, False)
+        if path in ("small", "small_default"):
+            set_low_latency_training(module, train_min_tokens=0 if path == "small" else None)
+        else:
+            for b in module.modules():
+                if isinstance(b, Block):            # 'hip': every block on the 128 x 128 kernels, however few tokens
+                    b.hip_train_min_tokens = HIP_TRAIN_MIN_TOKENS if path == "default" else 0
+
+    def entry(ts, **more):
+        med = {k: statistics.median(v) for k, v in ts.items()}
+        return {**more, **{f"{k}_ms": summary(v) for k, v in ts.items()},
+                "small_vs_torch": round(med["torch"] / med["small"], 3), "small_vs_hip": round(med["hip"] / med["small"], 3),
+                "hip_vs_torch": round(med["torch"] / med["hip"], 3),
+                "small_faster_than_torch": faster_by_more_than_the_spread(ts["small"], ts["torch"]),
+                "small_faster_than_hip": faster_by_more_than_the_spread(ts["small"], ts["hip"]),
+                "small_slower_than_hip": faster_by_more_than_the_spread(ts["hip"], ts["small"])}
+
+    for name, (per_clip, L, D) in STAGES.items():
+        B = args.batch * per_clip
+        torch.manual_seed(0)
+        blk = Block(D, 8, mlp_ratio=2., qkv_bias=True, drop_path=0.1, norm_layer=norm).to(dev).train()
+        x = torch.randn(B, L, D, device=dev, requires_grad=True)
+        dy = torch.randn(B, L, D, device=dev)
+
+        def run(path):
+            switch(blk, path)
+            assert blk.trains_on_hip(x) == (path != "torch") and blk.small_tiles_train == (path == "small")
+            x.grad = None
+            for p in blk.parameters():
+                p.grad = None
+            blk(x).backward(dy)
+        ts = alternate({p: partial(run, p) for p in PATHS}, args.repeats, args.warmup)
+        M = min(B * L, (32768 // L) * L)             # the rows of one slab of whole sequences
+        plans = {lin: F.vit_wgrad_plan(M, K, Nout, F.VIT_WGRAD_SMALL)
+                 for lin, (K, Nout) in {"qkv": (D, 3 * D), "proj": (D, D), "fc1": (D, 2 * D), "fc2": (2 * D, D)}.items()}
+        res["stages"][name] = entry(ts, B=B, L=L, D=D, tokens=B * L, wgrad_tile_splits_direct=plans)
+        del blk, x, dy
+        torch.cuda.empty_cache()
+    order = sorted(res["stages"].values(), key=lambda e: e["tokens"])
+    cut = None
+    for e in reversed(order):
+        if not e["small_faster_than_torch"]:
+            break
+        cut = e["tokens"]
+    res["low_latency_train_min_tokens"] = cut
+    graph = {22: "graph.SHRE", 46: "graph.LMDHG"}[args.joints]
+    for style in () if args.stages_only else ("ST", "TS"):
+        torch.manual_seed(1)
+        model = stgcn_amd.ST_GCN_AltFormer(channel=3, num_class=14, num_frame=180, num_joints=args.joints, style=style,
+                                           graph=graph, graph_args={"labeling_mode": "spatial"}).to(dev).train()
+        clips = torch.randn(args.batch, 180, args.joints, 3, device=dev)
+        labels = torch.arange(args.batch, device=dev) % 14
+        ce = torch.nn.CrossEntropyLoss()
+
+        def step(path):
+            switch(model, path)
+            model.zero_grad(set_to_none=True)
+            ce(model(clips), labels).backward()
+        ts = alternate({p: partial(step, p) for p in PATHS + ("default", "small_default")}, args.repeats, args.warmup)
+        res["models"][style] = entry(ts, clips_per_s={p: round(args.batch / (statistics.median(ts[p]) * 1e-3), 1) for p in ts},
+                                     small_default_vs_default=round(statistics.median(ts["default"]) / statistics.median(ts["small_default"]), 3),
+                                     small_default_faster_than_default=faster_by_more_than_the_spread(ts["small_default"], ts["default"]),
+                                     small_vs_default=round(statistics.median(ts["default"]) / statistics.median(ts["small"]), 3),
+                                     small_faster_than_default=faster_by_more_than_the_spread(ts["small"], ts["default"]))
+        del model, clips
+        torch.cuda.empty_cache()
+    return res
+
+
 def emit(res, out):
     line = json.dumps(res)
     if out:
@@ -303,9 +402,14 @@ def main():
                     help="time this opt-in training arithmetic against 'f32' and 'bf16x3' instead")
     ap.add_argument("--train-attention", choices=["bf16"], default=None,
                     help="time the opt-in bf16 training attention on top of 'bf16' training math, against that math alone")
+    ap.add_argument("--small", action="store_true",
+                    help="time the small training calls (set_low_latency_training) against the torch path and the 128-form HIP path")
+    ap.add_argument("--joints", type=int, choices=[22, 46], default=22, help="--small: joints of the whole models (46: LMDHG)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 5
+    if args.small:
+        return emit(small_calls(args), args.out)
     if args.train_attention is not None:
         return emit(train_attention_bf16(args), args.out)
     if args.train_math is not None:
