@@ -33,6 +33,24 @@
  *     axis (the graph conv, the stem, the temporal conv's inference and backward, the ST-TR
  *     unit, stgcn_patch_embed, the whole head), and fewer than 2^32 work-items a launch
  *     (workgroups times their threads), which bounds "any M / B / S" below: see each entry.
+ *   - Alignment.  TENSOR OPERANDS - inputs, parameters, cotangents, results, a caller's `out` -
+ *     need the alignment of their element only: 4 bytes for fp32, 2 bytes for bf16 (8 for the
+ *     int64 labels / pred of stgcn_step_stats).  A dense view at any element offset is served in
+ *     place: a batch slice x[1:], a parameter inside a flat buffer, a slice of a larger gradient.
+ *     The exceptions are the operands an entry point lists by name ("16-byte aligned" in its
+ *     comment): the ST-ViT ends (stgcn_vit_patch_embed: z, W; its backward: z, W, dx;
+ *     stgcn_vit_pool: x, out; stgcn_vit_pool_classify: x, W; its backward: x, dx), head_weight of
+ *     stgcn_altformer_head_forward, and m_proj, m_fc2, dy of stgcn_vit_block_backward_drop when a
+ *     mask is given.  BLOBS AND WORKSPACES - everything sized by a *_bytes query or made by the
+ *     library: prep, Wp, ws, the saved buffers - need 256 bytes, as the allocator gives them
+ *     (they are read by LDS-DMA and hold the targets of fp64 atomics); save_stats of the graph
+ *     conv's training pair keeps its 8.  An operand that misses its demand is refused with
+ *     STGCN_ERR_ARG before anything is launched or written, the message names it, and the next
+ *     correct call succeeds.  Checked on the host: 256 bytes for prep / ws of stgcn_stem_*, Wp / ws
+ *     of stgcn_tcn_pack / _forward_packed / _forward and ws of the agcn, tcn and st_attention
+ *     training and forward entry points; 16 bytes for the listed operands and the ws of their
+ *     entry points.  DESIGN.md section 4 ("Operand alignment") has the table of accesses behind
+ *     this.
  */
 #ifndef STGCN_HIP_H
 #define STGCN_HIP_H
@@ -47,7 +65,7 @@ extern "C" {
 
 typedef enum {
     STGCN_OK = 0,
-    STGCN_ERR_ARG = -1,          /* null pointer / non-positive dimension */
+    STGCN_ERR_ARG = -1,          /* null pointer / non-positive dimension / an operand off its alignment */
     STGCN_ERR_UNSUPPORTED = -2,  /* shape outside what the kernels cover  */
     STGCN_ERR_WORKSPACE = -3,    /* caller workspace too small            */
     STGCN_ERR_HIP = -4           /* a HIP runtime call failed             */

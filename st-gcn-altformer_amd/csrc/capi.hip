@@ -198,6 +198,7 @@ int stgcn_tcn_pack(const float *W, const float *scale, void *Wp, int Cin, int Co
                    void *stream) {
     REQUIRE_PTR(W); REQUIRE_PTR(scale); REQUIRE_PTR(Wp);
     REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(K);
+    REQUIRE_ALIGNED(Wp, kBlobAlign);
     return launch_tcn_pack(plan_tcn_pack(Cin, Cout, K, flags), W, scale, Wp, Cin, Cout, K, (hipStream_t)stream);
 }
 
@@ -206,6 +207,7 @@ int stgcn_tcn_forward_packed(const float *x, const void *Wp, const float *shift,
     REQUIRE_PTR(x); REQUIRE_PTR(Wp); REQUIRE_PTR(shift); REQUIRE_PTR(y);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(K);
     REQUIRE_POS(stride);
+    REQUIRE_ALIGNED(Wp, kBlobAlign);     // the matrix-core kernels stage it by LDS-DMA
     return launch_tcn(plan_tcn(Cin, Cout, T, V, K, stride, flags), x, Wp, shift, y, N, Cin, Cout, T, V, K, stride, flags,
                       (hipStream_t)stream);
 }
@@ -215,6 +217,7 @@ int stgcn_tcn_forward(const float *x, const float *W, const float *scale, const 
                       unsigned flags, void *stream) {
     REQUIRE_PTR(ws);
     REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(K);
+    REQUIRE_ALIGNED(ws, kBlobAlign);
     const size_t need = plan_tcn_pack(Cin, Cout, K, flags).bytes;
     if (ws_bytes < need)
         return fail(STGCN_ERR_WORKSPACE, "tcn_forward: workspace %zu B < %zu B", ws_bytes, need);
@@ -236,6 +239,7 @@ int stgcn_stem_prepare(const float *Wd, const float *bd, const float *Wdown, con
     REQUIRE_PTR(bn_shift); REQUIRE_PTR(down_scale); REQUIRE_PTR(down_shift); REQUIRE_PTR(Wt);
     REQUIRE_PTR(t_scale); REQUIRE_PTR(prep);
     REQUIRE_POS(Cin); REQUIRE_POS(C); REQUIRE_POS(K); REQUIRE_POS(subsets);
+    REQUIRE_ALIGNED(prep, kBlobAlign);
     return launch_stem_prepare(Wd, bd, Wdown, bdown, bn_scale, bn_shift, down_scale, down_shift, Wt, t_scale,
                                prep, Cin, C, K, subsets, flags, (hipStream_t)stream);
 }
@@ -285,6 +289,7 @@ int stgcn_stem_attention(const float *x, const float *A_eff, const float *Wa, co
     REQUIRE_PTR(ws);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(C); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(inter_c);
     REQUIRE_POS(subsets); REQUIRE_POS(K);
+    REQUIRE_ALIGNED(ws, kBlobAlign);     // the fused kernels read its features / fragments by LDS-DMA
     const StemPlan pl = plan_stem(N, Cin, C, T, V, K, subsets, flags);
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "stem: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);
     char *w = (char *)ws;
@@ -304,6 +309,7 @@ int stgcn_stem_tail_prepared(const float *x, const void *ws, size_t ws_bytes, co
     REQUIRE_PTR(x); REQUIRE_PTR(ws); REQUIRE_PTR(prep); REQUIRE_PTR(t_shift); REQUIRE_PTR(out);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(C); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(subsets);
     REQUIRE_POS(K);
+    REQUIRE_ALIGNED(ws, kBlobAlign); REQUIRE_ALIGNED(prep, kBlobAlign);
     const StemPlan pl = plan_stem(N, Cin, C, T, V, K, subsets, flags);
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "stem: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);
     return launch_stem(pl, x, ws, prep, t_shift, out, N, Cin, C, T, V, subsets, K, flags, (hipStream_t)stream);
@@ -313,6 +319,8 @@ int stgcn_stem_forward_prepared(const float *x, const float *A_eff, const float 
                                 const float *Wb, const float *bb, const void *prep, const float *t_shift, void *ws,
                                 size_t ws_bytes, void *out, int N, int Cin, int C, int T, int V, int inter_c,
                                 int subsets, int K, unsigned flags, void *stream) {
+    REQUIRE_PTR(prep); REQUIRE_PTR(t_shift); REQUIRE_PTR(out);      // (what the tail would refuse, before the attention writes)
+    REQUIRE_ALIGNED(prep, kBlobAlign);
     int rc = stgcn_stem_attention(x, A_eff, Wa, ba, Wb, bb, ws, ws_bytes, N, Cin, C, T, V, inter_c, subsets, K, flags,
                                   stream);
     if (rc != STGCN_OK) return rc;
@@ -336,6 +344,8 @@ int stgcn_agcn_forward_train(const float *x, const float *A_eff, const float *Wa
                              int N, int Cin, int Cout, int T, int V, int inter_c, int subsets, unsigned flags, void *stream) {
     REQUIRE_PTR(Wd); REQUIRE_PTR(bd); REQUIRE_PTR(bn_weight); REQUIRE_PTR(bn_bias); REQUIRE_PTR(bn_running_mean);
     REQUIRE_PTR(bn_running_var); REQUIRE_PTR(ws); REQUIRE_PTR(y); REQUIRE_POS(Cout);
+    REQUIRE_ALIGNED(ws, kBlobAlign);     // fp64 atomic sums
+    REQUIRE_ALIGNED(save_stats, 8);      // the 63 feature moments are doubles
     const bool has_down = Wdown != nullptr;
     if (has_down && (!bdown || !dbn_weight || !dbn_bias || !dbn_running_mean || !dbn_running_var))
         return fail(STGCN_ERR_ARG, "agcn_forward_train: down branch given without its bias / BatchNorm tensors");
@@ -378,6 +388,7 @@ int stgcn_agcn_backward_train(const float *x, const float *A_eff, const float *W
     REQUIRE_PTR(dWb); REQUIRE_PTR(dbb); REQUIRE_PTR(dWd); REQUIRE_PTR(dbd);
     REQUIRE_PTR(dgamma); REQUIRE_PTR(dbeta); REQUIRE_PTR(dPA); REQUIRE_PTR(ws);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(inter_c); REQUIRE_POS(subsets);
+    REQUIRE_ALIGNED(ws, kBlobAlign); REQUIRE_ALIGNED(save_stats, 8);
     const bool has_down = Wdown != nullptr;
     if (has_down) {
         REQUIRE_PTR(bdown); REQUIRE_PTR(dbn_weight); REQUIRE_PTR(dbn_bias); REQUIRE_PTR(dWdown); REQUIRE_PTR(dbdown);
@@ -421,6 +432,7 @@ int stgcn_tcn_forward_train(const float *x, const float *W, const float *conv_bi
     REQUIRE_PTR(x); REQUIRE_PTR(W); REQUIRE_PTR(bn_weight); REQUIRE_PTR(bn_bias); REQUIRE_PTR(bn_running_mean);
     REQUIRE_PTR(bn_running_var); REQUIRE_PTR(ws); REQUIRE_PTR(y);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(K); REQUIRE_POS(stride);
+    REQUIRE_ALIGNED(ws, kBlobAlign);     // packed weights (LDS-DMA) and fp64 atomic sums
     const TcnTrainPlan pl = plan_tcn_train(N, Cin, Cout, T, V, K, stride, flags);
     if (pl.ws_bytes == 0) return fail(STGCN_ERR_ARG, "tcn_forward_train: T=%d K=%d stride=%d gives no output frame", T, K, stride);
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "tcn_forward_train: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);
@@ -441,6 +453,7 @@ int stgcn_tcn_backward_train(const float *x, const float *W, const float *z, con
     REQUIRE_PTR(x); REQUIRE_PTR(W); REQUIRE_PTR(z); REQUIRE_PTR(bn_weight); REQUIRE_PTR(bn_bias); REQUIRE_PTR(save_mean);
     REQUIRE_PTR(save_invstd); REQUIRE_PTR(dy); REQUIRE_PTR(dW); REQUIRE_PTR(dgamma); REQUIRE_PTR(dbeta); REQUIRE_PTR(ws);
     REQUIRE_POS(N); REQUIRE_POS(Cin); REQUIRE_POS(Cout); REQUIRE_POS(T); REQUIRE_POS(V); REQUIRE_POS(K); REQUIRE_POS(stride);
+    REQUIRE_ALIGNED(ws, kBlobAlign);
     const TcnBackwardPlan pl = plan_tcn_backward(N, Cin, Cout, T, V, K, stride, flags);
     if (pl.ws_bytes == 0) return fail(STGCN_ERR_ARG, "tcn_backward: T=%d K=%d stride=%d gives no output frame", T, K, stride);
     if (ws_bytes < pl.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "tcn_backward: workspace %zu B < %zu B", ws_bytes, pl.ws_bytes);

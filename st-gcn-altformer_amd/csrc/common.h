@@ -47,6 +47,17 @@ int fail(stgcn_status st, const char *fmt, ...);
         if ((v) <= 0) return stgcn::fail(STGCN_ERR_ARG, "%s: %s = %d must be positive", __func__, #v, (int)(v)); \
     } while (0)
 
+// The alignment contract (include/stgcn_hip.h, "Alignment"): a blob or workspace that is an LDS-DMA source or the target of an
+// fp64 atomic is refused off 256 bytes, an operand an entry point lists by name off its listed demand; NULL (an optional
+// operand) passes.  Before anything is launched, and the message names the operand.
+static inline bool aligned_to(const void *p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+constexpr int kBlobAlign = 256;
+#define REQUIRE_ALIGNED(p, bytes)                                                          \
+    do {                                                                                   \
+        if (!stgcn::aligned_to((p), (bytes)))                                              \
+            return stgcn::fail(STGCN_ERR_ARG, "%s: %s must be %d-byte aligned", __func__, #p, (int)(bytes)); \
+    } while (0)
+
 // phases switched off by a diagnostic build (see tcn_conv.hip); always 0 in the shipped library
 // kernel option bits that travel in the high half of the kernels' `abl` argument (the low half is the ablation mask)
 constexpr int OPT_OUT_NTVC = 1 << 16;  // store the output as (N,T,V,C) instead of (N,C,T,V)

@@ -607,6 +607,7 @@ int stgcn_st_attention_forward_math(const float *x, const float *dbn_scale, cons
                                     int dk, int T, int V, int heads, unsigned flags, void *stream) {
     REQUIRE_PTR(x); REQUIRE_PTR(dbn_scale); REQUIRE_PTR(dbn_shift); REQUIRE_PTR(Wqkv); REQUIRE_PTR(bqkv);
     REQUIRE_PTR(Wout); REQUIRE_PTR(bout); REQUIRE_PTR(bn_scale); REQUIRE_PTR(bn_shift); REQUIRE_PTR(ws); REQUIRE_PTR(y);
+    REQUIRE_ALIGNED(ws, kBlobAlign);
     if (int rc = check_shape("st_attention_forward", N, Cin, Cout, dk, T, V, heads)) return rc;
     if (int rc = check_math("st_attention_forward", flags)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -642,6 +643,7 @@ int stgcn_st_attention_forward_train(const float *x, const float *dbn_weight, co
     REQUIRE_PTR(bn_weight); REQUIRE_PTR(bn_bias); REQUIRE_PTR(bn_running_mean); REQUIRE_PTR(bn_running_var);
     REQUIRE_PTR(ws); REQUIRE_PTR(y); REQUIRE_PTR(save_qkv); REQUIRE_PTR(save_o); REQUIRE_PTR(save_z);
     REQUIRE_PTR(save_rowstats); REQUIRE_PTR(save_stats);
+    REQUIRE_ALIGNED(ws, kBlobAlign);     // fp64 atomic sums
     if (int rc = check_shape("st_attention_forward_train", N, Cin, Cout, dk, T, V, heads)) return rc;
     if (int rc = check_math("st_attention_forward_train", flags)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -693,6 +695,7 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
     REQUIRE_PTR(save_rowstats); REQUIRE_PTR(save_stats); REQUIRE_PTR(dy); REQUIRE_PTR(ddbn_weight); REQUIRE_PTR(ddbn_bias);
     REQUIRE_PTR(dWqkv); REQUIRE_PTR(dbqkv); REQUIRE_PTR(dWout); REQUIRE_PTR(dbout); REQUIRE_PTR(dbn_weight_grad);
     REQUIRE_PTR(dbn_bias_grad); REQUIRE_PTR(ws);
+    REQUIRE_ALIGNED(ws, kBlobAlign);
     if (int rc = check_shape("st_attention_backward", N, Cin, Cout, dk, T, V, heads)) return rc;
     if (int rc = check_math("st_attention_backward", flags)) return rc;
     hipStream_t st = (hipStream_t)stream;

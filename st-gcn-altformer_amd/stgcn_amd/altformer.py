@@ -409,7 +409,10 @@ class _BlockTrain(torch.autograd.Function):
         x, s1, s2, *rest = ctx.saved_tensors
         params, drop = rest[:twelve], (tuple(rest[twelve:]) if len(rest) > twelve else None)
         heads, eps, scale, math = ctx.cfg
-        g = F.vit_block_backward(x, params, ctx.saved_buf, dy.contiguous(), heads, eps, scale, math, s1, s2, drop=drop)
+        dy = dy.contiguous()
+        if drop is not None and (drop[0] is not None or drop[2] is not None):
+            dy = F.aligned(dy)                  # with m_proj or m_fc2 the cotangent is a listed operand (16 bytes)
+        g = F.vit_block_backward(x, params, ctx.saved_buf, dy, heads, eps, scale, math, s1, s2, drop=drop)
         ctx.saved_buf = None
         return (g["x"], None, None, None, None, None, None) + tuple(g[n] for n in F.VIT_BLOCK_PARAMS) + (None,) * len(drop or ())
 
@@ -619,6 +622,8 @@ class _Head(nn.Module):
         plan = self._whole_plan(z)
         if plan is None:
             return None
+        w, b = plan["head_linear"]
+        plan["head_linear"] = (F.aligned(w), b)     # the call's one listed operand (16 bytes): a copy where a flat buffer holds it
         with torch.no_grad():
             return F.altformer_head_forward(z, **plan)
 

@@ -3,6 +3,15 @@
 Every function takes CUDA(HIP) tensors, validates dtype/contiguity/device, passes raw device
 pointers plus ``torch.cuda.current_stream()`` to libstgcn_hip.so and returns freshly allocated
 outputs.  Nothing here computes on the host and nothing falls back to torch ops.
+
+Alignment (include/stgcn_hip.h, "Alignment"; DESIGN.md section 4 has the table).  A tensor operand - input, parameter,
+cotangent, result, a caller's ``out`` - needs the alignment of its element only (4 bytes fp32, 2 bytes bf16): a contiguous
+view at any element offset (``x[1:]``, a parameter that lives in a flat buffer) is served in place.  The exceptions are the
+operands an entry point lists by name, which need ``ALIGN_LISTED`` = 16 bytes, and blobs and workspaces (``prep``, ``Wp``,
+``ws``, the saved buffers), which need ``ALIGN_BLOB`` = 256 as the allocator gives them.  A wrapper here raises ``ValueError``
+naming the operand that misses its demand, before anything is launched; ``aligned(t)`` returns ``t`` itself or, where its
+address misses the demand, a copy that meets it - the modules and autograd functions hand every listed operand through it, so
+they never surface such a refusal.
 """
 from __future__ import annotations
 
@@ -16,9 +25,28 @@ from . import _capi
 from ._capi import MATH_BF16, MATH_BF16X3, MATH_F16MX, MATH_F32, MATH_F32_VALU, OUT_BF16, VIT_ATTN_SPLIT, VIT_BF16, VIT_TRAIN_ATTN_BF16, VIT_TRAIN_BF16, VIT_WGRAD_SMALL  # noqa: F401 (re-export)
 
 BN_EPS = 1e-5
+ALIGN_LISTED = 16     # the operands an entry point lists by name
+ALIGN_BLOB = 256      # prep, Wp, ws and the saved buffers
 
 
-def _dev_ptr(t: Optional[torch.Tensor], name: str, device=None, dtype=torch.float32) -> c_void_p:
+def aligned(t: Optional[torch.Tensor], nbytes: int = ALIGN_LISTED) -> Optional[torch.Tensor]:
+    """``t`` itself where its first byte sits on a multiple of ``nbytes`` (or ``t`` is None), else a copy from the allocator
+    with the same values and dense strides (contiguous stays contiguous, channels-last stays channels-last).  For the
+    operands an entry point lists as exceptions to element alignment; a caller that saves the operand saves what this
+    returns."""
+    if t is None or t.data_ptr() % nbytes == 0:
+        return t
+    return t.detach().clone(memory_format=torch.preserve_format)
+
+
+def _require_aligned(t: Optional[torch.Tensor], name: str, nbytes: int) -> None:
+    if t is not None and t.data_ptr() % nbytes:
+        raise ValueError(f"{name} must be {nbytes}-byte aligned (its address is {t.data_ptr() % nbytes} past a multiple of {nbytes}); "
+                         f"stgcn_amd.functional.aligned makes the copy")
+
+
+def _dev_ptr(t: Optional[torch.Tensor], name: str, device=None, dtype=torch.float32, align: int = 0) -> c_void_p:
+    """``align``: the operand is a listed exception (ALIGN_LISTED) or a blob (ALIGN_BLOB): refuse it off that boundary."""
     if t is None:
         return c_void_p(0)
     if not t.is_cuda:
@@ -29,6 +57,14 @@ def _dev_ptr(t: Optional[torch.Tensor], name: str, device=None, dtype=torch.floa
         raise TypeError(f"{name} must be {dtype} (got {t.dtype})")
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
+    if align:
+        _require_aligned(t, name, align)
+    return c_void_p(t.data_ptr())
+
+
+def _blob_ptr(t: torch.Tensor, name: str) -> c_void_p:
+    """A byte blob or workspace (any dtype): ALIGN_BLOB."""
+    _require_aligned(t, name, ALIGN_BLOB)
     return c_void_p(t.data_ptr())
 
 
@@ -139,7 +175,7 @@ def tcn_forward_packed(x, Wp, shift, Cout, K, stride=1, math=MATH_F32, out_bf16=
     y = torch.empty(*shape, device=dev, dtype=torch.bfloat16 if out_bf16 else torch.float32)
     fl = _flags(math, out_bf16) | (_capi.CONV_ALONG_V if along_v else 0)
     with torch.cuda.device(dev):
-        _capi.call("stgcn_tcn_forward_packed", _dev_ptr(x, "x", dev), c_void_p(Wp.data_ptr()),
+        _capi.call("stgcn_tcn_forward_packed", _dev_ptr(x, "x", dev), _blob_ptr(Wp, "Wp"),
                    _dev_ptr(shift, "shift", dev), c_void_p(y.data_ptr()), c_int(N), c_int(Cin), c_int(Cout),
                    c_int(T), c_int(V), c_int(K), c_int(stride), c_uint(fl), _stream(dev))
     return y
@@ -222,10 +258,11 @@ def stem_forward(x, A_eff, Wa, ba, Wb, bb, prep, t_shift, C, K, math=MATH_F32, o
         ws = torch.empty((need + 3) // 4, device=dev, dtype=torch.float32)
     ws_bytes = c_size_t(ws.numel() * ws.element_size())
     st = _stream(dev)
+    _require_aligned(prep, "prep", ALIGN_BLOB)        # (both before the first of the two calls)
     with torch.cuda.device(dev):
         _capi.call("stgcn_stem_attention", _dev_ptr(x, "x", dev), _dev_ptr(A_eff, "A_eff", dev),
                    _dev_ptr(Wa, "Wa", dev), _dev_ptr(ba, "ba", dev), _dev_ptr(Wb, "Wb", dev),
-                   _dev_ptr(bb, "bb", dev), _dev_ptr(ws, "ws", dev), ws_bytes, c_int(N), c_int(Cin), c_int(C),
+                   _dev_ptr(bb, "bb", dev), _dev_ptr(ws, "ws", dev, align=ALIGN_BLOB), ws_bytes, c_int(N), c_int(Cin), c_int(C),
                    c_int(T), c_int(V), c_int(inter_c), c_int(S), c_int(K), c_uint(fl), st)
         timer = kernel_timer
         if timer is not None:
@@ -818,7 +855,7 @@ def vit_pool(x, mode="mean") -> torch.Tensor:
     S, L, D = x.shape
     out = torch.empty((S, D), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _capi.call("stgcn_vit_pool", _dev_ptr(x, "x", dev), _dev_ptr(out, "out"), c_int(S), c_int(L), c_int(D),
+        _capi.call("stgcn_vit_pool", _dev_ptr(x, "x", dev, align=ALIGN_LISTED), _dev_ptr(out, "out"), c_int(S), c_int(L), c_int(D),
                    c_uint(fl), _stream(dev))
     return out
 
@@ -841,8 +878,9 @@ def vit_pool_classify(x, ln_weight, ln_bias, eps, weight, bias=None, mode="max",
     elif logits.shape != (N, classes):
         raise ValueError(f"logits is {tuple(logits.shape)}, expected {(N, classes)}")
     with torch.cuda.device(dev):
-        _capi.call("stgcn_vit_pool_classify", _dev_ptr(x, "x", dev), _dev_ptr(ln_weight, "ln weight", dev),
-                   _dev_ptr(ln_bias, "ln bias", dev), c_float(eps), _dev_ptr(weight, "weight", dev), _dev_ptr(bias, "bias", dev),
+        _capi.call("stgcn_vit_pool_classify", _dev_ptr(x, "x", dev, align=ALIGN_LISTED), _dev_ptr(ln_weight, "ln weight", dev),
+                   _dev_ptr(ln_bias, "ln bias", dev), c_float(eps), _dev_ptr(weight, "weight", dev, align=ALIGN_LISTED),
+                   _dev_ptr(bias, "bias", dev),
                    _dev_ptr(logits, "logits", dev), c_int(N), c_int(L), c_int(D), c_int(classes),
                    c_uint(fl), _stream(dev))
     return logits
@@ -900,7 +938,8 @@ def vit_patch_embed(z, weight, bias, cls, pos, p1, p2, math=MATH_F32) -> torch.T
     ws = _bytes(dev, nbytes)
     x = torch.empty((N, n + 1, E), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _capi.call("stgcn_vit_patch_embed", _dev_ptr(z, "z", dev), _dev_ptr(weight, "weight", dev), _dev_ptr(bias, "bias", dev),
+        _capi.call("stgcn_vit_patch_embed", _dev_ptr(z, "z", dev, align=ALIGN_LISTED),
+                   _dev_ptr(weight, "weight", dev, align=ALIGN_LISTED), _dev_ptr(bias, "bias", dev),
                    _dev_ptr(cls.reshape(-1), "cls", dev), _dev_ptr(pos, "pos", dev), _dev_ptr(x, "x"), c_int(N), c_int(C), c_int(T),
                    c_int(V), c_int(p1), c_int(p2), c_int(E), c_void_p(ws.data_ptr()), c_size_t(nbytes), c_uint(fl), _stream(dev))
     return x
@@ -954,8 +993,9 @@ def vit_patch_embed_backward(z, weight, dx, p1, p2, math=MATH_F32, need_dw=True,
         else:
             dzin = out["dz"] = torch.empty((N, C, T, V), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _capi.call("stgcn_vit_patch_embed_backward", _dev_ptr(zin, "z", dev), _dev_ptr(weight, "weight", dev),
-                   _dev_ptr(dx, "dx", dev), _dev_ptr(out["dW"], "dW"), _dev_ptr(out["dbias"], "dbias"), _dev_ptr(out["dcls"], "dcls"),
+        _capi.call("stgcn_vit_patch_embed_backward", _dev_ptr(zin, "z", dev, align=ALIGN_LISTED),
+                   _dev_ptr(weight, "weight", dev, align=ALIGN_LISTED), _dev_ptr(dx, "dx", dev, align=ALIGN_LISTED),
+                   _dev_ptr(out["dW"], "dW"), _dev_ptr(out["dbias"], "dbias"), _dev_ptr(out["dcls"], "dcls"),
                    _dev_ptr(out["dpos"], "dpos"), _dev_ptr(dzin, "dz"), c_int(N), c_int(C), c_int(T), c_int(V), c_int(p1), c_int(p2),
                    c_int(E), c_void_p(ws.data_ptr()), c_size_t(nbytes), c_uint(fl), _stream(dev))
     return out
@@ -988,7 +1028,7 @@ def vit_pool_classify_backward(x, ln_weight, ln_bias, eps, weight, dlogits, mode
     nbytes = int(_capi.lib().stgcn_vit_pool_classify_backward_ws_bytes(N, L, D, classes, fl))
     ws = _bytes(dev, nbytes)
     with torch.cuda.device(dev):
-        _capi.call("stgcn_vit_pool_classify_backward", _dev_ptr(x, "x", dev), _dev_ptr(ln_weight, "ln weight", dev),
+        _capi.call("stgcn_vit_pool_classify_backward", _dev_ptr(x, "x", dev, align=ALIGN_LISTED), _dev_ptr(ln_weight, "ln weight", dev),
                    _dev_ptr(ln_bias, "ln bias", dev), c_float(eps), _dev_ptr(weight, "weight", dev), _dev_ptr(dlogits, "dlogits", dev),
                    _dev_ptr(out["dx"], "dx"), _dev_ptr(out["dln_weight"], "dln_weight"), _dev_ptr(out["dln_bias"], "dln_bias"),
                    _dev_ptr(out["dW"], "dW"), _dev_ptr(out["dbias"], "dbias"), c_int(N), c_int(L), c_int(D), c_int(classes),
@@ -1062,7 +1102,7 @@ def altformer_head_forward(z, embed1, pos1, blocks1, embed2, pos2, blocks2, head
         _dev_ptr(embed1[0], "embed1.weight", dev), _dev_ptr(embed1[1], "embed1.bias", dev), _dev_ptr(pos1, "pos1", dev), b1,
         _dev_ptr(embed2[0], "embed2.weight", dev), _dev_ptr(embed2[1], "embed2.bias", dev), _dev_ptr(pos2, "pos2", dev), b2,
         _dev_ptr(head_norm[0], "head_norm.weight", dev), _dev_ptr(head_norm[1], "head_norm.bias", dev),
-        _dev_ptr(head_linear[0], "head.weight", dev), _dev_ptr(head_linear[1], "head.bias", dev))
+        _dev_ptr(head_linear[0], "head.weight", dev, align=ALIGN_LISTED), _dev_ptr(head_linear[1], "head.bias", dev))
     nbytes = _head_ws_bytes(shape, fl1, fl2, hf)
     ws = _bytes(dev, nbytes)
     if logits is None:
@@ -1235,7 +1275,7 @@ def _drop_struct(drop, x, hidden):
     for (field, _), m, width in zip(_capi.VitDropMasks._fields_, drop, (D, hidden, D)):
         if m is not None and (tuple(m.shape) != (B, L, width) or not m.is_contiguous()):
             raise ValueError(f"{field}: expected a contiguous ({B}, {L}, {width}) tensor, got {tuple(m.shape)}")
-        setattr(masks, field, _dev_ptr(m, field, x.device))
+        setattr(masks, field, _dev_ptr(m, field, x.device, align=0 if field == "m_act" else ALIGN_LISTED))
     return masks
 
 
@@ -1299,7 +1339,8 @@ def vit_block_backward(x, params, saved, dy, heads, eps, scale, math=MATH_F32, s
         with torch.cuda.device(dev):
             _capi.call("stgcn_vit_block_backward_drop", _dev_ptr(x, "x", dev), weights, _dev_ptr(scale1, "scale1", dev),
                        _dev_ptr(scale2, "scale2", dev), ctypes.byref(masks), c_void_p(saved.data_ptr()), c_size_t(sbytes),
-                       _dev_ptr(dy, "dy", dev), _dev_ptr(grads["x"], "dx"), ctypes.byref(gs), c_float(eps), c_float(scale),
+                       _dev_ptr(dy, "dy", dev, align=ALIGN_LISTED if drop[0] is not None or drop[2] is not None else 0),
+                       _dev_ptr(grads["x"], "dx"), ctypes.byref(gs), c_float(eps), c_float(scale),
                        c_void_p(ws.data_ptr()), c_size_t(nbytes), c_int(B), c_int(L), c_int(D), c_int(heads), c_int(hidden),
                        c_uint(_vit_train_flags(math, small=True)), _stream(dev))
         return grads

@@ -106,10 +106,13 @@ def _ends_enabled() -> bool:
 class _PatchEmbedTrain(torch.autograd.Function):
     """The patch embedding under autograd: the forward is ``functional.vit_patch_embed`` as inference calls it, the backward
     ``functional.vit_patch_embed_backward``.  Saved: z and the weight, nothing the forward made.  The parameters arrive as
-    arguments (taken by attribute from the module), ``pos`` already sliced to its first n + 1 rows."""
+    arguments (taken by attribute from the module), ``pos`` already sliced to its first n + 1 rows.  z and the weight are
+    listed operands of both entry points (16 bytes): where one sits off that boundary - a parameter in a flat buffer - its
+    aligned copy is made once, here, and is what is saved."""
 
     @staticmethod
     def forward(ctx, z, weight, bias, cls, pos, p1, p2, math):
+        z, weight = F.aligned(z), F.aligned(weight)
         ctx.save_for_backward(z, weight)
         ctx.p1, ctx.p2, ctx.math = p1, p2, math
         ctx.shapes = (cls.shape, pos.shape)
@@ -119,7 +122,7 @@ class _PatchEmbedTrain(torch.autograd.Function):
     def backward(ctx, dx):
         z, weight = ctx.saved_tensors
         need = ctx.needs_input_grad
-        g = F.vit_patch_embed_backward(z, weight, dx.contiguous(), ctx.p1, ctx.p2, ctx.math, need_dz=need[0], need_dw=need[1],
+        g = F.vit_patch_embed_backward(z, weight, F.aligned(dx.contiguous()), ctx.p1, ctx.p2, ctx.math, need_dz=need[0], need_dw=need[1],
                                        need_dbias=need[2], need_dcls=need[3], need_dpos=need[4])
         dcls = g["dcls"].reshape(ctx.shapes[0]) if need[3] else None
         dpos = g["dpos"].reshape(ctx.shapes[1]) if need[4] else None
@@ -132,7 +135,7 @@ class _ClassifyTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln_weight, ln_bias, weight, bias, eps, mode):
-        x = x.contiguous()
+        x, weight = F.aligned(x.contiguous()), F.aligned(weight)      # listed operands of both entry points: copied once, saved
         ctx.save_for_backward(x, ln_weight, ln_bias, weight)
         ctx.eps, ctx.mode = eps, mode
         return F.vit_pool_classify(x, ln_weight, ln_bias, eps, weight, bias, mode=mode)
@@ -433,8 +436,8 @@ class ViT(nn.Module, HipSwitches):
             pat, lin = self.to_patch_embedding
             n1 = self._embed_tokens(z)
             with torch.no_grad():
-                return F.vit_patch_embed(z, lin.weight, lin.bias, self.cls_token, self.pos_embedding[0, :n1], pat.p1, pat.p2,
-                                         self._math())
+                return F.vit_patch_embed(F.aligned(z), F.aligned(lin.weight), lin.bias, self.cls_token, self.pos_embedding[0, :n1],
+                                         pat.p1, pat.p2, self._math())
         if self.embed_trains_on_hip(z):
             pat, lin = self.to_patch_embedding
             n1 = self._embed_tokens(z)
@@ -487,7 +490,8 @@ class ViT(nn.Module, HipSwitches):
         if self.head_on_hip(x):
             ln, lin = self.mlp_head
             with torch.no_grad():
-                return F.vit_pool_classify(x.contiguous(), ln.weight, ln.bias, ln.eps, lin.weight, lin.bias, mode=self.pool)
+                return F.vit_pool_classify(F.aligned(x.contiguous()), ln.weight, ln.bias, ln.eps, F.aligned(lin.weight), lin.bias,
+                                           mode=self.pool)
         if self.head_trains_on_hip(x):
             ln, lin = self.mlp_head
             return _ClassifyTrain.apply(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, self.pool)

@@ -168,8 +168,48 @@ class hostile_allocations:
         return False
 
 
+# ---- an operand off its allocation's alignment -------------------------------------------------------------------------------------
+class Skewed:
+    """What ``skewed`` keeps of one tensor: the backing bytes, where the tensor's bytes sit in them and the fill."""
+
+    def __init__(self, raw, lo, hi, fill):
+        self.raw, self.lo, self.hi, self.fill = raw, lo, hi, fill
+
+    def check(self):
+        """Both guard bands still hold nothing but the fill."""
+        for a, b, side in ((0, self.lo, "before"), (self.hi, self.raw.numel(), "after")):
+            bad = self.raw[a:b] != self.fill
+            if bool(bad.any()):
+                at = a + int(bad.to(torch.uint8).argmax())
+                where = f"start-{self.lo - at}" if side == "before" else f"end+{at - self.hi}"
+                raise AssertionError(f"guard of a skewed tensor overwritten {side} it: first changed byte at {where} "
+                                     f"(value 0x{int(self.raw[at]):02X}, fill 0x{self.fill:02X})")
+
+
+def skewed(t, k, fill=0xFF, guard=4096):
+    """A tensor equal to ``t`` - same shape, dtype, device and dense strides (contiguous stays contiguous, channels-last stays
+    channels-last) - whose first byte sits ``k`` elements behind a 256-byte boundary, between two guard bands of ``guard``
+    bytes filled with the byte ``fill`` (0xFF: NaN in fp32 and bf16).  ``.skew.check()`` of the result asserts that both
+    guards still hold the fill: a kernel that rounds the address down, or stores a vector where the row is not, writes there
+    or reads a NaN from there.  Works on the CPU (the allocation is windowed to a 256-byte boundary) as on the GPU."""
+    assert t.numel() > 0 and hostile_allocations._dense(t), "skewed: a dense, non-empty tensor"
+    assert 0 <= fill <= 0xFF and guard > 0 and guard % 256 == 0 and 0 <= k * t.element_size() < 256
+    nbytes = t.numel() * t.element_size()
+    raw = torch.empty(guard + 256 + nbytes + guard + 256, dtype=torch.uint8, device=t.device)
+    off = -(raw.data_ptr() + guard) % 256                    # the first byte behind the lower guard: on a 256-byte boundary
+    lo = off + guard + k * t.element_size()
+    raw = raw[off:lo + nbytes + guard]
+    raw.fill_(fill)
+    out = raw[lo - off:lo - off + nbytes].view(t.dtype).as_strided(t.shape, t.stride())
+    out.copy_(t.detach())
+    assert (out.data_ptr() - k * t.element_size()) % 256 == 0 and out.stride() == t.stride()
+    out.skew = Skewed(raw, lo - off, lo - off + nbytes, fill)
+    out.check = out.skew.check
+    return out
+
+
 # ---- a run under the hostile allocator --------------------------------------------------------------------------------------------
-FILLS = (0xFF, 0x7F)          # NaN in fp32 / fp64 / bf16; a huge finite positive number in all three
+FILLS =(0xFF, 0x7F)          # NaN in fp32 / fp64 / bf16; a huge finite positive number in all three
 
 
 class HostileCase:

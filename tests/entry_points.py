@@ -199,7 +199,8 @@ def agcn_train(cin, cout, N, T, V, want_dx, kink_free=False, frozen=False):
     ``kink_free``: the cotangent is _util.kink_free_cotangent of the first ``reference(x)`` - the clean input's.  ``on(dev, fresh)``:
     every run steps a fresh copy of the module and reports its running buffers after the step, or (``fresh=False``) the module
     itself with its gradients cleared; ``tile``: the cotangent repeated that often along the clips, for a tiled batch
-    (tests/large_extent.py)."""
+    (tests/large_extent.py).  ``module`` / ``cotangent`` ([G], filled by the first ``reference``): for callers that step the
+    module themselves."""
     from oracle import stgcn_oracle as so
     gcn, _, gp, _, gen = random_stem(V, None, 2000 + cin + cout + T + V, CPU, cin=cin, c=cout)
     gp = gp.to(torch.float64)
@@ -247,7 +248,7 @@ def agcn_train(cin, cout, N, T, V, want_dx, kink_free=False, frozen=False):
                 out["dx"] = xg.grad
             return out
         return run
-    return Setup(x, reference, on, leaves=names, module=gcn)
+    return Setup(x, reference, on, leaves=names, module=gcn, cotangent=G)
 
 
 # ---- the temporal conv ----------------------------------------------------------------------------------------------------------
