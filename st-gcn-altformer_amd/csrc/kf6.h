@@ -205,7 +205,10 @@ __device__ __forceinline__ void st_out4(float *p, const float4 &v) {
 // image's first row; 7 (3 + 2 + 2) counts from the first block a tap of the tile reads (pb0) and is chosen by the host plan
 // for the shapes in which no tile's taps read more than 28 blocks from there on (v6_blocks_read): what the frame-aligned image
 // holds behind them is then not produced either.
-template <int TERMS, bool BF16OUT, bool WIDE, int NPBW = 8>
+// PIXROWS (narrow three-term form, (N,C,T,V) output; launch_v6 chooses it): the consumer MFMAs take the activations as their A
+// and the weights as their B operand, from the same registers.  A lane then ends up with four consecutive pixels of one
+// channel instead of four channels of one pixel, and the epilogue stores them as they are (kf6_tile.h, "PIXROWS").
+template <int TERMS, bool BF16OUT, bool WIDE, int NPBW = 8, bool PIXROWS = false>
 __global__ __launch_bounds__(NT6) void stem_bf16_v6_kernel(
     const uint4 *__restrict__ pfrag, const float *__restrict__ x, int xsc, int xsp, const float *__restrict__ W12,
     const uint4 *__restrict__ Wp, const float *__restrict__ shift, void *y, int C, int T, int V, int ROWS,
@@ -670,6 +673,11 @@ int launch_v6(const uint4 *pf, const float *x, int xsc, int xsp, const float *W1
     auto kern = bf16out ? stem_bf16_v6_kernel<TERMS, true, WIDE> : stem_bf16_v6_kernel<TERMS, false, WIDE>;
     if constexpr (TERMS == 3 && !WIDE)        // (the one-term and the wide forms stay on 8 blocks: not measured on 7)
         if (pl.npbw == 7) kern = bf16out ? stem_bf16_v6_kernel<3, true, false, 7> : stem_bf16_v6_kernel<3, false, false, 7>;
+    if constexpr (TERMS == 3 && !WIDE)        // (N,C,T,V): results leave the accumulators as rows of pixels (PIXROWS)
+        if (!(opt & OPT_OUT_NTVC)) {
+            if (pl.npbw == 7) kern = bf16out ? stem_bf16_v6_kernel<3, true, false, 7, true> : stem_bf16_v6_kernel<3, false, false, 7, true>;
+            else kern = bf16out ? stem_bf16_v6_kernel<3, true, false, 8, true> : stem_bf16_v6_kernel<3, false, false, 8, true>;
+        }
     if constexpr (TERMS == 3 && !WIDE)
         if (pl.short_last) opt |= OPT_V6_SHORT;
     STGCN_HIP_CHECK(allow_lds(kern, pl.lds));

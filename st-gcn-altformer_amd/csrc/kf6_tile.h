@@ -9,8 +9,9 @@
         [[maybe_unused]] constexpr int SB = SHORT ? 8 : 0;        // (diagnostic builds: the short form's cycle stamps have slots of their own)
         // SHORT: the lane, opaque per tile — the lane-only address terms of its epilogue are then computed where they are used;
         // hoisted out of the tile loop beside the full form's they do not fit the register file (13 spilled registers)
+        // (PIXROWS: likewise in both forms, so that its epilogue's per-lane term stays out of the main loop's registers)
         int lane_t = lane;
-        if constexpr (SHORT) asm volatile("" : "+v"(lane_t));
+        if constexpr (SHORT || PIXROWS) asm volatile("" : "+v"(lane_t));
         TileInfo6 ti;
         if constexpr (WIDE) ti = tile_info(tile);
         else {
@@ -185,7 +186,15 @@
                     //  measured 2 % slower)
                     constexpr int mb = i / (NB * TERMS), nb = (i / TERMS) % NB, term = i % TERMS;
                     const bf16x8 a_h = __builtin_bit_cast(bf16x8, ah[mb & 1]), b_h = __builtin_bit_cast(bf16x8, b_cur.hi[nb]);
-                    if constexpr (TERMS == 3) {
+                    if constexpr (TERMS == 3 && PIXROWS) {
+                        // operands exchanged: the MFMA takes its A and B fragments in one lane layout (row or column lane & 15,
+                        // k-group lane >> 4), so the same registers give the transposed block D[row = pixel][col = channel],
+                        // every element the same sum of the same products over the same k (see the PIXROWS epilogue)
+                        const bf16x8 a_l = __builtin_bit_cast(bf16x8, al[mb & 1]), b_l = __builtin_bit_cast(bf16x8, b_cur.lo[nb]);
+                        if constexpr (term == 0) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b_l, a_h, acc[mb][nb], 0, 0, 0);
+                        else if constexpr (term == 1) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b_h, a_l, acc[mb][nb], 0, 0, 0);
+                        else acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b_h, a_h, acc[mb][nb], 0, 0, 0);
+                    } else if constexpr (TERMS == 3) {
                         const bf16x8 a_l = __builtin_bit_cast(bf16x8, al[mb & 1]), b_l = __builtin_bit_cast(bf16x8, b_cur.lo[nb]);
                         if constexpr (term == 0) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_h, b_l, acc[mb][nb], 0, 0, 0);
                         else if constexpr (term == 1) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_l, b_h, acc[mb][nb], 0, 0, 0);
@@ -230,7 +239,7 @@
         load_x(xn1, min(next_tile, ntiles - 1), wave + 4);
         load_x(xn2, min(next_tile, ntiles - 1), wave + 8);
         __builtin_amdgcn_sched_barrier(0);
-        float *stg = reinterpret_cast<float *>(buf0 + wave * EPI6);
+        [[maybe_unused]] float *stg = reinterpret_cast<float *>(buf0 + wave * EPI6);   // (PIXROWS stores without staging)
         const int qw = g.q0 + wave * (16 * NB);
         const bool full = !SHORT && g.q0 + NP6 - 1 <= g.q_last;            // (scalar) every pixel of the tile lies inside the clip
         if constexpr (WIDE) {
@@ -373,6 +382,62 @@
                         }
                     }
                 }
+            } else if constexpr (PIXROWS) {
+                // PIXROWS, (N,C,T,V) only (launch_v6): D[row = pixel 4*(lane>>4) + r][col = channel lane&15] per 16x16 block — a
+                // lane holds FOUR CONSECUTIVE PIXELS OF ONE CHANNEL, which is what a row of the output wants: one 16-byte store
+                // straight from the accumulators, no staging slice, no ds_write / ds_read, one shift value per block (the lane's
+                // channel, from lane (mb & 3) * 16 + (lane & 15) of sh_lo / sh_hi).  A store instruction writes 16 channel rows x
+                // 64 B; the four pixel blocks of a wave complete a row's 256 B within four consecutive stores.  The same three
+                // forms as the staged epilogue below, chosen by the same uniform branch per tile.
+                const int cl = lane_t & 15, p4 = 4 * (lane_t >> 4);
+                const unsigned lterm = (unsigned)(cl * TV + p4);            // the one per-lane address term
+                const size_t tb0 = ((size_t)n * C + cg * 128) * TV + qw;    // scalar: the wave's pixels in channel row 0 of the group
+                // 16-byte (8-byte for bf16) aligned rows, the same for all eight blocks, and a result that sits on them
+                const bool al16 = ((tb0 & 3) == 0) && (TV % 4 == 0) && (reinterpret_cast<size_t>(y) & (BF16OUT ? 7 : 15)) == 0;
+                auto blocks = [&](auto form_c) {
+                    constexpr int FORM = decltype(form_c)::value;  // 1: every store 16 B; 0: element by element; 2: whole groups 16 B
+                    float shv[8];
+#pragma unroll
+                    for (int mb = 0; mb < 8; ++mb)         // all eight up front: one lgkmcnt wait per tile
+                        shv[mb] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * ((mb & 3) * 16 + cl),
+                                                                                         __builtin_bit_cast(int, mb < 4 ? sh_lo : sh_hi)));
+                    // FORM 1: a block's four stores issue as soon as its 16 values exist (left alone, hipcc computes most of
+                    // the tile's 128 values first and issues the stores behind them in one clump)
+                    if constexpr (FORM == 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int mb = 0; mb < 8; ++mb) {
+                        const size_t tbase = tb0 + (size_t)(mb * 16) * TV;        // scalar
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb) {
+                            const float4 v = make_float4(max_nan(acc[mb][nb][0] + shv[mb], 0.f), max_nan(acc[mb][nb][1] + shv[mb], 0.f),
+                                                         max_nan(acc[mb][nb][2] + shv[mb], 0.f), max_nan(acc[mb][nb][3] + shv[mb], 0.f));
+                            const size_t sbase = tbase + nb * 16;                 // scalar
+                            auto store16 = [&]() {
+                                if constexpr (BF16OUT)
+                                    *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + sbase + lterm) =
+                                        make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+                                else
+                                    st_out4<true>(reinterpret_cast<float *>(y) + sbase + lterm, v);
+                            };
+                            auto store_elements = [&]() {               // element by element, each under its bounds check
+                                const float e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                                for (int e = 0; e < 4; ++e)
+                                    if (qw + nb * 16 + p4 + e <= g.q_last) store_out<BF16OUT>(y, sbase + lterm + e, e4[e]);
+                            };
+                            if constexpr (FORM == 1) store16();
+                            else if constexpr (FORM == 2) { if (qw + nb * 16 + p4 + 3 <= g.q_last) store16(); else store_elements(); }
+                            else store_elements();                       // last tile of a clip / unaligned rows
+                        }
+                        if constexpr (FORM == 1) __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
+#ifdef V6_SHORT_ELEMENT_STORES
+                if constexpr (SHORT) blocks(std::integral_constant<int, 0>{});
+#else
+                if constexpr (SHORT) { if (al16) blocks(std::integral_constant<int, 2>{}); else blocks(std::integral_constant<int, 0>{}); }
+#endif
+                else if (full && al16) blocks(std::integral_constant<int, 1>{}); else blocks(std::integral_constant<int, 0>{});
             } else {
                 // The narrow forms below exist twice, chosen by ONE uniform branch per tile: FAST (every pixel inside the clip, rows
                 // aligned) is straight-line code whose stores issue back to back — nothing between a tile's first and last store

@@ -6,7 +6,8 @@
 
 Per kernel whose mangled name contains --kernel (default: every kernel with a loop of >= 256 MFMAs):
   * main loop: instructions, MFMAs, v_accvgpr_* copies and s_waitcnt of the innermost loop that holds the MFMAs (one trip =
-    one period of 9 pairs);
+    one period of 9 pairs); a kernel with a short tile form has two such loops: the smaller is reported as the main loop and
+    both are listed beside it;
   * tile loop: global_load_dwordx4 (LDS-DMAs excluded: those are global_load_lds_*) and scratch_* / buffer_*_offen scratch use;
   * tile tail: global_store_* instructions behind the main loop, and the `s_waitcnt vmcnt` that stand between the first and
     the last of them in program order, basic blocks ignored (every form of the epilogue is counted: divide by the forms);
@@ -66,8 +67,12 @@ def analyse(name, body):
         return None
     main = min(with_mfma, key=lambda l: l[1] - l[0])
     tile = max((l for l in loops if l[0] <= main[0] and l[1] >= main[1]), key=lambda l: l[1] - l[0])
+    # every innermost MFMA loop: a kernel with a short tile form has two main loops (the short form's is the smaller `main`)
+    inner = [l for l in with_mfma if not any(o != l and l[0] <= o[0] and o[1] <= l[1] for o in with_mfma)]
     res = {
         "kernel": name,
+        "main_loops": [{"instructions": count(*l, lambda op, arg: True), "mfma": count(*l, mf),
+                        "v_accvgpr": count(*l, lambda op, arg: op.startswith("v_accvgpr"))} for l in inner],
         "main_loop": {
             "instructions": count(*main, lambda op, arg: True),
             "mfma": count(*main, mf),
@@ -136,6 +141,8 @@ def main():
         found = True
         print(r["kernel"])
         print("  main loop (one period):", r["main_loop"])
+        if len(r["main_loops"]) > 1:
+            print("  every main loop (short and full tile form):", r["main_loops"])
         print("  tile loop:", r["tile_loop"])
         print("  tile tail:", r["tile_tail"])
         print("  resources:", resources(text, name))
