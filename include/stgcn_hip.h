@@ -347,8 +347,12 @@ int stgcn_step_stats(const void *out, int out_is_bf16, float *stats, int N, int 
  *   y = relu(BatchNorm2d(z))
  * x, y: (N,Cin,T,V) / (N,Cout,T,V).  dk = Cout/4 in the reference's configuration; covered: (dk/heads, Cout/heads) in
  * {(4,16), (8,32), (16,64)} — Cout in {128, 256, 512} with 8 heads — any Cin, V <= 64, N <= 65535 clips with
- * N*T < 2^26 frames and N*max(Cin,Cout) < 2^24 (its launches' 2^32 work-items: below 32768 clips at 512 channels; else
- * STGCN_ERR_UNSUPPORTED). */
+ * N*T < 2^26 frames and N*max(Cin,Cout) < 2^24 (its launches' 2^32 work-items: below 32768 clips at 512 channels), and
+ * T*V columns a clip up to what the product kernel of the call's arithmetic tiles: T*V <= 65535*64 = 4,194,240 with
+ * STGCN_MATH_F32, T*V <= 65535*128 = 8,388,480 with STGCN_MATH_BF16X3 (the backward's weight gradients are f32 GEMMs over T*V
+ * and hold either), every operand of one clip below 2^31 elements.  Else STGCN_ERR_UNSUPPORTED.  Every entry point decides
+ * this before its first launch: a refused call has written nothing - not y, not the workspace, not a saved tensor or a
+ * gradient, and not the running statistics of either BatchNorm. */
 int stgcn_st_attention_supported(int Cin, int Cout, int dk, int V, int heads);
 /* workspace bytes of pass 0 = stgcn_st_attention_forward, 1 = _forward_train, 2 = _backward (0 for invalid sizes) */
 size_t stgcn_st_attention_ws_bytes(int N, int Cin, int Cout, int dk, int T, int V, int heads, int pass);

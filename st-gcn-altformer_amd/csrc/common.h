@@ -151,6 +151,8 @@ static inline int bn_chunks(int N, size_t plane, int C = 0) {
     if (chunks > 64) chunks = 64;
     return chunks < 1 ? 1 : chunks;
 }
+// ... and their grid.y: the channel rides on a 16-bit axis.  Asked by every launcher of them (train_bn.hip, tcn_backward.hip)
+static inline bool bn_rows_fit(int N, int C) { return N >= 1 && C >= 1 && C <= 65535; }
 
 // ---------------------------------------------------------------------------------------
 // launchers implemented in the kernel translation units (all enqueue on `st`, return status)
@@ -472,6 +474,12 @@ struct GemmArgs {
     int k_inner = 0;
     long long a_sk2 = 0, b_sk2 = 0;
 };
+// The shape limits of the launchers below, one host predicate each: the launcher asks it and refuses with
+// STGCN_ERR_UNSUPPORTED, and a plan that wants to refuse before its first launch asks it too (pointers are not read).
+bool gemm_f32_spans_fit(const GemmArgs &g);              // every operand of one batch entry within 32-bit offsets
+bool gemm_f32_grid_fits(const GemmArgs &g, int batch);   // column tiles and batch entries on 16-bit grid axes
+bool sum_parts_covers(int parts, size_t n);
+bool row_sum_covers(long long rows, long long cols);
 int launch_gemm_f32(const GemmArgs &g, int batch, hipStream_t st);
 // out[rep*rep_stride + e] = sum_p part[p*n + e] in a fixed order, written `reps` times (one bias gradient shared by the subsets)
 int launch_sum_parts(const float *part, float *out, int parts, size_t n, hipStream_t st, int reps = 1, size_t rep_stride = 0);
@@ -486,7 +494,7 @@ int launch_softmax_bwd(const float *P, const float *A_eff, const float *dP, floa
 
 // weights times channel-first activations in the three-term split arithmetic (wx_bf16.hip):
 // C[n] = W . X[n] (+ bias per row) (+ R[n]); W (M,K), or (K,M) with w_transposed; X[n] (K,TV); C[n], R[n] (M,TV); R may not overlap C
-bool wx_bf16x3_covers(int M, int K, long long TV);
+bool wx_bf16x3_covers(int M, int K, long long TV, int N);   // asked by its launcher and by plan_wx (st_attention.hip)
 int wx_bf16x3_tile_rows(int M);              // rows of the tile form that serves M: 128 or 64
 const char *wx_bf16x3_kernel_name(int M);
 int launch_wx_bf16x3(const float *W, const float *X, const float *bias, const float *R, float *C, int N, int M, int K,

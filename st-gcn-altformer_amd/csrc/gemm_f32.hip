@@ -320,28 +320,39 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float *__restric
 
 }  // namespace
 
+// wave arrangement by shape (see the kernel's header): 0 = 2 x 2 waves of 64 x 64, 1 = 4 x 1 of 128 x 32, 2 = 1 x 1, K in four
+static int gemm_f32_form(const GemmArgs &g) { return (g.M <= 32 && g.N <= 32 && g.K >= 256) ? 2 : (g.N <= 32 ? 1 : 0); }
+
+// offsets inside one batch entry are 32-bit in the kernel
+bool gemm_f32_spans_fit(const GemmArgs &g) {
+    auto span = [](long long n, long long inner, long long s1, long long s2) {
+        if (s1 < 0 || s2 < 0) return (long long)1 << 40;
+        return inner > 0 ? ((n - 1) / inner) * s1 + (inner - 1) * s2 : (n - 1) * s1;
+    };
+    const long long lim = ((long long)1 << 31) - 1;
+    const long long sa = span(g.M, g.m_inner, g.a_sm, g.a_sm2) + span(g.K, g.k_inner, g.a_sk, g.a_sk2);
+    const long long sb = span(g.K, g.k_inner, g.b_sk, g.b_sk2) + span(g.N, 0, g.b_sn, 0);
+    const long long sc = span(g.M, g.m_inner, g.c_sm, g.c_sm2) + span(g.N, 0, g.c_sn, 0);
+    return sa <= lim && sb <= lim && sc <= lim;
+}
+
+// the column tiles and the (batch entry, contraction part) pairs ride on 16-bit grid axes
+bool gemm_f32_grid_fits(const GemmArgs &g, int batch) {
+    const int ks = g.ksplit > 1 ? g.ksplit : 1, TN = gemm_f32_form(g) == 0 ? 64 : 32;
+    return (long long)batch * ks <= 65535 && ceil_div(g.N, TN) <= 65535;
+}
+
 int launch_gemm_f32(const GemmArgs &g, int batch, hipStream_t st) {
     if (g.M <= 0 || g.N <= 0 || g.K <= 0 || batch <= 0) return fail(STGCN_ERR_ARG, "gemm: empty problem");
     const int ks = g.ksplit > 1 ? g.ksplit : 1;
     if (ks > 1 && (g.accumulate || g.bias || g.nbias || g.cbias))
         return fail(STGCN_ERR_ARG, "gemm: a split contraction writes plain partial sums (no bias, no accumulate)");
-    {   // offsets inside one batch entry are 32-bit in the kernel
-        auto span = [](long long n, long long inner, long long s1, long long s2) {
-            if (s1 < 0 || s2 < 0) return (long long)1 << 40;
-            return inner > 0 ? ((n - 1) / inner) * s1 + (inner - 1) * s2 : (n - 1) * s1;
-        };
-        const long long lim = ((long long)1 << 31) - 1;
-        const long long sa = span(g.M, g.m_inner, g.a_sm, g.a_sm2) + span(g.K, g.k_inner, g.a_sk, g.a_sk2);
-        const long long sb = span(g.K, g.k_inner, g.b_sk, g.b_sk2) + span(g.N, 0, g.b_sn, 0);
-        const long long sc = span(g.M, g.m_inner, g.c_sm, g.c_sm2) + span(g.N, 0, g.c_sn, 0);
-        if (sa > lim || sb > lim || sc > lim)
-            return fail(STGCN_ERR_UNSUPPORTED, "gemm: an operand of one batch entry spans more than 2^31 elements (or a negative stride)");
-    }
+    if (!gemm_f32_spans_fit(g))
+        return fail(STGCN_ERR_UNSUPPORTED, "gemm: an operand of one batch entry spans more than 2^31 elements (or a negative stride)");
     if (g.b_inner > 0 && batch % g.b_inner != 0) return fail(STGCN_ERR_ARG, "gemm: batch %d is not a multiple of its inner count %d", batch, g.b_inner);
-    // wave arrangement by shape (see the kernel's header)
-    const int form = (g.M <= 32 && g.N <= 32 && g.K >= 256) ? 2 : (g.N <= 32 ? 1 : 0);
+    const int form = gemm_f32_form(g);
     const int TM = form == 0 ? 64 : (form == 1 ? 128 : 32), TN = form == 0 ? 64 : 32;
-    if ((long long)batch * ks > 65535 || ceil_div(g.N, TN) > 65535) return fail(STGCN_ERR_UNSUPPORTED, "gemm: grid too large");
+    if (!gemm_f32_grid_fits(g, batch)) return fail(STGCN_ERR_UNSUPPORTED, "gemm: grid too large");
     const dim3 grid(ceil_div(g.M, TM), ceil_div(g.N, TN), batch * ks);
     if (form == 0) hipLaunchKernelGGL((gemm_f32_kernel<2, 2, 1>), grid, dim3(256), 0, st, g);
     else if (form == 1) hipLaunchKernelGGL((gemm_f32_kernel<4, 1, 1>), grid, dim3(256), 0, st, g);
@@ -375,7 +386,11 @@ int launch_patch_embed(const float *z, const float *W, const float *b, const flo
     return launch_gemm_f32(g, N, st);
 }
 
+// one workgroup of up to 1024 threads per 32 outputs
+bool sum_parts_covers(int parts, size_t n) { return grid_fits((long long)(n / 32 + 1), parts >= 64 ? 1024 : 256); }
+
 int launch_sum_parts(const float *part, float *out, int parts, size_t n, hipStream_t st, int reps, size_t rep_stride) {
+    if (!sum_parts_covers(parts, n)) return fail(STGCN_ERR_UNSUPPORTED, "sum of %d parts: %zu outputs exceed the grid", parts, n);
     const dim3 grid((unsigned)((n + 31) / 32));
     if (parts >= 64)
         hipLaunchKernelGGL((sum_parts_kernel<32>), grid, dim3(1024), 0, st, part, out, parts, n, reps, rep_stride);
@@ -391,7 +406,13 @@ int launch_add_inplace(float *dst, const float *src, size_t n, hipStream_t st) {
     return STGCN_OK;
 }
 
+// four rows a workgroup; both counts are ints in the kernel, whose column walk steps by 64
+bool row_sum_covers(long long rows, long long cols) {
+    return rows >= 1 && cols >= 1 && rows <= 0x7fffffffLL && cols <= 0x7fffffffLL - 64 && grid_fits((rows + 3) / 4, 256);
+}
+
 int launch_row_sum(const float *in, float *out, int rows, int cols, hipStream_t st) {
+    if (!row_sum_covers(rows, cols)) return fail(STGCN_ERR_UNSUPPORTED, "row sum: %d rows of %d columns exceed the grid", rows, cols);
     hipLaunchKernelGGL(row_sum_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, st, in, out, rows, cols);
     STGCN_LAUNCH_CHECK("row_sum_kernel");
     return STGCN_OK;

@@ -22,6 +22,8 @@
 // Both BatchNorms use the training helpers of train_bn.hip / tcn_backward.hip.  data_bn's per-(c,v) statistics are summed
 // in a fixed order (fp32 inside a (clip, thread) strip, fp64 across, parts added in order), BatchNorm2d's with the fp64
 // atomics of bn_batch_stats (order-dependent only in the last fp64 bits).
+#include <stdarg.h>
+
 #include <cmath>
 
 #include "common.h"
@@ -352,29 +354,21 @@ __global__ __launch_bounds__(256) void cv_bwd_apply_kernel(const float *__restri
     dx[e] = d;
 }
 
-bool heads_supported(int Cout, int dk, int H, int *dkh, int *dvh) {
-    if (H < 1 || dk % H || Cout % H) return false;
-    *dkh = dk / H;
-    *dvh = Cout / H;
-    return (*dkh == 4 && *dvh == 16) || (*dkh == 8 && *dvh == 32) || (*dkh == 16 && *dvh == 64);
+// ----------------------------------------------------------------------------------------------------------------------
+// launchers.  Every shape limit of a launch is one host predicate next to it: the launcher asks it, and so does
+// plan_st_attention below, which refuses a call before its first launch.
+// ----------------------------------------------------------------------------------------------------------------------
+void say(Refusal &r, stgcn_status status, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(r.msg, sizeof(r.msg), fmt, ap);
+    va_end(ap);
+    r.status = status;
 }
 
-int check_shape(const char *fn, int N, int Cin, int Cout, int dk, int T, int V, int H) {
-    int dkh, dvh;
-    if (N < 1 || Cin < 1 || Cout < 1 || dk < 1 || T < 1 || V < 1 || H < 1)
-        return fail(STGCN_ERR_ARG, "%s: non-positive dimension (N=%d Cin=%d Cout=%d dk=%d T=%d V=%d heads=%d)", fn, N, Cin,
-                    Cout, dk, T, V, H);
-    if (!heads_supported(Cout, dk, H, &dkh, &dvh))
-        return fail(STGCN_ERR_UNSUPPORTED,
-                    "%s: Cout=%d dk=%d heads=%d gives per-head widths dkh=%d dvh=%d; the kernels cover (dkh, dvh) in "
-                    "{(4,16), (8,32), (16,64)} (Cout in {128, 256, 512} with dk = Cout/4, 8 heads)",
-                    fn, Cout, dk, H, dk / H, Cout / H);
-    if (V > kVP) return fail(STGCN_ERR_UNSUPPORTED, "%s: V=%d joints; the attention kernels cover V <= %d", fn, V, kVP);
-    if (!grid_fits((long long)N * T, 64) || H > 65535) return fail(STGCN_ERR_UNSUPPORTED, "%s: grid too large", fn);
-    if (!grid_fits((long long)N * (Cin > Cout ? Cin : Cout), 256) || N > 65535)
-        return fail(STGCN_ERR_UNSUPPORTED, "%s: N=%d clips exceed the grid", fn, N);
-    return STGCN_OK;
-}
+// sta_*: the instantiated per-head widths; one wave per (frame, head), lane = joint
+bool sta_widths_covered(int dkh, int dvh) { return (dkh == 4 && dvh == 16) || (dkh == 8 && dvh == 32) || (dkh == 16 && dvh == 64); }
+bool sta_covers(int N, int T, int V, int H) { return V >= 1 && V <= kVP && H >= 1 && H <= 65535 && grid_fits((long long)N * T, 64); }
 
 size_t bwd_lds_bytes(int DKH, int DVH) {
     return sizeof(float) * ((size_t)2 * kVP * DKH + (size_t)2 * kVP * DVH + (size_t)kVP * (kVP + 1) + kVP);
@@ -382,6 +376,8 @@ size_t bwd_lds_bytes(int DKH, int DVH) {
 
 int launch_sta_fwd(const float *qkv, const float *mask, float *o, float *rowstats, int N, int T, int V, int H, int dkh,
                    int dvh, hipStream_t st) {
+    if (!sta_widths_covered(dkh, dvh) || !sta_covers(N, T, V, H))
+        return fail(STGCN_ERR_UNSUPPORTED, "sta_fwd_kernel: N=%d T=%d V=%d heads=%d dkh=%d dvh=%d", N, T, V, H, dkh, dvh);
     const dim3 grid((unsigned)(N * T), (unsigned)H);
     const float qscale = (float)std::pow((double)dkh, -0.5);   // (the reference's Python scalar dkh ** -0.5)
     if (dkh == 4) hipLaunchKernelGGL((sta_fwd_kernel<4, 16>), grid, dim3(64), 0, st, qkv, mask, o, rowstats, T, V, H, qscale);
@@ -393,6 +389,8 @@ int launch_sta_fwd(const float *qkv, const float *mask, float *o, float *rowstat
 
 int launch_sta_bwd(const float *qkv, const float *dout, const float *mask, const float *rowstats, float *dqkv, int N, int T,
                    int V, int H, int dkh, int dvh, hipStream_t st) {
+    if (!sta_widths_covered(dkh, dvh) || !sta_covers(N, T, V, H))
+        return fail(STGCN_ERR_UNSUPPORTED, "sta_bwd_kernel: N=%d T=%d V=%d heads=%d dkh=%d dvh=%d", N, T, V, H, dkh, dvh);
     const dim3 grid((unsigned)(N * T), (unsigned)H);
     const float qscale = (float)std::pow((double)dkh, -0.5);
     const size_t lds = bwd_lds_bytes(dkh, dvh);
@@ -410,10 +408,20 @@ int launch_sta_bwd(const float *qkv, const float *dout, const float *mask, const
     return STGCN_OK;
 }
 
+// cv_*: a grid row per (clip, channel) and 256 pixels of its plane a workgroup along grid.y; T*V and 2*C*V are ints in the kernels
+bool cv_covers(int N, int C, int T, int V) {
+    return N >= 1 && C >= 1 && T >= 1 && V >= 1 && V <= kVP && grid_fits((long long)N * C, 256) &&
+           (long long)T * V <= 65535LL * 256 && 2LL * C * V <= 0x7fffffffLL;
+}
+int cv_refused(const char *kernel, int N, int C, int T, int V) {
+    return fail(STGCN_ERR_UNSUPPORTED, "%s: N=%d C=%d T=%d V=%d exceed the grid", kernel, N, C, T, V);
+}
+
 int cv_splits(int N) { return N < 16 ? N : 16; }
 
 int launch_cv_stats(const float *a, const float *g, const float *mean, const float *invstd, double *parts, double *sums,
                     int N, int C, int T, int V, hipStream_t st) {
+    if (!cv_covers(N, C, T, V)) return cv_refused("cv_stats_kernel", N, C, T, V);
     const int splits = cv_splits(N);
     hipLaunchKernelGGL(cv_stats_kernel, dim3(C, splits), dim3(256), 0, st, a, g, mean, invstd, parts, N, C, T, V);
     STGCN_LAUNCH_CHECK("cv_stats_kernel");
@@ -424,126 +432,227 @@ int launch_cv_stats(const float *a, const float *g, const float *mean, const flo
 
 int launch_cv_apply(const float *x, const float *scale, const float *shift, float *out, int N, int C, int T, int V,
                     hipStream_t st) {
+    if (!cv_covers(N, C, T, V)) return cv_refused("cv_apply_kernel", N, C, T, V);
     hipLaunchKernelGGL(cv_apply_kernel, dim3(N * C, ceil_div(T * V, 256)), dim3(256), 0, st, x, scale, shift, out, C, T, V);
     STGCN_LAUNCH_CHECK("cv_apply_kernel");
     return STGCN_OK;
 }
 
-// C[n] (+)= W . X[n] (+ bias): W (M,K) row-major shared by the clips, X[n] (K, TV), C[n] (M, TV)
-int gemm_w_x(const float *W, const float *X, float *Cm, const float *bias, int M, int K, long long TV, int N, int accumulate,
-             bool w_transposed, hipStream_t st) {
+int launch_cv_bwd_apply(const float *g, const float *x, const float *mean, const float *invstd, const float *coef,
+                        const float *res, float *dx, int N, int C, int T, int V, hipStream_t st) {
+    if (!cv_covers(N, C, T, V)) return cv_refused("cv_bwd_apply_kernel", N, C, T, V);
+    hipLaunchKernelGGL(cv_bwd_apply_kernel, dim3(N * C, ceil_div(T * V, 256)), dim3(256), 0, st, g, x, mean, invstd, coef, res,
+                       dx, C, T, V);
+    STGCN_LAUNCH_CHECK("cv_bwd_apply_kernel");
+    return STGCN_OK;
+}
+
+// ----------------------------------------------------------------------------------------------------------------------
+// One W . X product: C[n] = W . X[n] (+ bias) (+ R[n]), W (M,K) row-major (or (K,M): the input gradient through the weights)
+// shared by the N clips, X[n] (K,TV), C[n] (M,TV).  Its plan serves the unit's four products and stgcn_wx_product*.
+// ----------------------------------------------------------------------------------------------------------------------
+// extents and strides of the product on the strided f32 GEMM; the pointers are the launcher's
+GemmArgs wx_gemm(int M, int K, long long TV, bool w_transposed) {
     GemmArgs g{};
-    g.A = W;
-    if (w_transposed) { g.a_sm = 1; g.a_sk = M; }     // W given as (K, M): the input gradient through the weights
+    if (w_transposed) { g.a_sm = 1; g.a_sk = M; }
     else { g.a_sm = K; g.a_sk = 1; }
     g.a_sb = 0;
-    g.B = X; g.b_sk = TV; g.b_sn = 1; g.b_sb = (long long)K * TV;
-    g.C = Cm; g.c_sm = TV; g.c_sn = 1; g.c_sb = (long long)M * TV;
-    g.bias = bias;
+    g.b_sk = TV; g.b_sn = 1; g.b_sb = (long long)K * TV;
+    g.c_sm = TV; g.c_sn = 1; g.c_sb = (long long)M * TV;
     g.M = M; g.N = (int)TV; g.K = K;
     g.alpha = 1.f;
-    g.accumulate = accumulate;
-    return launch_gemm_f32(g, N, st);
+    return g;
 }
 
-// The arithmetic of the unit's four W . X products, from the low 4 bits of `flags`: f32 (gemm_w_x) or bf16x3 (wx_bf16.hip)
-int check_math(const char *fn, unsigned flags) {
+struct WxPlan {
+    enum Kernel { none, gemm_f32, bf16x3 } kernel = none;
+    int M = 0, K = 0, N = 0;
+    long long TV = 0;
+    bool transposed = false;
+    Refusal why;
+};
+
+// The arithmetic comes from the low 4 bits of `flags`.  Inside the unit (`alone` false) a product is covered where its own
+// kernel is: the f32 GEMM up to 65535 * 64 columns, the bf16x3 kernel up to 65535 * 128.  The stand-alone entry point covers
+// what BOTH kernels do and holds a clip to 2^31 - 1 elements, whichever arithmetic is asked for (include/stgcn_hip.h).
+WxPlan plan_wx(const char *fn, int M, int K, long long TV, int N, bool w_transposed, unsigned flags, bool alone) {
+    WxPlan p;
+    p.M = M, p.K = K, p.N = N, p.TV = TV, p.transposed = w_transposed;
+    if (N < 1 || M < 1 || K < 1 || TV < 1)
+        return say(p.why, STGCN_ERR_ARG, "%s: non-positive dimension (N=%d M=%d K=%d TV=%lld)", fn, N, M, K, TV), p;
     const unsigned m = flags & STGCN_MATH_MASK;
-    if (m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3) return STGCN_OK;
-    const char *name = m == STGCN_MATH_BF16 ? "STGCN_MATH_BF16" : m == STGCN_MATH_F32_VALU ? "STGCN_MATH_F32_VALU" : "unknown";
-    return fail(STGCN_ERR_UNSUPPORTED, "%s: arithmetic %u (%s) is not implemented for this product; STGCN_MATH_F32 and "
-                "STGCN_MATH_BF16X3 are", fn, m, name);
+    if (m != STGCN_MATH_F32 && m != STGCN_MATH_BF16X3) {
+        const char *name = m == STGCN_MATH_BF16 ? "STGCN_MATH_BF16" : m == STGCN_MATH_F32_VALU ? "STGCN_MATH_F32_VALU" : "unknown";
+        return say(p.why, STGCN_ERR_UNSUPPORTED, "%s: arithmetic %u (%s) is not implemented for this product; STGCN_MATH_F32 and "
+                   "STGCN_MATH_BF16X3 are", fn, m, name), p;
+    }
+    const bool f32 = TV <= 0x7fffffffLL && gemm_f32_spans_fit(wx_gemm(M, K, TV, w_transposed)) &&
+                     gemm_f32_grid_fits(wx_gemm(M, K, TV, w_transposed), N);
+    const bool b3 = wx_bf16x3_covers(M, K, TV, N);
+    const bool ok = alone ? f32 && b3 && (long long)(M > K ? M : K) * TV <= 0x7fffffffLL : (m == STGCN_MATH_F32 ? f32 : b3);
+    if (!ok)
+        return say(p.why, STGCN_ERR_UNSUPPORTED, "%s: N=%d M=%d K=%d TV=%lld exceed the grid or 2^31 elements a clip (%s product)", fn,
+                   N, M, K, TV, m == STGCN_MATH_F32 ? "f32" : "bf16x3"), p;
+    p.kernel = m == STGCN_MATH_F32 ? WxPlan::gemm_f32 : WxPlan::bf16x3;
+    return p;
 }
 
-// what both arithmetics of the product cover: the f32 GEMM's 32-bit offsets inside a clip and its 64-column grid
-bool wx_covers(int M, int K, long long TV) {
-    if (M < 1 || K < 1 || TV < 1 || TV > 65535LL * 64) return false;
-    return (long long)(M > K ? M : K) * TV <= 0x7fffffffLL && wx_bf16x3_covers(M, K, TV);
-}
-
-// C[n] = W . X[n] (+ bias) (+ R[n]) in the arithmetic of `flags`.  f32: R is copied into C and the product accumulated onto
-// it (the skip connection as it always ran); bf16x3: R is read in the kernel's epilogue.
-int w_x(unsigned flags, const float *W, const float *X, float *Cm, const float *bias, const float *R, int M, int K, long long TV,
-        int N, bool w_transposed, hipStream_t st) {
-    if ((flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3) return launch_wx_bf16x3(W, X, bias, R, Cm, N, M, K, TV, w_transposed, st);
+// f32: R is copied into C and the product accumulated onto it (the skip connection as it always ran); bf16x3: R is read in
+// the kernel's epilogue.
+int launch_wx(const WxPlan &p, const float *W, const float *X, float *Cm, const float *bias, const float *R, hipStream_t st) {
+    if (p.kernel == WxPlan::none) return refused(p.why);
+    if (p.kernel == WxPlan::bf16x3) return launch_wx_bf16x3(W, X, bias, R, Cm, p.N, p.M, p.K, p.TV, p.transposed, st);
     if (R && R != Cm)
-        STGCN_HIP_CHECK(hipMemcpyAsync(Cm, R, (size_t)N * M * TV * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return gemm_w_x(W, X, Cm, bias, M, K, TV, N, R ? 1 : 0, w_transposed, st);
+        STGCN_HIP_CHECK(hipMemcpyAsync(Cm, R, (size_t)p.N * p.M * p.TV * sizeof(float), hipMemcpyDeviceToDevice, st));
+    GemmArgs g = wx_gemm(p.M, p.K, p.TV, p.transposed);
+    g.A = W; g.B = X; g.C = Cm; g.bias = bias;
+    g.accumulate = R ? 1 : 0;
+    return launch_gemm_f32(g, p.N, st);
 }
 
-// dW = sum_n G[n] . X[n]^T  (G[n] (M, TV), X[n] (K, TV)): per-clip products into `part`, summed in clip order
-int gemm_wgrad(const float *G, const float *X, float *part, float *dW, int M, int K, long long TV, int N, hipStream_t st) {
+// dW = sum_n G[n] . X[n]^T  (G[n] (M, TV), X[n] (K, TV)): per-clip f32 products into `part`, summed in clip order
+GemmArgs wgrad_gemm(int M, int K, long long TV) {
     GemmArgs g{};
-    g.A = G; g.a_sm = TV; g.a_sk = 1; g.a_sb = (long long)M * TV;
-    g.B = X; g.b_sk = 1; g.b_sn = TV; g.b_sb = (long long)K * TV;
-    g.C = part; g.c_sm = K; g.c_sn = 1; g.c_sb = (long long)M * K;
+    g.a_sm = TV; g.a_sk = 1; g.a_sb = (long long)M * TV;
+    g.b_sk = 1; g.b_sn = TV; g.b_sb = (long long)K * TV;
+    g.c_sm = K; g.c_sn = 1; g.c_sb = (long long)M * K;
     g.M = M; g.N = K; g.K = (int)TV;
     g.alpha = 1.f;
+    return g;
+}
+bool wgrad_covers(int M, int K, long long TV, int N) {
+    return TV <= 0x7fffffffLL && gemm_f32_spans_fit(wgrad_gemm(M, K, TV)) && gemm_f32_grid_fits(wgrad_gemm(M, K, TV), N) &&
+           sum_parts_covers(N, (size_t)M * K);
+}
+int gemm_wgrad(const float *G, const float *X, float *part, float *dW, int M, int K, long long TV, int N, hipStream_t st) {
+    GemmArgs g = wgrad_gemm(M, K, TV);
+    g.A = G; g.B = X; g.C = part;
     int rc = launch_gemm_f32(g, N, st);
     if (rc) return rc;
     return launch_sum_parts(part, dW, N, (size_t)M * K, st);
 }
 
+bool bias_grad_covers(int M, long long TV, int N) { return row_sum_covers((long long)N * M, TV) && sum_parts_covers(N, (size_t)M); }
 int bias_grad(const float *G, float *part, float *db, int M, long long TV, int N, hipStream_t st) {
     int rc = launch_row_sum(G, part, N * M, (int)TV, st);
     if (rc) return rc;
     return launch_sum_parts(part, db, N, (size_t)M, st);
 }
 
-struct Dims {
-    int N, Cin, Cout, dk, T, V, H, dkh, dvh, Cq, CV;
-    size_t TV;
-    Dims(int N_, int Cin_, int Cout_, int dk_, int T_, int V_, int H_)
-        : N(N_), Cin(Cin_), Cout(Cout_), dk(dk_), T(T_), V(V_), H(H_) {
-        dkh = dk / H; dvh = Cout / H; Cq = 2 * dk + Cout; CV = Cin * V; TV = (size_t)T * V;
-    }
-    size_t act(int C) const { return (size_t)N * C * TV; }
-};
+// ----------------------------------------------------------------------------------------------------------------------
+// The plan of one call of the unit.  Every entry point and every query reads it: whether the pass is covered (else the
+// status and text of the refusal), the head widths, the plan of each W . X product of the pass, and the workspace.
+// ----------------------------------------------------------------------------------------------------------------------
+enum { kEval = 0, kTrain = 1, kBackward = 2 };      // `pass` of stgcn_st_attention_ws_bytes
+const char *const kEntry[3] = {"st_attention_forward", "st_attention_forward_train", "st_attention_backward"};
 
-// eval / training forward workspace (carved in 256-byte aligned pieces)
-struct FwdWs {
+struct FwdWs {      // eval / training forward (the latter writes qkv and o to the caller's save_* tensors)
     float *xn, *qkv, *o, *dscale, *dshift, *bscale, *bshift;
     double *parts, *sums;
 };
-FwdWs carve_fwd(void *base, const Dims &d, bool train, size_t *bytes) {
-    Carve c(base);
-    FwdWs w;
-    w.xn = c.take<float>(d.act(d.Cin));
-    w.qkv = train ? nullptr : c.take<float>(d.act(d.Cq));
-    w.o = train ? nullptr : c.take<float>(d.act(d.Cout));
-    w.dscale = c.take<float>(d.CV);
-    w.dshift = c.take<float>(d.CV);
-    w.bscale = c.take<float>(d.Cout);
-    w.bshift = c.take<float>(d.Cout);
-    w.parts = c.take<double>((size_t)cv_splits(d.N) * 2 * d.CV);
-    w.sums = c.take<double>((size_t)2 * (d.CV > d.Cout ? d.CV : d.Cout));
-    *bytes = c.off;
-    return w;
-}
-
 struct BwdWs {
     float *xn, *dz, *dout, *dqkv, *dxn, *part, *coef, *bscale, *bshift, *dcoef;
     double *sums, *parts;
 };
-BwdWs carve_bwd(void *base, const Dims &d, size_t *bytes) {
-    Carve c(base);
-    BwdWs w;
-    w.xn = c.take<float>(d.act(d.Cin));
-    w.dz = c.take<float>(d.act(d.Cout));
-    w.dout = c.take<float>(d.act(d.Cout));
-    w.dqkv = c.take<float>(d.act(d.Cq));
-    w.dxn = c.take<float>(d.act(d.Cin));
-    const size_t wparts = (size_t)d.N * ((size_t)d.Cout * d.Cout > (size_t)d.Cq * d.Cin ? (size_t)d.Cout * d.Cout
-                                                                                          : (size_t)d.Cq * d.Cin);
-    w.part = c.take<float>(wparts);
-    w.coef = c.take<float>((size_t)3 * d.Cout);
-    w.bscale = c.take<float>(d.Cout);
-    w.bshift = c.take<float>(d.Cout);
-    w.dcoef = c.take<float>((size_t)3 * d.CV);
-    w.sums = c.take<double>((size_t)3 * (d.CV > d.Cout ? d.CV : d.Cout));
-    w.parts = c.take<double>((size_t)cv_splits(d.N) * 2 * d.CV);
-    *bytes = c.off;
-    return w;
+
+struct StAttentionPlan {
+    bool covered = false;
+    Refusal why;
+    int pass = 0, N = 0, Cin = 0, Cout = 0, dk = 0, T = 0, V = 0, H = 0;
+    int dkh = 0, dvh = 0, Cq = 0, CV = 0;      // per-head widths, rows of Wqkv, channels of data_bn
+    size_t TV = 0;
+    bool frozen = false;
+    // forward passes: qkv = Wqkv . xn and z = Wout . o (+ x);  backward: d(xn) = Wqkv^T . dqkv and d(o) = Wout^T . dz
+    WxPlan qkv, out;
+    size_t ws_bytes = 0;                       // 0: a non-positive dimension or no such pass; else the pass's, covered or not
+
+    size_t act(int C) const { return (size_t)N * C * TV; }
+    // the workspace, carved in 256-byte aligned pieces (base NULL: sizes it)
+    FwdWs fwd_ws(void *base, size_t *bytes = nullptr) const {
+        Carve c(base);
+        FwdWs w;
+        const bool train = pass == kTrain;
+        w.xn = c.take<float>(act(Cin));
+        w.qkv = train ? nullptr : c.take<float>(act(Cq));
+        w.o = train ? nullptr : c.take<float>(act(Cout));
+        w.dscale = c.take<float>(CV);
+        w.dshift = c.take<float>(CV);
+        w.bscale = c.take<float>(Cout);
+        w.bshift = c.take<float>(Cout);
+        w.parts = c.take<double>((size_t)cv_splits(N) * 2 * CV);
+        w.sums = c.take<double>((size_t)2 * (CV > Cout ? CV : Cout));
+        if (bytes) *bytes = c.off;
+        return w;
+    }
+    BwdWs bwd_ws(void *base, size_t *bytes = nullptr) const {
+        Carve c(base);
+        BwdWs w;
+        w.xn = c.take<float>(act(Cin));
+        w.dz = c.take<float>(act(Cout));
+        w.dout = c.take<float>(act(Cout));
+        w.dqkv = c.take<float>(act(Cq));
+        w.dxn = c.take<float>(act(Cin));
+        const size_t wparts = (size_t)N * ((size_t)Cout * Cout > (size_t)Cq * Cin ? (size_t)Cout * Cout : (size_t)Cq * Cin);
+        w.part = c.take<float>(wparts);
+        w.coef = c.take<float>((size_t)3 * Cout);
+        w.bscale = c.take<float>(Cout);
+        w.bshift = c.take<float>(Cout);
+        w.dcoef = c.take<float>((size_t)3 * CV);
+        w.sums = c.take<double>((size_t)3 * (CV > Cout ? CV : Cout));
+        w.parts = c.take<double>((size_t)cv_splits(N) * 2 * CV);
+        if (bytes) *bytes = c.off;
+        return w;
+    }
+};
+
+StAttentionPlan plan_st_attention(int pass, int N, int Cin, int Cout, int dk, int T, int V, int H, unsigned flags) {
+    StAttentionPlan p;
+    p.pass = pass, p.N = N, p.Cin = Cin, p.Cout = Cout, p.dk = dk, p.T = T, p.V = V, p.H = H;
+    p.frozen = (flags & STGCN_BN_FROZEN) != 0;
+    const char *fn = kEntry[pass >= kEval && pass <= kBackward ? pass : kEval];
+    if (pass < kEval || pass > kBackward || N < 1 || Cin < 1 || Cout < 1 || dk < 1 || T < 1 || V < 1 || H < 1)
+        return say(p.why, STGCN_ERR_ARG, "%s: non-positive dimension (N=%d Cin=%d Cout=%d dk=%d T=%d V=%d heads=%d)", fn, N, Cin,
+                   Cout, dk, T, V, H), p;
+    p.dkh = dk / H, p.dvh = Cout / H, p.Cq = 2 * dk + Cout, p.CV = Cin * V, p.TV = (size_t)T * V;
+    if (pass == kBackward) p.bwd_ws(nullptr, &p.ws_bytes);
+    else p.fwd_ws(nullptr, &p.ws_bytes);
+    // the V x V part
+    if (dk % H || Cout % H || !sta_widths_covered(p.dkh, p.dvh))
+        return say(p.why, STGCN_ERR_UNSUPPORTED, "%s: Cout=%d dk=%d heads=%d give per-head widths (%d, %d); covered: (4,16), (8,32), "
+                   "(16,64)", fn, Cout, dk, H, p.dkh, p.dvh), p;
+    if (V > kVP) return say(p.why, STGCN_ERR_UNSUPPORTED, "%s: V=%d joints; the attention kernels cover V <= %d", fn, V, kVP), p;
+    if (!sta_covers(N, T, V, H))
+        return say(p.why, STGCN_ERR_UNSUPPORTED, "%s: N*T=%lld frames of %d heads exceed the grid", fn, (long long)N * T, H), p;
+    // data_bn's launches have a grid row per (clip, input channel); the unit has always held Cout to the same bound
+    if (!cv_covers(N, Cin > Cout ? Cin : Cout, T, V) || !bn_rows_fit(N, Cout))
+        return say(p.why, STGCN_ERR_UNSUPPORTED, "%s: N=%d clips of %d channels and %zu pixels exceed the grid", fn, N,
+                   Cin > Cout ? Cin : Cout, p.TV), p;
+    // the products, in the arithmetic of `flags`
+    const long long TV = (long long)p.TV;
+    const bool back = pass == kBackward;
+    p.qkv = back ? plan_wx(fn, Cin, p.Cq, TV, N, true, flags, false) : plan_wx(fn, p.Cq, Cin, TV, N, false, flags, false);
+    p.out = plan_wx(fn, Cout, Cout, TV, N, back, flags, false);
+    for (const WxPlan *x : {&p.qkv, &p.out})
+        if (x->kernel == WxPlan::none) return p.why = x->why, p;
+    // the weight and bias gradients stay on the f32 GEMM and the row sums
+    if (back && !(wgrad_covers(Cout, Cout, TV, N) && wgrad_covers(p.Cq, Cin, TV, N) && bias_grad_covers(Cout, TV, N) &&
+                  bias_grad_covers(p.Cq, TV, N)))
+        return say(p.why, STGCN_ERR_UNSUPPORTED, "%s: N=%d Cin=%d Cout=%d TV=%lld exceed the grid or 2^31 elements a clip of the "
+                   "weight gradients", fn, N, Cin, Cout, TV), p;
+    p.covered = true;
+    return p;
+}
+
+// what (Cin, Cout, dk, V, heads) and the arithmetic decide without N and T: every pass of one clip of one frame
+bool unit_covered(int Cin, int Cout, int dk, int V, int heads, unsigned flags) {
+    for (int pass = kEval; pass <= kBackward; ++pass)
+        if (!plan_st_attention(pass, 1, Cin, Cout, dk, 1, V, heads, flags & STGCN_MATH_MASK).covered) return false;
+    return true;
+}
+
+// BatchNorm2d + ReLU of both forward passes' tail
+int bn_relu(const StAttentionPlan &p, const float *z, const float *scale, const float *shift, float *y, hipStream_t st) {
+    return launch_bn_apply(z, scale, shift, nullptr, nullptr, nullptr, y, p.act(p.Cout), p.Cout, p.TV, st);
 }
 
 }  // namespace
@@ -555,50 +664,39 @@ using namespace stgcn;
 extern "C" {
 
 int stgcn_st_attention_supported(int Cin, int Cout, int dk, int V, int heads) {
-    int dkh, dvh;
-    return Cin >= 1 && V >= 1 && V <= kVP && heads_supported(Cout, dk, heads, &dkh, &dvh) ? 1 : 0;
+    return unit_covered(Cin, Cout, dk, V, heads, STGCN_MATH_F32) ? 1 : 0;
 }
 
 int stgcn_st_attention_math_supported(int Cin, int Cout, int dk, int V, int heads, unsigned flags) {
-    const unsigned m = flags & STGCN_MATH_MASK;
-    return (m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3) && stgcn_st_attention_supported(Cin, Cout, dk, V, heads) ? 1 : 0;
+    return unit_covered(Cin, Cout, dk, V, heads, flags) ? 1 : 0;
+}
+
+size_t stgcn_st_attention_ws_bytes(int N, int Cin, int Cout, int dk, int T, int V, int heads, int pass) {
+    return plan_st_attention(pass, N, Cin, Cout, dk, T, V, heads, STGCN_MATH_F32).ws_bytes;     // (the same in both arithmetics)
 }
 
 int stgcn_wx_product_supported(int M, int K, long long TV, unsigned flags) {
-    const unsigned m = flags & STGCN_MATH_MASK;
-    return (m == STGCN_MATH_F32 || m == STGCN_MATH_BF16X3) && wx_covers(M, K, TV) ? 1 : 0;
+    return plan_wx("wx_product", M, K, TV, 1, false, flags, true).kernel != WxPlan::none ? 1 : 0;
 }
 
 const char *stgcn_wx_product_kernel_name(int M, int K, long long TV, unsigned flags) {
-    if (!stgcn_wx_product_supported(M, K, TV, flags)) return "";
-    return (flags & STGCN_MATH_MASK) == STGCN_MATH_BF16X3 ? wx_bf16x3_kernel_name(M) : "gemm_f32_kernel";
+    const WxPlan p = plan_wx("wx_product", M, K, TV, 1, false, flags, true);
+    return p.kernel == WxPlan::bf16x3 ? wx_bf16x3_kernel_name(M) : p.kernel == WxPlan::gemm_f32 ? "gemm_f32_kernel" : "";
 }
 
 size_t stgcn_wx_product_ws_bytes(int M, int K, unsigned flags) {
     (void)M; (void)K; (void)flags;
-    return 0;        // both arithmetics split or read their operands in place
+    return 0;        // both kernels of plan_wx split or read their operands in place
 }
 
 int stgcn_wx_product(const float *W, const float *X, const float *bias, const float *R, float *C, void *ws, size_t ws_bytes,
                      int N, int M, int K, long long TV, int w_transposed, unsigned flags, void *stream) {
     REQUIRE_PTR(W); REQUIRE_PTR(X); REQUIRE_PTR(C);
     (void)ws; (void)ws_bytes;
-    if (N < 1 || M < 1 || K < 1 || TV < 1)
-        return fail(STGCN_ERR_ARG, "wx_product: non-positive dimension (N=%d M=%d K=%d TV=%lld)", N, M, K, TV);
     if (R == C) return fail(STGCN_ERR_ARG, "wx_product: R may not be C");
-    if (int rc = check_math("wx_product", flags)) return rc;
-    if (!wx_covers(M, K, TV) || N > 65535)
-        return fail(STGCN_ERR_UNSUPPORTED, "wx_product: N=%d M=%d K=%d TV=%lld exceed the grid or 2^31 elements a clip", N, M, K, TV);
-    return w_x(flags, W, X, C, bias, R, M, K, TV, N, w_transposed != 0, (hipStream_t)stream);
-}
-
-size_t stgcn_st_attention_ws_bytes(int N, int Cin, int Cout, int dk, int T, int V, int heads, int pass) {
-    if (N < 1 || Cin < 1 || Cout < 1 || dk < 1 || T < 1 || V < 1 || heads < 1 || pass < 0 || pass > 2) return 0;
-    const Dims d(N, Cin, Cout, dk, T, V, heads);
-    size_t bytes = 0;
-    if (pass == 2) carve_bwd(nullptr, d, &bytes);
-    else carve_fwd(nullptr, d, pass == 1, &bytes);
-    return bytes;
+    const WxPlan p = plan_wx("wx_product", M, K, TV, N, w_transposed != 0, flags, true);
+    if (p.kernel == WxPlan::none) return refused(p.why);
+    return launch_wx(p, W, X, C, bias, R, (hipStream_t)stream);
 }
 
 int stgcn_st_attention_forward_math(const float *x, const float *dbn_scale, const float *dbn_shift, const float *Wqkv,
@@ -608,19 +706,17 @@ int stgcn_st_attention_forward_math(const float *x, const float *dbn_scale, cons
     REQUIRE_PTR(x); REQUIRE_PTR(dbn_scale); REQUIRE_PTR(dbn_shift); REQUIRE_PTR(Wqkv); REQUIRE_PTR(bqkv);
     REQUIRE_PTR(Wout); REQUIRE_PTR(bout); REQUIRE_PTR(bn_scale); REQUIRE_PTR(bn_shift); REQUIRE_PTR(ws); REQUIRE_PTR(y);
     REQUIRE_ALIGNED(ws, kBlobAlign);
-    if (int rc = check_shape("st_attention_forward", N, Cin, Cout, dk, T, V, heads)) return rc;
-    if (int rc = check_math("st_attention_forward", flags)) return rc;
+    const StAttentionPlan p = plan_st_attention(kEval, N, Cin, Cout, dk, T, V, heads, flags);
+    if (!p.covered) return refused(p.why);
+    if (ws_bytes < p.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "st_attention_forward: workspace %zu < %zu bytes", ws_bytes, p.ws_bytes);
+    const FwdWs w = p.fwd_ws(ws);
     hipStream_t st = (hipStream_t)stream;
-    const Dims d(N, Cin, Cout, dk, T, V, heads);
-    size_t need = 0;
-    const FwdWs w = carve_fwd(ws, d, false, &need);
-    if (ws_bytes < need) return fail(STGCN_ERR_WORKSPACE, "st_attention_forward: workspace %zu < %zu bytes", ws_bytes, need);
     int rc;
     if ((rc = launch_cv_apply(x, dbn_scale, dbn_shift, w.xn, N, Cin, T, V, st))) return rc;
-    if ((rc = w_x(flags, Wqkv, w.xn, w.qkv, bqkv, nullptr, d.Cq, Cin, d.TV, N, false, st))) return rc;
-    if ((rc = launch_sta_fwd(w.qkv, nullptr, w.o, nullptr, N, T, V, heads, d.dkh, d.dvh, st))) return rc;
-    if ((rc = w_x(flags, Wout, w.o, y, bout, Cin == Cout ? x : nullptr, Cout, Cout, d.TV, N, false, st))) return rc;
-    return launch_bn_apply(y, bn_scale, bn_shift, nullptr, nullptr, nullptr, y, d.act(Cout), Cout, d.TV, st);
+    if ((rc = launch_wx(p.qkv, Wqkv, w.xn, w.qkv, bqkv, nullptr, st))) return rc;
+    if ((rc = launch_sta_fwd(w.qkv, nullptr, w.o, nullptr, N, T, V, heads, p.dkh, p.dvh, st))) return rc;
+    if ((rc = launch_wx(p.out, Wout, w.o, y, bout, Cin == Cout ? x : nullptr, st))) return rc;
+    return bn_relu(p, y, bn_scale, bn_shift, y, st);
 }
 
 int stgcn_st_attention_forward(const float *x, const float *dbn_scale, const float *dbn_shift, const float *Wqkv,
@@ -644,43 +740,40 @@ int stgcn_st_attention_forward_train(const float *x, const float *dbn_weight, co
     REQUIRE_PTR(ws); REQUIRE_PTR(y); REQUIRE_PTR(save_qkv); REQUIRE_PTR(save_o); REQUIRE_PTR(save_z);
     REQUIRE_PTR(save_rowstats); REQUIRE_PTR(save_stats);
     REQUIRE_ALIGNED(ws, kBlobAlign);     // fp64 atomic sums
-    if (int rc = check_shape("st_attention_forward_train", N, Cin, Cout, dk, T, V, heads)) return rc;
-    if (int rc = check_math("st_attention_forward_train", flags)) return rc;
+    const StAttentionPlan p = plan_st_attention(kTrain, N, Cin, Cout, dk, T, V, heads, flags);
+    if (!p.covered) return refused(p.why);      // before the first launch: nothing is written, the running statistics included
+    if (ws_bytes < p.ws_bytes)
+        return fail(STGCN_ERR_WORKSPACE, "st_attention_forward_train: workspace %zu < %zu bytes", ws_bytes, p.ws_bytes);
+    const FwdWs w = p.fwd_ws(ws);
     hipStream_t st = (hipStream_t)stream;
-    const Dims d(N, Cin, Cout, dk, T, V, heads);
-    size_t need = 0;
-    const FwdWs w = carve_fwd(ws, d, true, &need);
-    if (ws_bytes < need)
-        return fail(STGCN_ERR_WORKSPACE, "st_attention_forward_train: workspace %zu < %zu bytes", ws_bytes, need);
-    const bool frozen = (flags & STGCN_BN_FROZEN) != 0;
-    float *dmean = save_stats, *dinv = save_stats + d.CV, *bmean = save_stats + 2 * d.CV, *binv = bmean + Cout;
+    float *dmean = save_stats, *dinv = save_stats + p.CV, *bmean = save_stats + 2 * p.CV, *binv = bmean + Cout;
     int rc;
     // data_bn
-    if (frozen) {
-        rc = launch_bn_frozen_finalize(dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, eps, w.dscale, w.dshift, d.CV,
+    if (p.frozen) {
+        rc = launch_bn_frozen_finalize(dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, eps, w.dscale, w.dshift, p.CV,
                                        st, dmean, dinv);
     } else {
         if ((rc = launch_cv_stats(x, nullptr, nullptr, nullptr, w.parts, w.sums, N, Cin, T, V, st))) return rc;
         rc = launch_bn_train_finalize(w.sums, (double)N * T, dbn_weight, dbn_bias, dbn_running_mean, dbn_running_var, momentum,
-                                      eps, w.dscale, w.dshift, d.CV, st, dmean, dinv);
+                                      eps, w.dscale, w.dshift, p.CV, st, dmean, dinv);
     }
     if (rc) return rc;
     if ((rc = launch_cv_apply(x, w.dscale, w.dshift, w.xn, N, Cin, T, V, st))) return rc;
     // attention
-    if ((rc = w_x(flags, Wqkv, w.xn, save_qkv, bqkv, nullptr, d.Cq, Cin, d.TV, N, false, st))) return rc;
-    if ((rc = launch_sta_fwd(save_qkv, mask, save_o, save_rowstats, N, T, V, heads, d.dkh, d.dvh, st))) return rc;
-    if ((rc = w_x(flags, Wout, save_o, save_z, bout, Cin == Cout ? x : nullptr, Cout, Cout, d.TV, N, false, st))) return rc;
+    if ((rc = launch_wx(p.qkv, Wqkv, w.xn, save_qkv, bqkv, nullptr, st))) return rc;
+    if ((rc = launch_sta_fwd(save_qkv, mask, save_o, save_rowstats, N, T, V, heads, p.dkh, p.dvh, st))) return rc;
+    if ((rc = launch_wx(p.out, Wout, save_o, save_z, bout, Cin == Cout ? x : nullptr, st))) return rc;
     // BatchNorm2d + ReLU
-    if (frozen) {
+    if (p.frozen) {
         rc = launch_bn_frozen_finalize(bn_weight, bn_bias, bn_running_mean, bn_running_var, eps, w.bscale, w.bshift, Cout, st,
                                        bmean, binv);
     } else {
-        if ((rc = launch_bn_batch_stats(save_z, w.sums, N, Cout, d.TV, st))) return rc;
-        rc = launch_bn_train_finalize(w.sums, (double)N * d.TV, bn_weight, bn_bias, bn_running_mean, bn_running_var, momentum,
+        if ((rc = launch_bn_batch_stats(save_z, w.sums, N, Cout, p.TV, st))) return rc;
+        rc = launch_bn_train_finalize(w.sums, (double)N * p.TV, bn_weight, bn_bias, bn_running_mean, bn_running_var, momentum,
                                       eps, w.bscale, w.bshift, Cout, st, bmean, binv);
     }
     if (rc) return rc;
-    return launch_bn_apply(save_z, w.bscale, w.bshift, nullptr, nullptr, nullptr, y, d.act(Cout), Cout, d.TV, st);
+    return bn_relu(p, save_z, w.bscale, w.bshift, y, st);
 }
 
 int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const float *dbn_bias, const float *Wqkv,
@@ -696,50 +789,40 @@ int stgcn_st_attention_backward(const float *x, const float *dbn_weight, const f
     REQUIRE_PTR(dWqkv); REQUIRE_PTR(dbqkv); REQUIRE_PTR(dWout); REQUIRE_PTR(dbout); REQUIRE_PTR(dbn_weight_grad);
     REQUIRE_PTR(dbn_bias_grad); REQUIRE_PTR(ws);
     REQUIRE_ALIGNED(ws, kBlobAlign);
-    if (int rc = check_shape("st_attention_backward", N, Cin, Cout, dk, T, V, heads)) return rc;
-    if (int rc = check_math("st_attention_backward", flags)) return rc;
+    const StAttentionPlan p = plan_st_attention(kBackward, N, Cin, Cout, dk, T, V, heads, flags);
+    if (!p.covered) return refused(p.why);
+    if (ws_bytes < p.ws_bytes) return fail(STGCN_ERR_WORKSPACE, "st_attention_backward: workspace %zu < %zu bytes", ws_bytes, p.ws_bytes);
+    const BwdWs w = p.bwd_ws(ws);
     hipStream_t st = (hipStream_t)stream;
-    const Dims d(N, Cin, Cout, dk, T, V, heads);
-    size_t need = 0;
-    const BwdWs w = carve_bwd(ws, d, &need);
-    if (ws_bytes < need) return fail(STGCN_ERR_WORKSPACE, "st_attention_backward: workspace %zu < %zu bytes", ws_bytes, need);
-    const bool frozen = (flags & STGCN_BN_FROZEN) != 0;
-    const float *dmean = save_stats, *dinv = save_stats + d.CV, *bmean = save_stats + 2 * d.CV, *binv = bmean + Cout;
+    const float *dmean = save_stats, *dinv = save_stats + p.CV, *bmean = save_stats + 2 * p.CV, *binv = bmean + Cout;
     int rc;
     // BatchNorm2d + ReLU -> dz
     if ((rc = launch_bn_scale_shift(bn_weight, bn_bias, bmean, binv, w.bscale, w.bshift, Cout, st))) return rc;
     if ((rc = launch_bn_relu_bwd_stats(save_z, w.bscale, w.bshift, bmean, binv, nullptr, nullptr, nullptr, nullptr, nullptr, dy,
-                                       w.sums, N, Cout, d.TV, st))) return rc;
-    if ((rc = launch_bn_bwd_finalize(w.sums, 1, (double)N * d.TV, bn_weight, binv, dbn_weight_grad, dbn_bias_grad, w.coef, Cout,
-                                     st, frozen))) return rc;
+                                       w.sums, N, Cout, p.TV, st))) return rc;
+    if ((rc = launch_bn_bwd_finalize(w.sums, 1, (double)N * p.TV, bn_weight, binv, dbn_weight_grad, dbn_bias_grad, w.coef, Cout,
+                                     st, p.frozen))) return rc;
     if ((rc = launch_bn_relu_bwd_apply(save_z, w.bscale, w.bshift, bmean, binv, nullptr, nullptr, nullptr, nullptr, nullptr, dy,
-                                       w.coef, nullptr, w.dz, nullptr, nullptr, N, Cout, d.TV, st))) return rc;
+                                       w.coef, nullptr, w.dz, nullptr, nullptr, N, Cout, p.TV, st))) return rc;
     // output projection
-    if ((rc = gemm_wgrad(w.dz, save_o, w.part, dWout, Cout, Cout, d.TV, N, st))) return rc;
-    if ((rc = bias_grad(w.dz, w.part, dbout, Cout, d.TV, N, st))) return rc;
-    if ((rc = w_x(flags, Wout, w.dz, w.dout, nullptr, nullptr, Cout, Cout, d.TV, N, true, st))) return rc;
+    if ((rc = gemm_wgrad(w.dz, save_o, w.part, dWout, Cout, Cout, p.TV, N, st))) return rc;
+    if ((rc = bias_grad(w.dz, w.part, dbout, Cout, p.TV, N, st))) return rc;
+    if ((rc = launch_wx(p.out, Wout, w.dz, w.dout, nullptr, nullptr, st))) return rc;
     // attention
-    if ((rc = launch_sta_bwd(save_qkv, w.dout, mask, save_rowstats, w.dqkv, N, T, V, heads, d.dkh, d.dvh, st))) return rc;
+    if ((rc = launch_sta_bwd(save_qkv, w.dout, mask, save_rowstats, w.dqkv, N, T, V, heads, p.dkh, p.dvh, st))) return rc;
     // qkv projection (on data_bn's output, rebuilt from x and the saved statistics)
-    if ((rc = launch_bn_scale_shift(dbn_weight, dbn_bias, dmean, dinv, w.dcoef, w.dcoef + d.CV, d.CV, st))) return rc;
-    if ((rc = launch_cv_apply(x, w.dcoef, w.dcoef + d.CV, w.xn, N, Cin, T, V, st))) return rc;
-    if ((rc = gemm_wgrad(w.dqkv, w.xn, w.part, dWqkv, d.Cq, Cin, d.TV, N, st))) return rc;
-    if ((rc = bias_grad(w.dqkv, w.part, dbqkv, d.Cq, d.TV, N, st))) return rc;
-    if (dx == nullptr) {         // no input gradient: data_bn's parameter gradients still need d(xn)
-        if ((rc = w_x(flags, Wqkv, w.dqkv, w.dxn, nullptr, nullptr, Cin, d.Cq, d.TV, N, true, st))) return rc;
-        if ((rc = launch_cv_stats(x, w.dxn, dmean, dinv, w.parts, w.sums, N, Cin, T, V, st))) return rc;
-        return launch_bn_bwd_finalize(w.sums, 1, (double)N * T, dbn_weight, dinv, ddbn_weight, ddbn_bias, w.dcoef, d.CV, st,
-                                      frozen);
-    }
-    if ((rc = w_x(flags, Wqkv, w.dqkv, w.dxn, nullptr, nullptr, Cin, d.Cq, d.TV, N, true, st))) return rc;
-    // data_bn backward (+ the skip connection's dz)
+    if ((rc = launch_bn_scale_shift(dbn_weight, dbn_bias, dmean, dinv, w.dcoef, w.dcoef + p.CV, p.CV, st))) return rc;
+    if ((rc = launch_cv_apply(x, w.dcoef, w.dcoef + p.CV, w.xn, N, Cin, T, V, st))) return rc;
+    if ((rc = gemm_wgrad(w.dqkv, w.xn, w.part, dWqkv, p.Cq, Cin, p.TV, N, st))) return rc;
+    if ((rc = bias_grad(w.dqkv, w.part, dbqkv, p.Cq, p.TV, N, st))) return rc;
+    if ((rc = launch_wx(p.qkv, Wqkv, w.dqkv, w.dxn, nullptr, nullptr, st))) return rc;
+    // data_bn backward: its parameter gradients need d(xn) whether or not x wants a gradient ...
     if ((rc = launch_cv_stats(x, w.dxn, dmean, dinv, w.parts, w.sums, N, Cin, T, V, st))) return rc;
-    if ((rc = launch_bn_bwd_finalize(w.sums, 1, (double)N * T, dbn_weight, dinv, ddbn_weight, ddbn_bias, w.dcoef, d.CV, st,
-                                     frozen))) return rc;
-    hipLaunchKernelGGL(cv_bwd_apply_kernel, dim3(N * Cin, ceil_div(T * V, 256)), dim3(256), 0, st, w.dxn, x, dmean, dinv,
-                       w.dcoef, Cin == Cout ? w.dz : nullptr, dx, Cin, T, V);
-    STGCN_LAUNCH_CHECK("cv_bwd_apply_kernel");
-    return STGCN_OK;
+    if ((rc = launch_bn_bwd_finalize(w.sums, 1, (double)N * T, dbn_weight, dinv, ddbn_weight, ddbn_bias, w.dcoef, p.CV, st,
+                                     p.frozen))) return rc;
+    if (dx == nullptr) return STGCN_OK;
+    // ... dx (+ the skip connection's dz)
+    return launch_cv_bwd_apply(w.dxn, x, dmean, dinv, w.dcoef, Cin == Cout ? w.dz : nullptr, dx, N, Cin, T, V, st);
 }
 
 }  // extern "C"

@@ -550,6 +550,7 @@ inline WgradPlan plan_wgrad(int N, int Cin, int Cout, int T, int V, int K, int s
 int launch_bn_relu_bwd_stats(const float *za, const float *sa, const float *ta, const float *ma, const float *ia,
                              const float *zb, const float *sb, const float *tb, const float *mb, const float *ib,
                              const float *dy, double *sums, int N, int C, size_t plane, hipStream_t st) {
+    if (!bn_rows_fit(N, C)) return fail(STGCN_ERR_UNSUPPORTED, "BatchNorm backward statistics: N=%d C=%d exceed the grid", N, C);
     STGCN_HIP_CHECK(hipMemsetAsync(sums, 0, sizeof(double) * 3 * C, st));
     const BnSide a{za, sa, ta, ma, ia}, b{zb, sb, tb, mb, ib};
     hipLaunchKernelGGL(bn_relu_bwd_stats_kernel, dim3(bn_chunks(N, plane, C), C), dim3(256), 0, st, a, b, dy, sums, N,
@@ -571,6 +572,7 @@ int launch_bn_relu_bwd_apply(const float *za, const float *sa, const float *ta, 
                              const float *zb, const float *sb, const float *tb, const float *mb, const float *ib,
                              const float *dy, const float *coefa, const float *coefb, float *dza, float *dzb, double *bsum,
                              int N, int C, size_t plane, hipStream_t st, float *gout) {
+    if (!bn_rows_fit(N, C)) return fail(STGCN_ERR_UNSUPPORTED, "BatchNorm backward: N=%d C=%d exceed the grid", N, C);
     if (bsum) STGCN_HIP_CHECK(hipMemsetAsync(bsum, 0, sizeof(double) * 2 * C, st));
     const BnSide a{za, sa, ta, ma, ia}, b{zb, sb, tb, mb, ib};
     hipLaunchKernelGGL(bn_relu_bwd_apply_kernel, dim3(bn_chunks(N, plane, C), C), dim3(256), 0, st, a, b, dy, coefa,

@@ -205,13 +205,15 @@ const char *wx_bf16x3_kernel_name(int M) {
     return wx_bf16x3_tile_rows(M) == 64 ? "wx_bf16x3_kernel<64x128>" : "wx_bf16x3_kernel<128x128>";
 }
 
-bool wx_bf16x3_covers(int M, int K, long long TV) {      // (the kernel's offsets inside W and inside 32 rows of X are 32-bit)
-    return M >= 1 && K >= 1 && TV >= 1 && (TV + kBN - 1) / kBN <= 65535 && (long long)(M + 128) * (K + 32) < (1LL << 29);
+// the kernel's offsets inside W and inside 32 rows of X are 32-bit; column tiles and clips ride on 16-bit grid axes
+bool wx_bf16x3_covers(int M, int K, long long TV, int N) {
+    return M >= 1 && K >= 1 && TV >= 1 && (TV + kBN - 1) / kBN <= 65535 && (long long)(M + 128) * (K + 32) < (1LL << 29) && N >= 1 &&
+           N <= 65535;
 }
 
 int launch_wx_bf16x3(const float *W, const float *X, const float *bias, const float *R, float *C, int N, int M, int K,
                      long long TV, bool w_transposed, hipStream_t st) {
-    if (!wx_bf16x3_covers(M, K, TV) || N < 1 || N > 65535)
+    if (!wx_bf16x3_covers(M, K, TV, N))
         return fail(STGCN_ERR_UNSUPPORTED, "wx_bf16x3: M=%d K=%d TV=%lld N=%d exceed the grid", M, K, TV, N);
     const int BM = wx_bf16x3_tile_rows(M);
     const dim3 grid((unsigned)ceil_div(M, BM), (unsigned)((TV + kBN - 1) / kBN), (unsigned)N);   // row tiles of one X tile run together
