@@ -21,6 +21,10 @@
  *     state and never synchronises: all work is enqueued on `stream` (a hipStream_t
  *     passed as void*; NULL = the default stream).  Safe to call from several host
  *     threads / devices concurrently (the caller selects the device, as PyTorch does).
+ *   - Streams.  Everything a call does - every kernel, memset and copy - is ordered on `stream` and on
+ *     nothing else, and no call waits on the host: a call may be enqueued behind work that has not
+ *     run yet, its inputs may be written by that work, and every entry point may be captured into a
+ *     graph and replayed under new inputs (tests/test_stream_order_gpu.py; DESIGN.md section 4, "Streams").
  *   - Tensors are dense row-major fp32 unless stated: x is (N, C, T, V) exactly as
  *     unit_agcn.forward receives it.
  *   - Return value: 0 on success, a negative stgcn_status otherwise; the message for the

@@ -1,6 +1,7 @@
 """How the tests set up the HIP entry points: seeded modules, inputs and fp64 restatements, in one place.  The case tables of
-the two library-wide contracts - buffer discipline (tests/test_buffer_discipline_gpu.py) and non-finite inputs
-(tests/nonfinite_cases.py) - build their rows from the setups below, the other test files borrow the helpers.  A plain module:
+the library-wide contracts - buffer discipline (tests/test_buffer_discipline_gpu.py), non-finite inputs
+(tests/nonfinite_cases.py) and streams (tests/stream_order.py) - build their rows from the setups below, the other test files
+borrow the helpers.  A plain module:
 it imports no test module, and needs a GPU only where a function takes a device.
 
 A ``Setup`` is made on the CPU from seeds: ``x`` is the clean fp32 input, ``reference(x)`` the fp64 restatement the entry
@@ -563,3 +564,313 @@ def small_head(dev, cls_name="ST", **kw):
                 p.copy_(0.05 * torch.randn(p.shape))
     set_hip_min_tokens(head, 0)
     return head.to(dev).eval()
+
+
+# ---- entry points the non-finite table predates (the stream contract's rows, tests/stream_order.py) -----------------------------
+# Backward entry points take their cotangent as ``x`` where every output is linear in it: a stale cotangent then moves them all.
+def vit_patch_embed(name, layout, math):
+    """F.vit_patch_embed on an embedding case of stvit_ref, from (N,C,T,V) or channels-last memory."""
+    import stvit_ref as sr
+    N, C, T, V, p1, p2, E = sr.EMBED_CASES[name]
+    z, W, bias, cls, pos = sr.embed_case(name)
+
+    def reference(z):
+        return {"x": sr.embed64(z.double(), W, bias, cls, pos, p1, p2)}
+
+    def on(dev):
+        F = hipF()
+        Wd, bd, cd, pd = (t.to(dev) for t in (W, bias, cls, pos))
+
+        def run(z):
+            zd = z.to(dev)
+            if layout == "ntvc":
+                zd = zd.contiguous(memory_format=torch.channels_last)
+            assert F._is_channels_last(zd) == (layout == "ntvc")
+            return {"x": F.vit_patch_embed(zd, Wd, bd, cd, pd, p1, p2, math_flag(math))}
+        return run
+    return Setup(z, reference, on)
+
+
+def vit_patch_embed_backward(name, layout, math):
+    """F.vit_patch_embed_backward on an embedding case; ``x`` is dx, the gradient of the embedding's output."""
+    import stvit_ends_ref as er
+    import stvit_ref as sr
+    N, C, T, V, p1, p2, E = sr.EMBED_CASES[name]
+    z, W, bias, cls, pos = sr.embed_case(name)
+
+    def reference(dx):
+        return er.embed_grads64(z, W, bias, cls, pos, p1, p2, dx)
+
+    def on(dev):
+        F = hipF()
+        zd, Wd = z.to(dev), W.to(dev)
+        if layout == "ntvc":
+            zd = zd.contiguous(memory_format=torch.channels_last)
+        return lambda dx: F.vit_patch_embed_backward(zd, Wd, dx.to(dev), p1, p2, math_flag(math))
+    return Setup(er.make_dx(name), reference, on)
+
+
+def vit_pool_classify_backward(name, mode):
+    """F.vit_pool_classify_backward on a classifier case of stvit_ends_ref ('cls' | 'mean')."""
+    import stvit_ends_ref as er
+    import stvit_ref as sr
+    x, ln_w, ln_b, W, bias, dlogits = er.classify_case(name)
+
+    def reference(x):
+        return er.classify_grads64(x, ln_w, ln_b, W, bias, dlogits, mode)[1]
+
+    def on(dev):
+        F = hipF()
+        lw, lb, Wd, dl = (t.to(dev) for t in (ln_w, ln_b, W, dlogits))
+        return lambda x: F.vit_pool_classify_backward(x.to(dev), lw, lb, sr.LN_EPS, Wd, dl, mode=mode)
+    return Setup(x, reference, on)
+
+
+def vit_block_train_drop(name, mode):
+    """The dropout pair (vit_block_forward_train / vit_block_backward with ``drop``) on a layer case of stvit_train_ref."""
+    import stvit_train_ref as vr
+    B, L, D, heads, hidden = vr.CASES[name]
+    x, dy, sd, masks = vr.make_case(name)
+    scale = (D // heads) ** -0.5
+
+    def reference(x):
+        y, g = vr.grads64(x, sd, dy, masks, None, None, heads, scale)
+        return {"y": y, **{"d" + k: v for k, v in g.items()}}
+
+    def on(dev):
+        from stgcn_amd.altformer import HEAD_TRAIN_MATH
+        F = hipF()
+        ps = [None if sd.get(k) is None else sd[k].to(dev) for k in tr.PARAMS]
+        md, dyd = tuple(m.to(dev) for m in masks), dy.to(dev)
+        args = (heads, 1e-5, scale, HEAD_TRAIN_MATH[mode], None, None)
+
+        def run(x):
+            xd = x.to(dev)
+            y, saved = F.vit_block_forward_train(xd, ps, *args, drop=md)
+            g = F.vit_block_backward(xd, ps, saved, dyd, *args, drop=md)
+            return {"y": y, "dx": g["x"], **{"d" + k: g[n] for k, n in zip(tr.PARAMS, F.VIT_BLOCK_PARAMS) if g[n] is not None}}
+        return run
+    return Setup(x, reference, on)
+
+
+def vit_block_train_small(B, L, D, mode):
+    """The ``_drop`` pair under VIT_WGRAD_SMALL | VIT_TILE_AUTO with stochastic-depth factors and no masks
+    (test_row_factors_with_a_dropped_sequence); ``plans(F)``: the weight-gradient plans of the D x D and the qkv product."""
+    hidden, heads = 2 * D, ar.HEADS
+    x, sd = block_inputs(B, L, D, hidden)
+    dy = torch.randn(B, L, D, generator=torch.Generator().manual_seed(L + D + 21))
+    s1, s2 = tr.make_scales(B, 9300 + L)
+    scale = (D // heads) ** -0.5
+
+    def reference(x):
+        y, g = tr.grads64(x, sd, dy, scale=scale, s1=s1, s2=s2)
+        return {"y": y, **{"d" + k: v for k, v in g.items()}}
+
+    def plans(F):
+        from stgcn_amd import _capi
+        return F.vit_wgrad_plan(B * L, D, D, _capi.VIT_WGRAD_SMALL), F.vit_wgrad_plan(B * L, D, 3 * D, _capi.VIT_WGRAD_SMALL)
+
+    def on(dev):
+        from stgcn_amd import _capi
+        from stgcn_amd.altformer import HEAD_TRAIN_MATH
+        F = hipF()
+        ps = [sd[k].to(dev) for k in tr.PARAMS]
+        dyd, s1d, s2d = dy.to(dev), s1.to(dev), s2.to(dev)
+        args = (heads, ar.EPS, scale, HEAD_TRAIN_MATH[mode] | _capi.VIT_TILE_AUTO | _capi.VIT_WGRAD_SMALL, s1d, s2d)
+
+        def run(x):
+            xd = x.to(dev)
+            y, saved = F.vit_block_forward_train(xd, ps, *args, drop=(None, None, None))
+            g = F.vit_block_backward(xd, ps, saved, dyd, *args, drop=(None, None, None))
+            return {"y": y, "dx": g["x"], **{"d" + k: g[n] for k, n in zip(tr.PARAMS, F.VIT_BLOCK_PARAMS)}}
+        return run
+    return Setup(x, reference, on, plans=plans)
+
+
+def st_attention_math(name, math="bf16x3"):
+    """gcn_unit_attention under set_st_attention_math on a unit case of st_attention_math_ref without a drop-connect mask: the eval
+    forward ("eval" cases: {"y"}) or one training step ("train" cases: y, dx, every parameter gradient, the running statistics).
+    The state is loaded from device copies: nothing in ``run`` comes from the host."""
+    import st_attention_math_ref as MR
+    c, sd, x, dy, mask, _ = MR.unit_reference(name)
+    assert mask is None, "a recorded drop-connect mask is uploaded inside the step"
+    training = c["mode"] == "train"
+    sd64 = {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+
+    def reference(x):
+        if not training:
+            with torch.no_grad():
+                return {"y": R.forward64(sd64, x.double(), False)[0]}
+        yr, new, g, dx = R.grads64(sd, x, dy, training=True, mask=None)
+        return {"y": yr, "dx": dx, **{"d" + k: v for k, v in g.items()}, **new}
+
+    def on(dev):
+        from stgcn_amd import set_st_attention_math
+        m = st_unit(c["cin"], c["cout"], c["V"], sd, drop_connect=False).train(training)
+        set_st_attention_math(m, math)
+        sdd, dyd = {k: v.to(dev) for k, v in sd.items()}, dy.to(dev)
+
+        def run(x):
+            if not training:
+                with torch.no_grad():
+                    return {"y": m(x.to(dev))}
+            m.load_state_dict(sdd)
+            for p in m.parameters():
+                p.grad = None
+            xg = x.to(dev).detach().clone().requires_grad_(True)
+            y = m(xg)
+            y.backward(dyd)
+            return {"y": y.detach(), "dx": xg.grad, **{"d" + k: p.grad for k, p in m.named_parameters()},
+                    **{k: v.clone() for k, v in m.state_dict().items() if k.endswith(("running_mean", "running_var"))}}
+        return run
+    return Setup(x, reference, on)
+
+
+def wx_product(name, math="bf16x3"):
+    """F.wx_product on a product case of st_attention_math_ref; ``x`` is X (N, K, TV)."""
+    import st_attention_math_ref as MR
+    ref = MR.product_reference(name)
+    c = ref["case"]
+
+    def reference(X):
+        out = ref["Wmk"].double() @ X.double()
+        for add in (None if ref["bias"] is None else ref["bias"].view(1, -1, 1), ref["R"]):
+            out = out if add is None else out + add.double()
+        return {"C": out}
+
+    def on(dev):
+        F = hipF()
+        up = lambda t: None if t is None else t.to(dev)       # noqa: E731
+        W, bias, Rr = up(ref["W"]), up(ref["bias"]), up(ref["R"])
+        return lambda X: {"C": F.wx_product(W, X.to(dev), bias, Rr, w_transposed=c["wt"], math=math_flag(math))}
+    return Setup(ref["X"], reference, on)
+
+
+def vit_linear_backward(M, K, Nout, math):
+    """F.vit_linear_backward with GELU' and every output; ``x`` is dy (M, Nout)."""
+    g = torch.Generator().manual_seed(M + K + Nout + 1)
+    dy = torch.randn(M, Nout, generator=g) * (0.25 + 3.75 * torch.rand(M, 1, generator=g))
+    a = torch.randn(M, K, generator=g) + 0.5
+    W = (torch.rand(Nout, K, generator=g) * 2 - 1) / K ** 0.5
+    h = torch.randn(M, K, generator=g) * 1.5
+    h64 = h.double().requires_grad_(True)
+    TF.gelu(h64).sum().backward()
+
+    def reference(dy):
+        return {"dx": dy.double() @ W.double() * h64.grad, "dW": dy.double().T @ a.double(), "db": dy.double().sum(0)}
+
+    def on(dev):
+        F = hipF()
+        ad, Wd, hd = a.to(dev), W.to(dev), h.to(dev)
+        assert F.vit_linear_backward_supported(M, K, Nout, math_flag(math))
+        return lambda dy: dict(zip(("dx", "dW", "db"), F.vit_linear_backward(dy.to(dev), ad, Wd, h_pre=hd, math=math_flag(math))))
+    return Setup(dy, reference, on)
+
+
+def vit_layernorm_backward(M, D):
+    """F.vit_layernorm_backward with and without the residual gradient, against autograd of ar.layer_norm64; ``x`` is dn, the
+    gradient of the LayerNorm's output.  ``operands``: (x, w, b, dres) on the CPU."""
+    g = torch.Generator().manual_seed(D)
+    x = torch.randn(M, D, generator=g) * (0.25 + 3.75 * torch.rand(M, 1, generator=g)) + torch.randn(M, 1, generator=g)
+    w, b = 1 + 0.2 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g)
+    dn, dres = torch.randn(M, D, generator=g), torch.randn(M, D, generator=g)
+
+    def reference(dn):
+        x64, w64, b64 = (t.double().requires_grad_(True) for t in (x, w, b))
+        ar.layer_norm64(x64, w64, b64).backward(dn.double())
+        out = {}
+        for res in (False, True):
+            out[f"dx[dres={res}]"] = x64.grad + (dres.double() if res else 0)
+            out[f"dweight[dres={res}]"], out[f"dbias[dres={res}]"] = w64.grad, b64.grad
+        return out
+
+    def on(dev):
+        F = hipF()
+        xd, wd, dresd = (t.to(dev) for t in (x, w, dres))
+
+        def run(dn):
+            out, dnd = {}, dn.to(dev)
+            for res in (False, True):
+                out[f"dx[dres={res}]"], out[f"dweight[dres={res}]"], out[f"dbias[dres={res}]"] = \
+                    F.vit_layernorm_backward(xd, dnd, wd, ar.EPS, dres=dresd if res else None)
+            return out
+        return run
+    return Setup(dn, reference, on)
+
+
+def vit_attention_backward(B, L, hd, form="resident"):
+    """F.vit_attention then its backward ('resident': vit_attention_backward; 'stream': the streaming pair at every length) on
+    peaked scores, 8 heads; ``x`` is dout.  ``run`` also returns the forward's "out", which no reference names."""
+    heads = 8
+    qkv = peaked_qkv(B, L, heads, hd, 100 * L + hd)
+    dout = torch.randn(B, L, heads * hd, generator=torch.Generator().manual_seed(L + hd))
+
+    def reference(dout):
+        return {"dqkv": attention_grad64(qkv, dout, heads, hd ** -0.5)[1]}
+
+    def on(dev):
+        F = hipF()
+        qd = qkv.to(dev)
+        fwd, bwd = (F.vit_attention_stream, F.vit_attention_backward_stream) if form == "stream" else (F.vit_attention, F.vit_attention_backward)
+
+        def run(dout):
+            out = fwd(qd, heads)
+            return {"out": out, "dqkv": bwd(qd, out, dout.to(dev), heads)}
+        return run
+    return Setup(dout, reference, on)
+
+
+def step_stats(n, classes, special=False):
+    """dist.step_stats on quarter-rounded logits (ties) with labels that agree with numpy's argmax on about 70 % of the rows;
+    ``x`` is the logits.  ``special`` (n >= 8): an all-equal row, +inf, a row of -inf, a NaN and a tie with the first class.  The
+    probed tensor is the first four columns of the logits seen as (n, 4, 1, 1), in place through its strides, unless
+    ``on(dev, out)`` is given one.  Outputs: "pred"; "count_correct" = stats[[0, 3]]; "probe" = stats[1:3]."""
+    import numpy as np
+    gen = torch.Generator().manual_seed(n + classes)
+    logits = (torch.randn(n, classes, generator=gen) * 4).round() / 4
+    if special and n >= 8:
+        logits[1] = 0.0
+        logits[2, classes - 1] = float("inf")
+        logits[3, :] = float("-inf")
+        logits[4, 1] = float("nan")
+        logits[5, 0] = logits[5].max()
+    want = np.argmax(logits.numpy(), axis=1)
+    labels = torch.from_numpy(want.copy())
+    flip = torch.rand(n, generator=gen) < 0.3
+    labels[flip] = (labels[flip] + 1) % classes
+
+    def reference(logits, probe=None):
+        am = torch.from_numpy(np.argmax(logits.numpy(), axis=1))
+        probe = logits[:, :min(4, classes)].double() if probe is None else probe
+        return {"pred": am.double(), "count_correct": torch.tensor([float(len(logits)), float((am == labels).sum())], dtype=torch.float64),
+                "probe": torch.stack([probe.sum(), probe.square().sum()])}
+
+    def on(dev, out=None):
+        from stgcn_amd import dist as sd
+        lab = labels.to(dev)
+
+        def run(logits):
+            ld = logits.to(dev)
+            o = ld[:, :min(4, classes)].unsqueeze(-1).unsqueeze(-1) if out is None else out
+            pred = torch.full((len(ld),), -1, dtype=torch.int64, device=dev)
+            stats = sd.step_stats(o, len(ld), ld, lab, pred)
+            return {"pred": pred, "count_correct": torch.stack([stats[0], stats[3]]), "probe": stats[1:3]}
+        return run
+    return Setup(logits, reference, on, labels=labels, want=want, gen=gen)
+
+
+def bn_fold(C):
+    """F.bn_fold with a conv bias; ``x`` is the running mean: the shift follows it, the scale cannot."""
+    g = torch.Generator().manual_seed(C)
+    w, b, cb = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2, torch.randn(C, generator=g) * 0.1
+    mean, var = torch.randn(C, generator=g) * 0.3, torch.rand(C, generator=g) * 1.5 + 0.25
+
+    def reference(mean):
+        scale = w.double() / torch.sqrt(var.double() + hipF().BN_EPS)
+        return {"scale": scale, "shift": b.double() + (cb.double() - mean.double()) * scale}
+
+    def on(dev):
+        F = hipF()
+        wd, bd, vd, cd = (t.to(dev) for t in (w, b, var, cb))
+        return lambda mean: dict(zip(("scale", "shift"), F.bn_fold(wd, bd, mean.to(dev), vd, cd)))
+    return Setup(mean, reference, on)

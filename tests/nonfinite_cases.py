@@ -468,14 +468,15 @@ def prepare_st_attention_train(N, cin, cout, T, V):
 
     def on(dev):
         m = ep.st_unit(cin, cout, V, sd, drop_connect=False).train()
+        sdd, dyd = {k: v.to(dev) for k, v in sd.items()}, dy.to(dev)     # staged once: nothing in ``run`` comes from the host
 
         def run(x):
-            m.load_state_dict(sd)                   # the running statistics of the previous plant
+            m.load_state_dict(sdd)                  # the running statistics of the previous plant
             for p in m.parameters():
                 p.grad = None
             xg = x.to(dev).requires_grad_(True)
             y = m(xg)
-            y.backward(dy.to(dev))
+            y.backward(dyd)
             return {"y": y.detach(), "dx": xg.grad, **{"d" + k: p.grad for k, p in m.named_parameters()},
                     **{k: v.clone() for k, v in m.state_dict().items() if k.endswith(("running_mean", "running_var"))}}
         return run
@@ -500,11 +501,12 @@ def prepare_vit_block_train(B, L, D, mode, attention_bf16=False):
         ps = [sd[k].to(dev) for k in tr.PARAMS]
         math = HEAD_TRAIN_MATH[mode] | (_capi.VIT_TRAIN_ATTN_BF16 if attention_bf16 else 0)
         args = (heads, ar.EPS, (D // heads) ** -0.5, math)
+        dyd = dy.to(dev)
 
         def run(x):
             xd = x.to(dev)
             y, saved = F.vit_block_forward_train(xd, ps, *args)
-            g = F.vit_block_backward(xd, ps, saved, dy.to(dev), *args)
+            g = F.vit_block_backward(xd, ps, saved, dyd, *args)
             return {"y": y, "dx": g["x"], **{"d" + k: g[n] for k, n in zip(tr.PARAMS, F.VIT_BLOCK_PARAMS)}}
         return run
     return Prepared(x, token_positions(x.shape), reference, on, MATH_GATES["bf16" if mode == "bf16" or attention_bf16 else "f32"])

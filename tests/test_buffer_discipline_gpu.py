@@ -191,34 +191,19 @@ for _o, _l in itertools.product(("ST", "TS"), ("nctv", "ntvc")):
 def make_step_stats(n, classes, dev):
     """test_step_stats_argmax_is_numpy_argmax: ties, NaN rows and +-inf - the row maximum is where a stale NaN would be dropped
     and a stale huge value would win."""
-    from stgcn_amd import dist as sd
-    gen = torch.Generator().manual_seed(n + classes)
-    logits = (torch.randn(n, classes, generator=gen) * 4).round() / 4
-    if n >= 8:
-        logits[1] = 0.0
-        logits[2, classes - 1] = float("inf")
-        logits[3, :] = float("-inf")
-        logits[4, 1] = float("nan")
-        logits[5, 0] = logits[5].max()
-    want = np.argmax(logits.numpy(), axis=1)
-    labels = torch.from_numpy(want.copy())
-    flip = torch.rand(n, generator=gen) < 0.3
-    labels[flip] = (labels[flip] + 1) % classes
-    out = torch.randn(n, 4, 2, 3, generator=gen).to(dev)
+    s = ep.step_stats(n, classes, special=True)
+    want, labels = s.want, s.labels
+    out = torch.randn(n, 4, 2, 3, generator=s.gen).to(dev)
     probe = out[:, :, 0, 0].double().cpu()
-    ld, lab = logits.to(dev), labels.to(dev)
-
-    def run():
-        pred = torch.full((n,), -1, dtype=torch.int64, device=dev)
-        return {"stats": sd.step_stats(out, n, ld, lab, pred), "pred": pred}
+    staged, ld = s.on(dev, out), s.x.to(dev)
 
     def gate(o, what):
-        stats = o["stats"].cpu()
+        count, correct = o["count_correct"].cpu()
         assert np.array_equal(o["pred"].cpu().numpy(), want), what
-        assert float(stats[3]) == float((torch.from_numpy(want) == labels).sum()) and float(stats[0]) == n, what
-        assert torch.allclose(stats[1:3].double(), torch.tensor([probe.sum().item(), probe.square().sum().item()], dtype=torch.float64),
+        assert float(correct) == float((torch.from_numpy(want) == labels).sum()) and float(count) == n, what
+        assert torch.allclose(o["probe"].cpu().double(), torch.tensor([probe.sum().item(), probe.square().sum().item()], dtype=torch.float64),
                               rtol=1e-5, atol=1e-3), what
-    return run, gate
+    return (lambda: staged(ld)), gate
 
 
 for _n, _c in ((300, 28), (1, 2)):
@@ -438,20 +423,13 @@ for _s, _ma in itertools.product([(1, 256, 256), (129, 512, 512), (300, 256, 200
 
 
 def make_vit_attention_backward(L, hd, dev):
-    F = _F()
-    B, heads = 9, 8
-    qkv = ep.peaked_qkv(B, L, heads, hd, 100 * L + hd)
-    dout = torch.randn(B, L, heads * hd, generator=torch.Generator().manual_seed(L + hd))
-    _, want = ep.attention_grad64(qkv, dout, heads, hd ** -0.5)
-    qd, dd = qkv.to(dev), dout.to(dev)
-
-    def run():
-        out = F.vit_attention(qd, heads)
-        return {"out": out, "dqkv": F.vit_attention_backward(qd, out, dd, heads)}
+    s = ep.vit_attention_backward(9, L, hd)
+    want = s.reference(s.x)["dqkv"]
+    run, dd = s.on(dev), s.x.to(dev)
 
     def gate(o, what):
         parity_gate(o["dqkv"], want, REL, what)
-    return run, gate
+    return (lambda: run(dd)), gate
 
 
 for _L, _hd in itertools.product((1, 65, 256), (32, 64)):
@@ -461,28 +439,15 @@ for _L, _hd in itertools.product((1, 65, 256), (32, 64)):
 def make_vit_layernorm_backward(M, D, dev):
     """test_layernorm_backward_vs_fp64 at widths that are no multiple of the 256 floats a wave covers per pass (4, 260), one that
     is (256) and one of many passes (4096); autograd of ar.layer_norm64 is the reference."""
-    F = _F()
-    g = torch.Generator().manual_seed(D)
-    x = torch.randn(M, D, generator=g) * (0.25 + 3.75 * torch.rand(M, 1, generator=g)) + torch.randn(M, 1, generator=g)
-    w, b = 1 + 0.2 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g)
-    dn, dres = torch.randn(M, D, generator=g), torch.randn(M, D, generator=g)
-    x64, w64, b64 = (t.double().requires_grad_(True) for t in (x, w, b))
-    ar.layer_norm64(x64, w64, b64).backward(dn.double())
-    xd, dnd, wd, dresd = (t.to(dev) for t in (x, dn, w, dres))
-
-    def run():
-        out = {}
-        for res in (False, True):
-            out[f"dx[dres={res}]"], out[f"dweight[dres={res}]"], out[f"dbias[dres={res}]"] = \
-                F.vit_layernorm_backward(xd, dnd, wd, ar.EPS, dres=dresd if res else None)
-        return out
+    s = ep.vit_layernorm_backward(M, D)
+    want = s.reference(s.x)
+    run, dnd = s.on(dev), s.x.to(dev)
 
     def gate(o, what):
         for res in (False, True):
-            parity_gate(o[f"dx[dres={res}]"], x64.grad + (dres.double() if res else 0), REL, f"{what} dx dres={res}")
-            parity_gate(o[f"dweight[dres={res}]"], w64.grad, REL, f"{what} dweight dres={res}")
-            parity_gate(o[f"dbias[dres={res}]"], b64.grad, REL, f"{what} dbias dres={res}")
-    return run, gate
+            for k in ("dx", "dweight", "dbias"):
+                parity_gate(o[f"{k}[dres={res}]"], want[f"{k}[dres={res}]"], REL, f"{what} {k} dres={res}")
+    return (lambda: run(dnd)), gate
 
 
 for _m, _d in [(5, 4), (7, 260), (3001, 256), (2, 4096)]:
