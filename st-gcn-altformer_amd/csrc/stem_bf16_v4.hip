@@ -31,6 +31,8 @@
 //
 // Everything else (LDS image layout, k-step = 16 channels of one tap, 2x2 MFMA blocks per wave, hi/lo split of the
 // produced activations) is as described in tcn_bf16.hip.
+//
+// The weight ring, the operand fetch, the tile rows and the transposing epilogue are stated once, in front of KF4 and K3v4.
 #include "bf16_common.h"
 
 namespace stgcn {
@@ -65,6 +67,171 @@ __device__ __forceinline__ void dma16(const void *g, unsigned lds_addr) {  // ld
                  : "memory");
 }
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// -----------------------------------------------------------------------------------------------------
+// What both kernels of this file are built from (KF4 below, K3v4 behind it).  A kernel's differences enter as compile-time
+// values or as arguments, never as a question about the caller.  The kernels bind the ring and the fetches to their own
+// state in short lambdas, and the pieces in front of the epilogue take scalars, not the kernels' arrays: in this shape they
+// compile to the instruction streams of the written-out copies they replace (profiles/v4_pair_resources.txt, which also
+// lists what the other shapes cost).  In the ablation build K3v4 has the STGCN_ABL(8 / 16 / 64) exits too.
+// -----------------------------------------------------------------------------------------------------
+// The weight ring: 2 stages x 3 taps x 8 fragments of LDS, filled by LDS-DMA, one fragment per wave and tap:
+// f = wave -> m-block (f>>1), image (f&1).  ring_src: this lane's 16 bytes of the wave's fragment of flat k index 0.
+__device__ __forceinline__ const uint4 *ring_src(const uint4 *Wp, int cg, int nch, int wave, int lane) {
+    return Wp + ((size_t)(cg * 4 + (wave >> 1)) * nch * KT4 * 2 + (wave & 1)) * 64 + lane;
+}
+// stage gs (taps 3gs..3gs+2 of the flat k index) -> ring slot gs&1; ring_lds: LDS byte address of the ring (M0 of the DMA)
+__device__ __forceinline__ void ring_stage(const uint4 *wsrc, unsigned ring_lds, int wave, int nstage, int gs, int abl) {
+    const unsigned dst = ring_lds + (gs & 1) * STAGE_BYTES + wave * FRAG;
+    const int gsm = gs % nstage;             // weights repeat for every tile
+    if (STGCN_ABL(64)) return;
+#pragma unroll
+    for (int t = 0; t < STG; ++t) dma16(wsrc + (size_t)(gsm * STG + t) * 128, dst + t * 8 * FRAG);
+}
+// what this lane reads of stage gs: the fragments of m-blocks 2wm, 2wm+1
+__device__ __forceinline__ const char *ring_aslot(const char *ring, int gs, int wm, int lane) {
+    return ring + (gs & 1) * STAGE_BYTES + (wm * 4) * FRAG + lane * 16;
+}
+
+// Operand fetch (LDS -> registers): the weight fragments of tap tt of a stage, the activation fragments of a tap from a
+// chunk image (prow: tile row of the wave's NJ column blocks at tap 0; h = lane >> 5).
+template <int TERMS>
+__device__ __forceinline__ void fetch_a(Frag2<TERMS> &a, const char *aslot, int tt, int abl) {
+    if (STGCN_ABL(16)) return;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        a.hi[m] = *reinterpret_cast<const uint4 *>(aslot + (tt * 8 + m * 2) * FRAG);
+        if constexpr (TERMS == 3) a.lo[m] = *reinterpret_cast<const uint4 *>(aslot + (tt * 8 + m * 2 + 1) * FRAG);
+    }
+}
+template <int TERMS, int NJ>
+__device__ __forceinline__ void fetch_b(FragB<TERMS, NJ> &b, int j, const char *img, int img_bytes, int row, int h, int abl) {
+    if (STGCN_ABL(8)) return;
+    const int off = lds_off(row, h);
+    b.hi[j] = *reinterpret_cast<const uint4 *>(img + off);
+    if constexpr (TERMS == 3) b.lo[j] = *reinterpret_cast<const uint4 *>(img + img_bytes + off);
+}
+
+// Tile state of a wave (64 channels x 32*NJ pixels): the rows of its column blocks, and zeroed accumulators.
+__device__ __forceinline__ int tile_row(const TileGeomB &g, int V, int blk, int lane) {
+    int q = g.q0 + blk + (lane & 31);
+    q = min(q, g.q_last);
+    const int t = q / V, v = q - t * V;
+    return (t - g.t_first) * V + v;
+}
+__device__ __forceinline__ f32x16 zero16() {
+    f32x16 a;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[r] = 0.f;
+    return a;
+}
+
+// Opaque copies of a tile's scalars for its epilogue: everything the epilogue derives from them (store addresses: 64-bit
+// multiplies per lane) is then computed there.  Left visible, hipcc hoists that arithmetic above the channel loop and
+// spills it across the loop; a scratch reload in front of the next tile's feature phase then waits (vmcnt(0)) for every
+// store of this epilogue.
+struct TileIds {
+    int n, q0, q_last;
+    int lane;  // (the lane too: lane-only terms are kernel invariants)
+};
+__device__ __forceinline__ TileIds opaque_ids(int n, const TileGeomB &g, int lane) {
+    TileIds e = {n, g.q0, g.q_last, lane};
+    asm volatile("" : "+s"(e.n), "+s"(e.q0), "+s"(e.q_last), "+v"(e.lane));
+    return e;
+}
+
+// four results at element gidx of y in one store (fp32: 16 bytes, bf16: 8)
+template <bool BF16OUT>
+__device__ __forceinline__ void store_out4(void *y, size_t gidx, const float4 &v) {
+    if constexpr (BF16OUT) {
+        *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + gidx) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+    } else {
+        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(y) + gidx) = v;
+    }
+}
+
+// Epilogue of a wave: max(acc + shift, act_lo) of its 64 channels x 32*NJ pixels.  D[row = channel][col = pixel], col =
+// lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).  Per-lane dword stores are store-issue-bound (measured ~7 B/clk/CU):
+// each 32-channel block is transposed through this wave's slice of the (now idle) image buffers at buf0 (32 channels x
+// 32*NJ pixels fp32) and stored 16 B per lane, so one wave-instruction writes four 256-B channel rows — or, ntvc, 8 pixels
+// x 128 B.  What the two kernels set differently, and nothing else: act_lo (the stem: 0); PADDED, the wave-uniform skip of
+// the padded 32-channel blocks of a 64-channel layer (the conv); AMASK, the bits of the element index that must be clear
+// for a whole store in (N,C,T,V) (the stem: dword alignment of the bf16 store only; the conv: 16 / 8 bytes).
+// The two tile sizes index differently, on what hipcc makes of each (profiles/v4_pair_resources.txt, v4_pair_vs_parent.txt):
+// the 256-pixel tile, whose registers are tight, takes the staged row from the lane alone and has its first channel opaque
+// like the tile ids (else one more scalar spills); the 128-pixel tile divides the group index and leaves the channel
+// visible, which is the form its bf16x3 kernel is not 0.5 % slower in.  id comes by value and the staging slice is formed
+// per layout for the same reason.
+template <bool BF16OUT, int NJ, bool PADDED, int AMASK>
+__device__ __forceinline__ void store_tile(const f32x16 (&acc)[2][NJ], char *buf0, int wave, TileIds id, const float *shift,
+                                           void *y, int C, int TV, int cg, int wm, int wn, float act_lo, bool ntvc) {
+    constexpr int PW = 32 * NJ;                              // pixel columns of this wave
+    int ob0 = cg * 128 + wm * 64;                            // first channel of the wave (NJ = 2)
+    if constexpr (NJ == 2) asm volatile("" : "+s"(ob0));
+    if (ntvc) {
+        // (N,T,V,C) output: the block is staged pixel-major ([32*NJ pixels][32 channels], 16-byte slots XOR-swizzled by
+        // the pixel so the b128 accesses are conflict-free)
+        float *stg = reinterpret_cast<float *>(buf0 + wave * (EPI_BYTES * NJ / 2));
+        const int qw = id.q0 + wn * PW;
+        const int hh = id.lane >> 5;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const int ob = NJ == 2 ? ob0 + m * 32 : cg * 128 + (wm * 2 + m) * 32;     // first output channel of the block
+            if (PADDED && ob >= C) continue;
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 8 * gq + 4 * hh);
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    const int px = j * 32 + (id.lane & 31);
+                    const float4 v = make_float4(max_nan(acc[m][j][4 * gq + 0] + sh4.x, act_lo), max_nan(acc[m][j][4 * gq + 1] + sh4.y, act_lo),
+                                                 max_nan(acc[m][j][4 * gq + 2] + sh4.z, act_lo), max_nan(acc[m][j][4 * gq + 3] + sh4.w, act_lo));
+                    *reinterpret_cast<float4 *>(stg + px * 32 + (((2 * gq + hh) ^ (px & 7)) << 2)) = v;
+                }
+            }
+#pragma unroll
+            for (int it = 0; it < 4 * NJ; ++it) {
+                const int idx = it * 64 + id.lane, px = idx >> 3, sl = idx & 7;
+                const float4 v = *reinterpret_cast<const float4 *>(stg + px * 32 + ((sl ^ (px & 7)) << 2));
+                const int q = qw + px;
+                const size_t gidx = ((size_t)id.n * TV + q) * C + ob + 4 * sl;
+                if (q <= id.q_last) store_out4<BF16OUT>(y, gidx, v);
+            }
+        }
+    } else {
+        float *stg = reinterpret_cast<float *>(buf0 + wave * (EPI_BYTES * NJ / 2));
+        const int qw = id.q0 + wn * PW;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const int ob = NJ == 2 ? ob0 + m * 32 : cg * 128 + (wm * 2 + m) * 32;
+            if (PADDED && ob >= C) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int cr = (r & 3) + 8 * (r >> 2) + 4 * (id.lane >> 5);
+                const float sh = shift[ob + cr];
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) stg[cr * PW + j * 32 + (id.lane & 31)] = max_nan(acc[m][j][r] + sh, act_lo);
+            }
+#pragma unroll
+            for (int it = 0; it < 4 * NJ; ++it) {
+                // 16-byte group idx, PW / 4 = 8 NJ of them a row
+                const int idx = it * 64 + id.lane;
+                const int row = NJ == 2 ? it * 4 + (id.lane >> 4) : idx / 8, c4 = NJ == 2 ? (id.lane & 15) * 4 : (idx % 8) * 4;
+                const float4 v = *reinterpret_cast<const float4 *>(stg + row * PW + c4);
+                const int q = qw + c4;
+                const size_t gidx = ((size_t)id.n * C + ob + row) * TV + q;
+                if (q + 3 <= id.q_last && (gidx & AMASK) == 0) {
+                    store_out4<BF16OUT>(y, gidx, v);
+                } else {                                     // ragged end of the clip, or off alignment
+                    const float e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (q + e <= id.q_last) store_out<BF16OUT>(y, gidx + e, e4[e]);
+                }
+            }
+        }
+    }
+}
 
 // NJ = 32-pixel blocks per wave: 2 -> 256-pixel tile (the form described above); 1 -> 128-pixel tile for wide frames
 // (V = 46: the 256-pixel tile's rows do not fit LDS).  With NJ = 1 the folded graph-conv matrix is not copied to LDS
@@ -113,15 +280,8 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
     const unsigned pf_lds = lds0 + (unsigned)(reinterpret_cast<const char *>(Pf) - smem4);
 
     const int cg = blockIdx.y;               // 128-channel group of the output
-    // weight fragment this wave DMAs each tap: f = wave -> m-block (f>>1), image (f&1)
-    const uint4 *wsrc = Wp + ((size_t)(cg * 4 + (wave >> 1)) * nch * KT4 * 2 + (wave & 1)) * 64 + lane;
-    auto dma_stage = [&](int gs) {           // stage gs (taps 3gs..3gs+2 of the flat k index) -> ring slot gs&1
-        const unsigned dst = ring_lds + (gs & 1) * STAGE_BYTES + wave * FRAG;
-        const int gsm = gs % nstage;         // weights repeat for every tile
-        if (STGCN_ABL(64)) return;
-#pragma unroll
-        for (int t = 0; t < STG; ++t) dma16(wsrc + (size_t)(gsm * STG + t) * 128, dst + t * 8 * FRAG);
-    };
+    const uint4 *wsrc = ring_src(Wp, cg, nch, wave, lane);
+    auto dma_stage = [&](int gs) { ring_stage(wsrc, ring_lds, wave, nstage, gs, abl); };
     // feature rows of tile `tile` -> Fs (rows whose pixel lies outside the clip are fixed up afterwards)
     auto dma_features = [&](int tile) {
         const int n = tile / tiles_per_clip;
@@ -336,40 +496,20 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
 
         int prow[NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            int q = g.q0 + (wn * NJ + j) * 32 + (lane & 31);
-            q = min(q, g.q_last);
-            const int t = q / V, v = q - t * V;
-            prow[j] = (t - g.t_first) * V + v;
-        }
+        for (int j = 0; j < NJ; ++j) prow[j] = tile_row(g, V, (wn * NJ + j) * 32, lane);
         f32x16 acc[2][NJ];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
+            for (int j = 0; j < NJ; ++j) acc[m][j] = zero16();
         __syncthreads();                      // chunk 0 visible
         STGCN_STAMP(t_tile1)
         STGCN_ACC(0, t_tile0, t_tile1)
 
-        // operand fetch helpers (LDS -> registers)
-        auto load_a = [&](Frag2<TERMS> &a, const char *aslot, int tt) {
-            if (STGCN_ABL(16)) return;
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                a.hi[m] = *reinterpret_cast<const uint4 *>(aslot + (tt * 8 + m * 2) * FRAG);
-                if constexpr (TERMS == 3) a.lo[m] = *reinterpret_cast<const uint4 *>(aslot + (tt * 8 + m * 2 + 1) * FRAG);
-            }
-        };
+        auto load_a = [&](Frag2<TERMS> &a, const char *aslot, int tt) { fetch_a(a, aslot, tt, abl); };
         auto load_b = [&](FragB<TERMS, NJ> &b, const char *img, int tap) {
-            if (STGCN_ABL(8)) return;
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int off = lds_off(prow[j] + tap * V, h);
-                b.hi[j] = *reinterpret_cast<const uint4 *>(img + off);
-                if constexpr (TERMS == 3) b.lo[j] = *reinterpret_cast<const uint4 *>(img + img_bytes + off);
-            }
+            for (int j = 0; j < NJ; ++j) fetch_b(b, j, img, img_bytes, prow[j] + tap * V, h, abl);
         };
 
         // Software pipeline: the fragments of tap t+1 are fetched before the MFMAs of tap t are issued.  The activation
@@ -394,7 +534,7 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
 #pragma unroll
             for (int st = 0; st < KT4 / STG; ++st, ++gs) {
                 STGCN_STAMP(t_s0)
-                const char *aslot = ring + (gs & 1) * STAGE_BYTES + (wm * 4) * FRAG + lane * 16;
+                const char *aslot = ring_aslot(ring, gs, wm, lane);
                 load_a(a_cur, aslot, 0);
 #pragma unroll
                 for (int tt = 0; tt < STG; ++tt) {
@@ -432,95 +572,16 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
             }
         }
 
-        // epilogue: D[row = channel][col = pixel], col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
-        // Per-lane dword stores are store-issue-bound (measured ~7 B/clk/CU): transpose each 32-channel x 64-pixel
-        // block through this wave's 8 KiB slice of the (now idle) image buffers and store 16 B per lane, so one
-        // wave-instruction writes four 256-B channel rows.
         STGCN_STAMP(t_e0)
-        // Opaque copies of the tile's scalars: everything the epilogue derives from them (store addresses: 64-bit
-        // multiplies per lane) is then computed here.  Left visible, hipcc hoists that arithmetic above the channel loop
-        // and spills it across the loop; a scratch reload in front of the next tile's feature phase then waits
-        // (vmcnt(0)) for every store of this epilogue.
-        int n_e = n, q0_e = g.q0, qlast_e = g.q_last, lane_e = lane;   // (lane too: lane-only terms are kernel invariants)
-        asm volatile("" : "+s"(n_e), "+s"(q0_e), "+s"(qlast_e), "+v"(lane_e));
+        const TileIds id = opaque_ids(n, g, lane);
         XRegs xnext, xnext2;                  // (declared per tile and always fully written: dead across the loop back-edge)
         if constexpr (FK) {                   // next tile's x: in flight while this tile's results are stored
             load_x(xnext, min(next_tile, ntiles - 1), wave);
             load_x(xnext2, min(next_tile, ntiles - 1), wave + 8);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (!STGCN_ABL(4) && (abl & OPT_OUT_NTVC)) {
-            // (N,T,V,C) output: the block is staged pixel-major ([32*NJ pixels][32 channels], 16-byte slots XOR-swizzled by
-            // the pixel so the b128 accesses are conflict-free); a wave-instruction then writes 8 pixels x 128 B.
-            float *stg = reinterpret_cast<float *>(buf0 + wave * (EPI_BYTES * NJ / 2));   // 32 ch x 32*NJ px per wave
-            const int qw = q0_e + wn * 32 * NJ;
-            const int hh = lane_e >> 5;
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int ob = cg * 128 + (wm * 2 + m) * 32;
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 8 * gq + 4 * hh);
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        const int px = j * 32 + (lane_e & 31);
-                        const float4 v = make_float4(max_nan(acc[m][j][4 * gq + 0] + sh4.x, 0.f), max_nan(acc[m][j][4 * gq + 1] + sh4.y, 0.f),
-                                                     max_nan(acc[m][j][4 * gq + 2] + sh4.z, 0.f), max_nan(acc[m][j][4 * gq + 3] + sh4.w, 0.f));
-                        *reinterpret_cast<float4 *>(stg + px * 32 + (((2 * gq + hh) ^ (px & 7)) << 2)) = v;
-                    }
-                }
-#pragma unroll
-                for (int it = 0; it < 4 * NJ; ++it) {
-                    const int idx = it * 64 + lane_e, px = idx >> 3, sl = idx & 7;
-                    const float4 v = *reinterpret_cast<const float4 *>(stg + px * 32 + ((sl ^ (px & 7)) << 2));
-                    const int q = qw + px;
-                    const size_t gidx = ((size_t)n_e * TV + q) * C + ob + 4 * sl;
-                    if (q <= qlast_e) {
-                        if constexpr (BF16OUT) {
-                            *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + gidx) =
-                                make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-                        } else {
-                            *reinterpret_cast<float4 *>(reinterpret_cast<float *>(y) + gidx) = v;
-                        }
-                    }
-                }
-            }
-        } else if (!STGCN_ABL(4)) {
-            float *stg = reinterpret_cast<float *>(buf0 + wave * (EPI_BYTES * NJ / 2));   // 32 ch x 32*NJ px per wave
-            constexpr int PW = 32 * NJ;                          // pixel columns of this wave
-            const int qw = q0_e + wn * PW;                       // first of them
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int ob = cg * 128 + (wm * 2 + m) * 32;     // first output channel of the block
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int cr = (r & 3) + 8 * (r >> 2) + 4 * (lane_e >> 5);
-                    const float sh = shift[ob + cr];
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) stg[cr * PW + j * 32 + (lane_e & 31)] = max_nan(acc[m][j][r] + sh, 0.f);
-                }
-#pragma unroll
-                for (int it = 0; it < 4 * NJ; ++it) {
-                    const int idx = it * 64 + lane_e, row = idx / (PW / 4), c4 = (idx % (PW / 4)) * 4;
-                    const float4 v = *reinterpret_cast<const float4 *>(stg + row * PW + c4);
-                    const int q = qw + c4;
-                    const size_t gidx = ((size_t)n_e * C + ob + row) * TV + q;
-                    if (q + 3 <= qlast_e && (!BF16OUT || (gidx & 1) == 0)) {  // (bf16: keep the 8-B store dword-aligned)
-                        if constexpr (BF16OUT) {
-                            *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + gidx) =
-                                make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-                        } else {
-                            *reinterpret_cast<float4 *>(reinterpret_cast<float *>(y) + gidx) = v;
-                        }
-                    } else {                                     // ragged end of the clip
-                        const float e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (q + e <= qlast_e) store_out<BF16OUT>(y, gidx + e, e4[e]);
-                    }
-                }
-            }
-        }
+        if (!STGCN_ABL(4))
+            store_tile<BF16OUT, NJ, false, BF16OUT ? 1 : 0>(acc, buf0, wave, id, shift, y, C, TV, cg, wm, wn, 0.f, (abl & OPT_OUT_NTVC) != 0);
         STGCN_STAMP(t_e1)
         STGCN_ACC(3, t_e0, t_e1)
         if (next_tile < ntiles) {
@@ -546,9 +607,10 @@ __global__ __launch_bounds__(NT4) void stem_bf16_v4_kernel(
 }
 
 // =====================================================================================================
-// K3v4 — the stand-alone temporal conv block (Unit2D: K = 9, stride 1) in the same large-tile persistent form:
-// same tile, weight ring, fenced tap body and epilogue as KF4; the matrix-core producer is replaced by staging of the
-// real fp32 input.  A thread owns two (pixel, 8-channel) units of the chunk image: 8 coalesced dword loads each
+// K3v4 — the stand-alone temporal conv block (Unit2D: K = 9, stride 1) in the same large-tile persistent form, from the
+// same pieces as KF4 (weight ring, operand fetch, tile rows, epilogue); its fenced tap body is a second copy of KF4's with
+// the matrix-core producer replaced by staging of the real fp32 input (DESIGN.md says why that one is still written twice).
+// A thread owns two (pixel, 8-channel) units of the chunk image: 8 coalesced dword loads each
 // (lanes run along the pixels of one channel), issued at tap 0 for the NEXT chunk, split into bf16 hi/lo and stored
 // as one 16-byte LDS store per image at taps 6 and 7.  Chunk 0 of the next tile is loaded during the last chunk and
 // kept in registers across the epilogue (the image buffers are the epilogue's staging area).
@@ -573,17 +635,10 @@ __global__ __launch_bounds__(NT4) void tcn_bf16_v4_kernel(
     char *buf1 = buf0 + buf_bytes;
     const unsigned ring_lds = (unsigned)(size_t)(lptr_t)smem4;
     const int cg = blockIdx.y;
-    const uint4 *wsrc = Wp + ((size_t)(cg * 4 + (wave >> 1)) * nch * KT4 * 2 + (wave & 1)) * 64 + lane;
-    auto dma_stage = [&](int gs) {
-        const unsigned dst = ring_lds + (gs & 1) * STAGE_BYTES + wave * FRAG;
-        const int gsm = gs % nstage;
-#pragma unroll
-        for (int t = 0; t < STG; ++t) dma16(wsrc + (size_t)(gsm * STG + t) * 128, dst + t * 8 * FRAG);
-    };
+    const uint4 *wsrc = ring_src(Wp, cg, nch, wave, lane);
+    auto dma_stage = [&](int gs) { ring_stage(wsrc, ring_lds, wave, nstage, gs, abl); };
 
     // ---- input staging: units u = tid, tid + 512 of the chunk image; unit = (pixel row u % ROWS, channel half u / ROWS)
-    // (buffer-resource loads: one offset register per unit, the 8 channel strides ride in the scalar offset, and a
-    //  pixel outside the clip gets an offset past num_records, which reads as zero)
     // (buffer-resource loads: one offset register per unit, the 8 channel strides ride in the scalar offset, and a
     //  pixel outside the clip gets an offset past num_records, which reads as zero)
     float pv[2][8];
@@ -635,34 +690,17 @@ __global__ __launch_bounds__(NT4) void tcn_bf16_v4_kernel(
         store_unit(buf0, 1);
         int prow[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            int q = g.q0 + (wn * 2 + j) * 32 + (lane & 31);
-            q = min(q, g.q_last);
-            const int t = q / V, v = q - t * V;
-            prow[j] = (t - g.t_first) * V + v;
-        }
+        for (int j = 0; j < 2; ++j) prow[j] = tile_row(g, V, (wn * 2 + j) * 32, lane);
         f32x16 acc[2][2];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
+            for (int j = 0; j < 2; ++j) acc[m][j] = zero16();
         __syncthreads();                          // chunk 0 and the current weight stage visible
-        auto load_a = [&](Frag2<TERMS> &a, const char *aslot, int tt) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                a.hi[m] = *reinterpret_cast<const uint4 *>(aslot + (tt * 8 + m * 2) * FRAG);
-                if constexpr (TERMS == 3) a.lo[m] = *reinterpret_cast<const uint4 *>(aslot + (tt * 8 + m * 2 + 1) * FRAG);
-            }
-        };
+        auto load_a = [&](Frag2<TERMS> &a, const char *aslot, int tt) { fetch_a(a, aslot, tt, abl); };
         auto load_b = [&](Frag2<TERMS> &b, const char *img, int tap) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int off = lds_off(prow[j] + tap * V, h);
-                b.hi[j] = *reinterpret_cast<const uint4 *>(img + off);
-                if constexpr (TERMS == 3) b.lo[j] = *reinterpret_cast<const uint4 *>(img + img_bytes + off);
-            }
+            for (int j = 0; j < 2; ++j) fetch_b(b, j, img, img_bytes, prow[j] + tap * V, h, abl);
         };
         Frag2<TERMS> a_cur = {}, b_cur = {}, a_nxt = {}, b_nxt = {};
         for (int ch = 0; ch < nch; ++ch) {
@@ -672,7 +710,7 @@ __global__ __launch_bounds__(NT4) void tcn_bf16_v4_kernel(
             load_b(b_cur, cur, 0);
 #pragma unroll
             for (int st = 0; st < KT4 / STG; ++st, ++gs) {
-                const char *aslot = ring + (gs & 1) * STAGE_BYTES + (wm * 4) * FRAG + lane * 16;
+                const char *aslot = ring_aslot(ring, gs, wm, lane);
                 load_a(a_cur, aslot, 0);
 #pragma unroll
                 for (int tt = 0; tt < STG; ++tt) {
@@ -699,78 +737,7 @@ __global__ __launch_bounds__(NT4) void tcn_bf16_v4_kernel(
                 __syncthreads();                  // stage done: next weights landed and visible; chunk boundary at st == 2
             }
         }
-        // epilogue (see KF4): each 32-channel x 64-pixel block through this wave's 8 KiB staging slice, 16 B per lane
-        {
-            int n_e = n, q0_e = g.q0, qlast_e = g.q_last, lane_e = lane;   // opaque copies: see KF4's epilogue
-            asm volatile("" : "+s"(n_e), "+s"(q0_e), "+s"(qlast_e), "+v"(lane_e));
-            float *stg = reinterpret_cast<float *>(buf0 + wave * EPI_BYTES);
-            const int qw = q0_e + wn * 64;
-            if (abl & OPT_OUT_NTVC) {
-                const int hh = lane_e >> 5;
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const int ob = cg * 128 + (wm * 2 + m) * 32;
-                    if (ob >= C) continue;                // padded rows of a 64-channel layer (wave-uniform)
-#pragma unroll
-                    for (int gq = 0; gq < 4; ++gq) {
-                        const float4 sh4 = *reinterpret_cast<const float4 *>(shift + ob + 8 * gq + 4 * hh);
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const int px = j * 32 + (lane_e & 31);
-                            const float4 v = make_float4(max_nan(acc[m][j][4 * gq + 0] + sh4.x, act_lo), max_nan(acc[m][j][4 * gq + 1] + sh4.y, act_lo),
-                                                         max_nan(acc[m][j][4 * gq + 2] + sh4.z, act_lo), max_nan(acc[m][j][4 * gq + 3] + sh4.w, act_lo));
-                            *reinterpret_cast<float4 *>(stg + px * 32 + (((2 * gq + hh) ^ (px & 7)) << 2)) = v;
-                        }
-                    }
-#pragma unroll
-                    for (int it = 0; it < 8; ++it) {
-                        const int idx = it * 64 + lane_e, px = idx >> 3, sl = idx & 7;
-                        const float4 v = *reinterpret_cast<const float4 *>(stg + px * 32 + ((sl ^ (px & 7)) << 2));
-                        const int q = qw + px;
-                        const size_t gidx = ((size_t)n_e * TV + q) * C + ob + 4 * sl;
-                        if (q <= qlast_e) {
-                            if constexpr (BF16OUT)
-                                *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + gidx) =
-                                    make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-                            else
-                                *reinterpret_cast<float4 *>(reinterpret_cast<float *>(y) + gidx) = v;
-                        }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const int ob = cg * 128 + (wm * 2 + m) * 32;
-                    if (ob >= C) continue;                // padded rows of a 64-channel layer (wave-uniform)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int cr = (r & 3) + 8 * (r >> 2) + 4 * (lane_e >> 5);
-                        const float sh = shift[ob + cr];
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) stg[cr * 64 + j * 32 + (lane_e & 31)] = max_nan(acc[m][j][r] + sh, act_lo);
-                    }
-#pragma unroll
-                    for (int it = 0; it < 8; ++it) {
-                        const int idx = it * 64 + lane_e, row = idx >> 4, c4 = (idx & 15) * 4;
-                        const float4 v = *reinterpret_cast<const float4 *>(stg + row * 64 + c4);
-                        const int q = qw + c4;
-                        const size_t gidx = ((size_t)n_e * C + ob + row) * TV + q;
-                        if (q + 3 <= qlast_e && (gidx & 3) == 0) {       // 16-byte (8-byte for bf16) aligned store
-                            if constexpr (BF16OUT)
-                                *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(y) + gidx) =
-                                    make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-                            else
-                                *reinterpret_cast<float4 *>(reinterpret_cast<float *>(y) + gidx) = v;
-                        } else {
-                            const float e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (q + e <= qlast_e) store_out<BF16OUT>(y, gidx + e, e4[e]);
-                        }
-                    }
-                }
-            }
-        }
+        store_tile<BF16OUT, 2, true, 3>(acc, buf0, wave, opaque_ids(n, g, lane), shift, y, C, TV, cg, wm, wn, act_lo, (abl & OPT_OUT_NTVC) != 0);
         __syncthreads();                          // staging consumed before the next tile's chunk 0 is stored
     }
 }
